@@ -5,7 +5,20 @@ One "step" = one pass of the hot path over one per-GPU batch of synthetic input:
   fused FPN RoIAlign forward + backward, P2-P5, 256 ch, 800x1333, N=2 images, 512 RoIs/img, 7x7 bins
   x 4 samples (BASELINE.json configs[1]).  Inputs are resident in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: set up, pre-heat, W warm-up steps,
+the K timed steps, the outputs of the last timed step (--dump-outputs), one JSON line with `value` and
+`ms_per_step`.  Everything described below beside `value` -- the roofline, the instrumentation legs,
+the un-fused 4-op graph, the CPU baseline and the oracle check, the secondary operators, the N > 1
+single-rank and all-reduce legs -- runs with --full only.
+
+--dump-outputs DIR writes what the caller of the path receives from the last timed step as
+DIR/<name>.npy (float32): `out` (the forward output) and `d_feat_p2` .. `d_feat_p5` (the feature
+gradients), with --float-argmax also `argmax_x` / `argmax_y`.  An array of more than DUMP_MAX_ELEMS
+elements is written as a fixed sample (flattened, at sorted positions drawn by numpy's
+default_rng(0)); all inputs, dY included, are seeded, so two builds run with the same arguments can
+be compared file by file.
 
 N > 1 without a torchrun environment re-launches itself as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py
@@ -47,6 +60,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_HBM_GBS = 8000.0
 R50_FPN_GRAD_MB = 165.0  # fp32 gradients of faster_r50v1_fpn (reference: KVStore 'nccl' all-reduce)
+DUMP_MAX_ELEMS = 1 << 21  # per dumped array: 8 MB of float32, at most 7 arrays -> <= 56 MB in all
 
 
 def parse():
@@ -60,6 +74,12 @@ def parse():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--preheat-ms", type=float, default=100.0,
                     help="untimed clock pre-heat before the --warmup steps (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (roofline, "
+                         "instrumentation legs, un-fused graph, CPU baseline + oracle check, bench_ops, "
+                         "N > 1 legs); the --no-* and --calibrate options below act within --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
                     help="skip the CPU oracle (baseline timing AND the verification of the timed step)")
     ap.add_argument("--cpu-passes", type=int, default=3)
@@ -131,6 +151,58 @@ def algorithmic_bytes(n_img, n_roi, channels, shapes, pooled=49):
     s_f = 4 * channels * sum(h * w for h, w in shapes)      # every level read (fwd) / written (bwd)
     s_o = 4 * n_roi * channels * pooled                      # one (R,C,7,7) fp32 tensor per image
     return n_img * s_f + n_img * n_roi * 16 + 3 * n_img * s_o
+
+
+def dy_generator(seed):
+    """dY's own seeded generator: the process-wide CUDA generator starts at a different seed in every
+    process, so a dY drawn from it differs from run to run"""
+    import torch
+    return torch.Generator(device="cuda").manual_seed(seed)
+
+
+def dump_outputs(outdir, named):
+    """[(name, tensor)] -> outdir/<name>.npy as float32; a tensor of more than DUMP_MAX_ELEMS elements is
+    written flattened at DUMP_MAX_ELEMS sorted positions drawn by default_rng(0), the same in every run"""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in named:
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
+
+
+def headline(args, world, value, ms_per_step, rccl_ranks, per_rank_ms):
+    """the result line's fields that a plain run and a --full run share"""
+    return {
+        "metric": "images/sec at 800x1333 FPN 512-RoI RoIAlign fwd+bwd",
+        "value": value,
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "full": bool(args.full),
+        "config": {
+            "workload": "fused FPN RoIAlign_v2 fwd+bwd, P2-P5 %dch 800x1333, N=%d img/GPU, %d RoIs/img, "
+                        "7x7x4 samples (BASELINE configs[1])" % (args.channels, args.images, args.rois),
+            "images_per_gpu": args.images,
+            "rois_per_image": args.rois,
+            "argmax_state": "fp32 x,y planes" if args.float_argmax else "packed u8 (decoded in backward)",
+            "sharding": "images across ranks, no data-path collective",
+            "collectives_in_value": "none (the path has no exchange step; see grad_allreduce for the "
+                                    "reference's gradient all-reduce measured beside it)",
+        },
+        "rccl_ranks": rccl_ranks,
+        "per_rank_ms_per_step": per_rank_ms,
+    }
 
 
 def self_launch(n):
@@ -240,7 +312,7 @@ def main():
     feats = [torch.from_numpy(f).cuda() for f in feats_np]
     rois = torch.from_numpy(rois_np).cuda()
     out_shape = (args.images, args.rois, args.channels, 7, 7)
-    dy = torch.randn(out_shape, device="cuda")
+    dy = torch.randn(out_shape, device="cuda", generator=dy_generator(args.seed + 17 * rank))
     d_feats = [torch.empty_like(f) for f in feats]
     grad_mb = args.grad_allreduce if args.grad_allreduce >= 0 else (R50_FPN_GRAD_MB if multi else 0.0)
     reducer = None
@@ -250,7 +322,7 @@ def main():
         one = torch.ones(1, device="cuda")
         dist.all_reduce(one)
         rccl_ranks = int(one.item())
-        if grad_mb > 0:
+        if grad_mb > 0 and args.full:
             reducer = sdd.OverlappedAllReduce(grad_mb * 1e6, device="cuda")
 
     state = {}
@@ -323,6 +395,25 @@ def main():
     elapsed_local = time.perf_counter() - t0
     elapsed, vals = max_over_ranks(elapsed_local)
     per_rank_ms = [v * 1e3 / args.steps for v in vals]
+    ms_per_step = elapsed * 1e3 / args.steps
+    total_images = args.images * world * args.steps
+    value = total_images / elapsed
+    if args.dump_outputs and rank == 0:
+        named = [("out", state["out"])] + [("d_feat_p%d" % (l + 2), g) for l, g in enumerate(d_feats)]
+        if args.float_argmax:
+            named += [("argmax_x", state["arg"][0]), ("argmax_y", state["arg"][1])]
+        dump_outputs(args.dump_outputs, named)
+    if not args.full:
+        # the timed region above is the same in both modes (its event steps included), so `value` and
+        # `ms_per_step` mean the same with and without --full
+        if rank == 0:
+            print(json.dumps(headline(args, world, value, ms_per_step, rccl_ranks, per_rank_ms)))
+            sys.stdout.flush()
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     scaling = {}
     if multi:
         # afterwards, outside the timed region: rank 0 alone (the N = 1 figure of this box in this
@@ -352,9 +443,6 @@ def main():
                  "ms_per_step_no_events_again": leg(None)}
     fwd_ms = float(np.mean(fwd_samples))
     bwd_ms = float(np.mean(bwd_samples))
-    ms_per_step = elapsed * 1e3 / args.steps
-    total_images = args.images * world * args.steps
-    value = total_images / elapsed
 
     extra = {}
     if not args.no_extra and rank == 0:
@@ -491,14 +579,17 @@ def main():
     if not args.no_cpu_baseline:
         from oracle import pyoracle as orc
         avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        # a thread budget given to this process (OMP_NUM_THREADS) bounds the candidates below
+        omp = os.environ.get("OMP_NUM_THREADS", "")
+        budget = min(avail, int(omp)) if omp.isdigit() and int(omp) > 0 else avail
         dy_np = dy.cpu().numpy()
         fshapes = [f.shape for f in feats_np]
         # warm (page in) once; the multi-thread figure uses the thread count that is FASTEST on this
         # host (more OpenMP threads than memory channels can be slower than one: measured 0.67 img/s
         # on 256 threads against 1.48 on one), found with one forward pass per candidate
-        o = orc.fpn_roi_align_fwd(feats_np, rois_np, strides, (7, 7), nthreads=min(avail, 16))
+        o = orc.fpn_roi_align_fwd(feats_np, rois_np, strides, (7, 7), nthreads=min(budget, 16))
         cores, best = 1, None
-        for cand in sorted({avail, max(1, avail // 4), min(avail, 32), min(avail, 8)}):
+        for cand in sorted({budget, max(1, budget // 4), min(budget, 32), min(budget, 8)}):
             t0 = time.perf_counter()
             orc.fpn_roi_align_fwd(feats_np, rois_np, strides, (7, 7), nthreads=cand)
             dt = time.perf_counter() - t0
@@ -610,34 +701,9 @@ def main():
             cpu_ms = cpu_baseline["ms_per_step"] + extra["ops"]["nms"]["cpu_ms"]
             extra["roialign_plus_nms_speedup_vs_cpu"] = cpu_ms / gpu_ms
 
-    line = {
-        "metric": "images/sec at 800x1333 FPN 512-RoI RoIAlign fwd+bwd",
-        "value": value,
-        "unit": "images/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "fused FPN RoIAlign_v2 fwd+bwd, P2-P5 %dch 800x1333, N=%d img/GPU, %d RoIs/img, "
-                        "7x7x4 samples (BASELINE configs[1])" % (args.channels, args.images, args.rois),
-            "images_per_gpu": args.images,
-            "rois_per_image": args.rois,
-            "argmax_state": "fp32 x,y planes" if args.float_argmax else "packed u8 (decoded in backward)",
-            "sharding": "images across ranks, no data-path collective",
-            "collectives_in_value": "none (the path has no exchange step; see grad_allreduce for the "
-                                    "reference's gradient all-reduce measured beside it)",
-        },
-        "rccl_ranks": rccl_ranks,
-        "per_rank_ms_per_step": per_rank_ms,
-        "roofline": roofline,
-        "cpu_baseline": cpu_baseline,
-    }
+    line = headline(args, world, value, ms_per_step, rccl_ranks, per_rank_ms)
+    line["roofline"] = roofline
+    line["cpu_baseline"] = cpu_baseline
     line.update(scaling)
     line.update(extra)
     print(json.dumps(line))
@@ -658,7 +724,7 @@ def launcher_selftest(args, rank, world):
     one = torch.ones(1)
     if world > 1:
         dist.all_reduce(one)
-    reducer = sdd.OverlappedAllReduce(grad_mb * 1e6) if world > 1 and grad_mb > 0 else None
+    reducer = sdd.OverlappedAllReduce(grad_mb * 1e6) if world > 1 and grad_mb > 0 and args.full else None
     work = torch.randn(256, 256)
 
     def ops_only_step():  # stand-in for the hot path: the legs and their bookkeeping are what is tested
@@ -691,7 +757,7 @@ def launcher_selftest(args, rank, world):
     barrier()
     elapsed, vals = max_over_ranks(time.perf_counter() - t0)
     scaling = {}
-    if world > 1:
+    if world > 1 and args.full:
         t_single = leg_single_rank(step, barrier, args, rank, torch.device("cpu"))
         scaling = {"n1_ms_per_step_same_invocation": t_single * 1e3 / args.steps,
                    "weak_scaling_eff_same_invocation": t_single / elapsed}

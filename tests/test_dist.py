@@ -23,7 +23,10 @@ def _free_port():
 
 def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
+    # sdd.init binds LOCAL_RANK to a GPU wherever one is visible: on a box with fewer GPUs than ranks the
+    # ranks share them (every tensor of this test lives on the CPU)
+    ndev = torch.cuda.device_count()
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank % ndev if ndev else rank), WORLD_SIZE=str(world),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from simpledet_amd import dist as sdd
     r, _, w = sdd.init("gloo")
@@ -103,10 +106,16 @@ def test_two_rank_sharding_and_gradient_allreduce():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    allr, nb, ok, res = q.get(timeout=120)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    try:
+        allr, nb, ok, res = q.get(timeout=120)
+        for p in procs:
+            p.join(60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:  # a rank left waiting for a failed peer must not outlive the test
+            if p.is_alive():
+                p.terminate()
+                p.join(10)
     assert sorted(sum(allr, [])) == list(range(5))
     assert nb >= 3 and ok
     flat = sorted(sum(res, []))
@@ -136,7 +145,7 @@ def test_bench_self_launch_two_ranks_gloo():
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["SD_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                          "--warmup", "1", "--grad-allreduce", "2"], env=env, capture_output=True,
+                          "--warmup", "1", "--grad-allreduce", "2", "--full"], env=env, capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -174,7 +183,7 @@ def test_bench_rccl_code_path_with_one_rank():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-ops", "--no-extra"],
+                          "--full", "--no-cpu-baseline", "--no-ops", "--no-extra"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

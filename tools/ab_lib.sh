@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of two BUILDS of the library on one GPU box, alternating: tools/ab_lib.sh <other.so> [pairs] [bench flags...]
 OTHER=$1; PAIRS=${2:-3}; shift 2
-run() { python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-ops --no-extra $* 2>/tmp/ab_err.log | python -c "
+run() { python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-ops --no-extra $* 2>/tmp/ab_err.log | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,10 +2,11 @@
 # scratch: a few safe PMC passes (each under its own timeout) for a bench.py variant
 #   usage: tools/pmc_quick.sh <tag> "<bench args>" "<pmc set 1>" ["<pmc set 2>" ...]
 TAG=$1; BARGS=$2; shift 2
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-ops $BARGS"
+CMD="python $REPO/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-ops $BARGS"
 i=0
 for pmc in "$@"; do
   i=$((i+1))
