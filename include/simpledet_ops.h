@@ -616,6 +616,33 @@ int sd_decode_bbox(const float* rois, const float* bbox_pred, const float* im_in
 int sd_det_filter(const float* bbox, const float* cls_score, int B, int R, int K, int bbox_classes,
                   float min_det_score, float* dets, int32_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_GenProposalRetina  (mx.sym.contrib.GenProposalRetina, models/retinanet/builder.py:358-389)
+ *   replaces GenProposalRetinaGPUOp::Forward  operator_cxx/contrib/generate_proposal_retina.cu:301-468
+ *   (im_info D2H, thrust::stable_sort of every (anchor, class, y, x) score per image); the spec is
+ *   the .cu (grid :66-94, BBoxPredKernel :96-159, IoUPredKernel :161-209, FilterBoxKernel :211-233,
+ *   PrepareOutput :275-297), not the stale generate_proposal_retina.cc.
+ *   cls_prob (B,AK,H,W), channel c = anchor*K + class, K = AK / num_anchors; bbox_pred (B,4A,H,W);
+ *   im_info (B,3) DEVICE; anchors (H*W*A,4), or (B,H*W*A,4) when batch_wise_anchor.
+ *   out (B,rpn_pre_nms_top_n,4)  score (B,rpn_pre_nms_top_n,oc), oc = output_one_hot ? K+1 : 1:
+ *   the first min(rpn_pre_nms_top_n, A*K*H*W) rows of the stable descending order of
+ *   (filtered ? 0 : score), row i = (h*W + w)*AK + c; a filtered row (score <= thresh, box side <
+ *   rpn_min_size*im_info[2], or a NaN score) is zeros; the score goes to column
+ *   min(oc-1, class+1); every other element is zero.  Every element of out / score is written.
+ *   mean_host / std_host: anchor_mean / anchor_std, 4 floats each (host).
+ *   Limits: A*K*H*W <= 2^28 rows per image; min(rpn_pre_nms_top_n, rows) <= 16384.
+ *   SD_ERR_UNSUPPORTED (the reference reads out of bounds): iou_loss with K > 1 (:161-209 indexes
+ *   the deltas with a < A*K), batch_wise_anchor with B > 1 and K > 1 (anchor offset i*A*K*H*W*4,
+ *   :383).  Backward (:471-493) is all zeros and has no entry point.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_gen_proposal_retina_workspace_bytes(int B, int AK, int H, int W);
+int sd_gen_proposal_retina(const float* cls_prob, const float* bbox_pred, const float* im_info,
+                           const float* anchors, float* out, float* score, int B, int AK, int H,
+                           int W, int num_anchors, int rpn_pre_nms_top_n, int rpn_min_size,
+                           float thresh, const float* mean_host, const float* std_host, int iou_loss,
+                           int output_one_hot, int batch_wise_anchor, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,21 @@ def Proposal_v3(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_n
     return (out, score) if output_score else out
 
 
+def GenProposalRetina(cls_prob, bbox_pred, im_info, anchors, num_anchors, rpn_pre_nms_top_n=6000,
+                      rpn_min_size=16, thresh=0., anchor_mean=(0.,) * 4, anchor_std=(1.,) * 4,
+                      iou_loss=False, output_one_hot=True, batch_wise_anchor=False, feature_stride=16,
+                      workspace=256):
+    """mx.sym.contrib.GenProposalRetina as models/retinanet/builder.py:358-389 calls it: (out, score).
+    workspace (MB) is the reference's temp-space size and is ignored (the op sizes its own)."""
+    with torch.no_grad():
+        return ops.gen_proposal_retina(cls_prob, bbox_pred, im_info, anchors, num_anchors=num_anchors,
+                                       rpn_pre_nms_top_n=rpn_pre_nms_top_n, rpn_min_size=rpn_min_size,
+                                       thresh=thresh, anchor_mean=anchor_mean, anchor_std=anchor_std,
+                                       iou_loss=iou_loss, output_one_hot=output_one_hot,
+                                       batch_wise_anchor=batch_wise_anchor,
+                                       feature_stride=feature_stride)
+
+
 def get_top_proposal(bbox, score, top_n):
     """mxnext.tvm.get_top_proposal / models/FPN/get_top_proposal.py."""
     with torch.no_grad():

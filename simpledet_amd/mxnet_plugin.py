@@ -1044,6 +1044,105 @@ def _build_ops(mx):
 
     ops["_contrib_Proposal_v3"] = (ProposalV3Prop, ("contrib", "Proposal_v3"))
 
+    # ---- _contrib_GenProposalRetina: cls_prob, bbox_pred, im_info, anchors -> output, scores ----
+    #      (registered only by install(..., retina=True))
+    class GenProposalRetina(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            cls_prob, bbox_pred, im_info, anchors = in_data
+            _wait(cls_prob, bbox_pred, im_info, anchors)
+            g = self.g
+            B, AK, H, W = cls_prob.shape
+            lib().cdll.sd_gen_proposal_retina_workspace_bytes.restype = ctypes.c_size_t
+            wsb = lib().cdll.sd_gen_proposal_retina_workspace_bytes(B, AK, H, W)
+            ws = _scratch(cls_prob, wsb)
+            fa = lambda v: (ctypes.c_float * len(v))(*v)
+            _call("sd_gen_proposal_retina", _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(anchors),
+                  _ptr(out_data[0]), _ptr(out_data[1]), B, AK, H, W, g["A"], g["pre"], g["min_size"],
+                  float(g["thresh"]), fa(g["mean"]), fa(g["std"]), int(g["iou_loss"]), int(g["one_hot"]),
+                  int(g["bwa"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(4):  # generate_proposal_retina.cu:471-493
+                self.assign(in_grad[i], req[i], 0)
+
+    class GenProposalRetinaProp(CustomOpProp):
+        PARAMS = ("rpn_pre_nms_top_n", "rpn_min_size", "feature_stride", "num_anchors", "thresh", "anchor_mean",
+                  "anchor_std", "iou_loss", "output_one_hot", "batch_wise_anchor", "workspace")
+
+        def __init__(self, num_anchors, rpn_pre_nms_top_n="6000", rpn_min_size="16", feature_stride="16",
+                     thresh="0", anchor_mean="(0,0,0,0)", anchor_std="(1,1,1,1)", iou_loss="False",
+                     output_one_hot="True", batch_wise_anchor="False", workspace="256"):
+            # defaults: generate_proposal_retina-inl.h:62-89
+            super().__init__(need_top_grad=False)
+            why = self.sd_supports(dict(num_anchors=num_anchors, rpn_pre_nms_top_n=rpn_pre_nms_top_n,
+                                        iou_loss=iou_loss, batch_wise_anchor=batch_wise_anchor,
+                                        anchor_mean=anchor_mean, anchor_std=anchor_std))
+            if why:
+                raise ValueError("GenProposalRetina: " + why)
+            self.g = dict(A=int(num_anchors), pre=int(rpn_pre_nms_top_n), min_size=int(rpn_min_size),
+                          thresh=float(thresh), mean=_tuple(anchor_mean, 4), std=_tuple(anchor_std, 4),
+                          iou_loss=_bool(iou_loss), one_hot=_bool(output_one_hot), bwa=_bool(batch_wise_anchor))
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls
+            back to the native constructor)."""
+            for k in params:
+                if k not in cls.PARAMS:
+                    return "parameter %r is not one this operator takes" % k
+            try:
+                A = int(params.get("num_anchors", "0"))
+                pre = int(params.get("rpn_pre_nms_top_n", "6000"))
+                _tuple(params.get("anchor_mean", "(0,0,0,0)"), 4)
+                _tuple(params.get("anchor_std", "(1,1,1,1)"), 4)
+            except Exception as e:
+                return "unparsable parameter (%s)" % e
+            if A <= 0:
+                return "num_anchors must be > 0"
+            if not 0 < pre <= 16384:
+                return "rpn_pre_nms_top_n=%d outside 1..16384" % pre
+            # the class count is only known from the input shape: the reference reads out of bounds for
+            # K > 1 in both of these (generate_proposal_retina.cu:161-209, :383)
+            if _bool(params.get("iou_loss", "False")):
+                return "iou_loss is taken only for one class, unknown when the graph is built"
+            if _bool(params.get("batch_wise_anchor", "False")):
+                return "batch_wise_anchor is taken only for one class or one image, unknown when the graph is built"
+            return ""
+
+        def list_arguments(self):
+            return ["cls_prob", "bbox_pred", "im_info", "anchors"]
+
+        def list_outputs(self):
+            return ["output", "scores"]
+
+        def infer_shape(self, in_shape):
+            # GenProposalRetinaProp::InferShape (generate_proposal_retina-inl.h:106-140)
+            d = in_shape[0]
+            if len(d) != 4:
+                raise ValueError("cls_prob should be (batch, num_anchors * num_classes, H, W)")
+            g = self.g
+            A = g["A"]
+            if d[1] % A:
+                raise ValueError("cls_prob channels (%d) are not a multiple of num_anchors (%d)" % (d[1], A))
+            anchors = (d[0], d[2] * d[3] * A, 4) if g["bwa"] else (d[2] * d[3] * A, 4)
+            oc = d[1] // A + 1 if g["one_hot"] else 1
+            return ([d, (d[0], 4 * A, d[2], d[3]), (d[0], 3), anchors],
+                    [(d[0], g["pre"], 4), (d[0], g["pre"], oc)])
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return GenProposalRetina(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    ops["_contrib_GenProposalRetina"] = (GenProposalRetinaProp, ("contrib", "GenProposalRetina"))
+
     # ---- get_top_proposal (models/FPN/get_top_proposal.py): bbox, score -> top_n of each ----
     class GetTopProposal(CustomOp):
         def __init__(self, top_n):
@@ -1138,13 +1237,16 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None):
-    """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}."""
+def register(mx=None, retina=False):
+    """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
+    retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
     _state["mx"] = mx
     table = _build_ops(mx)
+    if not retina:
+        table.pop("_contrib_GenProposalRetina")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1173,7 +1275,7 @@ def _namespaces(mx, ns):
     return out
 
 
-def install(mx=None, stream=None, sync=True):
+def install(mx=None, stream=None, sync=True, retina=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1186,8 +1288,12 @@ def install(mx=None, stream=None, sync=True):
 
     `stream` / `sync`: the hipStream_t every operator launches on (None: the NULL stream; an int; or a callable
     evaluated per call) and whether forward() / backward() synchronise it before they return (the module
-    docstring has the ordering contract; sync=False is for a host that orders the outputs on `stream` itself)."""
-    props = register(mx)
+    docstring has the ordering contract; sync=False is for a host that orders the outputs on `stream` itself).
+
+    `retina=True` also replaces `_contrib_GenProposalRetina` (models/retinanet/builder.py:358-389); it is
+    opt-in because it changes which operator existing RetinaNet graphs hold.  iou_loss / batch_wise_anchor
+    calls fall back to the native constructor (sd_supports)."""
+    props = register(mx, retina=retina)
     mx = _state["mx"]
     _state["fallbacks"] = []
     _state["stream"], _state["sync"] = stream, bool(sync)

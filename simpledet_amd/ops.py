@@ -943,6 +943,57 @@ def get_top_proposal(bbox, score, top_n):
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_GenProposalRetina  (operator_cxx/contrib/generate_proposal_retina{-inl.h,.cu},
+# models/retinanet/builder.py:358-389)
+# --------------------------------------------------------------------------------------------------
+def gen_proposal_retina_workspace_bytes(B, AK, H, W):
+    lib().cdll.sd_gen_proposal_retina_workspace_bytes.restype = ctypes.c_size_t
+    return int(lib().cdll.sd_gen_proposal_retina_workspace_bytes(B, AK, H, W))
+
+
+def gen_proposal_retina(cls_prob, bbox_pred, im_info, anchors, *, num_anchors, rpn_pre_nms_top_n=6000,
+                        rpn_min_size=16, thresh=0., anchor_mean=(0.,) * 4, anchor_std=(1.,) * 4,
+                        iou_loss=False, output_one_hot=True, batch_wise_anchor=False,
+                        feature_stride=16, workspace=None):
+    """GenProposalRetina: cls_prob (B,A*K,H,W), bbox_pred (B,4A,H,W), im_info (B,3), anchors (H*W*A,4)
+    [(B,H*W*A,4) with batch_wise_anchor] -> out (B,rpn_pre_nms_top_n,4),
+    score (B,rpn_pre_nms_top_n,K+1 if output_one_hot else 1)  (generate_proposal_retina-inl.h:106-140).
+    feature_stride only feeds a host-side size check in the reference and is not used.
+    workspace: an optional uint8 tensor of at least gen_proposal_retina_workspace_bytes() bytes."""
+    _chk(cls_prob, "cls_prob", ndim=4)
+    _chk(bbox_pred, "bbox_pred", ndim=4)
+    _chk(im_info, "im_info", ndim=2)
+    _chk(anchors, "anchors")
+    B, AK, H, W = cls_prob.shape
+    A = int(num_anchors)
+    if A <= 0 or AK % A:
+        raise ValueError("cls_prob channels (%d) must be a multiple of num_anchors (%d)" % (AK, A))
+    K = AK // A
+    if bbox_pred.shape != (B, 4 * A, H, W) or im_info.shape != (B, 3):
+        raise ValueError("bbox_pred must be (B,4A,H,W) and im_info (B,3)")
+    want = (B, H * W * A, 4) if batch_wise_anchor else (H * W * A, 4)
+    if tuple(anchors.shape) != want:
+        raise ValueError("anchors must be %s, got %s" % (want, tuple(anchors.shape)))
+    if len(anchor_mean) != 4 or len(anchor_std) != 4:
+        raise ValueError("anchor_mean / anchor_std need 4 values")
+    top_n = int(rpn_pre_nms_top_n)
+    oc = K + 1 if output_one_hot else 1
+    out = torch.empty((B, top_n, 4), device=cls_prob.device, dtype=torch.float32)
+    score = torch.empty((B, top_n, oc), device=cls_prob.device, dtype=torch.float32)
+    wsb = gen_proposal_retina_workspace_bytes(B, AK, H, W)
+    if workspace is None:
+        workspace = torch.empty(wsb, device=cls_prob.device, dtype=torch.uint8)
+    elif workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    lib().call("sd_gen_proposal_retina", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(anchors),
+               _p(out), _p(score), B, AK, H, W, A, top_n, int(rpn_min_size), float(thresh),
+               _farr(anchor_mean), _farr(anchor_std), int(bool(iou_loss)), int(bool(output_one_hot)),
+               int(bool(batch_wise_anchor)), _p(workspace), ctypes.c_size_t(workspace.numel()),
+               _stream())
+    return out, score
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_DecodeBBox + test-time detection filter  (operator_cxx/contrib/decodebbox{-inl.h,.cc},
 # detection_test.py:233-247) -- SURVEY 8(f) rank 2
 # --------------------------------------------------------------------------------------------------
