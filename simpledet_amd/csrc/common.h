@@ -133,8 +133,9 @@ __device__ __forceinline__ int wave_scan_i32(int v) {
 // GEOMETRIC mean of its non-zero gradients (the mean itself is useless here: a lognormal's mean sits far out in
 // its tail).  In exponents, all integer and therefore independent of any summation order:
 //     E(max|g|) + ceil(log2(weight bound)) <= mean E(g) + kFxRangeBits - 1  (E = biased fp32 exponent field),
-// the mean taken over a fixed sample of the stream (the first element of a 16-byte item; the band kernel looks at
-// every fourth of its trips), zeros and denormals not counted.  Near-Gaussian gradients: E(max) - mean E ~ 3.5-4, so weight bounds up to ~2^11 pass;
+// the mean taken over a fixed sample of the stream (the first element of a 16-byte item, on the trips
+// fx_range_stride_mask picks: every fourth trip of the band kernel at the baseline), zeros and denormals not
+// counted.  Near-Gaussian gradients: E(max) - mean E ~ 3.5-4, so weight bounds up to ~2^11 pass;
 // a loss scale cancels out.  A workgroup that fails takes the fp32 compare-and-swap adds -- the reference's own
 // arithmetic (roi_align_v2.cu:67-83, upstream deformable_col2im: a float atomicAdd per tap).
 constexpr int kFxRangeBits = 16;   // (the threshold below adds one bit for the optimistic maximum: 15 against the true one)
@@ -143,21 +144,26 @@ __device__ __forceinline__ int ceil_log2_i32(int b) { return b <= 1 ? 0 : 32 - _
 // The statistic travels as ONE integer per thread / wave / workgroup (one wave reduction, one LDS atomic, one LDS
 // read behind the barrier that ends the scatter anyway -- every instruction in a short-lived workgroup's chain
 // counts: two reductions and a 64-bit verdict cost the headline backward 2 us): per non-zero sample
-//     ((E(g) - e_thr) << 12) + 1,    e_thr = E(optimistic max|g|) + 1 + ceil(log2(weight bound)) - kFxRangeBits,
-// so the upper bits sum the (signed) margins and the low 12 bits count the samples (< 4096 per workgroup: the
-// callers thin their sampling accordingly).  Fine <=> the margins sum to >= 0; when the true maximum turns out more
-// than twice the optimistic one the margins are corrected by the difference of the exponents times the count.
+//     ((E(g) - 127) << 12) + 1,
+// so the upper bits sum the exponents about 127 and the low 12 bits count the samples.  The callers thin their
+// sampling to fewer than 4096 samples per workgroup, so the count never carries, and |E - 127| <= 127 keeps the
+// exponent sum below 2^19 in magnitude: the int32 never wraps, whatever the data (a threshold taken from the
+// optimistic maximum would not do: a first trip of zeros puts it ~140 below every sample).  The threshold
+//     e_thr = E(optimistic max|g|) + 1 + ceil(log2(weight bound)) - kFxRangeBits
+// enters only in fx_range_fine: fine <=> the margins E(g) - e_thr sum to >= 0; when the true maximum turns out
+// more than twice the optimistic one they are corrected by the difference of the exponents times the count.
 __device__ __forceinline__ int fx_range_thr(float gmax_used, int bound) {
   return fp32_exponent_field(gmax_used) + 1 + ceil_log2_i32(bound) - kFxRangeBits;
 }
-__device__ __forceinline__ int fx_range_sample(float v, int e_thr) {
+__device__ __forceinline__ int fx_range_sample(float v) {
   const int ex = fp32_exponent_field(v);
-  return ex ? ((ex - e_thr) << 12) + 1 : 0;
+  return ex ? ((ex - 127) << 12) + 1 : 0;
 }
-__device__ __forceinline__ bool fx_range_fine(int packed, float gmax_used, float gmax_true) {
-  const int cnt = packed & 4095, margins = packed >> 12;
+__device__ __forceinline__ bool fx_range_fine(int packed, int e_thr, float gmax_used, float gmax_true) {
+  const int cnt = packed & 4095, esum = packed >> 12;   // esum = sum of (E - 127), |esum| < 2^19
   const int extra = fp32_exponent_field(gmax_true) - (fp32_exponent_field(gmax_used) + 1);
-  return margins - (extra > 0 ? extra * cnt : 0) >= 0;
+  // sum of the margins minus the correction, exact in int32: |127 - e_thr - extra| < 2^10, cnt < 2^12
+  return esum + cnt * (127 - e_thr - (extra > 0 ? extra : 0)) >= 0;
 }
 // trips between samples (a power of two minus one) so that `per_trip` samples per trip over `trips` trips stay < 4096
 __device__ __forceinline__ int fx_range_stride_mask(long per_trip, long trips, int at_least = 0) {

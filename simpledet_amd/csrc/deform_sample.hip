@@ -269,8 +269,8 @@ __global__ __launch_bounds__(T) void deform_col2im_chunk_kernel(const float* __r
                                                                 int band_rows, int req_add,
                                                                 const unsigned* __restrict__ wsum, int wshift) {
   extern __shared__ __attribute__((aligned(16))) float plane[];
-  __shared__ unsigned s_ctl[4];        // [0] max|col| bits of the first trip, [1] of everything, [2] non-finite flag
-  __shared__ int s_exp[2];             // [0] range margins | sample count of the sampled values (dynamic-range verdict)
+  __shared__ unsigned s_ctl[4];        // [0] max|col| bits of the first trip, [1] of everything, [2] / [3] non-finite flags of the two
+  __shared__ int s_exp[2];             // [0] exponent sum | sample count of the sampled values (dynamic-range verdict)
   const int P = g.Ho * g.Wo, K2 = g.kh * g.kw;
   const int c0 = blockIdx.x * CC, n = blockIdx.z;
   const int row0 = blockIdx.y * band_rows, row1 = iminr(row0 + band_rows, g.H);
@@ -284,11 +284,13 @@ __global__ __launch_bounds__(T) void deform_col2im_chunk_kernel(const float* __r
   const float* cp = col + ((long)n * g.C + c0) * K2 * P;
   const long cstride = (long)K2 * P;  // col elements per channel
   // maxima as bit patterns of |col| (absbits4: a NaN survives); anything above FLT_MAX's pattern is non-finite
-  auto wave_max_to = [&](unsigned m, int slot) {
+  // (the non-finite flag of the first trip goes to s_ctl[2], that of everything to s_ctl[3]: a fast wave's verdict
+  // cannot change the word a slow wave may still be reading before its scatter)
+  auto wave_max_to = [&](unsigned m, int slot, int flag) {
     m = wave_max_u32(m);
     if ((tid & (kWave - 1)) == 0) {
       atomicMax(&s_ctl[slot], m);
-      if (m > kFltMaxBits) atomicOr(&s_ctl[2], 1u);
+      if (m > kFltMaxBits) atomicOr(&s_ctl[flag], 1u);
     }
   };
   // Fixed point (round 6: self-contained -- no maximum from the producer of col, so the stand-alone
@@ -306,7 +308,7 @@ __global__ __launch_bounds__(T) void deform_col2im_chunk_kernel(const float* __r
 #pragma unroll
       for (int cc = 0; cc < CC; ++cc) m0 = umaxr(m0, absbits4(*reinterpret_cast<const float4*>(cp + cc * cstride + tid * 4)));
     }
-    wave_max_to(m0, 0);
+    wave_max_to(m0, 0, 2);
     __syncthreads();
     gmax_used = __uint_as_float(s_ctl[0]);
     // (the integer weight sum is exact in a float up to 2^24 units; beyond that it is rounded to nearest:
@@ -355,7 +357,7 @@ __global__ __launch_bounds__(T) void deform_col2im_chunk_kernel(const float* __r
 #pragma unroll
           for (int cc = 0; cc < CC; ++cc) {
             m_all = umaxr(m_all, absbits4(cv[cc]));
-            if (cc == 0 && tap == 0 && p4 < 16000) e_acc += fx_range_sample(cv[cc].x, e_thr);
+            if (cc == 0 && tap == 0 && p4 < 16000) e_acc += fx_range_sample(cv[cc].x);
           }
         }
         int h_out = p4 / g.Wo, w_out = p4 - h_out * g.Wo;
@@ -406,18 +408,19 @@ __global__ __launch_bounds__(T) void deform_col2im_chunk_kernel(const float* __r
     }
     if (!FX || !fx || attempt > 0) break;
     // was the optimistic maximum enough, and is the unit fine enough for what was streamed?
-    wave_max_to(m_all, 1);
+    wave_max_to(m_all, 1, 3);
     {
       const int es = wave_sum_i32(e_acc);
       if ((tid & (kWave - 1)) == 0) atomicAdd(&s_exp[0], es);   // integer sums: the order of the waves does not matter
     }
     __syncthreads();
     const float gmax_true = __uint_as_float(s_ctl[1]);
-    const bool fine = fx_range_fine(s_exp[0], gmax_used, gmax_true);
-    if (!s_ctl[2] && fine && gmax_true <= 2.f * gmax_used) break;   // also when every value is zero
+    const bool fine = fx_range_fine(s_exp[0], e_thr, gmax_used, gmax_true);
+    const bool nonfinite = (s_ctl[2] | s_ctl[3]) != 0u;
+    if (!nonfinite && fine && gmax_true <= 2.f * gmax_used) break;   // also when every value is zero
     __syncthreads();   // every thread has read the verdict before the planes are cleared
     for (int i = tid; i < CC * band_elems; i += T) plane[i] = 0.f;
-    if (s_ctl[2] || !fine) fx = false;
+    if (nonfinite || !fine) fx = false;
     else set_scale(gmax_true);
     __syncthreads();
   }

@@ -334,7 +334,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   float* plane = smem;
   float* tab = smem + plane_pad;                      // [TCH][TS] sample coordinates
   int* list = reinterpret_cast<int*>(tab + (FLT ? 0 : TCH * TS));  // RoIs of this image on this band
-  int* nlist = list + a.R;  // [0] count [1] bound [2] max|dY| bits, first chunk [3] non-finite [4] max|dY| bits, all
+  int* nlist = list + a.R;  // [0] count [1] bound [2] max|dY| bits, first chunk [3] non-finite, first chunk [4] max|dY| bits, all [5] range statistic [6] non-finite, all
   int* plane_i = reinterpret_cast<int*>(smem);
   const unsigned plane_lds = lds_offset_of(smem);
 
@@ -565,11 +565,13 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   // accumulated again with the exact maximum (or with float adds).  The result is the same
   // deterministic function of the inputs either way.
   // maxima as bit patterns of |g| (absbits4: a NaN survives); anything above FLT_MAX's pattern is non-finite
-  auto wave_max_to = [&](unsigned m, int slot) {
+  // (the non-finite flag of the first items goes to nlist[3], that of the whole stream to nlist[6]: a fast wave's
+  // verdict cannot change the word a slow wave may still be reading before its scatter)
+  auto wave_max_to = [&](unsigned m, int slot, int flag) {
     m = wave_max_u32(m);
     if ((tid & (kWave - 1)) == 0) {
       atomicMax(reinterpret_cast<unsigned*>(nlist + slot), m);
-      if (m > kFltMaxBits) atomicOr(nlist + 3, 1);
+      if (m > kFltMaxBits) atomicOr(nlist + flag, 1);
     }
   };
   auto set_scale = [&](float gmax) {
@@ -589,24 +591,29 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   load_item(tid, 0, iminr(tch, nl) * GP, cur);
   stage_tables(0, iminr(tch, nl));
   unsigned m_all = absbits4(cur.g);
-  if (use_fx) wave_max_to(m_all, 2);
+  if (use_fx) wave_max_to(m_all, 2, 3);
   __syncthreads();
   float gmax_used = 0.f;
-  // margins / count of the sampled non-zero gradients this thread streams: the dynamic-range verdict behind the
+  // exponent sum / count of the sampled non-zero gradients this thread streams: the dynamic-range verdict behind the
   // scatter (kFxRangeBits, common.h)
   int e_acc = 0, e_thr = 0, e_mask = 3;
+  // trips of 512 items: a chunk of tch RoIs takes ceil(tch * GP / THREADS) of them, and the sampling follows one
+  // trip index across the chunks (one trip per chunk at 7x7, two at 14x14)
+  const int chunk_trips = (tch * GP + THREADS - 1) / THREADS;
   if (use_fx) {
     gmax_used = __uint_as_float((unsigned)nlist[2]);
     if (nlist[3]) use_fx = false;  // non-finite gradients: float adds (a zeroed band is 0 in both formats)
     else set_scale(gmax_used > 0.f ? gmax_used : 1.f);
     e_thr = fx_range_thr(gmax_used, nlist[1]);
-    e_mask = fx_range_stride_mask(THREADS, ((long)nl * GP + THREADS - 1) / THREADS, 3);   // (every fourth trip at the baseline)
+    const long trips = (long)(nl / tch) * chunk_trips + ((nl % tch) * GP + THREADS - 1) / THREADS;
+    e_mask = fx_range_stride_mask(THREADS, trips, 3);   // (every fourth trip at the baseline)
   }
   bool synced = false;  // the scatter is already fenced by a barrier
   for (int attempt = 0; attempt < 2; ++attempt) {
     for (int cb = 0; cb < nl; cb += tch) {
       const int ncur = iminr(tch, nl - cb);
       const int nli = ncur * GP;  // lane items of this chunk
+      const int trip0 = (cb / tch) * chunk_trips;
       if (cb > 0 || attempt > 0) {
         load_item(tid, cb, nli, cur);
         __syncthreads();  // the previous chunk's tables are no longer read
@@ -617,7 +624,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
         Item nxt;
         load_item(t + THREADS, cb, nli, nxt);
         m_all = umaxr(m_all, absbits4(cur.g));
-        if (((t / THREADS) & e_mask) == 0) e_acc += fx_range_sample(cur.g.x, e_thr);   // (wave uniform)
+        if (((trip0 + t / THREADS) & e_mask) == 0) e_acc += fx_range_sample(cur.g.x);   // (wave uniform)
         if (TAPS) scatter_taps(cur, cur.j);
         else scatter_item(cur, cur.j);
         cur = nxt;
@@ -626,15 +633,16 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
     if (!use_fx || attempt > 0) break;
     // was the optimistic scale enough, and is the unit fine enough for what was streamed?  (checked behind
     // the barrier that ends the scatter anyway)
-    wave_max_to(m_all, 4);
+    wave_max_to(m_all, 4, 6);
     {
       const int es = wave_sum_i32(e_acc);
       if ((tid & (kWave - 1)) == 0) atomicAdd(nlist + 5, es);   // integer sums: the order of the waves does not matter
     }
     __syncthreads();
     const float gmax_true = __uint_as_float((unsigned)nlist[4]);
-    const bool fine = fx_range_fine(nlist[5], gmax_used, gmax_true);
-    if (!nlist[3] && fine && gmax_true <= 2.f * gmax_used) { synced = true; break; }  // also when all gradients are zero
+    const bool fine = fx_range_fine(nlist[5], e_thr, gmax_used, gmax_true);
+    const bool nonfinite = nlist[3] | nlist[6];
+    if (!nonfinite && fine && gmax_true <= 2.f * gmax_used) { synced = true; break; }  // also when all gradients are zero
     __syncthreads();  // every thread has read the verdict before the band is cleared
     // rare: accumulate the band again with the exact maximum, or -- non-finite gradients, a dynamic range the
     // fixed-point unit is too coarse for -- with float adds
@@ -643,7 +651,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int i = tid; i < plane_pad / 4; i += THREADS) p4[i] = z;
     }
-    if (nlist[3] || !fine) use_fx = false;
+    if (nonfinite || !fine) use_fx = false;
     else set_scale(gmax_true);
   }
   if (!synced) __syncthreads();
@@ -720,7 +728,7 @@ __global__ __launch_bounds__(THREADS) void roi_align_bwd_flt4_kernel(BwdFusedArg
   const int H = a.L.H[lvl], W = a.L.W[lvl], HW = H * W, PP = a.PP;
   float* plane = smem;  // [CC][HW]
   int* plane_i = reinterpret_cast<int*>(smem);
-  int* ctl = plane_i + CC * HW;  // [0] weight bound, [1] max|dY| of the first items, [2] non-finite flag, [3] true max|dY|, [4] range margins | sample count
+  int* ctl = plane_i + CC * HW;  // [0] weight bound, [1] max|dY| of the first items, [2] non-finite flag, [3] true max|dY|, [4] exponent sum | sample count of the range verdict
   bool use_fx = !a.float_adds;
   if (tid < 8) ctl[tid] = 0;
   if (use_fx) {
@@ -814,7 +822,7 @@ __global__ __launch_bounds__(THREADS) void roi_align_bwd_flt4_kernel(BwdFusedArg
   if (use_fx) wave_max_to(m_all, 1);
   __syncthreads();  // the planes are zero, the first maxima are in
   float gmax_used = 0.f;
-  int e_acc = 0, e_thr = 0, e_mask = 7;  // margins / count of the sampled non-zero gradients (kFxRangeBits, common.h)
+  int e_acc = 0, e_thr = 0, e_mask = 7;  // exponent sum / count of the sampled non-zero gradients (kFxRangeBits, common.h)
   if (use_fx) {
     gmax_used = __uint_as_float((unsigned)ctl[1]);
     // (the non-finite flag has its own barrier-separated read: a wave that reaches the verdict of attempt 0
@@ -831,7 +839,7 @@ __global__ __launch_bounds__(THREADS) void roi_align_bwd_flt4_kernel(BwdFusedArg
       Item nxt;
       load_item(u + THREADS, nxt);
       m_all = umaxr(m_all, absbits4(cur.g));
-      if (((u / THREADS) & e_mask) == 0) e_acc += fx_range_sample(cur.g.x, e_thr);   // (wave uniform)
+      if (((u / THREADS) & e_mask) == 0) e_acc += fx_range_sample(cur.g.x);   // (wave uniform)
       const float gg[4] = {cur.g.x, cur.g.y, cur.g.z, cur.g.w}, xx[4] = {cur.x.x, cur.x.y, cur.x.z, cur.x.w};
       const float yy[4] = {cur.y.x, cur.y.y, cur.y.z, cur.y.w};
 #pragma unroll
@@ -874,7 +882,7 @@ __global__ __launch_bounds__(THREADS) void roi_align_bwd_flt4_kernel(BwdFusedArg
     }
     __syncthreads();
     const float gmax_true = __uint_as_float((unsigned)ctl[3]);
-    const bool fine = fx_range_fine(ctl[4], gmax_used, gmax_true);
+    const bool fine = fx_range_fine(ctl[4], e_thr, gmax_used, gmax_true);
     if (!ctl[2] && fine && gmax_true <= 2.f * gmax_used) break;  // also when all gradients are zero
     __syncthreads();  // every thread has read the verdict before the planes are cleared
     // rare: again, with the exact maximum -- or with float adds (non-finite gradients, a dynamic range the
