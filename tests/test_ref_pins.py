@@ -1,7 +1,11 @@
-"""Parity pins against THE REFERENCE'S OWN CODE.
+"""Cross-checks against THE REFERENCE'S OWN C++, through oracle/mxshim (not a pin).
 
 oracle/build_ref_cxx.py compiles the reference's operator sources (operator_cxx/**/*.cc and, through
-a host emulation of the CUDA launch model, *.cu) unmodified and where they lie; the fixtures
+a host emulation of the CUDA launch model, *.cu) unmodified and where they lie, against the MXNet /
+CUDA stand-ins of oracle/mxshim -- our own code, so a misreading shared by the shim and the oracle
+would pass here.  The pins that no code of ours sits under are in tests/test_py_twin_pins.py
+(ProposalTarget and DecodeBBox against the reference's float64 Python twins); RoIAlign has no
+runnable reference-side twin.  The fixtures
 tests/golden/ref_cxx_{digests.json,arrays.npz} were produced by running the seeded cases of
 tests/refcases.py through those libraries (tests/golden/make_golden_cxx.py).
 
