@@ -56,9 +56,10 @@ const char* sd_last_dispatch(void);
  * slower tiled kernels); 4 sd_gemm_f32 computes products as three bf16 MFMA terms by default
  * (same signature, documented error model), sd_proposal_mask_target_ratio / sd_cast_* / *_f16 added;
  * 5 sd_gemm_f32_ws, the DCN products default to the scaled fp16 split (fp32-path accuracy), plain
- * sd_gemm_f32 to exact fp32.
+ * sd_gemm_f32 to exact fp32; 8 sd_proposal and sd_proposal_v2 added (the existing entry points and
+ * their workspace sizes are unchanged).
  * sd_abi_version() returns the library's value; compare with this macro. */
-#define SD_ABI_VERSION 7
+#define SD_ABI_VERSION 8
 int sd_abi_version(void);
 /* kernel-variant knobs for A/B measurements (bench.py, tests); every variant computes the same
  * result.  Unknown keys are an error.  Knobs that disable parts of a kernel for profiling exist
@@ -593,6 +594,52 @@ int sd_proposal_v3_iou(const float* cls_prob, const float* bbox_pred, const floa
                        const float* scales_host, int n_scales, const float* ratios_host,
                        int n_ratios, int feature_stride, int is_train, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_Proposal_v2  (mx.sym.contrib.Proposal_v2, models/tridentnet/builder.py:239-255) and
+ * _contrib_Proposal     (mx.sym.contrib.Proposal, X.proposal of symbol/builder.py:241)
+ *   replace ProposalGPUOp_v2::Forward  operator_cxx/contrib/proposal_v2.cu:413-620 and
+ *   ProposalGPUOp::Forward proposal.cu:417-614 (im_info / valid_ranges D2H, per image a thrust
+ *   stable sort of every anchor, the NMS mask D2H, a host scan and keep H2D).  The spec is the .cu:
+ *   - decode BBoxPredKernel (:92-147): centre x1 + 0.5 (w - 1), corners centre -/+ 0.5 (pred_w - 1),
+ *     dw / dh NOT clamped (exp may give inf; the clip to [0, im - 1] decides); or IoUPredKernel
+ *     (:155-195) with iou_loss; anchors as proposal_v2-inl.h GenerateAnchors (floor(x + 0.5f), not
+ *     the rintf of Proposal_v3)
+ *   - score -1 for anchors at h >= (int)(im_h / stride) or w >= (int)(im_w / stride) (both
+ *     variants).  An image taller / wider than H * stride (the reference aborts on CHECK_GE)
+ *     marks no anchor.
+ *   - FilterBoxKernel (:201-222) on ALL rows before the top-k: min_size = rpn_min_size * im_info[2];
+ *     a side < min_size grows the box by min_size / 2 on each side and scores it -1; else, for v2
+ *     with filter_scales, area < valid_ranges[i,0]^2 or > valid_ranges[i,1]^2 (fp32) scores it -1
+ *   - top-`pre` of a stable descending sort over all rows (the -1 rows included), NMS with IoU > thr
+ *     (strict, +1 areas); rows scored -1 are not excluded and can be emitted
+ *   - out (B,post,4)  score (B,post): the kept boxes, then zeros (v2; v1 test) or the kept boxes
+ *     repeated cyclically (v1 is_train).  Proposal in test mode keeps post as given
+ *     (proposal.cu:453-455), so post > pre is well formed there and zero padded.
+ *   cls_prob (B,2A,H,W) (foreground = second half)  bbox_pred (B,4A,H,W)  im_info (B,3)
+ *   valid_ranges (B,2) DEVICE (read only with filter_scales; may be NULL otherwise).
+ *   NaN rule: a NaN score is ordered by its bits (positive NaNs before +inf, negative after -inf);
+ *   a NaN box coordinate is clipped to im - 1 (the reference's fminf); a NaN side or area fails no
+ *   filter test; a NaN IoU suppresses nothing.
+ *   SD_ERR_UNSUPPORTED: rpn_post_nms_top_n > min(pre, A*H*W) for v2, and for v1 with is_train (the
+ *   reference shapes the output (B, post) but writes image i at stride min(post, pre): rows
+ *   misplaced, the tail never written);
+ *   pre > 16384 (the LDS sort capacity).  SD_ERR_INVALID_ARG: A*H*W >= 2^24.
+ *   Backward (proposal_v2.cu:617-639) is all zeros and has no entry point.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_proposal_v2_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n);
+int sd_proposal_v2(const float* cls_prob, const float* bbox_pred, const float* im_info,
+                   const float* valid_ranges, float* out, float* score, int B, int A, int H, int W,
+                   int rpn_pre_nms_top_n, int rpn_post_nms_top_n, float threshold,
+                   int rpn_min_size, const float* scales_host, int n_scales,
+                   const float* ratios_host, int n_ratios, int feature_stride, int filter_scales,
+                   int iou_loss, void* workspace, size_t workspace_bytes, void* stream);
+size_t sd_proposal_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n);
+int sd_proposal(const float* cls_prob, const float* bbox_pred, const float* im_info, float* out,
+                float* score, int B, int A, int H, int W, int rpn_pre_nms_top_n,
+                int rpn_post_nms_top_n, float threshold, int rpn_min_size, const float* scales_host,
+                int n_scales, const float* ratios_host, int n_ratios, int feature_stride,
+                int is_train, int iou_loss, void* workspace, size_t workspace_bytes, void* stream);
 /* get_top_proposal CustomOp (models/FPN/get_top_proposal.py:15-39): the top_n rows of bbox (B,N,4)
  * by score (B,N) descending (ties: lower row first), zero padded when N < top_n */
 int sd_get_top_proposal(const float* bbox, const float* score, int B, int N, int top_n,

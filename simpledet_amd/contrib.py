@@ -196,6 +196,30 @@ def Proposal_v3(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_n
     return (out, score) if output_score else out
 
 
+def Proposal_v2(cls_prob, bbox_pred, im_info, valid_ranges, rpn_pre_nms_top_n=6000,
+                rpn_post_nms_top_n=300, threshold=0.7, rpn_min_size=16, scales=(4., 8., 16., 32.),
+                ratios=(0.5, 1., 2.), feature_stride=16, output_score=False, iou_loss=False,
+                workspace=256, filter_scales=False):
+    """mx.sym.contrib.Proposal_v2 as models/tridentnet/builder.py:239-255 calls it.
+    workspace (MB) is the reference's temp-space size and is ignored (the op sizes its own)."""
+    with torch.no_grad():
+        out, score = ops.proposal_v2(cls_prob, bbox_pred, im_info, valid_ranges, rpn_pre_nms_top_n,
+                                     rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                                     feature_stride, filter_scales, iou_loss)
+    return (out, score) if output_score else out
+
+
+def Proposal(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300,
+             threshold=0.7, rpn_min_size=16, scales=(4., 8., 16., 32.), ratios=(0.5, 1., 2.),
+             feature_stride=16, output_score=False, iou_loss=False, workspace=256, is_train=False):
+    """mx.sym.contrib.Proposal (X.proposal, symbol/builder.py:241).  workspace (MB) is ignored."""
+    with torch.no_grad():
+        out, score = ops.proposal(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n,
+                                  rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                                  feature_stride, is_train, iou_loss)
+    return (out, score) if output_score else out
+
+
 def GenProposalRetina(cls_prob, bbox_pred, im_info, anchors, num_anchors, rpn_pre_nms_top_n=6000,
                       rpn_min_size=16, thresh=0., anchor_mean=(0.,) * 4, anchor_std=(1.,) * 4,
                       iou_loss=False, output_one_hot=True, batch_wise_anchor=False, feature_stride=16,

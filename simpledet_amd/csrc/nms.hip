@@ -309,11 +309,18 @@ struct PropArgs {
   int A, H, W, stride, count, pre, P2;
   int iou_loss;  // IoUPredKernel instead of BBoxPredKernel
   float min_size;
+  int v12;       // Proposal / Proposal_v2: the decode kernel filters, the gather does not
+  // Proposal_v2 only: per image (min, max) side of the valid scale range, and whether it is applied
+  const float* valid_ranges;
+  int filter_scales;
+  int rpn_min_size;  // Proposal / Proposal_v2: min_size = rpn_min_size * im_info[2]
   // multi-workgroup top-k (large levels): per image 4 x 256 digit counters, a candidate counter and
-  // P2 candidate keys in global memory; G workgroups per image
+  // P2 candidate keys in global memory; G workgroups per image; the last digit's histogram of
+  // every workgroup's chunk (G x 256 per image) ranks the ties at the cut-off key in row order
   int* ghist;
   int* gncand;
   unsigned long long* gcand;
+  int* gtie;
   int G;
 };
 
@@ -364,12 +371,94 @@ __global__ __launch_bounds__(256) void proposal_decode_kernel(PropArgs a) {
   a.score_all[(long)img * a.count + index] = sc;
 }
 
-// gather of the sorted rows + FilterBoxKernel (proposal_v3.cu:211-235)
+// _contrib_Proposal_v2 / _contrib_Proposal (proposal_v2.cu / proposal.cu): ProposalGridKernel
+// (:64-85), BBoxPredKernel (:92-147: centre x1 + 0.5 (w - 1), corners centre -/+ 0.5 (pred_w - 1),
+// no clamp of dw / dh) or IoUPredKernel (:155-195), the score -1 of anchors past the unpadded image
+// (both variants), then FilterBoxKernel (:201-222) on EVERY row before the top-k: a side below
+// rpn_min_size * im_info[2] grows the box by half of it on each side and scores it -1, else (v2 with
+// filter_scales) an area outside that image's squared valid range scores -1.  The clip maps a NaN
+// coordinate to im - 1 (CUDA fminf), as fminr does.
+__global__ __launch_bounds__(256) void proposal_v12_decode_kernel(PropArgs a) {
+  const int img = blockIdx.y;
+  const int index = blockIdx.x * blockDim.x + threadIdx.x;
+  if (index >= a.count) return;
+  const int an = index % a.A, w = (index / a.A) % a.W, h = index / a.A / a.W;
+  const float im_height = a.im_info[img * 3 + 0], im_width = a.im_info[img * 3 + 1];
+  const float im_scale = a.im_info[img * 3 + 2];
+  const long plane = (long)a.H * a.W;
+  const float* fg = a.cls_prob + ((long)img * 2 * a.A + a.A) * plane;
+  const float* deltas = a.bbox_pred + (long)img * 4 * a.A * plane;
+  const long hw = (long)h * a.W + w;
+  const float x1 = a.anchors[an * 4 + 0] + (float)(w * a.stride);
+  const float y1 = a.anchors[an * 4 + 1] + (float)(h * a.stride);
+  const float x2 = a.anchors[an * 4 + 2] + (float)(w * a.stride);
+  const float y2 = a.anchors[an * 4 + 3] + (float)(h * a.stride);
+  const float dx = deltas[(long)(an * 4) * plane + hw];
+  const float dy = deltas[(long)(an * 4 + 1) * plane + hw];
+  const float dw = deltas[(long)(an * 4 + 2) * plane + hw];
+  const float dh = deltas[(long)(an * 4 + 3) * plane + hw];
+  float px1, py1, px2, py2;
+  if (a.iou_loss) {
+    px1 = x1 + dx;
+    py1 = y1 + dy;
+    px2 = x2 + dw;
+    py2 = y2 + dh;
+  } else {
+    const float width = x2 - x1 + 1.0f, height = y2 - y1 + 1.0f;
+    const float ctr_x = x1 + 0.5f * (width - 1.0f), ctr_y = y1 + 0.5f * (height - 1.0f);
+    const float pred_ctr_x = dx * width + ctr_x, pred_ctr_y = dy * height + ctr_y;
+    const float pred_w = (float)exp((double)dw) * width, pred_h = (float)exp((double)dh) * height;
+    px1 = pred_ctr_x - 0.5f * (pred_w - 1.0f);
+    py1 = pred_ctr_y - 0.5f * (pred_h - 1.0f);
+    px2 = pred_ctr_x + 0.5f * (pred_w - 1.0f);
+    py2 = pred_ctr_y + 0.5f * (pred_h - 1.0f);
+  }
+  float4 o;
+  o.x = fmaxr(fminr(px1, im_width - 1.0f), 0.0f);
+  o.y = fmaxr(fminr(py1, im_height - 1.0f), 0.0f);
+  o.z = fmaxr(fminr(px2, im_width - 1.0f), 0.0f);
+  o.w = fmaxr(fminr(py2, im_height - 1.0f), 0.0f);
+  float sc = fg[(long)an * plane + hw];
+  // real_height / real_width (:492-493); an image taller than H * stride marks no anchor here
+  // (the reference aborts on CHECK_GE)
+  if (h >= (int)(im_height / (float)a.stride) || w >= (int)(im_width / (float)a.stride)) sc = -1.0f;
+  const float min_size = (float)a.rpn_min_size * im_scale;
+  const float iw = o.z - o.x + 1.0f, ih = o.w - o.y + 1.0f;
+  if (iw < min_size || ih < min_size) {
+    o.x -= min_size / 2;
+    o.y -= min_size / 2;
+    o.z += min_size / 2;
+    o.w += min_size / 2;
+    sc = -1.0f;
+  } else if (a.filter_scales) {
+    const float vmin = a.valid_ranges[img * 2 + 0], vmax = a.valid_ranges[img * 2 + 1];
+    const float area = iw * ih;
+    if (area < vmin * vmin || area > vmax * vmax) sc = -1.0f;
+  }
+  a.boxes_all[(long)img * a.count + index] = o;
+  a.score_all[(long)img * a.count + index] = sc;
+}
+
+// gather of the sorted rows + FilterBoxKernel (proposal_v3.cu:211-235); Proposal / Proposal_v2
+// filtered every row in the decode kernel, so their gather copies the rows as they are
 __device__ __forceinline__ void proposal_gather_filter(const PropArgs& a, int img,
                                                        const unsigned long long* keys, int tid,
                                                        int T) {
   const float* sc = a.score_all + (long)img * a.count;
   const float4* bx = a.boxes_all + (long)img * a.count;
+  if (a.v12) {
+    for (int i = tid; i < a.pre; i += T) {
+      const int src = (int)(unsigned)(keys[i] & 0xffffffffu);
+      const long o = (long)img * a.pre + i;
+      // exactly `pre` candidates reach here; the bound only keeps a broken invariant from reading
+      // outside the rows (a zero box with score 0, which the tests would report)
+      const bool ok = (unsigned)src < (unsigned)a.count;
+      a.ws.order[o] = ok ? src : -1;
+      a.ws.boxes[o] = ok ? bx[src] : make_float4(0.f, 0.f, 0.f, 0.f);
+      a.ws.score[o] = ok ? sc[src] : 0.f;
+    }
+    return;
+  }
   const float im_h = a.im_info[img * 3 + 0], im_w = a.im_info[img * 3 + 1];
   const float scale = a.im_info[img * 3 + 2];
   for (int i = tid; i < a.pre; i += T) {
@@ -508,9 +597,17 @@ __global__ __launch_bounds__(256) void topk_hist_kernel(PropArgs a, int pass) {
   }
   __syncthreads();
   if (lh[tid]) atomicAdd(&gh[pass * 256 + tid], lh[tid]);
+  // the last digit: this chunk's count of every full key, kept for the ranking of the ties at the
+  // cut-off key (topk_compact_kernel); every counter is written, so nothing needs clearing
+  if (pass == 3 && a.v12) a.gtie[((long)img * a.G + blockIdx.x) * 256 + tid] = lh[tid];
 }
 
-// grid (G, B): rows strictly better than the threshold key, plus the ties when all of them are taken
+// grid (G, B): rows strictly better than the threshold key, plus the ties at that key.  When only
+// `want` of the n_eq ties are taken (a stable sort keeps the lowest rows: for Proposal /
+// Proposal_v2 the cut usually falls inside a run of tens of thousands of rows filtered to -1), a
+// tie's rank in row order is the ties of the earlier chunks (chunks are contiguous row ranges: an
+// exclusive sum over the last-digit histograms of topk_hist_kernel) plus the ties before it in this
+// chunk (trip by trip in row order; inside a trip row = i0 + u * 256 + wave * 64 + lane).
 __global__ __launch_bounds__(256) void topk_compact_kernel(PropArgs a) {
   __shared__ int hist[260];
   const int img = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
@@ -518,11 +615,25 @@ __global__ __launch_bounds__(256) void topk_compact_kernel(PropArgs a) {
   const TopkState s = topk_resolve(a.ghist + (long)img * 4 * 256, 4, a.pre, hist);
   const unsigned Tkey = s.prefix;
   const bool all_ties = s.want >= s.n_eq;
+  // Proposal_v3 leaves partly taken ties to topk_finish_kernel (its single-workgroup row select)
+  const bool rank_ties = !all_ties && a.v12;
   unsigned long long* cand = a.gcand + (long)img * a.P2;
   const int chunk = (a.count + a.G - 1) / a.G;
   const int lo = blockIdx.x * chunk, hi = iminr(lo + chunk, a.count);
   __shared__ int wcount[4], wbase;
+  __shared__ int tcount[8][4], tbase;  // ties per (load slot, wave) of the trip; ties before it
   const int wave = tid / kWave;
+  if (rank_ties) {
+    if (tid < kWave) {
+      const int* th = a.gtie + (long)img * a.G * 256 + (Tkey & 255u);
+      int v = 0;
+      for (int c = lane; c < (int)blockIdx.x; c += kWave) v += th[(long)c * 256];
+#pragma unroll
+      for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) tbase = v;
+    }
+    __syncthreads();
+  }
   for (int i0 = lo; i0 < hi; i0 += 8 * 256) {  // eight loads in flight per lane
     unsigned kk[8];
 #pragma unroll
@@ -530,17 +641,41 @@ __global__ __launch_bounds__(256) void topk_compact_kernel(PropArgs a) {
       const int i = i0 + u * 256 + tid;
       kk[u] = i < hi ? ordered_desc_bits(sc[i]) : 0xffffffffu;
     }
+    unsigned long long bal[8];
+    if (!rank_ties) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * 256 + tid;
+        bal[u] = __ballot(i < hi && (kk[u] < Tkey || (kk[u] == Tkey && all_ties)));
+      }
+    } else {
+      unsigned long long beq[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * 256 + tid;
+        beq[u] = __ballot(i < hi && kk[u] == Tkey);
+        if (lane == 0) tcount[u][wave] = __popcll(beq[u]);
+      }
+      __syncthreads();
+      int rank = tbase;  // ties before slot (u, wave) in row order
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * 256 + tid;
+        int r = rank;
+        for (int w = 0; w < wave; ++w) r += tcount[u][w];
+        r += __popcll(beq[u] & ((1ull << lane) - 1));
+        const bool eq = (beq[u] >> lane) & 1ull;
+        bal[u] = __ballot(i < hi && (kk[u] < Tkey || (eq && r < s.want)));
+        rank += tcount[u][0] + tcount[u][1] + tcount[u][2] + tcount[u][3];
+      }
+      __syncthreads();  // every wave has read tcount / tbase
+      if (tid == 0) tbase = rank;
+    }
     // one global reservation per workgroup and trip (a per-wave atomic on the image's single
     // counter serialises ~4000 atomics at the L2: 30 us for P2)
-    unsigned long long bal[8];
     int mine = 0;
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + u * 256 + tid;
-      const bool take = i < hi && (kk[u] < Tkey || (kk[u] == Tkey && all_ties));
-      bal[u] = __ballot(take);
-      mine += __popcll(bal[u]);  // wave-uniform
-    }
+    for (int u = 0; u < 8; ++u) mine += __popcll(bal[u]);  // wave-uniform
     if (lane == 0) wcount[wave] = mine;
     __syncthreads();
     if (tid == 0) {
@@ -559,11 +694,13 @@ __global__ __launch_bounds__(256) void topk_compact_kernel(PropArgs a) {
       }
       base += __popcll(bal[u]);
     }
-    __syncthreads();  // wcount / wbase are reused by the next trip
+    __syncthreads();  // wcount / wbase / tcount / tbase are reused by the next trip
   }
 }
 
-// one workgroup per image: ties that are only partly taken (rare), sort, gather + FilterBox
+// one workgroup per image: Proposal_v3's ties that are only partly taken (rare: a single-workgroup
+// select of the lowest tied rows), sort, gather + FilterBox (v3 only).  Proposal / Proposal_v2 ranked
+// their ties in topk_compact_kernel and arrive with exactly `pre` candidates.
 __global__ __launch_bounds__(1024) void topk_finish_kernel(PropArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // P2 composite keys
   __shared__ int hist[260];
@@ -578,7 +715,7 @@ __global__ __launch_bounds__(1024) void topk_finish_kernel(PropArgs a) {
   for (int i = tid; i < a.P2; i += T) keys[i] = i < nc ? cand[i] : ~0ull;
   if (tid == 0) ncand = nc;
   __syncthreads();
-  if (s.want < s.n_eq) {
+  if (!a.v12 && s.want < s.n_eq) {
     // only the `want` lowest rows among the ties are taken: select the want-th smallest tied row
     unsigned ipre = 0, imask = 0;
     int iwant = s.want;
@@ -724,6 +861,29 @@ static void proposal_v3_anchors(int feature_stride, const float* scales, int ns,
     }
 }
 
+// proposal_v2-inl.h:295-321 / proposal-inl.h (the same): like proposal_v3_anchors but rounding
+// with floor(x + 0.5f), which differs from rintf at the halves (11.5 -> 12, 6.5 -> 7)
+static void proposal_v12_anchors(int feature_stride, const float* scales, int ns,
+                                 const float* ratios, int nr, float* anchors) {
+  const float base[4] = {0.0f, 0.0f, (float)(feature_stride - 1.0), (float)(feature_stride - 1.0)};
+  int n = 0;
+  for (int j = 0; j < nr; ++j)
+    for (int k = 0; k < ns; ++k) {
+      const float scale = scales[k], ratio = ratios[j];
+      const float w = base[2] - base[0] + 1.0f, h = base[3] - base[1] + 1.0f;
+      const float x_ctr = (float)(base[0] + 0.5 * (w - 1.0f));
+      const float y_ctr = (float)(base[1] + 0.5 * (h - 1.0f));
+      const float size_ratios = floorf((w * h) / ratio);
+      const float new_w = floorf(sqrtf(size_ratios) + 0.5f) * scale;
+      const float new_h = floorf((new_w / scale * ratio) + 0.5f) * scale;
+      anchors[n * 4 + 0] = x_ctr - 0.5f * (new_w - 1.0f);
+      anchors[n * 4 + 1] = y_ctr - 0.5f * (new_h - 1.0f);
+      anchors[n * 4 + 2] = x_ctr + 0.5f * (new_w - 1.0f);
+      anchors[n * 4 + 3] = y_ctr + 0.5f * (new_h - 1.0f);
+      ++n;
+    }
+}
+
 static void proposal_dims(int count, int pre_in, int post_in, int is_train, int* pre, int* post) {
   int p = pre_in > 0 ? pre_in : count;  // proposal_v3.cu:467-473
   if (p > count) p = count;
@@ -732,7 +892,15 @@ static void proposal_dims(int count, int pre_in, int post_in, int is_train, int*
   if (!is_train) *post = post_in;
 }
 
-extern "C" size_t sd_proposal_v3_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n) {
+// workgroups per image of the multi-workgroup top-k: one 8 x 256 trip each, at most 128
+static int topk_groups(int count) {
+  const int G = (count + 2047) / 2048;
+  return G > 128 ? 128 : G;
+}
+
+// with_ties: Proposal / Proposal_v2 also keep the last-digit histogram of every chunk (B x G x 256
+// ints) that ranks the ties at the cut-off; Proposal_v3's layout is unchanged
+static size_t proposal_ws_bytes(int B, int A, int H, int W, int pre_nms_top_n, bool with_ties) {
   if (B <= 0 || A <= 0 || H <= 0 || W <= 0) return 256;
   const long count = (long)A * H * W;
   int pre, post;
@@ -742,16 +910,42 @@ extern "C" size_t sd_proposal_v3_workspace_bytes(int B, int A, int H, int W, int
   while (P2 < pre) P2 <<= 1;
   return nms_layout(B, pre, nb, nullptr, nullptr) + align_up((size_t)B * count * 16, 256) +
          align_up((size_t)B * count * 4, 256) + align_up((size_t)B * (4 * 256 + 1) * 4, 256) +
-         align_up((size_t)B * P2 * 8, 256) + 512;
+         align_up((size_t)B * P2 * 8, 256) +
+         (with_ties ? align_up((size_t)B * topk_groups((int)count) * 1024, 256) : 0) + 512;
 }
 
-static int proposal_v3_impl(const float* cls_prob, const float* bbox_pred, const float* im_info,
-                            float* out, float* score, int B, int A, int H, int W,
-                            int rpn_pre_nms_top_n, int rpn_post_nms_top_n, float threshold,
-                            int rpn_min_size, const float* scales_host, int n_scales,
-                            const float* ratios_host, int n_ratios, int feature_stride,
-                            int is_train, int iou_loss, void* workspace, size_t workspace_bytes,
-                            void* stream) {
+extern "C" size_t sd_proposal_v3_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n) {
+  return proposal_ws_bytes(B, A, H, W, pre_nms_top_n, false);
+}
+
+extern "C" size_t sd_proposal_v2_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n) {
+  return proposal_ws_bytes(B, A, H, W, pre_nms_top_n, true);
+}
+
+extern "C" size_t sd_proposal_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n) {
+  return proposal_ws_bytes(B, A, H, W, pre_nms_top_n, true);
+}
+
+// the top-k counters (digit histograms, candidate counts) are zeroed by a kernel rather than
+// hipMemsetAsync: they must be zero in every replay of a captured graph as well (a memset node was
+// not repeated on replays here, see gen_proposal_retina.hip; stale counts let the finish kernel
+// read candidate slots this call never wrote)
+__global__ __launch_bounds__(256) void topk_zero_kernel(int* p, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+
+// version 3: Proposal_v3; 2: Proposal_v2 (valid_ranges / filter_scales); 1: Proposal (is_train
+// only chooses the padding)
+static int proposal_impl(int version, const float* cls_prob, const float* bbox_pred,
+                         const float* im_info, const float* valid_ranges, float* out, float* score,
+                         int B, int A, int H, int W, int rpn_pre_nms_top_n, int rpn_post_nms_top_n,
+                         float threshold, int rpn_min_size, const float* scales_host, int n_scales,
+                         const float* ratios_host, int n_ratios, int feature_stride, int is_train,
+                         int filter_scales, int iou_loss, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  const bool v12 = version != 3;
+  const char* name = version == 3 ? "Proposal" : (version == 2 ? "Proposal_v2" : "Proposal");
   SD_REQUIRE(B >= 0 && A > 0 && H > 0 && W > 0, "bad dimensions");
   SD_REQUIRE(scales_host && ratios_host && n_scales * n_ratios == A,
              "num_anchors (%d) != ratios (%d) x scales (%d)", A, n_ratios, n_scales);
@@ -761,9 +955,19 @@ static int proposal_v3_impl(const float* cls_prob, const float* bbox_pred, const
   SD_REQUIRE(count_l < (1L << 24), "too many anchors per image (%ld)", count_l);
   const int count = (int)count_l;
   int pre, post;
-  proposal_dims(count, rpn_pre_nms_top_n, rpn_post_nms_top_n, is_train, &pre, &post);
+  // Proposal in test mode keeps the unclamped post (proposal.cu:453-455: stride post, zero tail)
+  proposal_dims(count, rpn_pre_nms_top_n, rpn_post_nms_top_n, version == 2 ? 1 : is_train, &pre,
+                &post);
+  // proposal_v2.cu:450 / proposal.cu:453 with is_train write image i at stride min(post, pre)
+  if ((version == 2 || (version == 1 && is_train)) && rpn_post_nms_top_n > pre)
+    return fail(SD_ERR_UNSUPPORTED, "%s: rpn_post_nms_top_n=%d > min(rpn_pre_nms_top_n, anchors)=%d "
+                "(the reference shapes the output (B, post) but writes each image at stride %d)",
+                name, rpn_post_nms_top_n, pre, pre);
+  if (v12 && pre > kMaxSortKeys)
+    return fail(SD_ERR_UNSUPPORTED, "%s: rpn_pre_nms_top_n=%d exceeds %d", name, pre, kMaxSortKeys);
   if (B == 0 || post == 0) return SD_OK;
   SD_REQUIRE(cls_prob && bbox_pred && im_info && out && score, "null tensor pointer");
+  SD_REQUIRE(!(v12 && filter_scales) || valid_ranges, "null valid_ranges");
   SD_REQUIRE(pre <= kMaxSortKeys, "Proposal: rpn_pre_nms_top_n=%d exceeds %d", pre, kMaxSortKeys);
   SD_REQUIRE(((uintptr_t)out & 15) == 0, "out must be 16-byte aligned");
   const int nb = (pre + 63) / 64;
@@ -782,18 +986,32 @@ static int proposal_v3_impl(const float* cls_prob, const float* bbox_pred, const
   off += align_up(counters_bytes, 256);
   a.gcand = reinterpret_cast<unsigned long long*>(base + off);
   off += align_up((size_t)B * P2 * 8, 256);
+  if (v12) {
+    a.gtie = reinterpret_cast<int*>(base + off);  // B x G x 256 last-digit counts
+    off += align_up((size_t)B * topk_groups(count) * 1024, 256);
+  }
   const size_t need = off + (size_t)(base - (char*)workspace);
   if (!workspace || workspace_bytes < need)
-    return fail(SD_ERR_WORKSPACE, "Proposal workspace too small: %zu < %zu bytes", workspace_bytes,
+    return fail(SD_ERR_WORKSPACE, "%s workspace too small: %zu < %zu bytes", name, workspace_bytes,
                 need);
-  proposal_v3_anchors(feature_stride, scales_host, n_scales, ratios_host, n_ratios, a.anchors);
+  if (v12)
+    proposal_v12_anchors(feature_stride, scales_host, n_scales, ratios_host, n_ratios, a.anchors);
+  else
+    proposal_v3_anchors(feature_stride, scales_host, n_scales, ratios_host, n_ratios, a.anchors);
   a.cls_prob = cls_prob; a.bbox_pred = bbox_pred; a.im_info = im_info;
   a.A = A; a.H = H; a.W = W; a.stride = feature_stride; a.count = count; a.pre = pre;
   a.min_size = (float)rpn_min_size;
+  a.rpn_min_size = rpn_min_size;
   a.iou_loss = iou_loss ? 1 : 0;
+  a.v12 = v12 ? 1 : 0;
+  a.filter_scales = (version == 2 && filter_scales) ? 1 : 0;
+  a.valid_ranges = valid_ranges;
   a.P2 = P2;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(proposal_decode_kernel, dim3((count + 255) / 256, B), dim3(256), 0, st, a);
+  if (v12)
+    hipLaunchKernelGGL(proposal_v12_decode_kernel, dim3((count + 255) / 256, B), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(proposal_decode_kernel, dim3((count + 255) / 256, B), dim3(256), 0, st, a);
   SD_LAUNCH_CHECK();
   const size_t lds = (size_t)P2 * sizeof(unsigned long long);
   // levels with many anchors: the select is spread over G workgroups per image (6 short launches);
@@ -801,13 +1019,12 @@ static int proposal_v3_impl(const float* cls_prob, const float* bbox_pred, const
   const int mode = tuning("proposal_topk", 0);
   const bool multi = mode == 2 || (mode != 1 && count >= 32768);
   if (multi) {
-    int G = (count + 2047) / 2048;  // one 8 x 256 trip per workgroup
-    if (G > 128) G = 128;
-    a.G = G;
-    SD_HIP_CHECK(hipMemsetAsync(a.ghist, 0, counters_bytes, st));
+    a.G = topk_groups(count);
+    const int nctr = (int)(counters_bytes / 4);
+    hipLaunchKernelGGL(topk_zero_kernel, dim3((nctr + 255) / 256), dim3(256), 0, st, a.ghist, nctr);
     for (int pass = 0; pass < 4; ++pass)
-      hipLaunchKernelGGL(topk_hist_kernel, dim3(G, B), dim3(256), 0, st, a, pass);
-    hipLaunchKernelGGL(topk_compact_kernel, dim3(G, B), dim3(256), 0, st, a);
+      hipLaunchKernelGGL(topk_hist_kernel, dim3(a.G, B), dim3(256), 0, st, a, pass);
+    hipLaunchKernelGGL(topk_compact_kernel, dim3(a.G, B), dim3(256), 0, st, a);
     if (lds > 64 * 1024)
       SD_HIP_CHECK(hipFuncSetAttribute((const void*)topk_finish_kernel,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -819,10 +1036,13 @@ static int proposal_v3_impl(const float* cls_prob, const float* bbox_pred, const
     hipLaunchKernelGGL(proposal_topk_kernel, dim3(B), dim3(1024), lds, st, a);
   }
   SD_LAUNCH_CHECK();
-  MaskArgs ma{a.ws, pre, nb, nb * (nb + 1) / 2, threshold, 1};  // IoU >= threshold (:319)
+  // IoU >= threshold for v3 (proposal_v3.cu:319), > for v1 / v2 (proposal_v2.cu:306)
+  MaskArgs ma{a.ws, pre, nb, nb * (nb + 1) / 2, threshold, v12 ? 0 : 1};
   hipLaunchKernelGGL(nms_mask_kernel, dim3((ma.npairs + 3) / 4, B), dim3(256), 0, st, ma);
   SD_LAUNCH_CHECK();
-  ScanArgs ca{a.ws, out, score, nullptr, pre, post, nb, is_train ? 1 : 0};
+  // padding: v3 and v1 repeat the kept boxes when is_train, v2 always zero pads (:374-397)
+  const int cyclic = (version != 2 && is_train) ? 1 : 0;
+  ScanArgs ca{a.ws, out, score, nullptr, pre, post, nb, cyclic};
   hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(64), 0, st, ca);
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -871,10 +1091,10 @@ extern "C" int sd_proposal_v3(const float* cls_prob, const float* bbox_pred, con
                               int rpn_min_size, const float* scales_host, int n_scales,
                               const float* ratios_host, int n_ratios, int feature_stride,
                               int is_train, void* workspace, size_t workspace_bytes, void* stream) {
-  return proposal_v3_impl(cls_prob, bbox_pred, im_info, out, score, B, A, H, W, rpn_pre_nms_top_n,
-                          rpn_post_nms_top_n, threshold, rpn_min_size, scales_host, n_scales,
-                          ratios_host, n_ratios, feature_stride, is_train, 0, workspace,
-                          workspace_bytes, stream);
+  return proposal_impl(3, cls_prob, bbox_pred, im_info, nullptr, out, score, B, A, H, W,
+                       rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales_host,
+                       n_scales, ratios_host, n_ratios, feature_stride, is_train, 0, 0, workspace,
+                       workspace_bytes, stream);
 }
 
 extern "C" int sd_proposal_v3_iou(const float* cls_prob, const float* bbox_pred,
@@ -884,10 +1104,36 @@ extern "C" int sd_proposal_v3_iou(const float* cls_prob, const float* bbox_pred,
                                   int n_scales, const float* ratios_host, int n_ratios,
                                   int feature_stride, int is_train, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  return proposal_v3_impl(cls_prob, bbox_pred, im_info, out, score, B, A, H, W, rpn_pre_nms_top_n,
-                          rpn_post_nms_top_n, threshold, rpn_min_size, scales_host, n_scales,
-                          ratios_host, n_ratios, feature_stride, is_train, 1, workspace,
-                          workspace_bytes, stream);
+  return proposal_impl(3, cls_prob, bbox_pred, im_info, nullptr, out, score, B, A, H, W,
+                       rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales_host,
+                       n_scales, ratios_host, n_ratios, feature_stride, is_train, 0, 1, workspace,
+                       workspace_bytes, stream);
+}
+
+extern "C" int sd_proposal_v2(const float* cls_prob, const float* bbox_pred, const float* im_info,
+                              const float* valid_ranges, float* out, float* score, int B, int A,
+                              int H, int W, int rpn_pre_nms_top_n, int rpn_post_nms_top_n,
+                              float threshold, int rpn_min_size, const float* scales_host,
+                              int n_scales, const float* ratios_host, int n_ratios,
+                              int feature_stride, int filter_scales, int iou_loss, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  return proposal_impl(2, cls_prob, bbox_pred, im_info, valid_ranges, out, score, B, A, H, W,
+                       rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales_host,
+                       n_scales, ratios_host, n_ratios, feature_stride, 0, filter_scales, iou_loss,
+                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int sd_proposal(const float* cls_prob, const float* bbox_pred, const float* im_info,
+                           float* out, float* score, int B, int A, int H, int W,
+                           int rpn_pre_nms_top_n, int rpn_post_nms_top_n, float threshold,
+                           int rpn_min_size, const float* scales_host, int n_scales,
+                           const float* ratios_host, int n_ratios, int feature_stride,
+                           int is_train, int iou_loss, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  return proposal_impl(1, cls_prob, bbox_pred, im_info, nullptr, out, score, B, A, H, W,
+                       rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales_host,
+                       n_scales, ratios_host, n_ratios, feature_stride, is_train, 0, iou_loss,
+                       workspace, workspace_bytes, stream);
 }
 
 extern "C" int sd_get_top_proposal(const float* bbox, const float* score, int B, int N, int top_n,

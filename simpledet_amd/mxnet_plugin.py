@@ -1044,6 +1044,101 @@ def _build_ops(mx):
 
     ops["_contrib_Proposal_v3"] = (ProposalV3Prop, ("contrib", "Proposal_v3"))
 
+    # ---- _contrib_Proposal_v2 (cls_prob, bbox_pred, im_info, valid_ranges) and _contrib_Proposal
+    #      (cls_prob, bbox_pred, im_info) -> output [, score]  (registered only by install(...,
+    #      proposal=True)) ----
+    class ProposalV12(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            g = self.g
+            cls_prob, bbox_pred, im_info = in_data[:3]
+            B, A2, H, W = cls_prob.shape
+            A = A2 // 2
+            fn = "sd_proposal_v2" if g["v2"] else "sd_proposal"
+            getattr(lib().cdll, fn + "_workspace_bytes").restype = ctypes.c_size_t
+            wsb = getattr(lib().cdll, fn + "_workspace_bytes")(B, A, H, W, g["pre"])
+            ws = _scratch(cls_prob, wsb)
+            fa = lambda v: (ctypes.c_float * len(v))(*v)
+            common = (B, A, H, W, g["pre"], g["post"], float(g["thr"]), g["min_size"], fa(g["scales"]),
+                      len(g["scales"]), fa(g["ratios"]), len(g["ratios"]), g["stride"])
+            if g["v2"]:
+                _call(fn, _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(in_data[3]),
+                      _ptr(out_data[0]), _ptr(out_data[1]), *common, int(g["filter_scales"]),
+                      int(g["iou_loss"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            else:
+                _call(fn, _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(out_data[0]),
+                      _ptr(out_data[1]), *common, int(g["is_train"]), int(g["iou_loss"]), _ptr(ws),
+                      ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(in_grad)):  # proposal_v2.cu:617-639, proposal.cu: all zeros
+                self.assign(in_grad[i], req[i], 0)
+
+    class _ProposalV12Prop(CustomOpProp):
+        V2 = True
+
+        def _init(self, rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                  feature_stride, output_score, iou_loss, is_train="False", filter_scales="False"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(pre=int(rpn_pre_nms_top_n), post=int(rpn_post_nms_top_n), thr=float(threshold),
+                          min_size=int(rpn_min_size), scales=_tuple(scales), ratios=_tuple(ratios),
+                          stride=int(feature_stride), iou_loss=_bool(iou_loss), is_train=_bool(is_train),
+                          filter_scales=_bool(filter_scales), v2=self.V2)
+            self.num_visible_outputs = 2 if _bool(output_score) else 1
+
+        def list_arguments(self):
+            return ["cls_prob", "bbox_pred", "im_info"] + (["valid_ranges"] if self.V2 else [])
+
+        def list_outputs(self):
+            return ["output", "score"]
+
+        def infer_shape(self, in_shape):
+            # ProposalProp(_v2)::InferShape (proposal_v2-inl.h:199-220, proposal-inl.h:199-217)
+            d = in_shape[0]
+            if len(d) != 4:
+                raise ValueError("cls_prob should be (batch, 2 * num_anchors, H, W)")
+            g = self.g
+            A = d[1] // 2
+            if A != len(g["scales"]) * len(g["ratios"]):
+                raise ValueError("num_anchors != len(ratios) * len(scales)")
+            ins = [d, (d[0], 4 * A, d[2], d[3]), (d[0], 3)] + ([(d[0], 2)] if self.V2 else [])
+            return ins, [(d[0], g["post"], 4), (d[0], g["post"], 1)]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return ProposalV12(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    class ProposalV2Prop(_ProposalV12Prop):
+        V2 = True
+
+        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
+                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16",
+                     output_score="False", iou_loss="False", workspace="256", filter_scales="False"):
+            # defaults: proposal_v2-inl.h:141-183
+            self._init(rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                       feature_stride, output_score, iou_loss, filter_scales=filter_scales)
+
+    class ProposalV1Prop(_ProposalV12Prop):
+        V2 = False
+
+        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
+                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16",
+                     output_score="False", iou_loss="False", workspace="256", is_train="False"):
+            # defaults: proposal-inl.h:141-183
+            self._init(rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                       feature_stride, output_score, iou_loss, is_train=is_train)
+
+    ops["_contrib_Proposal_v2"] = (ProposalV2Prop, ("contrib", "Proposal_v2"))
+    ops["_contrib_Proposal"] = (ProposalV1Prop, ("contrib", "Proposal"))
+
     # ---- _contrib_GenProposalRetina: cls_prob, bbox_pred, im_info, anchors -> output, scores ----
     #      (registered only by install(..., retina=True))
     class GenProposalRetina(CustomOp):
@@ -1237,9 +1332,10 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None, retina=False):
+def register(mx=None, retina=False, proposal=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
-    retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs)."""
+    retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
+    proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -1247,6 +1343,9 @@ def register(mx=None, retina=False):
     table = _build_ops(mx)
     if not retina:
         table.pop("_contrib_GenProposalRetina")
+    if not proposal:
+        table.pop("_contrib_Proposal_v2")
+        table.pop("_contrib_Proposal")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1275,7 +1374,7 @@ def _namespaces(mx, ns):
     return out
 
 
-def install(mx=None, stream=None, sync=True, retina=False):
+def install(mx=None, stream=None, sync=True, retina=False, proposal=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1292,9 +1391,14 @@ def install(mx=None, stream=None, sync=True, retina=False):
 
     `retina=True` also replaces `_contrib_GenProposalRetina` (models/retinanet/builder.py:358-389); it is
     opt-in because it changes which operator existing RetinaNet graphs hold.  iou_loss / batch_wise_anchor
-    calls fall back to the native constructor (sd_supports)."""
-    props = register(mx, retina=retina)
+    calls fall back to the native constructor (sd_supports).
+
+    `proposal=True` also replaces `_contrib_Proposal_v2` (models/tridentnet/builder.py:239-255) and
+    `_contrib_Proposal`, and lets patch_mxnext rebind `X.proposal` when its probe sees `_contrib_Proposal`;
+    opt-in because it changes which operator existing TridentNet / C4 graphs hold."""
+    props = register(mx, retina=retina, proposal=proposal)
     mx = _state["mx"]
+    _state["proposal"] = bool(proposal)
     _state["fallbacks"] = []
     _state["stream"], _state["sync"] = stream, bool(sync)
 
@@ -1391,8 +1495,10 @@ def patch_mxnext(mxnext=None, mx=None):
         `ProposalTarget`, `_contrib_Proposal_v3`, `_contrib_DecodeBBox`): the wrapper captured the
         constructor before install(); it is rebound to a function with the call sites' signature that
         builds the alias;
-      * anything else (`_contrib_Proposal`, `_contrib_Proposal_v2`, `MultiProposal`, a TVM op ...), or a
-        probe that raises: LEFT ALONE -- `proposal.cu`, `proposal_v2.cu` and `proposal_v3.cu` differ in the
+      * with install(proposal=True) only: `_contrib_Proposal` for `X.proposal`, rebound to the
+        `_contrib_Proposal` alias (the same operator, so the numbers do not change);
+      * anything else (`_contrib_Proposal` without the opt-in, `_contrib_Proposal_v2`, `MultiProposal`, a TVM
+        op ...), or a probe that raises: LEFT ALONE -- `proposal.cu`, `proposal_v2.cu` and `proposal_v3.cu` differ in the
         +1 box convention, the dw / dh clamp and the min-size filter, rebinding would change the RPN's
         numbers silently.
     Call sites whose signatures the probes use:
@@ -1426,6 +1532,9 @@ def patch_mxnext(mxnext=None, mx=None):
 
     def proposal(**kw):
         return mx.sym.contrib.Proposal_v3(**kw)
+
+    def proposal_v1(**kw):
+        return mx.sym.contrib.Proposal(**kw)
 
     def decode_bbox(**kw):
         return mx.sym.contrib.DecodeBBox(**kw)
@@ -1462,7 +1571,9 @@ def patch_mxnext(mxnext=None, mx=None):
         if op == "Custom" and str(attrs.get("op_type", "")).startswith(_PREFIX) or str(op).startswith(_PREFIX):
             seen[attr] = "late binding: already builds %s" % (attrs.get("op_type", op),)
             continue
-        if op not in (native, short):
+        if attr == "proposal" and _state.get("proposal") and op in ("_contrib_Proposal", "Proposal"):
+            fn, native = proposal_v1, "_contrib_Proposal"  # install(proposal=True): the same operator
+        elif op not in (native, short):
             seen[attr] = "builds %s, not %s: left alone" % (op, native)
             continue
         seen[attr] = "builds %s at import-time binding: rebound" % (op,)

@@ -930,6 +930,78 @@ def proposal_v3(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_n
     return out, score
 
 
+# --------------------------------------------------------------------------------------------------
+# _contrib_Proposal_v2 (TridentNet) and _contrib_Proposal  (operator_cxx/contrib/proposal_v2.cu,
+# proposal.cu): filters before the top-k, NMS with IoU > threshold
+# --------------------------------------------------------------------------------------------------
+def _proposal_v12_args(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n, rpn_post_nms_top_n):
+    _chk(cls_prob, "cls_prob", ndim=4)
+    _chk(bbox_pred, "bbox_pred", ndim=4)
+    _chk(im_info, "im_info", ndim=2)
+    B, A2, H, W = cls_prob.shape
+    A = A2 // 2
+    if bbox_pred.shape != (B, 4 * A, H, W) or im_info.shape != (B, 3):
+        raise ValueError("bbox_pred must be (B,4A,H,W) and im_info (B,3)")
+    post = int(rpn_post_nms_top_n)
+    out = torch.empty((B, post, 4), device=cls_prob.device, dtype=torch.float32)
+    score = torch.empty((B, post, 1), device=cls_prob.device, dtype=torch.float32)
+    return B, A, H, W, out, score
+
+
+def _proposal_v12_ws(name, B, A, H, W, pre, device, workspace):
+    fn = getattr(lib().cdll, name)
+    fn.restype = ctypes.c_size_t
+    wsb = int(fn(B, A, H, W, int(pre)))
+    if workspace is None:
+        workspace = torch.empty(wsb, device=device, dtype=torch.uint8)
+    elif workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    return workspace
+
+
+def proposal_v2(cls_prob, bbox_pred, im_info, valid_ranges, rpn_pre_nms_top_n=6000,
+                rpn_post_nms_top_n=300, threshold=0.7, rpn_min_size=16, scales=(4., 8., 16., 32.),
+                ratios=(0.5, 1., 2.), feature_stride=16, filter_scales=False, iou_loss=False,
+                workspace=None):
+    """Proposal_v2: cls_prob (B,2A,H,W), bbox_pred (B,4A,H,W), im_info (B,3), valid_ranges (B,2) ->
+    output (B,post,4), score (B,post,1)  (proposal_v2-inl.h:196-220), zero padded.
+    rpn_post_nms_top_n > min(rpn_pre_nms_top_n, A*H*W) is refused (SimpleDetOpsError).
+    workspace: an optional uint8 tensor of at least sd_proposal_v2_workspace_bytes() bytes."""
+    B, A, H, W, out, score = _proposal_v12_args(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n,
+                                                rpn_post_nms_top_n)
+    _chk(valid_ranges, "valid_ranges", ndim=2)
+    if valid_ranges.shape != (B, 2):
+        raise ValueError("valid_ranges must be (B,2)")
+    scales, ratios = list(scales), list(ratios)
+    ws = _proposal_v12_ws("sd_proposal_v2_workspace_bytes", B, A, H, W, rpn_pre_nms_top_n,
+                          cls_prob.device, workspace)
+    lib().call("sd_proposal_v2", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(valid_ranges),
+               _p(out), _p(score), B, A, H, W, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n),
+               float(threshold), int(rpn_min_size), _farr(scales), len(scales), _farr(ratios),
+               len(ratios), int(feature_stride), int(bool(filter_scales)), int(bool(iou_loss)),
+               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return out, score
+
+
+def proposal(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300,
+             threshold=0.7, rpn_min_size=16, scales=(4., 8., 16., 32.), ratios=(0.5, 1., 2.),
+             feature_stride=16, is_train=False, iou_loss=False, workspace=None):
+    """Proposal: cls_prob (B,2A,H,W), bbox_pred (B,4A,H,W), im_info (B,3) -> output (B,post,4),
+    score (B,post,1)  (proposal-inl.h:196-214); padding: the kept boxes repeated when is_train,
+    else zeros.  rpn_post_nms_top_n > min(rpn_pre_nms_top_n, A*H*W) is refused."""
+    B, A, H, W, out, score = _proposal_v12_args(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n,
+                                                rpn_post_nms_top_n)
+    scales, ratios = list(scales), list(ratios)
+    ws = _proposal_v12_ws("sd_proposal_workspace_bytes", B, A, H, W, rpn_pre_nms_top_n,
+                          cls_prob.device, workspace)
+    lib().call("sd_proposal", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(out), _p(score), B, A,
+               H, W, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n), float(threshold),
+               int(rpn_min_size), _farr(scales), len(scales), _farr(ratios), len(ratios),
+               int(feature_stride), int(bool(is_train)), int(bool(iou_loss)), _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return out, score
+
+
 def get_top_proposal(bbox, score, top_n):
     """get_top_proposal CustomOp: bbox (B,N,4), score (B,N,1) -> (B,top_n,4), (B,top_n,1)."""
     _chk(bbox, "bbox", ndim=3)
