@@ -57,9 +57,10 @@ const char* sd_last_dispatch(void);
  * (same signature, documented error model), sd_proposal_mask_target_ratio / sd_cast_* / *_f16 added;
  * 5 sd_gemm_f32_ws, the DCN products default to the scaled fp16 split (fp32-path accuracy), plain
  * sd_gemm_f32 to exact fp32; 8 sd_proposal and sd_proposal_v2 added (the existing entry points and
- * their workspace sizes are unchanged).
+ * their workspace sizes are unchanged); 9 sd_hard_nms_batched and sd_bbox_post_processing added (nothing
+ * existing changes).
  * sd_abi_version() returns the library's value; compare with this macro. */
-#define SD_ABI_VERSION 8
+#define SD_ABI_VERSION 9
 int sd_abi_version(void);
 /* kernel-variant knobs for A/B measurements (bench.py, tests); every variant computes the same
  * result.  Unknown keys are an error.  Knobs that disable parts of a kernel for profiling exist
@@ -662,6 +663,49 @@ int sd_decode_bbox(const float* rois, const float* bbox_pred, const float* im_in
  * bbox_classes = K (class specific boxes) or 1 (shared box). */
 int sd_det_filter(const float* bbox, const float* cls_score, int B, int R, int K, int bbox_classes,
                   float min_det_score, float* dets, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * nms (numpy), batched  (operator_py/nms.py:41-75 through py_nms_wrapper :19-22 -- the default
+ *   test-time NMS, detection_test.py:224-267, and the one BboxPostProcessing runs)
+ *   dets (P,Nmax,5) [x1,y1,x2,y2,score]: problem p uses rows [0, counts[p]) (counts NULL: all Nmax)
+ *   -- the layout sd_det_filter writes.  Every operation is a float32 operation, as numpy's:
+ *   area = (x2-x1+1)*(y2-y1+1), w = max(0, xx2-xx1+1), ovr = w*h / (area_i + area_j - w*h); box j
+ *   survives a kept box i iff ovr <= thresh (float32), so a NaN ovr suppresses.  NOT
+ *   sd_soft_nms_batched(method 0), which adds 1 in double (cpu_nms.pyx) and selects by arg-max.
+ *   Order: descending score; among EQUAL scores the LATER input row first (argsort(kind="stable")[::-1];
+ *   the reference's own order of ties is numpy's unstable sort).  sd_nms keeps the LOWER row first.
+ *   NaN scores come before every number (numpy sorts them last, the reversal first).
+ *   out_dets (P,Nmax,5) / out_inds (P,Nmax): the kept rows (copies of the input's floats) and their
+ *   input rows, in that order; out_counts (P).  Rows past out_counts[p] are unspecified (not written).
+ *   SD_ERR_UNSUPPORTED: Nmax > 4096 (a problem is sorted and resolved in LDS).
+ * ---------------------------------------------------------------------------------------------- */
+int sd_hard_nms_batched(const float* dets, const int32_t* counts, int P, int Nmax, float thresh,
+                        float* out_dets, int32_t* out_inds, int32_t* out_counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * BboxPostProcessing CustomOp  (models/maskrcnn/bbox_post_processing.py:6-111, emitted by
+ *   models/maskrcnn/builder.py:65-84 between DecodeBBox and the mask head's RoIAlign)
+ *   replaces BboxPostProcessingOperator.forward :43-72 (asnumpy of both inputs, a Python loop over the
+ *   classes around the numpy nms above, argsort, three copies back) and multiclass_nms :6-32
+ *   cls_score (B,R,K), column 0 = background (dropped); bbox_xyxy (B,R,4*bbox_classes), bbox_classes
+ *   = 1 (shared box) or K (class c's box in columns 4c..4c+3, background's unused).
+ *   Per image and foreground class: the rows with score > min_det_score (NaN fails) in row order,
+ *   hard NMS as sd_hard_nms_batched; classes stacked in class order; the max_det_per_image best by
+ *   score, descending, among equal scores the LATER entry of the stacked list first.
+ *   post_score (B,max_det,1) zero padded, post_bbox (B,max_det,4) zero padded, post_cls (B,max_det,1)
+ *   = class id after dropping the background (0-based) as a float, padded with -1.  Every element of
+ *   the three outputs is written by every call.  Backward is all zeros (:74-76) and has no entry point.
+ *   Two launches on `stream` (per-class NMS, image top-k), no host synchronisation, capturable.
+ *   The (B*K,R,5) tensor of sd_det_filter is never formed: the kept rows' keys go to the workspace
+ *   (sd_bbox_post_processing_workspace_bytes, 8-byte aligned).
+ *   SD_ERR_UNSUPPORTED: R > 4096, K > 256, max_det_per_image > 1024, bbox_classes not in {1, K}.
+ *   B = 0, R = 0, K = 1 and "no row over the threshold" are valid and produce the padding.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_bbox_post_processing_workspace_bytes(int B, int R, int K, int bbox_classes, int max_det_per_image);
+int sd_bbox_post_processing(const float* cls_score, const float* bbox_xyxy, int B, int R, int K,
+                            int bbox_classes, float min_det_score, float nms_thr, int max_det_per_image,
+                            float* post_score, float* post_bbox, float* post_cls, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_GenProposalRetina  (mx.sym.contrib.GenProposalRetina, models/retinanet/builder.py:358-389)

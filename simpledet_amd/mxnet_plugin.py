@@ -1328,14 +1328,96 @@ def _build_ops(mx):
             return []
 
     ops["_contrib_DecodeBBox"] = (DecodeBBoxProp, ("contrib", "DecodeBBox"))
+
+    # ---- BboxPostProcessing (models/maskrcnn/bbox_post_processing.py:35-111): cls_score, bbox_xyxy ->
+    # post_score, post_bbox_xyxy, post_cls.  The reference's is itself a Python CustomOp reached through
+    # mx.sym.Custom, so there is no constructor to alias: patch_bbox_post rebinds the builder method ----
+    class BboxPostProcessing(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _require_write(req[:3], ["post_score", "post_bbox_xyxy", "post_cls"])
+            score, bbox = in_data
+            _wait(score, bbox)
+            g = self.g
+            B, R, K = score.shape
+            Kb = bbox.shape[2] // 4
+            wsb = lib().cdll.sd_bbox_post_processing_workspace_bytes(B, R, K, Kb, g["max_det"])
+            ws = _scratch(score, wsb)
+            _call("sd_bbox_post_processing", _ptr(score), _ptr(bbox), B, R, K, Kb, g["min_score"], g["thr"],
+                  g["max_det"], _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), _ptr(ws),
+                  ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            self.assign(in_grad[0], req[0], 0)
+            self.assign(in_grad[1], req[1], 0)
+
+    class BboxPostProcessingProp(CustomOpProp):
+        LIMITS = dict(rows=4096, classes=256, max_det=1024)
+
+        def __init__(self, max_det_per_image, min_det_score, nms_type, nms_thr):
+            super().__init__(need_top_grad=False)
+            # parsed as BboxPostProcessingProp.__init__ does (bbox_post_processing.py:81-86)
+            self.g = dict(max_det=int(max_det_per_image), min_score=float(min_det_score),
+                          nms_type=str(nms_type), thr=float(nms_thr))
+            if self.g["nms_type"] != "nms":
+                raise NotImplementedError("BboxPostProcessing: nms_type %r (the reference takes 'nms' only)"
+                                          % self.g["nms_type"])
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (patch_bbox_post then hands the
+            call back to the reference's method)."""
+            try:
+                top = int(params["max_det_per_image"])
+                float(params["min_det_score"])
+                float(params["nms_thr"])
+            except Exception as e:
+                return "unparsable parameter (%s)" % e
+            if str(params.get("nms_type")) != "nms":
+                return "nms_type %r is not 'nms'" % (params.get("nms_type"),)
+            if not 0 <= top <= cls.LIMITS["max_det"]:
+                return "max_det_per_image=%d outside 0..%d" % (top, cls.LIMITS["max_det"])
+            return ""
+
+        def list_arguments(self):
+            return ["cls_score", "bbox_xyxy"]
+
+        def list_outputs(self):
+            return ["post_score", "post_bbox_xyxy", "post_cls"]
+
+        def infer_shape(self, in_shape):
+            s, b = in_shape[0], in_shape[1]
+            if len(s) != 3 or len(b) != 3:
+                raise ValueError("cls_score should be (batch, rois, classes), bbox_xyxy (batch, rois, 4 or 4 * classes)")
+            if s[1] > self.LIMITS["rows"] or s[2] > self.LIMITS["classes"] or b[2] not in (4, 4 * s[2]):
+                raise ValueError("BboxPostProcessing: cls_score %s / bbox_xyxy %s outside rois <= %d, classes <= %d, "
+                                 "boxes (.,.,4) or (.,.,4 * classes)" % (tuple(s), tuple(b), self.LIMITS["rows"],
+                                                                         self.LIMITS["classes"]))
+            top = self.g["max_det"]
+            return [s, b], [(s[0], top, 1), (s[0], top, 4), (s[0], top, 1)]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return BboxPostProcessing(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    ops["BboxPostProcessing"] = (BboxPostProcessingProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None, retina=False, proposal=False):
+def register(mx=None, retina=False, proposal=False, bbox_post=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
-    proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason)."""
+    proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
+    bbox_post: also BboxPostProcessing (opt-in: it replaces the reference's own CustomOp of Mask R-CNN's
+    test graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -1346,6 +1428,8 @@ def register(mx=None, retina=False, proposal=False):
     if not proposal:
         table.pop("_contrib_Proposal_v2")
         table.pop("_contrib_Proposal")
+    if not bbox_post:
+        table.pop("BboxPostProcessing")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1374,7 +1458,7 @@ def _namespaces(mx, ns):
     return out
 
 
-def install(mx=None, stream=None, sync=True, retina=False, proposal=False):
+def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1395,8 +1479,14 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False):
 
     `proposal=True` also replaces `_contrib_Proposal_v2` (models/tridentnet/builder.py:239-255) and
     `_contrib_Proposal`, and lets patch_mxnext rebind `X.proposal` when its probe sees `_contrib_Proposal`;
-    opt-in because it changes which operator existing TridentNet / C4 graphs hold."""
-    props = register(mx, retina=retina, proposal=proposal)
+    opt-in because it changes which operator existing TridentNet / C4 graphs hold.
+
+    `bbox_post=True` also registers `sd_BboxPostProcessing` and rebinds
+    `models.maskrcnn.builder.BboxPostProcessor.get_post_processing` (patch_bbox_post) so that Mask R-CNN test
+    graphs hold it in place of the reference's numpy CustomOp; opt-in because it changes which operator those
+    graphs hold.  A `nms.type` other than "nms" or a max_det_per_image outside the kernels' limits falls back
+    to the reference's method and is listed in `_state["fallbacks"]`."""
+    props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["fallbacks"] = []
@@ -1463,7 +1553,72 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False):
     # ... and the mxnext wrappers the reference's builders go through, explicitly (not relying on
     # mxnext looking `mx.sym.*` up at call time)
     _state["mxnext_patched"] = patch_mxnext(mx=mx)
+    if bbox_post:
+        _state["bbox_post_patched"] = patch_bbox_post(mx=mx)
+    else:   # a default install() after an opt-in one builds the reference's node again
+        import sys
+        for m in _BBOX_POST_BUILDERS:
+            if sys.modules.get(m) is not None:
+                unpatch_bbox_post(sys.modules[m])
+        _state["bbox_post_patched"] = False
     return props
+
+
+# models/maskrcnn/builder.py:65-84 and the copy of the class in models/msrcnn/builder.py:170-189
+_BBOX_POST_BUILDERS = ("models.maskrcnn.builder", "models.msrcnn.builder")
+
+
+def patch_bbox_post(builder_module=None, mx=None):
+    """Route Mask R-CNN's test-time post-processing to the device op WITHOUT editing the reference: rebinds
+    `BboxPostProcessor.get_post_processing` of models/maskrcnn/builder.py:69-84 (and of its copy in
+    models/msrcnn/builder.py:174-189), which emits mx.sym.Custom(op_type='BboxPostProcessing'), to a method that
+    emits mx.sym.Custom(op_type='sd_BboxPostProcessing') over the same inputs with the same four parameters and
+    returns the same three symbols.  install(bbox_post=True) calls this for the builder modules that are
+    importable; returns True when a class was patched.  The original method is kept as
+    `_sd_reference_get_post_processing` (a second install() keeps the first original) and is what a call the
+    kernels do not take goes back to."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        done = False
+        for name in _BBOX_POST_BUILDERS:
+            try:
+                done = patch_bbox_post(importlib.import_module(name), mx) or done
+            except Exception:
+                pass
+        return done
+    cls = getattr(builder_module, "BboxPostProcessor", None)
+    if cls is None:
+        return False
+    original = cls.__dict__.get("_sd_reference_get_post_processing") or cls.get_post_processing
+
+    def get_post_processing(self, cls_score, bbox_xyxy):
+        p = self.p
+        params = {"max_det_per_image": _param_str(p.max_det_per_image),
+                  "min_det_score": _param_str(p.min_det_score), "nms_type": _param_str(p.nms.type),
+                  "nms_thr": _param_str(p.nms.thr)}
+        prop = (_state.get("table") or {}).get("BboxPostProcessing")
+        why = prop[0].sd_supports(params) if prop else "sd_BboxPostProcessing is not registered"
+        if why:
+            _state.setdefault("fallbacks", []).append(("BboxPostProcessing", None, why))
+            return original(self, cls_score, bbox_xyxy)
+        sym = mx.sym.Custom(cls_score=cls_score, bbox_xyxy=bbox_xyxy, op_type=_PREFIX + "BboxPostProcessing",
+                            **params)
+        return sym[0], sym[1], sym[2]
+
+    cls._sd_reference_get_post_processing = original
+    cls.get_post_processing = get_post_processing
+    return True
+
+
+def unpatch_bbox_post(builder_module):
+    """Put the reference's get_post_processing back."""
+    cls = getattr(builder_module, "BboxPostProcessor", None)
+    original = cls.__dict__.get("_sd_reference_get_post_processing") if cls is not None else None
+    if original is None:
+        return False
+    cls.get_post_processing = original
+    return True
 
 
 def _head_op(mx, sym):

@@ -1100,3 +1100,105 @@ def det_filter(bbox_xyxy, cls_score, min_det_score):
     lib().call("sd_det_filter", _p(bbox_xyxy), _p(cls_score), B, R, K, Kb, float(min_det_score),
                _p(dets), _p(counts), _stream())
     return dets, counts
+
+
+# --------------------------------------------------------------------------------------------------
+# numpy nms, batched, and the BboxPostProcessing CustomOp of Mask R-CNN's test graph
+# (operator_py/nms.py:41-75, models/maskrcnn/bbox_post_processing.py:6-111)
+# --------------------------------------------------------------------------------------------------
+def hard_nms_batched(dets, counts=None, thresh=0.5):
+    """nms (operator_py/nms.py:41-75, float32 numpy arithmetic, keeps ovr <= thresh) on P problems at
+    once: dets (P,Nmax,5), counts (P) int32 -> out_dets (P,Nmax,5), out_inds (P,Nmax) int32 (input
+    rows), out_counts (P) int32; rows past the count are unspecified.  Equal scores: the later input
+    row first.  The layout is det_filter's, so do_nms of detection_test.py is
+    hard_nms_batched(*det_filter(boxes, scores, min_det_score), thresh)."""
+    _chk(dets, "dets", ndim=3)
+    if dets.shape[2] != 5:
+        raise ValueError("dets should be (problems, boxes, 5)")
+    P, Nmax, _ = dets.shape
+    if counts is not None:
+        _chk(counts, "counts", dtype=torch.int32, ndim=1)
+        if counts.shape[0] != P:
+            raise ValueError("counts should have one entry per problem")
+    od = torch.empty_like(dets)
+    oi = torch.empty((P, Nmax), device=dets.device, dtype=torch.int32)
+    oc = torch.empty((P,), device=dets.device, dtype=torch.int32)
+    lib().call("sd_hard_nms_batched", _p(dets), _p(counts), P, Nmax, float(thresh), _p(od), _p(oi),
+               _p(oc), _stream())
+    return od, oi, oc
+
+
+def multiclass_nms(cls_score, bbox_xyxy, min_det_score=0.05, nms_thr=0.5, skip_background=False):
+    """The per-class kept lists of multiclass_nms / do_nms before the image top-k: det_filter ->
+    hard_nms_batched.  cls_score (B,R,K), bbox_xyxy (B,R,4) or (B,R,4K) -> out_dets (B,K',R,5),
+    out_inds (B,K',R) int32 (rows of the image), out_counts (B,K') int32.  detection_test.py:233-267
+    treats every column as a class (K' = K); skip_background drops column 0 as
+    bbox_post_processing.py:8-10 does (K' = K - 1, views of the same buffers)."""
+    dets, counts = det_filter(bbox_xyxy, cls_score, min_det_score)
+    B, R, K = cls_score.shape
+    od, oi, oc = hard_nms_batched(dets, counts, nms_thr)
+    od, oi, oc = od.view(B, K, R, 5), oi.view(B, K, R), oc.view(B, K)
+    if skip_background:
+        od, oi, oc = od[:, 1:], oi[:, 1:], oc[:, 1:]
+    return od, oi, oc
+
+
+def bbox_post_processing_workspace_bytes(B, R, K, bbox_classes, max_det_per_image):
+    return int(lib().cdll.sd_bbox_post_processing_workspace_bytes(B, R, K, bbox_classes,
+                                                                  int(max_det_per_image)))
+
+
+def bbox_post_processing(cls_score, bbox_xyxy, max_det_per_image=100, min_det_score=0.05, nms_thr=0.5,
+                         workspace=None, out=None):
+    """BboxPostProcessing (models/maskrcnn/bbox_post_processing.py:43-72): cls_score (B,R,K) with the
+    background in column 0, bbox_xyxy (B,R,4) or (B,R,4K) -> post_score (B,max_det,1),
+    post_bbox_xyxy (B,max_det,4) (zero padded), post_cls (B,max_det,1) (-1 padded).
+    workspace: an optional uint8 tensor of at least bbox_post_processing_workspace_bytes() bytes;
+    out: optional (post_score, post_bbox_xyxy, post_cls) to write into."""
+    _chk(cls_score, "cls_score", ndim=3)
+    _chk(bbox_xyxy, "bbox_xyxy", ndim=3)
+    B, R, K = cls_score.shape
+    if bbox_xyxy.shape[0] != B or bbox_xyxy.shape[1] != R or bbox_xyxy.shape[2] % 4:
+        raise ValueError("bbox_xyxy must be (B,R,4) or (B,R,4K), got %s" % (tuple(bbox_xyxy.shape),))
+    Kb = bbox_xyxy.shape[2] // 4
+    top = int(max_det_per_image)
+    if out is None:
+        out = (torch.empty((B, top, 1), device=cls_score.device, dtype=torch.float32),
+               torch.empty((B, top, 4), device=cls_score.device, dtype=torch.float32),
+               torch.empty((B, top, 1), device=cls_score.device, dtype=torch.float32))
+    ps, pb, pc = out
+    for t, name, last in ((ps, "post_score", 1), (pb, "post_bbox_xyxy", 4), (pc, "post_cls", 1)):
+        _chk(t, name, ndim=3)
+        if tuple(t.shape) != (B, top, last):
+            raise ValueError("%s must be %s" % (name, (B, top, last)))
+    wsb = bbox_post_processing_workspace_bytes(B, R, K, Kb, top) if K >= 1 and Kb in (1, K) else 16
+    if workspace is None:
+        workspace = torch.empty(wsb, device=cls_score.device, dtype=torch.uint8)
+    elif workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    lib().call("sd_bbox_post_processing", _p(cls_score), _p(bbox_xyxy), B, R, K, Kb,
+               float(min_det_score), float(nms_thr), top, _p(ps), _p(pb), _p(pc), _p(workspace),
+               ctypes.c_size_t(workspace.numel()), _stream())
+    return ps, pb, pc
+
+
+def maskrcnn_test_chain(feats, rois, cls_score, bbox_pred, im_info, rcnn_stride, max_det_per_image=100,
+                        min_det_score=0.05, nms_thr=0.5, bbox_mean=(0., 0., 0., 0.),
+                        bbox_std=(.1, .1, .2, .2), class_agnostic=False, roi_canonical_scale=224,
+                        roi_canonical_level=4):
+    """The device side of MaskFasterRcnn.get_test_symbol (models/maskrcnn/builder.py:41-58) around the
+    caller's heads: fused FPN RoIAlign 7x7 of `rois` -> [bbox head: cls_score (B,R,K), bbox_pred
+    (B,R,4K) are the caller's] -> decode_bbox -> bbox_post_processing -> fused FPN RoIAlign 14x14 on
+    post_bbox_xyxy.  No host synchronisation: capturable as one HIP graph.
+    Returns (roi_feat (B,R,C,7,7), bbox_xyxy, post_score, post_bbox_xyxy, post_cls,
+    mask_roi_feat (B,max_det,C,14,14)).  A padded row of post_bbox_xyxy is the box (0,0,0,0), an
+    ordinary RoI to the extractor as it is to the reference's: it is assigned a pyramid level like any
+    other tiny box and its 14x14 feature is whatever RoIAlign pools at the image's origin (NOT zeros);
+    callers tell padding by post_cls == -1."""
+    roi_feat, _ = fpn_roi_align_forward_packed(feats, rois, rcnn_stride, (7, 7), roi_canonical_scale,
+                                               roi_canonical_level)
+    boxes = decode_bbox(rois, bbox_pred, im_info, bbox_mean, bbox_std, class_agnostic=class_agnostic)
+    ps, pb, pc = bbox_post_processing(cls_score, boxes, max_det_per_image, min_det_score, nms_thr)
+    mask_feat, _ = fpn_roi_align_forward_packed(feats, pb, rcnn_stride, (14, 14), roi_canonical_scale,
+                                                roi_canonical_level)
+    return roi_feat, boxes, ps, pb, pc, mask_feat
