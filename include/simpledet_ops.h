@@ -58,9 +58,10 @@ const char* sd_last_dispatch(void);
  * 5 sd_gemm_f32_ws, the DCN products default to the scaled fp16 split (fp32-path accuracy), plain
  * sd_gemm_f32 to exact fp32; 8 sd_proposal and sd_proposal_v2 added (the existing entry points and
  * their workspace sizes are unchanged); 9 sd_hard_nms_batched and sd_bbox_post_processing added (nothing
- * existing changes).
+ * existing changes); 10 sd_retina_anchor_target, sd_focal_loss_fwd / _bwd and sd_bbox_norm_bwd with their
+ * workspace queries added (nothing existing changes).
  * sd_abi_version() returns the library's value; compare with this macro. */
-#define SD_ABI_VERSION 9
+#define SD_ABI_VERSION 10
 int sd_abi_version(void);
 /* kernel-variant knobs for A/B measurements (bench.py, tests); every variant computes the same
  * result.  Unknown keys are an error.  Knobs that disable parts of a kernel for profiling exist
@@ -733,6 +734,75 @@ int sd_gen_proposal_retina(const float* cls_prob, const float* bbox_pred, const 
                            float thresh, const float* mean_host, const float* std_host, int iou_loss,
                            int output_one_hot, int batch_wise_anchor, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * RetinaNet anchor targets  (the loader's PyramidAnchorTarget2D of models/retinanet/input.py:33-199,
+ *   over AnchorTarget2D core/detection_input.py:345-565; call site RetinaNetHead.get_loss
+ *   models/retinanet/builder.py:239-339).  A different assignment from sd_rpn_anchor_target: labels
+ *   are class-valued, nothing is subsampled (no generator state; image_anchor / pos_fraction of the
+ *   parameter are ignored), every valid anchor gets a regression target, and there is a per-image
+ *   foreground count.
+ *   im_info (B,3) DEVICE; gt_bbox (B,M,5) DEVICE [x1,y1,x2,y2,class], rows with x1 == -1 padding.
+ *   Labels (:42-66): -1; a valid anchor with max_overlap < neg_thr -> 0; every anchor i for which
+ *   some gt j has overlap[i,j] == gt_max[j] and overlap[i,j] >= min_pos_thr -> gt[j,4], the LARGEST
+ *   such j (numpy's fancy assignment keeps the last of np.where's row-major pairs; with
+ *   min_pos_thr = 0 a gt that overlaps no valid anchor labels every zero-overlap anchor: the
+ *   reference's own TODO, reproduced); max_overlap >= pos_thr -> gt[argmax,4], first maximum.
+ *   reg_target (:69) is the nonlinear_transform encoding against the arg-max gt for EVERY valid
+ *   anchor, reg_weight (:70) is 1 where label >= 1.  No valid gt: label 0 on valid anchors, targets
+ *   and weights 0.  Anchors outside allowed_border: -1 / 0 / 0.
+ *   fg_count (B) float = max(1, #(label > 0))  (:192).
+ *   layout 0: cls_label (B,N), reg_target / reg_weight (B,N,4) in all-anchor order (level, y, x, a);
+ *   layout 1: the loader's final arrays (:149-199): cls_label (B,N) = per level (A, fh, fw), levels
+ *            concatenated; reg_target / reg_weight (B, 4A, sumHW), levels concatenated along the
+ *            last axis -- the order get_loss's cls_logit_concat expects.
+ *   Limits (those of sd_rpn_anchor_target): N < 2^28 anchors per image, A <= 16, nlvl <= 8,
+ *   M <= 3276 (20 bytes of LDS per gt row).  reg_target / reg_weight 16-byte aligned.
+ *   No host synchronisation; graph-capturable.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_retina_target_workspace_bytes(const sd_rpn_target_param* param_host, int B, int M);
+int sd_retina_anchor_target(const float* im_info, const float* gt_bbox, int B, int M,
+                            const sd_rpn_target_param* param_host, float* cls_label,
+                            float* reg_target, float* reg_weight, float* fg_count, int layout,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_FocalLoss  (X.focal_loss; models/retinanet/builder.py:289-297, models/RepPoints/
+ *   builder.py:404) and _contrib_BBoxNorm  (X.bbox_norm; builder.py:320-324), fp32.
+ *   replaces FocalLossOp::Forward / Backward  operator_cxx/contrib/focal_loss-inl.h:90-231 (seven
+ *   full-size temporaries out of a 1.5-1.8 GB workspace) and BBoxNormOp::Backward
+ *   operator_cxx/contrib/bbox_norm-inl.h:99-129.
+ *   sd_focal_loss_fwd: out = 1 / (1 + exp(-data)) over n elements (:113).
+ *   sd_focal_loss_bwd: out / ograd / gdata (B,nbox,nclass), label (B,nbox).  Element rule (:186-230),
+ *     p = out[b,n,c], eps = 1e-14f, every operation in fp32 in the reference's order:
+ *       class c == int(label - 1)  [one_hot truncates toward zero; an index outside [0,nclass) and a
+ *       NaN label select no class]:     alpha * (1-p)^gamma * (gamma * p * log(p + eps) + p - 1)
+ *       elsewhere:                 -((1-alpha) * p^gamma * (gamma * (1-p) * log((1-p) + eps) - p))
+ *       label == -1: the whole row is 0.
+ *     Then * ograd when ograd_or_null is given (the op's out_grad=True), then
+ *       normalization 2 (valid): (g * grad_scale) / (count + 1), count = #(label >= 1) over the whole
+ *                                batch, reduced on the device as an integer; no max, as in :220-221
+ *       normalization 1 (batch): g * (grad_scale / B)
+ *       normalization 0 (null):  g * grad_scale.
+ *     gamma == 2, 1, 0 multiply; any other gamma goes through powf.  gdata is written (kWriteTo);
+ *     the label gradient (zeros in the reference) has no entry point.
+ *   sd_bbox_norm_bwd: gout / gdata (B, n_per_image), label (B, n_label_per_image):
+ *     gdata = gout / max(1, count + 1), the same count (bbox_norm-inl.h:116-126).  The forward is a copy.
+ *   The count lives in the workspace (sd_focal_loss_workspace_bytes(), shared by both backwards) and
+ *   the gradient kernels read it from device memory: no host synchronisation, graph-capturable.
+ *   16-byte loads and stores when nclass % 4 == 0 (n for the other two) and every data pointer is
+ *   16-byte aligned; a scalar path otherwise (4-byte alignment suffices).
+ *   Limits: B * nbox * nclass <= 2^31 - 1 elements for the focal backward, B * n_label_per_image <= 2^31 - 1
+ *   labels for sd_bbox_norm_bwd (the count is a 32-bit integer); SD_ERR_UNSUPPORTED beyond.  B = 0, nbox = 0 or
+ *   nclass = 0 succeed without touching the device.
+ * ---------------------------------------------------------------------------------------------- */
+int sd_focal_loss_fwd(const float* data, float* out, long n, void* stream);
+size_t sd_focal_loss_workspace_bytes(void);
+int sd_focal_loss_bwd(const float* out, const float* label, const float* ograd_or_null, float* gdata,
+                      int B, int nbox, int nclass, float alpha, float gamma, float grad_scale,
+                      int normalization, void* workspace, size_t workspace_bytes, void* stream);
+int sd_bbox_norm_bwd(const float* gout, const float* label, float* gdata, int B, long n_per_image,
+                     long n_label_per_image, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

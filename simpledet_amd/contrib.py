@@ -247,3 +247,49 @@ def DecodeBBox(rois, bbox_pred, im_info, bbox_mean=(0., 0., 0., 0.), bbox_std=(.
     with torch.no_grad():
         return ops.decode_bbox(rois, bbox_pred, im_info, bbox_mean, bbox_std, class_agnostic,
                                bbox_decode_type)
+
+
+class _FocalLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, label, alpha, gamma, grad_scale, normalization, out_grad):
+        out = ops.focal_loss_forward(data.contiguous())
+        ctx.save_for_backward(out, label)
+        ctx.cfg = (alpha, gamma, grad_scale, normalization, out_grad)
+        ctx.mark_non_differentiable(label)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        out, label = ctx.saved_tensors
+        alpha, gamma, grad_scale, normalization, out_grad = ctx.cfg
+        g = ops.focal_loss_backward(out, label, dy.contiguous() if out_grad else None, alpha=alpha, gamma=gamma,
+                                    grad_scale=grad_scale, normalization=normalization)
+        return g, None, None, None, None, None, None
+
+
+def focal_loss(data, label, alpha=0.25, gamma=2.0, grad_scale=1.0, normalization="null", out_grad=False):
+    """mx.sym.contrib.FocalLoss / X.focal_loss (models/retinanet/builder.py:289-297): data (B,nbox,nclass),
+    label (B,nbox) -> sigmoid(data).  The backward is the reference's (focal_loss-inl.h:186-230), NOT the
+    derivative of the sigmoid: it is the focal-loss gradient itself, and the head gradient enters only with
+    out_grad=True.  Defaults: focal_loss-inl.h:52-79."""
+    return _FocalLoss.apply(data, label, float(alpha), float(gamma), float(grad_scale), normalization,
+                            bool(out_grad))
+
+
+class _BBoxNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, label):
+        ctx.save_for_backward(label)
+        return data.clone()
+
+    @staticmethod
+    def backward(ctx, dy):
+        (label,) = ctx.saved_tensors
+        return ops.bbox_norm_backward(dy.contiguous(), label), None
+
+
+def bbox_norm(data, label):
+    """mx.sym.contrib.BBoxNorm / X.bbox_norm (models/retinanet/builder.py:320-324): the identity forward;
+    the backward divides the head gradient by max(1, #(label >= 1) over the batch + 1)
+    (bbox_norm-inl.h:116-126)."""
+    return _BBoxNorm.apply(data, label)

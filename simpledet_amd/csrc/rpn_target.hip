@@ -71,6 +71,7 @@ struct RpnArgs {
   int* bg_list;          // (B,N)
   int* counts;           // (B,4): n_fg, n_bg, fg_sampled, bg_sampled
   int nblk;
+  const double* base64;  // retina: (nlvl, kRpnMaxA, 4) base anchors in double, device memory
 };
 
 struct AnchorRef {
@@ -78,8 +79,12 @@ struct AnchorRef {
   int lvl, y, x, a, fh, fw, hwoff;
 };
 
-// anchor n of an image whose orientation is `portrait` (h >= w: fh = long, fw = short)
-__device__ __forceinline__ AnchorRef rpn_anchor(const RpnArgs& a, int n, bool portrait) {
+// anchor n of an image whose orientation is `portrait` (h >= w: fh = long, fw = short).
+// F64 (retina): the reference's anchors are float64 = float32 grid + float64 base (detection_input.py:409-415),
+// and RetinaNet's scales 4 * 2^(k/3) make the base irrational: the float64 box goes to `dbox` (validity test and
+// encoding), and r.box is its float32 rounding, the `valid_anchor.astype(np.float32)` the IoU sees.
+template <bool F64 = false>
+__device__ __forceinline__ AnchorRef rpn_anchor(const RpnArgs& a, int n, bool portrait, double* dbox = nullptr) {
   AnchorRef r;
   int off = 0, hwoff = 0, l = 0, fh = 0, fw = 0;
   for (; l < a.p.nlvl; ++l) {
@@ -97,6 +102,13 @@ __device__ __forceinline__ AnchorRef rpn_anchor(const RpnArgs& a, int n, bool po
   r.x = cell % fw;
   r.y = cell / fw;
   const float sx = (float)r.x * (float)a.p.stride[l], sy = (float)r.y * (float)a.p.stride[l];
+  if (F64) {
+    const double* b = a.base64 + (l * kRpnMaxA + r.a) * 4;
+    dbox[0] = (double)sx + b[0]; dbox[1] = (double)sy + b[1];
+    dbox[2] = (double)sx + b[2]; dbox[3] = (double)sy + b[3];
+    r.box = make_float4((float)dbox[0], (float)dbox[1], (float)dbox[2], (float)dbox[3]);
+    return r;
+  }
   const float* b = a.base[l][r.a];
   r.box = make_float4(sx + b[0], sy + b[1], sx + b[2], sy + b[3]);
   return r;
@@ -120,7 +132,7 @@ __device__ __forceinline__ float rpn_iou(const float4 b, const float4 q) {
 
 // valid gt rows (gt[:,0] != -1), order preserved, into LDS; returns their number (all threads)
 template <int THREADS>
-__device__ int rpn_load_gt(const RpnArgs& a, int img, float4* gbox, int* wsum) {
+__device__ int rpn_load_gt(const RpnArgs& a, int img, float4* gbox, int* wsum, float* gcls = nullptr) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   int n_gt = 0;
   for (int base = 0; base < a.M; base += THREADS) {
@@ -140,7 +152,11 @@ __device__ int rpn_load_gt(const RpnArgs& a, int img, float4* gbox, int* wsum) {
       if (w < wave) off += wsum[w];
       tot += wsum[w];
     }
-    if (ok) gbox[off + __popcll(m & ((1ull << lane) - 1))] = g;
+    if (ok) {
+      const int k = off + __popcll(m & ((1ull << lane) - 1));
+      gbox[k] = g;
+      if (gcls) gcls[k] = a.gt[((long)img * a.M + j) * a.G + 4];  // (retina: the class column, G = 5)
+    }
     n_gt += tot;
   }
   __syncthreads();
@@ -152,8 +168,15 @@ __device__ __forceinline__ bool rpn_valid(const RpnArgs& a, const float4 b, floa
   return b.x >= -ab && b.y >= -ab && b.z < w + ab && b.w < h + ab;
 }
 
+// float64 anchors against float32 bounds (w + allowed_border is a float32 sum in numpy, then promoted)
+__device__ __forceinline__ bool rpn_valid64(const RpnArgs& a, const double* b, float h, float w) {
+  const float ab = (float)a.p.allowed_border;
+  return b[0] >= (double)-ab && b[1] >= (double)-ab && b[2] < (double)(w + ab) && b[3] < (double)(h + ab);
+}
+
 constexpr int kRpnT = 256;
 
+template <bool F64 = false>
 __global__ __launch_bounds__(kRpnT) void rpn_overlap_kernel(RpnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float4 gbox[];
   __shared__ int wsum[kRpnT / kWave];
@@ -165,10 +188,11 @@ __global__ __launch_bounds__(kRpnT) void rpn_overlap_kernel(RpnArgs a) {
   __syncthreads();
   const float h = a.im_info[img * 3], w = a.im_info[img * 3 + 1];
   if (n < a.N) {
-    const AnchorRef r = rpn_anchor(a, n, h >= w);
+    double d[4];
+    const AnchorRef r = rpn_anchor<F64>(a, n, h >= w, d);
     float maxv = 0.f;
     int maxi = 0;
-    if (rpn_valid(a, r.box, h, w)) {
+    if (F64 ? rpn_valid64(a, d, h, w) : rpn_valid(a, r.box, h, w)) {
       for (int j = 0; j < n_gt; ++j) {
         const float o = rpn_iou(r.box, gbox[j]);
         if (j == 0 || o > maxv) {  // np.argmax: first maximum
@@ -574,6 +598,21 @@ __global__ __launch_bounds__((1 + kMtProd) * kWave) void rpn_sample_kernel(RpnAr
   mt_st(ctl + 5, 1);   // the producers may leave
 }
 
+// nonlinear_transform (operator_py/bbox_transform.py:52-77) on a float64 anchor / float32 gt box
+__device__ __forceinline__ void rpn_encode_box(const double* box, const float4 g, float* t) {
+  const double ex0 = box[0], ey0 = box[1], ex1 = box[2], ey1 = box[3];
+  const double ew = ex1 - ex0 + 1.0, eh = ey1 - ey0 + 1.0;
+  const double ecx = ex0 + 0.5 * (ew - 1.0), ecy = ey0 + 0.5 * (eh - 1.0);
+  // gt is float32: gt[:,2] - gt[:,0] is a float32 subtraction, "+ 1.0" promotes per numpy 2 rules
+  // (python float is weak: stays float32)
+  const float gwf = g.z - g.x + 1.0f, ghf = g.w - g.y + 1.0f;
+  const float gcxf = g.x + 0.5f * (gwf - 1.0f), gcyf = g.y + 0.5f * (ghf - 1.0f);
+  t[0] = (float)(((double)gcxf - ecx) / (ew + 1e-14));
+  t[1] = (float)(((double)gcyf - ecy) / (eh + 1e-14));
+  t[2] = (float)log((double)gwf / ew);
+  t[3] = (float)log((double)ghf / eh);
+}
+
 __global__ __launch_bounds__(kRpnT) void rpn_encode_kernel(RpnArgs a) {
   const int img = blockIdx.y;
   const int n = blockIdx.x * kRpnT + threadIdx.x;
@@ -597,17 +636,8 @@ __global__ __launch_bounds__(kRpnT) void rpn_encode_kernel(RpnArgs a) {
       const float* p = a.gt + ((long)img * a.M + j) * a.G;
       if (p[0] != -1.f && ++seen == g) { gp = p; break; }
     }
-    const double ex0 = r.box.x, ey0 = r.box.y, ex1 = r.box.z, ey1 = r.box.w;
-    const double ew = ex1 - ex0 + 1.0, eh = ey1 - ey0 + 1.0;
-    const double ecx = ex0 + 0.5 * (ew - 1.0), ecy = ey0 + 0.5 * (eh - 1.0);
-    // gt is float32: gt[:,2] - gt[:,0] is a float32 subtraction, "+ 1.0" promotes per numpy 2 rules
-    // (python float is weak: stays float32)
-    const float gwf = gp[2] - gp[0] + 1.0f, ghf = gp[3] - gp[1] + 1.0f;
-    const float gcxf = gp[0] + 0.5f * (gwf - 1.0f), gcyf = gp[1] + 0.5f * (ghf - 1.0f);
-    t[0] = (float)(((double)gcxf - ecx) / (ew + 1e-14));
-    t[1] = (float)(((double)gcyf - ecy) / (eh + 1e-14));
-    t[2] = (float)log((double)gwf / ew);
-    t[3] = (float)log((double)ghf / eh);
+    const double d[4] = {r.box.x, r.box.y, r.box.z, r.box.w};
+    rpn_encode_box(d, make_float4(gp[0], gp[1], gp[2], gp[3]), t);
   }
   if (a.layout == 0) {
     a.cls[(long)img * a.N + n] = (float)lab;
@@ -624,6 +654,108 @@ __global__ __launch_bounds__(kRpnT) void rpn_encode_kernel(RpnArgs a) {
       a.wgt[o] = wv;
     }
   }
+}
+
+// ---- RetinaNet anchor targets (models/retinanet/input.py:42-104, :149-199) -------------------------
+// After rpn_overlap (per-anchor max / first arg-max, per-gt max over the valid anchors) ONE kernel
+// does the rest: there is no sampling between the labels and the encoding.  RpnArgs carries the
+// per-image foreground counters in `counts`; retina_fg turns them into max(1, count) floats.
+__global__ __launch_bounds__(kRpnT) void retina_encode_kernel(RpnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float4 gbox[];
+  __shared__ int wsum[kRpnT / kWave];
+  float* gcls = reinterpret_cast<float*>(gbox + a.M);
+  const int img = blockIdx.y, tid = threadIdx.x;
+  const int n = blockIdx.x * kRpnT + tid;
+  const int n_gt = rpn_load_gt<kRpnT>(a, img, gbox, wsum, gcls);
+  const float h = a.im_info[img * 3], w = a.im_info[img * 3 + 1];
+  float lab = -1.f, wv = 0.f;
+  float t[4] = {0.f, 0.f, 0.f, 0.f};
+  AnchorRef r{};
+  if (n < a.N) {
+    double d[4];
+    r = rpn_anchor<true>(a, n, h >= w, d);
+    if (rpn_valid64(a, d, h, w)) {
+      if (n_gt > 0) {
+        const float mo = a.maxov[(long)img * a.N + n];
+        const int am = a.argmax[(long)img * a.N + n];
+        if (mo < a.p.neg_thr) lab = 0.f;                                        // :62
+        for (int j = 0; j < n_gt; ++j) {                                        // :59-64, the last j wins
+          const float o = rpn_iou(r.box, gbox[j]);
+          const float gm = __uint_as_float(a.gtmax[(long)img * a.M + j]);
+          if (o == gm && o >= a.p.min_pos_thr) lab = gcls[j];
+        }
+        if (mo >= a.p.pos_thr) lab = gcls[am];                                  // :66
+        rpn_encode_box(d, gbox[am], t);                                         // :69, every valid anchor
+        if (lab >= 1.f) wv = 1.f;                                               // :70
+      } else {
+        lab = 0.f;                                                              // :72
+      }
+    }
+  }
+  const unsigned long long mf = __ballot(lab > 0.f);                            // :192
+  if ((tid & (kWave - 1)) == 0 && mf) atomicAdd(&a.counts[img], __popcll(mf));
+  if (n >= a.N) return;
+  if (a.layout == 0) {
+    a.cls[(long)img * a.N + n] = lab;
+    reinterpret_cast<float4*>(a.tgt)[(long)img * a.N + n] = make_float4(t[0], t[1], t[2], t[3]);
+    reinterpret_cast<float4*>(a.wgt)[(long)img * a.N + n] = make_float4(wv, wv, wv, wv);
+  } else {
+    // label: per level (A, fh, fw), levels concatenated (:176, :187); targets (4A, sumHW) (:177-189)
+    const int cell = r.y * r.fw + r.x;
+    a.cls[(long)img * a.N + (long)r.hwoff * a.A + (long)r.a * r.fh * r.fw + cell] = lab;
+    for (int k = 0; k < 4; ++k) {
+      const long o = ((long)img * a.A * 4 + r.a * 4 + k) * a.sumHW + r.hwoff + cell;
+      a.tgt[o] = t[k];
+      a.wgt[o] = wv;
+    }
+  }
+}
+
+// base anchors in double from the host's (ws, hs) (detection_input.py:392-397; 2 KB of arguments: together
+// with RpnArgs they would pass the 4 KB a kernel may take, so they go through device memory)
+struct RetinaBaseWH {
+  double ws[kRpnMaxLvl][kRpnMaxA], hs[kRpnMaxLvl][kRpnMaxA];
+  int stride[kRpnMaxLvl];
+};
+__global__ void retina_base_kernel(RetinaBaseWH p, double* base64, unsigned* clear, int nclear) {
+  // ... and clears the per-gt maxima and the per-image counters behind them (a captured graph then holds kernel
+  // nodes only)
+  for (int k = threadIdx.x; k < nclear; k += blockDim.x) clear[k] = 0u;
+  const int l = threadIdx.x / kRpnMaxA, i = threadIdx.x % kRpnMaxA;
+  const double s = p.stride[l];
+  const double x_ctr = 0.5 * (s - 1), y_ctr = 0.5 * (s - 1);
+  double* b = base64 + (l * kRpnMaxA + i) * 4;
+  b[0] = x_ctr - 0.5 * (p.ws[l][i] - 1);
+  b[1] = y_ctr - 0.5 * (p.hs[l][i] - 1);
+  b[2] = x_ctr + 0.5 * (p.ws[l][i] - 1);
+  b[3] = y_ctr + 0.5 * (p.hs[l][i] - 1);
+}
+
+__global__ void retina_fg_kernel(const int* counts, float* fg_count, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) fg_count[b] = (float)imaxr(1, counts[b]);
+}
+
+static size_t retina_layout(int B, int N, int M, RpnArgs* a, char* base) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    size_t o = off;
+    off = (off + bytes + 255) / 256 * 256;
+    return o;
+  };
+  const size_t o_mo = take((size_t)B * N * 4), o_am = take((size_t)B * N * 4), o_kp = take((size_t)B * N);
+  // gtmax and the per-image counters are adjacent: retina_base clears both
+  const size_t o_gm = take((size_t)B * (M > 0 ? M : 1) * 4), o_ct = take((size_t)B * 4);
+  const size_t o_ba = take((size_t)kRpnMaxLvl * kRpnMaxA * 4 * sizeof(double));
+  if (a) {
+    a->base64 = reinterpret_cast<const double*>(base + o_ba);
+    a->maxov = reinterpret_cast<float*>(base + o_mo);
+    a->argmax = reinterpret_cast<int*>(base + o_am);
+    a->keep = reinterpret_cast<unsigned char*>(base + o_kp);   // (written by rpn_overlap, not read)
+    a->gtmax = reinterpret_cast<unsigned*>(base + o_gm);
+    a->counts = reinterpret_cast<int*>(base + o_ct);
+  }
+  return off;
 }
 
 static size_t rpn_layout(int B, int N, int M, int nblk, RpnArgs* a, char* base) {
@@ -666,6 +798,26 @@ static int rpn_count(const sd_rpn_target_param& p, int* A, int* N, int* sumHW) {
   *N = (int)n;
   *sumHW = (int)hw;
   return SD_OK;
+}
+
+// base anchors: core/detection_input.py:373-399 in double (np.round = rint, half to even)
+static void rpn_base_anchors(RpnArgs* a) {
+  for (int l = 0; l < a->p.nlvl; ++l) {
+    const double s = a->p.stride[l];
+    const double w = s, h = s, x_ctr = 0.5 * (w - 1), y_ctr = 0.5 * (h - 1);
+    for (int i = 0; i < a->p.n_aspects; ++i) {
+      const double wr = rint(sqrt(w * h / a->p.aspects[i]));
+      const double hr = rint(wr * a->p.aspects[i]);
+      for (int j = 0; j < a->p.n_scales; ++j) {
+        const double ws = wr * a->p.scales[j], hs = hr * a->p.scales[j];
+        float* b = a->base[l][i * a->p.n_scales + j];
+        b[0] = (float)(x_ctr - 0.5 * (ws - 1));
+        b[1] = (float)(y_ctr - 0.5 * (hs - 1));
+        b[2] = (float)(x_ctr + 0.5 * (ws - 1));
+        b[3] = (float)(y_ctr + 0.5 * (hs - 1));
+      }
+    }
+  }
 }
 
 }  // namespace sd
@@ -716,23 +868,7 @@ extern "C" int sd_rpn_anchor_target(const float* im_info, const float* gt_bbox, 
   SD_REQUIRE((((uintptr_t)reg_target | (uintptr_t)reg_weight) & 15) == 0, "outputs must be 16-B aligned");
   // num_fg = int(fg_fraction * num) with a python float fraction: evaluated in double
   a.num_fg = (int)(a.p.pos_fraction * (double)a.p.image_anchor);
-  // base anchors: core/detection_input.py:373-399 in double (np.round = rint, half to even)
-  for (int l = 0; l < a.p.nlvl; ++l) {
-    const double s = a.p.stride[l];
-    const double w = s, h = s, x_ctr = 0.5 * (w - 1), y_ctr = 0.5 * (h - 1);
-    for (int i = 0; i < a.p.n_aspects; ++i) {
-      const double wr = rint(sqrt(w * h / a.p.aspects[i]));
-      const double hr = rint(wr * a.p.aspects[i]);
-      for (int j = 0; j < a.p.n_scales; ++j) {
-        const double ws = wr * a.p.scales[j], hs = hr * a.p.scales[j];
-        float* b = a.base[l][i * a.p.n_scales + j];
-        b[0] = (float)(x_ctr - 0.5 * (ws - 1));
-        b[1] = (float)(y_ctr - 0.5 * (hs - 1));
-        b[2] = (float)(x_ctr + 0.5 * (ws - 1));
-        b[3] = (float)(y_ctr + 0.5 * (hs - 1));
-      }
-    }
-  }
+  rpn_base_anchors(&a);
   a.im_info = im_info; a.gt = gt_bbox; a.B = B; a.M = M; a.G = G; a.mt = mt_state;
   a.cls = cls_label; a.tgt = reg_target; a.wgt = reg_weight; a.layout = layout;
   a.nblk = cdiv(a.N, kRpnT);
@@ -746,12 +882,66 @@ extern "C" int sd_rpn_anchor_target(const float* im_info, const float* gt_bbox, 
   const size_t lds = (size_t)(M > 0 ? M : 1) * (sizeof(float4) + sizeof(unsigned));
   SD_REQUIRE(lds <= 64 * 1024, "too many gt boxes per image (M=%d)", M);
   const dim3 grid(a.nblk, B);
-  hipLaunchKernelGGL(rpn_overlap_kernel, grid, dim3(kRpnT), lds, st, a);
+  hipLaunchKernelGGL(rpn_overlap_kernel<false>, grid, dim3(kRpnT), lds, st, a);
   hipLaunchKernelGGL(rpn_label_kernel, grid, dim3(kRpnT), lds, st, a);
   hipLaunchKernelGGL(rpn_scan_kernel, dim3(B), dim3(1024), 0, st, a);
   hipLaunchKernelGGL(rpn_lists_kernel, grid, dim3(kRpnT), 0, st, a);
   hipLaunchKernelGGL(rpn_sample_kernel, dim3(1), dim3((1 + kMtProd) * kWave), 0, st, a);
   hipLaunchKernelGGL(rpn_encode_kernel, grid, dim3(kRpnT), 0, st, a);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+extern "C" size_t sd_retina_target_workspace_bytes(const sd_rpn_target_param* p, int B, int M) {
+  int A, N, S;
+  if (!p || B <= 0 || M < 0 || rpn_count(*p, &A, &N, &S)) return 256;
+  return retina_layout(B, N, M, nullptr, nullptr) + 256;
+}
+
+extern "C" int sd_retina_anchor_target(const float* im_info, const float* gt_bbox, int B, int M,
+                                       const sd_rpn_target_param* param_host, float* cls_label,
+                                       float* reg_target, float* reg_weight, float* fg_count, int layout,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  SD_REQUIRE(param_host, "param is null");
+  RpnArgs a{};
+  a.p = *param_host;
+  if (int e = rpn_count(a.p, &a.A, &a.N, &a.sumHW)) return e;
+  SD_REQUIRE(B >= 0 && M >= 0, "bad B / M");
+  SD_REQUIRE(layout == 0 || layout == 1, "layout must be 0 (flat) or 1 (loader layout)");
+  const size_t lds = (size_t)(M > 0 ? M : 1) * (sizeof(float4) + sizeof(unsigned));
+  SD_REQUIRE(lds <= 64 * 1024, "too many gt boxes per image (M=%d)", M);
+  if (B == 0) return SD_OK;
+  SD_REQUIRE(im_info && (gt_bbox || M == 0) && cls_label && reg_target && reg_weight && fg_count,
+             "null pointer");
+  SD_REQUIRE((((uintptr_t)reg_target | (uintptr_t)reg_weight) & 15) == 0, "outputs must be 16-B aligned");
+  RetinaBaseWH wh{};
+  for (int l = 0; l < a.p.nlvl; ++l) {
+    const double s = a.p.stride[l];
+    wh.stride[l] = a.p.stride[l];
+    for (int i = 0; i < a.p.n_aspects; ++i) {
+      const double wr = rint(sqrt(s * s / a.p.aspects[i]));   // np.round: half to even (:387-390)
+      const double hr = rint(wr * a.p.aspects[i]);
+      for (int j = 0; j < a.p.n_scales; ++j) {
+        wh.ws[l][i * a.p.n_scales + j] = wr * a.p.scales[j];
+        wh.hs[l][i * a.p.n_scales + j] = hr * a.p.scales[j];
+      }
+    }
+  }
+  a.im_info = im_info; a.gt = gt_bbox; a.B = B; a.M = M; a.G = 5;
+  a.cls = cls_label; a.tgt = reg_target; a.wgt = reg_weight; a.layout = layout;
+  a.nblk = cdiv(a.N, kRpnT);
+  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  const size_t need = retina_layout(B, a.N, M, &a, base) + (size_t)(base - (char*)workspace);
+  if (!workspace || workspace_bytes < need)
+    return fail(SD_ERR_WORKSPACE, "retina_anchor_target workspace too small: %zu < %zu bytes",
+                workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(a.nblk, B);
+  hipLaunchKernelGGL(retina_base_kernel, dim3(1), dim3(kRpnMaxLvl * kRpnMaxA), 0, st, wh,
+                     const_cast<double*>(a.base64), a.gtmax, (int)(reinterpret_cast<unsigned*>(a.counts + B) - a.gtmax));
+  hipLaunchKernelGGL(rpn_overlap_kernel<true>, grid, dim3(kRpnT), lds, st, a);
+  hipLaunchKernelGGL(retina_encode_kernel, grid, dim3(kRpnT), lds, st, a);
+  hipLaunchKernelGGL(retina_fg_kernel, dim3(cdiv(B, kRpnT)), dim3(kRpnT), 0, st, a.counts, fg_count, B);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

@@ -1238,6 +1238,122 @@ def _build_ops(mx):
 
     ops["_contrib_GenProposalRetina"] = (GenProposalRetinaProp, ("contrib", "GenProposalRetina"))
 
+    # ---- _contrib_FocalLoss / _contrib_BBoxNorm: data, label -> output ----
+    #      (registered only by install(..., retina_loss=True))
+    NORMALIZATION = {"null": 0, "batch": 1, "valid": 2}
+
+    def _loss_scratch(like):
+        lib().cdll.sd_focal_loss_workspace_bytes.restype = ctypes.c_size_t
+        wsb = int(lib().cdll.sd_focal_loss_workspace_bytes())
+        return _scratch(like, wsb), wsb
+
+    class FocalLoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            data = in_data[0]
+            _wait(data)
+            _call("sd_focal_loss_fwd", _ptr(data), _ptr(out_data[0]), ctypes.c_long(_numel(data.shape)), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # focal_loss-inl.h:116-231: kWriteTo on the data gradient (:129); the label gradient is not written
+            _require_write(req[:1], ["FocalLoss data gradient"])
+            g = self.g
+            label, out = in_data[1], out_data[0]
+            ograd = out_grad[0] if g["out_grad"] else None
+            _wait(label, out, ograd)
+            if _req(req[0]) != REQ["null"]:
+                B, nbox, nclass = out.shape
+                ws, wsb = _loss_scratch(out)
+                _call("sd_focal_loss_bwd", _ptr(out), _ptr(label), _ptr(ograd), _ptr(in_grad[0]), B, nbox, nclass,
+                      float(g["alpha"]), float(g["gamma"]), float(g["grad_scale"]), g["normalization"], _ptr(ws),
+                      ctypes.c_size_t(wsb), None)
+            _sync()
+
+    class FocalLossProp(CustomOpProp):
+        def __init__(self, alpha="0.25", gamma="2.0", grad_scale="1.0", normalization="null", out_grad="False",
+                     workspace="256"):
+            # defaults: focal_loss-inl.h:59-80.  `workspace` (MB of temporaries in the reference) is accepted and unused.
+            out_grad = _bool(out_grad)
+            super().__init__(need_top_grad=out_grad)
+            if normalization not in NORMALIZATION:
+                raise ValueError("FocalLoss: normalization must be one of %s" % sorted(NORMALIZATION))
+            self.g = dict(alpha=float(alpha), gamma=float(gamma), grad_scale=float(grad_scale),
+                          normalization=NORMALIZATION[normalization], out_grad=out_grad)
+
+        def list_arguments(self):
+            return ["data", "label"]
+
+        def list_outputs(self):
+            return ["output"]
+
+        def infer_shape(self, in_shape):
+            # FocalLossProp::InferShape (focal_loss-inl.h:258-272): data (B, nbox, nclass), label (B, nbox)
+            d = in_shape[0]
+            if len(d) != 3:
+                raise ValueError("FocalLoss: data should be (batch, box, class)")
+            return [d, (d[0], d[1])], [d]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return FocalLoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            # focal_loss-inl.h:314-324
+            deps = [in_data[1], out_data[0]]
+            return deps + [out_grad[0]] if self.g["out_grad"] else deps
+
+    class BBoxNorm(CustomOp):
+        def forward(self, is_train, req, in_data, out_data, aux):
+            self.assign(out_data[0], req[0], in_data[0])   # F<identity> (bbox_norm-inl.h:96)
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            _require_write(req[:1], ["BBoxNorm data gradient"])
+            gout, label = out_grad[0], in_data[1]
+            _wait(gout, label)
+            if _req(req[0]) != REQ["null"]:
+                B = gout.shape[0]
+                ws, wsb = _loss_scratch(gout)
+                _call("sd_bbox_norm_bwd", _ptr(gout), _ptr(label), _ptr(in_grad[0]), B,
+                      ctypes.c_long(_numel(gout.shape) // B if B else 0),
+                      ctypes.c_long(_numel(label.shape) // B if B else 0), _ptr(ws), ctypes.c_size_t(wsb), None)
+            if len(req) > 1:
+                self.assign(in_grad[1], req[1], 0)         # :128
+            _sync()
+
+    class BBoxNormProp(CustomOpProp):
+        def __init__(self, normalization="null"):
+            # bbox_norm-inl.h:52-65: the parameter is declared and never read by the operator
+            super().__init__(need_top_grad=True)
+            if normalization not in NORMALIZATION:
+                raise ValueError("BBoxNorm: normalization must be one of %s" % sorted(NORMALIZATION))
+
+        def list_arguments(self):
+            return ["data", "label"]
+
+        def list_outputs(self):
+            return ["output"]
+
+        def infer_shape(self, in_shape):
+            # BBoxNormProp::InferShape: data (B, 4A, npos), label (B, A * npos); the output has data's shape
+            d = in_shape[0]
+            if len(d) < 2:
+                raise ValueError("BBoxNorm: data should be (batch, 4 * anchor, position)")
+            label = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else (d[0], _numel(d[1:]) // 4)
+            return [d, label], [d]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return BBoxNorm()
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [in_data[1], out_grad[0]]               # bbox_norm-inl.h:212-217
+
+    ops["_contrib_FocalLoss"] = (FocalLossProp, ("contrib", "FocalLoss"))
+    ops["_contrib_BBoxNorm"] = (BBoxNormProp, ("contrib", "BBoxNorm"))
+
     # ---- get_top_proposal (models/FPN/get_top_proposal.py): bbox, score -> top_n of each ----
     class GetTopProposal(CustomOp):
         def __init__(self, top_n):
@@ -1412,12 +1528,14 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None, retina=False, proposal=False, bbox_post=False):
+def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
     bbox_post: also BboxPostProcessing (opt-in: it replaces the reference's own CustomOp of Mask R-CNN's
-    test graphs)."""
+    test graphs);
+    retina_loss: also _contrib_FocalLoss and _contrib_BBoxNorm (opt-in: they replace native operators of
+    existing RetinaNet / RepPoints train graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -1430,6 +1548,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False):
         table.pop("_contrib_Proposal")
     if not bbox_post:
         table.pop("BboxPostProcessing")
+    if not retina_loss:
+        table.pop("_contrib_FocalLoss")
+        table.pop("_contrib_BBoxNorm")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1458,7 +1579,7 @@ def _namespaces(mx, ns):
     return out
 
 
-def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False):
+def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1485,10 +1606,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     `models.maskrcnn.builder.BboxPostProcessor.get_post_processing` (patch_bbox_post) so that Mask R-CNN test
     graphs hold it in place of the reference's numpy CustomOp; opt-in because it changes which operator those
     graphs hold.  A `nms.type` other than "nms" or a max_det_per_image outside the kernels' limits falls back
-    to the reference's method and is listed in `_state["fallbacks"]`."""
-    props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post)
+    to the reference's method and is listed in `_state["fallbacks"]`.
+
+    `retina_loss=True` also replaces `_contrib_FocalLoss` and `_contrib_BBoxNorm` (models/retinanet/builder.py:294-332,
+    models/RepPoints/builder.py:404,439,472) and lets patch_mxnext bind `X.focal_loss` / `X.bbox_norm` to the
+    aliases; opt-in because it changes which operators existing RetinaNet / RepPoints train graphs hold."""
+    props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
+    _state["retina_loss"] = bool(retina_loss)
     _state["fallbacks"] = []
     _state["stream"], _state["sync"] = stream, bool(sync)
 
@@ -1639,6 +1765,13 @@ def _head_op(mx, sym):
     return getattr(node, "op_type", None), dict(getattr(node, "params", {}) or {})
 
 
+def _late_contrib(mx, ctor):
+    """a wrapper that looks mx.sym.contrib.<ctor> up at call time (positional and keyword inputs pass through)"""
+    def wrapper(*a, **kw):
+        return getattr(mx.sym.contrib, ctor)(*a, **kw)
+    return wrapper
+
+
 def patch_mxnext(mxnext=None, mx=None):
     """Point the mxnext wrappers on the hot path at the aliased symbol constructors WHERE THAT IS KNOWN TO
     BE A NO-OP FOR THE GRAPH'S MEANING.  mxnext (github.com/RogerChern/mxnext) is not part of the
@@ -1739,6 +1872,27 @@ def patch_mxnext(mxnext=None, mx=None):
             done.append("mxnext." + attr)
         except Exception:
             pass
+    # install(retina_loss=True): X.focal_loss / X.bbox_norm build the FocalLoss / BBoxNorm aliases at call time.  The
+    # wrappers' names pin the operator (models/retinanet/builder.py:296-332 passes the operators' own keyword
+    # arguments), so they are bound without a probe; a default install() puts the saved originals back.
+    for attr, ctor in (("focal_loss", "FocalLoss"), ("bbox_norm", "BBoxNorm")):
+        try:
+            cur = getattr(mxnext, attr)
+        except Exception:
+            continue
+        orig = cur._sd_original if getattr(cur, "_sd_alias", False) else cur
+        if not _state.get("retina_loss"):
+            if cur is not orig:
+                setattr(mxnext, attr, orig)
+            continue
+
+        loss = _late_contrib(mx, ctor)
+        loss.__name__ = attr
+        loss._sd_alias, loss._sd_original = True, orig
+        setattr(mxnext, "_sd_reference_" + attr, orig)
+        setattr(mxnext, attr, loss)
+        seen[attr] = "install(retina_loss=True): bound to mx.sym.contrib.%s at call time" % ctor
+        done.append("mxnext." + attr)
     try:
         import importlib
         m = importlib.import_module("mxnext.tvm.get_top_proposal")

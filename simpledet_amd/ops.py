@@ -684,6 +684,124 @@ def rpn_anchor_target(im_info, gt_bbox, param, mt_state, layout=1):
     return cls, tgt, wgt
 
 
+def retina_anchor_target(im_info, gt_bbox, param, layout=1, workspace=None):
+    """RetinaNet labels / box targets / weights / foreground counts for a batch of images: the loader's
+    PyramidAnchorTarget2D of models/retinanet/input.py:33-199 on the device (class-valued labels, no
+    subsampling, a target for every valid anchor).  im_info (B,3), gt_bbox (B,M,5) padded with -1 rows;
+    param: rpn_target_param(...), of which image_anchor / pos_fraction are ignored.
+    layout 1: cls_label (B, N) as per-level (A, fh, fw) blocks, reg_target / reg_weight (B, 4A, sumHW);
+    layout 0: (B,N), (B,N,4) in all-anchor order.  fg_count (B,) = max(1, #(label > 0))."""
+    _chk(im_info, "im_info", ndim=2)
+    _chk(gt_bbox, "gt_bbox", ndim=3)
+    B, M, G = gt_bbox.shape
+    if G != 5 or im_info.shape != (B, 3):
+        raise ValueError("gt_bbox must be (B,M,5) and im_info (B,3)")
+    N = int(lib().cdll.sd_rpn_target_num_anchors(ctypes.byref(param)))
+    if N < 0:
+        raise ValueError("bad anchor target parameters")
+    A = param.n_scales * param.n_aspects
+    dev = im_info.device
+    cls = torch.empty((B, N), device=dev, dtype=torch.float32)
+    tgt = torch.empty((B, 4 * A, N // A) if layout == 1 else (B, N, 4), device=dev, dtype=torch.float32)
+    wgt = torch.empty_like(tgt)
+    fg = torch.empty((B,), device=dev, dtype=torch.float32)
+    lib().cdll.sd_retina_target_workspace_bytes.restype = ctypes.c_size_t
+    wsb = int(lib().cdll.sd_retina_target_workspace_bytes(ctypes.byref(param), B, M))
+    if workspace is None:
+        workspace = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    elif workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    lib().call("sd_retina_anchor_target", _p(im_info), _p(gt_bbox), B, M, ctypes.byref(param), _p(cls),
+               _p(tgt), _p(wgt), _p(fg), int(layout), _p(workspace), ctypes.c_size_t(workspace.numel()),
+               _stream())
+    return cls, tgt, wgt, fg
+
+
+# --------------------------------------------------------------------------------------------------
+# _contrib_FocalLoss / _contrib_BBoxNorm  (operator_cxx/contrib/focal_loss-inl.h, bbox_norm-inl.h;
+# models/retinanet/builder.py:289-324)
+# --------------------------------------------------------------------------------------------------
+NORMALIZATION = {"null": 0, "batch": 1, "valid": 2}
+
+
+def focal_loss_workspace_bytes():
+    lib().cdll.sd_focal_loss_workspace_bytes.restype = ctypes.c_size_t
+    return int(lib().cdll.sd_focal_loss_workspace_bytes())
+
+
+def _loss_ws(dev, workspace):
+    wsb = focal_loss_workspace_bytes()
+    if workspace is None:
+        return torch.empty(wsb, device=dev, dtype=torch.uint8)
+    if workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    return workspace
+
+
+def focal_loss_forward(data, out=None):
+    """FocalLoss forward: out = sigmoid(data), any shape (focal_loss-inl.h:113)."""
+    _chk(data, "data")
+    if out is None:
+        out = torch.empty_like(data)
+    else:
+        _chk(out, "out")
+        if out.shape != data.shape:
+            raise ValueError("out must have the shape of data")
+    lib().call("sd_focal_loss_fwd", _p(data), _p(out), ctypes.c_long(data.numel()), _stream())
+    return out
+
+
+def focal_loss_backward(out, label, ograd=None, *, alpha=0.25, gamma=2.0, grad_scale=1.0,
+                        normalization="valid", gdata=None, workspace=None):
+    """FocalLoss backward (focal_loss-inl.h:186-230): out (B,nbox,nclass) = the forward's sigmoid,
+    label (B,nbox) in {-1 ignore, 0 background, 1..nclass}; ograd (same shape as out) only for the
+    op's out_grad=True.  normalization 'valid' divides by (#(label >= 1) over the batch + 1), counted
+    on the device; 'batch' by B; 'null' by nothing.  Returns gdata."""
+    _chk(out, "out", ndim=3)
+    _chk(label, "label", ndim=2)
+    B, nbox, nclass = out.shape
+    if label.shape != (B, nbox):
+        raise ValueError("label must be (B, nbox) = %s, got %s" % ((B, nbox), tuple(label.shape)))
+    if ograd is not None:
+        _chk(ograd, "ograd", ndim=3)
+        if ograd.shape != out.shape:
+            raise ValueError("ograd must have the shape of out")
+    if normalization not in NORMALIZATION:
+        raise ValueError("normalization must be one of %s" % sorted(NORMALIZATION))
+    if gdata is None:
+        gdata = torch.empty_like(out)
+    else:
+        _chk(gdata, "gdata", ndim=3)
+        if gdata.shape != out.shape:
+            raise ValueError("gdata must have the shape of out")
+    ws = _loss_ws(out.device, workspace)
+    lib().call("sd_focal_loss_bwd", _p(out), _p(label), _p(ograd), _p(gdata), B, nbox, nclass,
+               float(alpha), float(gamma), float(grad_scale), NORMALIZATION[normalization], _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return gdata
+
+
+def bbox_norm_backward(gout, label, gdata=None, workspace=None):
+    """BBoxNorm backward (bbox_norm-inl.h:116-126): gout (B, ...), label (B, ...);
+    gdata = gout / max(1, #(label >= 1) over the batch + 1).  The forward is the identity."""
+    _chk(gout, "gout")
+    _chk(label, "label")
+    if gout.dim() < 1 or label.dim() < 1 or gout.shape[0] != label.shape[0]:
+        raise ValueError("gout and label must share the batch dimension")
+    B = gout.shape[0]
+    if gdata is None:
+        gdata = torch.empty_like(gout)
+    else:
+        _chk(gdata, "gdata")
+        if gdata.shape != gout.shape:
+            raise ValueError("gdata must have the shape of gout")
+    ws = _loss_ws(gout.device, workspace)
+    lib().call("sd_bbox_norm_bwd", _p(gout), _p(label), _p(gdata), B,
+               ctypes.c_long(gout.numel() // B if B else 0), ctypes.c_long(label.numel() // B if B else 0),
+               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return gdata
+
+
 # --------------------------------------------------------------------------------------------------
 # _contrib_NMS  (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
 # --------------------------------------------------------------------------------------------------
