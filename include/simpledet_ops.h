@@ -59,9 +59,10 @@ const char* sd_last_dispatch(void);
  * sd_gemm_f32 to exact fp32; 8 sd_proposal and sd_proposal_v2 added (the existing entry points and
  * their workspace sizes are unchanged); 9 sd_hard_nms_batched and sd_bbox_post_processing added (nothing
  * existing changes); 10 sd_retina_anchor_target, sd_focal_loss_fwd / _bwd and sd_bbox_norm_bwd with their
- * workspace queries added (nothing existing changes).
+ * workspace queries added (nothing existing changes); 11 sd_group_norm_fwd / _bwd and
+ * sd_group_norm_workspace_bytes added (nothing existing changes).
  * sd_abi_version() returns the library's value; compare with this macro. */
-#define SD_ABI_VERSION 10
+#define SD_ABI_VERSION 11
 int sd_abi_version(void);
 /* kernel-variant knobs for A/B measurements (bench.py, tests); every variant computes the same
  * result.  Unknown keys are an error.  Knobs that disable parts of a kernel for profiling exist
@@ -803,6 +804,46 @@ int sd_focal_loss_bwd(const float* out, const float* label, const float* ograd_o
                       int normalization, void* workspace, size_t workspace_bytes, void* stream);
 int sd_bbox_norm_bwd(const float* gout, const float* label, float* gdata, int B, long n_per_image,
                      long n_label_per_image, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_GroupNorm  (mx.sym.contrib.GroupNorm; config/scratch/mask_r50v1b_fpn_gn_scratch_2x.py,
+ *   the five config/RepPoints and three config/efficientnet configs), fp32, NCHW.
+ *   replaces GroupNormOp::Forward / Backward  operator_cxx/contrib/group_norm.cu:71-298 and the Moments /
+ *   InvStd helpers of group_norm_helper.cu:36-63,258-268 (five launches; X read twice forward, dY and X three
+ *   times backward).
+ *   x / y / dy / dx (N,C,HxW) contiguous, gamma / beta / dgamma / dbeta (C), mu / rsig N*G floats, D = C / G.
+ *   sd_group_norm_fwd, per group (n, g) over its D*HxW contiguous floats:
+ *       mu = mean,  rsig = 1 / sqrt(var + eps) with the biased variance,
+ *       y = gamma[c] * (x - mu) * rsig + beta[c]              (the reference's order, :87-89).
+ *     The variance is taken ABOUT THE MEAN (two passes over resident data; Chan merging of per-chunk partials in
+ *     double where a group is split over workgroups), not as the reference's fp32 E[x^2] - mu^2, which cancels
+ *     when |mu| >> sigma and can go negative (NaN from rsqrtf): the one deliberate departure.
+ *     mu and rsig receive N*G floats each; a larger buffer (the reference declares the outputs (N,C)) keeps its
+ *     tail untouched.
+ *   sd_group_norm_bwd, with the sums taken about mu (ds = sum gamma[c] * dy * (x - mu), db = sum gamma[c] * dy
+ *     over the group, so the reference's (db * mu - ds) of :152 is -ds without its cancellation):
+ *       dx = gamma[c] * dy * rsig + ((-ds) * (x - mu) * rsig^3 - db * rsig) * (1 / (D*HxW))      (:152-158)
+ *       dgamma[c] = sum over n, hw of dy * (x - mu) * rsig,   dbeta[c] = sum over n, hw of dy    (:184-186)
+ *     dx, dgamma and dbeta are written (kWriteTo).  dgamma and dbeta may be NULL together: they are skipped.
+ *   Groups of up to 4096 (backward 2048) 16-byte items are held in registers: x (and dy) read once, y (dx)
+ *   written once, one launch (+ one tiny launch for dgamma / dbeta).  Larger groups are split over workgroups:
+ *   three launches, x (dy and x) read twice.  sd_last_dispatch() names the kernels taken.
+ *   16-byte loads and stores when HxW % 4 == 0 and x, y (dy, x, dx) are 16-byte aligned; a scalar path otherwise
+ *   (4-byte alignment suffices).  Every reduction has a fixed order and there are no floating-point atomics: two
+ *   calls on the same inputs give equal bits.  The workspace (sd_group_norm_workspace_bytes, monotone in N and C,
+ *   one size for both directions) needs no clearing; kernels only, no host synchronisation, graph-capturable.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a null pointer, G <= 0, C % G != 0, a
+ *   negative size, dgamma / dbeta not NULL together, a NULL or too small workspace; SD_ERR_UNSUPPORTED:
+ *   N*C*HxW > 2^31 - 1 elements.  N = 0, C = 0 or HxW = 0 succeed without a launch (no pointer is looked at;
+ *   sd_group_norm_workspace_bytes returns its minimum for them and for invalid sizes).
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_group_norm_workspace_bytes(int N, int C, long HxW, int G);
+int sd_group_norm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mu, float* rsig,
+                      int N, int C, long HxW, int G, float eps, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int sd_group_norm_bwd(const float* dy, const float* x, const float* mu, const float* rsig, const float* gamma,
+                      float* dx, float* dgamma, float* dbeta, int N, int C, long HxW, int G, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,20 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
          __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
 }
 
+// fp32 sum in a FIXED order (the butterfly's pairs, then the four rows left to right): equal bits on every call
+__device__ __forceinline__ float wave_sum_f32(float v) {
+  v += __int_as_float(SD_DPP_STEP(__float_as_int(v), 0xB1));
+  v += __int_as_float(SD_DPP_STEP(__float_as_int(v), 0x4E));
+  v += __int_as_float(SD_DPP_STEP(__float_as_int(v), 0x141));
+  v += __int_as_float(SD_DPP_STEP(__float_as_int(v), 0x140));
+  const int x = __float_as_int(v);
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(x, 0));
+  const float r1 = __int_as_float(__builtin_amdgcn_readlane(x, 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(x, 32));
+  const float r3 = __int_as_float(__builtin_amdgcn_readlane(x, 48));
+  return (r0 + r1) + (r2 + r3);
+}
+
 // max|.| of four gradients as the maximum of the BIT PATTERNS of |.| (non-negative floats order like unsigned
 // integers; a NaN's pattern lies above inf's, so it survives every maximum -- `a > b ? a : b` on floats drops a NaN
 // in its first operand, which let NaN gradients slip past the "non-finite -> float adds" test until round 6)

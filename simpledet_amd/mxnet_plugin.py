@@ -1351,6 +1351,88 @@ def _build_ops(mx):
         def declare_backward_dependency(self, out_grad, in_data, out_data):
             return [in_data[1], out_grad[0]]               # bbox_norm-inl.h:212-217
 
+    # ---- _contrib_GroupNorm: data, gamma, beta -> output, mean, var (1 visible) ----
+    #      (registered only by install(..., group_norm=True))
+    class GroupNorm(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def _dims(self, data):
+            N, C = int(data.shape[0]), int(data.shape[1])
+            return N, C, (_numel(data.shape) // (N * C) if N * C else 0), self.g["num_group"]
+
+        def _ws(self, like, dims):
+            wsb = int(lib().cdll.sd_group_norm_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2]), dims[3]))
+            return _scratch(like, wsb), wsb
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            # group_norm-inl.h:88-122.  mean / var are declared (N, C) and receive N * G floats (:199-200): the
+            # first N * G floats of the buffers are written, the rest is left as it was.
+            _no_add(req)
+            data, gamma, beta = in_data[:3]
+            _wait(data, gamma, beta)
+            N, C, HxW, G = dims = self._dims(data)
+            ws, wsb = self._ws(data, dims)
+            _call("sd_group_norm_fwd", _ptr(data), _ptr(gamma), _ptr(beta), _ptr(out_data[0]), _ptr(out_data[1]),
+                  _ptr(out_data[2]), N, C, ctypes.c_long(HxW), G, float(self.g["eps"]), _ptr(ws),
+                  ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # group_norm-inl.h:124-164: dX, dgamma and dbeta are plain stores (no Assign with req): kWriteTo
+            _require_write(req[:3], ["GroupNorm data gradient", "GroupNorm gamma gradient", "GroupNorm beta gradient"])
+            data, gamma = in_data[0], in_data[1]
+            _wait(out_grad[0], data, gamma, out_data[1], out_data[2])
+            N, C, HxW, G = dims = self._dims(data)
+            want_dx = _req(req[0]) != REQ["null"]
+            want = [_req(r) != REQ["null"] for r in req[1:3]]
+            if want[0] != want[1]:
+                raise RuntimeError("GroupNorm: the gamma and beta gradients are written together or not at all")
+            if want_dx or want[0]:
+                # (a frozen input with trainable gamma / beta: dX goes to scratch, as the reference always writes it)
+                dx = in_grad[0] if want_dx else _scratch(data, 4 * _numel(data.shape))
+                ws, wsb = self._ws(data, dims)
+                _call("sd_group_norm_bwd", _ptr(out_grad[0]), _ptr(data), _ptr(out_data[1]), _ptr(out_data[2]),
+                      _ptr(gamma), _ptr(dx), _ptr(in_grad[1]) if want[0] else None,
+                      _ptr(in_grad[2]) if want[0] else None, N, C, ctypes.c_long(HxW), G, _ptr(ws),
+                      ctypes.c_size_t(wsb), None)
+            _sync()
+
+    class GroupNormProp(CustomOpProp):
+        def __init__(self, num_group="32", eps="1e-5"):
+            # defaults: group_norm-inl.h:70-77
+            super().__init__(need_top_grad=True)
+            self.g = dict(num_group=int(num_group), eps=float(eps))
+            if self.g["num_group"] <= 0:
+                raise ValueError("GroupNorm: num_group must be positive, got %d" % self.g["num_group"])
+
+        def list_arguments(self):
+            return ["data", "gamma", "beta"]
+
+        def list_outputs(self):
+            return ["output", "mean", "var"]
+
+        num_visible_outputs = 1
+
+        def infer_shape(self, in_shape):
+            # GroupNormProp::InferShape (group_norm-inl.h:185-202): gamma / beta (C,); mean / var (N, C)
+            d = tuple(in_shape[0])
+            if len(d) < 2:
+                raise ValueError("GroupNorm: data should be (batch, channel, ...)")
+            if d[1] % self.g["num_group"]:
+                raise ValueError("GroupNorm: channels (%d) are not divisible by num_group (%d)"
+                                 % (d[1], self.g["num_group"]))
+            return [d, (d[1],), (d[1],)], [d, (d[0], d[1]), (d[0], d[1])]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return GroupNorm(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            # group_norm-inl.h:211-220
+            return [out_grad[0], out_data[1], out_data[2], in_data[0], in_data[1]]
+
+    ops["_contrib_GroupNorm"] = (GroupNormProp, ("contrib", "GroupNorm"))
     ops["_contrib_FocalLoss"] = (FocalLossProp, ("contrib", "FocalLoss"))
     ops["_contrib_BBoxNorm"] = (BBoxNormProp, ("contrib", "BBoxNorm"))
 
@@ -1528,14 +1610,16 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False):
+def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
     bbox_post: also BboxPostProcessing (opt-in: it replaces the reference's own CustomOp of Mask R-CNN's
     test graphs);
     retina_loss: also _contrib_FocalLoss and _contrib_BBoxNorm (opt-in: they replace native operators of
-    existing RetinaNet / RepPoints train graphs)."""
+    existing RetinaNet / RepPoints train graphs);
+    group_norm: also _contrib_GroupNorm (opt-in: it replaces a native operator of the GN Mask R-CNN, RepPoints
+    and EfficientNet graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -1551,6 +1635,8 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     if not retina_loss:
         table.pop("_contrib_FocalLoss")
         table.pop("_contrib_BBoxNorm")
+    if not group_norm:
+        table.pop("_contrib_GroupNorm")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1579,7 +1665,8 @@ def _namespaces(mx, ns):
     return out
 
 
-def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False):
+def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
+            group_norm=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1610,11 +1697,18 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
 
     `retina_loss=True` also replaces `_contrib_FocalLoss` and `_contrib_BBoxNorm` (models/retinanet/builder.py:294-332,
     models/RepPoints/builder.py:404,439,472) and lets patch_mxnext bind `X.focal_loss` / `X.bbox_norm` to the
-    aliases; opt-in because it changes which operators existing RetinaNet / RepPoints train graphs hold."""
-    props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss)
+    aliases; opt-in because it changes which operators existing RetinaNet / RepPoints train graphs hold.
+
+    `group_norm=True` also replaces `_contrib_GroupNorm` (mx.sym.contrib.GroupNorm: the normaliser of
+    config/scratch/mask_r50v1b_fpn_gn_scratch_2x.py and of the RepPoints / EfficientNet configs) and lets patch_mxnext
+    bind `X.group_norm` to the alias where mxnext has one; opt-in because it changes which operator those graphs hold.
+    mean / var keep the reference's declared shape (N, C); the first N * G floats are written."""
+    props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
+                     group_norm=group_norm)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
+    _state["group_norm"] = bool(group_norm)
     _state["fallbacks"] = []
     _state["stream"], _state["sync"] = stream, bool(sync)
 
@@ -1875,13 +1969,17 @@ def patch_mxnext(mxnext=None, mx=None):
     # install(retina_loss=True): X.focal_loss / X.bbox_norm build the FocalLoss / BBoxNorm aliases at call time.  The
     # wrappers' names pin the operator (models/retinanet/builder.py:296-332 passes the operators' own keyword
     # arguments), so they are bound without a probe; a default install() puts the saved originals back.
-    for attr, ctor in (("focal_loss", "FocalLoss"), ("bbox_norm", "BBoxNorm")):
+    # install(group_norm=True): the same for `X.group_norm` where mxnext has one.  That mxnext's
+    # normalizer_factory(type="gn") ends in mx.sym.contrib.GroupNorm, looked up at call time, is inferred: mxnext is
+    # not part of the reference tree.
+    for attr, ctor, flag in (("focal_loss", "FocalLoss", "retina_loss"), ("bbox_norm", "BBoxNorm", "retina_loss"),
+                             ("group_norm", "GroupNorm", "group_norm")):
         try:
             cur = getattr(mxnext, attr)
         except Exception:
             continue
         orig = cur._sd_original if getattr(cur, "_sd_alias", False) else cur
-        if not _state.get("retina_loss"):
+        if not _state.get(flag):
             if cur is not orig:
                 setattr(mxnext, attr, orig)
             continue
@@ -1891,7 +1989,7 @@ def patch_mxnext(mxnext=None, mx=None):
         loss._sd_alias, loss._sd_original = True, orig
         setattr(mxnext, "_sd_reference_" + attr, orig)
         setattr(mxnext, attr, loss)
-        seen[attr] = "install(retina_loss=True): bound to mx.sym.contrib.%s at call time" % ctor
+        seen[attr] = "install(%s=True): bound to mx.sym.contrib.%s at call time" % (flag, ctor)
         done.append("mxnext." + attr)
     try:
         import importlib

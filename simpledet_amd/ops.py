@@ -803,6 +803,117 @@ def bbox_norm_backward(gout, label, gdata=None, workspace=None):
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_GroupNorm  (operator_cxx/contrib/group_norm{-inl.h,.cu}, group_norm_helper.cu)
+# --------------------------------------------------------------------------------------------------
+def group_norm_workspace_bytes(N, C, HxW, num_group):
+    fn = lib().cdll.sd_group_norm_workspace_bytes
+    return int(fn(int(N), int(C), ctypes.c_long(int(HxW)), int(num_group)))
+
+
+def _gn_dims(x, gamma, num_group):
+    _chk(x, "data")
+    if x.dim() < 2:
+        raise ValueError("data should be (batch, channel, ...), got shape %s" % (tuple(x.shape),))
+    N, C = int(x.shape[0]), int(x.shape[1])
+    G = int(num_group)
+    if G <= 0 or C % G:
+        raise ValueError("channels (%d) are not divisible by num_group (%d)" % (C, G))
+    _chk(gamma, "gamma", ndim=1)
+    if gamma.shape[0] != C:
+        raise ValueError("gamma must have %d entries, got %d" % (C, gamma.shape[0]))
+    return N, C, (x.numel() // (N * C) if N * C else 0), G
+
+
+def _gn_ws(x, dims, workspace):
+    wsb = group_norm_workspace_bytes(*dims)
+    if workspace is None:
+        return torch.empty(wsb, device=x.device, dtype=torch.uint8)
+    if workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    return workspace
+
+
+def _gn_out(t, name, like=None, shape=None, at_least=None):
+    """an output the caller passed: float32, on the device, contiguous, of the given shape or size"""
+    _chk(t, name)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if at_least is not None and t.numel() < at_least:
+        raise ValueError("%s needs at least %d floats, got %d" % (name, at_least, t.numel()))
+    return t
+
+
+def group_norm_forward(x, gamma, beta, num_group=32, eps=1e-5, y=None, mu=None, rsig=None, workspace=None):
+    """_contrib_GroupNorm forward (group_norm.cu:71-91,198-233): x (N,C,...) NCHW, gamma / beta (C,)
+    -> y (the shape of x), mu (N,G), rsig (N,G) = 1 / sqrt(biased variance + eps), the variance taken about
+    the mean.  mu / rsig passed in may be larger (the reference declares them (N,C)): the first N*G floats are
+    written, the rest is left alone."""
+    N, C, HxW, G = dims = _gn_dims(x, gamma, num_group)
+    _chk(beta, "beta", ndim=1)
+    if beta.shape[0] != C:
+        raise ValueError("beta must have %d entries, got %d" % (C, beta.shape[0]))
+    y = torch.empty_like(x) if y is None else _gn_out(y, "y", shape=x.shape)
+    mu = torch.empty((N, G), device=x.device, dtype=torch.float32) if mu is None else _gn_out(mu, "mu", at_least=N * G)
+    rsig = (torch.empty((N, G), device=x.device, dtype=torch.float32) if rsig is None
+            else _gn_out(rsig, "rsig", at_least=N * G))
+    ws = _gn_ws(x, dims, workspace)
+    lib().call("sd_group_norm_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(mu), _p(rsig), N, C, ctypes.c_long(HxW), G,
+               float(eps), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return y, mu, rsig
+
+
+def group_norm_backward(dy, x, mu, rsig, gamma, num_group=32, dx=None, dgamma=None, dbeta=None, param_grads=True,
+                        workspace=None):
+    """_contrib_GroupNorm backward (group_norm.cu:93-196,235-298): dy / x (N,C,...), mu / rsig the forward's
+    (their first N*G floats are read), gamma (C,) -> dx, dgamma, dbeta (written, not accumulated).
+    param_grads=False skips dgamma / dbeta and returns None for them."""
+    N, C, HxW, G = dims = _gn_dims(x, gamma, num_group)
+    _gn_out(dy, "dy", shape=x.shape)
+    _gn_out(mu, "mu", at_least=N * G)
+    _gn_out(rsig, "rsig", at_least=N * G)
+    dx = torch.empty_like(x) if dx is None else _gn_out(dx, "dx", shape=x.shape)
+    if param_grads:
+        dgamma = torch.empty_like(gamma) if dgamma is None else _gn_out(dgamma, "dgamma", shape=gamma.shape)
+        dbeta = torch.empty_like(gamma) if dbeta is None else _gn_out(dbeta, "dbeta", shape=gamma.shape)
+        if N * HxW == 0:   # sums over nothing (the entry point writes nothing on an empty problem)
+            dgamma.zero_()
+            dbeta.zero_()
+    elif dgamma is not None or dbeta is not None:
+        raise ValueError("param_grads=False takes no dgamma / dbeta")
+    ws = _gn_ws(x, dims, workspace)
+    lib().call("sd_group_norm_bwd", _p(dy), _p(x), _p(mu), _p(rsig), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), N, C,
+               ctypes.c_long(HxW), G, _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return dx, dgamma, dbeta
+
+
+class GroupNormFunction(torch.autograd.Function):
+    """y, mu, rsig = GroupNormFunction.apply(x, gamma, beta, num_group, eps); mu and rsig carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, num_group, eps):
+        y, mu, rsig = group_norm_forward(x, gamma, beta, num_group, eps)
+        ctx.save_for_backward(x, gamma, mu, rsig)
+        ctx.num_group = int(num_group)
+        ctx.mark_non_differentiable(mu, rsig)
+        return y, mu, rsig
+
+    @staticmethod
+    def backward(ctx, dy, _dmu, _drsig):
+        x, gamma, mu, rsig = ctx.saved_tensors
+        need = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dx, dgamma, dbeta = group_norm_backward(dy.contiguous(), x, mu, rsig, gamma, ctx.num_group, param_grads=need)
+        return (dx if ctx.needs_input_grad[0] else None, dgamma if ctx.needs_input_grad[1] else None,
+                dbeta if ctx.needs_input_grad[2] else None, None, None)
+
+
+def group_norm(x, gamma, beta, num_group=32, eps=1e-5, return_stats=False):
+    """mx.sym.contrib.GroupNorm(data, gamma, beta, num_group=32, eps=1e-5) with autograd: y, or
+    (y, mu, rsig) with return_stats=True (the operator's two hidden outputs)."""
+    y, mu, rsig = GroupNormFunction.apply(x, gamma, beta, int(num_group), float(eps))
+    return (y, mu, rsig) if return_stats else y
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_NMS  (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
 # --------------------------------------------------------------------------------------------------
 def nms(dets, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300, threshold=0.7, already_sorted=False,
