@@ -60,9 +60,10 @@ const char* sd_last_dispatch(void);
  * their workspace sizes are unchanged); 9 sd_hard_nms_batched and sd_bbox_post_processing added (nothing
  * existing changes); 10 sd_retina_anchor_target, sd_focal_loss_fwd / _bwd and sd_bbox_norm_bwd with their
  * workspace queries added (nothing existing changes); 11 sd_group_norm_fwd / _bwd and
- * sd_group_norm_workspace_bytes added (nothing existing changes).
+ * sd_group_norm_workspace_bytes added (nothing existing changes); 12 sd_sigmoid_ce_fwd / _bwd and
+ * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).
  * sd_abi_version() returns the library's value; compare with this macro. */
-#define SD_ABI_VERSION 11
+#define SD_ABI_VERSION 12
 int sd_abi_version(void);
 /* kernel-variant knobs for A/B measurements (bench.py, tests); every variant computes the same
  * result.  Unknown keys are an error.  Knobs that disable parts of a kernel for profiling exist
@@ -844,6 +845,60 @@ int sd_group_norm_fwd(const float* x, const float* gamma, const float* beta, flo
 int sd_group_norm_bwd(const float* dy, const float* x, const float* mu, const float* rsig, const float* gamma,
                       float* dx, float* dgamma, float* dbeta, int N, int C, long HxW, int G, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_SigmoidCrossEntropy  (mx.sym.contrib.SigmoidCrossEntropy; the mask loss of
+ *   models/maskrcnn/builder.py:307-312 and models/msrcnn/builder.py:418-423) and the fused mask loss of
+ *   MaskFasterRcnnHead.get_loss (models/maskrcnn/builder.py:278-313), fp32.
+ *   replaces SigmoidCrossEntropyOp::Forward / Backward  operator_cxx/contrib/sigmoid_cross_entropy.cu:44-122,
+ *   -inl.h:68-119 (the reference has no CPU implementation: sigmoid_cross_entropy.cc:40,50 are LOG(FATAL)) and,
+ *   for the fused op, the split / stack / gather_nd / concat / reshape subgraph in front of it, whose backward
+ *   zero-fills and scatters a (R, K, P) gradient.
+ *   Element rule, x = logit, t = target; the reference's literals `-1.`, `1.` and `1. /` are doubles, so each
+ *   expression is evaluated partly in double and rounded to float once:
+ *       t == -1:  loss = 0, count = 0, gradient = +0.0.  The branch is on the target alone: the logit is not
+ *                 looked at (NaN and inf included) and the element does not reach the row sum.
+ *       else      loss = float((-1.0 * x) * double(t - [x >= 0]) + double(logf(1 + expf(x - 2 * x * [x >= 0]))))
+ *                 g    = float(1.0 / (1.0 + double(expf(-x))) - double(t)),   count = 1
+ *       per row:  loss_sum = sum loss,  count_sum = float(sum count) + 1e-5f,  out = loss_sum / count_sum,
+ *                 d = (g / count_sum) * grad_scale                      (two float roundings, as the reference)
+ *   Quirks kept: the operator's `normalization` parameter is parsed and never used (the division by the count
+ *   always happens; there is no such argument here); `out` is NOT multiplied by grad_scale, only the gradient
+ *   is; the backward recomputes count and count_sum itself.
+ *   sd_sigmoid_ce_fwd: data / label / loss / count (n, k) rows, out / loss_sum / count_sum (n).  loss and count
+ *     may be NULL: they are then not written (the full-size tensors the visible output does not need).
+ *   sd_sigmoid_ce_bwd: d_data (n, k) is written (kWriteTo), count_sum (n) too; count (n, k) may be NULL.
+ *   sd_mask_loss_fwd / _bwd: logits (R, K, P), cls (R) float -- the builder's mask_label --, target (R, P),
+ *     out / count_sum one float each, d_logits (R, K, P).  Equivalent to gathering plane (int)cls[r] of every
+ *     row, flattening to one row of R*P elements and applying the operator above with n = 1: out, count_sum and
+ *     the selected planes' gradients are bit-equal to that (the same element and reduction code runs).
+ *     The backward writes ALL of d_logits once, in one pass: +0.0 in the planes that are not selected, the
+ *     gradient in the selected one (kWriteTo; there is no add mode).  A row whose cls is NaN, negative or >= K
+ *     is fully ignored: its logits are not read, it is not counted, its gradient is zero (the reference's
+ *     gather_nd has undefined behaviour there).
+ *   Counts are integers reduced on the device and converted once (exact for any k; equal to the reference's
+ *   float sum of ones for k <= 2^24).  Row sums have a fixed order and use no floating-point atomics: two
+ *   calls give equal bits.  Partials live in the workspace (sd_*_workspace_bytes, monotone in their arguments)
+ *   and need no clearing; kernels only, no memset node, no host synchronisation, graph-capturable.  One long
+ *   row (n = 1, k ~ 2e5, the reference's call sites) is spread over k / 256 waves; short rows get a wave each.
+ *   16-byte loads and stores when k % 4 == 0 (P % 4 == 0) and the pointers are 16-byte aligned -- in the fused
+ *   backward the stores follow d_logits and the loads follow logits and target, separately; a scalar path
+ *   otherwise (4-byte alignment suffices), with equal bits.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a negative size, a null pointer (other
+ *   than loss / count), a NULL or too small workspace (SD_ERR_WORKSPACE); SD_ERR_UNSUPPORTED: n*k (R*K*P)
+ *   > 2^31 - 1 elements.  n = 0 or k = 0 (R, K or P = 0) succeed without a launch, the sizes still checked.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_sigmoid_ce_workspace_bytes(long n, long k);
+int sd_sigmoid_ce_fwd(const float* data, const float* label, float* out, float* loss, float* loss_sum,
+                      float* count, float* count_sum, long n, long k, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int sd_sigmoid_ce_bwd(const float* data, const float* label, float* d_data, float* count, float* count_sum,
+                      long n, long k, float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+size_t sd_mask_loss_workspace_bytes(int R, int K, long P);
+int sd_mask_loss_fwd(const float* logits, const float* cls, const float* target, float* out, float* count_sum,
+                     int R, int K, long P, void* workspace, size_t workspace_bytes, void* stream);
+int sd_mask_loss_bwd(const float* logits, const float* cls, const float* target, float* d_logits, int R, int K,
+                     long P, float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -293,3 +293,51 @@ def bbox_norm(data, label):
     the backward divides the head gradient by max(1, #(label >= 1) over the batch + 1)
     (bbox_norm-inl.h:116-126)."""
     return _BBoxNorm.apply(data, label)
+
+
+class _SigmoidCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, label, grad_scale):
+        data = data.contiguous()
+        out, _, _ = ops.sigmoid_cross_entropy_forward(data, label.contiguous())
+        ctx.save_for_backward(data, label)
+        ctx.grad_scale = grad_scale
+        return out
+
+    @staticmethod
+    def backward(ctx, _dy):
+        data, label = ctx.saved_tensors
+        return ops.sigmoid_cross_entropy_backward(data, label.contiguous(), ctx.grad_scale)[0], None, None
+
+
+def sigmoid_cross_entropy(data, label, grad_scale=1.0):
+    """mx.sym.contrib.SigmoidCrossEntropy (models/maskrcnn/builder.py:307-312): data / label (n, ...) -> out (n,),
+    the mean loss of every row over its labels != -1.  A loss operator: the backward IGNORES the incoming
+    gradient, as the reference's does (sigmoid_cross_entropy-inl.h:94-119 never reads out_grad), and grad_scale
+    scales the gradient only, not `out`.  The reference's `normalization` parameter is never used and has no
+    counterpart here."""
+    return _SigmoidCrossEntropy.apply(data, label, float(grad_scale))
+
+
+class _MaskLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, cls, target, grad_scale):
+        logits = logits.contiguous()
+        out, _ = ops.mask_loss_forward(logits, cls.contiguous(), target.contiguous())
+        ctx.save_for_backward(logits, cls, target)
+        ctx.grad_scale = grad_scale
+        return out
+
+    @staticmethod
+    def backward(ctx, _dy):
+        logits, cls, target = ctx.saved_tensors
+        return (ops.mask_loss_backward(logits, cls.contiguous(), target.contiguous(), ctx.grad_scale), None, None,
+                None)
+
+
+def mask_loss(logits, cls, target, grad_scale=1.0):
+    """MaskFasterRcnnHead.get_loss (models/maskrcnn/builder.py:278-313) as one op: logits (R, K, h, w), cls (R,)
+    float class of every RoI (mask_label), target (R, h, w) in {-1 ignore, 0, 1} -> the (1,) mask loss.  The
+    backward writes the dense (R, K, h, w) gradient once and IGNORES the incoming gradient, as the reference's
+    loss operator does; grad_scale scales the gradient only."""
+    return _MaskLoss.apply(logits, cls, target, float(grad_scale))

@@ -1606,11 +1606,162 @@ def _build_ops(mx):
             return []
 
     ops["BboxPostProcessing"] = (BboxPostProcessingProp, None)
+
+    # ---- _contrib_SigmoidCrossEntropy: data, label -> output, loss, loss_sum, count, count_sum (1 visible) and
+    #      the fused MaskLoss: logits, cls, target -> output, count_sum (1 visible)
+    #      (registered only by install(..., mask_loss=True)) ----
+    class SigmoidCrossEntropy(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        @staticmethod
+        def _rows(data):
+            n = int(data.shape[0])
+            return n, (_numel(data.shape) // n if n else 0)
+
+        def _ws(self, like, n, k):
+            wsb = int(lib().cdll.sd_sigmoid_ce_workspace_bytes(ctypes.c_long(n), ctypes.c_long(k)))
+            return _scratch(like, wsb), wsb
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            # sigmoid_cross_entropy-inl.h:68-92: all five outputs are plain stores
+            _no_add(req)
+            data, label = in_data[:2]
+            _wait(data, label)
+            n, k = self._rows(data)
+            ws, wsb = self._ws(data, n, k)
+            _call("sd_sigmoid_ce_fwd", _ptr(data), _ptr(label), _ptr(out_data[0]), _ptr(out_data[1]),
+                  _ptr(out_data[2]), _ptr(out_data[3]), _ptr(out_data[4]), ctypes.c_long(n), ctypes.c_long(k),
+                  _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # :94-119: d_data is a plain store (kWriteTo), count / count_sum are written again, out_grad is
+            # never read; the label gradient is not written by the reference and is zeroed here
+            _require_write(req[:1], ["SigmoidCrossEntropy data gradient"])
+            data, label = in_data[:2]
+            _wait(data, label)
+            if _req(req[0]) != REQ["null"]:
+                n, k = self._rows(data)
+                ws, wsb = self._ws(data, n, k)
+                _call("sd_sigmoid_ce_bwd", _ptr(data), _ptr(label), _ptr(in_grad[0]), _ptr(out_data[3]),
+                      _ptr(out_data[4]), ctypes.c_long(n), ctypes.c_long(k), float(self.g["grad_scale"]), _ptr(ws),
+                      ctypes.c_size_t(wsb), None)
+            if len(req) > 1:
+                self.assign(in_grad[1], req[1], 0)
+            _sync()
+
+    class SigmoidCrossEntropyProp(CustomOpProp):
+        def __init__(self, grad_scale="1.0", normalization="valid"):
+            # defaults: sigmoid_cross_entropy-inl.h:52-60.  `normalization` is parsed and never used by the
+            # reference's operator (the division by the count always happens): accepted and unused here as well
+            super().__init__(need_top_grad=False)
+            if normalization not in ("null", "valid"):
+                raise ValueError("SigmoidCrossEntropy: normalization must be 'null' or 'valid'")
+            self.g = dict(grad_scale=float(grad_scale), normalization=normalization)
+
+        def list_arguments(self):
+            return ["data", "label"]
+
+        def list_outputs(self):
+            return ["output", "loss", "loss_sum", "count", "count_sum"]
+
+        num_visible_outputs = 1
+
+        def infer_shape(self, in_shape):
+            # SigmoidCrossEntropyProp::InferShape (:152-172): out / loss_sum / count_sum (n,), loss / count as data
+            d = tuple(in_shape[0])
+            if len(d) < 2:
+                raise ValueError("SigmoidCrossEntropy: data should be (row, ...) with at least 2 dimensions")
+            label = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else d
+            if len(label) < 2:
+                raise ValueError("SigmoidCrossEntropy: label should have at least 2 dimensions")
+            o = (d[0],)
+            return [d, label], [o, d, o, d, o]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return SigmoidCrossEntropy(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [in_data[0], in_data[1], out_data[3], out_data[4]]     # :200-206
+
+    class MaskLoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        @staticmethod
+        def _dims(logits):
+            R, K = int(logits.shape[0]), int(logits.shape[1])
+            return R, K, (_numel(logits.shape) // (R * K) if R * K else 0)
+
+        def _ws(self, like, dims):
+            wsb = int(lib().cdll.sd_mask_loss_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2])))
+            return _scratch(like, wsb), wsb
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            logits, cls, target = in_data[:3]
+            _wait(logits, cls, target)
+            R, K, P = dims = self._dims(logits)
+            ws, wsb = self._ws(logits, dims)
+            _call("sd_mask_loss_fwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(out_data[0]), _ptr(out_data[1]),
+                  R, K, ctypes.c_long(P), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            _require_write(req[:1], ["MaskLoss logits gradient"])
+            logits, cls, target = in_data[:3]
+            _wait(logits, cls, target)
+            if _req(req[0]) != REQ["null"]:
+                R, K, P = dims = self._dims(logits)
+                ws, wsb = self._ws(logits, dims)
+                _call("sd_mask_loss_bwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(in_grad[0]), R, K,
+                      ctypes.c_long(P), float(self.g["grad_scale"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            for i in (1, 2):
+                if len(req) > i:
+                    self.assign(in_grad[i], req[i], 0)
+            _sync()
+
+    class MaskLossProp(CustomOpProp):
+        def __init__(self, grad_scale="1.0"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(grad_scale=float(grad_scale))
+
+        def list_arguments(self):
+            return ["logits", "cls", "target"]
+
+        def list_outputs(self):
+            return ["output", "count_sum"]
+
+        num_visible_outputs = 1
+
+        def infer_shape(self, in_shape):
+            # logits (R, K, h, w); cls R floats in any shape (the builder's mask_label is (batch, fg)); target R*h*w
+            d = tuple(in_shape[0])
+            if len(d) < 2:
+                raise ValueError("MaskLoss: logits should be (roi, class, ...)")
+            cls = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else (d[0],)
+            target = tuple(in_shape[2]) if len(in_shape) > 2 and in_shape[2] else (d[0],) + d[2:]
+            if _numel(cls) != d[0] or _numel(target) != d[0] * _numel(d[2:]):
+                raise ValueError("MaskLoss: cls %s / target %s do not match logits %s" % (cls, target, d))
+            return [d, cls, target], [(1,), (1,)]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return MaskLoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [in_data[0], in_data[1], in_data[2]]
+
+    ops["_contrib_SigmoidCrossEntropy"] = (SigmoidCrossEntropyProp, ("contrib", "SigmoidCrossEntropy"))
+    ops["MaskLoss"] = (MaskLossProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False):
+def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
+             mask_loss=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -1619,12 +1770,15 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     retina_loss: also _contrib_FocalLoss and _contrib_BBoxNorm (opt-in: they replace native operators of
     existing RetinaNet / RepPoints train graphs);
     group_norm: also _contrib_GroupNorm (opt-in: it replaces a native operator of the GN Mask R-CNN, RepPoints
-    and EfficientNet graphs)."""
+    and EfficientNet graphs);
+    mask_loss: also _contrib_SigmoidCrossEntropy and the fused MaskLoss (opt-in: they replace a native operator,
+    and a subgraph, of the Mask R-CNN train graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
     _state["mx"] = mx
     table = _build_ops(mx)
+    _state["all_ops"] = {name: (None, where) for name, (_, where) in table.items()}
     if not retina:
         table.pop("_contrib_GenProposalRetina")
     if not proposal:
@@ -1637,12 +1791,20 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
         table.pop("_contrib_BBoxNorm")
     if not group_norm:
         table.pop("_contrib_GroupNorm")
+    if not mask_loss:
+        table.pop("_contrib_SigmoidCrossEntropy")
+        table.pop("MaskLoss")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
     _state["registered"] = True
     _state["table"] = table
     return out
+
+
+def _build_ops_names():
+    """{name: (None, (namespace, attribute) or None)} of every operator _build_ops knows, opt-in ones included"""
+    return _state.get("all_ops") or {}
 
 
 def _namespaces(mx, ns):
@@ -1666,7 +1828,7 @@ def _namespaces(mx, ns):
 
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False):
+            group_norm=False, mask_loss=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1702,9 +1864,16 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     `group_norm=True` also replaces `_contrib_GroupNorm` (mx.sym.contrib.GroupNorm: the normaliser of
     config/scratch/mask_r50v1b_fpn_gn_scratch_2x.py and of the RepPoints / EfficientNet configs) and lets patch_mxnext
     bind `X.group_norm` to the alias where mxnext has one; opt-in because it changes which operator those graphs hold.
-    mean / var keep the reference's declared shape (N, C); the first N * G floats are written."""
+    mean / var keep the reference's declared shape (N, C); the first N * G floats are written.
+
+    `mask_loss=True` also replaces `_contrib_SigmoidCrossEntropy` (mx.sym.contrib.SigmoidCrossEntropy: the mask loss
+    of models/maskrcnn/builder.py:307-312 and models/msrcnn/builder.py:418-423), registers the fused `sd_MaskLoss`
+    and rebinds `models.maskrcnn.builder.MaskFasterRcnnHead.get_loss` (patch_mask_loss) so that Mask R-CNN train
+    graphs hold ONE node in place of split / stack / gather_nd / concat / reshape / SigmoidCrossEntropy; opt-in
+    because it changes which operators those graphs hold.  models/msrcnn/builder.py is not patched (its get_loss
+    also returns the gathered logits): it gets the aliased operator only."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
-                     group_norm=group_norm)
+                     group_norm=group_norm, mask_loss=mask_loss)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -1767,6 +1936,21 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
             original = cur._sd_original if getattr(cur, "_sd_alias", False) else cur
             setattr(target, attr, make(name, props[name], original))
             setattr(target, "_sd_reference_" + attr, original)
+    # an alias an earlier opt-in install() left for an operator that is not in the table now: the constructor it
+    # replaced is put back
+    for name, (_, where) in _build_ops_names().items():
+        if where is None or name in _state["table"]:
+            continue
+        ns, attr = where
+        for target in _namespaces(mx, ns):
+            cur = getattr(target, "__dict__", {}).get(attr)
+            if getattr(cur, "_sd_alias", False):
+                if cur._sd_original is None:
+                    delattr(target, attr)
+                else:
+                    setattr(target, attr, cur._sd_original)
+                if "_sd_reference_" + attr in getattr(target, "__dict__", {}):
+                    delattr(target, "_sd_reference_" + attr)
     # the fused FPN extractor has no single reference symbol to alias: rebind the builder method
     # that emits the subgraph (no reference file is edited)
     _state["fpn_patched"] = patch_fpn_roi_align(mx=mx)
@@ -1781,6 +1965,13 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
             if sys.modules.get(m) is not None:
                 unpatch_bbox_post(sys.modules[m])
         _state["bbox_post_patched"] = False
+    if mask_loss:
+        _state["mask_loss_patched"] = patch_mask_loss(mx=mx)
+    else:
+        import sys
+        if sys.modules.get(_MASK_LOSS_BUILDER) is not None:
+            unpatch_mask_loss(sys.modules[_MASK_LOSS_BUILDER])
+        _state["mask_loss_patched"] = False
     return props
 
 
@@ -1838,6 +2029,64 @@ def unpatch_bbox_post(builder_module):
     if original is None:
         return False
     cls.get_post_processing = original
+    return True
+
+
+_MASK_LOSS_BUILDER = "models.maskrcnn.builder"
+
+
+def patch_mask_loss(builder_module=None, mx=None):
+    """Route Mask R-CNN's mask loss to the fused device op WITHOUT editing the reference: rebinds
+    `MaskFasterRcnnHead.get_loss` of models/maskrcnn/builder.py:278-313 -- which splits the logits per image,
+    builds stack(arange, mask_ind), gathers every RoI's class plane with gather_nd, concatenates, reshapes to
+    (1, -1) and calls mx.sym.contrib.SigmoidCrossEntropy -- to a method that calls `self.get_output(conv_feat)` and
+    emits ONE mx.sym.Custom(op_type='sd_MaskLoss') over (mask_fcn_logit, mask_ind, mask_target) with
+    grad_scale = 128.0 if pMask.fp16 else 1.0, and returns `(mask_loss,)`.  The backward of that node writes the
+    dense logits gradient once instead of a zero fill, a scatter and the backward of concat and split.
+    install(mask_loss=True) calls this when the builder module is importable; returns True when the class was
+    patched.  The original method is kept as `_sd_reference_get_loss` (a second install() keeps the first
+    original); a default install() afterwards puts it back (unpatch_mask_loss).
+    models/msrcnn/builder.py is NOT patched: its get_loss also returns the gathered logits (the MaskIoU head
+    reads them), so it keeps its subgraph and gets the aliased SigmoidCrossEntropy only."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_MASK_LOSS_BUILDER)
+        except ModuleNotFoundError as e:
+            # the reference tree is not on the path: nothing to patch.  A missing dependency OF the builder, or
+            # any other error raised inside it, is the caller's to see
+            if e.name is None or not _MASK_LOSS_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_mask_loss(module, mx)
+    cls = getattr(builder_module, "MaskFasterRcnnHead", None)
+    if cls is None:
+        return False
+    original = cls.__dict__.get("_sd_reference_get_loss") or cls.get_loss
+
+    def get_loss(self, conv_feat, mask_target, mask_ind):
+        if "MaskLoss" not in (_state.get("table") or {}):
+            _state.setdefault("fallbacks", []).append(("MaskLoss", None, "sd_MaskLoss is not registered"))
+            return original(self, conv_feat, mask_target, mask_ind)
+        mask_fcn_logit = self.get_output(conv_feat)
+        scale_loss_shift = 128.0 if self.pMask.fp16 else 1.0
+        sym = mx.sym.Custom(logits=mask_fcn_logit, cls=mask_ind, target=mask_target, op_type=_PREFIX + "MaskLoss",
+                            grad_scale=_param_str(1.0 * scale_loss_shift), name="mask_loss")
+        return (sym[0],)
+
+    cls._sd_reference_get_loss = original
+    cls.get_loss = get_loss
+    return True
+
+
+def unpatch_mask_loss(builder_module):
+    """Put the reference's get_loss back."""
+    cls = getattr(builder_module, "MaskFasterRcnnHead", None)
+    original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
+    if original is None:
+        return False
+    cls.get_loss = original
     return True
 
 

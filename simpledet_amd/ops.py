@@ -914,6 +914,137 @@ def group_norm(x, gamma, beta, num_group=32, eps=1e-5, return_stats=False):
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_SigmoidCrossEntropy and the fused Mask R-CNN mask loss  (operator_cxx/contrib/
+# sigmoid_cross_entropy{-inl.h,.cu}; models/maskrcnn/builder.py:278-313)
+# --------------------------------------------------------------------------------------------------
+def sigmoid_cross_entropy_workspace_bytes(n, k):
+    return int(lib().cdll.sd_sigmoid_ce_workspace_bytes(ctypes.c_long(int(n)), ctypes.c_long(int(k))))
+
+
+def mask_loss_workspace_bytes(R, K, P):
+    return int(lib().cdll.sd_mask_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
+
+
+def _ce_ws(dev, wsb, workspace):
+    if workspace is None:
+        return torch.empty(wsb, device=dev, dtype=torch.uint8)
+    if workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    return workspace
+
+
+def _ce_rows(data, label):
+    """(n, k) of the operator: n = shape[0], k = everything else (sigmoid_cross_entropy-inl.h:80-84)"""
+    _chk(data, "data")
+    _chk(label, "label")
+    if data.dim() < 1 or label.numel() != data.numel():
+        raise ValueError("data %s and label %s must hold (n, k) rows of the same size"
+                         % (tuple(data.shape), tuple(label.shape)))
+    n = int(data.shape[0])
+    return n, (data.numel() // n if n else 0)
+
+
+def _ce_out(t, name, numel, dev, shape):
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=torch.float32)
+    _chk(t, name)
+    if t.numel() != numel:
+        raise ValueError("%s needs %d floats, got %d" % (name, numel, t.numel()))
+    return t
+
+
+def sigmoid_cross_entropy_forward(data, label, *, full=False, out=None, loss=None, loss_sum=None, count=None,
+                                  count_sum=None, workspace=None):
+    """SigmoidCrossEntropy forward (sigmoid_cross_entropy.cu:44-104): data / label (n, ...) rows -> out, loss_sum,
+    count_sum (n,); with full=True (or loss / count passed in) also the operator's hidden full-size outputs
+    loss and count, returned as (out, loss, loss_sum, count, count_sum) in the operator's order.  A label of -1
+    ignores its element whatever the logit is.  out is NOT scaled by grad_scale (only the gradient is)."""
+    n, k = _ce_rows(data, label)
+    dev = data.device
+    out = _ce_out(out, "out", n, dev, (n,))
+    loss_sum = _ce_out(loss_sum, "loss_sum", n, dev, (n,))
+    count_sum = _ce_out(count_sum, "count_sum", n, dev, (n,))
+    if full or loss is not None or count is not None:
+        loss = _ce_out(loss, "loss", n * k, dev, data.shape)
+        count = _ce_out(count, "count", n * k, dev, data.shape)
+    if n * k == 0:        # rows of nothing: an empty sum over an empty count (the entry point writes nothing)
+        out.zero_()
+        loss_sum.zero_()
+        count_sum.fill_(1e-5)
+        return (out, loss, loss_sum, count, count_sum) if loss is not None else (out, loss_sum, count_sum)
+    ws = _ce_ws(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
+    lib().call("sd_sigmoid_ce_fwd", _p(data), _p(label), _p(out), _p(loss), _p(loss_sum), _p(count), _p(count_sum),
+               ctypes.c_long(n), ctypes.c_long(k), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    if loss is not None:
+        return out, loss, loss_sum, count, count_sum
+    return out, loss_sum, count_sum
+
+
+def sigmoid_cross_entropy_backward(data, label, grad_scale=1.0, *, d_data=None, count=None, count_sum=None,
+                                   workspace=None):
+    """SigmoidCrossEntropy backward (sigmoid_cross_entropy.cu:66-122): d = ((sigmoid(x) - t) / count_sum) *
+    grad_scale, 0 where the label is -1; the count is recomputed, as the reference does.  The head gradient has
+    no part in it.  Returns (d_data, count_sum); `count` (full size) is written only when passed in."""
+    n, k = _ce_rows(data, label)
+    dev = data.device
+    d_data = _ce_out(d_data, "d_data", n * k, dev, data.shape)
+    count_sum = _ce_out(count_sum, "count_sum", n, dev, (n,))
+    if count is not None:
+        count = _ce_out(count, "count", n * k, dev, data.shape)
+    if n * k == 0:
+        count_sum.fill_(1e-5)
+        return d_data, count_sum
+    ws = _ce_ws(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
+    lib().call("sd_sigmoid_ce_bwd", _p(data), _p(label), _p(d_data), _p(count), _p(count_sum), ctypes.c_long(n),
+               ctypes.c_long(k), float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return d_data, count_sum
+
+
+def _mask_dims(logits, cls, target):
+    _chk(logits, "logits")
+    _chk(cls, "cls")
+    _chk(target, "target")
+    if logits.dim() < 2:
+        raise ValueError("logits should be (roi, class, ...), got shape %s" % (tuple(logits.shape),))
+    R, K = int(logits.shape[0]), int(logits.shape[1])
+    P = logits.numel() // (R * K) if R * K else 0
+    if cls.numel() != R or target.numel() != R * P:
+        raise ValueError("cls must hold %d floats and target %d, got %d and %d" % (R, R * P, cls.numel(),
+                                                                                   target.numel()))
+    return R, K, P
+
+
+def mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, workspace=None):
+    """The mask loss of MaskFasterRcnnHead.get_loss (models/maskrcnn/builder.py:278-313) in one op: logits
+    (R, K, h, w), cls (R,) float -- the builder's mask_label --, target (R, h, w).  Plane int(cls[r]) of every RoI
+    goes through SigmoidCrossEntropy as ONE row of R*h*w elements; bit-equal to sigmoid_cross_entropy_forward on
+    the gathered row.  A cls that is NaN, negative or >= K ignores its RoI.  Returns (out, count_sum), (1,) each."""
+    R, K, P = _mask_dims(logits, cls, target)
+    dev = logits.device
+    out = _ce_out(out, "out", 1, dev, (1,))
+    count_sum = _ce_out(count_sum, "count_sum", 1, dev, (1,))
+    if R * K * P == 0:    # an empty sum over an empty count (the entry point writes nothing)
+        out.zero_()
+        count_sum.fill_(1e-5)
+        return out, count_sum
+    ws = _ce_ws(dev, mask_loss_workspace_bytes(R, K, P), workspace)
+    lib().call("sd_mask_loss_fwd", _p(logits), _p(cls), _p(target), _p(out), _p(count_sum), R, K, ctypes.c_long(P),
+               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return out, count_sum
+
+
+def mask_loss_backward(logits, cls, target, grad_scale=1.0, *, d_logits=None, workspace=None):
+    """Backward of mask_loss_forward: ALL of d_logits (the shape of logits) is written once -- +0.0 in the planes
+    that are not selected and in ignored RoIs, the SigmoidCrossEntropy gradient in plane int(cls[r])."""
+    R, K, P = _mask_dims(logits, cls, target)
+    d_logits = _ce_out(d_logits, "d_logits", R * K * P, logits.device, logits.shape)
+    ws = _ce_ws(logits.device, mask_loss_workspace_bytes(R, K, P), workspace)
+    lib().call("sd_mask_loss_bwd", _p(logits), _p(cls), _p(target), _p(d_logits), R, K, ctypes.c_long(P),
+               float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return d_logits
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_NMS  (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
 # --------------------------------------------------------------------------------------------------
 def nms(dets, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300, threshold=0.7, already_sorted=False,
