@@ -61,7 +61,8 @@ const char* sd_last_dispatch(void);
  * existing changes); 10 sd_retina_anchor_target, sd_focal_loss_fwd / _bwd and sd_bbox_norm_bwd with their
  * workspace queries added (nothing existing changes); 11 sd_group_norm_fwd / _bwd and
  * sd_group_norm_workspace_bytes added (nothing existing changes); 12 sd_sigmoid_ce_fwd / _bwd and
- * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).
+ * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).  The
+ * sd_quant_int8_* entry points were added at 12 as well: no existing signature, layout or size contract moved.
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -899,6 +900,54 @@ int sd_mask_loss_fwd(const float* logits, const float* cls, const float* target,
                      int R, int K, long P, void* workspace, size_t workspace_bytes, void* stream);
 int sd_mask_loss_bwd(const float* logits, const float* cls, const float* target, float* d_logits, int R, int K,
                      long P, float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_Quantization_int8  (mx.sym.contrib.Quantization_int8; utils/graph_optimize.py:attach_quantize_node puts
+ *   one in front of the data and the weight of every Convolution / FullyConnected / Deconvolution), fp32.
+ *   replaces Quantization_int8Op::Forward / Backward  operator_cxx/contrib/quantization_int8-inl.h:113-294 in the
+ *   "minmax" mode without per-channel weights.  The tensor is n flat floats.
+ *   minmax: float[1], the operator's auxiliary state.  state: int32[2] = {countdown, init}, created as
+ *   {delay_quant, 1}: the reference keeps both in the Operator object, here they live on the device.
+ *   Forward, per call:
+ *     is_train && countdown > 0:  out = data (a copy), countdown -= 1, nothing else changes.
+ *     otherwise quantise.  When is_train && !fix_act_scale, with m = max |data|:
+ *         weight:                   minmax = m
+ *         activation, init != 0:    minmax = m if (double)minmax < 1e-6, else unchanged;  init = 0
+ *         activation, init == 0:    minmax = fl(fl(d * minmax) + fl((1.0f - d) * m)),  d = (float)ema_decay
+ *       then t = minmax, u = t / 127 (one IEEE divide) and out = roundf(c / u) * u with c = x for weights (the
+ *       reference does not clip them) and c = x clipped to [-t, t] for activations; a NaN x passes through;
+ *       roundf rounds halves away from zero; c / u is a correctly rounded divide, the product a second rounding.
+ *       With is_train == 0 neither minmax nor state changes and the call quantises whatever countdown is.
+ *       t == 0 gives NaN everywhere, as the reference's arithmetic does.  A NaN in data during a training
+ *       reduction is outside the contract (the reference's min / max reduce is not defined for it either).
+ *     A clearing kernel (only when the reduction spans several workgroups) and two kernels; the host reads nothing
+ *     back, so the call captures into a graph and replays with the state evolving on the device.  max |data| is
+ *     the unsigned maximum of the floats' bit patterns: it does not depend on any order.  Calls that need no
+ *     reduction (eval, fix_act_scale, a delay step) do not read data in the first kernel.  out may equal data.
+ *   Backward, one kernel: grad_clip == 0 ("ste", and every weight): dgrad = ograd; data and minmax may be NULL.
+ *     grad_clip != 0 ("clip"): dgrad = (-t <= x && x <= t) ? ograd : +0.0, t read from minmax on the device; a
+ *     NaN x gives 0.  req: SD_REQ_WRITE, SD_REQ_ADD (dgrad += ...) or SD_REQ_NULL (nothing is launched).
+ *   sd_quant_int8_weights_fwd: the weight forward above for T <= 1024 tensors in the same two kernels.  The five
+ *     tables are DEVICE arrays of T entries (data, out, minmax and state pointers, element counts); n_total is
+ *     the sum of the counts (it sizes the grids; every access is bounded by the counts themselves).  Outputs,
+ *     minmax and state are bit-equal to T single calls.  A tensor of 0 elements is skipped, like n == 0 below.
+ *   Pointers need 4-byte alignment only; 16-byte stores start at the output's first 16-byte boundary, inputs on
+ *   another phase are loaded by 4-byte accesses, with equal bits.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a null pointer, a negative count,
+ *   ema_decay outside [0, 1] (NaN included), an unknown req; SD_ERR_WORKSPACE: a NULL or too small workspace
+ *   (sd_quant_int8*_workspace_bytes; its content needs no clearing); SD_ERR_UNSUPPORTED: T > 1024 or more than
+ *   2^40 elements.  n == 0 (T == 0, n_total == 0) returns 0 without touching the device or the state.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_quant_int8_workspace_bytes(long n);
+int sd_quant_int8_fwd(const float* data, float* out, float* minmax, int* state, long n, int is_weight,
+                      int is_train, int fix_act_scale, double ema_decay, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int sd_quant_int8_bwd(const float* ograd, const float* data, const float* minmax, float* dgrad, long n,
+                      int grad_clip, int req, void* stream);
+size_t sd_quant_int8_weights_workspace_bytes(int T, long n_total);
+int sd_quant_int8_weights_fwd(const float* const* data_ptrs, float* const* out_ptrs, float* const* minmax_ptrs,
+                              int* const* state_ptrs, const long* counts, int T, long n_total, int is_train,
+                              int fix_act_scale, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1433,6 +1433,105 @@ def _build_ops(mx):
             return [out_grad[0], out_data[1], out_data[2], in_data[0], in_data[1]]
 
     ops["_contrib_GroupNorm"] = (GroupNormProp, ("contrib", "GroupNorm"))
+    # ---- _contrib_Quantization_int8: data -> output, aux minmax ----
+    #      (registered only by install(..., quant_int8=True))
+    class QuantizationInt8(CustomOp):
+        """Owns the step state {countdown, init} the reference keeps in its Operator object
+        (quantization_int8-inl.h:103-108), as two ints on the device; made on the first forward, on the data's
+        context (create_operator only knows the context's name)."""
+
+        def __init__(self, q):
+            super().__init__()
+            self.q = q
+            self.state = None
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            # quantization_int8-inl.h:125: CHECK_EQ(req[kOut], kWriteTo)
+            _require_write(req[:1], ["Quantization_int8 output"])
+            data, minmax = in_data[0], aux[0]
+            _wait(data, minmax)
+            if self.state is None:
+                self.state = _state["mx"].nd.array([self.q["delay_quant"], 1], ctx=data.context, dtype="int32")
+            n = _numel(data.shape)
+            if n and _req(req[0]) != REQ["null"]:
+                wsb = int(lib().cdll.sd_quant_int8_workspace_bytes(ctypes.c_long(n)))
+                ws = _scratch(data, wsb)
+                _call("sd_quant_int8_fwd", _ptr(data), _ptr(out_data[0]), _ptr(minmax), _ptr(self.state),
+                      ctypes.c_long(n), int(self.q["is_weight"]), int(bool(is_train)), int(self.q["fix_act_scale"]),
+                      float(self.q["ema_decay"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # :229-294: the reference only writes; add is this adapter's usual extension
+            r = _req(req[0])
+            clip = self.q["grad_mode"] == "clip" and not self.q["is_weight"]
+            _wait(out_grad[0], in_data[0], aux[0])
+            n = _numel(in_data[0].shape)
+            if n and r != REQ["null"]:
+                _call("sd_quant_int8_bwd", _ptr(out_grad[0]), _ptr(in_data[0]) if clip else None,
+                      _ptr(aux[0]) if clip else None, _ptr(in_grad[0]), ctypes.c_long(n), int(clip), r, None)
+            _sync()
+
+    class QuantizationInt8Prop(CustomOpProp):
+        PARAMS = ("quant_mode", "is_weight", "is_weight_perchannel", "delay_quant", "ema_decay", "grad_mode",
+                  "fix_act_scale")
+
+        def __init__(self, quant_mode="minmax", is_weight="True", is_weight_perchannel="False", delay_quant="0",
+                     ema_decay="0.99", grad_mode="ste", fix_act_scale="False"):
+            # defaults: quantization_int8-inl.h:85-100
+            super().__init__(need_top_grad=True)
+            self.q = dict(quant_mode=str(quant_mode), is_weight=_bool(is_weight),
+                          is_weight_perchannel=_bool(is_weight_perchannel), delay_quant=int(delay_quant),
+                          ema_decay=float(ema_decay), grad_mode=str(grad_mode), fix_act_scale=_bool(fix_act_scale))
+            why = self.sd_supports({k: str(v) for k, v in self.q.items()})
+            if why:
+                raise ValueError("Quantization_int8: " + why)
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls
+            back to the native constructor)."""
+            for k in params:
+                if k not in cls.PARAMS:
+                    return "parameter %r is not one this operator takes" % k
+            try:
+                delay = int(params.get("delay_quant", "0"))
+                decay = float(params.get("ema_decay", "0.99"))
+            except Exception as e:
+                return "unparsable parameter (%s)" % e
+            if params.get("quant_mode", "minmax") != "minmax":
+                return "quant_mode %r is not 'minmax'" % (params.get("quant_mode"),)
+            if _bool(params.get("is_weight", "True")) and _bool(params.get("is_weight_perchannel", "False")):
+                return "per-channel weights are not supported"
+            if params.get("grad_mode", "ste") not in ("ste", "clip"):
+                return "grad_mode %r is neither 'ste' nor 'clip'" % (params.get("grad_mode"),)
+            if delay < 0 or not 0.0 <= decay <= 1.0:
+                return "delay_quant=%d / ema_decay=%g out of range" % (delay, decay)
+            return ""
+
+        def list_arguments(self):
+            return ["data"]
+
+        def list_outputs(self):
+            return ["output"]
+
+        def list_auxiliary_states(self):
+            return ["minmax"]
+
+        def infer_shape(self, in_shape):
+            # Quantization_int8Prop::InferShape: data of rank 2 or 4, the output has its shape, the aux is (1,)
+            d = tuple(in_shape[0])
+            if len(d) not in (2, 4):
+                raise ValueError("Quantization_int8: data should be 2D or 4D, got shape %s" % (d,))
+            return [d], [d], [(1,)]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return QuantizationInt8(self.q)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [out_grad[0], in_data[0]]
+
+    ops["_contrib_Quantization_int8"] = (QuantizationInt8Prop, ("contrib", "Quantization_int8"))
     ops["_contrib_FocalLoss"] = (FocalLossProp, ("contrib", "FocalLoss"))
     ops["_contrib_BBoxNorm"] = (BBoxNormProp, ("contrib", "BBoxNorm"))
 
@@ -1761,7 +1860,7 @@ def _build_ops(mx):
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False):
+             mask_loss=False, quant_int8=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -1772,7 +1871,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     group_norm: also _contrib_GroupNorm (opt-in: it replaces a native operator of the GN Mask R-CNN, RepPoints
     and EfficientNet graphs);
     mask_loss: also _contrib_SigmoidCrossEntropy and the fused MaskLoss (opt-in: they replace a native operator,
-    and a subgraph, of the Mask R-CNN train graphs)."""
+    and a subgraph, of the Mask R-CNN train graphs);
+    quant_int8: also _contrib_Quantization_int8 (opt-in: it replaces the native operator that
+    utils/graph_optimize.py:attach_quantize_node puts into the int8 graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -1794,6 +1895,8 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     if not mask_loss:
         table.pop("_contrib_SigmoidCrossEntropy")
         table.pop("MaskLoss")
+    if not quant_int8:
+        table.pop("_contrib_Quantization_int8")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1828,7 +1931,7 @@ def _namespaces(mx, ns):
 
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False, mask_loss=False):
+            group_norm=False, mask_loss=False, quant_int8=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1871,9 +1974,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     and rebinds `models.maskrcnn.builder.MaskFasterRcnnHead.get_loss` (patch_mask_loss) so that Mask R-CNN train
     graphs hold ONE node in place of split / stack / gather_nd / concat / reshape / SigmoidCrossEntropy; opt-in
     because it changes which operators those graphs hold.  models/msrcnn/builder.py is not patched (its get_loss
-    also returns the gathered logits): it gets the aliased operator only."""
+    also returns the gathered logits): it gets the aliased operator only.
+
+    `quant_int8=True` also replaces `_contrib_Quantization_int8` (mx.sym.contrib.Quantization_int8: the node
+    utils/graph_optimize.py:162,169,182 attaches in front of every quantised operator's data and weight; config/int8/);
+    opt-in because it changes which operator those graphs hold.  `minmax` stays the operator's auxiliary state; the
+    step state (countdown, init) lives on the device with the operator instance.  Per-channel weights, a
+    quant_mode other than "minmax" and a grad_mode other than "ste" / "clip" fall back to the native constructor."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
-                     group_norm=group_norm, mask_loss=mask_loss)
+                     group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)

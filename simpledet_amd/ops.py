@@ -1045,6 +1045,167 @@ def mask_loss_backward(logits, cls, target, grad_scale=1.0, *, d_logits=None, wo
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_Quantization_int8  (operator_cxx/contrib/quantization_int8{-inl.h,.cu}; utils/graph_optimize.py)
+# --------------------------------------------------------------------------------------------------
+QUANT_GRAD_MODES = ("ste", "clip")
+
+
+def quant_int8_state(delay_quant=0, device=None):
+    """The operator's step state on the device: int32 {countdown, init} = {delay_quant, 1}, as the reference's
+    Operator object starts (quantization_int8-inl.h:103-108)."""
+    if int(delay_quant) < 0:
+        raise ValueError("delay_quant must be >= 0, got %d" % int(delay_quant))
+    return torch.tensor([int(delay_quant), 1], dtype=torch.int32, device="cuda" if device is None else device)
+
+
+def quant_int8_workspace_bytes(n):
+    return int(lib().cdll.sd_quant_int8_workspace_bytes(ctypes.c_long(int(n))))
+
+
+def quant_int8_weights_workspace_bytes(T, n_total):
+    return int(lib().cdll.sd_quant_int8_weights_workspace_bytes(int(T), ctypes.c_long(int(n_total))))
+
+
+def _q_aux(minmax, state):
+    _chk(minmax, "minmax")
+    _chk(state, "state", dtype=torch.int32)
+    if minmax.numel() != 1 or state.numel() != 2:
+        raise ValueError("minmax holds 1 float and state 2 ints, got %d and %d" % (minmax.numel(), state.numel()))
+
+
+def quantization_int8_forward(data, minmax, state, *, is_weight, is_train=True, fix_act_scale=False,
+                              ema_decay=0.99, out=None, workspace=None):
+    """Quantization_int8 forward (quantization_int8-inl.h:113-226): data (any shape, fp32), minmax (1,) the
+    operator's aux state, state = quant_int8_state(delay_quant).  minmax and state are updated in place on the
+    device (a delay step copies and counts down; a training step tracks max|data| -- directly for weights, with
+    the init rule and then the EMA for activations); out = round(clip(data) / u) * u with u = minmax / 127,
+    weights unclipped.  Nothing is read back: the call can be captured in a graph.  Returns out."""
+    _chk(data, "data")
+    _q_aux(minmax, state)
+    if out is None:
+        out = torch.empty_like(data)
+    else:
+        _chk(out, "out")
+        if out.shape != data.shape:
+            raise ValueError("out must have the shape of data")
+    if not 0.0 <= float(ema_decay) <= 1.0:
+        raise ValueError("ema_decay must lie in [0, 1], got %r" % (ema_decay,))
+    n = data.numel()
+    if n == 0:
+        return out
+    ws = _ce_ws(data.device, quant_int8_workspace_bytes(n), workspace)
+    lib().call("sd_quant_int8_fwd", _p(data), _p(out), _p(minmax), _p(state), ctypes.c_long(n), int(bool(is_weight)),
+               int(bool(is_train)), int(bool(fix_act_scale)), float(ema_decay), _p(ws), ctypes.c_size_t(ws.numel()),
+               _stream())
+    return out
+
+
+def quantization_int8_backward(out_grad, data, minmax, *, is_weight, grad_mode="ste", req="write", d_data=None):
+    """Quantization_int8 backward (quantization_int8-inl.h:229-294): "ste" and every weight pass out_grad on;
+    "clip" keeps it where -minmax <= data <= minmax (a NaN gives 0), minmax read on the device.  req 'write',
+    'add' (d_data += ...; d_data required) or 'null' (nothing runs).  Returns d_data."""
+    if grad_mode not in QUANT_GRAD_MODES:
+        raise ValueError("grad_mode must be one of %s, got %r" % (QUANT_GRAD_MODES, grad_mode))
+    if req not in REQ:
+        raise ValueError("req must be one of %s, got %r" % (sorted(REQ), req))
+    _chk(out_grad, "out_grad")
+    clip = grad_mode == "clip" and not is_weight
+    if clip:
+        _chk(data, "data")
+        _chk(minmax, "minmax")
+        if data.numel() != out_grad.numel() or minmax.numel() != 1:
+            raise ValueError("data must have the size of out_grad and minmax 1 float")
+    if d_data is None:
+        if req == "add":
+            raise ValueError("req='add' accumulates into d_data: pass it")
+        d_data = torch.empty_like(out_grad)
+    else:
+        _chk(d_data, "d_data")
+        if d_data.numel() != out_grad.numel():
+            raise ValueError("d_data must have the size of out_grad")
+    lib().call("sd_quant_int8_bwd", _p(out_grad), _p(data) if clip else None, _p(minmax) if clip else None,
+               _p(d_data), ctypes.c_long(out_grad.numel()), int(clip), REQ[req], _stream())
+    return d_data
+
+
+def quant_int8_weights_table(datas, outs, minmaxes, states):
+    """The device table of quantization_int8_weights_forward: (5, T) int64 -- data, out, minmax and state
+    addresses and element counts.  Build it once per set of buffers (it is copied from the host) and pass it as
+    `table=` to every step; the tensors must stay alive while it is used."""
+    T = len(datas)
+    if not (len(outs) == len(minmaxes) == len(states) == T):
+        raise ValueError("datas, outs, minmaxes and states must have one entry per tensor")
+    for d, o, m, s in zip(datas, outs, minmaxes, states):
+        _chk(d, "data")
+        _chk(o, "out")
+        _q_aux(m, s)
+        if o.shape != d.shape:
+            raise ValueError("out must have the shape of data")
+    dev = datas[0].device if T else "cuda"
+    rows = [[t.data_ptr() for t in col] for col in (datas, outs, minmaxes, states)] + [[d.numel() for d in datas]]
+    return torch.tensor(rows, dtype=torch.int64).reshape(5, T).to(dev)
+
+
+def quantization_int8_weights_forward(datas, minmaxes, states, *, is_train=True, fix_act_scale=False, outs=None,
+                                      table=None, workspace=None):
+    """The weight forward of quantization_int8_forward for a list of tensors in two kernels in all (behind a
+    one-workgroup clearing kernel when a tensor spans several workgroups): a segmented abs-max with one state
+    transition per tensor, then one element-wise pass over the segment table.  Outputs,
+    minmax and state are bit-equal to one call per tensor.  Returns the list of outputs."""
+    T = len(datas)
+    if table is None:
+        if outs is None:
+            outs = [torch.empty_like(d) for d in datas]
+        table = quant_int8_weights_table(datas, outs, minmaxes, states)
+    else:
+        # the kernels write what the table names: it is taken on trust (checking it would be a copy to the host per
+        # step), so the outputs it was built from must be named too
+        if outs is None or len(outs) != T:
+            raise ValueError("a table names its outputs: pass the outs it was built from")
+        _chk(table, "table", dtype=torch.int64, ndim=2)
+        if tuple(table.shape) != (5, T):
+            raise ValueError("table must be (5, %d), got %s" % (T, tuple(table.shape)))
+    n_total = sum(int(d.numel()) for d in datas)
+    if T == 0 or n_total == 0:
+        return outs
+    ws = _ce_ws(table.device, quant_int8_weights_workspace_bytes(T, n_total), workspace)
+    row = [ctypes.c_void_p(table[i].data_ptr()) for i in range(5)]
+    lib().call("sd_quant_int8_weights_fwd", row[0], row[1], row[2], row[3], row[4], T, ctypes.c_long(n_total),
+               int(bool(is_train)), int(bool(fix_act_scale)), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return outs
+
+
+class QuantizationInt8Function(torch.autograd.Function):
+    """out = QuantizationInt8Function.apply(data, minmax, state, is_weight, is_train, fix_act_scale, ema_decay,
+    grad_mode); minmax and state are updated in place and carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, data, minmax, state, is_weight, is_train, fix_act_scale, ema_decay, grad_mode):
+        if grad_mode not in QUANT_GRAD_MODES:
+            raise ValueError("grad_mode must be one of %s, got %r" % (QUANT_GRAD_MODES, grad_mode))
+        data = data.contiguous()
+        out = quantization_int8_forward(data, minmax, state, is_weight=is_weight, is_train=is_train,
+                                        fix_act_scale=fix_act_scale, ema_decay=ema_decay)
+        ctx.save_for_backward(data, minmax)
+        ctx.is_weight, ctx.grad_mode = bool(is_weight), grad_mode
+        return out
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        data, minmax = ctx.saved_tensors
+        d = quantization_int8_backward(out_grad.contiguous(), data, minmax, is_weight=ctx.is_weight,
+                                       grad_mode=ctx.grad_mode).view(data.shape)
+        return (d,) + (None,) * 7
+
+
+def quantization_int8(data, minmax, state, *, is_weight=True, is_train=True, fix_act_scale=False, ema_decay=0.99,
+                      grad_mode="ste"):
+    """mx.sym.contrib.Quantization_int8 with autograd (the reference's defaults)."""
+    return QuantizationInt8Function.apply(data, minmax, state, bool(is_weight), bool(is_train), bool(fix_act_scale),
+                                          float(ema_decay), grad_mode)
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_NMS  (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
 # --------------------------------------------------------------------------------------------------
 def nms(dets, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300, threshold=0.7, already_sorted=False,
