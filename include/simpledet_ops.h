@@ -63,6 +63,7 @@ const char* sd_last_dispatch(void);
  * sd_group_norm_workspace_bytes added (nothing existing changes); 12 sd_sigmoid_ce_fwd / _bwd and
  * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).  The
  * sd_quant_int8_* entry points were added at 12 as well: no existing signature, layout or size contract moved.
+ * So were the sd_fcos_* entry points (FCOS targets and losses): additions only.
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -948,6 +949,77 @@ size_t sd_quant_int8_weights_workspace_bytes(int T, long n_total);
 int sd_quant_int8_weights_fwd(const float* const* data_ptrs, float* const* out_ptrs, float* const* minmax_ptrs,
                               int* const* state_ptrs, const long* counts, int T, long n_total, int is_train,
                               int fix_act_scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * FCOS training head (config/fcos_r50v1_fpn_1x.py), fp32
+ *   sd_fcos_target replaces make_fcos_gt with its two Python CustomOps make_fcos_gt_preparation and
+ *     prepare_fcos_cls_gt (models/FCOS/input.py:14-263);
+ *   sd_fcos_loss_fwd / _bwd replace make_sigmoid_focal_loss, make_binary_cross_entropy_loss (loss and `grad`
+ *     symbols, with the pass-through CustomOps compute_focal_loss / compute_bce_loss) and IoULoss
+ *     (models/FCOS/loss.py:86-196), and the per-level reshape + concat in front of them (builder.py:207-214).
+ *   Location grid: level l has len(range(0, data_h, stride_l)) x len(range(0, data_w, stride_l)) locations at
+ *     index * stride + stride / 2; HW is their sum over the L <= SD_MAX_FPN_LEVELS levels
+ *     (sd_fcos_num_locations: hw_levels_host, L entries, may be NULL).  Image 0's im_info decides for the whole
+ *     batch, on the device: ori_h < ori_w takes the row-major grid, otherwise the transposed one
+ *     (loc_x_T / loc_y_T), and the padding mask loc_x < ori_w && loc_y < ori_h is image 0's as well.
+ *   sd_fcos_target: gt_bbox (N, M, 5) [x1, y1, x2, y2, cls], im_info (N, 3) ->
+ *       centerness (N, HW), offset (N, 4, HW), cls_id (N, HW) int32: -1 = ignored (padding), 0 = background,
+ *       1..K = class; cls_dense_or_null (N, K*HW): the reference's one-hot with ignore_label rows;
+ *       state int32[4]: [0] = #(cls_id >= 1) = the reference's sum(labels * mask), [1] = #(centerness !=
+ *       ignore_label && centerness > 0), [2] = the BITS of the float sum(centerness * [offset_left !=
+ *       ignore_offset && centerness > 0]) (reduced in a fixed order), [3] = 0.  The three are the normalisers of
+ *       the losses: they depend on the targets alone.
+ *     Per box, in the reference's float32 order: l, t, r, b; in-box = min >= 0; the stage test lower <= greatest
+ *     offset < upper on the offsets AFTER the in-box masking; box_size = (l + r) * (t + b), 1e10 when unassigned;
+ *     the first minimum wins (ties: the lowest box index; nothing assigned: box 0, whose offsets are then
+ *     ignore_offset); centerness = sqrt(min * min / (max * max)) * [left != ignore_offset] with IEEE divide and
+ *     sqrt -- a degenerate box gives 0/0 = NaN on its own line, as the reference does.  The stage bounds are two
+ *     HOST tables of L floats, or both NULL for the reference's [-1e-5, 64, 128, 256, 512] /
+ *     [64, 128, 256, 512, 1e5] (L <= 5).  ignore_offset and ignore_label must be negative (an in-box offset
+ *     is >= 0 and a label is 0 or 1; the reference uses -1 for both).  M > 128 is served in chunks.
+ *   sd_fcos_loss_fwd / _bwd: three HOST tables of L device pointers -- class logits (N, K, H_l, W_l), centerness
+ *     logits (N, 1, H_l, W_l), offset predictions (N, 4, H_l, W_l) after the graph's exp -- and hw_host, L sizes
+ *     H_l * W_l whose sum is the targets' HW; L = 1 is the concatenated form.  The tables are read during the
+ *     call only (they travel as kernel arguments).  losses: float[3] = centerness, classification, offset, the
+ *     order of FCOSFPNHead.get_loss.  The backward writes (kWriteTo) three gradients per level in the logits' own
+ *     shapes; it takes no top gradient (the reference's CustomOps ignore it, MakeLoss has grad_scale = 1).
+ *       focal:  p = 1 / (1 + exp(-x)), log(clip(p, 1e-5, 1)), -x * [x >= 0] - log(1 + exp(-|x|)), pow by gamma,
+ *               norm = state[0] + 1; the gradient is the reference's explicit `grad` expression.  alpha and
+ *               gamma are doubles: (1 - alpha) is formed in double and rounded once, as the Python float is.
+ *       BCE:    mask = label != ignore_label && label > 0, both logs clipped at 1e-5, normaliser state[1] + 1e-30,
+ *               gradient (p - label) * mask / normaliser.
+ *       IoU:    predictions clipped to [0, 1e4], mask = target_left != ignore_offset && centerness > 0,
+ *               -log((I + 1) / (U + 1)) * centerness, normaliser state[2] + 1e-30; the gradient is the true
+ *               derivative with respect to the unclipped prediction, zero outside [0, 1e4]; at pred == target
+ *               the min hands its gradient to the prediction.
+ *     Ignored locations get +0.0 in all three gradients.  The one-hot labels are never formed.  The sums run
+ *     over the concatenated index order whatever L is, in a fixed order without float atomics: L = 5 and L = 1,
+ *     two calls, and a graph replay give equal bits.  The class gradient moves in 16-byte items from each
+ *     gradient row's first 16-byte boundary, with a scalar path for the ragged ends and for logits on another
+ *     phase: any 4-byte aligned pointers give the same bits.
+ *   Kernels only (no memset node), no host synchronisation, graph-capturable.  Workspaces need no clearing.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a negative dimension, a null pointer, a NaN
+ *   parameter, a stride < 1, M == 0; SD_ERR_WORKSPACE: a NULL or too small workspace; SD_ERR_UNSUPPORTED: L > 8,
+ *   N * max(K, 4) * HW or N * M * 5 > 2^31 - 1, N > 65535 (sd_fcos_target: one grid row per image).  N == 0, K == 0 (losses) or HW == 0 succeed without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+int sd_fcos_num_locations(int data_h, int data_w, const int* strides_host, int L, long* hw_levels_host,
+                          long* hw_total_host);
+size_t sd_fcos_target_workspace_bytes(int N, long HW);
+int sd_fcos_target(const float* gt_bbox, const float* im_info, float* centerness, float* offset, int* cls_id,
+                   float* cls_dense_or_null, int* state, int N, int M, int K, int data_h, int data_w,
+                   const int* strides_host, const float* lower_host_or_null, const float* upper_host_or_null, int L,
+                   float ignore_offset, float ignore_label, void* workspace, size_t workspace_bytes, void* stream);
+size_t sd_fcos_loss_workspace_bytes(int N, int K, long HW);
+int sd_fcos_loss_fwd(const float* const* cls_ptrs_host, const float* const* ctr_ptrs_host,
+                     const float* const* off_ptrs_host, const long* hw_host, int L, const float* centerness,
+                     const float* offset, const int* cls_id, const int* state, float* losses, int N, int K,
+                     double alpha, double gamma, float ignore_offset, float ignore_label, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int sd_fcos_loss_bwd(const float* const* cls_ptrs_host, const float* const* ctr_ptrs_host,
+                     const float* const* off_ptrs_host, float* const* dcls_ptrs_host, float* const* dctr_ptrs_host,
+                     float* const* doff_ptrs_host, const long* hw_host, int L, const float* centerness,
+                     const float* offset, const int* cls_id, const int* state, int N, int K, double alpha,
+                     double gamma, float ignore_offset, float ignore_label, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1855,12 +1855,171 @@ def _build_ops(mx):
 
     ops["_contrib_SigmoidCrossEntropy"] = (SigmoidCrossEntropyProp, ("contrib", "SigmoidCrossEntropy"))
     ops["MaskLoss"] = (MaskLossProp, None)
+
+    # ---- the FCOS training head (registered only by install(..., fcos=True)):
+    #      fcos_target: gt_bbox, im_info -> centerness, offset, cls_id (int32), state (int32[4])
+    #      fcos_loss:   3 * L level tensors + the four targets -> centerness_loss, cls_loss, offset_loss ----
+    def _fcos_strides(v):
+        return _tuple(v, typ=int)
+
+    class FCOSTarget(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            gt, info = in_data[:2]
+            _wait(gt, info)
+            g = self.g
+            N, M = int(gt.shape[0]), int(gt.shape[1])
+            HW = int(out_data[0].shape[1])
+            wsb = int(lib().cdll.sd_fcos_target_workspace_bytes(N, ctypes.c_long(HW)))
+            ws = _scratch(gt, wsb)
+            _call("sd_fcos_target", _ptr(gt), _ptr(info), _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]),
+                  None, _ptr(out_data[3]), N, M, g["num_classifier"], g["data_size"][0], g["data_size"][1],
+                  _iarr(g["stride"]), None, None, len(g["stride"]), float(g["ignore_offset"]),
+                  float(g["ignore_label"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(req)):       # targets carry no gradient (the reference blocks it)
+                self.assign(in_grad[i], req[i], 0)
+
+    class FCOSTargetProp(CustomOpProp):
+        def __init__(self, data_size, stride, num_classifier, ignore_offset="-1", ignore_label="-1"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(data_size=_tuple(data_size, typ=int), stride=_fcos_strides(stride),
+                          num_classifier=int(num_classifier), ignore_offset=float(ignore_offset),
+                          ignore_label=float(ignore_label))
+            if len(self.g["data_size"]) != 2 or not 1 <= len(self.g["stride"]) <= 5:
+                raise ValueError("fcos_target: data_size is (h, w) and stride has 1 to 5 entries")
+
+        def list_arguments(self):
+            return ["gt_bbox", "im_info"]
+
+        def list_outputs(self):
+            return ["centerness", "offset", "cls_id", "state"]
+
+        def infer_shape(self, in_shape):
+            # PreMakeFCOSGTProp.infer_shape (models/FCOS/input.py:99-107)
+            gt = tuple(in_shape[0])
+            if len(gt) != 3 or gt[2] != 5:
+                raise ValueError("fcos_target: gt_bbox should be (N, M, 5), got %s" % (gt,))
+            n, (h, w) = gt[0], self.g["data_size"]
+            hw = sum(len(range(0, w, s)) * len(range(0, h, s)) for s in self.g["stride"])
+            info = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else (n, 3)
+            return [gt, info], [(n, hw), (n, 4, hw), (n, hw), (4,)]
+
+        def infer_type(self, in_type):
+            import numpy as np
+            return [in_type[0]] * 2, [in_type[0], in_type[0], np.int32, np.int32], []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return FCOSTarget(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    class FCOSLoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def _tables(self, in_data):
+            L = self.g["num_levels"]
+            cls, ctr, off = in_data[:L], in_data[L:2 * L], in_data[2 * L:3 * L]
+            N, K = int(cls[0].shape[0]), int(cls[0].shape[1])
+            hws = [_numel(c.shape) // (N * K) if N * K else 0 for c in cls]
+            tab = lambda arrs: (ctypes.c_void_p * L)(*[_ptr(a).value for a in arrs])
+            return L, N, K, hws, tab, (cls, ctr, off), in_data[3 * L:3 * L + 4]
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            L, N, K, hws, tab, (cls, ctr, off), (cen, offs, cid, state) = self._tables(in_data)
+            g = self.g
+            wsb = int(lib().cdll.sd_fcos_loss_workspace_bytes(N, K, ctypes.c_long(sum(hws))))
+            ws, losses = _scratch(cls[0], wsb), _scratch(cls[0], 12)
+            _call("sd_fcos_loss_fwd", tab(cls), tab(ctr), tab(off), (ctypes.c_long * L)(*hws), L, _ptr(cen),
+                  _ptr(offs), _ptr(cid), _ptr(state), _ptr(losses), N, K, g["alpha"], g["gamma"],
+                  float(g["ignore_offset"]), float(g["ignore_label"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+            for i in range(3):
+                self.assign(out_data[i], req[i], losses[i:i + 1])
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # the gradients do not depend on out_grad (compute_focal_loss / compute_bce_loss ignore it and
+            # MakeLoss has grad_scale = 1); all three are plain stores, one launch for every level
+            L, N, K, hws, tab, (cls, ctr, off), (cen, offs, cid, state) = self._tables(in_data)
+            _require_write(req[:3 * L], ["FCOSLoss logits gradient"] * (3 * L))
+            _wait(*in_data)
+            live = [_req(r) != REQ["null"] for r in req[:3 * L]]
+            if any(live):
+                if not all(live):
+                    raise RuntimeError("FCOSLoss writes the gradients of all levels in one launch: req must be "
+                                       "'write' for every logit tensor or 'null' for every one")
+                g = self.g
+                _call("sd_fcos_loss_bwd", tab(cls), tab(ctr), tab(off), tab(in_grad[:L]), tab(in_grad[L:2 * L]),
+                      tab(in_grad[2 * L:3 * L]), (ctypes.c_long * L)(*hws), L, _ptr(cen), _ptr(offs), _ptr(cid),
+                      _ptr(state), N, K, g["alpha"], g["gamma"], float(g["ignore_offset"]),
+                      float(g["ignore_label"]), None)
+            for i in range(3 * L, len(req)):
+                self.assign(in_grad[i], req[i], 0)
+            _sync()
+
+    class FCOSLossProp(CustomOpProp):
+        def __init__(self, num_levels, alpha="0.25", gamma="2.0", ignore_offset="-1", ignore_label="-1"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(num_levels=int(num_levels), alpha=float(alpha), gamma=float(gamma),
+                          ignore_offset=float(ignore_offset), ignore_label=float(ignore_label))
+            if not 1 <= self.g["num_levels"] <= 8:
+                raise ValueError("fcos_loss: num_levels must lie in 1..8")
+
+        def list_arguments(self):
+            L = self.g["num_levels"]
+            return (["cls_logit_%d" % i for i in range(L)] + ["centerness_logit_%d" % i for i in range(L)]
+                    + ["offset_logit_%d" % i for i in range(L)] + ["centerness", "offset", "cls_id", "state"])
+
+        def list_outputs(self):
+            return ["centerness_loss", "cls_loss", "offset_loss"]
+
+        def infer_shape(self, in_shape):
+            L = self.g["num_levels"]
+            shapes = [tuple(s) for s in in_shape]
+            if len(shapes) != 3 * L + 4:
+                raise ValueError("fcos_loss: expected %d inputs, got %d" % (3 * L + 4, len(shapes)))
+            n, k, hw = shapes[0][0], shapes[0][1], 0
+            for i in range(L):
+                c, t, o = shapes[i], shapes[L + i], shapes[2 * L + i]
+                if not (len(c) >= 3 and c[:2] == (n, k) and t == (n, 1) + c[2:] and o == (n, 4) + c[2:]):
+                    raise ValueError("fcos_loss: level %d shapes %s / %s / %s do not belong together" % (i, c, t, o))
+                hw += _numel(c[2:])
+            targets = [(n, hw), (n, 4, hw), (n, hw), (4,)]
+            for want, got in zip(targets, shapes[3 * L:]):
+                if got and got != want:
+                    raise ValueError("fcos_loss: target shape %s, expected %s" % (got, want))
+            return shapes[:3 * L] + targets, [(1,)] * 3
+
+        def infer_type(self, in_type):
+            import numpy as np
+            L = self.g["num_levels"]
+            return [in_type[0]] * (3 * L + 2) + [np.int32, np.int32], [in_type[0]] * 3, []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return FCOSLoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return list(in_data)
+
+    ops["fcos_target"] = (FCOSTargetProp, None)
+    ops["fcos_loss"] = (FCOSLossProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False, quant_int8=False):
+             mask_loss=False, quant_int8=False, fcos=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -1873,7 +2032,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     mask_loss: also _contrib_SigmoidCrossEntropy and the fused MaskLoss (opt-in: they replace a native operator,
     and a subgraph, of the Mask R-CNN train graphs);
     quant_int8: also _contrib_Quantization_int8 (opt-in: it replaces the native operator that
-    utils/graph_optimize.py:attach_quantize_node puts into the int8 graphs)."""
+    utils/graph_optimize.py:attach_quantize_node puts into the int8 graphs);
+    fcos: also sd_fcos_target and sd_fcos_loss (opt-in: patch_fcos_loss puts them in place of the target and loss
+    subgraphs of the FCOS train graph)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -1897,6 +2058,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
         table.pop("MaskLoss")
     if not quant_int8:
         table.pop("_contrib_Quantization_int8")
+    if not fcos:
+        table.pop("fcos_target")
+        table.pop("fcos_loss")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -1931,7 +2095,7 @@ def _namespaces(mx, ns):
 
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False, mask_loss=False, quant_int8=False):
+            group_norm=False, mask_loss=False, quant_int8=False, fcos=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -1980,9 +2144,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     utils/graph_optimize.py:162,169,182 attaches in front of every quantised operator's data and weight; config/int8/);
     opt-in because it changes which operator those graphs hold.  `minmax` stays the operator's auxiliary state; the
     step state (countdown, init) lives on the device with the operator instance.  Per-channel weights, a
-    quant_mode other than "minmax" and a grad_mode other than "ste" / "clip" fall back to the native constructor."""
+    quant_mode other than "minmax" and a grad_mode other than "ste" / "clip" fall back to the native constructor.
+
+    `fcos=True` also registers `sd_fcos_target` and `sd_fcos_loss` and rebinds
+    `models.FCOS.builder.FCOSFPNHead.get_loss` (patch_fcos_loss) so that the FCOS train graph holds these two nodes
+    in place of make_fcos_gt's ~60 nodes with their two Python CustomOps, the five reshapes and the concat per
+    logit tensor, and the three loss subgraphs with their pass-through CustomOps; opt-in because it changes which
+    operators that graph holds.  The three outputs keep the reference's order (centerness, cls, offset)."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
-                     group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8)
+                     group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -2081,6 +2251,13 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_MASK_LOSS_BUILDER) is not None:
             unpatch_mask_loss(sys.modules[_MASK_LOSS_BUILDER])
         _state["mask_loss_patched"] = False
+    if fcos:
+        _state["fcos_patched"] = patch_fcos_loss(mx=mx)
+    else:
+        import sys
+        if sys.modules.get(_FCOS_BUILDER) is not None:
+            unpatch_fcos_loss(sys.modules[_FCOS_BUILDER])
+        _state["fcos_patched"] = False
     return props
 
 
@@ -2192,6 +2369,83 @@ def patch_mask_loss(builder_module=None, mx=None):
 def unpatch_mask_loss(builder_module):
     """Put the reference's get_loss back."""
     cls = getattr(builder_module, "MaskFasterRcnnHead", None)
+    original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
+    if original is None:
+        return False
+    cls.get_loss = original
+    return True
+
+
+_FCOS_BUILDER = "models.FCOS.builder"
+_FCOS_CONFIG = "config.fcos_r50v1_fpn_1x"     # where the reference's own CustomOpProps read throwout_param (input.py:88)
+
+
+def patch_fcos_loss(builder_module=None, mx=None):
+    """Route the FCOS training head to the device ops WITHOUT editing the reference: rebinds
+    `FCOSFPNHead.get_loss` of models/FCOS/builder.py:181-231 -- make_fcos_gt (two Python CustomOps and ~60 nodes),
+    five reshapes and a concat per logit tensor, and three loss subgraphs behind compute_focal_loss /
+    compute_bce_loss / MakeLoss -- to a method that calls `self.get_output(conv_fpn_feat)` and emits
+        sd_fcos_target(gt_bbox, im_info) -> sd_fcos_loss(the 3 * L per-level tensors, the four targets)
+    and returns `(centerness_loss, cls_loss, offset_loss)`, the reference's order.  The parameters come from where
+    the reference reads them: data_size and stride from config.fcos_r50v1_fpn_1x.throwout_param at call time
+    (input.py:88-91), ignore_offset / ignore_label / focal_loss_alpha / focal_loss_gamma from p.loss_setting,
+    num_classifier and the level order from p.FCOSParam.  install(fcos=True) calls this when the builder module is
+    importable; returns True when the class was patched.  The original method is kept as `_sd_reference_get_loss`
+    (a second install() keeps the first original); a default install() afterwards puts it back."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_FCOS_BUILDER)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _FCOS_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_fcos_loss(module, mx)
+    cls = getattr(builder_module, "FCOSFPNHead", None)
+    if cls is None:
+        return False
+    original = cls.__dict__.get("_sd_reference_get_loss") or cls.get_loss
+
+    def get_loss(self, conv_fpn_feat, gt_bbox, im_info):
+        import sys
+        throwout = getattr(sys.modules.get(_FCOS_CONFIG), "throwout_param", None)
+        table = _state.get("table") or {}
+        why = ("sd_fcos_target / sd_fcos_loss are not registered" if "fcos_loss" not in table else
+               "%s.throwout_param is not set" % _FCOS_CONFIG if throwout is None else "")
+        if why:
+            _state.setdefault("fallbacks", []).append(("fcos_loss", None, why))
+            return original(self, conv_fpn_feat, gt_bbox, im_info)
+        p = self.p
+        centerness_logit_dict, cls_logit_dict, offset_logit_dict = self.get_output(conv_fpn_feat)
+        strides = tuple(p.FCOSParam.stride)
+        ignore = {"ignore_offset": _param_str(p.loss_setting.ignore_offset),
+                  "ignore_label": _param_str(p.loss_setting.ignore_label)}
+        # the reference binds the two inputs by name as well (builder.py:193-194)
+        targets = mx.sym.Custom(gt_bbox=mx.sym.var("gt_bbox"), im_info=mx.sym.var("im_info"),
+                                op_type=_PREFIX + "fcos_target", name="fcos_target",
+                                data_size=_param_str(tuple(throwout.data_size)), stride=_param_str(tuple(throwout.stride)),
+                                num_classifier=_param_str(p.FCOSParam.num_classifier), **ignore)
+        inputs = {}
+        for prefix, d in (("cls_logit_%d", cls_logit_dict), ("centerness_logit_%d", centerness_logit_dict),
+                          ("offset_logit_%d", offset_logit_dict)):
+            for i, stride in enumerate(strides):
+                inputs[prefix % i] = d[stride]
+        for i, name in enumerate(("centerness", "offset", "cls_id", "state")):
+            inputs[name] = targets[i]
+        loss = mx.sym.Custom(op_type=_PREFIX + "fcos_loss", name="fcos_loss", num_levels=_param_str(len(strides)),
+                             alpha=_param_str(p.loss_setting.focal_loss_alpha),
+                             gamma=_param_str(p.loss_setting.focal_loss_gamma), **ignore, **inputs)
+        return loss[0], loss[1], loss[2]
+
+    cls._sd_reference_get_loss = original
+    cls.get_loss = get_loss
+    return True
+
+
+def unpatch_fcos_loss(builder_module):
+    """Put the reference's get_loss back."""
+    cls = getattr(builder_module, "FCOSFPNHead", None)
     original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
     if original is None:
         return False

@@ -6,6 +6,7 @@ on the CPU and nothing falls back: non-CUDA tensors raise.
 
 Function names/arguments mirror the reference operators (operator_cxx/, see each docstring).
 """
+import collections
 import ctypes
 
 import torch
@@ -1203,6 +1204,180 @@ def quantization_int8(data, minmax, state, *, is_weight=True, is_train=True, fix
     """mx.sym.contrib.Quantization_int8 with autograd (the reference's defaults)."""
     return QuantizationInt8Function.apply(data, minmax, state, bool(is_weight), bool(is_train), bool(fix_act_scale),
                                           float(ema_decay), grad_mode)
+
+
+# --------------------------------------------------------------------------------------------------
+# FCOS training head  (models/FCOS/input.py make_fcos_gt, models/FCOS/loss.py, models/FCOS/builder.py get_loss)
+# --------------------------------------------------------------------------------------------------
+FcosTargets = collections.namedtuple("FcosTargets", "centerness offset cls_id state cls_dense")
+
+
+def fcos_num_locations(data_size, strides):
+    """(HW, [H_l * W_l per level]) of the reference's location grid (input.py:99-107)."""
+    h, w = (int(v) for v in data_size)
+    L = len(strides)
+    levels, total = (ctypes.c_long * max(L, 1))(), ctypes.c_long(0)
+    lib().call("sd_fcos_num_locations", h, w, _iarr(strides), L, levels, ctypes.byref(total))
+    return int(total.value), [int(levels[i]) for i in range(L)]
+
+
+def fcos_target_workspace_bytes(N, HW):
+    return int(lib().cdll.sd_fcos_target_workspace_bytes(int(N), ctypes.c_long(int(HW))))
+
+
+def fcos_loss_workspace_bytes(N, K, HW):
+    return int(lib().cdll.sd_fcos_loss_workspace_bytes(int(N), int(K), ctypes.c_long(int(HW))))
+
+
+def _fcos_out(t, name, shape, dev, dtype=torch.float32):
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=dtype)
+    _chk(t, name, dtype=dtype)
+    n = 1
+    for d in shape:
+        n *= int(d)
+    if t.numel() != n:
+        raise ValueError("%s needs %d elements, got %d" % (name, n, t.numel()))
+    return t
+
+
+def fcos_target(gt_bbox, im_info, data_size, strides, num_classifier, *, ignore_offset=-1.0, ignore_label=-1.0,
+                stage_lower=None, stage_upper=None, dense=False, centerness=None, offset=None, cls_id=None,
+                cls_dense=None, state=None, workspace=None):
+    """make_fcos_gt (models/FCOS/input.py:180-263) in one kernel: gt_bbox (N, M, 5) [x1, y1, x2, y2, cls],
+    im_info (N, 3), data_size (h, w), the FPN strides.  Returns FcosTargets: centerness (N, HW), offset (N, 4, HW),
+    the compact cls_id (N, HW) int32 (-1 ignored, 0 background, 1..K class), the state block int32[4] with the three
+    normalisers of the losses (state[0] = the foreground count), and with dense=True the reference's one-hot
+    cls_gt (N, K * HW).  Nothing is read back from the device."""
+    _chk(gt_bbox, "gt_bbox", ndim=3)
+    _chk(im_info, "im_info", ndim=2)
+    N, M = int(gt_bbox.shape[0]), int(gt_bbox.shape[1])
+    if gt_bbox.shape[2] != 5 or tuple(im_info.shape) != (N, 3):
+        raise ValueError("gt_bbox should be (N, M, 5) and im_info (N, 3), got %s and %s"
+                         % (tuple(gt_bbox.shape), tuple(im_info.shape)))
+    if (stage_lower is None) != (stage_upper is None):
+        raise ValueError("stage_lower and stage_upper go together")
+    L, K = len(strides), int(num_classifier)
+    if stage_lower is not None and not (len(stage_lower) == len(stage_upper) == L):
+        raise ValueError("the stage bounds need one entry per stride")
+    HW, _ = fcos_num_locations(data_size, strides)
+    dev = gt_bbox.device
+    centerness = _fcos_out(centerness, "centerness", (N, HW), dev)
+    offset = _fcos_out(offset, "offset", (N, 4, HW), dev)
+    cls_id = _fcos_out(cls_id, "cls_id", (N, HW), dev, torch.int32)
+    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    if dense or cls_dense is not None:
+        cls_dense = _fcos_out(cls_dense, "cls_dense", (N, K * HW), dev)
+    if N * HW == 0:       # the entry point writes nothing: the normalisers of an empty problem are zero
+        state.zero_()
+    ws = _ce_ws(dev, fcos_target_workspace_bytes(N, HW), workspace)
+    lib().call("sd_fcos_target", _p(gt_bbox), _p(im_info), _p(centerness), _p(offset), _p(cls_id), _p(cls_dense),
+               _p(state), N, M, K, int(data_size[0]), int(data_size[1]), _iarr(strides),
+               None if stage_lower is None else _farr(stage_lower), None if stage_upper is None else _farr(stage_upper),
+               L, float(ignore_offset), float(ignore_label), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return FcosTargets(centerness, offset, cls_id, state, cls_dense)
+
+
+def _fcos_levels(cls_logits, ctr_logits, off_preds, targets):
+    """(N, K, HW, hw table) of three lists of level tensors (N, K, H, W) / (N, 1, H, W) / (N, 4, H, W); a single
+    level may also be the concatenated (N, K, HW) / (N, 1, HW) / (N, 4, HW) form."""
+    L = len(cls_logits)
+    if not (len(ctr_logits) == len(off_preds) == L) or L == 0:
+        raise ValueError("cls_logits, ctr_logits and off_preds need one tensor per level each")
+    N, K = int(cls_logits[0].shape[0]), int(cls_logits[0].shape[1])
+    hws = []
+    for i, (c, t, o) in enumerate(zip(cls_logits, ctr_logits, off_preds)):
+        for v, name in ((c, "cls_logits"), (t, "ctr_logits"), (o, "off_preds")):
+            _chk(v, "%s[%d]" % (name, i))
+            if v.dim() < 3 or int(v.shape[0]) != N:
+                raise ValueError("%s[%d] should be (N, C, ...), got %s" % (name, i, tuple(v.shape)))
+        hw = c.numel() // (N * K) if N * K else 0
+        if int(c.shape[1]) != K or t.numel() != N * hw or o.numel() != 4 * N * hw or int(o.shape[1]) != 4:
+            raise ValueError("level %d: cls %s, centerness %s and offset %s do not belong together"
+                             % (i, tuple(c.shape), tuple(t.shape), tuple(o.shape)))
+        hws.append(hw)
+    HW = sum(hws)
+    _chk(targets.centerness, "centerness")
+    _chk(targets.offset, "offset")
+    _chk(targets.cls_id, "cls_id", dtype=torch.int32)
+    _chk(targets.state, "state", dtype=torch.int32)
+    if (targets.centerness.numel() != N * HW or targets.offset.numel() != 4 * N * HW
+            or targets.cls_id.numel() != N * HW or targets.state.numel() < 4):
+        raise ValueError("the targets do not hold N = %d images of HW = %d locations" % (N, HW))
+    return N, K, HW, (ctypes.c_long * L)(*hws)
+
+
+def fcos_loss_forward(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25, gamma=2.0, ignore_offset=-1.0,
+                      ignore_label=-1.0, losses=None, workspace=None):
+    """The three FCOS losses (models/FCOS/loss.py:86-196) over per-level tensors, without reshape / concat and
+    without the one-hot labels: returns (3,) = centerness BCE, sigmoid focal, IoU -- the order of get_loss."""
+    N, K, HW, hws = _fcos_levels(cls_logits, ctr_logits, off_preds, targets)
+    dev = cls_logits[0].device
+    losses = _fcos_out(losses, "losses", (3,), dev)
+    if N * K * HW == 0:
+        return losses.zero_()
+    ws = _ce_ws(dev, fcos_loss_workspace_bytes(N, K, HW), workspace)
+    lib().call("sd_fcos_loss_fwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), hws, len(cls_logits),
+               _p(targets.centerness), _p(targets.offset), _p(targets.cls_id), _p(targets.state), _p(losses), N, K,
+               float(alpha), float(gamma), float(ignore_offset), float(ignore_label), _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return losses
+
+
+def fcos_loss_backward(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25, gamma=2.0, ignore_offset=-1.0,
+                       ignore_label=-1.0, d_cls=None, d_ctr=None, d_off=None):
+    """The gradients of fcos_loss_forward, written straight into per-level tensors of the inputs' shapes in ONE
+    launch: (d_cls list, d_ctr list, d_off list).  No top gradient enters (the reference's losses ignore it)."""
+    N, K, HW, hws = _fcos_levels(cls_logits, ctr_logits, off_preds, targets)
+    outs = []
+    for given, like, name in ((d_cls, cls_logits, "d_cls"), (d_ctr, ctr_logits, "d_ctr"), (d_off, off_preds, "d_off")):
+        if given is None:
+            given = [torch.empty_like(t) for t in like]
+        if len(given) != len(like):
+            raise ValueError("%s needs one tensor per level" % name)
+        for g, t in zip(given, like):
+            _chk(g, name)
+            if g.numel() != t.numel():
+                raise ValueError("%s must have the sizes of the inputs" % name)
+        outs.append(list(given))
+    if N * K * HW == 0:
+        return tuple(outs)
+    lib().call("sd_fcos_loss_bwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), _parr(outs[0]),
+               _parr(outs[1]), _parr(outs[2]), hws, len(cls_logits), _p(targets.centerness), _p(targets.offset),
+               _p(targets.cls_id), _p(targets.state), N, K, float(alpha), float(gamma), float(ignore_offset),
+               float(ignore_label), _stream())
+    return tuple(outs)
+
+
+class FcosLossFunction(torch.autograd.Function):
+    """losses = FcosLossFunction.apply(targets, alpha, gamma, ignore_offset, ignore_label, L, *cls, *ctr, *off) with
+    3 * L level tensors.  The backward returns the reference's gradients as they are: like the reference's loss
+    nodes it does not look at the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, targets, alpha, gamma, ignore_offset, ignore_label, L, *levels):
+        if len(levels) != 3 * L:
+            raise ValueError("expected %d level tensors, got %d" % (3 * L, len(levels)))
+        levels = [t.contiguous() for t in levels]
+        ctx.kw = dict(alpha=alpha, gamma=gamma, ignore_offset=ignore_offset, ignore_label=ignore_label)
+        ctx.targets, ctx.L = targets, L
+        ctx.save_for_backward(*levels)
+        return fcos_loss_forward(levels[:L], levels[L:2 * L], levels[2 * L:], targets, **ctx.kw)
+
+    @staticmethod
+    def backward(ctx, _out_grad):
+        levels, L = list(ctx.saved_tensors), ctx.L
+        d = fcos_loss_backward(levels[:L], levels[L:2 * L], levels[2 * L:], ctx.targets, **ctx.kw)
+        return (None,) * 6 + tuple(d[0]) + tuple(d[1]) + tuple(d[2])
+
+
+def fcos_loss(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25, gamma=2.0, ignore_offset=-1.0,
+              ignore_label=-1.0):
+    """The FCOS head's three losses with autograd over lists of level tensors: (3,) = centerness, classification,
+    offset.  `targets` is what fcos_target returned; off_preds are the offsets after the graph's exp."""
+    L = len(cls_logits)
+    return FcosLossFunction.apply(targets, float(alpha), float(gamma), float(ignore_offset), float(ignore_label), L,
+                                  *cls_logits, *ctr_logits, *off_preds)
 
 
 # --------------------------------------------------------------------------------------------------
