@@ -63,7 +63,8 @@ const char* sd_last_dispatch(void);
  * sd_group_norm_workspace_bytes added (nothing existing changes); 12 sd_sigmoid_ce_fwd / _bwd and
  * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).  The
  * sd_quant_int8_* entry points were added at 12 as well: no existing signature, layout or size contract moved.
- * So were the sd_fcos_* entry points (FCOS targets and losses): additions only.
+ * So were the sd_fcos_* entry points (FCOS targets and losses; sd_fcos_decode and sd_fcos_sigmoid, the test-time
+ * decode): additions only.
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1020,6 +1021,55 @@ int sd_fcos_loss_bwd(const float* const* cls_ptrs_host, const float* const* ctr_
                      float* const* doff_ptrs_host, const long* hw_host, int L, const float* centerness,
                      const float* offset, const int* cls_id, const int* state, int N, int K, double alpha,
                      double gamma, float ignore_offset, float ignore_label, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * FCOS test-time decode (config/fcos_r50v1_fpn_1x.py), fp32: FCOSFPNHead.get_all_proposal
+ * (models/FCOS/builder.py:234-259) in ONE call -- the ten sigmoid nodes (input_logits = 1), the five Python
+ * CustomOps get_proposal_single_stage (models/FCOS/utils.py:7-94), the concat and the Python CustomOp
+ * get_batch_proposal (utils.py:99-149).  Additions only: the ABI version stays 12.
+ *   Inputs: three HOST tables of L device pointers (the convention of sd_fcos_loss_fwd; read during the call
+ *     only) -- cls (N, C, H_l, W_l), ctr (N, 1, H_l, W_l), off (N, 4, H_l, W_l) -- im_info (N, 3) [h, w, scale] ON
+ *     THE DEVICE, three HOST tables of L ints (H_l, W_l, stride_l).  input_logits = 0: cls and ctr are
+ *     probabilities (the CustomOps' own contract); 1: raw logits, 1.0f / (1.0f + expf(-x)) is applied first, the
+ *     expression sd_fcos_sigmoid computes element-wise (equal bits).
+ *   Outputs, R = L * top_n, every element written by every call: bbox (N, R, 4), score (N, R, 81), cls_id (N, R),
+ *     and stage_out (N, R, 6) or NULL = the concat of the per-level rows [cls, fused, x1, y1, x2, y2] (builder.py:255).
+ *   Per level and image (the reference is the spec, quirks included):
+ *     cand = cls > thresh (float32; equality is no candidate), fused = cls * ctr (float32)       utils.py:17-19
+ *     count(cand) >= top_n: the top_n best of ALL C*H*W fused scores, descending;                 utils.py:32-36
+ *       flat idx = (c*H + y)*W + x, cls = c + 1 (integer arithmetic; the reference's float32 idx is exact up to
+ *       2^24, beyond that SD_ERR_UNSUPPORTED)
+ *     0 < count < top_n: the candidates in ascending flat index order; count == 0: nothing        utils.py:38-46
+ *     cx = x*stride + stride/2, x1 = clip(cx - off[0], 0, img_w), y1 = clip(cy - off[1], 0, img_h),
+ *       x2 = clip(cx + off[2], 0, img_w), y2 = clip(cy + off[3], 0, img_h)                          utils.py:49-55
+ *     "remove small bboxes" works on the 6-column row: (cls >= x1) && (fused >= y1) turns the row into six -1
+ *                                                                                                 utils.py:61-64
+ *     rows past the selected ones are -1                                                          utils.py:22,66
+ *   Per image: rows in descending order of fused; bbox = columns 2..5, cls_id = column 0, score zero except
+ *     score[i, r, int(cls_r)] = sqrtf(clip(fused_r, 1e-20f, 1)) for EVERY row -- cls = -1 (padding, masked)
+ *     indexes the LAST column, so column 80 of such rows holds sqrt(float32(1e-20)); column 0 is never written
+ *     by a real row (utils.py:110-124).  81 is the reference's constant: C > 80 is SD_ERR_UNSUPPORTED.
+ *   Ties (the project's choice; MXNet's order among equal keys is not documented): inside a level the lower flat
+ *     index first, in the batch sort stable in concat order (the lower level first); -0.0 == +0.0.
+ *   NaN (not part of the contract): a NaN cls is no candidate; NaN fused scores are ordered by their bits
+ *     (positive NaN before +inf, negative NaN after -inf); NaN offsets give NaN coordinates and never mask a row.
+ *   No host read of device data, no allocation, no float atomics, kernels only (the counters are cleared by a
+ *   kernel of the call): equal bits between calls and under graph replay.  Loads are scalar: any 4-byte aligned
+ *   tensor pointer works.  The workspace needs no clearing, must be 16-byte aligned and hold
+ *   sd_fcos_decode_workspace_bytes(N, C, L, hw_host, top_n) bytes, hw_host = L sizes H_l * W_l.
+ *   SD_ERR_INVALID_ARG: L outside 1..8, top_n < 1, C < 1, N < 0, a level size or stride < 1, a NaN threshold,
+ *   input_logits outside {0, 1}, a null pointer, a misaligned workspace; SD_ERR_UNSUPPORTED: C > 80,
+ *   C*H_l*W_l > 2^24, L*top_n > 16384, N > 65535; SD_ERR_WORKSPACE: a NULL or too small workspace.  N == 0
+ *   succeeds without a launch (the query then returns 256, as it does for invalid dimensions).
+ *   sd_fcos_sigmoid: p[i] = 1.0f / (1.0f + expf(-x[i])), n elements.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_fcos_decode_workspace_bytes(int N, int C, int L, const long* hw_host, int top_n);
+int sd_fcos_decode(const float* const* cls_ptrs_host, const float* const* ctr_ptrs_host,
+                   const float* const* off_ptrs_host, const float* im_info, const int* H_host, const int* W_host,
+                   const int* stride_host, int L, int N, int C, int top_n, float pre_nms_thresh, int input_logits,
+                   float* bbox, float* score, float* cls_id, float* stage_out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int sd_fcos_sigmoid(const float* x, float* p, long n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,7 +29,7 @@
 // rounded divide / sqrt).  Where the reference multiplies by a 0/1 mask and adds, the per-box loop selects
 // (equal bits for finite boxes); the two places where a NaN target can meet a zero mask -- the final centerness
 // and the forward sums -- keep the multiplication, so a degenerate box's NaN goes where the reference's goes.
-#include "common.h"
+#include "fcos_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -239,7 +239,7 @@ struct FocalTerms { float a, logp, minus_log, p; };
 template <int GAMMA>
 __device__ __forceinline__ FocalTerms fcos_focal_terms(const FcosLossArgs& a, float x, bool pos) {
   FocalTerms t;
-  t.p = 1.0f / (1.0f + expf(-x));
+  t.p = fcos_sigmoid(x);
   const float ge = x >= 0.f ? 1.0f : 0.0f;
   const float minus_logits_mask = (-1.0f * x) * ge;
   const float negative_abs = x - (2.0f * x) * ge;
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(kFcT) void fcos_loss_fwd_kernel(FcosLossArgs a) {
   for (unsigned i = blockIdx.x * kFcT + threadIdx.x; i < nloc; i += step) {
     const int n = (int)(i / a.HW), j = (int)(i - (unsigned)n * a.HW);
     const FcosLoc q = fcos_load_loc(a, n, j);
-    const float p = 1.0f / (1.0f + expf(-q.x_ctr));
+    const float p = fcos_sigmoid(q.x_ctr);
     const float bce = (-q.c) * logf(fcos_clip(p, 1e-5f, 1.0f)) - (1.0f - q.c) * logf(fcos_clip(1.0f - p, 1e-5f, 1.0f));
     s_ctr += bce * q.maskc;
     const IouTerms r = fcos_iou_terms(q);
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kFcT) void fcos_loss_bwd_kernel(FcosLossArgs a) {
     const int n = (int)(i / a.HW), j = (int)(i - (unsigned)n * a.HW);
     const int l = fcos_level(a, j), p = j - a.begin[l], hw = a.hw[l];
     const FcosLoc q = fcos_load_loc(a, n, j);
-    const float pc = 1.0f / (1.0f + expf(-q.x_ctr));
+    const float pc = fcos_sigmoid(q.x_ctr);
     a.dctr[l][(long)n * hw + p] = ((pc - q.c) * q.maskc) / norm_ctr;
     float g[4] = {0.f, 0.f, 0.f, 0.f};
     if (q.maski != 0.f) {

@@ -2014,12 +2014,83 @@ def _build_ops(mx):
 
     ops["fcos_target"] = (FCOSTargetProp, None)
     ops["fcos_loss"] = (FCOSLossProp, None)
+
+    # ---- the FCOS test-time decode (registered only by install(..., fcos_decode=True)):
+    #      fcos_decode: 3 * L level tensors (class logits, centerness logits, offsets) + im_info -> bbox, score, cls_id
+    class FCOSDecode(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            g = self.g
+            L = g["num_levels"]
+            cls, ctr, off, info = in_data[:L], in_data[L:2 * L], in_data[2 * L:3 * L], in_data[3 * L]
+            N, C = int(cls[0].shape[0]), int(cls[0].shape[1])
+            Hs, Ws = [int(c.shape[2]) for c in cls], [int(c.shape[3]) for c in cls]
+            tab = lambda arrs: (ctypes.c_void_p * L)(*[_ptr(a).value for a in arrs])
+            hws = (ctypes.c_long * L)(*[h * w for h, w in zip(Hs, Ws)])
+            wsb = int(lib().cdll.sd_fcos_decode_workspace_bytes(N, C, L, hws, g["pre_nms_top_n"]))
+            ws = _scratch(cls[0], wsb)
+            _call("sd_fcos_decode", tab(cls), tab(ctr), tab(off), _ptr(info), _iarr(Hs), _iarr(Ws), _iarr(g["stride"]),
+                  L, N, C, g["pre_nms_top_n"], float(g["pre_nms_thresh"]), int(g["input_logits"]), _ptr(out_data[0]),
+                  _ptr(out_data[1]), _ptr(out_data[2]), None, _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(req)):       # the reference's CustomOps have an empty backward (utils.py:70,127)
+                self.assign(in_grad[i], req[i], 0)
+
+    class FCOSDecodeProp(CustomOpProp):
+        def __init__(self, stride, pre_nms_top_n, pre_nms_thresh, input_logits="1"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(stride=_fcos_strides(stride), pre_nms_top_n=int(pre_nms_top_n),
+                          pre_nms_thresh=float(pre_nms_thresh), input_logits=_bool(input_logits))
+            self.g["num_levels"] = len(self.g["stride"])
+            if not 1 <= self.g["num_levels"] <= 8 or self.g["pre_nms_top_n"] < 1:
+                raise ValueError("fcos_decode: stride has 1 to 8 entries and pre_nms_top_n is >= 1")
+
+        def list_arguments(self):
+            L = self.g["num_levels"]
+            return (["cls_logit_%d" % i for i in range(L)] + ["centerness_logit_%d" % i for i in range(L)]
+                    + ["offset_logit_%d" % i for i in range(L)] + ["im_info"])
+
+        def list_outputs(self):
+            return ["bbox", "score", "cls_id"]
+
+        def infer_shape(self, in_shape):
+            L = self.g["num_levels"]
+            shapes = [tuple(s) for s in in_shape]
+            if len(shapes) != 3 * L + 1:
+                raise ValueError("fcos_decode: expected %d inputs, got %d" % (3 * L + 1, len(shapes)))
+            n, k = shapes[0][0], shapes[0][1]
+            for i in range(L):
+                c, t, o = shapes[i], shapes[L + i], shapes[2 * L + i]
+                if not (len(c) == 4 and c[:2] == (n, k) and t == (n, 1) + c[2:] and o == (n, 4) + c[2:]):
+                    raise ValueError("fcos_decode: level %d shapes %s / %s / %s do not belong together" % (i, c, t, o))
+            if shapes[3 * L] and shapes[3 * L] != (n, 3):
+                raise ValueError("fcos_decode: im_info shape %s, expected %s" % (shapes[3 * L], (n, 3)))
+            r = L * self.g["pre_nms_top_n"]
+            return shapes[:3 * L] + [(n, 3)], [(n, r, 4), (n, r, 81), (n, r)]
+
+        def infer_type(self, in_type):
+            return [in_type[0]] * (3 * self.g["num_levels"] + 1), [in_type[0]] * 3, []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return FCOSDecode(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    ops["fcos_decode"] = (FCOSDecodeProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False, quant_int8=False, fcos=False):
+             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -2034,7 +2105,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     quant_int8: also _contrib_Quantization_int8 (opt-in: it replaces the native operator that
     utils/graph_optimize.py:attach_quantize_node puts into the int8 graphs);
     fcos: also sd_fcos_target and sd_fcos_loss (opt-in: patch_fcos_loss puts them in place of the target and loss
-    subgraphs of the FCOS train graph)."""
+    subgraphs of the FCOS train graph);
+    fcos_decode: also sd_fcos_decode (opt-in: patch_fcos_decode puts it in place of the sigmoids and the two Python
+    CustomOps of the FCOS test graph)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -2061,6 +2134,8 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     if not fcos:
         table.pop("fcos_target")
         table.pop("fcos_loss")
+    if not fcos_decode:
+        table.pop("fcos_decode")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2095,7 +2170,7 @@ def _namespaces(mx, ns):
 
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False, mask_loss=False, quant_int8=False, fcos=False):
+            group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2150,9 +2225,16 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     `models.FCOS.builder.FCOSFPNHead.get_loss` (patch_fcos_loss) so that the FCOS train graph holds these two nodes
     in place of make_fcos_gt's ~60 nodes with their two Python CustomOps, the five reshapes and the concat per
     logit tensor, and the three loss subgraphs with their pass-through CustomOps; opt-in because it changes which
-    operators that graph holds.  The three outputs keep the reference's order (centerness, cls, offset)."""
+    operators that graph holds.  The three outputs keep the reference's order (centerness, cls, offset).
+
+    `fcos_decode=True` also registers `sd_fcos_decode` and rebinds `models.FCOS.builder.FCOSFPNHead.get_all_proposal`
+    (patch_fcos_decode) so that the FCOS test graph holds this ONE node in place of the ten sigmoid nodes, the five
+    Python CustomOps get_proposal_single_stage, the concat and the Python CustomOp get_batch_proposal; opt-in because
+    it changes which operators that graph holds, and independent of `fcos` (which keeps meaning the train head
+    alone).  Where the builder module is not importable nothing is rebound and `_state["fallbacks"]` says so."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
-                     group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos)
+                     group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
+                     fcos_decode=fcos_decode)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -2258,6 +2340,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_FCOS_BUILDER) is not None:
             unpatch_fcos_loss(sys.modules[_FCOS_BUILDER])
         _state["fcos_patched"] = False
+    if fcos_decode:
+        _state["fcos_decode_patched"] = patch_fcos_decode(mx=mx)
+        if not _state["fcos_decode_patched"]:
+            _state["fallbacks"].append(("fcos_decode", None, "%s.FCOSFPNHead is not importable" % _FCOS_BUILDER))
+    else:
+        import sys
+        if sys.modules.get(_FCOS_BUILDER) is not None:
+            unpatch_fcos_decode(sys.modules[_FCOS_BUILDER])
+        _state["fcos_decode_patched"] = False
     return props
 
 
@@ -2450,6 +2541,68 @@ def unpatch_fcos_loss(builder_module):
     if original is None:
         return False
     cls.get_loss = original
+    return True
+
+
+def patch_fcos_decode(builder_module=None, mx=None):
+    """Route the FCOS test-time decode to the device op WITHOUT editing the reference: rebinds
+    `FCOSFPNHead.get_all_proposal` of models/FCOS/builder.py:234-259 -- ten sigmoid nodes, five Python CustomOps
+    get_proposal_single_stage, a concat and the Python CustomOp get_batch_proposal -- to a method that calls
+    `self.get_output(conv_fpn_feat)` and emits
+        sd_fcos_decode(the 3 * L per-level tensors: raw class and centerness logits, offsets; im_info)
+    with input_logits = 1, sets `self._proposal` and returns `(score, bboxes)` as the reference does.  pre_nms_top_n and
+    pre_nms_thresh come from p.proposal, the strides and the level order from p.FCOSParam.stride.
+    install(fcos_decode=True) calls this when the builder module is importable; returns True when the class was
+    patched.  The original method is kept as `_sd_reference_get_all_proposal` (a second install() keeps the first
+    original); a default install() afterwards puts it back."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_FCOS_BUILDER)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _FCOS_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_fcos_decode(module, mx)
+    cls = getattr(builder_module, "FCOSFPNHead", None)
+    if cls is None:
+        return False
+    original = cls.__dict__.get("_sd_reference_get_all_proposal") or cls.get_all_proposal
+
+    def get_all_proposal(self, conv_fpn_feat, im_info):
+        table = _state.get("table") or {}
+        if "fcos_decode" not in table:
+            _state.setdefault("fallbacks", []).append(("fcos_decode", None, "sd_fcos_decode is not registered"))
+            return original(self, conv_fpn_feat, im_info)
+        p = self.p
+        centerness_logit_dict, cls_logit_dict, offset_logit_dict = self.get_output(conv_fpn_feat)
+        strides = tuple(p.FCOSParam.stride)
+        inputs = {}
+        for prefix, d in (("cls_logit_%d", cls_logit_dict), ("centerness_logit_%d", centerness_logit_dict),
+                          ("offset_logit_%d", offset_logit_dict)):
+            for i, stride in enumerate(strides):
+                inputs[prefix % i] = d[stride]
+        inputs["im_info"] = im_info
+        out = mx.sym.Custom(op_type=_PREFIX + "fcos_decode", name="fcos_decode", stride=_param_str(strides),
+                            pre_nms_top_n=_param_str(int(p.proposal.pre_nms_top_n)),
+                            pre_nms_thresh=_param_str(p.proposal.pre_nms_thresh), input_logits="1", **inputs)
+        bboxes, score = out[0], out[1]
+        self._proposal = score, bboxes
+        return score, bboxes
+
+    cls._sd_reference_get_all_proposal = original
+    cls.get_all_proposal = get_all_proposal
+    return True
+
+
+def unpatch_fcos_decode(builder_module):
+    """Put the reference's get_all_proposal back."""
+    cls = getattr(builder_module, "FCOSFPNHead", None)
+    original = cls.__dict__.get("_sd_reference_get_all_proposal") if cls is not None else None
+    if original is None:
+        return False
+    cls.get_all_proposal = original
     return True
 
 

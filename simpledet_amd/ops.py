@@ -1381,7 +1381,67 @@ def fcos_loss(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25, gamma=2
 
 
 # --------------------------------------------------------------------------------------------------
-# _contrib_NMS  (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
+# FCOS test-time decode  (models/FCOS/builder.py get_all_proposal, models/FCOS/utils.py: the CustomOps
+# get_proposal_single_stage and get_batch_proposal)
+# --------------------------------------------------------------------------------------------------
+def fcos_decode_workspace_bytes(N, C, hws, top_n):
+    """bytes of workspace of fcos_decode; hws = H_l * W_l per level"""
+    L = len(hws)
+    return int(lib().cdll.sd_fcos_decode_workspace_bytes(int(N), int(C), L, (ctypes.c_long * max(L, 1))(*hws),
+                                                         int(top_n)))
+
+
+def fcos_sigmoid(x, out=None):
+    """1.0f / (1.0f + expf(-x)) element-wise: the sigmoid fcos_decode(input_logits=True) applies, same bits."""
+    _chk(x, "x")
+    out = _fcos_out(out, "out", tuple(x.shape), x.device)
+    lib().call("sd_fcos_sigmoid", _p(x), _p(out), ctypes.c_long(x.numel()), _stream())
+    return out
+
+
+def fcos_decode(cls_list, ctr_list, off_list, im_info, strides, top_n, pre_nms_thresh, input_logits=False,
+                return_stage=False, *, bbox=None, score=None, cls_id=None, stage=None, workspace=None):
+    """FCOSFPNHead.get_all_proposal (models/FCOS/builder.py:234-259) in one call: per level cls (N, C, H, W),
+    ctr (N, 1, H, W), off (N, 4, H, W); im_info (N, 3) on the device; strides, top_n = pre_nms_top_n and
+    pre_nms_thresh as the reference's CustomOp takes them.  input_logits=False: cls and ctr are probabilities (the
+    CustomOps' contract); True: raw logits, the sigmoid is fused.  Returns (bbox (N, R, 4), score (N, R, 81),
+    cls_id (N, R)) with R = L * top_n, and with return_stage=True also the concat of the per-level (N, top_n, 6)
+    rows.  Nothing is read back from the device."""
+    L = len(cls_list)
+    if L == 0 or not (len(ctr_list) == len(off_list) == len(strides) == L):
+        raise ValueError("cls_list, ctr_list, off_list and strides need one entry per level each")
+    _chk(im_info, "im_info", ndim=2)
+    N, C = int(cls_list[0].shape[0]), int(cls_list[0].shape[1])
+    if tuple(im_info.shape) != (N, 3):
+        raise ValueError("im_info should be (N, 3) = (%d, 3), got %s" % (N, tuple(im_info.shape)))
+    Hs, Ws = [], []
+    for i, (c, t, o) in enumerate(zip(cls_list, ctr_list, off_list)):
+        for v, name in ((c, "cls_list"), (t, "ctr_list"), (o, "off_list")):
+            _chk(v, "%s[%d]" % (name, i), ndim=4)
+        H, W = int(c.shape[2]), int(c.shape[3])
+        if tuple(c.shape) != (N, C, H, W) or tuple(t.shape) != (N, 1, H, W) or tuple(o.shape) != (N, 4, H, W):
+            raise ValueError("level %d: cls %s, centerness %s and offset %s do not belong together"
+                             % (i, tuple(c.shape), tuple(t.shape), tuple(o.shape)))
+        Hs.append(H)
+        Ws.append(W)
+    top_n = int(top_n)
+    R = L * max(top_n, 0)
+    dev = im_info.device
+    bbox = _fcos_out(bbox, "bbox", (N, R, 4), dev)
+    score = _fcos_out(score, "score", (N, R, 81), dev)
+    cls_id = _fcos_out(cls_id, "cls_id", (N, R), dev)
+    if return_stage or stage is not None:
+        stage = _fcos_out(stage, "stage", (N, R, 6), dev)
+    hws = [h * w for h, w in zip(Hs, Ws)]
+    ws = _ce_ws(dev, fcos_decode_workspace_bytes(N, C, hws, top_n), workspace)
+    lib().call("sd_fcos_decode", _parr(cls_list), _parr(ctr_list), _parr(off_list), _p(im_info), _iarr(Hs), _iarr(Ws),
+               _iarr(strides), L, N, C, top_n, float(pre_nms_thresh), int(bool(input_logits)), _p(bbox), _p(score),
+               _p(cls_id), _p(stage), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return (bbox, score, cls_id, stage) if return_stage else (bbox, score, cls_id)
+
+
+# --------------------------------------------------------------------------------------------------
+# _contrib_NMS (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
 # --------------------------------------------------------------------------------------------------
 def nms(dets, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300, threshold=0.7, already_sorted=False,
         threshold_ge=False, return_index=False):
