@@ -64,7 +64,7 @@ const char* sd_last_dispatch(void);
  * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).  The
  * sd_quant_int8_* entry points were added at 12 as well: no existing signature, layout or size contract moved.
  * So were the sd_fcos_* entry points (FCOS targets and losses; sd_fcos_decode and sd_fcos_sigmoid, the test-time
- * decode): additions only.
+ * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*.
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -282,6 +282,59 @@ int sd_roi_pool_v1_bwd(const float* out_grad, const float* rois, const float* ma
                        float* d_data, float* d_rois, int req_data, int req_rois, int B, int C,
                        int H, int W, int K, int pooled_h, int pooled_w, float spatial_scale,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_DeformablePSROIPooling  (mx.sym.contrib.DeformablePSROIPooling, upstream MXNet; the reference
+ *   calls it from models/TSD/poolings.py:87-100, 151-164).  The arithmetic is restated in DESIGN.md 4.15.
+ *   data (B,C,H,W), C == output_dim * group_size^2;  rois (K,5) [batch, x1, y1, x2, y2];
+ *   trans (K, 2*num_classes, part, part), not read when no_trans (num_classes is then taken as 1);
+ *   part_size 0 means pooled_size.  out, top_count (K, output_dim, pooled, pooled); top_count holds the
+ *   number of samples each output kept (0: the output is 0) and is the backward's state.
+ *   A batch index outside [0, B) pools nothing.  All arithmetic fp32.
+ *   The tap table of a RoI and the backward's per-wave d_trans sums live in LDS.  ONE predicate,
+ *   sd_deform_psroi_pool_supported(num_classes, pooled_size, sample_per_part) (1 / 0; num_classes = 1 when
+ *   no_trans), names the sets all four entry points below take -- forward and backward alike; every other set
+ *   is SD_ERR_UNSUPPORTED in each of them.  It holds when U = num_classes * pooled^2 and NT = U * sample_per_part^2
+ *   satisfy NT <= 4096 and 4 * (3 NT + 8 U + 8) <= 65536 bytes (e.g. 7 x 7 x 16 with up to 5 classes, 14 x 14 x 16;
+ *   not 32 x 32 x 4).  sd_set_tuning("deform_psroi_bwd_patch", 0) makes the backward add every tap to memory directly.
+ * ---------------------------------------------------------------------------------------------- */
+int sd_deform_psroi_pool_supported(int num_classes, int pooled_size, int sample_per_part);
+int sd_deform_psroi_pool_fwd(const float* data, const float* rois, const float* trans, float* out,
+                             float* top_count, int B, int C, int H, int W, int K, int num_classes,
+                             float spatial_scale, int output_dim, int group_size, int pooled_size,
+                             int part_size, int sample_per_part, float trans_std, int no_trans, void* stream);
+/*   d_data (B,C,H,W) and d_trans (shape of trans) honour their req (write / add / null); d_rois (K,5) is
+ *   zero-filled on write and untouched otherwise.  d_trans is bit-reproducible (fixed summation order);
+ *   d_data is summed with global float atomics and depends on the order the hardware serves them in. */
+int sd_deform_psroi_pool_bwd(const float* out_grad, const float* data, const float* rois, const float* trans,
+                             const float* top_count, float* d_data, float* d_rois, float* d_trans, int req_data,
+                             int req_rois, int req_trans, int B, int C, int H, int W, int K, int num_classes,
+                             float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size,
+                             int sample_per_part, float trans_std, int no_trans, void* stream);
+/* Fused TSD extractor = FPNRoIAlign_DeltaC / FPNRoIAlign_DeltaR.get_roi_feature, models/TSD/poolings.py:51-174:
+ *   fpn_roi_assign_offset (:12-47) -> one DeformablePSROIPooling per level on the masked RoIs and offsets
+ *   (group_size 1, output_dim == C, one class, part_size == pooled_size) -> add_n, as ONE launch.
+ *   feats_host / Hs / Ws / strides as in sd_fpn_roi_align_fwd, nlvl <= 5;  rois (B,R,4);
+ *   trans (B*R, 2, trans_part, trans_part), trans_part == pooled_size (DeltaC) or 1 (DeltaR: the
+ *   reference tiles a (B*R,2) offset over the bins; here it is read with stride 0);
+ *   out (B*R, C, pooled, pooled);  top_count (B*R, nlvl, pooled, pooled): the samples level l kept for a
+ *   bin -- channel-independent, so stored once per (RoI, level, bin).
+ *   A level a RoI is NOT assigned to pools the RoI (-1,-1,-1,-1) with zero offsets, as the reference's masks
+ *   make it; where that keeps samples (levels with 1/stride < 0.1) they are pooled and summed like the
+ *   reference does, and the backward returns their gradient to the same pixels.  d_trans receives the
+ *   assigned level's terms only. */
+int sd_fpn_deform_roi_pool_fwd(const float* const* feats_host, const int* Hs_host, const int* Ws_host,
+                               const int* strides_host, int nlvl, const float* rois, const float* trans,
+                               float* out, float* top_count, int B, int C, int R, int pooled_size,
+                               int trans_part, int sample_per_part, float trans_std,
+                               float roi_canonical_scale, float roi_canonical_level, void* stream);
+int sd_fpn_deform_roi_pool_bwd(const float* out_grad, const float* const* feats_host,
+                               float* const* d_feats_host, const int* Hs_host, const int* Ws_host,
+                               const int* strides_host, int nlvl, const float* rois, const float* trans,
+                               const float* top_count, float* d_trans, int req_data, int req_trans, int B,
+                               int C, int R, int pooled_size, int trans_part, int sample_per_part,
+                               float trans_std, float roi_canonical_scale, float roi_canonical_level,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_GenAnchor  (mx.sym.contrib.GenAnchor)

@@ -42,6 +42,7 @@ Knob g_knobs[] = {
     {"roi_align_bwd_lists", 0, false},   // workspace pre-pass: 1 RoI lists + tap tables per band unit (default), 2 lists only, 0 none
     {"roi_pool_fwd", 0, false},          // 1 (default) four planes in LDS per workgroup, 2 one plane, 0 wave per (roi, channel)
     {"roi_pool_bwd", 0, false},          // 1 (default) LDS planes, four channels per workgroup, 2 one channel, 0 global atomics
+    {"deform_psroi_bwd_patch", 0, false}, // 1 (default) (RoI, channel) patch summed in LDS, one atomic per touched pixel; 0 one global atomic per tap
     {"proposal_topk", 0, false},         // 0 by level size (default), 1 single workgroup, 2 multi-workgroup
     {"soft_nms_threads", 0, false},      // threads per problem: 64, 128 or 256 (default)
     {"deform_gemm_split", 0, false},     // 2 (default): scaled fp16 hi/lo split (needs operand maxima); 1: bf16 hi/lo split; 0: fp32 MFMA

@@ -971,6 +971,213 @@ def _build_ops(mx):
 
     ops["fpn_roi_align"] = (FPNRoIAlignProp, None)
 
+    def _dpsroi_supported(ncls, pooled, samples):
+        """the set forward AND backward take: the library's predicate, not a copy of its limits"""
+        if min(ncls, pooled, samples) < 1 or max(ncls, pooled, samples) > 4096:
+            return False
+        return bool(lib().cdll.sd_deform_psroi_pool_supported(int(ncls), int(pooled), int(samples)))
+
+    # ---- _contrib_DeformablePSROIPooling (upstream MXNet; models/TSD/poolings.py:87-100, 151-164):
+    #      data, rois[, trans] -> output, top_count (1 visible) ----
+    class DeformablePSROIPooling(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def _tail(self, data, rois, trans):
+            g = self.g
+            B, C, H, W = data.shape
+            ncls = 1 if g["no_trans"] else trans.shape[1] // 2
+            return (B, C, H, W, rois.shape[0], ncls, float(g["spatial_scale"]), g["output_dim"], g["group_size"],
+                    g["pooled_size"], g["part_size"], g["sample_per_part"], float(g["trans_std"]), int(g["no_trans"]),
+                    None)
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            data, rois = in_data[:2]
+            trans = None if self.g["no_trans"] else in_data[2]
+            _wait(*in_data)
+            _call("sd_deform_psroi_pool_fwd", _ptr(data), _ptr(rois), _ptr(trans), _ptr(out_data[0]),
+                  _ptr(out_data[1]), *self._tail(data, rois, trans))
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            data, rois = in_data[:2]
+            no_trans = self.g["no_trans"]
+            trans = None if no_trans else in_data[2]
+            _wait(out_grad[0], out_data[1], *in_data)
+            _call("sd_deform_psroi_pool_bwd", _ptr(out_grad[0]), _ptr(data), _ptr(rois), _ptr(trans),
+                  _ptr(out_data[1]), _ptr(in_grad[0]), _ptr(in_grad[1]), None if no_trans else _ptr(in_grad[2]),
+                  _req(req[0]), _req(req[1]), REQ["null"] if no_trans else _req(req[2]),
+                  *self._tail(data, rois, trans))
+            _sync()
+
+    class DeformablePSROIPoolingProp(CustomOpProp):
+        PARAMS = ("spatial_scale", "output_dim", "group_size", "pooled_size", "part_size", "sample_per_part",
+                  "trans_std", "no_trans")
+
+        def __init__(self, spatial_scale, output_dim, group_size, pooled_size, part_size="0", sample_per_part="1",
+                     trans_std="0.0", no_trans="False"):
+            super().__init__(need_top_grad=True)
+            params = dict(spatial_scale=spatial_scale, output_dim=output_dim, group_size=group_size,
+                          pooled_size=pooled_size, part_size=part_size, sample_per_part=sample_per_part,
+                          trans_std=trans_std, no_trans=no_trans)
+            why = self.sd_supports({k: str(v) for k, v in params.items()})
+            if why:
+                raise ValueError("DeformablePSROIPooling: " + why)
+            self.g = dict(spatial_scale=float(spatial_scale), output_dim=int(output_dim), group_size=int(group_size),
+                          pooled_size=int(pooled_size), part_size=int(part_size), sample_per_part=int(sample_per_part),
+                          trans_std=float(trans_std), no_trans=_bool(no_trans))
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls back to
+            the native constructor)."""
+            for k in params:
+                if k not in cls.PARAMS:
+                    return "parameter %r is not one this operator takes" % k
+            try:
+                float(params["spatial_scale"])
+                float(params.get("trans_std", "0.0"))
+                od, G, P = int(params["output_dim"]), int(params["group_size"]), int(params["pooled_size"])
+                part, S = int(params.get("part_size", "0")), int(params.get("sample_per_part", "1"))
+            except Exception as e:
+                return "missing or unparsable parameter (%s)" % e
+            if od < 1 or G < 1 or P < 1 or S < 1 or part < 0:
+                return "output_dim, group_size, pooled_size, sample_per_part must be >= 1 and part_size >= 0"
+            # the library's own predicate, here for ONE class: the class count is known only from the offsets' shape
+            # (infer_shape asks again with it, and can only raise by then)
+            if not _dpsroi_supported(1, P, S):
+                return ("pooled_size %d with sample_per_part %d: the RoI's tap table and the backward's sums do not "
+                        "fit in LDS (sd_deform_psroi_pool_supported)" % (P, S))
+            return ""
+
+        def list_arguments(self):
+            return ["data", "rois"] if self.g["no_trans"] else ["data", "rois", "trans"]
+
+        def list_outputs(self):
+            return ["output", "top_count"]
+
+        num_visible_outputs = 1
+
+        def infer_shape(self, in_shape):
+            g = self.g
+            d, b = in_shape[:2]
+            if len(d) != 4:
+                raise ValueError("data should be a 4D tensor")
+            if len(b) != 2 or b[1] != 5:
+                raise ValueError("bbox should be a 2D tensor of shape [batch, 5]")
+            if d[1] != g["output_dim"] * g["group_size"] ** 2:
+                raise ValueError("data has %d channels, output_dim * group_size^2 = %d"
+                                 % (d[1], g["output_dim"] * g["group_size"] ** 2))
+            if not g["no_trans"]:
+                t = in_shape[2]
+                part = g["part_size"] or g["pooled_size"]
+                if len(t) != 4 or t[0] != b[0] or t[1] % 2 or t[1] < 2 or tuple(t[2:]) != (part, part):
+                    raise ValueError("trans should have shape (rois, 2 * num_classes, %d, %d)" % (part, part))
+                if g["output_dim"] % (t[1] // 2):
+                    raise ValueError("output_dim is not a multiple of num_classes")
+                if not _dpsroi_supported(t[1] // 2, g["pooled_size"], g["sample_per_part"]):
+                    raise ValueError("DeformablePSROIPooling: %d classes with pooled_size %d and sample_per_part %d do "
+                                     "not fit the kernels' LDS (sd_deform_psroi_pool_supported)"
+                                     % (t[1] // 2, g["pooled_size"], g["sample_per_part"]))
+            o = (b[0], g["output_dim"], g["pooled_size"], g["pooled_size"])
+            return list(in_shape), [o, o]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return DeformablePSROIPooling(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [out_grad[0]] + list(in_data) + [out_data[1]]
+
+    ops["_contrib_DeformablePSROIPooling"] = (DeformablePSROIPoolingProp, ("contrib", "DeformablePSROIPooling"))
+
+    # ---- fpn_deform_roi_pool: the whole FPNRoIAlign_DeltaC / DeltaR.get_roi_feature subgraph
+    #      (models/TSD/poolings.py:51-174: fpn_roi_assign_offset -> per level DeformablePSROIPooling on masked
+    #      rois / offsets -> add_n) as ONE op: feats..., rois (B,R,4), trans (B*R,2,P,P) | (B*R,2) -> output ----
+    class FPNDeformRoIPool(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def _levels(self, feats):
+            ptrs = (ctypes.c_void_p * len(feats))(*[_ptr(f).value for f in feats])
+            return ptrs, _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
+
+        def _tail(self, feats, rois, trans):
+            g = self.g
+            B, C = feats[0].shape[:2]
+            return (B, C, rois.shape[1], g["pooled_size"], g["pooled_size"] if len(trans.shape) == 4 else 1,
+                    g["sample_per_part"], float(g["trans_std"]), float(g["scale0"]), float(g["lvl0"]), None)
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            feats, rois, trans = in_data[:-2], in_data[-2], in_data[-1]
+            _wait(*in_data)
+            ptrs, Hs, Ws = self._levels(feats)
+            _call("sd_fpn_deform_roi_pool_fwd", ptrs, Hs, Ws, _iarr(self.g["stride"]), len(feats), _ptr(rois),
+                  _ptr(trans), _ptr(out_data[0]), _ptr(out_data[1]), *self._tail(feats, rois, trans))
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            feats, rois, trans = in_data[:-2], in_data[-2], in_data[-1]
+            _wait(out_grad[0], out_data[1], *in_data)
+            rq = {_req(r) for r in req[:-2]}
+            if len(rq) != 1:
+                raise RuntimeError("fpn_deform_roi_pool: all feature gradients must share one req")
+            ptrs, Hs, Ws = self._levels(feats)
+            dptrs = self._levels(in_grad[:-2])[0]
+            _call("sd_fpn_deform_roi_pool_bwd", _ptr(out_grad[0]), ptrs, dptrs, Hs, Ws, _iarr(self.g["stride"]),
+                  len(feats), _ptr(rois), _ptr(trans), _ptr(out_data[1]), _ptr(in_grad[-1]), rq.pop(),
+                  _req(req[-1]), *self._tail(feats, rois, trans))
+            _sync()
+            self.assign(in_grad[-2], req[-2], 0)
+
+    class FPNDeformRoIPoolProp(CustomOpProp):
+        def __init__(self, rcnn_stride, pooled_size="7", sample_per_part="4", trans_std="0.1",
+                     roi_canonical_scale="224", roi_canonical_level="4"):
+            super().__init__(need_top_grad=True)
+            self.g = dict(stride=_tuple(rcnn_stride, typ=int), pooled_size=int(pooled_size),
+                          sample_per_part=int(sample_per_part), trans_std=float(trans_std),
+                          scale0=float(roi_canonical_scale), lvl0=float(roi_canonical_level))
+            g = self.g
+            if not 1 <= len(g["stride"]) <= 5:
+                raise ValueError("fpn_deform_roi_pool: 1 to 5 levels, got %d" % len(g["stride"]))
+            if not _dpsroi_supported(1, g["pooled_size"], g["sample_per_part"]):
+                raise ValueError("fpn_deform_roi_pool: pooled_size %d with sample_per_part %d does not fit the kernels' "
+                                 "LDS (sd_deform_psroi_pool_supported)" % (g["pooled_size"], g["sample_per_part"]))
+
+        def list_arguments(self):
+            return ["data_s{}".format(s) for s in self.g["stride"]] + ["rois", "trans"]
+
+        def list_outputs(self):
+            return ["output", "top_count"]
+
+        num_visible_outputs = 1
+
+        def infer_shape(self, in_shape):
+            feats, b, t = in_shape[:-2], in_shape[-2], in_shape[-1]
+            P = self.g["pooled_size"]
+            if len(feats) != len(self.g["stride"]):
+                raise ValueError("one feature map per stride expected")
+            if len(b) != 3 or b[2] != 4:
+                raise ValueError("bbox should be a 3D tensor of shape [batch, rois, 4]")
+            n = b[0] * b[1]
+            if tuple(t) not in ((n, 2, P, P), (n, 2)):
+                raise ValueError("trans should have shape (%d, 2, %d, %d) or (%d, 2), got %s" % (n, P, P, n, tuple(t)))
+            for f in feats:
+                if len(f) != 4 or tuple(f[:2]) != (b[0], feats[0][1]):
+                    raise ValueError("every level should be (batch, C, H, W)")
+            return list(in_shape), [(n, feats[0][1], P, P), (n, len(feats), P, P)]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return FPNDeformRoIPool(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [out_grad[0]] + list(in_data) + [out_data[1]]
+
+    ops["fpn_deform_roi_pool"] = (FPNDeformRoIPoolProp, None)
+
     # ---- _contrib_Proposal_v3: cls_prob, bbox_pred, im_info -> output [, score] ----
     class ProposalV3(CustomOp):
         def __init__(self, g):
@@ -2090,7 +2297,7 @@ def _build_ops(mx):
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False):
+             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -2107,7 +2314,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     fcos: also sd_fcos_target and sd_fcos_loss (opt-in: patch_fcos_loss puts them in place of the target and loss
     subgraphs of the FCOS train graph);
     fcos_decode: also sd_fcos_decode (opt-in: patch_fcos_decode puts it in place of the sigmoids and the two Python
-    CustomOps of the FCOS test graph)."""
+    CustomOps of the FCOS test graph);
+    tsd_pool: also _contrib_DeformablePSROIPooling and sd_fpn_deform_roi_pool (opt-in: the first replaces a native
+    operator, patch_tsd_pool puts the second in place of the two get_roi_feature subgraphs of the TSD graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -2136,6 +2345,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
         table.pop("fcos_loss")
     if not fcos_decode:
         table.pop("fcos_decode")
+    if not tsd_pool:
+        table.pop("_contrib_DeformablePSROIPooling")
+        table.pop("fpn_deform_roi_pool")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2170,7 +2382,7 @@ def _namespaces(mx, ns):
 
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False):
+            group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2231,10 +2443,16 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     (patch_fcos_decode) so that the FCOS test graph holds this ONE node in place of the ten sigmoid nodes, the five
     Python CustomOps get_proposal_single_stage, the concat and the Python CustomOp get_batch_proposal; opt-in because
     it changes which operators that graph holds, and independent of `fcos` (which keeps meaning the train head
-    alone).  Where the builder module is not importable nothing is rebound and `_state["fallbacks"]` says so."""
+    alone).  Where the builder module is not importable nothing is rebound and `_state["fallbacks"]` says so.
+
+    `tsd_pool=True` also replaces `_contrib_DeformablePSROIPooling` (mx.sym.contrib.DeformablePSROIPooling; parameter
+    sets that sd_deform_psroi_pool_supported refuses for one class fall back to the native constructor), registers `sd_fpn_deform_roi_pool` and
+    rebinds `FPNRoIAlign_DeltaC.get_roi_feature` and `FPNRoIAlign_DeltaR.get_roi_feature` of models/TSD/poolings.py
+    (patch_tsd_pool) so that a TSD graph holds TWO nodes in place of 2 x (level rule, eight masks, four
+    DeformablePSROIPooling, add_n); opt-in because it changes which operators those graphs hold."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
                      group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
-                     fcos_decode=fcos_decode)
+                     fcos_decode=fcos_decode, tsd_pool=tsd_pool)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -2349,6 +2567,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_FCOS_BUILDER) is not None:
             unpatch_fcos_decode(sys.modules[_FCOS_BUILDER])
         _state["fcos_decode_patched"] = False
+    if tsd_pool:
+        _state["tsd_pool_patched"] = patch_tsd_pool(mx=mx)
+        if not _state["tsd_pool_patched"]:
+            _state["fallbacks"].append(("fpn_deform_roi_pool", None, "%s is not importable" % _TSD_POOLINGS))
+    else:
+        import sys
+        if sys.modules.get(_TSD_POOLINGS) is not None:
+            unpatch_tsd_pool(sys.modules[_TSD_POOLINGS])
+        _state["tsd_pool_patched"] = False
     return props
 
 
@@ -2604,6 +2831,83 @@ def unpatch_fcos_decode(builder_module):
         return False
     cls.get_all_proposal = original
     return True
+
+
+_TSD_POOLINGS = "models.TSD.poolings"
+_TSD_EXTRACTORS = (("FPNRoIAlign_DeltaC", "delta_c"), ("FPNRoIAlign_DeltaR", "delta_r"))
+
+
+def patch_tsd_pool(builder_module=None, mx=None):
+    """Route TSD's two RoI extractors to the fused op WITHOUT editing the reference: rebinds
+    `FPNRoIAlign_DeltaC.get_roi_feature` and `FPNRoIAlign_DeltaR.get_roi_feature` of models/TSD/poolings.py:51-174
+    (fpn_roi_assign_offset -> per stride the masked rois and offsets, a concat with the batch column and
+    DeformablePSROIPooling -> add_n) to a method that emits ONE
+        sd_fpn_deform_roi_pool(the level features, rois (B,R,4), trans reshaped to (B*R,2,P,P) | (B*R,2))
+    node and returns the same (B*R, C, out, out) symbol (fp16 graphs: cast to fp32 before, back to fp16 after, as
+    :71-76, 104-105).  get_roi_feature_test calls get_roi_feature (:109-110, 173-174), so test graphs follow.
+    install(tsd_pool=True) calls this when the module is importable; returns True when both classes were patched.
+    The originals are kept as `_sd_reference_get_roi_feature`; a default install() afterwards puts them back."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_TSD_POOLINGS)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _TSD_POOLINGS.startswith(e.name):
+                raise
+            return False
+        return patch_tsd_pool(module, mx)
+    classes = [getattr(builder_module, n, None) for n, _ in _TSD_EXTRACTORS]
+    if any(c is None for c in classes):
+        return False
+
+    def make(original, tag, per_roi):
+        def get_roi_feature(self, conv_fpn_feat, rois, trans, image_rois, batch_image):
+            table = _state.get("table") or {}
+            if "fpn_deform_roi_pool" not in table:
+                _state.setdefault("fallbacks", []).append(("fpn_deform_roi_pool", None,
+                                                           "sd_fpn_deform_roi_pool is not registered"))
+                return original(self, conv_fpn_feat, rois, trans, image_rois, batch_image)
+            p = self.p
+            strides = tuple(int(s) for s in p.stride)
+            out = int(p.out_size)
+            fp16 = bool(getattr(p, "fp16", False))
+            feats = []
+            for s_ in strides:
+                f = conv_fpn_feat["stride%s" % s_]
+                if fp16:
+                    f = mx.sym.Cast(data=f, dtype="float32", name="fpn_stride%s_to_fp32" % s_)
+                feats.append(f)
+            tr = mx.sym.reshape(data=trans, shape=(-1, 2) if per_roi else (-1, 2, out, out),
+                                name=tag + "_offset_reshape")
+            # sample_per_part 4, trans_std 0.1: the constants of poolings.py:96-97, 160-161
+            sym = mx.sym.Custom(*feats, rois, tr, op_type=_PREFIX + "fpn_deform_roi_pool",
+                                rcnn_stride=_param_str(strides), pooled_size=_param_str(out), sample_per_part="4",
+                                trans_std="0.1", roi_canonical_scale=_param_str(p.roi_canonical_scale),
+                                roi_canonical_level=_param_str(p.roi_canonical_level), name=tag + "_pooled_feat")
+            roi_feat = sym[0]
+            if fp16:
+                roi_feat = mx.sym.Cast(data=roi_feat, dtype="float16", name=tag + "_roi_feat_to_fp16")
+            return roi_feat
+        return get_roi_feature
+
+    for cls, (_, tag) in zip(classes, _TSD_EXTRACTORS):
+        original = cls.__dict__.get("_sd_reference_get_roi_feature") or cls.get_roi_feature
+        cls._sd_reference_get_roi_feature = original
+        cls.get_roi_feature = make(original, tag, tag == "delta_r")
+    return True
+
+
+def unpatch_tsd_pool(builder_module):
+    """Put the reference's two get_roi_feature methods back."""
+    done = False
+    for n, _ in _TSD_EXTRACTORS:
+        cls = getattr(builder_module, n, None)
+        original = cls.__dict__.get("_sd_reference_get_roi_feature") if cls is not None else None
+        if original is not None:
+            cls.get_roi_feature = original
+            done = True
+    return done
 
 
 def _head_op(mx, sym):

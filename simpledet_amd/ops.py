@@ -409,6 +409,199 @@ def roi_pool_v1_backward(out_grad, rois, maxidx, data_shape, spatial_scale, req_
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_DeformablePSROIPooling (upstream MXNet) and TSD's fused FPN extractor
+# (models/TSD/poolings.py:51-174)
+# --------------------------------------------------------------------------------------------------
+def _req_of(r):
+    return REQ[r] if isinstance(r, str) else int(r)
+
+
+def _grad_buf(t, name, shape, rd, dev):
+    if t is None:
+        if rd == REQ["add"]:
+            raise ValueError("req 'add' needs the %s tensor to accumulate into" % name)
+        return torch.empty(shape, device=dev, dtype=torch.float32)
+    _chk(t, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    return t
+
+
+def _dpsroi_dims(data, rois, trans, output_dim, pooled_size, part_size, no_trans):
+    _chk(data, "data", ndim=4)
+    _chk(rois, "rois", ndim=2)
+    if rois.shape[1] != 5:
+        raise ValueError("rois should be a 2D tensor of shape [K, 5]")
+    K, P = rois.shape[0], int(pooled_size)
+    part = int(part_size) or P
+    ncls = 1
+    if not no_trans:
+        _chk(trans, "trans", ndim=4)
+        if trans.shape[0] != K or trans.shape[1] % 2 or trans.shape[1] < 2 or tuple(trans.shape[2:]) != (part, part):
+            raise ValueError("trans should have shape (K, 2 * num_classes, %d, %d), got %s"
+                             % (part, part, tuple(trans.shape)))
+        ncls = trans.shape[1] // 2
+    return K, P, ncls
+
+
+def deform_psroi_pool_forward(data, rois, trans=None, *, spatial_scale, output_dim, group_size, pooled_size,
+                              part_size=0, sample_per_part=1, trans_std=0.0, no_trans=False, out=None,
+                              top_count=None):
+    """_contrib_DeformablePSROIPooling forward: data (B,C,H,W), rois (K,5), trans (K,2*num_classes,part,part)
+    -> out, top_count (K,output_dim,P,P).  top_count is the operator's hidden output, the backward's state."""
+    K, P, ncls = _dpsroi_dims(data, rois, trans, output_dim, pooled_size, part_size, no_trans)
+    B, C, H, W = data.shape
+    shape = (K, int(output_dim), P, P)
+    out = _grad_buf(out, "out", shape, 0, data.device)
+    top_count = _grad_buf(top_count, "top_count", shape, 0, data.device)
+    lib().call("sd_deform_psroi_pool_fwd", _p(data), _p(rois), None if no_trans else _p(trans), _p(out),
+               _p(top_count), B, C, H, W, K, ncls, float(spatial_scale), int(output_dim), int(group_size), P,
+               int(part_size), int(sample_per_part), float(trans_std), int(bool(no_trans)), _stream())
+    return out, top_count
+
+
+def deform_psroi_pool_backward(out_grad, data, rois, trans, top_count, *, spatial_scale, output_dim, group_size,
+                               pooled_size, part_size=0, sample_per_part=1, trans_std=0.0, no_trans=False,
+                               req_data="write", req_rois="write", req_trans="write", d_data=None, d_trans=None):
+    """-> d_data, d_rois (zeros on write, None otherwise), d_trans (None when no_trans or req_trans null)"""
+    K, P, ncls = _dpsroi_dims(data, rois, trans, output_dim, pooled_size, part_size, no_trans)
+    B, C, H, W = data.shape
+    shape = (K, int(output_dim), P, P)
+    _chk(out_grad, "out_grad", ndim=4)
+    _chk(top_count, "top_count", ndim=4)
+    if tuple(out_grad.shape) != shape or tuple(top_count.shape) != shape:
+        raise ValueError("out_grad / top_count should have shape %s" % (shape,))
+    rd, rr, rt = _req_of(req_data), _req_of(req_rois), _req_of(req_trans)
+    if no_trans:
+        rt = 0
+    if rd:
+        d_data = _grad_buf(d_data, "d_data", tuple(data.shape), rd, data.device)
+    if rt:
+        d_trans = _grad_buf(d_trans, "d_trans", tuple(trans.shape), rt, data.device)
+    d_rois = torch.empty_like(rois) if rr == REQ["write"] else None
+    lib().call("sd_deform_psroi_pool_bwd", _p(out_grad), _p(data), _p(rois), None if no_trans else _p(trans),
+               _p(top_count), _p(d_data) if rd else None, _p(d_rois), _p(d_trans) if rt else None, rd, rr, rt,
+               B, C, H, W, K, ncls, float(spatial_scale), int(output_dim), int(group_size), P, int(part_size),
+               int(sample_per_part), float(trans_std), int(bool(no_trans)), _stream())
+    return (d_data if rd else None), d_rois, (d_trans if rt else None)
+
+
+class DeformPSROIPoolFunction(torch.autograd.Function):
+    """out = f(data, rois, trans); rois gets a zero gradient like the operator's"""
+
+    @staticmethod
+    def forward(ctx, data, rois, trans, kw):
+        kw = dict(kw)
+        out, top_count = deform_psroi_pool_forward(data, rois, trans, **kw)
+        ctx.kw = kw
+        ctx.save_for_backward(data, rois, trans, top_count)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        data, rois, trans, top_count = ctx.saved_tensors
+        need_t = trans is not None and ctx.needs_input_grad[2]
+        dd, dr, dt = deform_psroi_pool_backward(dy.contiguous(), data, rois, trans, top_count,
+                                                req_data="write" if ctx.needs_input_grad[0] else "null",
+                                                req_rois="write" if ctx.needs_input_grad[1] else "null",
+                                                req_trans="write" if need_t else "null", **ctx.kw)
+        return dd, dr, dt, None
+
+
+def deform_psroi_pool(data, rois, trans=None, **kw):
+    return DeformPSROIPoolFunction.apply(data, rois, trans, kw)
+
+
+def _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size):
+    _chk(rois, "rois", ndim=3)
+    if rois.shape[2] != 4:
+        raise ValueError("rois should be a 3D tensor of shape [batch, rois, 4]")
+    if len(feats) != len(rcnn_stride):
+        raise ValueError("one feature map per stride expected")
+    B, C = feats[0].shape[:2]
+    for i, f in enumerate(feats):
+        _chk(f, "feats[%d]" % i, ndim=4)
+        if tuple(f.shape[:2]) != (B, C):
+            raise ValueError("all levels must share (B,C)")
+    if rois.shape[0] != B:
+        raise ValueError("rois batch mismatch")
+    R, P = rois.shape[1], int(pooled_size)
+    _chk(trans, "trans")
+    if tuple(trans.shape) == (B * R, 2, P, P):
+        tpart = P
+    elif tuple(trans.shape) in ((B * R, 2), (B * R, 2, 1, 1)):
+        tpart = 1
+    else:
+        raise ValueError("trans should have shape (B*R, 2, P, P) or (B*R, 2), got %s" % (tuple(trans.shape),))
+    return B, C, R, P, tpart
+
+
+def fpn_deform_roi_pool_forward(feats, rois, trans, rcnn_stride, pooled_size, sample_per_part=4, trans_std=0.1,
+                                roi_canonical_scale=224, roi_canonical_level=4, out=None, top_count=None):
+    """FPNRoIAlign_DeltaC / DeltaR.get_roi_feature (models/TSD/poolings.py:51-174) as one launch.
+
+    feats: list of (B,C,H_l,W_l); rois (B,R,4); trans (B*R,2,P,P) (DeltaC) or (B*R,2) (DeltaR)
+    -> out (B*R,C,P,P), top_count (B*R,nlvl,P,P)."""
+    B, C, R, P, tpart = _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size)
+    out = _grad_buf(out, "out", (B * R, C, P, P), 0, rois.device)
+    top_count = _grad_buf(top_count, "top_count", (B * R, len(feats), P, P), 0, rois.device)
+    lib().call("sd_fpn_deform_roi_pool_fwd", _parr(feats), _iarr([f.shape[2] for f in feats]),
+               _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride), len(feats), _p(rois), _p(trans), _p(out),
+               _p(top_count), B, C, R, P, tpart, int(sample_per_part), float(trans_std),
+               float(roi_canonical_scale), float(roi_canonical_level), _stream())
+    return out, top_count
+
+
+def fpn_deform_roi_pool_backward(out_grad, feats, rois, trans, top_count, rcnn_stride, pooled_size,
+                                 sample_per_part=4, trans_std=0.1, roi_canonical_scale=224, roi_canonical_level=4,
+                                 req_data="write", req_trans="write", d_feats=None, d_trans=None):
+    """-> [d_feat per level] (None when req_data null), d_trans (None when req_trans null)"""
+    B, C, R, P, tpart = _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size)
+    _chk(out_grad, "out_grad", ndim=4)
+    _chk(top_count, "top_count", ndim=4)
+    if tuple(out_grad.shape) != (B * R, C, P, P) or tuple(top_count.shape) != (B * R, len(feats), P, P):
+        raise ValueError("out_grad / top_count shape mismatch")
+    rd, rt = _req_of(req_data), _req_of(req_trans)
+    if rd:
+        if d_feats is None:
+            d_feats = [None] * len(feats)
+        d_feats = [_grad_buf(d, "d_feats[%d]" % i, tuple(f.shape), rd, rois.device)
+                   for i, (d, f) in enumerate(zip(d_feats, feats))]
+    if rt:
+        d_trans = _grad_buf(d_trans, "d_trans", tuple(trans.shape), rt, rois.device)
+    lib().call("sd_fpn_deform_roi_pool_bwd", _p(out_grad), _parr(feats), _parr(d_feats) if rd else None,
+               _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride),
+               len(feats), _p(rois), _p(trans), _p(top_count), _p(d_trans) if rt else None, rd, rt, B, C, R, P,
+               tpart, int(sample_per_part), float(trans_std), float(roi_canonical_scale),
+               float(roi_canonical_level), _stream())
+    return (d_feats if rd else None), (d_trans if rt else None)
+
+
+class FpnDeformRoiPoolFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rois, trans, kw, *feats):
+        kw = dict(kw)
+        out, top_count = fpn_deform_roi_pool_forward(list(feats), rois, trans, **kw)
+        ctx.kw = kw
+        ctx.save_for_backward(rois, trans, top_count, *feats)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        rois, trans, top_count, *feats = ctx.saved_tensors
+        need_d = any(ctx.needs_input_grad[3:])
+        dfs, dt = fpn_deform_roi_pool_backward(dy.contiguous(), feats, rois, trans, top_count,
+                                               req_data="write" if need_d else "null",
+                                               req_trans="write" if ctx.needs_input_grad[1] else "null", **ctx.kw)
+        return (None, dt, None) + tuple(dfs if need_d else [None] * len(feats))
+
+
+def fpn_deform_roi_pool(feats, rois, trans, rcnn_stride, pooled_size, **kw):
+    kw = dict(kw, rcnn_stride=list(rcnn_stride), pooled_size=pooled_size)
+    return FpnDeformRoiPoolFunction.apply(rois, trans, kw, *feats)
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_GenAnchor  (operator_cxx/contrib/generate_anchor{-inl.h,.cc,.cu})
 # --------------------------------------------------------------------------------------------------
 def _darr(vals):
