@@ -1124,6 +1124,75 @@ int sd_fcos_decode(const float* const* cls_ptrs_host, const float* const* ctr_pt
                    size_t workspace_bytes, void* stream);
 int sd_fcos_sigmoid(const float* x, float* p, long n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RepPoints training head (config/RepPoints/), fp32.  Additions only: the ABI version stays 12.
+ *   sd_reppoints_target replaces _gen_points, _offset_to_boxes and both _point_target calls of
+ *     RepPointsHead.get_loss (models/RepPoints/builder.py:328-388, models/RepPoints/point_ops.py:18-216);
+ *   sd_reppoints_box_loss_fwd / _bwd replace _offset_to_pts, _points2bbox, the per-level concat, smooth_l1, the
+ *     weight product, BBoxNorm and MakeLoss of both box branches (builder.py:415-481).
+ *   Levels: three HOST tables of L ints (H_l, W_l, stride_l) and HOST tables of L device pointers to the point maps
+ *     (N, 2 * num_points, H_l, W_l), channels (y0, x0, y1, x1, ...); the tables are read during the call only.
+ *     P = sum H_l * W_l; point j = (level, h, w) in the reference's concat order, at (w * stride, h * stride);
+ *     its level is floor(log2(stride)); lvl_min / lvl_max come from the strides passed.  An empty level is skipped.
+ *   transform: 0 = minmax, 1 = partial_minmax (the first four points), 2 = moment (moment_transfer (2,) on the
+ *     device: the half extents are std * exp(moment_transfer[0]) in x and std * exp(moment_transfer[1]) in y;
+ *     may be NULL for 0 and 1).  Sums over the points of a set run sequentially in point order, the mean is the
+ *     sum / num_points, the deviation sqrt(mean((v - mean)^2)).
+ *   sd_reppoints_target: pts_init maps, gt_bbox (N, M, 5) [x1, y1, x2, y2, cls] ->
+ *       label_init (N, P), gt_init (N, P, 4): the point assigner (point_ops.py:67-137).  A gt is valid if cls > 0;
+ *         centre ((l + r) / 2, (t + b) / 2), w, h = max(r - l, 1e-6), max(b - t, 1e-6), level
+ *         floor((log2(w / target_scale) + log2(h / target_scale)) / 2) clipped to the point levels; the distance of a
+ *         point of that level is sqrt(dx * dx + dy * dy) of (point - centre) / (w, h); per valid gt the num_pos
+ *         smallest distances survive (ties: the lower flat point index), per point the gt of least surviving
+ *         distance wins (ties: the lower gt index): label = its cls, gt = its box; elsewhere label = -1, gt = 0.
+ *       label_refine (N, P), gt_refine (N, P, 4): the IoU assigner (point_ops.py:140-175) on the init boxes
+ *         centre + stride * _points2bbox(raw offsets) (in this order).  box_iou, corner format, no +1: extents
+ *         clamped at 0, inter / (area_a + area_b - inter), 0 where the union is <= 0.  Per box the FIRST arg-max
+ *         over the M rows (padding rows included) and the max; per gt the max over the P boxes of its image;
+ *         assigned = -1; 0 where max < neg_iou_thr; 1 where some gt has iou == its column max and that column max >
+ *         min_pos_iou; 1 where max >= pos_iou_thr; label = cls[argmax] where assigned > 0 else assigned,
+ *         gt = box[argmax] where assigned > 0 else 0.
+ *       state int32[4]: [0] = #(label_init >= 1), [1] = #(label_refine >= 1) over the batch, [2], [3] = the BITS
+ *         of the floats [0] + 1 and [1] + 1, the BBoxNorm denominators (bbox_norm-inl.h:116-122).
+ *     The weights are label > 0 and are not materialised.  Every output is bit-reproducible (integer atomics only).
+ *   sd_reppoints_box_loss_fwd: per stage, points = pred * stride + centre after the (y, x) -> (x, y) flip, box =
+ *     _points2bbox of those absolute points, loss = smooth_l1((box - gt) / (stride * scale), sigma 3) * [label > 0]
+ *     -> loss_init, loss_refine (N, P, 4).
+ *   sd_reppoints_box_loss_bwd: no top gradient; the head gradient is grad_scale / state denominator, taken back
+ *     through the weight, smooth-L1, the normaliser and the transform (min / max: EVERY tied point takes the
+ *     gradient; moment: the chain rule of the expressions as written, so a set of coincident points, std = 0,
+ *     gives NaN) into HOST tables of gradient maps shaped like the inputs, req = 1 (write) or 3 (add), and into
+ *     d_moment_transfer (2,) (same req; 0 for minmax / partial_minmax), summed over both stages from
+ *     per-workgroup partials in a fixed order.
+ *   Kernels only, no allocation, no host synchronisation, graph-capturable; workspaces need no clearing; any
+ *   4-byte aligned tensor pointer works.  Checked before anything touches the device -- SD_ERR_INVALID_ARG: a
+ *   negative dimension, a null pointer or table, a NaN or non-positive scale, a NaN threshold, a stride < 1, an
+ *   unknown transform or req, partial_minmax with fewer than 4 points, M == 0; SD_ERR_UNSUPPORTED: L > 8,
+ *   M > 128, num_pos outside 1..16, num_points not in {1, 9, 25}, N > 65535, N * 2 * num_points * P > 2^31 - 1, a
+ *   coordinate beyond 2^24; SD_ERR_WORKSPACE: a NULL or too small workspace.  N == 0 or P == 0 succeed without a
+ *   launch.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_reppoints_target_workspace_bytes(int N, int M, long P);
+int sd_reppoints_target(const float* const* pts_init_ptrs_host, const int* H_host, const int* W_host,
+                        const int* stride_host, int L, const float* gt_bbox, const float* moment_transfer_or_null,
+                        float* label_init, float* gt_init, float* label_refine, float* gt_refine, int* state, int N,
+                        int M, int num_points, int transform, float target_scale, int num_pos, float pos_iou_thr,
+                        float neg_iou_thr, float min_pos_iou, void* workspace, size_t workspace_bytes, void* stream);
+int sd_reppoints_box_loss_fwd(const float* const* pts_init_ptrs_host, const float* const* pts_refine_ptrs_host,
+                              const int* H_host, const int* W_host, const int* stride_host, int L,
+                              const float* moment_transfer_or_null, const float* label_init, const float* gt_init,
+                              const float* label_refine, const float* gt_refine, float* loss_init,
+                              float* loss_refine, int N, int num_points, int transform, float scale, void* stream);
+size_t sd_reppoints_box_loss_workspace_bytes(int N, long P);
+int sd_reppoints_box_loss_bwd(const float* const* pts_init_ptrs_host, const float* const* pts_refine_ptrs_host,
+                              const int* H_host, const int* W_host, const int* stride_host, int L,
+                              const float* moment_transfer_or_null, const float* label_init, const float* gt_init,
+                              const float* label_refine, const float* gt_refine, const int* state,
+                              float* const* d_init_ptrs_host, float* const* d_refine_ptrs_host,
+                              float* d_moment_transfer, int N, int num_points, int transform, float scale,
+                              float grad_scale_init, float grad_scale_refine, int req, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -341,3 +341,19 @@ def mask_loss(logits, cls, target, grad_scale=1.0):
     backward writes the dense (R, K, h, w) gradient once and IGNORES the incoming gradient, as the reference's
     loss operator does; grad_scale scales the gradient only."""
     return _MaskLoss.apply(logits, cls, target, float(grad_scale))
+
+
+def reppoints_head_loss(pts_init, pts_refine, gt_bbox, moment_transfer, strides, transform="moment", scale=4,
+                        target_scale=4, num_pos=1, pos_iou_thr=0.5, neg_iou_thr=0.5, min_pos_iou=0.0):
+    """The box branches of RepPointsHead.get_loss (models/RepPoints/builder.py:311-484) on lists of per-level point
+    maps (N, 2 * num_points, H_l, W_l): both assigners on the (gradient-blocked) init maps, then the two box losses.
+    Returns (pts_init_loss, pts_refine_loss, targets): the losses (N, P, 4) with autograd into the maps and
+    moment_transfer (the incoming gradient is IGNORED, as the reference's MakeLoss does: the head gradient is 0.5 /
+    1.0 over the BBoxNorm denominators), and the RepPointsTargets whose label_refine feeds focal_loss."""
+    targets = ops.reppoints_target([t.detach().contiguous() for t in pts_init], gt_bbox.contiguous(), strides,
+                                   transform=transform, moment_transfer=None if moment_transfer is None else moment_transfer.detach(),
+                                   target_scale=target_scale, num_pos=num_pos, pos_iou_thr=pos_iou_thr,
+                                   neg_iou_thr=neg_iou_thr, min_pos_iou=min_pos_iou)
+    loss_init, loss_refine = ops.reppoints_box_loss(pts_init, pts_refine, targets, strides, transform=transform,
+                                                    moment_transfer=moment_transfer, scale=scale)
+    return loss_init, loss_refine, targets

@@ -2292,12 +2292,188 @@ def _build_ops(mx):
             return []
 
     ops["fcos_decode"] = (FCOSDecodeProp, None)
+
+    # ---- the RepPoints training head (registered only by install(..., reppoints=True)):
+    #      reppoints_target:   L init point maps, gt_bbox, moment_transfer -> label_init, gt_init, label_refine,
+    #                          gt_refine, state (int32[4])
+    #      reppoints_box_loss: L init maps, L refine maps, moment_transfer, the five targets -> pts_init_loss,
+    #                          pts_refine_loss (N, P, 4) ----
+    _RP_TRANSFORMS = {"minmax": 0, "partial_minmax": 1, "moment": 2}
+
+    def _rp_geometry(stride, num_points, transform, who):
+        g = dict(stride=_tuple(stride, typ=int), num_points=int(num_points), transform=str(transform))
+        if not 1 <= len(g["stride"]) <= 8 or g["num_points"] not in (1, 9, 25) or g["transform"] not in _RP_TRANSFORMS:
+            raise ValueError("%s: stride has 1 to 8 entries, num_points is 1, 9 or 25 and transform one of %s"
+                             % (who, sorted(_RP_TRANSFORMS)))
+        return g
+
+    def _rp_levels(g, maps):
+        """(N, P, H table, W table, stride table) of L level maps (N, 2 * num_points, H_l, W_l)"""
+        Hs, Ws = [int(m.shape[2]) for m in maps], [int(m.shape[3]) for m in maps]
+        return int(maps[0].shape[0]), sum(h * w for h, w in zip(Hs, Ws)), _iarr(Hs), _iarr(Ws), _iarr(g["stride"])
+
+    def _rp_map_shapes(g, shapes, who):
+        """checks L level shapes; returns (N, P)"""
+        n, c = shapes[0][0], 2 * g["num_points"]
+        for i, sh in enumerate(shapes):
+            if len(sh) != 4 or sh[0] != n or sh[1] != c:
+                raise ValueError("%s: level %d should be (N, %d, H, W), got %s" % (who, i, c, sh))
+        return n, sum(sh[2] * sh[3] for sh in shapes)
+
+    class RepPointsTarget(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            g = self.g
+            L = len(g["stride"])
+            maps, gt, mt = in_data[:L], in_data[L], in_data[L + 1]
+            N, P, Hs, Ws, st = _rp_levels(g, maps)
+            M = int(gt.shape[1])
+            wsb = int(lib().cdll.sd_reppoints_target_workspace_bytes(N, M, ctypes.c_long(P)))
+            ws = _scratch(gt, wsb)
+            tab = (ctypes.c_void_p * L)(*[_ptr(a).value for a in maps])
+            _call("sd_reppoints_target", tab, Hs, Ws, st, L, _ptr(gt), _ptr(mt), _ptr(out_data[0]), _ptr(out_data[1]),
+                  _ptr(out_data[2]), _ptr(out_data[3]), _ptr(out_data[4]), N, M, g["num_points"],
+                  _RP_TRANSFORMS[g["transform"]], g["target_scale"], g["num_pos"], g["pos_iou_thr"], g["neg_iou_thr"],
+                  g["min_pos_iou"], _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(req)):       # targets carry no gradient (box_iou, topk and take of gt rows)
+                self.assign(in_grad[i], req[i], 0)
+
+    class RepPointsTargetProp(CustomOpProp):
+        def __init__(self, stride, num_points="9", transform="moment", target_scale="4", num_pos="1",
+                     pos_iou_thr="0.5", neg_iou_thr="0.5", min_pos_iou="0.0"):
+            super().__init__(need_top_grad=False)
+            self.g = _rp_geometry(stride, num_points, transform, "reppoints_target")
+            self.g.update(target_scale=float(target_scale), num_pos=int(num_pos), pos_iou_thr=float(pos_iou_thr),
+                          neg_iou_thr=float(neg_iou_thr), min_pos_iou=float(min_pos_iou))
+            if not 1 <= self.g["num_pos"] <= 16:
+                raise ValueError("reppoints_target: num_pos must lie in 1..16")
+
+        def list_arguments(self):
+            return ["pts_init_%d" % i for i in range(len(self.g["stride"]))] + ["gt_bbox", "moment_transfer"]
+
+        def list_outputs(self):
+            return ["label_init", "gt_init", "label_refine", "gt_refine", "state"]
+
+        def infer_shape(self, in_shape):
+            L = len(self.g["stride"])
+            shapes = [tuple(s) for s in in_shape]
+            if len(shapes) != L + 2:
+                raise ValueError("reppoints_target: expected %d inputs, got %d" % (L + 2, len(shapes)))
+            n, p = _rp_map_shapes(self.g, shapes[:L], "reppoints_target")
+            gt = shapes[L]
+            if len(gt) != 3 or gt[0] != n or gt[2] != 5 or not 1 <= gt[1] <= 128:
+                raise ValueError("reppoints_target: gt_bbox should be (%d, M <= 128, 5), got %s" % (n, gt))
+            return shapes[:L] + [gt, (2,)], [(n, p), (n, p, 4), (n, p), (n, p, 4), (4,)]
+
+        def infer_type(self, in_type):
+            import numpy as np
+            return [in_type[0]] * len(in_type), [in_type[0]] * 4 + [np.int32], []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return RepPointsTarget(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    class RepPointsBoxLoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def _args(self, in_data):
+            g = self.g
+            L = len(g["stride"])
+            pi, pr, mt, targets = in_data[:L], in_data[L:2 * L], in_data[2 * L], in_data[2 * L + 1:2 * L + 6]
+            tab = lambda arrs: (ctypes.c_void_p * L)(*[_ptr(a).value for a in arrs])
+            return L, pi, pr, mt, targets, tab, _rp_levels(g, pi)
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            g = self.g
+            L, pi, pr, mt, (li, gi, lr, gr, state), tab, (N, P, Hs, Ws, st) = self._args(in_data)
+            _call("sd_reppoints_box_loss_fwd", tab(pi), tab(pr), Hs, Ws, st, L, _ptr(mt), _ptr(li), _ptr(gi), _ptr(lr),
+                  _ptr(gr), _ptr(out_data[0]), _ptr(out_data[1]), N, g["num_points"], _RP_TRANSFORMS[g["transform"]],
+                  g["scale"], None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # MakeLoss ignores the incoming gradient: the head gradient is grad_scale / the BBoxNorm denominator
+            g = self.g
+            L, pi, pr, mt, (li, gi, lr, gr, state), tab, (N, P, Hs, Ws, st) = self._args(in_data)
+            _wait(*in_data)
+            reqs = {_req(r) for r in req[:2 * L + 1]}
+            if reqs != {REQ["null"]}:
+                if len(reqs) != 1:
+                    raise RuntimeError("RepPointsBoxLoss writes every gradient in one launch: req must be the same "
+                                       "('write', 'add' or 'null') for the 2 * L point maps and moment_transfer")
+                wsb = int(lib().cdll.sd_reppoints_box_loss_workspace_bytes(N, ctypes.c_long(P)))
+                ws = _scratch(pi[0], wsb)
+                _call("sd_reppoints_box_loss_bwd", tab(pi), tab(pr), Hs, Ws, st, L, _ptr(mt), _ptr(li), _ptr(gi),
+                      _ptr(lr), _ptr(gr), _ptr(state), tab(in_grad[:L]), tab(in_grad[L:2 * L]), _ptr(in_grad[2 * L]),
+                      N, g["num_points"], _RP_TRANSFORMS[g["transform"]], g["scale"], g["grad_scale_init"],
+                      g["grad_scale_refine"], reqs.pop(), _ptr(ws), ctypes.c_size_t(wsb), None)
+            for i in range(2 * L + 1, len(req)):
+                self.assign(in_grad[i], req[i], 0)
+            _sync()
+
+    class RepPointsBoxLossProp(CustomOpProp):
+        def __init__(self, stride, num_points="9", transform="moment", scale="4", grad_scale_init="0.5",
+                     grad_scale_refine="1.0"):
+            super().__init__(need_top_grad=False)
+            self.g = _rp_geometry(stride, num_points, transform, "reppoints_box_loss")
+            self.g.update(scale=float(scale), grad_scale_init=float(grad_scale_init),
+                          grad_scale_refine=float(grad_scale_refine))
+
+        def list_arguments(self):
+            L = len(self.g["stride"])
+            return (["pts_init_%d" % i for i in range(L)] + ["pts_refine_%d" % i for i in range(L)]
+                    + ["moment_transfer", "label_init", "gt_init", "label_refine", "gt_refine", "state"])
+
+        def list_outputs(self):
+            return ["pts_init_loss", "pts_refine_loss"]
+
+        def infer_shape(self, in_shape):
+            L = len(self.g["stride"])
+            shapes = [tuple(s) for s in in_shape]
+            if len(shapes) != 2 * L + 6:
+                raise ValueError("reppoints_box_loss: expected %d inputs, got %d" % (2 * L + 6, len(shapes)))
+            n, p = _rp_map_shapes(self.g, shapes[:L], "reppoints_box_loss")
+            if shapes[L:2 * L] != shapes[:L]:
+                raise ValueError("reppoints_box_loss: the refine maps %s differ from the init maps %s"
+                                 % (shapes[L:2 * L], shapes[:L]))
+            rest = [(2,), (n, p), (n, p, 4), (n, p), (n, p, 4), (4,)]
+            for want, got in zip(rest, shapes[2 * L:]):
+                if got and got != want:
+                    raise ValueError("reppoints_box_loss: input shape %s, expected %s" % (got, want))
+            return shapes[:2 * L] + rest, [(n, p, 4), (n, p, 4)]
+
+        def infer_type(self, in_type):
+            import numpy as np
+            return [in_type[0]] * (len(in_type) - 1) + [np.int32], [in_type[0]] * 2, []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return RepPointsBoxLoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return list(in_data)
+
+    ops["reppoints_target"] = (RepPointsTargetProp, None)
+    ops["reppoints_box_loss"] = (RepPointsBoxLossProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False):
+             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False, reppoints=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -2316,7 +2492,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     fcos_decode: also sd_fcos_decode (opt-in: patch_fcos_decode puts it in place of the sigmoids and the two Python
     CustomOps of the FCOS test graph);
     tsd_pool: also _contrib_DeformablePSROIPooling and sd_fpn_deform_roi_pool (opt-in: the first replaces a native
-    operator, patch_tsd_pool puts the second in place of the two get_roi_feature subgraphs of the TSD graphs)."""
+    operator, patch_tsd_pool puts the second in place of the two get_roi_feature subgraphs of the TSD graphs);
+    reppoints: also sd_reppoints_target and sd_reppoints_box_loss (opt-in: patch_reppoints_loss puts them in place of
+    both assigners and both box-loss subgraphs of the RepPoints train graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -2348,6 +2526,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     if not tsd_pool:
         table.pop("_contrib_DeformablePSROIPooling")
         table.pop("fpn_deform_roi_pool")
+    if not reppoints:
+        table.pop("reppoints_target")
+        table.pop("reppoints_box_loss")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2382,7 +2563,8 @@ def _namespaces(mx, ns):
 
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False):
+            group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False,
+            reppoints=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2449,10 +2631,16 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     sets that sd_deform_psroi_pool_supported refuses for one class fall back to the native constructor), registers `sd_fpn_deform_roi_pool` and
     rebinds `FPNRoIAlign_DeltaC.get_roi_feature` and `FPNRoIAlign_DeltaR.get_roi_feature` of models/TSD/poolings.py
     (patch_tsd_pool) so that a TSD graph holds TWO nodes in place of 2 x (level rule, eight masks, four
-    DeformablePSROIPooling, add_n); opt-in because it changes which operators those graphs hold."""
+    DeformablePSROIPooling, add_n); opt-in because it changes which operators those graphs hold.
+
+    `reppoints=True` also registers `sd_reppoints_target` and `sd_reppoints_box_loss` and rebinds
+    `models.RepPoints.builder.RepPointsHead.get_loss` (patch_reppoints_loss) so that a RepPoints train graph holds
+    these two nodes in place of _gen_points, _offset_to_boxes, both _point_target subgraphs, _offset_to_pts,
+    _points2bbox, smooth_l1, BBoxNorm and MakeLoss of both box branches; the focal loss on the concatenated class
+    logits stays the node it was.  A default install() afterwards puts the reference's method back."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
                      group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
-                     fcos_decode=fcos_decode, tsd_pool=tsd_pool)
+                     fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -2576,6 +2764,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_TSD_POOLINGS) is not None:
             unpatch_tsd_pool(sys.modules[_TSD_POOLINGS])
         _state["tsd_pool_patched"] = False
+    if reppoints:
+        _state["reppoints_patched"] = patch_reppoints_loss(mx=mx)
+        if not _state["reppoints_patched"]:
+            _state["fallbacks"].append(("reppoints_box_loss", None, "%s.RepPointsHead is not importable" % _REPPOINTS_BUILDER))
+    else:
+        import sys
+        if sys.modules.get(_REPPOINTS_BUILDER) is not None:
+            unpatch_reppoints_loss(sys.modules[_REPPOINTS_BUILDER])
+        _state["reppoints_patched"] = False
     return props
 
 
@@ -2830,6 +3027,108 @@ def unpatch_fcos_decode(builder_module):
     if original is None:
         return False
     cls.get_all_proposal = original
+    return True
+
+
+_REPPOINTS_BUILDER = "models.RepPoints.builder"
+
+
+def _reppoints_unsupported(p):
+    """why the device ops do not take this head, or ''"""
+    table = _state.get("table") or {}
+    if "reppoints_box_loss" not in table:
+        return "sd_reppoints_target / sd_reppoints_box_loss are not registered"
+    if p.fp16:
+        return "fp16: the device ops are float32"
+    if not 1 <= len(p.point_generate.stride) <= 8:
+        return "%d levels, the limit is 8" % len(p.point_generate.stride)
+    if p.point_generate.num_points not in (1, 9, 25):
+        return "num_points=%s is not the square of an odd number up to 25" % (p.point_generate.num_points,)
+    if p.point_generate.transform not in ("minmax", "partial_minmax", "moment"):
+        return "transform=%s" % (p.point_generate.transform,)
+    if not 1 <= int(p.point_target.num_pos) <= 16:
+        return "num_pos=%s lies outside 1..16" % (p.point_target.num_pos,)
+    return ""
+
+
+def patch_reppoints_loss(builder_module=None, mx=None):
+    """Route the RepPoints training head to the device ops WITHOUT editing the reference: rebinds
+    `RepPointsHead.get_loss` of models/RepPoints/builder.py:311-484 -- per level _gen_points, _offset_to_boxes and two
+    _offset_to_pts, per image _point_assign and _iou_assign, three _points2bbox, two smooth_l1 / BBoxNorm / MakeLoss
+    chains -- to a method that calls `self.get_output(conv_feat)` and emits
+        sd_reppoints_target(the L init point maps, gt_bbox, moment_transfer)
+        sd_reppoints_box_loss(the L init and L refine point maps, moment_transfer, the five targets)
+    and keeps the class branch as it is: the per-level transpose and reshape, the concat and X.focal_loss on
+    label_refine.  Every parameter is read from self.p as the reference reads it.  Returns the reference's five
+    outputs in order: cls_loss, pts_init_loss, pts_refine_loss and label_refine twice behind BlockGrad.  A head
+    with p.fp16 set, or beyond the limits of the device ops, goes back to the original method
+    (`_state["fallbacks"]` records why).  install(reppoints=True) calls this when the builder module is importable;
+    returns True when the class was patched.  The original is kept as `_sd_reference_get_loss` (a second install()
+    keeps the first original); a default install() afterwards puts it back."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_REPPOINTS_BUILDER)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _REPPOINTS_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_reppoints_loss(module, mx)
+    cls = getattr(builder_module, "RepPointsHead", None)
+    if cls is None:
+        return False
+    original = cls.__dict__.get("_sd_reference_get_loss") or cls.get_loss
+    X = builder_module.X
+
+    def get_loss(self, conv_feat, gt_bbox):
+        p = self.p
+        why = _reppoints_unsupported(p)
+        if why:
+            _state.setdefault("fallbacks", []).append(("reppoints_box_loss", None, why))
+            return original(self, conv_feat, gt_bbox)
+        stride = tuple(p.point_generate.stride)
+        pts_out_inits, pts_out_refines, cls_outs = self.get_output(conv_feat)
+        geometry = {"stride": _param_str(stride), "num_points": _param_str(p.point_generate.num_points),
+                    "transform": _param_str(p.point_generate.transform)}
+        inputs = {"pts_init_%d" % i: X.block_grad(pts_out_inits["stride%s" % s]) for i, s in enumerate(stride)}
+        targets = mx.sym.Custom(op_type=_PREFIX + "reppoints_target", name="reppoints_target", **inputs,
+                                gt_bbox=gt_bbox, moment_transfer=self.moment_transfer, **geometry,
+                                target_scale=_param_str(p.point_target.target_scale),
+                                num_pos=_param_str(p.point_target.num_pos),
+                                pos_iou_thr=_param_str(p.bbox_target.pos_iou_thr),
+                                neg_iou_thr=_param_str(p.bbox_target.neg_iou_thr),
+                                min_pos_iou=_param_str(p.bbox_target.min_pos_iou))
+        points_labels_refine = targets[2]
+        # cls branch (builder.py:390-413), unchanged
+        cls_flat = [X.reshape(X.transpose(data=cls_outs["stride%s" % s], axes=(0, 2, 3, 1)), (0, -3, -2)) for s in stride]
+        cls_outs_concat = X.concat(cls_flat, axis=1, name="cls_concat")
+        cls_loss = X.focal_loss(data=cls_outs_concat, label=points_labels_refine, normalization='valid',
+                                alpha=p.focal_loss.alpha, gamma=p.focal_loss.gamma, grad_scale=1.0, workspace=1500,
+                                name="cls_loss")
+        inputs = {"pts_init_%d" % i: pts_out_inits["stride%s" % s] for i, s in enumerate(stride)}
+        inputs.update({"pts_refine_%d" % i: pts_out_refines["stride%s" % s] for i, s in enumerate(stride)})
+        inputs["moment_transfer"] = self.moment_transfer
+        for i, name in enumerate(("label_init", "gt_init", "label_refine", "gt_refine", "state")):
+            inputs[name] = targets[i]
+        loss = mx.sym.Custom(op_type=_PREFIX + "reppoints_box_loss", name="reppoints_box_loss", **inputs, **geometry,
+                             scale=_param_str(p.point_generate.scale), grad_scale_init="0.5", grad_scale_refine="1.0")
+        points_init_labels = X.block_grad(points_labels_refine, name="points_init_labels")
+        points_refine_labels = X.block_grad(points_labels_refine, name="point_refine_labels")
+        return cls_loss, loss[0], loss[1], points_init_labels, points_refine_labels
+
+    cls._sd_reference_get_loss = original
+    cls.get_loss = get_loss
+    return True
+
+
+def unpatch_reppoints_loss(builder_module):
+    """Put the reference's get_loss back."""
+    cls = getattr(builder_module, "RepPointsHead", None)
+    original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
+    if original is None:
+        return False
+    cls.get_loss = original
     return True
 
 

@@ -1574,6 +1574,168 @@ def fcos_loss(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25, gamma=2
 
 
 # --------------------------------------------------------------------------------------------------
+# RepPoints training head  (models/RepPoints/point_ops.py, models/RepPoints/builder.py get_loss)
+# --------------------------------------------------------------------------------------------------
+RepPointsTargets = collections.namedtuple("RepPointsTargets", "label_init gt_init label_refine gt_refine state")
+REPPOINTS_TRANSFORMS = {"minmax": 0, "partial_minmax": 1, "moment": 2}
+
+
+def reppoints_target_workspace_bytes(N, M, P):
+    return int(lib().cdll.sd_reppoints_target_workspace_bytes(int(N), int(M), ctypes.c_long(int(P))))
+
+
+def reppoints_box_loss_workspace_bytes(N, P):
+    return int(lib().cdll.sd_reppoints_box_loss_workspace_bytes(int(N), ctypes.c_long(int(P))))
+
+
+def _reppoints_levels(maps, strides, name, like=None):
+    """(N, num_points, P, H table, W table, stride table) of a list of point maps (N, 2 * num_points, H_l, W_l)"""
+    L = len(maps)
+    if L == 0 or len(strides) != L:
+        raise ValueError("%s needs one map per stride" % name)
+    N, C = int(maps[0].shape[0]), int(maps[0].shape[1])
+    for i, t in enumerate(maps):
+        _chk(t, "%s[%d]" % (name, i), ndim=4)
+        if int(t.shape[0]) != N or int(t.shape[1]) != C or C % 2:
+            raise ValueError("%s[%d] should be (N, 2 * num_points, H, W), got %s" % (name, i, tuple(t.shape)))
+        if like is not None and tuple(t.shape) != tuple(like[i].shape):
+            raise ValueError("%s[%d] has shape %s, expected %s" % (name, i, tuple(t.shape), tuple(like[i].shape)))
+    Hs, Ws = [int(t.shape[2]) for t in maps], [int(t.shape[3]) for t in maps]
+    return N, C // 2, sum(h * w for h, w in zip(Hs, Ws)), _iarr(Hs), _iarr(Ws), _iarr(strides)
+
+
+def _reppoints_transform(transform, moment_transfer):
+    if transform not in REPPOINTS_TRANSFORMS:
+        raise ValueError("transform %r is none of %s" % (transform, sorted(REPPOINTS_TRANSFORMS)))
+    if moment_transfer is not None:
+        _chk(moment_transfer, "moment_transfer")
+        if moment_transfer.numel() != 2:
+            raise ValueError("moment_transfer holds 2 values")
+    elif transform == "moment":
+        raise ValueError("the moment transform needs moment_transfer")
+    return REPPOINTS_TRANSFORMS[transform]
+
+
+def reppoints_target(pts_init, gt_bbox, strides, *, transform="moment", moment_transfer=None, target_scale=4,
+                     num_pos=1, pos_iou_thr=0.5, neg_iou_thr=0.5, min_pos_iou=0.0, label_init=None, gt_init=None,
+                     label_refine=None, gt_refine=None, state=None, workspace=None):
+    """Both assigners of RepPointsHead.get_loss (models/RepPoints/builder.py:328-388) in one call: pts_init is the
+    list of init-stage point maps (N, 2 * num_points, H_l, W_l), gt_bbox (N, M, 5) [x1, y1, x2, y2, cls].  Returns
+    RepPointsTargets: label_init (N, P), gt_init (N, P, 4) of the point assigner, label_refine, gt_refine of the IoU
+    assigner on the init boxes, and the state block int32[4] with the two BBoxNorm counts and denominators.
+    Nothing is read back from the device."""
+    N, K, P, Hs, Ws, st = _reppoints_levels(pts_init, strides, "pts_init")
+    _chk(gt_bbox, "gt_bbox", ndim=3)
+    if int(gt_bbox.shape[0]) != N or int(gt_bbox.shape[2]) != 5:
+        raise ValueError("gt_bbox should be (N, M, 5) with N = %d, got %s" % (N, tuple(gt_bbox.shape)))
+    M = int(gt_bbox.shape[1])
+    tr = _reppoints_transform(transform, moment_transfer)
+    dev = gt_bbox.device
+    label_init = _fcos_out(label_init, "label_init", (N, P), dev)
+    gt_init = _fcos_out(gt_init, "gt_init", (N, P, 4), dev)
+    label_refine = _fcos_out(label_refine, "label_refine", (N, P), dev)
+    gt_refine = _fcos_out(gt_refine, "gt_refine", (N, P, 4), dev)
+    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    if N * P == 0:        # the entry point writes nothing: no label, and the denominators are 0 + 1
+        state.copy_(torch.tensor([0, 0, 0x3f800000, 0x3f800000], dtype=torch.int32))
+    ws = _ce_ws(dev, reppoints_target_workspace_bytes(N, M, P), workspace)
+    lib().call("sd_reppoints_target", _parr(pts_init), Hs, Ws, st, len(pts_init), _p(gt_bbox), _p(moment_transfer),
+               _p(label_init), _p(gt_init), _p(label_refine), _p(gt_refine), _p(state), N, M, K, tr,
+               float(target_scale), int(num_pos), float(pos_iou_thr), float(neg_iou_thr), float(min_pos_iou), _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return RepPointsTargets(label_init, gt_init, label_refine, gt_refine, state)
+
+
+def _reppoints_loss_args(pts_init, pts_refine, targets, strides, transform, moment_transfer):
+    N, K, P, Hs, Ws, st = _reppoints_levels(pts_init, strides, "pts_init")
+    _reppoints_levels(pts_refine, strides, "pts_refine", like=pts_init)
+    tr = _reppoints_transform(transform, moment_transfer)
+    for name in ("label_init", "gt_init", "label_refine", "gt_refine"):
+        t = getattr(targets, name)
+        _chk(t, name)
+        if t.numel() != N * P * (4 if name.startswith("gt") else 1):
+            raise ValueError("the targets do not hold N = %d images of P = %d points" % (N, P))
+    _chk(targets.state, "state", dtype=torch.int32)
+    return N, K, P, Hs, Ws, st, tr
+
+
+def reppoints_box_loss_forward(pts_init, pts_refine, targets, strides, *, transform="moment", moment_transfer=None,
+                               scale=4, loss_init=None, loss_refine=None):
+    """pts_init_loss and pts_refine_loss of RepPointsHead.get_loss (builder.py:415-481), each (N, P, 4), over
+    per-level point maps in one launch: smooth_l1((box - gt) / (stride * scale), 3) * (label > 0)."""
+    N, K, P, Hs, Ws, st, tr = _reppoints_loss_args(pts_init, pts_refine, targets, strides, transform, moment_transfer)
+    dev = pts_init[0].device
+    loss_init = _fcos_out(loss_init, "loss_init", (N, P, 4), dev)
+    loss_refine = _fcos_out(loss_refine, "loss_refine", (N, P, 4), dev)
+    lib().call("sd_reppoints_box_loss_fwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init),
+               _p(moment_transfer), _p(targets.label_init), _p(targets.gt_init), _p(targets.label_refine),
+               _p(targets.gt_refine), _p(loss_init), _p(loss_refine), N, K, tr, float(scale), _stream())
+    return loss_init, loss_refine
+
+
+def reppoints_box_loss_backward(pts_init, pts_refine, targets, strides, *, transform="moment", moment_transfer=None,
+                                scale=4, grad_scale_init=0.5, grad_scale_refine=1.0, req="write", d_init=None,
+                                d_refine=None, d_moment_transfer=None, workspace=None):
+    """The gradients of both box losses in one launch: (d_pts_init list, d_pts_refine list, d_moment_transfer (2,)).
+    No top gradient enters (MakeLoss); the head gradient is grad_scale / the BBoxNorm denominator of the state block.
+    req = 'add' accumulates into the tensors given."""
+    N, K, P, Hs, Ws, st, tr = _reppoints_loss_args(pts_init, pts_refine, targets, strides, transform, moment_transfer)
+    if req not in ("write", "add"):
+        raise ValueError("req is 'write' or 'add'")
+    dev = pts_init[0].device
+    outs = []
+    for given, like, name in ((d_init, pts_init, "d_init"), (d_refine, pts_refine, "d_refine")):
+        if given is None:
+            if req == "add":
+                raise ValueError("req='add' needs the tensors to add to")
+            given = [torch.empty_like(t) for t in like]
+        _reppoints_levels(given, strides, name, like=like)
+        outs.append(list(given))
+    if d_moment_transfer is None and req == "add":
+        raise ValueError("req='add' needs the tensors to add to")
+    d_moment_transfer = _fcos_out(d_moment_transfer, "d_moment_transfer", (2,), dev)
+    if N * P == 0:
+        return outs[0], outs[1], d_moment_transfer if req == "add" else d_moment_transfer.zero_()
+    ws = _ce_ws(dev, reppoints_box_loss_workspace_bytes(N, P), workspace)
+    lib().call("sd_reppoints_box_loss_bwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init),
+               _p(moment_transfer), _p(targets.label_init), _p(targets.gt_init), _p(targets.label_refine),
+               _p(targets.gt_refine), _p(targets.state), _parr(outs[0]), _parr(outs[1]), _p(d_moment_transfer), N, K,
+               tr, float(scale), float(grad_scale_init), float(grad_scale_refine), REQ[req], _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return outs[0], outs[1], d_moment_transfer
+
+
+class RepPointsBoxLossFunction(torch.autograd.Function):
+    """loss_init, loss_refine = RepPointsBoxLossFunction.apply(targets, strides, kw, moment_transfer, *pts_init,
+    *pts_refine).  Like the reference's MakeLoss nodes the backward does not look at the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, targets, strides, kw, moment_transfer, *maps):
+        L = len(strides)
+        maps = [t.contiguous() for t in maps]
+        ctx.targets, ctx.strides, ctx.kw, ctx.has_mt = targets, strides, kw, moment_transfer is not None
+        ctx.save_for_backward(*([moment_transfer] if ctx.has_mt else []), *maps)
+        fkw = {k: v for k, v in kw.items() if not k.startswith("grad_scale")}
+        return reppoints_box_loss_forward(maps[:L], maps[L:], targets, strides, moment_transfer=moment_transfer, **fkw)
+
+    @staticmethod
+    def backward(ctx, *_out_grads):
+        saved, L = list(ctx.saved_tensors), len(ctx.strides)
+        mt = saved.pop(0) if ctx.has_mt else None
+        di, dr, dmt = reppoints_box_loss_backward(saved[:L], saved[L:], ctx.targets, ctx.strides, moment_transfer=mt,
+                                                  **ctx.kw)
+        return (None, None, None, dmt if ctx.has_mt else None) + tuple(di) + tuple(dr)
+
+
+def reppoints_box_loss(pts_init, pts_refine, targets, strides, *, transform="moment", moment_transfer=None, scale=4,
+                       grad_scale_init=0.5, grad_scale_refine=1.0):
+    """Both RepPoints box losses with autograd over lists of level maps: (loss_init, loss_refine), each (N, P, 4).
+    `targets` is what reppoints_target returned."""
+    kw = dict(transform=transform, scale=scale, grad_scale_init=grad_scale_init, grad_scale_refine=grad_scale_refine)
+    return RepPointsBoxLossFunction.apply(targets, tuple(strides), kw, moment_transfer, *pts_init, *pts_refine)
+
+
+# --------------------------------------------------------------------------------------------------
 # FCOS test-time decode  (models/FCOS/builder.py get_all_proposal, models/FCOS/utils.py: the CustomOps
 # get_proposal_single_stage and get_batch_proposal)
 # --------------------------------------------------------------------------------------------------
