@@ -289,6 +289,14 @@ __global__ __launch_bounds__(THREADS) void roi_align_bwd_plane(BwdArgs a) {
 // in the fp32 kernel: fp32 tap values, fixed-point or fp32 accumulation in LDS; only the two I/O
 // conversions move into the kernel) -- what an fp16 graph computes with the reference's casts around
 // the op (models/FPN/builder.py:581-586, 607-608), without the two cast passes over 26 + 182 MB.
+// Does one of four packed arg-max codes (3k + l, k, l in 0..2; 255 = nothing pooled) name a third candidate, k == 2
+// or l == 2: a byte in {2, 5, 6, 7, 8}?  All four bytes at once: 5..8 have bit 3 set after + 3 (255 is masked to 127
+// first: 130, bit 3 clear, no carry into the next byte), 2 is the zero byte of code ^ 0x02...
+__device__ __forceinline__ bool codes_name_third(unsigned code) {
+  const unsigned ge5 = ((code & 0x7f7f7f7fu) + 0x03030303u) & 0x08080808u;
+  const unsigned z = code ^ 0x02020202u;
+  return (ge5 | ((z - 0x01010101u) & ~z & 0x80808080u)) != 0u;
+}
 struct __attribute__((packed, aligned(2))) H4u {
   __half x, y, z, w;
 };
@@ -303,7 +311,10 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   // the three-output fused op): an item carries its four (x, y) coordinates, no table
   constexpr bool TAPS = MODE == 1, FLT = MODE == 2;
   constexpr int PP = PH * PW, PPS = amax_stride(PP), GP = (PP + 3) / 4, NE = 3 * (PH + PW);
-  constexpr int TS = TAPS ? 2 * NE : NE;
+  // words per RoI in the staged table: TAPS keeps two candidate entries per axis bin in LDS (the third is a side
+  // table in global memory, see scatter_taps), the coordinate table three floats
+  constexpr int TS = TAPS ? kTapMainWords * (PH + PW) : NE;
+  constexpr int SS = kTapSideWords * (PH + PW);
   constexpr int CW = kCoordWords * (PH + PW);  // words per RoI in the forward's table
   constexpr bool TAIL = (PP % 4) != 0;         // last lane of a RoI owns fewer than four bins
   static_assert(TS % 4 == 0 || !TAPS, "tap tables are copied as float4");
@@ -343,7 +354,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   const int* wl = nullptr;
   int wl_n = 0, wl_bound = 0, wl_first = 0;
   float4 rb0 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (a.ws_list) {
+  if (TAPS || a.ws_list) {   // (the tap tables come with the lists: MODE 1 carries no list builder)
     wl = a.ws_list + (long)(a.unit_base[li] + u) * (a.R + 2);
     wl_n = wl[0];
     wl_bound = wl[1];
@@ -357,7 +368,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
     for (int i = tid; i < plane_pad / 4; i += THREADS) p4[i] = z;
   }
   if (tid < 8) nlist[tid] = 0;
-  if (wl) {
+  if (TAPS || wl) {
     if (tid < wl_n) list[tid] = wl_first;
     for (int i = tid + THREADS; i < wl_n; i += THREADS) list[i] = wl[2 + i];
     __syncthreads();  // (nlist cleared)
@@ -366,7 +377,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
       nlist[1] = wl_bound;
     }
     __syncthreads();
-  } else {
+  } else if constexpr (!TAPS) {
     __syncthreads();
     bwd_band_list<PH, PW, THREADS>(a, lvl, img, nbands, row0, row1, rb0, list, nlist, wcnt);
   }
@@ -498,7 +509,15 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   // the two neighbour rows, 0xffff = outside the band, + fraction; column entry: the two columns +
   // fraction) and needs no floor / ceil / clamp / row multiply of its own; with fixed point the
   // gradient is scaled first (a power of two: the products are the same floats times 2^S).
-  auto scatter_taps = [&](const Item& it, int slot) {
+  // The staged table holds candidates 0 and 1 of every bin: the reference's sample loop makes exactly two samples
+  // per bin unless the sample stride rounds to 0.01 px (bins 0.03 px wide), so a third entry per bin would be a third of
+  // the LDS table and of the staging traffic for nothing, and the same LDS holds half as many RoIs again per chunk.
+  // An item one of whose codes names candidate 2 (third = true_type; the caller tests the four code bytes at
+  // once, codes_name_third) fetches that entry from the unit's side table in global memory: rare, divergent, cold.
+  const float2* side = TAPS ? reinterpret_cast<const float2*>(
+                                  a.ws_taps + (long)(a.unit_base[li] + u) * a.R * (2 * NE) + (long)a.R * TS)
+                            : nullptr;
+  auto scatter_taps = [&](const Item& it, int slot, int cb, auto third) {
     if (it.code == 0xffffffffu || (SD_ABLATE(a, 1))) return;  // (profiling build, 1: no scatter)
     const float* tj = tab + slot * TS;
     const float gg[4] = {it.g.x, it.g.y, it.g.z, it.g.w};
@@ -509,8 +528,11 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
       const int code = (it.code >> (8 * s)) & 0xff;
       if (code == 255) continue;
       const int k = __mul24(code, 11) >> 5, l = code - __mul24(k, 3);  // code = 3k + l, k,l in 0..2
-      const float2 re = *reinterpret_cast<const float2*>(tj + 2 * (__mul24(p, 3) + k));
-      const float2 ce = *reinterpret_cast<const float2*>(tj + 2 * (3 * PH + __mul24(q, 3) + l));
+      float2 re, ce;
+      if (decltype(third)::value && k == 2) re = side[(cb + slot) * (SS / 2) + p];
+      else re = *reinterpret_cast<const float2*>(tj + 2 * (2 * p + k));
+      if (decltype(third)::value && l == 2) ce = side[(cb + slot) * (SS / 2) + PH + q];
+      else ce = *reinterpret_cast<const float2*>(tj + 2 * (2 * (PH + q) + l));
       // (the entries hold BYTE offsets into the band: row offsets 4 * (row - row0) * W, 0xffff = outside; columns 4 * col)
       const unsigned rp = __float_as_uint(re.x), cp = __float_as_uint(ce.x);
       const unsigned o0 = rp & 0xffffu, o1 = rp >> 16, wleft = cp & 0xffffu, wright = cp >> 16;
@@ -542,9 +564,9 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
 
   auto stage_tables = [&](int cb, int ncur) {
     if (FLT) return;
-    if (TAPS) {  // the chunk's entries are contiguous in the workspace (list order)
+    if (TAPS) {  // the chunk's main-table entries are contiguous in the workspace (list order)
       const float4* src = reinterpret_cast<const float4*>(
-          a.ws_taps + ((long)(a.unit_base[li] + u) * a.R + cb) * TS);
+          a.ws_taps + (long)(a.unit_base[li] + u) * a.R * (2 * NE) + (long)cb * TS);
       for (int i = tid; i < ncur * (TS / 4); i += THREADS) reinterpret_cast<float4*>(tab)[i] = src[i];
       return;
     }
@@ -625,8 +647,12 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
         load_item(t + THREADS, cb, nli, nxt);
         m_all = umaxr(m_all, absbits4(cur.g));
         if (((trip0 + t / THREADS) & e_mask) == 0) e_acc += fx_range_sample(cur.g.x);   // (wave uniform)
-        if (TAPS) scatter_taps(cur, cur.j);
-        else scatter_item(cur, cur.j);
+        if (TAPS) {
+          if (codes_name_third(cur.code)) scatter_taps(cur, cur.j, cb, std::true_type{});
+          else scatter_taps(cur, cur.j, cb, std::false_type{});
+        } else {
+          scatter_item(cur, cur.j);
+        }
         cur = nxt;
       }
     }
@@ -913,7 +939,9 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   const bool flt = !a.amax8 && a.ax && a.ay;  // float arg-max planes: the same kernel without tables
   SD_REQUIRE(a.amax8 || flt, "RoIAlign backward needs the forward's arg-max (packed bytes or the two float planes)");
   a.float_adds = tuning("roi_align_bwd_fx", 1) == 0 ? 1 : 0;
-  const int tch = a.PP == 49 ? 32 : 16;   // RoIs per staged coordinate-table chunk
+  // RoIs per staged table chunk: the coordinate table (MODE 0) takes 3 words per axis bin and RoI, the tap table
+  // (MODE 1) kTapMainWords = 4 -- two candidate entries of 8 bytes; 48 x 56 words = 10.75 KB at 7x7, as 24 x 112 at 14x14
+  const int tch_coords = a.PP == 49 ? 32 : 16, tch_taps = a.PP == 49 ? 48 : 24;
   const int ne = a.PP == 49 ? 3 * 14 : 3 * 28;  // sample coordinates per RoI
   a.ablate = SD_PROF_TUNING("roi_align_bwd_ablate", 0);
   if ((long)a.R * a.C * a.PP >= (1L << 31)) return SD_ERR_UNSUPPORTED;  // 32-bit lane offsets
@@ -934,9 +962,9 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   long work[SD_MAX_FPN_LEVELS];
   int nl = 0;
   long units = 0;
-  // bands of every level for a band budget and a table entry size (words per sample coordinate)
-  auto plan = [&](long budget, int entry_words) -> int {
-    const size_t tab_bytes = !flt ? (size_t)tch * ne * entry_words * 4 : 0;
+  // bands of every level for a band budget and a table form (tap entries or sample coordinates)
+  auto plan = [&](long budget, bool taps) -> int {
+    const size_t tab_bytes = flt ? 0 : taps ? (size_t)tch_taps * (ne / 3) * kTapMainWords * 4 : (size_t)tch_coords * ne * 4;
     lds_max = 0;
     nl = 0;
     units = 0;
@@ -968,7 +996,7 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   bool use_taps = false, use_lists = false;
   size_t list_bytes = 0;
   if (!flt && workspace && ((uintptr_t)workspace & 15) == 0 && lists_mode == 1) {
-    if (int e = plan(27L * 1024, 2)) return e;
+    if (int e = plan(27L * 1024, true)) return e;
     list_bytes = (((size_t)units * (a.R + 2) * sizeof(int)) + 15) & ~(size_t)15;
     use_taps = workspace_bytes >= list_bytes + (size_t)units * a.R * 2 * ne * sizeof(float);
     // (the tap entries hold 16-bit BYTE offsets into the band: a band wider than 64 KB -- a single row of > 16 K
@@ -978,7 +1006,7 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
     use_lists = use_taps;
   }
   if (!use_taps) {
-    if (int e = plan(36L * 1024, 1)) return e;
+    if (int e = plan(36L * 1024, false)) return e;
     list_bytes = (((size_t)units * (a.R + 2) * sizeof(int)) + 15) & ~(size_t)15;
     use_lists = workspace && lists_mode >= 1 && workspace_bytes >= list_bytes;
   }
@@ -1031,12 +1059,12 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   }
   if (prepass != 0 && !(a.ws_list && a.ws_taps)) return SD_ERR_UNSUPPORTED;
   if (prepass == 1) return SD_OK;
-  // the wide-load kernel: 512 lanes, coordinate tables staged 32 (7x7) / 16 (14x14) RoIs at a time
+  // the wide-load kernel: 512 lanes, coordinate tables staged 32 (7x7) / 16 (14x14) RoIs at a time, tap tables 48 / 24
   // MODE 0: packed arg-max, tables derived per workgroup; 1: tap tables from the list pre-pass; 2: float arg-max planes
-#define SD_BWDW(PHv, TCHv, HALFv)                                                                \
+#define SD_BWDW(PHv, TCHv, TCHTv, HALFv)                                                         \
   do {                                                                                           \
     auto k = flt ? roi_align_bwd_packed4<PHv, PHv, 512, TCHv, 2, false>                          \
-                 : a.ws_taps ? roi_align_bwd_packed4<PHv, PHv, 512, TCHv, 1, HALFv>              \
+                 : a.ws_taps ? roi_align_bwd_packed4<PHv, PHv, 512, TCHTv, 1, HALFv>             \
                              : roi_align_bwd_packed4<PHv, PHv, 512, TCHv, 0, HALFv>;             \
     if (lds_max > 64 * 1024)                                                                     \
       SD_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -1045,13 +1073,13 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   } while (0)
   if (a.half_io) {   // fp16 I/O: packed arg-max only
     if (flt) return SD_ERR_UNSUPPORTED;
-    if (a.PP == 49) SD_BWDW(7, 32, true); else SD_BWDW(14, 16, true);
+    if (a.PP == 49) SD_BWDW(7, 32, 48, true); else SD_BWDW(14, 16, 24, true);
   } else {
-    if (a.PP == 49) SD_BWDW(7, 32, false); else SD_BWDW(14, 16, false);
+    if (a.PP == 49) SD_BWDW(7, 32, 48, false); else SD_BWDW(14, 16, 24, false);
   }
 #undef SD_BWDW
   note_dispatch("%ssd::roi_align_bwd_packed4<%d,%d,512,%d,%d%s>", prepass == 0 && a.ws_list ? "sd::roi_align_bwd_lists + " : "",
-                a.PP == 49 ? 7 : 14, a.PP == 49 ? 7 : 14, tch, flt ? 2 : (a.ws_taps ? 1 : 0), a.half_io ? ",true" : "");
+                a.PP == 49 ? 7 : 14, a.PP == 49 ? 7 : 14, !flt && a.ws_taps ? tch_taps : tch_coords, flt ? 2 : (a.ws_taps ? 1 : 0), a.half_io ? ",true" : "");
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

@@ -305,7 +305,12 @@ struct BwdFusedArgs {
   // packed4 with a workspace: the RoI lists of all (level, image, band) units, built once by
   // roi_align_bwd_lists instead of once per channel: unit u -> [count, weight bound, R indices]
   int* ws_list;
-  float* ws_taps;                    // [unit][R][2 * 3 * (PH + PW)] band-relative tap entries, list order
+  // band-relative tap entries (8 bytes: two packed byte offsets + the fraction), list order.  Per unit a block of
+  // R * 2 * 3 * (PH + PW) words: first the main table [R][2 * (PH + PW)] entries -- candidates 0 and 1 of every row
+  // bin, then of every column bin: (2 * bin + candidate) -- staged into LDS chunk by chunk, then the side table
+  // [R][PH + PW] entries -- candidate 2 (a sample stride <= 0.01 px only), read from global memory by the rare bin
+  // whose code names it
+  float* ws_taps;
   int unit_base[SD_MAX_FPN_LEVELS];  // first unit of launch-order level li
   int lists_units;                   // (level, image, band) units the list pre-pass covers
   int half_io;                       // dy and dx are fp16 (packed arg-max, wide kernel only)
@@ -313,6 +318,7 @@ struct BwdFusedArgs {
   int pix_bound_words;               // list pre-pass: LDS words for the per-cell (4 x 4 pixels) weight bound of a band, of the
                                      // largest level that gets one; 0: the bands keep the summed bound
 };
+constexpr int kTapMainWords = 4, kTapSideWords = 2;   // words per axis bin in the main / side tap table of a RoI
 constexpr int kPixBoundMaxWords = 10240;  // 40 KB of difference array at most
 
 constexpr int kListSplit = 4;         // 512-thread blocks per unit of the stand-alone list pre-pass

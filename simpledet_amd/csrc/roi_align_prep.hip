@@ -295,12 +295,16 @@ __device__ __forceinline__ void bwd_lists_block(const BwdFusedArgs& a, int block
   }
   // ... and the tap entries of the listed RoIs (see roi_align_bwd_packed4): per sample coordinate
   // {neighbours, fraction} with the backward's own expressions, the row neighbours as offsets
-  // inside this band (0xffff: outside), 8 bytes each, in list order
+  // inside this band (0xffff: outside), 8 bytes each, in list order.  A unit's block of R * 2 * NE words is
+  // split in two (BwdFusedArgs::ws_taps): the MAIN table, candidates 0 and 1 of every bin -- all the reference's
+  // sample loop makes unless the sample stride is <= 0.01 px -- which the channel workgroups stage into LDS, and
+  // the SIDE table, candidate 2, which they read from here only for a bin whose code names it.
   if (a.ws_taps) {
-    constexpr int NE = 3 * (PH + PW);
+    constexpr int NE = 3 * (PH + PW), TS = kTapMainWords * (PH + PW), SS = kTapSideWords * (PH + PW);
     const int H = a.L.H[lvl], W = a.L.W[lvl];
     const float scale = a.L.scale[lvl];
     float* tdst = a.ws_taps + (long)unit * a.R * (2 * NE);
+    float* sdst = tdst + (long)a.R * TS;
     for (int i = part * THREADS + tid; i < nl * NE; i += PARTS * THREADS) {
       const int j = i / NE, e = i - j * NE;
       const bool row = e < 3 * PH;
@@ -320,7 +324,9 @@ __device__ __forceinline__ void bwd_lists_block(const BwdFusedArgs& a, int block
         const unsigned o1 = (hi >= row0 && hi < row1) ? (unsigned)(4 * (hi - row0) * W) : 0xffffu;
         w0 = o0 | (o1 << 16);
       }
-      *reinterpret_cast<float2*>(tdst + (long)j * (2 * NE) + 2 * e) = make_float2(__uint_as_float(w0), frac);
+      const int bin = (row ? 0 : PH) + ee / 3, cand = ee % 3;   // axis bin (rows, then columns) and its candidate
+      float* dstp = cand < 2 ? tdst + (long)j * TS + 2 * (2 * bin + cand) : sdst + (long)j * SS + 2 * bin;
+      *reinterpret_cast<float2*>(dstp) = make_float2(__uint_as_float(w0), frac);
     }
   }
 }
