@@ -45,8 +45,9 @@ extern "C" {
 
 const char* sd_last_error(void);
 /* the kernels the calling thread's last fused-RoIAlign entry point launched, e.g.
- * "sd::roi_prep_merged_kernel<7> + sd::roi_align_fwd_band<7,true,false>" (measurement tools label
- * their numbers with the dispatch actually taken instead of assuming one) */
+ * "sd::roi_fwd_prep_kernel<7> + sd::roi_align_fwd_band<7,true,false> (tail tasks: 42 coordinate table + 90
+ * backward plan)" (measurement tools label their numbers with the dispatch actually taken instead of
+ * assuming one) */
 const char* sd_last_dispatch(void);
 /* ABI version of this header: bumped on any signature change AND on any change of a buffer layout
  * or size contract (a caller built against an older header must not pass it buffers of the old
@@ -240,7 +241,9 @@ int sd_fpn_roi_align_bwd_packed_f16(const void* out_grad, const float* rois, con
  * item lists / tap entries / coordinate table and the backward's band lists / tap tables -- are pure
  * functions of `rois` and the level geometry.  With a `plan` buffer of sd_fpn_roi_align_plan_bytes()
  * (16-byte aligned, op state between forward and backward like argmax / coords; ~9 MB at the
- * baseline) the forward builds both in its single pre-pass launch and the backward launches its main
+ * baseline) the forward builds both in its own two launches -- what its main kernel reads in the pre-pass
+ * launch, the rest (coordinate table, the backward's tables) in the main kernel's tail; knob
+ * roi_align_plan_tail = 0: all of it in the pre-pass launch -- and the backward launches its main
  * kernel only: 3 launches per step instead of 4.  Same bits as the _ws pair.  The plan is valid for the
  * shapes, rois and tuning knobs of the forward that filled it; where the band / tap-table form does
  * not apply (knob roi_align_bwd_lists != 1, a level that does not fit) both calls fall back to the

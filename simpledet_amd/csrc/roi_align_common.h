@@ -259,6 +259,11 @@ struct BandPlan {
   unsigned char* fbflag;  // [B*R] 1: handled by the exact per-element workgroups, 2: constant output (nothing pooled)
   int* chan_ctr;    // [kBandMaxUnits] next channel of every virtual unit (zeroed by the pre-pass)
   int nlist, nent;  // pre-pass blocks: lists, entries (then, packed, the coordinate table)
+  // rois-only tables no forward kernel reads, built by the band kernel's workgroups after their band work
+  // (null: built by the pre-pass launch): a counter the workgroups draw task numbers from, zeroed by the pre-pass;
+  // tasks [0, tail_coord): coords_block, [tail_coord, tail_coord + tail_lists): bwd_lists_block
+  int* ticket;
+  int tail_coord, tail_lists;
 };
 
 struct BandArgs {

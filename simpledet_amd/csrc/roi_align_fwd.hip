@@ -19,7 +19,7 @@
 //    global atomics.  (The reference zero-fills dX and issues 4 global atomics per output.)
 //  * naive kernels (one thread per output, the reference's structure) are kept for unusual pooled
 //    sizes, as the in-kernel fallback for degenerate sample loops, and as the A/B baseline.
-#include "roi_align_common.h"
+#include "roi_align_lists.h"
 
 namespace sd {
 
@@ -532,8 +532,9 @@ __device__ __forceinline__ int band_fill(const float* gsrc, int len, float* buf,
 // on their way into LDS, the maximum is rounded to nearest even on the way out) -- what an fp16 graph
 // gets from X.to_fp32 -> ROIAlign -> X.to_fp16 (models/FPN/builder.py:581-586, 607-608) without the
 // two cast passes, and with half the feature traffic.
+// bplan: the backward's plan (launch_bwd_fused, prepass = 1) when the tail builds its tables (A.p.tail_lists > 0)
 template <int POOL, bool PK, bool HALF = false>
-__global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A) {
+__global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, BwdFusedArgs bplan) {
   using TIn = typename std::conditional<HALF, __half, float>::type;
   constexpr int AL = HALF ? 8 : 4;   // elements per 16 bytes of the input
   const FwdArgs& a = A.f;
@@ -1095,6 +1096,35 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A) {
       }  // flagged RoIs
     }
     }
+  // ---- tail: the rois-only tables that nothing in this launch reads -- the packed arg-max's coordinate table (an
+  // output of the op) and the backward's band lists / tap tables / weight bounds (read one launch later) -- as tasks
+  // drawn from one counter.  As blocks of the pre-pass they kept the band kernel waiting (~3 us of every step);
+  // here they run on the CUs whose workgroups are done while the slowest units finish.  A workgroup never waits
+  // for another: the counter is a relaxed add, nothing is published or polled, the stream orders the readers
+  // behind the whole kernel; a workgroup that finishes late finds the counter exhausted and leaves. ----
+  if (P.ticket) {   // (uniform)
+    const int ntasks = P.tail_coord + P.tail_lists;
+    // the task blocks reuse the band buffers: every LDS-targeted load of this workgroup has landed (the barrier at
+    // the top of the loop makes that true of all its waves; it also holds for a workgroup that made no visit)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // The coordinate tasks index the level geometry per lane.  Through `a.L` the compiler answers that with
+    // either a private copy of an array (20 bytes of scratch per lane) or fifteen more live scalars in a kernel
+    // that is already short of them; read from the kernel-argument segment as plain memory -- an address the
+    // compiler knows nothing about -- it is three loads.
+    static_assert(offsetof(BandArgs, f) == 0 && offsetof(FwdArgs, L) == 0, "RoiLevels leads the kernel arguments");
+    const RoiLevels* geom_p = (const RoiLevels*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(geom_p));
+    const RoiLevels& geom = *geom_p;
+    for (;;) {
+      __syncthreads();   // everyone is done with the last task's LDS and has read its number
+      if (tid == 0) s_pick = __hip_atomic_fetch_add(P.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __syncthreads();
+      const int t = s_pick;
+      if (t >= ntasks) break;
+      if (PK && t < P.tail_coord) coords_block<POOL>(a, geom, t);
+      else bwd_lists_block<POOL, POOL, kBandThreads, kMergedListSplit>(bplan, t - P.tail_coord, band_smem);
+    }
+  }
 #ifdef SD_PROFILING
   if (a.dbg && lane == 0) {
     long long* d = a.dbg + ((long)blockIdx.x * kBandWaves + wave) * 8;
@@ -1407,7 +1437,9 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     const size_t itemb = al16((size_t)a.B * SD_MAX_FPN_LEVELS * kBandSub * ((a.R + kBandSub - 1) / kBandSub) *
                               POOL * sizeof(unsigned));
     const size_t segb = al16((size_t)units * kBandSub * sizeof(int2));
-    const size_t need = 16 + 2 * ent + 2 * valb + itemb + segb + al16(nroi) + kBandMaxUnits * sizeof(int);
+    // (+ 16: the task counter of the kernel's tail behind chan_ctr, out of the slack of
+    // sd_fpn_roi_align_workspace_bytes -- the alignment padding above stays below 100 of its 256 bytes)
+    const size_t need = 16 + 2 * ent + 2 * valb + itemb + segb + al16(nroi) + kBandMaxUnits * sizeof(int) + 16;
     int wg = 0;
     P.nunits = units;
     // channels a workgroup reserves at a time: 4 (single-channel grabs +7 %: the 196-byte rows of
@@ -1447,7 +1479,23 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
       const int smem = 2 * kBandBufFloats * (int)sizeof(float);
       const bool merged = bplan && bplan->lists_units > 0 && bplan->PP == POOL * POOL;
       if (bplan_done) *bplan_done = merged;
-      if (int e = launch_fwd_prep(A, POOL, nlist + nent + ncoord, merged ? bplan : nullptr, st)) return e;
+      // roi_align_plan_tail = 1 (default): the pre-pass launch builds only what the band kernel reads (lists and
+      // entries); the coordinate table and the backward's tables are tasks in the band kernel's tail.  0: all of
+      // it in the pre-pass launch (merged with the backward's blocks when there is a plan).  (Float arg-max without
+      // a plan has no such tables; roi_align_fwd_quad, float arg-max only, keeps its pre-pass as it is.)
+      const int nbwd = merged ? bplan->lists_units * (kMergedListSplit + (bplan->pix_bound_words > 0 ? 1 : 0)) : 0;
+      const size_t tail_lds = merged ? (size_t)(a.R + 8 + 16 + bplan->pix_bound_words) * 4 : 0;
+      const bool tail = tuning("roi_align_plan_tail", 1) == 1 && ncoord + nbwd > 0 && tail_lds <= (size_t)smem;
+      static const BwdFusedArgs no_plan{};
+      const BwdFusedArgs& tplan = tail && merged ? *bplan : no_plan;
+      if (tail) {
+        P.ticket = P.chan_ctr + kBandMaxUnits;
+        P.tail_coord = ncoord;
+        P.tail_lists = nbwd;
+      }
+      if (int e = tail ? launch_fwd_prep(A, POOL, nlist + nent, nullptr, st)
+                       : launch_fwd_prep(A, POOL, nlist + nent + ncoord, merged ? bplan : nullptr, st))
+        return e;
       // single level, 7x7, float arg-max, four whole planes fit in LDS together (the C4 family): one workgroup
       // per (channel quad, image) with channel-last planes and 784-byte stores (`roi_align_fwd_quad` = 0: the band kernel)
       {
@@ -1469,7 +1517,7 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     auto k = roi_align_fwd_band<POOLV, PK>;                                                       \
     SD_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                      smem));                                                      \
-    hipLaunchKernelGGL(k, dim3(wg + kBandFallbackWGs), dim3(kBandThreads), smem, st, A);          \
+    hipLaunchKernelGGL(k, dim3(wg + kBandFallbackWGs), dim3(kBandThreads), smem, st, A, tplan);   \
   } while (0)
       if (a.half_io) {  // fp16 features and output, packed arg-max
 #define SD_FWD_BAND_H(POOLV)                                                                      \
@@ -1477,7 +1525,7 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     auto k = roi_align_fwd_band<POOLV, true, true>;                                               \
     SD_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                      smem));                                                      \
-    hipLaunchKernelGGL(k, dim3(wg + kBandFallbackWGs), dim3(kBandThreads), smem, st, A);          \
+    hipLaunchKernelGGL(k, dim3(wg + kBandFallbackWGs), dim3(kBandThreads), smem, st, A, tplan);   \
   } while (0)
         if (POOL == 7) SD_FWD_BAND_H(7); else SD_FWD_BAND_H(14);
 #undef SD_FWD_BAND_H
@@ -1487,8 +1535,10 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
         if (a.amax8) SD_FWD_BAND(14, true); else SD_FWD_BAND(14, false);
       }
 #undef SD_FWD_BAND
-      note_dispatch("sd::%s<%d> + sd::roi_align_fwd_band<%d,%s,%s>", merged ? "roi_prep_merged_kernel" : "roi_fwd_prep_kernel",
-                    POOL, POOL, a.amax8 ? "true" : "false", a.half_io ? "true" : "false");
+      char tail_note[96] = "";
+      if (tail) snprintf(tail_note, sizeof(tail_note), " (tail tasks: %d coordinate table + %d backward plan)", ncoord, nbwd);
+      note_dispatch("sd::%s<%d> + sd::roi_align_fwd_band<%d,%s,%s>%s", merged && !tail ? "roi_prep_merged_kernel" : "roi_fwd_prep_kernel",
+                    POOL, POOL, a.amax8 ? "true" : "false", a.half_io ? "true" : "false", tail_note);
       SD_LAUNCH_CHECK();
       return SD_OK;
     }
