@@ -65,7 +65,8 @@ const char* sd_last_dispatch(void);
  * sd_mask_loss_fwd / _bwd with their workspace queries added (nothing existing changes).  The
  * sd_quant_int8_* entry points were added at 12 as well: no existing signature, layout or size contract moved.
  * So were the sd_fcos_* entry points (FCOS targets and losses; sd_fcos_decode and sd_fcos_sigmoid, the test-time
- * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*.
+ * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*, and
+ * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -958,6 +959,59 @@ int sd_mask_loss_fwd(const float* logits, const float* cls, const float* target,
                      int R, int K, long P, void* workspace, size_t workspace_bytes, void* stream);
 int sd_mask_loss_bwd(const float* logits, const float* cls, const float* target, float* d_logits, int R, int K,
                      long P, float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The Mask Scoring R-CNN training head (models/msrcnn/builder.py), fp32: the mask loss of
+ *   MaskFasterRcnnHead.get_loss (:383-424), which also returns the gathered sigmoid `mask_pred_prob`, and the
+ *   MaskIoU loss of MaskIoUConvHead.get_loss (:143-168) with the Python CustomOp `maskiou_compute`
+ *   (models/msrcnn/maskiou_compute.py:14-38: four asnumpy() copies, numpy, two copies back) inside it.
+ *   R rows (RoIs), K classes, P = resolution^2 pixels; cls (R) float is the builder's mask_label (mask_inds).
+ *   sd_msrcnn_mask_loss_fwd: logits (R, K, P), cls, target (R, P) -> out, count_sum (one float each), bit-equal to
+ *     sd_mask_loss_fwd on the same inputs (the same unit and reduction code runs), and prob (R, P):
+ *         prob[r, p] = 1.0f / (1.0f + expf(-logits[r, (int)cls[r], p]))       MXNet's Activation(sigmoid)
+ *     for EVERY element of a row whose cls names a plane, those with target -1 included (the MaskIoU head reads
+ *     them).  A row whose cls is NaN, negative or >= K is ignored as in sd_mask_loss_*: its logits are not
+ *     read and its prob row is +0.0.  One pass over the selected planes, one launch, plus the fixed-order finish.
+ *   sd_msrcnn_mask_loss_bwd: d_prob (R, P) may be NULL.  d_logits (R, K, P) is written once (kWriteTo): +0.0 in
+ *     the planes that are not selected; in the selected plane
+ *         g_ce + d_prob * (p * (1.0f - p)),   g_ce = sd_mask_loss_bwd's value (+0.0 where the target is -1),
+ *     p recomputed by the forward's expression (equal bits to reading prob).  With d_prob == NULL all of d_logits
+ *     is bit-equal to sd_mask_loss_bwd (the same kernel runs).  d_prob of ignored rows is not read.  16-byte loads
+ *     (logits, target, d_prob) and 16-byte stores (d_logits) are decided separately; P % 4 != 0 or a pointer off
+ *     its 16-byte boundary takes a scalar path with equal bits.
+ *   sd_maskiou_loss_fwd: iou_pred (R, K), prob (R, P), target (R, P), ratio (R), cls (R) -> iou_target (R),
+ *     weight (R), loss (1), weight_sum (1).  Per row, restating maskiou_compute.py:20-35 with numpy's types:
+ *         pred = prob > 0.5f;  Ps = count(pred);  I = sum(target where pred);  T = sum(target)
+ *         union = max(double(T) / double(ratio) + double(Ps) - double(I), 1.0)
+ *         iou_target = float(double(max(I, 0)) / union);       weight = cls > 0 ? 1 : 0
+ *     max is numpy.maximum (a NaN propagates); a zero ratio follows IEEE (a -inf union becomes 1, 0 / 0 a NaN).
+ *     The contract is integer-valued targets (-1, 0, 1): any summation order gives the reference's bits; for other
+ *     values I and T are fixed-order float sums.  Then p = iou_pred[r, (int)cls[r]] and
+ *         S = sum_r ((iou_target - p)^2 * weight),  W = sum_r weight,  loss = 0.5f * S / max(W, 1),  weight_sum = W
+ *     over the rows whose cls names a column; a row whose cls is NaN, negative or >= K reaches neither S nor W and
+ *     its iou_pred is not read (iou_target and weight are still written for it).  Fixed-order sums, no float atomics.
+ *   sd_maskiou_loss_bwd: d_iou_pred (R, K) written once: ((-(iou_target - p)) * weight) / max(W, 1) * grad_scale in
+ *     column (int)cls[r], +0.0 everywhere else.  Nothing flows to prob, target or ratio (the reference BlockGrads
+ *     the CustomOp's outputs).  It needs no workspace.
+ *   All: kernels only, no memset node, no host synchronisation, graph-capturable; workspaces need no clearing and
+ *   their sizes are monotone; repeated calls give equal bits; 4-byte alignment suffices.  Checked before anything
+ *   touches the device -- SD_ERR_INVALID_ARG: a negative size, a null pointer (other than d_prob);
+ *   SD_ERR_WORKSPACE: a NULL or too small workspace; SD_ERR_UNSUPPORTED: R*K*P (mask loss) or R*K, R*P (MaskIoU)
+ *   > 2^31 - 1 elements.  A zero size succeeds without a launch, the sizes still checked.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_msrcnn_mask_loss_workspace_bytes(int R, int K, long P);
+int sd_msrcnn_mask_loss_fwd(const float* logits, const float* cls, const float* target, float* out,
+                            float* count_sum, float* prob, int R, int K, long P, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int sd_msrcnn_mask_loss_bwd(const float* logits, const float* cls, const float* target, const float* d_prob,
+                            float* d_logits, int R, int K, long P, float grad_scale, void* workspace,
+                            size_t workspace_bytes, void* stream);
+size_t sd_maskiou_loss_workspace_bytes(int R, int K, long P);
+int sd_maskiou_loss_fwd(const float* iou_pred, const float* prob, const float* target, const float* ratio,
+                        const float* cls, float* iou_target, float* weight, float* loss, float* weight_sum, int R,
+                        int K, long P, void* workspace, size_t workspace_bytes, void* stream);
+int sd_maskiou_loss_bwd(const float* iou_pred, const float* cls, const float* iou_target, const float* weight,
+                        const float* weight_sum, float* d_iou_pred, int R, int K, float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_Quantization_int8  (mx.sym.contrib.Quantization_int8; utils/graph_optimize.py:attach_quantize_node puts

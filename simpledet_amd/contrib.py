@@ -343,6 +343,62 @@ def mask_loss(logits, cls, target, grad_scale=1.0):
     return _MaskLoss.apply(logits, cls, target, float(grad_scale))
 
 
+class _MsrcnnMaskLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, cls, target, grad_scale):
+        logits = logits.contiguous()
+        out, _, prob = ops.msrcnn_mask_loss_forward(logits, cls.contiguous(), target.contiguous())
+        ctx.save_for_backward(logits, cls, target)
+        ctx.grad_scale = grad_scale
+        ctx.set_materialize_grads(False)      # no gradient into prob: d_prob stays None, not a tensor of zeros
+        return out, prob
+
+    @staticmethod
+    def backward(ctx, _dy, d_prob):
+        logits, cls, target = ctx.saved_tensors
+        if d_prob is not None:
+            d_prob = d_prob.contiguous()
+        return (ops.msrcnn_mask_loss_backward(logits, cls.contiguous(), target.contiguous(), d_prob, ctx.grad_scale),
+                None, None, None)
+
+
+def msrcnn_mask_loss(logits, cls, target, grad_scale=1.0):
+    """Mask Scoring R-CNN's MaskFasterRcnnHead.get_loss (models/msrcnn/builder.py:383-424) as one op: logits
+    (R, K, h, w), cls (R,) float, target (R, h, w) -> (mask loss (1,), mask_pred_prob (R, h, w)).  The loss output
+    IGNORES its incoming gradient, as the reference's loss operator does (grad_scale scales the gradient only); prob
+    is an ordinary differentiable output: what flows into it is added, through the sigmoid, to the selected plane's
+    gradient in the same single pass that writes the dense (R, K, h, w) gradient."""
+    return _MsrcnnMaskLoss.apply(logits, cls, target, float(grad_scale))
+
+
+class _MaskIoULoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, iou_pred, prob, target, ratio, cls, grad_scale):
+        iou_pred = iou_pred.contiguous()
+        cls = cls.contiguous()
+        iou_target, weight, loss, weight_sum = ops.maskiou_loss_forward(
+            iou_pred, prob.contiguous(), target.contiguous(), ratio.contiguous(), cls)
+        ctx.save_for_backward(iou_pred, cls, iou_target, weight, weight_sum)
+        ctx.grad_scale = grad_scale
+        ctx.mark_non_differentiable(iou_target, weight)
+        return loss, iou_target, weight
+
+    @staticmethod
+    def backward(ctx, _dy, _dt, _dw):
+        iou_pred, cls, iou_target, weight, weight_sum = ctx.saved_tensors
+        return (ops.maskiou_loss_backward(iou_pred, cls, iou_target, weight, weight_sum, ctx.grad_scale),
+                None, None, None, None, None)
+
+
+def maskiou_loss(iou_pred, prob, target, ratio, cls, grad_scale=1.0, return_target=False):
+    """MaskIoUConvHead.get_loss behind its tower (models/msrcnn/builder.py:146-167) as one op: iou_pred (R, K), prob
+    and target (R, h, w), ratio (R,), cls (R,) float -> the (1,) MaskIoU loss; with return_target=True also
+    (iou_target, weight), maskiou_compute.py's outputs.  Gradient flows to iou_pred alone (the reference BlockGrads
+    the target and the weight) and IGNORES the incoming gradient, as MakeLoss does."""
+    loss, iou_target, weight = _MaskIoULoss.apply(iou_pred, prob, target, ratio, cls, float(grad_scale))
+    return (loss, iou_target, weight) if return_target else loss
+
+
 def reppoints_head_loss(pts_init, pts_refine, gt_bbox, moment_transfer, strides, transform="moment", scale=4,
                         target_scale=4, num_pos=1, pos_iou_thr=0.5, neg_iou_thr=0.5, min_pos_iou=0.0):
     """The box branches of RepPointsHead.get_loss (models/RepPoints/builder.py:311-484) on lists of per-level point

@@ -39,210 +39,10 @@
 // The 16-byte path (k % 4 == 0, or P % 4 == 0, and 16-byte aligned pointers) and the scalar path assign the
 // same elements to the same lanes in the same order: equal bits.  The fused op on (R, K, P) and the drop-in
 // operator on the gathered (1, R*P) row run the same units through the same functions: equal bits as well.
-#include "common.h"
-#include "../../include/simpledet_ops.h"
-#include <math.h>
+// The element, unit and reduction code lives in sigmoid_ce_common.h: msrcnn_head.hip runs the same functions.
+#include "sigmoid_ce_common.h"
 
 namespace sd {
-
-constexpr int kCeT = 256;
-constexpr int kCeWaves = kCeT / kWave;
-constexpr unsigned kCeUnit = 4 * kWave;        // elements per unit (one wave, four per lane)
-constexpr int kCeMaxBlocks = kNumCU * 8;       // memory-bound grid: 8 workgroups per CU, stride the rest
-constexpr long kCeMaxElems = 2147483647L;      // element and unit indices are 32-bit inside the kernels
-
-__device__ __forceinline__ float ce_loss(float x, float t) {
-  const float ge = x >= 0.0f ? 1.0f : 0.0f;
-  const float lg = logf(1.0f + expf(x - (2.0f * x) * ge));
-  return (float)((-1.0 * (double)x) * (double)(t - ge) + (double)lg);
-}
-
-__device__ __forceinline__ float ce_grad(float x, float t, float count_sum, float scale) {
-  const float g = (float)(1.0 / (1.0 + (double)expf(-x)) - (double)t);
-  return (g / count_sum) * scale;
-}
-
-// (int)cls when it names a plane, -1 otherwise (NaN fails both comparisons)
-__device__ __forceinline__ int mask_class(float c, unsigned K) {
-  return c >= 0.0f && c < (float)K ? (int)c : -1;
-}
-
-template <bool VEC>
-__device__ __forceinline__ float4 ce_load4(const float* __restrict__ p, unsigned cnt) {
-  if (VEC) return *reinterpret_cast<const float4*>(p);
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (cnt > 0) v.x = p[0];
-  if (cnt > 1) v.y = p[1];
-  if (cnt > 2) v.z = p[2];
-  if (cnt > 3) v.w = p[3];
-  return v;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void ce_store4(float* __restrict__ p, unsigned cnt, const float4& v) {
-  if (VEC) {
-    *reinterpret_cast<float4*>(p) = v;
-    return;
-  }
-  if (cnt > 0) p[0] = v.x;
-  if (cnt > 1) p[1] = v.y;
-  if (cnt > 2) p[2] = v.z;
-  if (cnt > 3) p[3] = v.w;
-}
-
-// The two sources of (x, t) for `cnt` (1..4) consecutive elements of row `row` from element e0 on.
-// Absent elements and ignored ones come back with t = -1 and x = 0.
-struct CeRows {            // the drop-in operator: (n, k) rows
-  const float* data;
-  const float* label;
-  unsigned k;
-  template <bool VEC>
-  __device__ __forceinline__ float4 targets(unsigned row, unsigned e0, unsigned cnt) const {
-    float4 t = ce_load4<VEC>(label + (size_t)row * k + e0, cnt);
-    if (!VEC) {
-      if (cnt < 2) t.y = -1.0f;
-      if (cnt < 3) t.z = -1.0f;
-      if (cnt < 4) t.w = -1.0f;
-    }
-    return t;
-  }
-  template <bool VEC>
-  __device__ __forceinline__ float4 logits_at(unsigned row, unsigned e0, unsigned cnt, const float4&) const {
-    return ce_load4<VEC>(data + (size_t)row * k + e0, cnt);
-  }
-};
-
-struct CeMask {            // the fused op: element e of the one row is (r, p) = (e / P, e % P) of plane cls[r]
-  const float* logits;
-  const float* cls;
-  const float* target;
-  unsigned K, P;
-  __device__ __forceinline__ float one_target(unsigned e) const {
-    return mask_class(cls[e / P], K) < 0 ? -1.0f : target[e];
-  }
-  __device__ __forceinline__ float one_logit(unsigned e) const {
-    const unsigned r = e / P;
-    const int c = mask_class(cls[r], K);
-    return logits[((size_t)r * K + (unsigned)c) * P + (e - r * P)];
-  }
-  template <bool VEC>
-  __device__ __forceinline__ float4 targets(unsigned, unsigned e0, unsigned cnt) const {
-    if (VEC) {   // P % 4 == 0: the four elements lie in one RoI
-      const float4 t = *reinterpret_cast<const float4*>(target + e0);
-      return mask_class(cls[e0 / P], K) < 0 ? make_float4(-1.f, -1.f, -1.f, -1.f) : t;
-    }
-    float4 t = make_float4(-1.f, -1.f, -1.f, -1.f);
-    if (cnt > 0) t.x = one_target(e0);
-    if (cnt > 1) t.y = one_target(e0 + 1);
-    if (cnt > 2) t.z = one_target(e0 + 2);
-    if (cnt > 3) t.w = one_target(e0 + 3);
-    return t;
-  }
-  // (a rejected row's logits are not read: its targets came back as -1)
-  template <bool VEC>
-  __device__ __forceinline__ float4 logits_at(unsigned, unsigned e0, unsigned cnt, const float4& t) const {
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (VEC) {
-      const unsigned r = e0 / P;
-      const int c = mask_class(cls[r], K);
-      if (c >= 0) x = *reinterpret_cast<const float4*>(logits + ((size_t)r * K + (unsigned)c) * P + (e0 - r * P));
-      return x;
-    }
-    if (cnt > 0 && t.x != -1.0f) x.x = one_logit(e0);
-    if (cnt > 1 && t.y != -1.0f) x.y = one_logit(e0 + 1);
-    if (cnt > 2 && t.z != -1.0f) x.z = one_logit(e0 + 2);
-    if (cnt > 3 && t.w != -1.0f) x.w = one_logit(e0 + 3);
-    return x;
-  }
-};
-
-struct CeUnits {
-  unsigned units, per_row, k;   // units = n * per_row, per_row = ceil(k / kCeUnit)
-};
-
-// elements of the lane in unit u: row, first element, how many (0..4)
-__device__ __forceinline__ void ce_lane_span(const CeUnits& g, unsigned u, unsigned& row, unsigned& e0, unsigned& cnt) {
-  row = u / g.per_row;
-  e0 = (u - row * g.per_row) * kCeUnit + 4u * (threadIdx.x & (kWave - 1));
-  cnt = e0 >= g.k ? 0u : (g.k - e0 < 4u ? g.k - e0 : 4u);
-}
-
-// forward: loss / count elements (when asked for) and the unit's partial loss sum and count
-template <class Src, bool VEC>
-__global__ __launch_bounds__(kCeT) void ce_fwd_units_kernel(Src s, CeUnits g, float* __restrict__ loss,
-                                                            float* __restrict__ count, float* __restrict__ lpart,
-                                                            int* __restrict__ cpart) {
-  const unsigned step = gridDim.x * kCeWaves;
-  for (unsigned u = blockIdx.x * kCeWaves + threadIdx.x / kWave; u < g.units; u += step) {
-    unsigned row, e0, cnt;
-    ce_lane_span(g, u, row, e0, cnt);
-    float4 l = make_float4(0.f, 0.f, 0.f, 0.f), c = l;
-    if (cnt) {
-      const float4 t = s.template targets<VEC>(row, e0, cnt);
-      const float4 x = s.template logits_at<VEC>(row, e0, cnt, t);
-      if (t.x != -1.0f) { l.x = ce_loss(x.x, t.x); c.x = 1.0f; }
-      if (t.y != -1.0f) { l.y = ce_loss(x.y, t.y); c.y = 1.0f; }
-      if (t.z != -1.0f) { l.z = ce_loss(x.z, t.z); c.z = 1.0f; }
-      if (t.w != -1.0f) { l.w = ce_loss(x.w, t.w); c.w = 1.0f; }
-      const size_t at = (size_t)row * g.k + e0;
-      if (loss) ce_store4<VEC>(loss + at, cnt, l);
-      if (count) ce_store4<VEC>(count + at, cnt, c);
-    }
-    const float a = wave_sum_f32(((l.x + l.y) + l.z) + l.w);
-    const int n = wave_sum_i32((int)c.x + (int)c.y + (int)c.z + (int)c.w);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-      lpart[u] = a;
-      cpart[u] = n;
-    }
-  }
-}
-
-// backward, first pass: the unit's count (and the count elements when asked for)
-template <class Src, bool VEC>
-__global__ __launch_bounds__(kCeT) void ce_count_units_kernel(Src s, CeUnits g, float* __restrict__ count,
-                                                              int* __restrict__ cpart) {
-  const unsigned step = gridDim.x * kCeWaves;
-  for (unsigned u = blockIdx.x * kCeWaves + threadIdx.x / kWave; u < g.units; u += step) {
-    unsigned row, e0, cnt;
-    ce_lane_span(g, u, row, e0, cnt);
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (cnt) {
-      const float4 t = s.template targets<VEC>(row, e0, cnt);
-      c = make_float4(t.x != -1.0f ? 1.f : 0.f, t.y != -1.0f ? 1.f : 0.f, t.z != -1.0f ? 1.f : 0.f,
-                      t.w != -1.0f ? 1.f : 0.f);
-      if (count) ce_store4<VEC>(count + (size_t)row * g.k + e0, cnt, c);
-    }
-    const int n = wave_sum_i32((int)c.x + (int)c.y + (int)c.z + (int)c.w);
-    if ((threadIdx.x & (kWave - 1)) == 0) cpart[u] = n;
-  }
-}
-
-// a wave per row: the partials in a fixed order.  lpart null: counts only (the backward)
-__global__ __launch_bounds__(kCeT) void ce_rows_kernel(const float* __restrict__ lpart, const int* __restrict__ cpart,
-                                                       unsigned n, unsigned per_row, float* __restrict__ out,
-                                                       float* __restrict__ loss_sum, float* __restrict__ count_sum) {
-  const unsigned lane = threadIdx.x & (kWave - 1);
-  const unsigned step = gridDim.x * kCeWaves;
-  for (unsigned row = blockIdx.x * kCeWaves + threadIdx.x / kWave; row < n; row += step) {
-    const size_t base = (size_t)row * per_row;
-    float a = 0.f;
-    int c = 0;
-    for (unsigned i = lane; i < per_row; i += kWave) {
-      if (lpart) a += lpart[base + i];
-      c += cpart[base + i];
-    }
-    a = wave_sum_f32(a);
-    c = wave_sum_i32(c);
-    if (lane == 0) {
-      const float cs = (float)c + 1e-5f;
-      count_sum[row] = cs;
-      if (lpart) {
-        if (loss_sum) loss_sum[row] = a;
-        out[row] = a / cs;
-      }
-    }
-  }
-}
 
 // drop-in backward, second pass: the gradient of every unit
 template <bool VEC>
@@ -263,126 +63,6 @@ __global__ __launch_bounds__(kCeT) void ce_bwd_units_kernel(CeRows s, CeUnits g,
     if (t.w != -1.0f) d.w = ce_grad(x.w, t.w, cs, scale);
     ce_store4<VEC>(d_data + (size_t)row * g.k + e0, cnt, d);
   }
-}
-
-// fused backward, second pass: a workgroup per plane (r, kk) of d_logits, every plane written exactly once.
-// VST: 16-byte stores; VLD: 16-byte loads of the selected plane and its targets.
-template <bool VST, bool VLD>
-__global__ __launch_bounds__(kCeT) void mask_loss_bwd_kernel(const float* __restrict__ logits,
-                                                             const float* __restrict__ cls,
-                                                             const float* __restrict__ target,
-                                                             float* __restrict__ d_logits,
-                                                             const float* __restrict__ count_sum, unsigned planes,
-                                                             unsigned K, unsigned P, float scale) {
-  const float cs = *count_sum;
-  unsigned pl = blockIdx.x;
-  float cv = pl < planes ? cls[pl / K] : 0.f;
-  while (pl < planes) {
-    // the next plane's class is asked for before this plane's stores are issued
-    const unsigned next = pl + gridDim.x;
-    const float cn = next < planes ? cls[next / K] : 0.f;
-    const unsigned r = pl / K;
-    const bool sel = mask_class(cv, K) == (int)(pl - r * K);
-    const size_t base = (size_t)pl * P;
-    const float* tp = target + (size_t)r * P;
-    if (VST) {
-      for (unsigned i = 4u * threadIdx.x; i < P; i += 4u * kCeT) {
-        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (sel) {
-          const float4 t = ce_load4<VLD>(tp + i, 4);
-          const float4 x = ce_load4<VLD>(logits + base + i, 4);
-          if (t.x != -1.0f) d.x = ce_grad(x.x, t.x, cs, scale);
-          if (t.y != -1.0f) d.y = ce_grad(x.y, t.y, cs, scale);
-          if (t.z != -1.0f) d.z = ce_grad(x.z, t.z, cs, scale);
-          if (t.w != -1.0f) d.w = ce_grad(x.w, t.w, cs, scale);
-        }
-        *reinterpret_cast<float4*>(d_logits + base + i) = d;
-      }
-    } else {
-      for (unsigned i = threadIdx.x; i < P; i += kCeT) {
-        float d = 0.f;
-        if (sel) {
-          const float t = tp[i];
-          if (t != -1.0f) d = ce_grad(logits[base + i], t, cs, scale);
-        }
-        d_logits[base + i] = d;
-      }
-    }
-    cv = cn;
-    pl = next;
-  }
-}
-
-static bool ce_aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
-}
-
-static int ce_grid(long items, int per_block) {
-  const long b = (items + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : b > kCeMaxBlocks ? kCeMaxBlocks : b);
-}
-
-static long ce_units_per_row(long k) { return (k + kCeUnit - 1) / kCeUnit; }
-
-// workspace: [256-byte alignment slack][units floats][units ints][one float: the fused backward's count_sum]
-static size_t ce_workspace_bytes(long n, long k) {
-  if (n <= 0 || k <= 0 || n > kCeMaxElems / k) return 512;
-  const size_t units = (size_t)n * (size_t)ce_units_per_row(k);
-  return 256 + ((units * 8 + 255) & ~(size_t)255) + 256;
-}
-
-struct CeWorkspace {
-  float* lpart;
-  int* cpart;
-  float* count_sum;
-};
-
-static int ce_carve(void* workspace, size_t workspace_bytes, long n, long k, const char* who, CeWorkspace* w) {
-  const size_t need = ce_workspace_bytes(n, k);
-  if (!workspace || workspace_bytes < need)
-    return fail(SD_ERR_WORKSPACE, "%s workspace too small: %zu < %zu bytes", who, workspace_bytes, need);
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  const size_t units = (size_t)n * (size_t)ce_units_per_row(k);
-  w->lpart = reinterpret_cast<float*>(base);
-  w->cpart = reinterpret_cast<int*>(base + units * 4);
-  w->count_sum = reinterpret_cast<float*>(base + ((units * 8 + 255) & ~(size_t)255));
-  return SD_OK;
-}
-
-static CeUnits ce_units(long n, long k) {
-  CeUnits g;
-  g.per_row = (unsigned)ce_units_per_row(k);
-  g.units = (unsigned)(n * ce_units_per_row(k));
-  g.k = (unsigned)k;
-  return g;
-}
-
-template <class Src>
-static void launch_fwd_units(const Src& s, const CeUnits& g, bool vec, float* loss, float* count,
-                             const CeWorkspace& w, hipStream_t st) {
-  const int grid = ce_grid(g.units, kCeWaves);
-  if (vec)
-    hipLaunchKernelGGL((ce_fwd_units_kernel<Src, true>), dim3(grid), dim3(kCeT), 0, st, s, g, loss, count, w.lpart,
-                       w.cpart);
-  else
-    hipLaunchKernelGGL((ce_fwd_units_kernel<Src, false>), dim3(grid), dim3(kCeT), 0, st, s, g, loss, count, w.lpart,
-                       w.cpart);
-}
-
-template <class Src>
-static void launch_count_units(const Src& s, const CeUnits& g, bool vec, float* count, const CeWorkspace& w,
-                               hipStream_t st) {
-  const int grid = ce_grid(g.units, kCeWaves);
-  if (vec)
-    hipLaunchKernelGGL((ce_count_units_kernel<Src, true>), dim3(grid), dim3(kCeT), 0, st, s, g, count, w.cpart);
-  else
-    hipLaunchKernelGGL((ce_count_units_kernel<Src, false>), dim3(grid), dim3(kCeT), 0, st, s, g, count, w.cpart);
-}
-
-static void launch_rows(const float* lpart, const CeWorkspace& w, const CeUnits& g, long n, float* out,
-                        float* loss_sum, float* count_sum, hipStream_t st) {
-  hipLaunchKernelGGL(ce_rows_kernel, dim3(ce_grid(n, kCeWaves)), dim3(kCeT), 0, st, lpart, w.cpart, (unsigned)n,
-                     g.per_row, out, loss_sum, count_sum);
 }
 
 }  // namespace sd
@@ -441,18 +121,7 @@ extern "C" int sd_sigmoid_ce_bwd(const float* data, const float* label, float* d
 }
 
 // ------------------------------------------------------------------------------------ fused mask loss --
-static int mask_check_dims(int R, int K, long P) {
-  SD_REQUIRE(R >= 0 && K >= 0 && P >= 0, "negative dimension (R=%d K=%d P=%ld)", R, K, P);
-  const long planes = (long)R * K;
-  if (P > 0 && planes > kCeMaxElems / P)
-    return fail(SD_ERR_UNSUPPORTED, "R*K*P = %d x %d x %ld elements exceed the limit %ld", R, K, P, kCeMaxElems);
-  return SD_OK;
-}
-
-extern "C" size_t sd_mask_loss_workspace_bytes(int R, int K, long P) {
-  if (R <= 0 || K <= 0 || P <= 0) return 512;
-  return ce_workspace_bytes(1, (long)R * P > kCeMaxElems ? 0 : (long)R * P);
-}
+extern "C" size_t sd_mask_loss_workspace_bytes(int R, int K, long P) { return mask_workspace_bytes(R, K, P); }
 
 extern "C" int sd_mask_loss_fwd(const float* logits, const float* cls, const float* target, float* out,
                                 float* count_sum, int R, int K, long P, void* workspace, size_t workspace_bytes,
@@ -478,25 +147,9 @@ extern "C" int sd_mask_loss_bwd(const float* logits, const float* cls, const flo
   if (int e = mask_check_dims(R, K, P)) return e;
   if (R == 0 || K == 0 || P == 0) return SD_OK;
   SD_REQUIRE(logits && cls && target && d_logits, "null pointer");
-  const long k = (long)R * P;
   CeWorkspace w;
-  if (int e = ce_carve(workspace, workspace_bytes, 1, k, "mask_loss_bwd", &w)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  const CeUnits g = ce_units(1, k);
-  const CeMask s{logits, cls, target, (unsigned)K, (unsigned)P};
-  const bool vld = P % 4 == 0 && ce_aligned16(logits, target);
-  launch_count_units(s, g, vld, nullptr, w, st);
-  launch_rows(nullptr, w, g, 1, nullptr, nullptr, w.count_sum, st);
-  const unsigned planes = (unsigned)((long)R * K);
-  const int grid = ce_grid(planes, 1);
-  const bool vst = P % 4 == 0 && ce_aligned16(d_logits);
-#define SD_MASK_BWD(VST, VLD)                                                                                  \
-  hipLaunchKernelGGL((mask_loss_bwd_kernel<VST, VLD>), dim3(grid), dim3(kCeT), 0, st, logits, cls, target,     \
-                     d_logits, (const float*)w.count_sum, planes, (unsigned)K, (unsigned)P, grad_scale)
-  if (vst && vld) SD_MASK_BWD(true, true);
-  else if (vst) SD_MASK_BWD(true, false);
-  else SD_MASK_BWD(false, false);
-#undef SD_MASK_BWD
+  if (int e = ce_carve(workspace, workspace_bytes, 1, (long)R * P, "mask_loss_bwd", &w)) return e;
+  launch_mask_bwd(logits, cls, target, nullptr, d_logits, R, K, P, grad_scale, w, (hipStream_t)stream);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

@@ -2063,6 +2063,152 @@ def _build_ops(mx):
     ops["_contrib_SigmoidCrossEntropy"] = (SigmoidCrossEntropyProp, ("contrib", "SigmoidCrossEntropy"))
     ops["MaskLoss"] = (MaskLossProp, None)
 
+    # ---- the Mask Scoring R-CNN training head (registered only by install(..., msrcnn=True)):
+    #      MsrcnnMaskLoss: logits, cls, target -> output (the mask loss), mask_pred_prob (the gathered sigmoid)
+    #      MaskIoULoss:    iou_pred, prob, target, ratio, cls -> output, iou_target, weight, weight_sum (1 visible) ----
+    class MsrcnnMaskLoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def _ws(self, like, dims):
+            wsb = int(lib().cdll.sd_msrcnn_mask_loss_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2])))
+            return _scratch(like, wsb), wsb
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            logits, cls, target = in_data[:3]
+            _wait(logits, cls, target)
+            R, K, P = dims = MaskLoss._dims(logits)
+            ws, wsb = self._ws(logits, dims)
+            count_sum = _scratch(logits, 4)      # the reference's hidden output; nothing downstream reads it
+            _call("sd_msrcnn_mask_loss_fwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(out_data[0]),
+                  _ptr(count_sum), _ptr(out_data[1]), R, K, ctypes.c_long(P), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # the loss output's head gradient is never read (a loss operator); the one that reached mask_pred_prob
+            # joins the selected plane in the same pass
+            _require_write(req[:1], ["MsrcnnMaskLoss logits gradient"])
+            logits, cls, target = in_data[:3]
+            d_prob = out_grad[1] if len(out_grad) > 1 else None
+            _wait(logits, cls, target, d_prob)
+            if _req(req[0]) != REQ["null"]:
+                R, K, P = dims = MaskLoss._dims(logits)
+                ws, wsb = self._ws(logits, dims)
+                _call("sd_msrcnn_mask_loss_bwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(d_prob),
+                      _ptr(in_grad[0]), R, K, ctypes.c_long(P), float(self.g["grad_scale"]), _ptr(ws),
+                      ctypes.c_size_t(wsb), None)
+            for i in (1, 2):
+                if len(req) > i:
+                    self.assign(in_grad[i], req[i], 0)
+            _sync()
+
+    class MsrcnnMaskLossProp(CustomOpProp):
+        def __init__(self, grad_scale="1.0"):
+            super().__init__(need_top_grad=True)
+            self.g = dict(grad_scale=float(grad_scale))
+
+        def list_arguments(self):
+            return ["logits", "cls", "target"]
+
+        def list_outputs(self):
+            return ["output", "mask_pred_prob"]
+
+        def infer_shape(self, in_shape):
+            # as MaskLoss; mask_pred_prob is the gathered plane of every RoI: (R, h, w)
+            d = tuple(in_shape[0])
+            if len(d) < 2:
+                raise ValueError("MsrcnnMaskLoss: logits should be (roi, class, ...)")
+            cls = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else (d[0],)
+            target = tuple(in_shape[2]) if len(in_shape) > 2 and in_shape[2] else (d[0],) + d[2:]
+            if _numel(cls) != d[0] or _numel(target) != d[0] * _numel(d[2:]):
+                raise ValueError("MsrcnnMaskLoss: cls %s / target %s do not match logits %s" % (cls, target, d))
+            return [d, cls, target], [(1,), (d[0],) + d[2:]]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return MsrcnnMaskLoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [out_grad[1], in_data[0], in_data[1], in_data[2]]
+
+    class MaskIoULoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        @staticmethod
+        def _dims(iou_pred, prob):
+            R, K = int(iou_pred.shape[0]), int(iou_pred.shape[1])
+            return R, K, (_numel(prob.shape) // R if R else 0)
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            iou_pred, prob, target, ratio, cls = in_data[:5]
+            _wait(iou_pred, prob, target, ratio, cls)
+            R, K, P = self._dims(iou_pred, prob)
+            wsb = int(lib().cdll.sd_maskiou_loss_workspace_bytes(R, K, ctypes.c_long(P)))
+            ws = _scratch(iou_pred, wsb)
+            _call("sd_maskiou_loss_fwd", _ptr(iou_pred), _ptr(prob), _ptr(target), _ptr(ratio), _ptr(cls),
+                  _ptr(out_data[1]), _ptr(out_data[2]), _ptr(out_data[0]), _ptr(out_data[3]), R, K, ctypes.c_long(P),
+                  _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # MakeLoss: the head gradient is not read.  prob, target, ratio and cls get zeros: the reference
+            # BlockGrads the CustomOp's outputs and its backward assigns 0
+            _require_write(req[:1], ["MaskIoULoss iou_pred gradient"])
+            iou_pred, cls = in_data[0], in_data[4]
+            _wait(iou_pred, cls, out_data[1], out_data[2], out_data[3])
+            if _req(req[0]) != REQ["null"]:
+                R, K = int(iou_pred.shape[0]), int(iou_pred.shape[1])
+                _call("sd_maskiou_loss_bwd", _ptr(iou_pred), _ptr(cls), _ptr(out_data[1]), _ptr(out_data[2]),
+                      _ptr(out_data[3]), _ptr(in_grad[0]), R, K, float(self.g["grad_scale"]), None)
+            for i in (1, 2, 3, 4):
+                if len(req) > i:
+                    self.assign(in_grad[i], req[i], 0)
+            _sync()
+
+    class MaskIoULossProp(CustomOpProp):
+        def __init__(self, grad_scale="1.0"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(grad_scale=float(grad_scale))
+
+        def list_arguments(self):
+            return ["iou_pred", "prob", "target", "ratio", "cls"]
+
+        def list_outputs(self):
+            return ["output", "iou_target", "weight", "weight_sum"]
+
+        num_visible_outputs = 1
+
+        def infer_shape(self, in_shape):
+            # iou_pred (R, K); prob / target R * h * w floats; ratio and cls R floats in any shape (the builder's
+            # mask_ratio and mask_label are (batch, fg))
+            d = tuple(in_shape[0])
+            if len(d) != 2:
+                raise ValueError("MaskIoULoss: iou_pred should be (roi, class)")
+            R = d[0]
+            prob = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else None
+            if prob is None or len(prob) < 2 or prob[0] != R:
+                raise ValueError("MaskIoULoss: prob %s should be (roi, ...) with %d rows" % (prob, R))
+            target = tuple(in_shape[2]) if len(in_shape) > 2 and in_shape[2] else prob
+            ratio = tuple(in_shape[3]) if len(in_shape) > 3 and in_shape[3] else (R,)
+            cls = tuple(in_shape[4]) if len(in_shape) > 4 and in_shape[4] else (R,)
+            if _numel(target) != _numel(prob) or _numel(ratio) != R or _numel(cls) != R:
+                raise ValueError("MaskIoULoss: target %s / ratio %s / cls %s do not match prob %s"
+                                 % (target, ratio, cls, prob))
+            return [d, prob, target, ratio, cls], [(1,), (R,), (R,), (1,)]
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return MaskIoULoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [in_data[0], in_data[4], out_data[1], out_data[2], out_data[3]]
+
+    ops["MsrcnnMaskLoss"] = (MsrcnnMaskLossProp, None)
+    ops["MaskIoULoss"] = (MaskIoULossProp, None)
+
     # ---- the FCOS training head (registered only by install(..., fcos=True)):
     #      fcos_target: gt_bbox, im_info -> centerness, offset, cls_id (int32), state (int32[4])
     #      fcos_loss:   3 * L level tensors + the four targets -> centerness_loss, cls_loss, offset_loss ----
@@ -2473,7 +2619,8 @@ def _build_ops(mx):
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False, reppoints=False):
+             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False, reppoints=False,
+             msrcnn=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -2494,7 +2641,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     tsd_pool: also _contrib_DeformablePSROIPooling and sd_fpn_deform_roi_pool (opt-in: the first replaces a native
     operator, patch_tsd_pool puts the second in place of the two get_roi_feature subgraphs of the TSD graphs);
     reppoints: also sd_reppoints_target and sd_reppoints_box_loss (opt-in: patch_reppoints_loss puts them in place of
-    both assigners and both box-loss subgraphs of the RepPoints train graphs)."""
+    both assigners and both box-loss subgraphs of the RepPoints train graphs);
+    msrcnn: also sd_MsrcnnMaskLoss and sd_MaskIoULoss (opt-in: patch_msrcnn_loss puts them in place of the mask-loss
+    and MaskIoU-loss subgraphs, the Python CustomOp maskiou_compute included, of the Mask Scoring R-CNN train graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -2529,6 +2678,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     if not reppoints:
         table.pop("reppoints_target")
         table.pop("reppoints_box_loss")
+    if not msrcnn:
+        table.pop("MsrcnnMaskLoss")
+        table.pop("MaskIoULoss")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2564,7 +2716,7 @@ def _namespaces(mx, ns):
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
             group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False,
-            reppoints=False):
+            reppoints=False, msrcnn=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2606,8 +2758,8 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     of models/maskrcnn/builder.py:307-312 and models/msrcnn/builder.py:418-423), registers the fused `sd_MaskLoss`
     and rebinds `models.maskrcnn.builder.MaskFasterRcnnHead.get_loss` (patch_mask_loss) so that Mask R-CNN train
     graphs hold ONE node in place of split / stack / gather_nd / concat / reshape / SigmoidCrossEntropy; opt-in
-    because it changes which operators those graphs hold.  models/msrcnn/builder.py is not patched (its get_loss
-    also returns the gathered logits): it gets the aliased operator only.
+    because it changes which operators those graphs hold.  models/msrcnn/builder.py is not patched by this flag (its
+    get_loss also returns the gathered sigmoid): it gets the aliased operator only; `msrcnn=True` is its flag.
 
     `quant_int8=True` also replaces `_contrib_Quantization_int8` (mx.sym.contrib.Quantization_int8: the node
     utils/graph_optimize.py:162,169,182 attaches in front of every quantised operator's data and weight; config/int8/);
@@ -2637,10 +2789,20 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     `models.RepPoints.builder.RepPointsHead.get_loss` (patch_reppoints_loss) so that a RepPoints train graph holds
     these two nodes in place of _gen_points, _offset_to_boxes, both _point_target subgraphs, _offset_to_pts,
     _points2bbox, smooth_l1, BBoxNorm and MakeLoss of both box branches; the focal loss on the concatenated class
-    logits stays the node it was.  A default install() afterwards puts the reference's method back."""
+    logits stays the node it was.  A default install() afterwards puts the reference's method back.
+
+    `msrcnn=True` also registers `sd_MsrcnnMaskLoss` and `sd_MaskIoULoss` and rebinds
+    `models.msrcnn.builder.MaskFasterRcnnHead.get_loss` and `MaskIoUConvHead.get_loss` (patch_msrcnn_loss) so that a
+    Mask Scoring R-CNN train graph holds these two nodes in place of both split / stack / gather_nd / concat chains,
+    Activation(sigmoid), reshape / SigmoidCrossEntropy, the Python CustomOp `maskiou_compute` (a host round trip in
+    the middle of every step) and the loss arithmetic behind it; the conv / FC tower `_get_output` stays the
+    reference's.  Opt-in because it changes which operators those graphs hold, and independent of `mask_loss`, which
+    keeps its meaning (the Mask R-CNN builder and the aliased operator).  Where the builder module is not importable
+    nothing is rebound and `_state["fallbacks"]` says so; a default install() afterwards puts the reference's
+    methods back.  The test-time path (get_maskiou_prediction) is not touched."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
                      group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
-                     fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints)
+                     fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints, msrcnn=msrcnn)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -2773,6 +2935,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_REPPOINTS_BUILDER) is not None:
             unpatch_reppoints_loss(sys.modules[_REPPOINTS_BUILDER])
         _state["reppoints_patched"] = False
+    if msrcnn:
+        _state["msrcnn_patched"] = patch_msrcnn_loss(mx=mx)
+        if not _state["msrcnn_patched"]:
+            _state["fallbacks"].append(("MaskIoULoss", None, "%s is not importable" % _MSRCNN_BUILDER))
+    else:
+        import sys
+        if sys.modules.get(_MSRCNN_BUILDER) is not None:
+            unpatch_msrcnn_loss(sys.modules[_MSRCNN_BUILDER])
+        _state["msrcnn_patched"] = False
     return props
 
 
@@ -2847,8 +3018,9 @@ def patch_mask_loss(builder_module=None, mx=None):
     install(mask_loss=True) calls this when the builder module is importable; returns True when the class was
     patched.  The original method is kept as `_sd_reference_get_loss` (a second install() keeps the first
     original); a default install() afterwards puts it back (unpatch_mask_loss).
-    models/msrcnn/builder.py is NOT patched: its get_loss also returns the gathered logits (the MaskIoU head
-    reads them), so it keeps its subgraph and gets the aliased SigmoidCrossEntropy only."""
+    models/msrcnn/builder.py is NOT patched by this flag: its get_loss also returns the gathered sigmoid (the MaskIoU
+    head reads it), so it keeps its subgraph and gets the aliased SigmoidCrossEntropy only; install(msrcnn=True)
+    (patch_msrcnn_loss) is what moves that model's head onto the device."""
     mx = mx or _state["mx"]
     if builder_module is None:
         import importlib
@@ -2889,6 +3061,88 @@ def unpatch_mask_loss(builder_module):
         return False
     cls.get_loss = original
     return True
+
+
+_MSRCNN_BUILDER = "models.msrcnn.builder"
+
+
+def patch_msrcnn_loss(builder_module=None, mx=None):
+    """Route Mask Scoring R-CNN's training head to the device ops WITHOUT editing the reference: rebinds, in
+    models/msrcnn/builder.py,
+      MaskFasterRcnnHead.get_loss (:383-424) -- split / stack / gather_nd / concat, Activation(sigmoid), two reshapes
+        and SigmoidCrossEntropy -- to a method that calls `self.get_output(conv_feat)` and emits ONE
+        mx.sym.Custom(op_type='sd_MsrcnnMaskLoss') over (mask_fcn_logit, mask_ind, mask_target) with
+        grad_scale = 128.0 if pMask.fp16 else 1.0, and returns `((mask_loss,), mask_pred_prob)`;
+      MaskIoUConvHead.get_loss (:143-168) -- the same gather chain on the IoU predictions, the Python CustomOp
+        maskiou_compute, two BlockGrads and the loss arithmetic under MakeLoss -- to a method that calls the
+        reference's own `self._get_output(mask_pred_logits, conv_feat)` and emits ONE
+        mx.sym.Custom(op_type='sd_MaskIoULoss') over (iou_pred, mask_pred_logits, mask_target, mask_ratio, mask_inds)
+        with grad_scale = 1.0, and returns `(maskiou_head_loss,)`.
+    Signatures and return shapes are the reference's.  install(msrcnn=True) calls this when the builder module is
+    importable; returns True when both classes were patched.  The original methods are kept as
+    `_sd_reference_get_loss` (a second install() keeps the first originals); a default install() afterwards puts
+    them back (unpatch_msrcnn_loss)."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_MSRCNN_BUILDER)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _MSRCNN_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_msrcnn_loss(module, mx)
+    mask_cls = getattr(builder_module, "MaskFasterRcnnHead", None)
+    iou_cls = getattr(builder_module, "MaskIoUConvHead", None)
+    if mask_cls is None or iou_cls is None:
+        return False
+    mask_original = mask_cls.__dict__.get("_sd_reference_get_loss") or mask_cls.get_loss
+    iou_original = iou_cls.__dict__.get("_sd_reference_get_loss") or iou_cls.get_loss
+
+    def registered(name):
+        if name in (_state.get("table") or {}):
+            return True
+        _state.setdefault("fallbacks", []).append((name, None, "%s%s is not registered" % (_PREFIX, name)))
+        return False
+
+    def mask_get_loss(self, conv_feat, mask_target, mask_ind):
+        if not registered("MsrcnnMaskLoss"):
+            return mask_original(self, conv_feat, mask_target, mask_ind)
+        mask_fcn_logit = self.get_output(conv_feat)
+        scale_loss_shift = 128.0 if self.pMask.fp16 else 1.0
+        sym = mx.sym.Custom(logits=mask_fcn_logit, cls=mask_ind, target=mask_target,
+                            op_type=_PREFIX + "MsrcnnMaskLoss", grad_scale=_param_str(1.0 * scale_loss_shift),
+                            name="mask_loss")
+        return (sym[0],), sym[1]
+
+    def iou_get_loss(self, conv_feat, mask_pred_logits, mask_target, mask_inds, mask_ratio):
+        if not registered("MaskIoULoss"):
+            return iou_original(self, conv_feat, mask_pred_logits, mask_target, mask_inds, mask_ratio)
+        iou_pred_logits = self._get_output(mask_pred_logits, conv_feat)
+        sym = mx.sym.Custom(iou_pred=iou_pred_logits, prob=mask_pred_logits, target=mask_target, ratio=mask_ratio,
+                            cls=mask_inds, op_type=_PREFIX + "MaskIoULoss", grad_scale=_param_str(1.0),
+                            name="iou_head_loss")
+        return (sym[0],)
+
+    mask_get_loss.__name__ = iou_get_loss.__name__ = "get_loss"
+    mask_cls._sd_reference_get_loss = mask_original
+    mask_cls.get_loss = mask_get_loss
+    iou_cls._sd_reference_get_loss = iou_original
+    iou_cls.get_loss = iou_get_loss
+    return True
+
+
+def unpatch_msrcnn_loss(builder_module):
+    """Put the reference's two get_loss methods back (and forget them: the classes are as they were)."""
+    done = False
+    for name in ("MaskFasterRcnnHead", "MaskIoUConvHead"):
+        cls = getattr(builder_module, name, None)
+        original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
+        if original is not None:
+            cls.get_loss = original
+            del cls._sd_reference_get_loss
+            done = True
+    return done
 
 
 _FCOS_BUILDER = "models.FCOS.builder"

@@ -1239,6 +1239,113 @@ def mask_loss_backward(logits, cls, target, grad_scale=1.0, *, d_logits=None, wo
 
 
 # --------------------------------------------------------------------------------------------------
+# The Mask Scoring R-CNN training head  (models/msrcnn/builder.py:143-168, :383-424; models/msrcnn/maskiou_compute.py)
+# --------------------------------------------------------------------------------------------------
+def msrcnn_mask_loss_workspace_bytes(R, K, P):
+    return int(lib().cdll.sd_msrcnn_mask_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
+
+
+def maskiou_loss_workspace_bytes(R, K, P):
+    return int(lib().cdll.sd_maskiou_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
+
+
+def msrcnn_mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, prob=None, workspace=None):
+    """The mask loss of Mask Scoring R-CNN's MaskFasterRcnnHead.get_loss (models/msrcnn/builder.py:383-424) in one
+    op: mask_loss_forward's (out, count_sum), bit for bit, and prob (R, h, w) = sigmoid of plane int(cls[r]) of every
+    RoI -- the builder's mask_pred_prob, written for every pixel of a valid RoI (target -1 included) and +0.0 for a
+    RoI whose cls is NaN, negative or >= K.  Returns (out, count_sum, prob)."""
+    R, K, P = _mask_dims(logits, cls, target)
+    dev = logits.device
+    out = _ce_out(out, "out", 1, dev, (1,))
+    count_sum = _ce_out(count_sum, "count_sum", 1, dev, (1,))
+    prob = _ce_out(prob, "prob", R * P, dev, (R,) + tuple(logits.shape[2:]))
+    if R * K * P == 0:    # an empty sum over an empty count (the entry point writes nothing)
+        out.zero_()
+        count_sum.fill_(1e-5)
+        prob.zero_()
+        return out, count_sum, prob
+    ws = _ce_ws(dev, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
+    lib().call("sd_msrcnn_mask_loss_fwd", _p(logits), _p(cls), _p(target), _p(out), _p(count_sum), _p(prob), R, K,
+               ctypes.c_long(P), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return out, count_sum, prob
+
+
+def msrcnn_mask_loss_backward(logits, cls, target, d_prob=None, grad_scale=1.0, *, d_logits=None, workspace=None):
+    """Backward of msrcnn_mask_loss_forward: ALL of d_logits is written once -- +0.0 in the planes that are not
+    selected, mask_loss_backward's gradient plus d_prob * p * (1 - p) in plane int(cls[r]).  d_prob (R, h, w) is the
+    gradient that reached prob (None: none did; the result is then mask_loss_backward's, bit for bit)."""
+    R, K, P = _mask_dims(logits, cls, target)
+    if d_prob is not None:
+        _chk(d_prob, "d_prob")
+        if d_prob.numel() != R * P:
+            raise ValueError("d_prob needs %d floats, got %d" % (R * P, d_prob.numel()))
+    d_logits = _ce_out(d_logits, "d_logits", R * K * P, logits.device, logits.shape)
+    ws = _ce_ws(logits.device, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
+    lib().call("sd_msrcnn_mask_loss_bwd", _p(logits), _p(cls), _p(target), _p(d_prob), _p(d_logits), R, K,
+               ctypes.c_long(P), float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return d_logits
+
+
+def _maskiou_dims(iou_pred, cls, prob=None, target=None, ratio=None):
+    _chk(iou_pred, "iou_pred")
+    _chk(cls, "cls")
+    if iou_pred.dim() != 2:
+        raise ValueError("iou_pred should be (roi, class), got shape %s" % (tuple(iou_pred.shape),))
+    R, K = int(iou_pred.shape[0]), int(iou_pred.shape[1])
+    if cls.numel() != R:
+        raise ValueError("cls must hold %d floats, got %d" % (R, cls.numel()))
+    if prob is None:
+        return R, K, 0
+    _chk(prob, "prob")
+    _chk(target, "target")
+    _chk(ratio, "ratio")
+    P = prob.numel() // R if R else 0
+    if prob.numel() != R * P or target.numel() != R * P or ratio.numel() != R:
+        raise ValueError("prob and target must hold (%d, P) floats and ratio %d, got %d, %d and %d"
+                         % (R, R, prob.numel(), target.numel(), ratio.numel()))
+    return R, K, P
+
+
+def maskiou_loss_forward(iou_pred, prob, target, ratio, cls, *, iou_target=None, weight=None, loss=None,
+                         weight_sum=None, workspace=None):
+    """MaskIoUConvHead.get_loss behind its conv / FC tower (models/msrcnn/builder.py:146-167) in one op: iou_pred
+    (R, K), prob and target (R, h, w), ratio (R,), cls (R,) float -> (iou_target (R,), weight (R,), loss (1,),
+    weight_sum (1,)).  iou_target and weight are maskiou_compute.py's outputs computed on the device (no host round
+    trip); loss = 0.5 * sum((iou_target - iou_pred[r, int(cls[r])])^2 * weight) / max(sum weight, 1) over the rows
+    whose cls names a column."""
+    R, K, P = _maskiou_dims(iou_pred, cls, prob, target, ratio)
+    dev = iou_pred.device
+    iou_target = _ce_out(iou_target, "iou_target", R, dev, (R,))
+    weight = _ce_out(weight, "weight", R, dev, (R,))
+    loss = _ce_out(loss, "loss", 1, dev, (1,))
+    weight_sum = _ce_out(weight_sum, "weight_sum", 1, dev, (1,))
+    if R * K * P == 0:    # nothing to look at: empty sums (the entry point writes nothing)
+        for t in (iou_target, weight, loss, weight_sum):
+            t.zero_()
+        return iou_target, weight, loss, weight_sum
+    ws = _ce_ws(dev, maskiou_loss_workspace_bytes(R, K, P), workspace)
+    lib().call("sd_maskiou_loss_fwd", _p(iou_pred), _p(prob), _p(target), _p(ratio), _p(cls), _p(iou_target),
+               _p(weight), _p(loss), _p(weight_sum), R, K, ctypes.c_long(P), _p(ws), ctypes.c_size_t(ws.numel()),
+               _stream())
+    return iou_target, weight, loss, weight_sum
+
+
+def maskiou_loss_backward(iou_pred, cls, iou_target, weight, weight_sum, grad_scale=1.0, *, d_iou_pred=None):
+    """Backward of maskiou_loss_forward: d_iou_pred (R, K), written once -- -(iou_target - p) * weight /
+    max(weight_sum, 1) * grad_scale in column int(cls[r]), +0.0 everywhere else.  Nothing flows to prob, target or
+    ratio."""
+    R, K, _ = _maskiou_dims(iou_pred, cls)
+    for t, name, n in ((iou_target, "iou_target", R), (weight, "weight", R), (weight_sum, "weight_sum", 1)):
+        _chk(t, name)
+        if t.numel() != n:
+            raise ValueError("%s needs %d floats, got %d" % (name, n, t.numel()))
+    d_iou_pred = _ce_out(d_iou_pred, "d_iou_pred", R * K, iou_pred.device, iou_pred.shape)
+    lib().call("sd_maskiou_loss_bwd", _p(iou_pred), _p(cls), _p(iou_target), _p(weight), _p(weight_sum),
+               _p(d_iou_pred), R, K, float(grad_scale), _stream())
+    return d_iou_pred
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_Quantization_int8  (operator_cxx/contrib/quantization_int8{-inl.h,.cu}; utils/graph_optimize.py)
 # --------------------------------------------------------------------------------------------------
 QUANT_GRAD_MODES = ("ste", "clip")

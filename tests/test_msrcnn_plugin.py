@@ -1,0 +1,236 @@
+"""`install(mx, msrcnn=True)`: `MaskFasterRcnnHead.get_loss` and `MaskIoUConvHead.get_loss` of
+models/msrcnn/builder.py emit ONE `sd_MsrcnnMaskLoss` and ONE `sd_MaskIoULoss` node in place of both split / stack /
+gather_nd / concat chains, Activation(sigmoid), reshape / SigmoidCrossEntropy, the Python CustomOp `maskiou_compute`
+and the loss arithmetic; the conv / FC tower stays the reference's.  Without the flag the graph holds what it held.
+CPU only on tests/mx_stub.py and tests/ref_stubs.py (the builder tests are skipped where /root/reference is absent,
+like tests/test_mask_loss_plugin.py); the GPU round trip through the adapter is the last test."""
+import collections
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+from . import mx_stub
+from . import ref_stubs as RS
+
+REF = "/root/reference"
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="/root/reference not present")
+CONFIGS = ("config.ms_r50v1_fpn_1x", "config.resnet_v1b.ms_r50v1b_fpn_1x")
+# the operator types of the two subgraphs that the two device nodes stand for (and the nodes themselves)
+SUBGRAPHS = ("gather_nd", "stack", "split", "concat", "arange", "Activation", "reshape", "SigmoidCrossEntropy",
+             "maskiou_compute", "BlockGrad", "MakeLoss", "_minus", "_power", "_mul", "_div", "sum", "maximum", "_output",
+             "sd_MsrcnnMaskLoss", "sd_MaskIoULoss")
+
+
+def _fresh(**flags):
+    from simpledet_amd import mxnet_plugin
+    mx = mx_stub.make_stub()
+    mxnet_plugin._state.update(registered=False)
+    props = mxnet_plugin.install(mx, **flags)
+    return mx, props, mxnet_plugin
+
+
+@pytest.fixture()
+def plugin():
+    mx, props, mxnet_plugin = _fresh(msrcnn=True)
+    yield mx, props, mxnet_plugin
+    mxnet_plugin._state.update(registered=False)
+
+
+def test_the_flag_is_opt_in_and_independent_of_mask_loss():
+    for flags in ({}, dict(mask_loss=True), dict(retina=True, proposal=True, bbox_post=True, retina_loss=True,
+                                                  group_norm=True, mask_loss=True, quant_int8=True, fcos=True,
+                                                  fcos_decode=True, tsd_pool=True, reppoints=True)):
+        mx, props, plug = _fresh(**flags)
+        try:
+            assert "MsrcnnMaskLoss" not in props and "MaskIoULoss" not in props
+            assert "sd_MsrcnnMaskLoss" not in mx.registry and "sd_MaskIoULoss" not in mx.registry
+            assert plug._state["msrcnn_patched"] is False
+        finally:
+            plug._state.update(registered=False)
+    mx, props, plug = _fresh(msrcnn=True)
+    try:
+        assert "sd_MsrcnnMaskLoss" in mx.registry and "sd_MaskIoULoss" in mx.registry
+        assert "MaskLoss" not in props and "_contrib_SigmoidCrossEntropy" not in props      # mask_loss keeps its meaning
+    finally:
+        plug._state.update(registered=False)
+
+
+def test_an_unimportable_builder_lands_in_the_fallbacks(monkeypatch):
+    from simpledet_amd import mxnet_plugin
+    monkeypatch.setattr(mxnet_plugin, "_MSRCNN_BUILDER", "models.msrcnn.no_such_builder")
+    mx, props, plug = _fresh(msrcnn=True)
+    try:
+        assert "sd_MsrcnnMaskLoss" in mx.registry and "sd_MaskIoULoss" in mx.registry       # registered all the same
+        assert plug._state["msrcnn_patched"] is False and plug.patch_msrcnn_loss(mx=mx) is False
+        hits = [f for f in plug._state["fallbacks"] if f[0] == "MaskIoULoss"]
+        assert len(hits) == 1 and "models.msrcnn.no_such_builder is not importable" in hits[0][2]
+        # a module that imports but holds neither class: nothing is rebound either
+        import sys
+        import types
+        broken = types.ModuleType("sd_test_broken_builder")
+        monkeypatch.setitem(sys.modules, "sd_test_broken_builder", broken)
+        monkeypatch.setattr(plug, "_MSRCNN_BUILDER", "sd_test_broken_builder")
+        assert plug.patch_msrcnn_loss(mx=mx) is False
+    finally:
+        plug._state.update(registered=False)
+
+
+def test_props_describe_the_two_nodes(plugin):
+    mx, props, _ = plugin
+    M = props["MsrcnnMaskLoss"]
+    m = M(grad_scale="128.0")
+    assert m.g == {"grad_scale": 128.0} and m.need_top_grad_ is True          # d_prob arrives as a head gradient
+    assert M().g == {"grad_scale": 1.0}
+    assert m.list_arguments() == ["logits", "cls", "target"] and m.list_outputs() == ["output", "mask_pred_prob"]
+    assert m.infer_shape([(256, 81, 28, 28), (2, 128), (256, 28, 28)]) == (
+        [(256, 81, 28, 28), (2, 128), (256, 28, 28)], [(1,), (256, 28, 28)])
+    assert m.infer_shape([(256, 81, 28, 28), (), ()])[0] == [(256, 81, 28, 28), (256,), (256, 28, 28)]
+    with pytest.raises(ValueError):
+        m.infer_shape([(256, 81, 28, 28), (255,), (256, 28, 28)])
+    with pytest.raises(ValueError):
+        m.infer_shape([(256,), (256,), (256,)])
+    assert m.declare_backward_dependency(["g", "gp"], ["l", "c", "t"], ["o", "p"]) == ["gp", "l", "c", "t"]
+    I = props["MaskIoULoss"]
+    i = I()
+    assert i.g == {"grad_scale": 1.0} and i.need_top_grad_ is False and i.num_visible_outputs == 1
+    assert i.list_arguments() == ["iou_pred", "prob", "target", "ratio", "cls"]
+    assert i.list_outputs() == ["output", "iou_target", "weight", "weight_sum"]
+    shapes = [(256, 81), (256, 28, 28), (256, 28, 28), (2, 128), (2, 128)]
+    assert i.infer_shape(shapes) == (shapes, [(1,), (256,), (256,), (1,)])
+    assert i.infer_shape([(256, 81), (256, 28, 28), (), (), ()])[0] == [(256, 81), (256, 28, 28), (256, 28, 28), (256,),
+                                                                         (256,)]
+    for bad in ([(256, 81, 1), (256, 28, 28), (), (), ()], [(256, 81), (255, 28, 28), (), (), ()],
+                [(256, 81), (256, 28, 28), (256, 28, 27), (), ()], [(256, 81), (256, 28, 28), (), (255,), ()],
+                [(256, 81), (256, 28, 28), (), (), (2, 127)]):
+        with pytest.raises(ValueError):
+            i.infer_shape(bad)
+    assert i.declare_backward_dependency(["g"], ["p", "pr", "t", "r", "c"], ["o", "it", "w", "ws"]) == [
+        "p", "c", "it", "w", "ws"]
+
+
+def _train_symbol(cfg_name, R, **flags):
+    from simpledet_amd import mxnet_plugin as plug
+    cfg = importlib.import_module(cfg_name)
+    plug._state.update(registered=False)
+    plug.install(R.mx, **flags)
+    sym = None
+    for o in cfg.get_config(True):
+        s = getattr(o, "train_symbol", None)
+        if isinstance(s, RS.Symbol):
+            sym = s
+    assert sym is not None
+    return sym
+
+
+def _count(sym):
+    return collections.Counter(n.op_type for n in RS.walk(sym, {}).values())
+
+
+def _loss_names(sym):
+    """the names of the nodes behind the group's outputs, in order"""
+    return [RS.source(s).name for s in sym.inputs]
+
+
+@needs_ref
+@pytest.mark.parametrize("cfg_name", CONFIGS)
+def test_train_graph_holds_the_two_nodes_only_with_the_opt_in(cfg_name):
+    with RS.reference_modules() as R:
+        from simpledet_amd import mxnet_plugin as plug
+        builder = importlib.import_module("models.msrcnn.builder")
+        ref_mask, ref_iou = builder.MaskFasterRcnnHead.get_loss, builder.MaskIoUConvHead.get_loss
+        # a default install leaves the graph as the reference builds it
+        native_sym = _train_symbol(cfg_name, R)
+        assert builder.MaskFasterRcnnHead.get_loss is ref_mask and builder.MaskIoUConvHead.get_loss is ref_iou
+        assert not plug._state["msrcnn_patched"]
+        native = _count(native_sym)
+        assert native["gather_nd"] == 4 and native["SigmoidCrossEntropy"] == 1 and native["maskiou_compute"] == 1
+        assert native["sd_MsrcnnMaskLoss"] == 0 and native["sd_MaskIoULoss"] == 0
+        # mask_loss alone does not patch this builder
+        only_mask = _count(_train_symbol(cfg_name, R, mask_loss=True))
+        assert only_mask["gather_nd"] == 4 and only_mask["sd_MsrcnnMaskLoss"] == 0 and only_mask["sd_MaskLoss"] == 0
+        # opt-in: one node each, none of the subgraphs, the same loss outputs in the same order
+        fused_sym = _train_symbol(cfg_name, R, msrcnn=True)
+        assert plug._state["msrcnn_patched"] and not plug._state["fallbacks"]
+        assert builder.MaskFasterRcnnHead._sd_reference_get_loss is ref_mask
+        assert builder.MaskIoUConvHead._sd_reference_get_loss is ref_iou
+        fused = _count(fused_sym)
+        assert fused["sd_MsrcnnMaskLoss"] == 1 and fused["sd_MaskIoULoss"] == 1
+        assert all(fused[o] == native[o] - d for o, d in (("gather_nd", 4), ("stack", 4), ("arange", 4),
+                                                         ("SigmoidCrossEntropy", 1), ("BlockGrad", 2)))
+        assert fused["gather_nd"] == 0 and fused["SigmoidCrossEntropy"] == 0
+        assert fused["maskiou_compute"] == 0 and fused["split"] == native["split"] - 4
+        assert _loss_names(fused_sym) == _loss_names(native_sym)
+        assert _loss_names(fused_sym)[-2:] == ["mask_loss", "iou_head_loss"]
+        nodes = {n.op_type: n for n in RS.walk(fused_sym, {}).values() if n.op_type.startswith("sd_M")}
+        m, i = nodes["sd_MsrcnnMaskLoss"], nodes["sd_MaskIoULoss"]
+        assert m.nout == 2 and float(m.params["grad_scale"]) == 1.0 and set(m.params) == {"grad_scale"}
+        assert i.nout == 4 and float(i.params["grad_scale"]) == 1.0
+        assert RS.source(m.inputs[0]).name == "mask_fcn_logit"
+        # the MaskIoU node reads the tower's prediction and output 1 (mask_pred_prob) of the mask node
+        assert RS.source(i.inputs[0]).name == "iou_head_pred"
+        assert RS.source(i.inputs[1]) is m and i.inputs[1].index == 1
+        # everything else -- the tower's convolutions, FCs and pooling among it -- is the reference's, node for node
+        rest = lambda cnt: {k: v for k, v in cnt.items() if k not in SUBGRAPHS}
+        assert rest(fused) == rest(native)
+        assert fused["Activation"] == native["Activation"] - 1 and fused["MakeLoss"] == native["MakeLoss"] - 1
+        assert native["Convolution"] > 4 and native["FullyConnected"] >= 3
+        # a second install keeps the first originals; a default install puts the reference's methods back
+        plug.install(R.mx, msrcnn=True)
+        assert builder.MaskFasterRcnnHead._sd_reference_get_loss is ref_mask
+        plug._state.update(registered=False)
+        plug.install(R.mx)
+        assert builder.MaskFasterRcnnHead.get_loss is ref_mask and builder.MaskIoUConvHead.get_loss is ref_iou
+        assert "_sd_reference_get_loss" not in builder.MaskFasterRcnnHead.__dict__
+        assert "_sd_reference_get_loss" not in builder.MaskIoUConvHead.__dict__
+        assert _count(_train_symbol(cfg_name, R)) == native
+        plug._state.update(registered=False)
+
+
+@pytest.mark.gpu
+def test_adapter_round_trip_equals_the_ops_calls(plugin, ops):
+    import torch
+    from . import msrcnn_ref as mr
+    mx, props, _ = plugin
+    c = mr.make_case(5, 784, 0)
+    R, K, P = c["logits"].shape
+    cuda = lambda a, s=None: torch.from_numpy(a).cuda().view(s or a.shape)
+    nan = lambda s: mx_stub.wrap(torch.full(s, float("nan"), device="cuda"))
+    # the mask loss node
+    m = props["MsrcnnMaskLoss"](grad_scale="128.0")
+    shapes = [(R, K, 28, 28), (1, R), (R, 28, 28)]
+    ishape, oshape = m.infer_shape(shapes)[:2]
+    op = m.create_operator(None, ishape, None)
+    ins = [mx_stub.wrap(cuda(c[k], s)) for k, s in zip(("logits", "cls", "target"), shapes)]
+    outs = [nan(s) for s in oshape]
+    op.forward(True, ["write"] * 2, ins, outs, [])
+    want = ops.msrcnn_mask_loss_forward(ins[0].t, ins[1].t, ins[2].t)
+    assert torch.equal(outs[0].t.view(torch.int32), want[0].view(torch.int32))
+    assert torch.equal(outs[1].t.view(torch.int32), want[2].view(torch.int32)) and outs[1].t.shape == (R, 28, 28)
+    d_prob = mx_stub.wrap(cuda(c["d_prob"], (R, 28, 28)))
+    grads = [nan(s) for s in ishape]
+    op.backward(["write"] * 3, [nan((1,)), d_prob], ins, outs, grads, [])
+    d = ops.msrcnn_mask_loss_backward(ins[0].t, ins[1].t, ins[2].t, d_prob.t, 128.0)
+    assert torch.equal(grads[0].t.view(torch.int32), d.view(torch.int32))
+    assert not grads[1].t.any() and not grads[2].t.any()
+    with pytest.raises(RuntimeError, match="kWriteTo"):
+        op.backward(["add", "write", "write"], [nan((1,)), d_prob], ins, outs, grads, [])
+    # the MaskIoU node, fed by the mask node's prob
+    i = props["MaskIoULoss"]()
+    shapes = [(R, K), (R, 28, 28), (R, 28, 28), (1, R), (1, R)]
+    ishape, oshape = i.infer_shape(shapes)[:2]
+    op = i.create_operator(None, ishape, None)
+    ins = [mx_stub.wrap(cuda(c["iou_pred"])), outs[1], mx_stub.wrap(cuda(c["target"], (R, 28, 28))),
+           mx_stub.wrap(cuda(c["ratio"], (1, R))), mx_stub.wrap(cuda(c["cls"], (1, R)))]
+    outs = [nan(s) for s in oshape]
+    op.forward(True, ["write"] * 4, ins, outs, [])
+    it, w, loss, wsum = ops.maskiou_loss_forward(ins[0].t, ins[1].t, ins[2].t, ins[3].t, ins[4].t)
+    for g, e in zip(outs, (loss, it, w, wsum)):
+        assert torch.equal(g.t.view(torch.int32), e.view(torch.int32))
+    grads = [nan(s) for s in ishape]
+    op.backward(["write"] * 5, [], ins, outs, grads, [])
+    di = ops.maskiou_loss_backward(ins[0].t, ins[4].t, it, w, wsum, 1.0)
+    assert torch.equal(grads[0].t.view(torch.int32), di.view(torch.int32))
+    assert all(not g.t.any() for g in grads[1:])
+    assert np.array_equal(ins[0].t.cpu().numpy(), c["iou_pred"])
