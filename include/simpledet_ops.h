@@ -66,7 +66,8 @@ const char* sd_last_dispatch(void);
  * sd_quant_int8_* entry points were added at 12 as well: no existing signature, layout or size contract moved.
  * So were the sd_fcos_* entry points (FCOS targets and losses; sd_fcos_decode and sd_fcos_sigmoid, the test-time
  * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*, and
- * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head).
+ * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head), and sd_reppoints_decode (the
+ * RepPoints test-time decode).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1249,6 +1250,50 @@ int sd_reppoints_box_loss_bwd(const float* const* pts_init_ptrs_host, const floa
                               float* d_moment_transfer, int N, int num_points, int transform, float scale,
                               float grad_scale_init, float grad_scale_refine, int req, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * RepPoints test-time decode (config/RepPoints/), fp32: RepPointsHead.get_prediction
+ * (models/RepPoints/builder.py:486-576) in ONE call -- per level the transposes, the sigmoid (input_logits = 1), the
+ * max, the topk and the per-image take / scale / add / clip chains, then the padded column and the concat of the
+ * levels.  Additions only: the ABI version stays 12.
+ *   Inputs: two HOST tables of L device pointers (the convention of sd_fcos_decode; read during the call only) --
+ *     cls (N, C, H_l, W_l) and pts_out_refine (N, 2 * num_points, H_l, W_l), channels (y0, x0, y1, x1, ...) --
+ *     im_info (N, 3) [h, w, scale] and moment_transfer (2,) ON THE DEVICE (moment_transfer may be NULL unless
+ *     transform = 2), four HOST tables of L ints: H_l, W_l, stride_l and k_l, the rows kept of the level; k_l <= 0
+ *     keeps all H_l * W_l (MXNet's topk with k < 1).  The reference's rule k_l = pre_nms_top_n if stride <= 32 else
+ *     -1 (builder.py:499-502) belongs to the caller.  input_logits = 0: cls holds probabilities; 1: raw logits,
+ *     1.0f / (1.0f + expf(-x)) is applied to every element first, the expression sd_fcos_sigmoid computes (equal
+ *     bits); the sigmoid is never taken of a maximum logit.
+ *   Outputs, K_l = k_l > 0 ? k_l : H_l * W_l, R = sum K_l, every element written by every call:
+ *     cls_score (N, R, C + 1) and bbox_xyxy (N, R, 4).
+ *   Per level l and image i, p = y * W_l + x, s = stride_l (the reference is the spec):
+ *     score[p, c] = cls[i, c, y, x] or its sigmoid; m[p] = max over c                          builder.py:518-519
+ *     the K_l best m in descending order; rank r is output row (sum of K_l' over l' < l) + r: the levels are
+ *       concatenated in the order given, there is NO batch sort                                builder.py:520,569-574
+ *     cls_score[i, row, 0] = 0, cls_score[i, row, 1 + c] = score[p, c]                          builder.py:559-562
+ *     box = _points2bbox(pts, transform, y_first=True) at p: 0 = minmax over all points, 1 = partial_minmax over
+ *       the first four, 2 = moment: mean +- sqrt(mean((v - mean)^2)) * expf(moment_transfer[0 for x, 1 for y]),
+ *       sums sequential in point order -- the expressions of the training head (sd_reppoints_*)  point_ops.py:219-274
+ *     b = box * s + (x*s, y*s, x*s, y*s): a float32 product, then a float32 add                 builder.py:541
+ *     bbox_xyxy = max(min(b, lim), 0), lim = im_info[i, 1] - 1 for x and im_info[i, 0] - 1 for y builder.py:545-548
+ *   Ties (the project's choice; MXNet's order among equal keys is not documented): the lower p first;
+ *     -0.0 == +0.0.  NaN (not part of the contract): a NaN maximum is ordered by its bits.
+ *   No host read of device data, no allocation, no float atomics, no counter to clear, kernels only: equal bits between
+ *   calls and under graph replay.  Loads are scalar: any 4-byte aligned tensor pointer works.  The workspace needs
+ *   no clearing, must be 16-byte aligned and hold sd_reppoints_decode_workspace_bytes(N, C, L, hw_host, k_host)
+ *   bytes, hw_host = L sizes H_l * W_l.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: L outside 1..8, C < 1, N < 0,
+ *   num_points < 1, num_points < 4 with partial_minmax, a level size or stride < 1, k_l > H_l * W_l, transform
+ *   outside 0..2, moment with a NULL moment_transfer, input_logits outside {0, 1}, a null pointer, a misaligned
+ *   workspace; SD_ERR_UNSUPPORTED: K_l > 16384, H_l * W_l > 2^24, N > 65535, N * R * (C + 1) or N * C * H_l * W_l
+ *   above 2^31 - 1; SD_ERR_WORKSPACE: a NULL or too small workspace.  N == 0 succeeds without a launch (the query
+ *   then returns 256, as it does for invalid dimensions).
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_reppoints_decode_workspace_bytes(int N, int C, int L, const long* hw_host, const int* k_host);
+int sd_reppoints_decode(const float* const* cls_ptrs_host, const float* const* pts_ptrs_host, const float* im_info,
+                        const float* moment_transfer, const int* H_host, const int* W_host, const int* stride_host,
+                        const int* k_host, int L, int N, int C, int num_points, int transform, int input_logits,
+                        float* cls_score, float* bbox_xyxy, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

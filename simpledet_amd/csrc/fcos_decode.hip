@@ -159,19 +159,6 @@ __global__ __launch_bounds__(256) void fcos_decode_zero_kernel(int* p, long n) {
   if (i < n) p[i] = 0;
 }
 
-// position of this lane's item in an LDS list when the lanes with `take` append one item each: one LDS atomic
-// per wave.  Every lane of the wave must call it.
-__device__ __forceinline__ int dc_wave_append(bool take, int* counter) {
-  const unsigned long long m = __ballot(take);
-  if (m == 0) return 0;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int leader = __ffsll((long long)m) - 1;
-  int wbase = 0;
-  if (lane == leader) wbase = atomicAdd(counter, __popcll(m));
-  wbase = __shfl(wbase, leader);
-  return wbase + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 // step 2, grid (sum of the levels' chunks, N)
 __global__ __launch_bounds__(kDcT) void fcos_decode_scan_kernel(DecodeArgs a) {
   __shared__ int lh[kDcBins];
@@ -209,7 +196,7 @@ __global__ __launch_bounds__(kDcT) void fcos_decode_scan_kernel(DecodeArgs a) {
       }
       hw += hw_step;
       if (hw >= HW) hw -= HW;
-      const int pos = dc_wave_append(is_cand, &nl);  // < kDcTrip: the list is flushed every trip
+      const int pos = wave_append(is_cand, &nl);  // < kDcTrip: the list is flushed every trip
       if (is_cand) ll[pos] = (unsigned)e;
     }
     __syncthreads();
@@ -275,7 +262,7 @@ __global__ __launch_bounds__(kDcT) void fcos_decode_collect_kernel(DecodeArgs a)
       }
       hw += hw_step;
       if (hw >= HW) hw -= HW;
-      const int pos = dc_wave_append(take, &nl);
+      const int pos = wave_append(take, &nl);
       if (take) lc[pos] = ((unsigned long long)key << 32) | (unsigned)e;
     }
     __syncthreads();

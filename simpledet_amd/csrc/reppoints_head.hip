@@ -26,7 +26,7 @@
 // No float atomics, no memset node, no host read: every call is graph-capturable and repeatable bit for bit.  The
 // arithmetic is the reference's float32 expressions one operation at a time (-ffp-contract=off, correctly rounded
 // divide / sqrt); the sums over the points of a set run sequentially in point order.
-#include "common.h"
+#include "reppoints_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -41,7 +41,6 @@ constexpr int kRpMaxImages = 65535;            // gridDim.y
 constexpr long kRpMaxElems = 2147483647L;      // element indices are 32-bit inside the kernels
 constexpr unsigned kRpInfBits = 0x7f800000u;
 constexpr unsigned long long kRpNoKey = ~0ull;
-enum { kRpMinmax = 0, kRpPartial = 1, kRpMoment = 2 };
 
 struct RpLevels {   // _gen_points (point_ops.py:18-30): level l holds (h, w) row-major, x = w * stride, y = h * stride
   int L, P;
@@ -83,44 +82,7 @@ __device__ __forceinline__ void rp_load(const float* base, int hw, float* y, flo
   }
 }
 
-struct RpMoment { float mean, std, half; };
-// mean of K, sqrt(mean((v - mean)^2)), half extent std * exp(moment_transfer) (point_ops.py:253-265)
-template <int K>
-__device__ __forceinline__ RpMoment rp_moment(const float* v, float e) {
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k) s = s + v[k];
-  RpMoment r;
-  r.mean = s / (float)K;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float d = v[k] - r.mean;
-    q = q + d * d;
-  }
-  r.std = sqrtf(q / (float)K);
-  r.half = r.std * e;
-  return r;
-}
-
-// _points2bbox (point_ops.py:219-274): box = [left, top, right, bottom]
-template <int K, int TR>
-__device__ __forceinline__ void rp_points2bbox(const float* x, const float* y, float e0, float e1, float* box) {
-  if (TR == kRpMoment) {
-    const RpMoment mx = rp_moment<K>(x, e0), my = rp_moment<K>(y, e1);
-    box[0] = mx.mean - mx.half; box[1] = my.mean - my.half;
-    box[2] = mx.mean + mx.half; box[3] = my.mean + my.half;
-  } else {
-    constexpr int Q = TR == kRpPartial ? (K < 4 ? K : 4) : K;
-    float l = x[0], r = x[0], t = y[0], b = y[0];
-#pragma unroll
-    for (int k = 1; k < Q; ++k) {
-      l = fminr(l, x[k]); r = fmaxr(r, x[k]);
-      t = fminr(t, y[k]); b = fmaxr(b, y[k]);
-    }
-    box[0] = l; box[1] = t; box[2] = r; box[3] = b;
-  }
-}
+// rp_moment and rp_points2bbox (_points2bbox, point_ops.py:219-274): reppoints_common.h, shared with the decode
 
 // upstream box_iou, corner format (no +1): extents clamped at 0, 0 where the union is <= 0
 __device__ __forceinline__ float rp_iou(const float* a, const float* g) {

@@ -21,6 +21,19 @@ __device__ __forceinline__ unsigned ordered_desc_bits(float f) {
   return ~u;                                        // descending
 }
 
+// position of this lane's item in an LDS list when the lanes with `take` append one item each: one LDS atomic
+// per wave.  Every lane of the wave must call it.
+__device__ __forceinline__ int wave_append(bool take, int* counter) {
+  const unsigned long long m = __ballot(take);
+  if (m == 0) return 0;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int leader = __ffsll((long long)m) - 1;
+  int wbase = 0;
+  if (lane == leader) wbase = atomicAdd(counter, __popcll(m));
+  wbase = __shfl(wbase, leader);
+  return wbase + __popcll(m & ((1ull << lane) - 1ull));
+}
+
 // ascending bitonic sort of P2 (power of two) 64-bit keys in LDS by the whole workgroup.
 // Stages with a pair distance j <= 64 only exchange inside aligned 128-key blocks, so a wave that
 // owns such a block runs them back to back with no workgroup barrier (the LDS accesses of one wave

@@ -2614,13 +2614,106 @@ def _build_ops(mx):
 
     ops["reppoints_target"] = (RepPointsTargetProp, None)
     ops["reppoints_box_loss"] = (RepPointsBoxLossProp, None)
+
+    # ---- the RepPoints test-time decode (registered only by install(..., reppoints_decode=True)):
+    #      reppoints_decode: L class logit maps, L refine point maps, im_info, moment_transfer -> cls_score (N, R, C + 1),
+    #                        bbox_xyxy (N, R, 4) ----
+    class RepPointsDecode(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            g = self.g
+            L = len(g["stride"])
+            cls, pts, info, mt = in_data[:L], in_data[L:2 * L], in_data[2 * L], in_data[2 * L + 1]
+            N, C = int(cls[0].shape[0]), int(cls[0].shape[1])
+            Hs, Ws = [int(c.shape[2]) for c in cls], [int(c.shape[3]) for c in cls]
+            tab = lambda arrs: (ctypes.c_void_p * L)(*[_ptr(a).value for a in arrs])
+            hws = (ctypes.c_long * L)(*[h * w for h, w in zip(Hs, Ws)])
+            ks = _iarr(_rp_topk_table(g))
+            wsb = int(lib().cdll.sd_reppoints_decode_workspace_bytes(N, C, L, hws, ks))
+            ws = _scratch(cls[0], wsb)
+            _call("sd_reppoints_decode", tab(cls), tab(pts), _ptr(info), _ptr(mt), _iarr(Hs), _iarr(Ws),
+                  _iarr(g["stride"]), ks, L, N, C, g["num_points"], _RP_TRANSFORMS[g["transform"]],
+                  int(g["input_logits"]), _ptr(out_data[0]), _ptr(out_data[1]), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(req)):       # a test-time head: topk and take of rows carry no gradient
+                self.assign(in_grad[i], req[i], 0)
+
+    def _rp_topk_table(g):
+        """rows kept per level (builder.py:499-502): pre_nms_top_n where the stride is <= 32, else all (-1)"""
+        return [g["pre_nms_top_n"] if s <= 32 else -1 for s in g["stride"]]
+
+    class RepPointsDecodeProp(CustomOpProp):
+        def __init__(self, stride, pre_nms_top_n, transform="moment", num_points="9", input_logits="1"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(stride=_tuple(stride, typ=int), pre_nms_top_n=int(pre_nms_top_n), transform=str(transform),
+                          num_points=int(num_points), input_logits=_bool(input_logits))
+            g = self.g
+            if not 1 <= len(g["stride"]) <= 8 or min(g["stride"]) < 1 or g["num_points"] < 1 \
+                    or g["transform"] not in _RP_TRANSFORMS or (g["transform"] == "partial_minmax" and g["num_points"] < 4):
+                raise ValueError("reppoints_decode: stride has 1 to 8 positive entries, num_points is >= 1 (>= 4 for "
+                                 "partial_minmax) and transform one of %s" % sorted(_RP_TRANSFORMS))
+
+        def list_arguments(self):
+            L = len(self.g["stride"])
+            return ["cls_logit_%d" % i for i in range(L)] + ["pts_refine_%d" % i for i in range(L)] + ["im_info", "moment_transfer"]
+
+        def list_outputs(self):
+            return ["cls_score", "bbox_xyxy"]
+
+        def infer_shape(self, in_shape):
+            g = self.g
+            L = len(g["stride"])
+            shapes = [tuple(s) for s in in_shape]
+            if len(shapes) != 2 * L + 2:
+                raise ValueError("reppoints_decode: expected %d inputs, got %d" % (2 * L + 2, len(shapes)))
+            n, c = shapes[0][0], shapes[0][1]
+            r = 0
+            for i, (s, k) in enumerate(zip(g["stride"], _rp_topk_table(g))):
+                a, b = shapes[i], shapes[L + i]
+                if not (len(a) == 4 and a[:2] == (n, c) and b == (n, 2 * g["num_points"]) + a[2:]):
+                    raise ValueError("reppoints_decode: level %d shapes %s / %s do not belong together" % (i, a, b))
+                hw = a[2] * a[3]
+                if k > hw:
+                    raise ValueError(
+                        "reppoints_decode: the stride-%d level holds %d locations, fewer than pre_nms_top_n = %d.  The "
+                        "reference's note (models/RepPoints/builder.py:499-501): pre_nms_top_n_ is hard-coded as -1 only "
+                        "for strides above 32, because the number of proposals is less than pre_nms_top_n in these "
+                        "low-resolution feature maps; one should select the appropriate params here if using "
+                        "low-resolution images as input." % (s, hw, k))
+                keep = k if k > 0 else hw
+                if keep > 16384:
+                    raise ValueError("reppoints_decode: the stride-%d level keeps %d rows, the limit is 16384" % (s, keep))
+                r += keep
+            if shapes[2 * L] and shapes[2 * L] != (n, 3):
+                raise ValueError("reppoints_decode: im_info shape %s, expected %s" % (shapes[2 * L], (n, 3)))
+            if shapes[2 * L + 1] and shapes[2 * L + 1] != (2,):
+                raise ValueError("reppoints_decode: moment_transfer shape %s, expected (2,)" % (shapes[2 * L + 1],))
+            return shapes[:2 * L] + [(n, 3), (2,)], [(n, r, c + 1), (n, r, 4)]
+
+        def infer_type(self, in_type):
+            return [in_type[0]] * (2 * len(self.g["stride"]) + 2), [in_type[0]] * 2, []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return RepPointsDecode(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return []
+
+    ops["reppoints_decode"] = (RepPointsDecodeProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
              mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False, reppoints=False,
-             msrcnn=False):
+             msrcnn=False, reppoints_decode=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
@@ -2643,7 +2736,9 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     reppoints: also sd_reppoints_target and sd_reppoints_box_loss (opt-in: patch_reppoints_loss puts them in place of
     both assigners and both box-loss subgraphs of the RepPoints train graphs);
     msrcnn: also sd_MsrcnnMaskLoss and sd_MaskIoULoss (opt-in: patch_msrcnn_loss puts them in place of the mask-loss
-    and MaskIoU-loss subgraphs, the Python CustomOp maskiou_compute included, of the Mask Scoring R-CNN train graphs)."""
+    and MaskIoU-loss subgraphs, the Python CustomOp maskiou_compute included, of the Mask Scoring R-CNN train graphs);
+    reppoints_decode: also sd_reppoints_decode (opt-in: patch_reppoints_decode puts it in place of the per-level
+    sigmoid / max / topk / take / clip subgraphs of the RepPoints test graphs)."""
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
@@ -2681,6 +2776,8 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
     if not msrcnn:
         table.pop("MsrcnnMaskLoss")
         table.pop("MaskIoULoss")
+    if not reppoints_decode:
+        table.pop("reppoints_decode")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2716,7 +2813,7 @@ def _namespaces(mx, ns):
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
             group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False,
-            reppoints=False, msrcnn=False):
+            reppoints=False, msrcnn=False, reppoints_decode=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2799,10 +2896,20 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     reference's.  Opt-in because it changes which operators those graphs hold, and independent of `mask_loss`, which
     keeps its meaning (the Mask R-CNN builder and the aliased operator).  Where the builder module is not importable
     nothing is rebound and `_state["fallbacks"]` says so; a default install() afterwards puts the reference's
-    methods back.  The test-time path (get_maskiou_prediction) is not touched."""
+    methods back.  The test-time path (get_maskiou_prediction) is not touched.
+
+    `reppoints_decode=True` also registers `sd_reppoints_decode` and rebinds
+    `models.RepPoints.builder.RepPointsHead.get_prediction` (patch_reppoints_decode) so that a RepPoints test graph
+    holds this ONE node in place of, per level, two transposes and reshapes, the sigmoid, max and topk and, per image,
+    the slice / take / scale / add / clip chains, and of the padded column and the two concats behind them; opt-in
+    because it changes which operators that graph holds, and independent of `reppoints` (which keeps meaning the
+    train head alone).  A head with p.fp16 set or beyond the op's limits goes back to the reference's method; where the
+    builder module is not importable nothing is rebound; `_state["fallbacks"]` says so in both cases.  A default
+    install() afterwards puts the reference's method back."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
                      group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
-                     fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints, msrcnn=msrcnn)
+                     fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints, msrcnn=msrcnn,
+                     reppoints_decode=reppoints_decode)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -2944,6 +3051,15 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_MSRCNN_BUILDER) is not None:
             unpatch_msrcnn_loss(sys.modules[_MSRCNN_BUILDER])
         _state["msrcnn_patched"] = False
+    if reppoints_decode:
+        _state["reppoints_decode_patched"] = patch_reppoints_decode(mx=mx)
+        if not _state["reppoints_decode_patched"]:
+            _state["fallbacks"].append(("reppoints_decode", None, "%s.RepPointsHead is not importable" % _REPPOINTS_BUILDER))
+    else:
+        import sys
+        if sys.modules.get(_REPPOINTS_BUILDER) is not None:
+            unpatch_reppoints_decode(sys.modules[_REPPOINTS_BUILDER])
+        _state["reppoints_decode_patched"] = False
     return props
 
 
@@ -3383,6 +3499,83 @@ def unpatch_reppoints_loss(builder_module):
     if original is None:
         return False
     cls.get_loss = original
+    return True
+
+
+def _reppoints_decode_unsupported(p):
+    """why the device op does not take this head's test graph, or ''"""
+    table = _state.get("table") or {}
+    if "reppoints_decode" not in table:
+        return "sd_reppoints_decode is not registered"
+    if p.fp16:
+        return "fp16: the device op is float32"
+    if not 1 <= len(p.point_generate.stride) <= 8:
+        return "%d levels, the limit is 8" % len(p.point_generate.stride)
+    if p.point_generate.transform not in ("minmax", "partial_minmax", "moment"):
+        return "transform=%s" % (p.point_generate.transform,)
+    if int(p.proposal.pre_nms_top_n) > 16384:
+        return "pre_nms_top_n=%s, the limit is 16384" % (p.proposal.pre_nms_top_n,)
+    return ""
+
+
+def patch_reppoints_decode(builder_module=None, mx=None):
+    """Route the RepPoints test-time decode to the device op WITHOUT editing the reference: rebinds
+    `RepPointsHead.get_prediction` of models/RepPoints/builder.py:486-576 -- per level _gen_points, _points2bbox, two
+    transposes and reshapes, sigmoid, max and topk, per image the slice / reshape / take / concat / scale / add / clip
+    chains, then stack, the padded column and the concat of the levels -- to a method that calls
+    `self.get_output(conv_feat)` and emits
+        sd_reppoints_decode(the L raw class logit maps, the L pts_out_refine maps, im_info, moment_transfer)
+    with input_logits = 1 and returns `(cls_score, bbox_xyxy)` as the reference does.  stride, transform and num_points
+    come from p.point_generate, pre_nms_top_n from p.proposal; the rule that keeps every location of a level with a
+    stride above 32 (builder.py:499-502) is the op's.  A head with p.fp16 set, or beyond the limits of the op, goes
+    back to the original method (`_state["fallbacks"]` records why).  install(reppoints_decode=True) calls this when
+    the builder module is importable; returns True when the class was patched.  The original method is kept as
+    `_sd_reference_get_prediction` (a second install() keeps the first original); a default install() afterwards
+    puts it back."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_REPPOINTS_BUILDER)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _REPPOINTS_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_reppoints_decode(module, mx)
+    cls = getattr(builder_module, "RepPointsHead", None)
+    if cls is None:
+        return False
+    original = cls.__dict__.get("_sd_reference_get_prediction") or cls.get_prediction
+
+    def get_prediction(self, conv_feat, im_info):
+        p = self.p
+        why = _reppoints_decode_unsupported(p)
+        if why:
+            _state.setdefault("fallbacks", []).append(("reppoints_decode", None, why))
+            return original(self, conv_feat, im_info)
+        stride = tuple(p.point_generate.stride)
+        _, pts_out_refines, cls_outs = self.get_output(conv_feat)
+        inputs = {"cls_logit_%d" % i: cls_outs["stride%s" % s] for i, s in enumerate(stride)}
+        inputs.update({"pts_refine_%d" % i: pts_out_refines["stride%s" % s] for i, s in enumerate(stride)})
+        out = mx.sym.Custom(op_type=_PREFIX + "reppoints_decode", name="reppoints_decode", **inputs, im_info=im_info,
+                            moment_transfer=self.moment_transfer, stride=_param_str(stride),
+                            pre_nms_top_n=_param_str(int(p.proposal.pre_nms_top_n)),
+                            transform=_param_str(p.point_generate.transform),
+                            num_points=_param_str(p.point_generate.num_points), input_logits="1")
+        return out[0], out[1]
+
+    cls._sd_reference_get_prediction = original
+    cls.get_prediction = get_prediction
+    return True
+
+
+def unpatch_reppoints_decode(builder_module):
+    """Put the reference's get_prediction back."""
+    cls = getattr(builder_module, "RepPointsHead", None)
+    original = cls.__dict__.get("_sd_reference_get_prediction") if cls is not None else None
+    if original is None:
+        return False
+    cls.get_prediction = original
     return True
 
 

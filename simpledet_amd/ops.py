@@ -1903,6 +1903,65 @@ def fcos_decode(cls_list, ctr_list, off_list, im_info, strides, top_n, pre_nms_t
 
 
 # --------------------------------------------------------------------------------------------------
+# RepPoints test-time decode  (models/RepPoints/builder.py RepPointsHead.get_prediction)
+# --------------------------------------------------------------------------------------------------
+def reppoints_topk_table(strides, pre_nms_top_n):
+    """rows kept per level as get_prediction chooses them (builder.py:499-502): pre_nms_top_n if stride <= 32 else
+    -1 (= all locations of the level)"""
+    return [int(pre_nms_top_n) if int(s) <= 32 else -1 for s in strides]
+
+
+def reppoints_decode_workspace_bytes(N, C, hws, ks):
+    """bytes of workspace of reppoints_decode; hws = H_l * W_l and ks = rows kept (<= 0: all) per level"""
+    L = len(hws)
+    if len(ks) != L:
+        raise ValueError("hws and ks need one entry per level each")
+    return int(lib().cdll.sd_reppoints_decode_workspace_bytes(int(N), int(C), L, (ctypes.c_long * max(L, 1))(*hws),
+                                                              _iarr(ks)))
+
+
+def reppoints_decode(cls_list, pts_refine_list, im_info, strides, ks, *, transform="moment", moment_transfer=None,
+                     input_logits=False, cls_score=None, bbox_xyxy=None, workspace=None):
+    """RepPointsHead.get_prediction (models/RepPoints/builder.py:486-576) in one call: per level cls (N, C, H, W) and
+    pts_out_refine (N, 2 * num_points, H, W); im_info (N, 3) on the device; ks = rows kept per level, <= 0 keeps
+    every location (reppoints_topk_table gives the reference's rule).  input_logits=False: cls holds probabilities;
+    True: raw logits, the sigmoid is fused.  Returns (cls_score (N, R, C + 1), bbox_xyxy (N, R, 4)) with R the sum
+    of the rows kept, levels in the order given, each in descending order of its best class score.  Nothing is read
+    back from the device."""
+    L = len(cls_list)
+    if L == 0 or not (len(pts_refine_list) == len(strides) == len(ks) == L):
+        raise ValueError("cls_list, pts_refine_list, strides and ks need one entry per level each")
+    _chk(im_info, "im_info", ndim=2)
+    N, C = int(cls_list[0].shape[0]), int(cls_list[0].shape[1])
+    if tuple(im_info.shape) != (N, 3):
+        raise ValueError("im_info should be (N, 3) = (%d, 3), got %s" % (N, tuple(im_info.shape)))
+    K2 = int(pts_refine_list[0].shape[1]) if pts_refine_list[0].dim() == 4 else 0
+    if K2 < 2 or K2 % 2:
+        raise ValueError("pts_refine_list[0] should be (N, 2 * num_points, H, W), got %s" % (tuple(pts_refine_list[0].shape),))
+    Hs, Ws = [], []
+    for i, (c, t) in enumerate(zip(cls_list, pts_refine_list)):
+        _chk(c, "cls_list[%d]" % i, ndim=4)
+        _chk(t, "pts_refine_list[%d]" % i, ndim=4)
+        H, W = int(c.shape[2]), int(c.shape[3])
+        if tuple(c.shape) != (N, C, H, W) or tuple(t.shape) != (N, K2, H, W):
+            raise ValueError("level %d: cls %s and points %s do not belong together" % (i, tuple(c.shape), tuple(t.shape)))
+        Hs.append(H)
+        Ws.append(W)
+    tr = _reppoints_transform(transform, moment_transfer)
+    hws = [h * w for h, w in zip(Hs, Ws)]
+    ks = [int(k) for k in ks]
+    R = sum(k if k > 0 else hw for k, hw in zip(ks, hws))
+    dev = im_info.device
+    cls_score = _fcos_out(cls_score, "cls_score", (N, R, C + 1), dev)
+    bbox_xyxy = _fcos_out(bbox_xyxy, "bbox_xyxy", (N, R, 4), dev)
+    ws = _ce_ws(dev, reppoints_decode_workspace_bytes(N, C, hws, ks), workspace)
+    lib().call("sd_reppoints_decode", _parr(cls_list), _parr(pts_refine_list), _p(im_info), _p(moment_transfer),
+               _iarr(Hs), _iarr(Ws), _iarr(strides), _iarr(ks), L, N, C, K2 // 2, tr, int(bool(input_logits)),
+               _p(cls_score), _p(bbox_xyxy), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return cls_score, bbox_xyxy
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_NMS (operator_cxx/contrib/nms{-inl.h,.cu}) and the Cython soft-NMS family
 # --------------------------------------------------------------------------------------------------
 def nms(dets, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300, threshold=0.7, already_sorted=False,
