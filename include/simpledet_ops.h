@@ -516,6 +516,8 @@ int sd_rpn_anchor_target(const float* im_info, const float* gt_bbox, int B, int 
  *   replaces the function of the same name there.
  *   x (N,C,H,W)  offset (N, dgroup*2*kh*kw, Ho, Wo)  weight (F, C, kh, kw)  y (N,F,Ho,Wo)
  *   col (N, C*kh*kw, Ho*Wo), row (c*kh + i)*kw + j
+ *   Ho = (H + 2*pad_h - (dil_h*(kh-1) + 1)) / stride_h + 1, Wo likewise; a dilated kernel extent larger than
+ *   the padded input on either axis is SD_ERR_INVALID_ARG ("kernel size exceed input") at every stride.
  * ---------------------------------------------------------------------------------------------- */
 int sd_deform_im2col(const float* x, const float* offset, float* col, int N, int C, int H, int W,
                      int kh, int kw, int pad_h, int pad_w, int stride_h, int stride_w, int dil_h,

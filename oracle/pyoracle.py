@@ -366,20 +366,30 @@ def bbox_overlaps(boxes, query):
 # ------------------------------------------------------------------------------------------------
 # DeformableConvolution v1 (parity unpinned: restated published algorithm, see deform_conv.c)
 # ------------------------------------------------------------------------------------------------
+def _hw(v):
+    """an int (both axes) or an (h, w) pair -> (h, w)"""
+    if isinstance(v, (tuple, list)):
+        h, w = v
+        return int(h), int(w)
+    return int(v), int(v)
+
+
 def _out_hw(H, W, kh, kw, pad, stride, dil):
-    return ((H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1,
-            (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1)
+    (ph, pw), (sh, sw), (dh, dw) = _hw(pad), _hw(stride), _hw(dil)
+    return ((H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1,
+            (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1)
 
 
 def deform_im2col(x, offset, kernel=(3, 3), pad=1, stride=1, dil=1, dgroup=1):
-    """x (C,H,W), offset (dgroup*2*kh*kw,Ho,Wo) -> col (C*kh*kw, Ho*Wo)."""
+    """x (C,H,W), offset (dgroup*2*kh*kw,Ho,Wo) -> col (C*kh*kw, Ho*Wo).  pad, stride and dil: an int or an
+    (h, w) pair, here and in the two col2im pieces."""
     x, px = _f(x)
     offset, po = _f(offset)
     C, H, W = x.shape
     kh, kw = kernel
     Ho, Wo = _out_hw(H, W, kh, kw, pad, stride, dil)
     col = np.empty((C * kh * kw, Ho * Wo), np.float32)
-    cdll().orc_deform_im2col(px, po, col.ctypes, C, H, W, kh, kw, pad, pad, stride, stride, dil, dil,
+    cdll().orc_deform_im2col(px, po, col.ctypes, C, H, W, kh, kw, *_hw(pad), *_hw(stride), *_hw(dil),
                              dgroup, Ho, Wo)
     return col
 
@@ -391,7 +401,7 @@ def deform_col2im(col, offset, x_shape, kernel=(3, 3), pad=1, stride=1, dil=1, d
     kh, kw = kernel
     Ho, Wo = _out_hw(H, W, kh, kw, pad, stride, dil)
     dx = np.zeros((C, H, W), np.float32)
-    cdll().orc_deform_col2im(pc, po, dx.ctypes, C, H, W, kh, kw, pad, pad, stride, stride, dil, dil,
+    cdll().orc_deform_col2im(pc, po, dx.ctypes, C, H, W, kh, kw, *_hw(pad), *_hw(stride), *_hw(dil),
                              dgroup, Ho, Wo)
     return dx
 
@@ -404,8 +414,8 @@ def deform_col2im_coord(col, x, offset, kernel=(3, 3), pad=1, stride=1, dil=1, d
     kh, kw = kernel
     Ho, Wo = _out_hw(H, W, kh, kw, pad, stride, dil)
     doff = np.zeros_like(offset)
-    cdll().orc_deform_col2im_coord(pc, px, po, doff.ctypes, C, H, W, kh, kw, pad, pad, stride,
-                                   stride, dil, dil, dgroup, Ho, Wo)
+    cdll().orc_deform_col2im_coord(pc, px, po, doff.ctypes, C, H, W, kh, kw, *_hw(pad), *_hw(stride),
+                                   *_hw(dil), dgroup, Ho, Wo)
     return doff
 
 

@@ -911,6 +911,10 @@ int make_geom(DcnGeom& g, int N, int C, int H, int W, int kh, int kw, int pad_h,
              "bad kernel/stride/dilate");
   SD_REQUIRE(pad_h >= 0 && pad_w >= 0, "negative pad");
   SD_REQUIRE(dgroup > 0 && C % dgroup == 0, "input num_filter must divide deformable group size");
+  // (checked on the extents, not on Ho / Wo: with a stride above 1, C's division rounds a negative numerator towards
+  // zero and gives an output size of 1 where the floor division of the callers' shape arithmetic gives 0)
+  SD_REQUIRE(dil_h * (kh - 1) + 1 <= H + 2 * pad_h && dil_w * (kw - 1) + 1 <= W + 2 * pad_w,
+             "kernel size exceed input");
   g = DcnGeom{N, C, H, W, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, dgroup, 0, 0};
   g.Ho = (H + 2 * pad_h - (dil_h * (kh - 1) + 1)) / stride_h + 1;
   g.Wo = (W + 2 * pad_w - (dil_w * (kw - 1) + 1)) / stride_w + 1;

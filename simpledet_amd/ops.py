@@ -2024,21 +2024,37 @@ def bbox_overlaps(boxes, query_boxes):
 # --------------------------------------------------------------------------------------------------
 # DeformableConvolution v1 (mx.sym.contrib.DeformableConvolution, models/dcn/builder.py:14-17)
 # --------------------------------------------------------------------------------------------------
+def _dcn_hw(v, name):
+    """an int (both axes) or an (h, w) pair -> (h, w)"""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("%s must be an int or have 2 entries (h, w)" % name)
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
 def _dcn_out_hw(H, W, kh, kw, pad, stride, dil):
-    return ((H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1,
-            (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1)
+    (ph, pw), (sh, sw), (dh, dw) = _dcn_hw(pad, "pad"), _dcn_hw(stride, "stride"), _dcn_hw(dil, "dilate")
+    return ((H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1,
+            (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1)
+
+
+def _dcn_geom(pad, stride, dilate):
+    """the six per-axis geometry arguments of the piece entry points, in the C ABI's order"""
+    return _dcn_hw(pad, "pad") + _dcn_hw(stride, "stride") + _dcn_hw(dilate, "dilate")
 
 
 def deform_im2col(x, offset, kernel=(3, 3), pad=1, stride=1, dilate=1, num_deformable_group=1):
-    """deformable_im2col: x (N,C,H,W), offset (N,dg*2*kh*kw,Ho,Wo) -> col (N, C*kh*kw, Ho*Wo)."""
+    """deformable_im2col: x (N,C,H,W), offset (N,dg*2*kh*kw,Ho,Wo) -> col (N, C*kh*kw, Ho*Wo).
+    pad, stride and dilate are each an int (both axes) or an (h, w) pair, here and in the two col2im pieces."""
     _chk(x, "x", ndim=4)
     _chk(offset, "offset", ndim=4)
     N, C, H, W = x.shape
     kh, kw = kernel
     Ho, Wo = _dcn_out_hw(H, W, kh, kw, pad, stride, dilate)
     col = torch.empty((N, C * kh * kw, Ho * Wo), device=x.device, dtype=torch.float32)
-    lib().call("sd_deform_im2col", _p(x), _p(offset), _p(col), N, C, H, W, kh, kw, pad, pad, stride,
-               stride, dilate, dilate, int(num_deformable_group), _stream())
+    lib().call("sd_deform_im2col", _p(x), _p(offset), _p(col), N, C, H, W, kh, kw,
+               *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _stream())
     return col
 
 
@@ -2050,15 +2066,14 @@ def deform_col2im(col, offset, x_shape, kernel=(3, 3), pad=1, stride=1, dilate=1
     kh, kw = kernel
     dx = torch.empty((N, C, H, W), device=col.device, dtype=torch.float32)
     if not workspace:   # fp32 compare-and-swap adds (what a caller without a workspace gets)
-        lib().call("sd_deform_col2im", _p(col), _p(offset), _p(dx), REQ["write"], N, C, H, W, kh, kw, pad,
-                   pad, stride, stride, dilate, dilate, int(num_deformable_group), _stream())
+        lib().call("sd_deform_col2im", _p(col), _p(offset), _p(dx), REQ["write"], N, C, H, W, kh, kw,
+                   *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _stream())
         return dx
     lib().cdll.sd_deform_col2im_workspace_bytes.restype = ctypes.c_size_t
     n = int(lib().cdll.sd_deform_col2im_workspace_bytes(N, int(num_deformable_group)))
     ws = torch.empty(n, device=col.device, dtype=torch.uint8)
-    lib().call("sd_deform_col2im_ws", _p(col), _p(offset), _p(dx), REQ["write"], N, C, H, W, kh, kw, pad,
-               pad, stride, stride, dilate, dilate, int(num_deformable_group), _p(ws), ctypes.c_size_t(n),
-               _stream())
+    lib().call("sd_deform_col2im_ws", _p(col), _p(offset), _p(dx), REQ["write"], N, C, H, W, kh, kw,
+               *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _p(ws), ctypes.c_size_t(n), _stream())
     return dx
 
 
@@ -2071,8 +2086,7 @@ def deform_col2im_coord(col, x, offset, kernel=(3, 3), pad=1, stride=1, dilate=1
     kh, kw = kernel
     doff = torch.empty_like(offset)
     lib().call("sd_deform_col2im_coord", _p(col), _p(x), _p(offset), _p(doff), REQ["write"], N, C, H,
-               W, kh, kw, pad, pad, stride, stride, dilate, dilate, int(num_deformable_group),
-               _stream())
+               W, kh, kw, *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _stream())
     return doff
 
 

@@ -29,15 +29,22 @@ Forward semantics restated (the only facts taken from the published kernel):
 import torch
 
 
+def _hw(v):
+    """an int (both axes) or an (h, w) pair -> (h, w)"""
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
 def _coords(offset, H, W, kh, kw, pad, stride, dil, dgroup):
-    """sample coordinates (N, dgroup, kh*kw, Ho, Wo) in fp64, from offsets in their stored precision"""
+    """sample coordinates (N, dgroup, kh*kw, Ho, Wo) in fp64, from offsets in their stored precision;
+    pad, stride and dil are each an int or an (h, w) pair (here and in every function below)"""
+    (ph, pw), (sh, sw), (dh, dw) = _hw(pad), _hw(stride), _hw(dil)
     N, _, Ho, Wo = offset.shape
     off = offset.double().reshape(N, dgroup, kh * kw, 2, Ho, Wo)
     dev = offset.device
-    hs = (torch.arange(Ho, device=dev, dtype=torch.float64) * stride - pad).reshape(1, 1, 1, Ho, 1)
-    ws = (torch.arange(Wo, device=dev, dtype=torch.float64) * stride - pad).reshape(1, 1, 1, 1, Wo)
-    ti = (torch.arange(kh * kw, device=dev) // kw).double().reshape(1, 1, kh * kw, 1, 1) * dil
-    tj = (torch.arange(kh * kw, device=dev) % kw).double().reshape(1, 1, kh * kw, 1, 1) * dil
+    hs = (torch.arange(Ho, device=dev, dtype=torch.float64) * sh - ph).reshape(1, 1, 1, Ho, 1)
+    ws = (torch.arange(Wo, device=dev, dtype=torch.float64) * sw - pw).reshape(1, 1, 1, 1, Wo)
+    ti = (torch.arange(kh * kw, device=dev) // kw).double().reshape(1, 1, kh * kw, 1, 1) * dh
+    tj = (torch.arange(kh * kw, device=dev) % kw).double().reshape(1, 1, kh * kw, 1, 1) * dw
     return hs + ti + off[:, :, :, 0], ws + tj + off[:, :, :, 1]
 
 

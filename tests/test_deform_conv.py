@@ -10,14 +10,16 @@ import numpy as np
 import pytest
 
 
-def _case(seed, N=2, C=8, H=9, W=11, F=6, k=3, pad=1, stride=1, dil=1, dg=4, off_scale=1.5):
+def _case(seed, N=2, C=8, H=9, W=11, F=6, k=3, pad=1, stride=1, dil=1, dg=4, off_scale=1.5, kernel=None):
+    """kernel=(kh, kw) overrides the square k x k"""
     rs = np.random.RandomState(seed)
-    Ho = (H + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
-    Wo = (W + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
+    kh, kw = kernel if kernel is not None else (k, k)
+    Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) // stride + 1
+    Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) // stride + 1
     x = rs.standard_normal((N, C, H, W)).astype(np.float32)
-    off = (rs.standard_normal((N, dg * 2 * k * k, Ho, Wo)) * off_scale).astype(np.float32)
-    w = (rs.standard_normal((F, C, k, k)) * 0.2).astype(np.float32)
-    return x, off, w, dict(pad=pad, stride=stride, dil=dil, dgroup=dg, kernel=(k, k))
+    off = (rs.standard_normal((N, dg * 2 * kh * kw, Ho, Wo)) * off_scale).astype(np.float32)
+    w = (rs.standard_normal((F, C, kh, kw)) * 0.2).astype(np.float32)
+    return x, off, w, dict(pad=pad, stride=stride, dil=dil, dgroup=dg, kernel=(kh, kw))
 
 
 def _nok(kw):
@@ -397,7 +399,12 @@ def test_gemm_k_slices_of_the_last_round(ops):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", [dict(), dict(stride=2, H=14, W=15), dict(pad=2, dil=2),
-                                 dict(N=2, C=32, H=25, W=42, F=24, dg=4)])
+                                 dict(N=2, C=32, H=25, W=42, F=24, dg=4),
+                                 # kh != kw (pad 1 on both axes): the dW layout (c*kh + i)*kw + j, the dcol GEMM
+                                 # and both col2im kernels behind the operator
+                                 dict(kernel=(1, 3)), dict(kernel=(3, 1)), dict(kernel=(2, 3)),
+                                 dict(kernel=(2, 3), stride=2), dict(kernel=(3, 5)), dict(kernel=(1, 9)),
+                                 dict(kernel=(9, 1))])
 def test_deform_conv_forward_backward(ops, oracle, cfg):
     x, off, w, kw = _case(11, **cfg)
     a = dict(pad=kw["pad"], stride=kw["stride"], dilate=kw["dil"], num_deformable_group=kw["dgroup"])
@@ -722,6 +729,8 @@ def test_backward_with_the_forward_col_matrix(ops):
     dict(N=2, C=32, H=9, W=11, F=12, dg=2, bias=False, G=4),
     dict(N=2, C=24, H=10, W=12, F=8, dg=3, bias=True, G=2, stride=2),         # filter groups != deformable groups
     dict(N=2, C=32, H=12, W=16, F=16, dg=2, bias=True, G=1, pad=2, dil=2),
+    dict(N=2, C=32, H=12, W=16, F=12, dg=2, bias=True, G=2, kernel=(1, 3)),   # kh != kw with filter groups
+    dict(N=2, C=32, H=12, W=16, F=12, dg=2, bias=False, G=4, kernel=(3, 5)),
 ])
 def test_full_operator_bias_and_groups(ops, oracle, cfg):
     """sd_deform_convolution_fwd / _bwd against the oracle's DeformableConvolutionOp restatement: y and the
@@ -800,6 +809,21 @@ def test_autograd_mirror_with_bias_and_groups(ops):
     close = lambda u, v: float((u - v).abs().max()) <= 1e-5 * max(1.0, float(v.abs().max()))
     assert close(out.detach(), y) and torch.equal(offr.grad, g[1]) and torch.equal(br.grad, g[3])
     assert close(xr.grad, g[0]) and close(wr.grad, g[2])
+    # a 1x3 kernel (pad 1 on both axes: Ho = H + 2, Wo = W) through the same mirror
+    off13 = torch.randn(N, 2 * 2 * 3, H + 2, W, device="cuda")
+    w13 = torch.randn(F, C // G, 1, 3, device="cuda") * 0.1
+    y13 = ops.deform_conv_forward(x, off13, w13, bias=b, **a)
+    assert tuple(y13.shape) == (N, F, H + 2, W)
+    dy13 = torch.randn_like(y13)
+    g13 = ops.deform_conv_backward(dy13, x, off13, w13, bias=True, **a)
+    xr3, offr3, wr3, br3 = (t.clone().requires_grad_(True) for t in (x, off13, w13, b))
+    out13 = contrib.DeformableConvolution(xr3, offr3, wr3, bias=br3, kernel=(1, 3), pad=(1, 1), num_filter=F,
+                                          num_group=G, num_deformable_group=2)
+    out13.backward(dy13)
+    assert close(out13.detach(), y13) and torch.equal(offr3.grad, g13[1]) and torch.equal(br3.grad, g13[3])
+    assert close(xr3.grad, g13[0]) and close(wr3.grad, g13[2])
+    with pytest.raises(ValueError):   # the kernel argument is checked against the weight: (3, 1) is not (1, 3)
+        contrib.DeformableConvolution(x, off13, w13, bias=b, kernel=(3, 1), pad=(1, 1), num_group=G)
     with pytest.raises(ValueError):
         contrib.DeformableConvolution(x, off, w, bias=None, kernel=(3, 3), pad=(1, 1), num_group=G)   # no_bias=False, no bias
     # no gradient wanted: the col-free path (its workspace is a few MB, not N*C*9*Ho*Wo*4 bytes)
