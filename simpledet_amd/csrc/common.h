@@ -50,6 +50,29 @@ int tuning(const char* key, int dflt);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Carves a caller's workspace into 256-byte aligned buffers.  A layout function takes its buffers from one
+// carver in one order, so the size query (a null workspace: every take() is null and only counts) and the call
+// (real pointers) cannot disagree.
+static inline size_t round256(size_t v) { return (v + 255) / 256 * 256; }
+struct WsCarver {
+  char* base;      // the workspace rounded up to 256 bytes
+  size_t off = 0;  // bytes taken from base
+  size_t slack;    // bytes between the workspace and base
+  explicit WsCarver(void* workspace)
+      : base(reinterpret_cast<char*>(round256((size_t)(uintptr_t)workspace))),
+        slack((size_t)(base - (char*)workspace)) {}
+  template <typename T>
+  T* take(size_t bytes) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off = round256(off + bytes);
+    return p;
+  }
+  size_t need() const { return off + slack; }  // bytes of the caller's workspace in use
+};
+
+// clears n int counters on the stream with a kernel (runtime.hip)
+void zero_counters(int* p, long n, hipStream_t stream);
+
 // mshadow_op::maximum / minimum semantics (a > b ? a : b), kept explicit for NaN parity
 __host__ __device__ static inline float fmaxr(float a, float b) { return a > b ? a : b; }
 __host__ __device__ static inline float fminr(float a, float b) { return a < b ? a : b; }

@@ -33,8 +33,7 @@
 //
 // MI355X design (all launches on the caller's stream, nothing read back by the host, no device allocation, no float
 // atomics -- integer atomics only, for counts, histograms and list appends whose order the sorts restore):
-//   1. fcos_decode_zero_kernel   clears the per-(image, level) counters.  A kernel, not a memset node: the counters
-//                                must be zero again in every replay of a captured graph (see quant_int8.hip).
+//   1. zero_counters             clears the per-(image, level) counters (runtime.hip: a kernel, not a memset node).
 //   2. fcos_decode_scan_kernel   grid over (level chunk, image): streams cls once, counts the candidates, appends
 //                                their flat indices to the level's sparse list while it has room (top_n words),
 //                                and builds a 4096-bin histogram of the top 12 bits of ordered_desc_bits(fused).
@@ -117,48 +116,6 @@ __device__ __forceinline__ float dc_clip(float v, float hi) {  // np.clip(v, 0, 
   return v > hi ? hi : v;
 }
 
-// cut-off bin of the `want`-th best key from a level's global histogram (total >= want); wave 0 scans, every
-// thread of the workgroup gets the result; sh: LDS scratch of 3 ints
-__device__ __forceinline__ void dc_resolve_bin(const int* __restrict__ gh, int want, int* sh, int* bstar,
-                                               int* below, int* nb) {
-  __syncthreads();
-  if (threadIdx.x < kWave) {
-    const int lane = threadIdx.x;
-    const int4* h4 = reinterpret_cast<const int4*>(gh + lane * (kDcBins / kWave));
-    int tot = 0;
-#pragma unroll
-    for (int q = 0; q < kDcBins / kWave / 4; ++q) {
-      const int4 v = h4[q];
-      tot += v.x + v.y + v.z + v.w;
-    }
-    int incl = tot;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    const int excl = incl - tot;
-    if (excl < want && want <= incl) {  // exactly one lane
-      int run = excl, b = lane * (kDcBins / kWave);
-      const int bend = b + kDcBins / kWave - 1;
-      while (b < bend && run + gh[b] < want) run += gh[b++];
-      sh[0] = b;
-      sh[1] = run;
-      sh[2] = gh[b];
-    }
-  }
-  __syncthreads();
-  *bstar = sh[0];
-  *below = sh[1];
-  *nb = sh[2];
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void fcos_decode_zero_kernel(int* p, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
-
 // step 2, grid (sum of the levels' chunks, N)
 __global__ __launch_bounds__(kDcT) void fcos_decode_scan_kernel(DecodeArgs a) {
   __shared__ int lh[kDcBins];
@@ -201,15 +158,7 @@ __global__ __launch_bounds__(kDcT) void fcos_decode_scan_kernel(DecodeArgs a) {
     }
     __syncthreads();
     const int n = nl;
-    if (n > 0) {
-      if (tid == 0) base = atomicAdd(&gc[0], n);
-      __syncthreads();
-      const int b = base;
-      for (int j = tid; j < n; j += kDcT)
-        if (b + j < a.top_n) sp[b + j] = ll[j];
-      __syncthreads();
-      if (tid == 0) nl = 0;
-    }
+    if (n > 0) wg_list_flush<kDcT>(ll, n, &nl, &base, &gc[0], sp, a.top_n);
     __syncthreads();
   }
   int* gh = a.hist + il * kDcBins;
@@ -226,7 +175,7 @@ __global__ __launch_bounds__(kDcT) void fcos_decode_collect_kernel(DecodeArgs a)
   int* gc = a.gctr + il * kDcCtr;
   if (gc[0] < a.top_n) return;  // sparse or empty level: step 2 left everything step 4 needs
   int bstar, below, nb;
-  dc_resolve_bin(a.hist + il * kDcBins, a.top_n, sh, &bstar, &below, &nb);
+  hist_cut_bin<kDcBins>(a.hist + il * kDcBins, a.top_n, sh, &bstar, &below, &nb);
   const int count = a.count[l], HW = a.H[l] * a.W[l], hw_step = kDcT % HW;
   const int lo = ((int)blockIdx.x - a.wg_begin[l]) * a.chunk[l];
   const int hi = (long)lo + a.chunk[l] < count ? lo + a.chunk[l] : count;
@@ -267,23 +216,9 @@ __global__ __launch_bounds__(kDcT) void fcos_decode_collect_kernel(DecodeArgs a)
     }
     __syncthreads();
     const int n = nl;
-    if (n > 0) {
-      if (tid == 0) base = atomicAdd(&gc[1], n);
-      __syncthreads();
-      const int b = base;
-      for (int j = tid; j < n; j += kDcT)
-        if (b + j < kDcCap) cand[b + j] = lc[j];
-      __syncthreads();
-      if (tid == 0) nl = 0;
-    }
+    if (n > 0) wg_list_flush<kDcT>(lc, n, &nl, &base, &gc[1], cand, kDcCap);
     __syncthreads();
   }
-}
-
-__device__ __forceinline__ int dc_pow2(int n) {
-  int p = 64;
-  while (p < n) p <<= 1;
-  return p;
 }
 
 // step 4, grid (L, N)
@@ -299,13 +234,13 @@ __global__ __launch_bounds__(1024) void fcos_decode_level_kernel(DecodeArgs a) {
   int nsel = 0;
   if (nc >= a.top_n) {  // dense (utils.py:32-36)
     int bstar, below, nb;
-    dc_resolve_bin(a.hist + il * kDcBins, a.top_n, sh, &bstar, &below, &nb);
+    hist_cut_bin<kDcBins>(a.hist + il * kDcBins, a.top_n, sh, &bstar, &below, &nb);
     if (below + nb > kDcCap) {
-      select_sort_topk<1>(a.eff + (long)img * a.eff_img + a.eff_begin[l], count, a.top_n, dc_pow2(a.top_n), keys,
-                          hist, &ncand);
+      select_sort_topk<1>(a.eff + (long)img * a.eff_img + a.eff_begin[l], count, a.top_n, sort_size(a.top_n, 64),
+                          keys, hist, &ncand);
     } else {
       const int n = iminr(gc[1], kDcCap);  // == below + nb >= top_n
-      const int P2 = dc_pow2(n);
+      const int P2 = sort_size(n, 64);
       const unsigned long long* cand = a.cand + il * kDcCap;
       for (int i = tid; i < P2; i += T) keys[i] = i < n ? cand[i] : ~0ull;
       __syncthreads();
@@ -313,7 +248,7 @@ __global__ __launch_bounds__(1024) void fcos_decode_level_kernel(DecodeArgs a) {
     }
     nsel = a.top_n;
   } else if (nc > 0) {  // sparse (utils.py:38-46): ascending flat index
-    const int P2 = dc_pow2(nc);
+    const int P2 = sort_size(nc, 64);
     const unsigned* sp = a.sparse + il * a.top_n;
     for (int i = tid; i < P2; i += T) keys[i] = i < nc ? (unsigned long long)sp[i] : ~0ull;
     __syncthreads();
@@ -352,7 +287,7 @@ __global__ __launch_bounds__(1024) void fcos_decode_batch_kernel(DecodeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
   const int img = blockIdx.x, tid = threadIdx.x, T = blockDim.x, R = a.R;
   const float* st = a.stage + (long)img * R * 6;
-  const int P2 = dc_pow2(R);
+  const int P2 = sort_size(R, 64);
   for (int r = tid; r < P2; r += T)
     keys[r] = r < R ? ((unsigned long long)ordered_desc_bits(st[(long)r * 6 + 1]) << 32) | (unsigned)r : ~0ull;
   __syncthreads();
@@ -403,30 +338,18 @@ struct DecodeWs {
   float* val;
 };
 
-size_t decode_layout(int N, int L, long total, int top_n, DecodeWs* ws, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = (off + bytes + 255) / 256 * 256;
-    return o;
-  };
+// bytes of the workspace in use; the size query passes a null workspace and gets null pointers
+size_t decode_layout(int N, int L, long total, int top_n, DecodeWs* ws, void* workspace) {
+  WsCarver c(workspace);
   const size_t NL = (size_t)N * L, R = (size_t)L * top_n;
-  const size_t o_hist = take(NL * (kDcBins + kDcCtr) * sizeof(int));
-  const size_t o_sparse = take(NL * top_n * sizeof(unsigned));
-  const size_t o_cand = take(NL * kDcCap * sizeof(unsigned long long));
-  const size_t o_eff = take((size_t)N * total * sizeof(float));
-  const size_t o_stage = take((size_t)N * R * 6 * sizeof(float));
-  const size_t o_val = take((size_t)N * R * sizeof(float));
-  if (ws) {
-    ws->hist = reinterpret_cast<int*>(base + o_hist);
-    ws->gctr = ws->hist + NL * kDcBins;
-    ws->sparse = reinterpret_cast<unsigned*>(base + o_sparse);
-    ws->cand = reinterpret_cast<unsigned long long*>(base + o_cand);
-    ws->eff = reinterpret_cast<float*>(base + o_eff);
-    ws->stage = reinterpret_cast<float*>(base + o_stage);
-    ws->val = reinterpret_cast<float*>(base + o_val);
-  }
-  return off;
+  ws->hist = c.take<int>(NL * (kDcBins + kDcCtr) * sizeof(int));
+  ws->gctr = ws->hist ? ws->hist + NL * kDcBins : nullptr;
+  ws->sparse = c.take<unsigned>(NL * top_n * sizeof(unsigned));
+  ws->cand = c.take<unsigned long long>(NL * kDcCap * sizeof(unsigned long long));
+  ws->eff = c.take<float>((size_t)N * total * sizeof(float));
+  ws->stage = c.take<float>((size_t)N * R * 6 * sizeof(float));
+  ws->val = c.take<float>((size_t)N * R * sizeof(float));
+  return c.need();
 }
 
 // the argument checks the workspace query and the call share; *total = sum of C*H_l*W_l
@@ -461,7 +384,8 @@ using namespace sd;
 extern "C" size_t sd_fcos_decode_workspace_bytes(int N, int C, int L, const long* hw_host, int top_n) {
   long total = 0;
   if (decode_dims(N, C, L, hw_host, top_n, &total) != SD_OK || N == 0) return 256;
-  return decode_layout(N, L, total, top_n, nullptr, nullptr) + 256;
+  DecodeWs ws;
+  return decode_layout(N, L, total, top_n, &ws, nullptr) + 256;
 }
 
 extern "C" int sd_fcos_decode(const float* const* cls, const float* const* ctr, const float* const* off,
@@ -489,8 +413,7 @@ extern "C" int sd_fcos_decode(const float* const* cls, const float* const* ctr, 
   if (!workspace) return fail(SD_ERR_WORKSPACE, "fcos_decode: null workspace");
   SD_REQUIRE(((uintptr_t)workspace & 15) == 0, "fcos_decode: workspace must be 16-byte aligned");
   DecodeWs ws;
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) / 256 * 256);
-  const size_t need = decode_layout(N, L, total, top_n, &ws, base) + (size_t)(base - (char*)workspace);
+  const size_t need = decode_layout(N, L, total, top_n, &ws, workspace);
   if (workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "fcos_decode workspace too small: %zu < %zu bytes", workspace_bytes, need);
   DecodeArgs a{};
@@ -519,12 +442,9 @@ extern "C" int sd_fcos_decode(const float* const* cls, const float* const* ctr, 
     const int held = (int)(count < kDcCap ? count : kDcCap);
     if (held > max_keys) max_keys = held;
   }
-  int P2 = 64;
-  while (P2 < max_keys) P2 <<= 1;
-  const size_t lds = (size_t)P2 * sizeof(unsigned long long);
+  const size_t lds = (size_t)sort_size(max_keys, 64) * sizeof(unsigned long long);
   hipStream_t st = (hipStream_t)stream;
-  const long nctr = (long)N * L * (kDcBins + kDcCtr);  // < 2^31 * 1.01: the grid below stays under 2^24 blocks
-  hipLaunchKernelGGL(fcos_decode_zero_kernel, dim3((unsigned)((nctr + 255) / 256)), dim3(256), 0, st, ws.hist, nctr);
+  zero_counters(ws.hist, (long)N * L * (kDcBins + kDcCtr), st);  // < 2^31 * 1.01 counters
   SD_LAUNCH_CHECK();
   hipLaunchKernelGGL(fcos_decode_scan_kernel, dim3(a.wg_begin[L], N), dim3(kDcT), 0, st, a);
   SD_LAUNCH_CHECK();

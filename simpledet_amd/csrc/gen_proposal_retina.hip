@@ -115,43 +115,6 @@ __device__ __forceinline__ unsigned retina_key(const RetinaArgs& a, int img, int
   return *keep ? ordered_desc_bits(s) : kKey0;
 }
 
-// cut-off bin of the `want`-th best live key from the global histogram (wave 0 scans, every thread
-// of the workgroup gets the result); sh: LDS scratch of 3 ints
-__device__ __forceinline__ void resolve_bin(const int* __restrict__ gh, int want, int* sh,
-                                            int* bstar, int* below, int* nb) {
-  __syncthreads();
-  if (threadIdx.x < kWave) {
-    const int lane = threadIdx.x;
-    const int4* h4 = reinterpret_cast<const int4*>(gh + lane * (kBins / kWave));
-    int tot = 0;
-#pragma unroll
-    for (int q = 0; q < kBins / kWave / 4; ++q) {
-      const int4 v = h4[q];
-      tot += v.x + v.y + v.z + v.w;
-    }
-    int incl = tot;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    const int excl = incl - tot;
-    if (excl < want && want <= incl) {  // exactly one lane
-      int run = excl, b = lane * (kBins / kWave);
-      const int bend = b + kBins / kWave - 1;
-      while (b < bend && run + gh[b] < want) run += gh[b++];
-      sh[0] = b;
-      sh[1] = run;
-      sh[2] = gh[b];
-    }
-  }
-  __syncthreads();
-  *bstar = sh[0];
-  *below = sh[1];
-  *nb = sh[2];
-  __syncthreads();
-}
-
 // the elements [lo, hi) of this workgroup's chunk, kUnroll float4 (or scalar) loads per lane a trip
 template <typename Fn>
 __device__ __forceinline__ void stream_trip(const RetinaArgs& a, const float* __restrict__ sc,
@@ -182,13 +145,6 @@ __device__ __forceinline__ void stream_trip(const RetinaArgs& a, const float* __
       const int e = t0 + (u * kScanT + tid) * 4 + q;
       if (e < hi) fn(e, v[u][q]);
     }
-}
-
-// the per-call counters (histograms, list lengths) are zeroed by a kernel rather than hipMemsetAsync:
-// the counters must be zero in every replay of a captured graph as well
-__global__ __launch_bounds__(256) void retina_zero_kernel(int* p, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0;
 }
 
 // pass 1, grid (G, B)
@@ -251,7 +207,7 @@ __global__ __launch_bounds__(kScanT) void retina_compact_kernel(RetinaArgs a) {
   const int nlive = gc[0];
   if (nlive <= kCap && gc[1] == 0) return;  // the pass-1 list holds every live row
   int bstar, below, nb;
-  resolve_bin(a.ghist + (long)img * kBins, a.pre < nlive ? a.pre : nlive, sh, &bstar, &below, &nb);
+  hist_cut_bin<kBins>(a.ghist + (long)img * kBins, a.pre < nlive ? a.pre : nlive, sh, &bstar, &below, &nb);
   const bool overflow = below + nb > kCap;
   const float* sc = a.cls_prob + (long)img * a.count;
   const int lo = blockIdx.x * a.chunk;
@@ -284,14 +240,8 @@ __global__ __launch_bounds__(kScanT) void retina_compact_kernel(RetinaArgs a) {
     });
     __syncthreads();
     const int n = nl;
-    if (n > kLocal2 - kTrip || (t0 + kTrip >= hi && n > 0)) {  // flush: one reservation
-      if (tid == 0) base = atomicAdd(n2, n);
-      __syncthreads();
-      for (int j = tid; j < n; j += kScanT)
-        if (base + j < kCap) cand[base + j] = lc[j];
-      __syncthreads();
-      if (tid == 0) nl = 0;
-    }
+    if (n > kLocal2 - kTrip || (t0 + kTrip >= hi && n > 0))
+      wg_list_flush<kScanT>(lc, n, &nl, &base, n2, cand, kCap);
     __syncthreads();
   }
 }
@@ -310,7 +260,7 @@ __global__ __launch_bounds__(1024) void retina_finish_kernel(RetinaArgs a) {
     if (nlive > 0) {
       const int want = a.pre < nlive ? a.pre : nlive;
       int bstar, below, nb;
-      resolve_bin(a.ghist + (long)img * kBins, want, sh, &bstar, &below, &nb);
+      hist_cut_bin<kBins>(a.ghist + (long)img * kBins, want, sh, &bstar, &below, &nb);
       const bool from1 = nlive <= kCap && gc[1] == 0;
       if (!from1 && below + nb > kCap) {
         general = true;
@@ -325,8 +275,7 @@ __global__ __launch_bounds__(1024) void retina_finish_kernel(RetinaArgs a) {
         }
         __syncthreads();
         const int m = ncand;
-        int P2 = 64;
-        while (P2 < m) P2 <<= 1;
+        const int P2 = sort_size(m, 64);
         for (int i = m + tid; i < P2; i += T) keys[i] = ~0ull;
         __syncthreads();
         bitonic_sort_lds(keys, P2, tid, T);
@@ -335,8 +284,7 @@ __global__ __launch_bounds__(1024) void retina_finish_kernel(RetinaArgs a) {
     }
   }
   if (general) {
-    int P2 = 64;
-    while (P2 < a.pre) P2 <<= 1;
+    const int P2 = sort_size(a.pre, 64);
     select_sort_topk<1>(a.eff + (long)img * a.count, a.count, a.pre, P2, keys, hist, &ncand);
     nsel = a.pre;
   }
@@ -377,23 +325,14 @@ struct RetinaWs {
   float* eff;
 };
 
-size_t retina_layout(int B, long count, RetinaWs* ws, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = (off + bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t o_hist = take((size_t)B * (kBins + 4) * sizeof(int));
-  const size_t o_cand = take((size_t)B * kCap * sizeof(unsigned long long));
-  const size_t o_eff = take((size_t)B * count * sizeof(float));
-  if (ws) {
-    ws->ghist = reinterpret_cast<int*>(base + o_hist);
-    ws->gctr = ws->ghist + (size_t)B * kBins;
-    ws->cand = reinterpret_cast<unsigned long long*>(base + o_cand);
-    ws->eff = reinterpret_cast<float*>(base + o_eff);
-  }
-  return off;
+// bytes of the workspace in use; the size query passes a null workspace and gets null pointers
+size_t retina_layout(int B, long count, RetinaWs* ws, void* workspace) {
+  WsCarver c(workspace);
+  ws->ghist = c.take<int>((size_t)B * (kBins + 4) * sizeof(int));
+  ws->gctr = ws->ghist ? ws->ghist + (size_t)B * kBins : nullptr;
+  ws->cand = c.take<unsigned long long>((size_t)B * kCap * sizeof(unsigned long long));
+  ws->eff = c.take<float>((size_t)B * count * sizeof(float));
+  return c.need();
 }
 
 }  // namespace
@@ -403,7 +342,8 @@ using namespace sd;
 
 extern "C" size_t sd_gen_proposal_retina_workspace_bytes(int B, int AK, int H, int W) {
   if (B <= 0 || AK <= 0 || H <= 0 || W <= 0) return 256;
-  return retina_layout(B, (long)AK * H * W, nullptr, nullptr) + 256;
+  RetinaWs ws;
+  return retina_layout(B, (long)AK * H * W, &ws, nullptr) + 256;
 }
 
 extern "C" int sd_gen_proposal_retina(const float* cls_prob, const float* bbox_pred,
@@ -438,8 +378,7 @@ extern "C" int sd_gen_proposal_retina(const float* cls_prob, const float* bbox_p
   SD_REQUIRE(cls_prob && bbox_pred && im_info && anchors && out && score,
              "GenProposalRetina: null tensor pointer");
   RetinaWs ws;
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) / 256 * 256);
-  const size_t need = retina_layout(B, count, &ws, base) + (size_t)(base - (char*)workspace);
+  const size_t need = retina_layout(B, count, &ws, workspace);
   if (!workspace || workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "GenProposalRetina workspace too small: %zu < %zu bytes",
                 workspace_bytes, need);
@@ -467,8 +406,7 @@ extern "C" int sd_gen_proposal_retina(const float* cls_prob, const float* bbox_p
   a.G = (int)((count + chunk - 1) / chunk);
   a.ghist = ws.ghist; a.gctr = ws.gctr; a.cand = ws.cand; a.eff = ws.eff;
   hipStream_t st = (hipStream_t)stream;
-  const int nctr = B * (kBins + 4);
-  hipLaunchKernelGGL(retina_zero_kernel, dim3((nctr + 255) / 256), dim3(256), 0, st, ws.ghist, nctr);
+  zero_counters(ws.ghist, (long)B * (kBins + 4), st);
   SD_LAUNCH_CHECK();
   hipLaunchKernelGGL(retina_scan_kernel, dim3(a.G, B), dim3(kScanT), 0, st, a);
   SD_LAUNCH_CHECK();

@@ -538,28 +538,7 @@ __device__ __forceinline__ TopkState topk_resolve(const int* __restrict__ gh, in
   for (int p = 0; p < npass; ++p) {
     const int shift = 24 - 8 * p;
     __syncthreads();
-    if (threadIdx.x < kWave) {
-      const int lane = threadIdx.x;
-      const int* h = gh + p * 256;
-      const int c0 = h[4 * lane], c1 = h[4 * lane + 1], c2 = h[4 * lane + 2], c3 = h[4 * lane + 3];
-      const int tot = c0 + c1 + c2 + c3;
-      int incl = tot;
-#pragma unroll
-      for (int o = 1; o < kWave; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-      }
-      const int excl = incl - tot;
-      if (excl < s.want && s.want <= incl) {  // exactly one lane
-        int run = excl, d = 4 * lane, sz = c0;
-        if (run + c0 < s.want) { run += c0; d = 4 * lane + 1; sz = c1;
-          if (run + c1 < s.want) { run += c1; d = 4 * lane + 2; sz = c2;
-            if (run + c2 < s.want) { run += c2; d = 4 * lane + 3; sz = c3; } } }
-        hist[256] = d;
-        hist[257] = run;
-        hist[258] = sz;
-      }
-    }
+    if (threadIdx.x < kWave) rank_pick256(gh + p * 256, s.want, hist + 256);
     __syncthreads();
     s.want -= hist[257];
     s.prefix |= (unsigned)hist[256] << shift;
@@ -716,18 +695,8 @@ __global__ __launch_bounds__(1024) void topk_finish_kernel(PropArgs a) {
   if (tid == 0) ncand = nc;
   __syncthreads();
   if (!a.v12 && s.want < s.n_eq) {
-    // only the `want` lowest rows among the ties are taken: select the want-th smallest tied row
-    unsigned ipre = 0, imask = 0;
-    int iwant = s.want;
-    auto ikey = [&](int i) { return skey(i) == Tkey ? (unsigned)i : 0xffffffffu; };
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      int below, bucket;
-      const int d = radix_digit(a.count, shift, imask, ipre, iwant, hist, &below, &bucket, ikey);
-      iwant -= below;
-      ipre |= (unsigned)d << shift;
-      imask |= 255u << shift;
-    }
-    const unsigned Irow = ipre;
+    // only the `want` lowest rows among the ties are taken
+    const unsigned Irow = select_tie_row(a.count, s.want, Tkey, hist, skey);
     for (int i = tid; i < a.count; i += T) {
       if (skey(i) == Tkey && (unsigned)i <= Irow) {
         const int pos = atomicAdd(&ncand, 1);
@@ -741,8 +710,6 @@ __global__ __launch_bounds__(1024) void topk_finish_kernel(PropArgs a) {
 }
 
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 static void nms_dims(int N, int pre_in, int post_in, int* pre, int* post, int* nb) {
   int p = pre_in > 0 ? pre_in : N;  // nms.cu:274-277
   if (p > N) p = N;
@@ -751,24 +718,12 @@ static void nms_dims(int N, int pre_in, int post_in, int* pre, int* post, int* n
   *nb = (p + 63) / 64;
 }
 
-static size_t nms_layout(int B, int pre, int nb, NmsWs* ws, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  const size_t o_order = take((size_t)B * pre * sizeof(int));
-  const size_t o_boxes = take((size_t)B * pre * sizeof(float4));
-  const size_t o_score = take((size_t)B * pre * sizeof(float));
-  const size_t o_mask = take((size_t)B * pre * nb * sizeof(unsigned long long));
-  if (ws) {
-    ws->order = reinterpret_cast<int*>(base + o_order);
-    ws->boxes = reinterpret_cast<float4*>(base + o_boxes);
-    ws->score = reinterpret_cast<float*>(base + o_score);
-    ws->mask = reinterpret_cast<unsigned long long*>(base + o_mask);
-  }
-  return off;
+// the layouts serve the size query (a carver over a null workspace: the pointers come out null) and the call
+static void nms_layout(int B, int pre, int nb, NmsWs* ws, WsCarver& c) {
+  ws->order = c.take<int>((size_t)B * pre * sizeof(int));
+  ws->boxes = c.take<float4>((size_t)B * pre * sizeof(float4));
+  ws->score = c.take<float>((size_t)B * pre * sizeof(float));
+  ws->mask = c.take<unsigned long long>((size_t)B * pre * nb * sizeof(unsigned long long));
 }
 
 }  // namespace sd
@@ -779,7 +734,10 @@ extern "C" size_t sd_nms_workspace_bytes(int B, int N, int pre_nms_top_n) {
   if (B <= 0 || N <= 0) return 256;
   int pre, post, nb;
   nms_dims(N, pre_nms_top_n, N, &pre, &post, &nb);
-  return nms_layout(B, pre, nb, nullptr, nullptr) + 256;
+  NmsWs ws;
+  WsCarver c(nullptr);
+  nms_layout(B, pre, nb, &ws, c);
+  return c.need() + 256;
 }
 
 extern "C" int sd_nms(const float* dets, int B, int N, int pre_nms_top_n, int post_nms_top_n,
@@ -793,8 +751,7 @@ extern "C" int sd_nms(const float* dets, int B, int N, int pre_nms_top_n, int po
   nms_dims(N, pre_nms_top_n, post_nms_top_n, &pre, &post, &nb);
   SD_REQUIRE(dets && out && score, "null tensor pointer");
   SD_REQUIRE(((uintptr_t)out & 15) == 0, "out must be 16-byte aligned");
-  int P2 = 1;
-  while (P2 < N) P2 <<= 1;
+  int P2 = sort_size(N, 1);
   // more rows than one LDS sort holds: select the pre_nms_top_n best first (pre < N), sort those
   const bool select = !already_sorted && P2 > kMaxSortKeys;
   if (select && pre > kMaxSortKeys)
@@ -802,13 +759,11 @@ extern "C" int sd_nms(const float* dets, int B, int N, int pre_nms_top_n, int po
                 "sort capacity; got %d), or already_sorted=1 with pre-sorted input", N, kMaxSortKeys, pre);
   SD_REQUIRE(pre <= kMaxSortKeys, "NMS: pre_nms_top_n=%d exceeds %d", pre, kMaxSortKeys);
   SD_REQUIRE(N < (1 << 24), "NMS: N=%d rows per image exceed 2^24", N);
-  if (select) {
-    P2 = 1;
-    while (P2 < pre) P2 <<= 1;
-  }
+  if (select) P2 = sort_size(pre, 1);
   NmsWs ws;
-  char* base = reinterpret_cast<char*>(align_up((size_t)(uintptr_t)workspace, 256));
-  const size_t need = nms_layout(B, pre, nb, &ws, base) + (size_t)(base - (char*)workspace);
+  WsCarver c(workspace);
+  nms_layout(B, pre, nb, &ws, c);
+  const size_t need = c.need();
   if (!workspace || workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "NMS workspace too small: %zu < %zu bytes", workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
@@ -898,20 +853,33 @@ static int topk_groups(int count) {
   return G > 128 ? 128 : G;
 }
 
-// with_ties: Proposal / Proposal_v2 also keep the last-digit histogram of every chunk (B x G x 256
-// ints) that ranks the ties at the cut-off; Proposal_v3's layout is unchanged
-static size_t proposal_ws_bytes(int B, int A, int H, int W, int pre_nms_top_n, bool with_ties) {
+// ints the multi-workgroup top-k clears per call: per image 4 x 256 digit counters and a candidate counter
+static size_t proposal_counters(int B) { return (size_t)B * (4 * 256 + 1); }
+
+// The Proposal workspace: the NMS buffers, every decoded box and score, the multi-workgroup top-k's counters
+// (B x 4 x 256 digit counters, then B candidate counters) and P2 candidate words per image, and for Proposal /
+// Proposal_v2 (v12) the last-digit histogram of every chunk (B x G x 256 ints) that ranks the ties at the cut-off.
+// Returns the bytes of the workspace in use; the size query passes a null workspace and gets null pointers.
+static size_t proposal_layout(int B, long count, int pre, int nb, int P2, bool v12, PropArgs* a,
+                              void* workspace) {
+  WsCarver c(workspace);
+  nms_layout(B, pre, nb, &a->ws, c);
+  a->boxes_all = c.take<float4>((size_t)B * count * 16);
+  a->score_all = c.take<float>((size_t)B * count * 4);
+  a->ghist = c.take<int>(proposal_counters(B) * sizeof(int));
+  a->gncand = a->ghist ? a->ghist + (size_t)B * 4 * 256 : nullptr;
+  a->gcand = c.take<unsigned long long>((size_t)B * P2 * 8);
+  if (v12) a->gtie = c.take<int>((size_t)B * topk_groups((int)count) * 1024);
+  return c.need();
+}
+
+static size_t proposal_ws_bytes(int B, int A, int H, int W, int pre_nms_top_n, bool v12) {
   if (B <= 0 || A <= 0 || H <= 0 || W <= 0) return 256;
   const long count = (long)A * H * W;
   int pre, post;
   proposal_dims((int)count, pre_nms_top_n, 1, 1, &pre, &post);
-  const int nb = (pre + 63) / 64;
-  int P2 = 64;
-  while (P2 < pre) P2 <<= 1;
-  return nms_layout(B, pre, nb, nullptr, nullptr) + align_up((size_t)B * count * 16, 256) +
-         align_up((size_t)B * count * 4, 256) + align_up((size_t)B * (4 * 256 + 1) * 4, 256) +
-         align_up((size_t)B * P2 * 8, 256) +
-         (with_ties ? align_up((size_t)B * topk_groups((int)count) * 1024, 256) : 0) + 512;
+  PropArgs a;
+  return proposal_layout(B, count, pre, (pre + 63) / 64, sort_size(pre, 64), v12, &a, nullptr) + 512;
 }
 
 extern "C" size_t sd_proposal_v3_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n) {
@@ -924,15 +892,6 @@ extern "C" size_t sd_proposal_v2_workspace_bytes(int B, int A, int H, int W, int
 
 extern "C" size_t sd_proposal_workspace_bytes(int B, int A, int H, int W, int pre_nms_top_n) {
   return proposal_ws_bytes(B, A, H, W, pre_nms_top_n, true);
-}
-
-// the top-k counters (digit histograms, candidate counts) are zeroed by a kernel rather than
-// hipMemsetAsync: they must be zero in every replay of a captured graph as well (a memset node was
-// not repeated on replays here, see gen_proposal_retina.hip; stale counts let the finish kernel
-// read candidate slots this call never wrote)
-__global__ __launch_bounds__(256) void topk_zero_kernel(int* p, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0;
 }
 
 // version 3: Proposal_v3; 2: Proposal_v2 (valid_ranges / filter_scales); 1: Proposal (is_train
@@ -972,25 +931,8 @@ static int proposal_impl(int version, const float* cls_prob, const float* bbox_p
   SD_REQUIRE(((uintptr_t)out & 15) == 0, "out must be 16-byte aligned");
   const int nb = (pre + 63) / 64;
   PropArgs a{};
-  char* base = reinterpret_cast<char*>(align_up((size_t)(uintptr_t)workspace, 256));
-  size_t off = nms_layout(B, pre, nb, &a.ws, base);
-  a.boxes_all = reinterpret_cast<float4*>(base + off);
-  off += align_up((size_t)B * count * 16, 256);
-  a.score_all = reinterpret_cast<float*>(base + off);
-  off += align_up((size_t)B * count * 4, 256);
-  int P2 = 64;
-  while (P2 < pre) P2 <<= 1;
-  a.ghist = reinterpret_cast<int*>(base + off);  // B x 4 x 256 counters, then B candidate counters
-  a.gncand = a.ghist + (size_t)B * 4 * 256;
-  const size_t counters_bytes = (size_t)B * (4 * 256 + 1) * 4;
-  off += align_up(counters_bytes, 256);
-  a.gcand = reinterpret_cast<unsigned long long*>(base + off);
-  off += align_up((size_t)B * P2 * 8, 256);
-  if (v12) {
-    a.gtie = reinterpret_cast<int*>(base + off);  // B x G x 256 last-digit counts
-    off += align_up((size_t)B * topk_groups(count) * 1024, 256);
-  }
-  const size_t need = off + (size_t)(base - (char*)workspace);
+  const int P2 = sort_size(pre, 64);
+  const size_t need = proposal_layout(B, count, pre, nb, P2, v12, &a, workspace);
   if (!workspace || workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "%s workspace too small: %zu < %zu bytes", name, workspace_bytes,
                 need);
@@ -1020,8 +962,7 @@ static int proposal_impl(int version, const float* cls_prob, const float* bbox_p
   const bool multi = mode == 2 || (mode != 1 && count >= 32768);
   if (multi) {
     a.G = topk_groups(count);
-    const int nctr = (int)(counters_bytes / 4);
-    hipLaunchKernelGGL(topk_zero_kernel, dim3((nctr + 255) / 256), dim3(256), 0, st, a.ghist, nctr);
+    zero_counters(a.ghist, (long)proposal_counters(B), st);
     for (int pass = 0; pass < 4; ++pass)
       hipLaunchKernelGGL(topk_hist_kernel, dim3(a.G, B), dim3(256), 0, st, a, pass);
     hipLaunchKernelGGL(topk_compact_kernel, dim3(a.G, B), dim3(256), 0, st, a);
@@ -1142,10 +1083,8 @@ extern "C" int sd_get_top_proposal(const float* bbox, const float* score, int B,
   if (B == 0 || top_n == 0) return SD_OK;
   SD_REQUIRE(out_bbox && out_score && ((bbox && score) || N == 0), "null tensor pointer");
   SD_REQUIRE((((uintptr_t)bbox | (uintptr_t)out_bbox) & 15) == 0, "bbox must be 16-byte aligned");
-  int P2 = 64;
-  while (P2 < N) P2 <<= 1;
-  int P2t = 64;
-  while (P2t < top_n) P2t <<= 1;
+  int P2 = sort_size(N, 64);
+  const int P2t = sort_size(top_n, 64);
   // fewer rows wanted than given: radix select, then sort the survivors only (N is then bounded by
   // the 2^24 rows of the select, not by the LDS sort capacity)
   const int select = (top_n < N && P2t < P2) ? 1 : 0;

@@ -849,36 +849,23 @@ __global__ __launch_bounds__(kMaskThreads) void pt_mask_ratio_kernel(PtArgs a) {
   }
 }
 
-static inline size_t align_up(size_t v, size_t al) { return (v + al - 1) / al * al; }
-
-static size_t pt_layout(int B, int N, int M, int S, PtWs* ws, char* base) {
+// bytes of the workspace in use; the size query passes a null workspace and gets null pointers
+static size_t pt_layout(int B, int N, int M, int S, PtWs* ws, void* workspace) {
   if (M < 1) M = 1;  // ProposalTarget_v2 substitutes one zero gt / roi for an empty list
   const size_t Ncand = (size_t)N + M;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  const size_t o_cand = take(B * Ncand * 16), o_ov = take(B * Ncand * 4), o_gta = take(B * Ncand * 4);
-  const size_t o_gtbox = take((size_t)B * M * 16), o_gtcls = take((size_t)B * M * 4);
-  const size_t o_fg = take(B * Ncand * 4), o_neg = take(B * Ncand * 4), o_bg = take(B * Ncand * 4);
-  const size_t o_cnt = take((size_t)B * 8 * 4), o_kept = take((size_t)B * (S > 0 ? S : 1) * 4);
-  const size_t o_gtsrc = take((size_t)B * M * 4);
-  if (ws) {
-    ws->cand = reinterpret_cast<float4*>(base + o_cand);
-    ws->ov = reinterpret_cast<float*>(base + o_ov);
-    ws->gta = reinterpret_cast<int*>(base + o_gta);
-    ws->gtbox = reinterpret_cast<float4*>(base + o_gtbox);
-    ws->gtcls = reinterpret_cast<float*>(base + o_gtcls);
-    ws->fg = reinterpret_cast<int*>(base + o_fg);
-    ws->neg = reinterpret_cast<int*>(base + o_neg);
-    ws->bg = reinterpret_cast<int*>(base + o_bg);
-    ws->counts = reinterpret_cast<int*>(base + o_cnt);
-    ws->kept = reinterpret_cast<int*>(base + o_kept);
-    ws->gtsrc = reinterpret_cast<int*>(base + o_gtsrc);
-  }
-  return off;
+  WsCarver c(workspace);
+  ws->cand = c.take<float4>(B * Ncand * 16);
+  ws->ov = c.take<float>(B * Ncand * 4);
+  ws->gta = c.take<int>(B * Ncand * 4);
+  ws->gtbox = c.take<float4>((size_t)B * M * 16);
+  ws->gtcls = c.take<float>((size_t)B * M * 4);
+  ws->fg = c.take<int>(B * Ncand * 4);
+  ws->neg = c.take<int>(B * Ncand * 4);
+  ws->bg = c.take<int>(B * Ncand * 4);
+  ws->counts = c.take<int>((size_t)B * 8 * 4);
+  ws->kept = c.take<int>((size_t)B * (S > 0 ? S : 1) * 4);
+  ws->gtsrc = c.take<int>((size_t)B * M * 4);
+  return c.need();
 }
 
 constexpr int kPtMaxRois = 4096;  // S bound for the workspace query (kept list)
@@ -916,7 +903,8 @@ extern "C" int sd_glibc_srand_host(uint32_t seed, int32_t* state_host) {
 
 extern "C" size_t sd_proposal_target_workspace_bytes(int B, int N, int M) {
   if (B <= 0 || N < 0 || M < 0) return 256;
-  return pt_layout(B, N, M, kPtMaxRois, nullptr, nullptr) + 256;
+  PtWs ws;
+  return pt_layout(B, N, M, kPtMaxRois, &ws, nullptr) + 256;
 }
 
 static int proposal_target_impl(const float* rois, const float* gt_boxes, const float* valid_ranges,
@@ -943,13 +931,12 @@ static int proposal_target_impl(const float* rois, const float* gt_boxes, const 
   SD_REQUIRE(rng_state, "rng_state is null");
   SD_REQUIRE((((uintptr_t)rois | (uintptr_t)roi_output) & 15) == 0, "rois must be 16-byte aligned");
   PtArgs a{};
-  char* base = reinterpret_cast<char*>(align_up((size_t)(uintptr_t)workspace, 256));
-  size_t need = pt_layout(B, N, M, S, &a.ws, base) + (size_t)(base - (char*)workspace);
+  size_t need = pt_layout(B, N, M, S, &a.ws, workspace);
   if (mask_ratio) {  // two bitmaps of max_raster_pixels bits per foreground row behind the rest
     const int FG = (int)((float)S * p.fg_fraction);
     a.bit_words = (max_raster_pixels + 63) / 64;
-    a.bits = reinterpret_cast<unsigned long long*>((char*)workspace + align_up(need, 256));
-    need = align_up(need, 256) + (size_t)B * FG * 2 * a.bit_words * sizeof(unsigned long long);
+    a.bits = reinterpret_cast<unsigned long long*>((char*)workspace + round256(need));
+    need = round256(need) + (size_t)B * FG * 2 * a.bit_words * sizeof(unsigned long long);
     a.ratio_out = mask_ratio;
   }
   if (!workspace || workspace_bytes < need)
@@ -1008,7 +995,8 @@ extern "C" size_t sd_proposal_mask_target_ratio_workspace_bytes(int B, int N, in
   if (B <= 0 || N < 0 || M < 0 || image_rois < 0 || max_raster_pixels <= 0) return 256;
   const int FG = (int)((float)image_rois * fg_fraction);
   const size_t words = ((size_t)max_raster_pixels + 63) / 64;
-  return align_up(pt_layout(B, N, M, kPtMaxRois, nullptr, nullptr) + 256, 256) + 256 +
+  PtWs ws;
+  return round256(pt_layout(B, N, M, kPtMaxRois, &ws, nullptr) + 256) + 256 +
          (size_t)B * (FG > 0 ? FG : 0) * 2 * words * sizeof(unsigned long long);
 }
 

@@ -109,12 +109,6 @@ __global__ __launch_bounds__(kRdT) void rd_max_kernel(RdArgs a) {
     a.m[(long)img * a.P + a.m_begin[l] + p] = fmaxr(fmaxr(sm[0][lane], sm[1][lane]), fmaxr(sm[2][lane], sm[3][lane]));
 }
 
-__device__ __forceinline__ int rd_pow2(int n) {
-  int p = 64;
-  while (p < n) p <<= 1;
-  return p;
-}
-
 // The stable top-`pre` of `count` <= kRdSelT * kRdRegKeys scores by one workgroup of kRdSelT threads, the keys held
 // in REGISTERS: thread t owns the U = ceil(count / kRdSelT) consecutive rows from t * U, so thread order is row
 // order.  Four 8-bit radix passes find the pre-th best key (one LDS add per key into a histogram kept in kRdRep
@@ -147,17 +141,8 @@ __device__ __forceinline__ void rd_select_regs(const float* __restrict__ sc, int
       sum[tid] = s;
     }
     __syncthreads();
-    if (wave == 0) {  // the digit where the running count reaches `want`: exactly one lane finds it
-      const int c0 = sum[4 * lane], c1 = sum[4 * lane + 1], c2 = sum[4 * lane + 2], c3 = sum[4 * lane + 3];
-      const int tot = c0 + c1 + c2 + c3, incl = wave_scan_i32(tot), excl = incl - tot;
-      if (excl < want && want <= incl) {
-        int run = excl, d = 4 * lane, sz = c0;
-        if (run + c0 < want) { run += c0; d = 4 * lane + 1; sz = c1;
-          if (run + c1 < want) { run += c1; d = 4 * lane + 2; sz = c2;
-            if (run + c2 < want) { run += c2; d = 4 * lane + 3; sz = c3; } } }
-        sh[0] = d; sh[1] = run; sh[2] = sz;
-      }
-    }
+    if (wave == 0)  // the digit where the running count reaches `want`: exactly one lane finds it
+      rank_pick256(lane, sum, want, sh, [](int, int tot) { return wave_scan_i32(tot); });
     __syncthreads();
     want -= sh[1];
     n_eq = sh[2];
@@ -205,9 +190,9 @@ __global__ __launch_bounds__(kRdSelT) void rd_select_kernel(RdArgs a) {
   const int HW = a.H[l] * a.W[l], K = a.K[l];
   const float* m = a.m + (long)img * a.P + a.m_begin[l];
   if (HW <= kRdSelT * kRdRegKeys)
-    rd_select_regs(m, HW, K, rd_pow2(K), keys, hist, sum, sh, &ncand);
+    rd_select_regs(m, HW, K, sort_size(K, 64), keys, hist, sum, sh, &ncand);
   else  // a level too large for the registers: the shared select, its keys re-read per pass
-    select_sort_topk<1>(m, HW, K, rd_pow2(K), keys, hist, &ncand);
+    select_sort_topk<1>(m, HW, K, sort_size(K, 64), keys, hist, &ncand);
   __syncthreads();
   int* sel = a.sel + (long)img * a.R + a.row_begin[l];
   for (int j = threadIdx.x; j < K; j += blockDim.x) sel[j] = (int)(unsigned)(keys[j] & 0xffffffffu);
@@ -261,20 +246,12 @@ struct RdWs {
   int* sel;
 };
 
-size_t rd_layout(int N, long P, long R, RdWs* ws, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = (off + bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t o_m = take((size_t)N * P * sizeof(float));
-  const size_t o_sel = take((size_t)N * R * sizeof(int));
-  if (ws) {
-    ws->m = reinterpret_cast<float*>(base + o_m);
-    ws->sel = reinterpret_cast<int*>(base + o_sel);
-  }
-  return off;
+// bytes of the workspace in use; the size query passes a null workspace and gets null pointers
+size_t rd_layout(int N, long P, long R, RdWs* ws, void* workspace) {
+  WsCarver c(workspace);
+  ws->m = c.take<float>((size_t)N * P * sizeof(float));
+  ws->sel = c.take<int>((size_t)N * R * sizeof(int));
+  return c.need();
 }
 
 // the argument checks the workspace query and the call share; Kl[l] = rows kept of level l, *P = sum H_l*W_l,
@@ -320,7 +297,8 @@ extern "C" size_t sd_reppoints_decode_workspace_bytes(int N, int C, int L, const
   int Kl[kRdMaxL];
   long P = 0, R = 0;
   if (rd_dims(N, C, L, hw_host, k_host, Kl, &P, &R) != SD_OK || N == 0) return 256;
-  return rd_layout(N, P, R, nullptr, nullptr) + 256;
+  RdWs ws;
+  return rd_layout(N, P, R, &ws, nullptr) + 256;
 }
 
 extern "C" int sd_reppoints_decode(const float* const* cls, const float* const* pts, const float* im_info,
@@ -354,8 +332,7 @@ extern "C" int sd_reppoints_decode(const float* const* cls, const float* const* 
   if (!workspace) return fail(SD_ERR_WORKSPACE, "reppoints_decode: null workspace");
   SD_REQUIRE(((uintptr_t)workspace & 15) == 0, "reppoints_decode: workspace must be 16-byte aligned");
   RdWs ws;
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) / 256 * 256);
-  const size_t need = rd_layout(N, P, R, &ws, base) + (size_t)(base - (char*)workspace);
+  const size_t need = rd_layout(N, P, R, &ws, workspace);
   if (workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "reppoints_decode workspace too small: %zu < %zu bytes", workspace_bytes, need);
   RdArgs a{};
@@ -377,9 +354,7 @@ extern "C" int sd_reppoints_decode(const float* const* cls, const float* const* 
     a.wg_begin[l + 1] = a.wg_begin[l] + cdiv(hw[l], kWave);
     if (Kl[l] > max_keys) max_keys = Kl[l];
   }
-  int P2 = 64;
-  while (P2 < max_keys) P2 <<= 1;
-  const size_t lds = (size_t)P2 * sizeof(unsigned long long);
+  const size_t lds = (size_t)sort_size(max_keys, 64) * sizeof(unsigned long long);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rd_max_kernel, dim3(a.wg_begin[L], N), dim3(kRdT), 0, st, a);
   SD_LAUNCH_CHECK();

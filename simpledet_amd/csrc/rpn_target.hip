@@ -736,51 +736,31 @@ __global__ void retina_fg_kernel(const int* counts, float* fg_count, int B) {
   if (b < B) fg_count[b] = (float)imaxr(1, counts[b]);
 }
 
-static size_t retina_layout(int B, int N, int M, RpnArgs* a, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = (off + bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t o_mo = take((size_t)B * N * 4), o_am = take((size_t)B * N * 4), o_kp = take((size_t)B * N);
+// the layouts return the bytes of the workspace in use; the size queries pass a null workspace and get null pointers
+static size_t retina_layout(int B, int N, int M, RpnArgs* a, void* workspace) {
+  WsCarver c(workspace);
+  a->maxov = c.take<float>((size_t)B * N * 4);
+  a->argmax = c.take<int>((size_t)B * N * 4);
+  a->keep = c.take<unsigned char>((size_t)B * N);   // (written by rpn_overlap, not read)
   // gtmax and the per-image counters are adjacent: retina_base clears both
-  const size_t o_gm = take((size_t)B * (M > 0 ? M : 1) * 4), o_ct = take((size_t)B * 4);
-  const size_t o_ba = take((size_t)kRpnMaxLvl * kRpnMaxA * 4 * sizeof(double));
-  if (a) {
-    a->base64 = reinterpret_cast<const double*>(base + o_ba);
-    a->maxov = reinterpret_cast<float*>(base + o_mo);
-    a->argmax = reinterpret_cast<int*>(base + o_am);
-    a->keep = reinterpret_cast<unsigned char*>(base + o_kp);   // (written by rpn_overlap, not read)
-    a->gtmax = reinterpret_cast<unsigned*>(base + o_gm);
-    a->counts = reinterpret_cast<int*>(base + o_ct);
-  }
-  return off;
+  a->gtmax = c.take<unsigned>((size_t)B * (M > 0 ? M : 1) * 4);
+  a->counts = c.take<int>((size_t)B * 4);
+  a->base64 = c.take<const double>((size_t)kRpnMaxLvl * kRpnMaxA * 4 * sizeof(double));
+  return c.need();
 }
 
-static size_t rpn_layout(int B, int N, int M, int nblk, RpnArgs* a, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = (off + bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t o_mo = take((size_t)B * N * 4), o_am = take((size_t)B * N * 4), o_lb = take((size_t)B * N);
-  const size_t o_kp = take((size_t)B * N), o_gm = take((size_t)B * (M > 0 ? M : 1) * 4);
-  const size_t o_bk = take((size_t)B * nblk * 2 * 4), o_fg = take((size_t)B * N * 4);
-  const size_t o_bg = take((size_t)B * N * 4), o_ct = take((size_t)(B * 4 + 1) * 4);
-  if (a) {
-    a->maxov = reinterpret_cast<float*>(base + o_mo);
-    a->argmax = reinterpret_cast<int*>(base + o_am);
-    a->label = reinterpret_cast<signed char*>(base + o_lb);
-    a->keep = reinterpret_cast<unsigned char*>(base + o_kp);
-    a->gtmax = reinterpret_cast<unsigned*>(base + o_gm);
-    a->blk = reinterpret_cast<int*>(base + o_bk);
-    a->fg_list = reinterpret_cast<int*>(base + o_fg);
-    a->bg_list = reinterpret_cast<int*>(base + o_bg);
-    a->counts = reinterpret_cast<int*>(base + o_ct);
-  }
-  return off;
+static size_t rpn_layout(int B, int N, int M, int nblk, RpnArgs* a, void* workspace) {
+  WsCarver c(workspace);
+  a->maxov = c.take<float>((size_t)B * N * 4);
+  a->argmax = c.take<int>((size_t)B * N * 4);
+  a->label = c.take<signed char>((size_t)B * N);
+  a->keep = c.take<unsigned char>((size_t)B * N);
+  a->gtmax = c.take<unsigned>((size_t)B * (M > 0 ? M : 1) * 4);
+  a->blk = c.take<int>((size_t)B * nblk * 2 * 4);
+  a->fg_list = c.take<int>((size_t)B * N * 4);
+  a->bg_list = c.take<int>((size_t)B * N * 4);
+  a->counts = c.take<int>((size_t)(B * 4 + 1) * 4);
+  return c.need();
 }
 
 static int rpn_count(const sd_rpn_target_param& p, int* A, int* N, int* sumHW) {
@@ -833,7 +813,8 @@ extern "C" int sd_rpn_target_num_anchors(const sd_rpn_target_param* p) {
 extern "C" size_t sd_rpn_target_workspace_bytes(const sd_rpn_target_param* p, int B, int M) {
   int A, N, S;
   if (!p || B <= 0 || rpn_count(*p, &A, &N, &S)) return 256;
-  return rpn_layout(B, N, M, cdiv(N, kRpnT), nullptr, nullptr) + 256;
+  RpnArgs a{};
+  return rpn_layout(B, N, M, cdiv(N, kRpnT), &a, nullptr) + 256;
 }
 
 // numpy MT19937 seeding (init_genrand via _legacy_seeding(seed)): key[624] + pos = 624
@@ -872,8 +853,7 @@ extern "C" int sd_rpn_anchor_target(const float* im_info, const float* gt_bbox, 
   a.im_info = im_info; a.gt = gt_bbox; a.B = B; a.M = M; a.G = G; a.mt = mt_state;
   a.cls = cls_label; a.tgt = reg_target; a.wgt = reg_weight; a.layout = layout;
   a.nblk = cdiv(a.N, kRpnT);
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  const size_t need = rpn_layout(B, a.N, M, a.nblk, &a, base) + (size_t)(base - (char*)workspace);
+  const size_t need = rpn_layout(B, a.N, M, a.nblk, &a, workspace);
   if (!workspace || workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "rpn_anchor_target workspace too small: %zu < %zu bytes",
                 workspace_bytes, need);
@@ -895,7 +875,8 @@ extern "C" int sd_rpn_anchor_target(const float* im_info, const float* gt_bbox, 
 extern "C" size_t sd_retina_target_workspace_bytes(const sd_rpn_target_param* p, int B, int M) {
   int A, N, S;
   if (!p || B <= 0 || M < 0 || rpn_count(*p, &A, &N, &S)) return 256;
-  return retina_layout(B, N, M, nullptr, nullptr) + 256;
+  RpnArgs a{};
+  return retina_layout(B, N, M, &a, nullptr) + 256;
 }
 
 extern "C" int sd_retina_anchor_target(const float* im_info, const float* gt_bbox, int B, int M,
@@ -930,8 +911,7 @@ extern "C" int sd_retina_anchor_target(const float* im_info, const float* gt_bbo
   a.im_info = im_info; a.gt = gt_bbox; a.B = B; a.M = M; a.G = 5;
   a.cls = cls_label; a.tgt = reg_target; a.wgt = reg_weight; a.layout = layout;
   a.nblk = cdiv(a.N, kRpnT);
-  char* base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  const size_t need = retina_layout(B, a.N, M, &a, base) + (size_t)(base - (char*)workspace);
+  const size_t need = retina_layout(B, a.N, M, &a, workspace);
   if (!workspace || workspace_bytes < need)
     return fail(SD_ERR_WORKSPACE, "retina_anchor_target workspace too small: %zu < %zu bytes",
                 workspace_bytes, need);

@@ -83,6 +83,18 @@ int tuning(const char* key, int dflt) {
 }  // namespace sd
 
 namespace sd {
+// The per-call counters of the selection operators (digit and bin histograms, candidate counts, list lengths) are
+// zeroed by a kernel rather than hipMemsetAsync: they must be zero in every replay of a captured graph as well (a
+// memset node was not repeated on replays here; stale counts let a finishing kernel read candidate slots its call
+// never wrote).  n < 2^31 * 1.01: the grid stays under 2^24 blocks.
+__global__ __launch_bounds__(256) void zero_counters_kernel(int* p, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+void zero_counters(int* p, long n, hipStream_t stream) {
+  hipLaunchKernelGGL(zero_counters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, n);
+}
+
 // HBM streaming copy: the measured-peak companion of the 8 TB/s spec figure and the known-byte
 // calibration stream for rocprofv3's FETCH_SIZE / WRITE_SIZE (MI355X_MICROARCH.md, HBM).
 template <typename T>

@@ -1,13 +1,24 @@
-// Stable descending top-k pieces shared by the selection kernels (nms.hip: NMS, Proposal_v3;
-// gen_proposal_retina.hip): the score -> sort-key map, the LDS bitonic sort of composite
-// (key, row) words, one 8-bit digit of a workgroup radix select and the single-workgroup
-// stable top-k built from them.
+// The single implementation of the stable descending top-k ("Selection rule"): the
+// score -> sort-key map, the size and the LDS bitonic sort of composite (key, row) words, the pick of
+// the counter that holds a rank (256 digit counters or a histogram of bins), one 8-bit digit of a
+// workgroup radix select, the row select among partly taken ties, the single-workgroup stable top-k
+// built from them and the flush of a workgroup's candidate list.
+// Users: nms.hip (_contrib_NMS, Proposal / Proposal_v2 / Proposal_v3, get_top_proposal),
+// gen_proposal_retina.hip (GenProposalRetina), fcos_decode.hip (FCOS decode), reppoints_decode.hip
+// (RepPoints decode) and bbox_post.hip (BboxPostProcessing: the LDS sort).
 #pragma once
 #include "common.h"
 
 namespace sd {
 
 constexpr int kMaxSortKeys = 16384;
+
+// keys an LDS sort of n words runs over: the first power of two >= n, counted up from `start`
+__host__ __device__ __forceinline__ int sort_size(int n, int start) {
+  int p = start;
+  while (p < n) p <<= 1;
+  return p;
+}
 
 // Sort key of a score: smaller key = better score.  -0.0 and +0.0 get the SAME key (the reference's
 // thrust::stable_sort_by_key(greater<float>) and MXNet's SortByKey compare them equal and keep
@@ -82,6 +93,87 @@ __device__ __forceinline__ void bitonic_sort_lds(unsigned long long* keys, int P
   }
 }
 
+// inclusive prefix sum over wave 0 (lane = threadIdx.x) through __shfl_up
+__device__ __forceinline__ int wave0_scan_shfl(int lane, int tot) {
+  int incl = tot;
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  return incl;
+}
+
+// The digit or bin where the running count of 256 counters reaches `want` (1-based): the 64 lanes of wave 0 scan
+// them (4 per lane + the wave prefix sum `scan(lane, total)`), and the one lane whose four counters hold the rank
+// publishes (digit, count below it, its size) in out[0 .. 3).  Called by wave 0 only, between two barriers.
+template <typename Scan>
+__device__ __forceinline__ void rank_pick256(int lane, const int* ctr, int want, int* out, Scan scan) {
+  const int c0 = ctr[4 * lane], c1 = ctr[4 * lane + 1], c2 = ctr[4 * lane + 2], c3 = ctr[4 * lane + 3];
+  const int tot = c0 + c1 + c2 + c3, incl = scan(lane, tot), excl = incl - tot;
+  if (excl < want && want <= incl) {  // exactly one lane
+    int run = excl, d = 4 * lane, sz = c0;
+    if (run + c0 < want) { run += c0; d = 4 * lane + 1; sz = c1;
+      if (run + c1 < want) { run += c1; d = 4 * lane + 2; sz = c2;
+        if (run + c2 < want) { run += c2; d = 4 * lane + 3; sz = c3; } } }
+    out[0] = d;
+    out[1] = run;
+    out[2] = sz;
+  }
+}
+// with the __shfl_up scan (radix_digit, nms.hip's topk_resolve); reppoints_decode.hip passes its DPP scan
+__device__ __forceinline__ void rank_pick256(const int* ctr, int want, int* out) {
+  rank_pick256(threadIdx.x, ctr, want, out, wave0_scan_shfl);
+}
+
+// cut-off bin of the `want`-th best key from a global histogram of BINS bins (total >= want); wave 0
+// scans, every thread of the workgroup gets the result; sh: LDS scratch of 3 ints
+template <int BINS>
+__device__ __forceinline__ void hist_cut_bin(const int* __restrict__ gh, int want, int* sh, int* bstar,
+                                             int* below, int* nb) {
+  __syncthreads();
+  if (threadIdx.x < kWave) {
+    const int lane = threadIdx.x;
+    const int4* h4 = reinterpret_cast<const int4*>(gh + lane * (BINS / kWave));
+    int tot = 0;
+#pragma unroll
+    for (int q = 0; q < BINS / kWave / 4; ++q) {
+      const int4 v = h4[q];
+      tot += v.x + v.y + v.z + v.w;
+    }
+    const int incl = wave0_scan_shfl(lane, tot), excl = incl - tot;
+    if (excl < want && want <= incl) {  // exactly one lane
+      int run = excl, b = lane * (BINS / kWave);
+      const int bend = b + BINS / kWave - 1;
+      while (b < bend && run + gh[b] < want) run += gh[b++];
+      sh[0] = b;
+      sh[1] = run;
+      sh[2] = gh[b];
+    }
+  }
+  __syncthreads();
+  *bstar = sh[0];
+  *below = sh[1];
+  *nb = sh[2];
+  __syncthreads();
+}
+
+// A workgroup of T threads moves its LDS list of n > 0 items (n read from *nl behind a barrier, the same in every
+// thread) to a global list: one reservation on *gcount for the whole workgroup, the items that land below `cap`
+// copied out, the LDS count reset.  The caller's next barrier orders the reset.
+template <int T, typename W>
+__device__ __forceinline__ void wg_list_flush(const W* list, int n, int* nl, int* base, int* gcount, W* dst,
+                                              int cap) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *base = atomicAdd(gcount, n);
+  __syncthreads();
+  const int b = *base;
+  for (int j = tid; j < n; j += T)
+    if (b + j < cap) dst[b + j] = list[j];
+  __syncthreads();
+  if (tid == 0) *nl = 0;
+}
+
 // one 8-bit digit of a radix select among the elements whose key matches `prefix` under `mask`:
 // returns the digit where the running count reaches `want` (1-based rank inside the matching set)
 // and updates below (elements before that digit) -- all threads get the same values
@@ -120,36 +212,32 @@ __device__ __forceinline__ int radix_digit(int count, int shift, unsigned mask, 
     }
   }
   __syncthreads();
-  // wave 0 scans the 256 counters (4 per lane + a wave prefix sum) and publishes the digit where
-  // the running count reaches `want`
-  if (threadIdx.x < kWave) {
-    const int lane = threadIdx.x;
-    const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2],
-              c3 = hist[4 * lane + 3];
-    const int tot = c0 + c1 + c2 + c3;
-    int incl = tot;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    const int excl = incl - tot;
-    if (excl < want && want <= incl) {  // exactly one lane
-      int run = excl, d = 4 * lane, sz = c0;
-      if (run + c0 < want) { run += c0; d = 4 * lane + 1; sz = c1;
-        if (run + c1 < want) { run += c1; d = 4 * lane + 2; sz = c2;
-          if (run + c2 < want) { run += c2; d = 4 * lane + 3; sz = c3; } } }
-      hist[256] = d;
-      hist[257] = run;
-      hist[258] = sz;
-    }
-  }
+  if (threadIdx.x < kWave) rank_pick256(hist, want, hist + 256);
   __syncthreads();
   const int digit = hist[256], lower = hist[257], size = hist[258];
   *below = lower;
   *bucket = size;
   __syncthreads();
   return digit;
+}
+
+// Ties on the score key Tkey that are only partly taken: the lowest rows win (stable sort).  Returns the
+// want-th smallest row among the rows whose key skey(i) is Tkey; ties with row <= that row are taken.
+template <typename KeyFn>
+__device__ __forceinline__ unsigned select_tie_row(int count, int want, unsigned Tkey, int* hist,
+                                                   KeyFn skey) {
+  unsigned ipre = 0, imask = 0;
+  int iwant = want;
+  auto ikey = [&](int i) { return skey(i) == Tkey ? (unsigned)i : 0xffffffffu; };
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    int below, bucket;
+    // rows that do not carry Tkey map to 0xffffffff and never match a prefix below 2^24 rows
+    const int d = radix_digit(count, shift, imask, ipre, iwant, hist, &below, &bucket, ikey);
+    iwant -= below;
+    ipre |= (unsigned)d << shift;
+    imask |= 255u << shift;
+  }
+  return ipre;
 }
 
 // Stable top-`pre` of `count` scores by one workgroup: 8-bit radix select of the pre-th best score
@@ -174,23 +262,10 @@ __device__ __forceinline__ void select_sort_topk(const float* __restrict__ sc, i
   }
   const unsigned Tkey = prefix;  // `want` of the elements with this key are still needed
   const int n_eq = last_bucket;  // how many elements carry exactly this key
-  // ---- ties on the score: the lowest rows win (stable sort); select the want-th smallest row
-  //      (skipped when every tied element is taken, the usual case) ----
+  // ---- ties on the score: select the want-th smallest tied row (skipped when every tied element
+  //      is taken, the usual case) ----
   unsigned Irow = 0xffffffffu;  // ties with row <= Irow are taken
-  if (want < n_eq) {
-    unsigned ipre = 0, imask = 0;
-    int iwant = want;
-    auto ikey = [&](int i) { return skey(i) == Tkey ? (unsigned)i : 0xffffffffu; };
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      int below, bucket;
-      // rows that do not carry Tkey map to 0xffffffff and never match a prefix below 2^24 rows
-      const int d = radix_digit(count, shift, imask, ipre, iwant, hist, &below, &bucket, ikey);
-      iwant -= below;
-      ipre |= (unsigned)d << shift;
-      imask |= 255u << shift;
-    }
-    Irow = ipre;
-  }
+  if (want < n_eq) Irow = select_tie_row(count, want, Tkey, hist, skey);
   // ---- unordered compaction of the selected rows into composite keys, then sort ----
   if (tid == 0) *ncand = 0;
   for (int i = tid; i < P2; i += T) keys[i] = ~0ull;

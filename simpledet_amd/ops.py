@@ -24,6 +24,15 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _workspace(dev, wsb, workspace):
+    """the caller's uint8 workspace when it holds the wsb bytes the call needs, a fresh one when there is none"""
+    if workspace is None:
+        return torch.empty(wsb, device=dev, dtype=torch.uint8)
+    if workspace.numel() < wsb:
+        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    return workspace
+
+
 def _chk(t, name, dtype=torch.float32, ndim=None):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
@@ -901,10 +910,7 @@ def retina_anchor_target(im_info, gt_bbox, param, layout=1, workspace=None):
     fg = torch.empty((B,), device=dev, dtype=torch.float32)
     lib().cdll.sd_retina_target_workspace_bytes.restype = ctypes.c_size_t
     wsb = int(lib().cdll.sd_retina_target_workspace_bytes(ctypes.byref(param), B, M))
-    if workspace is None:
-        workspace = torch.empty(wsb, device=dev, dtype=torch.uint8)
-    elif workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    workspace = _workspace(dev, wsb, workspace)
     lib().call("sd_retina_anchor_target", _p(im_info), _p(gt_bbox), B, M, ctypes.byref(param), _p(cls),
                _p(tgt), _p(wgt), _p(fg), int(layout), _p(workspace), ctypes.c_size_t(workspace.numel()),
                _stream())
@@ -921,15 +927,6 @@ NORMALIZATION = {"null": 0, "batch": 1, "valid": 2}
 def focal_loss_workspace_bytes():
     lib().cdll.sd_focal_loss_workspace_bytes.restype = ctypes.c_size_t
     return int(lib().cdll.sd_focal_loss_workspace_bytes())
-
-
-def _loss_ws(dev, workspace):
-    wsb = focal_loss_workspace_bytes()
-    if workspace is None:
-        return torch.empty(wsb, device=dev, dtype=torch.uint8)
-    if workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
-    return workspace
 
 
 def focal_loss_forward(data, out=None):
@@ -968,7 +965,7 @@ def focal_loss_backward(out, label, ograd=None, *, alpha=0.25, gamma=2.0, grad_s
         _chk(gdata, "gdata", ndim=3)
         if gdata.shape != out.shape:
             raise ValueError("gdata must have the shape of out")
-    ws = _loss_ws(out.device, workspace)
+    ws = _workspace(out.device, focal_loss_workspace_bytes(), workspace)
     lib().call("sd_focal_loss_bwd", _p(out), _p(label), _p(ograd), _p(gdata), B, nbox, nclass,
                float(alpha), float(gamma), float(grad_scale), NORMALIZATION[normalization], _p(ws),
                ctypes.c_size_t(ws.numel()), _stream())
@@ -989,7 +986,7 @@ def bbox_norm_backward(gout, label, gdata=None, workspace=None):
         _chk(gdata, "gdata")
         if gdata.shape != gout.shape:
             raise ValueError("gdata must have the shape of gout")
-    ws = _loss_ws(gout.device, workspace)
+    ws = _workspace(gout.device, focal_loss_workspace_bytes(), workspace)
     lib().call("sd_bbox_norm_bwd", _p(gout), _p(label), _p(gdata), B,
                ctypes.c_long(gout.numel() // B if B else 0), ctypes.c_long(label.numel() // B if B else 0),
                _p(ws), ctypes.c_size_t(ws.numel()), _stream())
@@ -1018,15 +1015,6 @@ def _gn_dims(x, gamma, num_group):
     return N, C, (x.numel() // (N * C) if N * C else 0), G
 
 
-def _gn_ws(x, dims, workspace):
-    wsb = group_norm_workspace_bytes(*dims)
-    if workspace is None:
-        return torch.empty(wsb, device=x.device, dtype=torch.uint8)
-    if workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
-    return workspace
-
-
 def _gn_out(t, name, like=None, shape=None, at_least=None):
     """an output the caller passed: float32, on the device, contiguous, of the given shape or size"""
     _chk(t, name)
@@ -1050,7 +1038,7 @@ def group_norm_forward(x, gamma, beta, num_group=32, eps=1e-5, y=None, mu=None, 
     mu = torch.empty((N, G), device=x.device, dtype=torch.float32) if mu is None else _gn_out(mu, "mu", at_least=N * G)
     rsig = (torch.empty((N, G), device=x.device, dtype=torch.float32) if rsig is None
             else _gn_out(rsig, "rsig", at_least=N * G))
-    ws = _gn_ws(x, dims, workspace)
+    ws = _workspace(x.device, group_norm_workspace_bytes(*dims), workspace)
     lib().call("sd_group_norm_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(mu), _p(rsig), N, C, ctypes.c_long(HxW), G,
                float(eps), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return y, mu, rsig
@@ -1074,7 +1062,7 @@ def group_norm_backward(dy, x, mu, rsig, gamma, num_group=32, dx=None, dgamma=No
             dbeta.zero_()
     elif dgamma is not None or dbeta is not None:
         raise ValueError("param_grads=False takes no dgamma / dbeta")
-    ws = _gn_ws(x, dims, workspace)
+    ws = _workspace(x.device, group_norm_workspace_bytes(*dims), workspace)
     lib().call("sd_group_norm_bwd", _p(dy), _p(x), _p(mu), _p(rsig), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), N, C,
                ctypes.c_long(HxW), G, _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return dx, dgamma, dbeta
@@ -1119,14 +1107,6 @@ def mask_loss_workspace_bytes(R, K, P):
     return int(lib().cdll.sd_mask_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
 
 
-def _ce_ws(dev, wsb, workspace):
-    if workspace is None:
-        return torch.empty(wsb, device=dev, dtype=torch.uint8)
-    if workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
-    return workspace
-
-
 def _ce_rows(data, label):
     """(n, k) of the operator: n = shape[0], k = everything else (sigmoid_cross_entropy-inl.h:80-84)"""
     _chk(data, "data")
@@ -1166,7 +1146,7 @@ def sigmoid_cross_entropy_forward(data, label, *, full=False, out=None, loss=Non
         loss_sum.zero_()
         count_sum.fill_(1e-5)
         return (out, loss, loss_sum, count, count_sum) if loss is not None else (out, loss_sum, count_sum)
-    ws = _ce_ws(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
+    ws = _workspace(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
     lib().call("sd_sigmoid_ce_fwd", _p(data), _p(label), _p(out), _p(loss), _p(loss_sum), _p(count), _p(count_sum),
                ctypes.c_long(n), ctypes.c_long(k), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     if loss is not None:
@@ -1188,7 +1168,7 @@ def sigmoid_cross_entropy_backward(data, label, grad_scale=1.0, *, d_data=None, 
     if n * k == 0:
         count_sum.fill_(1e-5)
         return d_data, count_sum
-    ws = _ce_ws(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
+    ws = _workspace(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
     lib().call("sd_sigmoid_ce_bwd", _p(data), _p(label), _p(d_data), _p(count), _p(count_sum), ctypes.c_long(n),
                ctypes.c_long(k), float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return d_data, count_sum
@@ -1221,7 +1201,7 @@ def mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, workspac
         out.zero_()
         count_sum.fill_(1e-5)
         return out, count_sum
-    ws = _ce_ws(dev, mask_loss_workspace_bytes(R, K, P), workspace)
+    ws = _workspace(dev, mask_loss_workspace_bytes(R, K, P), workspace)
     lib().call("sd_mask_loss_fwd", _p(logits), _p(cls), _p(target), _p(out), _p(count_sum), R, K, ctypes.c_long(P),
                _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return out, count_sum
@@ -1232,7 +1212,7 @@ def mask_loss_backward(logits, cls, target, grad_scale=1.0, *, d_logits=None, wo
     that are not selected and in ignored RoIs, the SigmoidCrossEntropy gradient in plane int(cls[r])."""
     R, K, P = _mask_dims(logits, cls, target)
     d_logits = _ce_out(d_logits, "d_logits", R * K * P, logits.device, logits.shape)
-    ws = _ce_ws(logits.device, mask_loss_workspace_bytes(R, K, P), workspace)
+    ws = _workspace(logits.device, mask_loss_workspace_bytes(R, K, P), workspace)
     lib().call("sd_mask_loss_bwd", _p(logits), _p(cls), _p(target), _p(d_logits), R, K, ctypes.c_long(P),
                float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return d_logits
@@ -1264,7 +1244,7 @@ def msrcnn_mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, p
         count_sum.fill_(1e-5)
         prob.zero_()
         return out, count_sum, prob
-    ws = _ce_ws(dev, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
+    ws = _workspace(dev, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
     lib().call("sd_msrcnn_mask_loss_fwd", _p(logits), _p(cls), _p(target), _p(out), _p(count_sum), _p(prob), R, K,
                ctypes.c_long(P), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return out, count_sum, prob
@@ -1280,7 +1260,7 @@ def msrcnn_mask_loss_backward(logits, cls, target, d_prob=None, grad_scale=1.0, 
         if d_prob.numel() != R * P:
             raise ValueError("d_prob needs %d floats, got %d" % (R * P, d_prob.numel()))
     d_logits = _ce_out(d_logits, "d_logits", R * K * P, logits.device, logits.shape)
-    ws = _ce_ws(logits.device, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
+    ws = _workspace(logits.device, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
     lib().call("sd_msrcnn_mask_loss_bwd", _p(logits), _p(cls), _p(target), _p(d_prob), _p(d_logits), R, K,
                ctypes.c_long(P), float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
     return d_logits
@@ -1323,7 +1303,7 @@ def maskiou_loss_forward(iou_pred, prob, target, ratio, cls, *, iou_target=None,
         for t in (iou_target, weight, loss, weight_sum):
             t.zero_()
         return iou_target, weight, loss, weight_sum
-    ws = _ce_ws(dev, maskiou_loss_workspace_bytes(R, K, P), workspace)
+    ws = _workspace(dev, maskiou_loss_workspace_bytes(R, K, P), workspace)
     lib().call("sd_maskiou_loss_fwd", _p(iou_pred), _p(prob), _p(target), _p(ratio), _p(cls), _p(iou_target),
                _p(weight), _p(loss), _p(weight_sum), R, K, ctypes.c_long(P), _p(ws), ctypes.c_size_t(ws.numel()),
                _stream())
@@ -1394,7 +1374,7 @@ def quantization_int8_forward(data, minmax, state, *, is_weight, is_train=True, 
     n = data.numel()
     if n == 0:
         return out
-    ws = _ce_ws(data.device, quant_int8_workspace_bytes(n), workspace)
+    ws = _workspace(data.device, quant_int8_workspace_bytes(n), workspace)
     lib().call("sd_quant_int8_fwd", _p(data), _p(out), _p(minmax), _p(state), ctypes.c_long(n), int(bool(is_weight)),
                int(bool(is_train)), int(bool(fix_act_scale)), float(ema_decay), _p(ws), ctypes.c_size_t(ws.numel()),
                _stream())
@@ -1469,7 +1449,7 @@ def quantization_int8_weights_forward(datas, minmaxes, states, *, is_train=True,
     n_total = sum(int(d.numel()) for d in datas)
     if T == 0 or n_total == 0:
         return outs
-    ws = _ce_ws(table.device, quant_int8_weights_workspace_bytes(T, n_total), workspace)
+    ws = _workspace(table.device, quant_int8_weights_workspace_bytes(T, n_total), workspace)
     row = [ctypes.c_void_p(table[i].data_ptr()) for i in range(5)]
     lib().call("sd_quant_int8_weights_fwd", row[0], row[1], row[2], row[3], row[4], T, ctypes.c_long(n_total),
                int(bool(is_train)), int(bool(fix_act_scale)), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
@@ -1570,7 +1550,7 @@ def fcos_target(gt_bbox, im_info, data_size, strides, num_classifier, *, ignore_
         cls_dense = _fcos_out(cls_dense, "cls_dense", (N, K * HW), dev)
     if N * HW == 0:       # the entry point writes nothing: the normalisers of an empty problem are zero
         state.zero_()
-    ws = _ce_ws(dev, fcos_target_workspace_bytes(N, HW), workspace)
+    ws = _workspace(dev, fcos_target_workspace_bytes(N, HW), workspace)
     lib().call("sd_fcos_target", _p(gt_bbox), _p(im_info), _p(centerness), _p(offset), _p(cls_id), _p(cls_dense),
                _p(state), N, M, K, int(data_size[0]), int(data_size[1]), _iarr(strides),
                None if stage_lower is None else _farr(stage_lower), None if stage_upper is None else _farr(stage_upper),
@@ -1616,7 +1596,7 @@ def fcos_loss_forward(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25,
     losses = _fcos_out(losses, "losses", (3,), dev)
     if N * K * HW == 0:
         return losses.zero_()
-    ws = _ce_ws(dev, fcos_loss_workspace_bytes(N, K, HW), workspace)
+    ws = _workspace(dev, fcos_loss_workspace_bytes(N, K, HW), workspace)
     lib().call("sd_fcos_loss_fwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), hws, len(cls_logits),
                _p(targets.centerness), _p(targets.offset), _p(targets.cls_id), _p(targets.state), _p(losses), N, K,
                float(alpha), float(gamma), float(ignore_offset), float(ignore_label), _p(ws),
@@ -1745,7 +1725,7 @@ def reppoints_target(pts_init, gt_bbox, strides, *, transform="moment", moment_t
     state = _fcos_out(state, "state", (4,), dev, torch.int32)
     if N * P == 0:        # the entry point writes nothing: no label, and the denominators are 0 + 1
         state.copy_(torch.tensor([0, 0, 0x3f800000, 0x3f800000], dtype=torch.int32))
-    ws = _ce_ws(dev, reppoints_target_workspace_bytes(N, M, P), workspace)
+    ws = _workspace(dev, reppoints_target_workspace_bytes(N, M, P), workspace)
     lib().call("sd_reppoints_target", _parr(pts_init), Hs, Ws, st, len(pts_init), _p(gt_bbox), _p(moment_transfer),
                _p(label_init), _p(gt_init), _p(label_refine), _p(gt_refine), _p(state), N, M, K, tr,
                float(target_scale), int(num_pos), float(pos_iou_thr), float(neg_iou_thr), float(min_pos_iou), _p(ws),
@@ -1803,7 +1783,7 @@ def reppoints_box_loss_backward(pts_init, pts_refine, targets, strides, *, trans
     d_moment_transfer = _fcos_out(d_moment_transfer, "d_moment_transfer", (2,), dev)
     if N * P == 0:
         return outs[0], outs[1], d_moment_transfer if req == "add" else d_moment_transfer.zero_()
-    ws = _ce_ws(dev, reppoints_box_loss_workspace_bytes(N, P), workspace)
+    ws = _workspace(dev, reppoints_box_loss_workspace_bytes(N, P), workspace)
     lib().call("sd_reppoints_box_loss_bwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init),
                _p(moment_transfer), _p(targets.label_init), _p(targets.gt_init), _p(targets.label_refine),
                _p(targets.gt_refine), _p(targets.state), _parr(outs[0]), _parr(outs[1]), _p(d_moment_transfer), N, K,
@@ -1895,7 +1875,7 @@ def fcos_decode(cls_list, ctr_list, off_list, im_info, strides, top_n, pre_nms_t
     if return_stage or stage is not None:
         stage = _fcos_out(stage, "stage", (N, R, 6), dev)
     hws = [h * w for h, w in zip(Hs, Ws)]
-    ws = _ce_ws(dev, fcos_decode_workspace_bytes(N, C, hws, top_n), workspace)
+    ws = _workspace(dev, fcos_decode_workspace_bytes(N, C, hws, top_n), workspace)
     lib().call("sd_fcos_decode", _parr(cls_list), _parr(ctr_list), _parr(off_list), _p(im_info), _iarr(Hs), _iarr(Ws),
                _iarr(strides), L, N, C, top_n, float(pre_nms_thresh), int(bool(input_logits)), _p(bbox), _p(score),
                _p(cls_id), _p(stage), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
@@ -1954,7 +1934,7 @@ def reppoints_decode(cls_list, pts_refine_list, im_info, strides, ks, *, transfo
     dev = im_info.device
     cls_score = _fcos_out(cls_score, "cls_score", (N, R, C + 1), dev)
     bbox_xyxy = _fcos_out(bbox_xyxy, "bbox_xyxy", (N, R, 4), dev)
-    ws = _ce_ws(dev, reppoints_decode_workspace_bytes(N, C, hws, ks), workspace)
+    ws = _workspace(dev, reppoints_decode_workspace_bytes(N, C, hws, ks), workspace)
     lib().call("sd_reppoints_decode", _parr(cls_list), _parr(pts_refine_list), _p(im_info), _p(moment_transfer),
                _iarr(Hs), _iarr(Ws), _iarr(strides), _iarr(ks), L, N, C, K2 // 2, tr, int(bool(input_logits)),
                _p(cls_score), _p(bbox_xyxy), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
@@ -2242,12 +2222,7 @@ def _proposal_v12_args(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n, rpn_post
 def _proposal_v12_ws(name, B, A, H, W, pre, device, workspace):
     fn = getattr(lib().cdll, name)
     fn.restype = ctypes.c_size_t
-    wsb = int(fn(B, A, H, W, int(pre)))
-    if workspace is None:
-        workspace = torch.empty(wsb, device=device, dtype=torch.uint8)
-    elif workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
-    return workspace
+    return _workspace(device, int(fn(B, A, H, W, int(pre))), workspace)
 
 
 def proposal_v2(cls_prob, bbox_pred, im_info, valid_ranges, rpn_pre_nms_top_n=6000,
@@ -2343,11 +2318,7 @@ def gen_proposal_retina(cls_prob, bbox_pred, im_info, anchors, *, num_anchors, r
     oc = K + 1 if output_one_hot else 1
     out = torch.empty((B, top_n, 4), device=cls_prob.device, dtype=torch.float32)
     score = torch.empty((B, top_n, oc), device=cls_prob.device, dtype=torch.float32)
-    wsb = gen_proposal_retina_workspace_bytes(B, AK, H, W)
-    if workspace is None:
-        workspace = torch.empty(wsb, device=cls_prob.device, dtype=torch.uint8)
-    elif workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    workspace = _workspace(cls_prob.device, gen_proposal_retina_workspace_bytes(B, AK, H, W), workspace)
     lib().call("sd_gen_proposal_retina", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(anchors),
                _p(out), _p(score), B, AK, H, W, A, top_n, int(rpn_min_size), float(thresh),
                _farr(anchor_mean), _farr(anchor_std), int(bool(iou_loss)), int(bool(output_one_hot)),
@@ -2463,10 +2434,7 @@ def bbox_post_processing(cls_score, bbox_xyxy, max_det_per_image=100, min_det_sc
         if tuple(t.shape) != (B, top, last):
             raise ValueError("%s must be %s" % (name, (B, top, last)))
     wsb = bbox_post_processing_workspace_bytes(B, R, K, Kb, top) if K >= 1 and Kb in (1, K) else 16
-    if workspace is None:
-        workspace = torch.empty(wsb, device=cls_score.device, dtype=torch.uint8)
-    elif workspace.numel() < wsb:
-        raise ValueError("workspace needs %d bytes, got %d" % (wsb, workspace.numel()))
+    workspace = _workspace(cls_score.device, wsb, workspace)
     lib().call("sd_bbox_post_processing", _p(cls_score), _p(bbox_xyxy), B, R, K, Kb,
                float(min_det_score), float(nms_thr), top, _p(ps), _p(pb), _p(pc), _p(workspace),
                ctypes.c_size_t(workspace.numel()), _stream())
