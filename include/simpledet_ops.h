@@ -67,7 +67,7 @@ const char* sd_last_dispatch(void);
  * So were the sd_fcos_* entry points (FCOS targets and losses; sd_fcos_decode and sd_fcos_sigmoid, the test-time
  * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*, and
  * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head), and sd_reppoints_decode (the
- * RepPoints test-time decode).
+ * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1015,6 +1015,84 @@ int sd_maskiou_loss_fwd(const float* iou_pred, const float* prob, const float* t
                         int K, long P, void* workspace, size_t workspace_bytes, void* stream);
 int sd_maskiou_loss_bwd(const float* iou_pred, const float* cls, const float* iou_target, const float* weight,
                         const float* weight_sum, float* d_iou_pred, int R, int K, float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The CrowdHuman double-prediction head's training side (models/crowdhuman), fp32.
+ *
+ * sd_crowdhuman_target: RoI sampling and box targets.  mode 0 replaces the Python CustomOp `bbox_target`
+ *   (models/crowdhuman/bbox_target.py: _sample_proposal :12-81, _expand_bbox_targets :84-104, forward :121-178),
+ *   mode 1 `doublebbox_target` (models/crowdhuman/bbox_sec_target.py: _sample_proposal :13-120,
+ *   _expand_bbox_targets :123-143, forward :159-224); IoU operator_py/cython/bbox.pyx:31-72, encoding
+ *   operator_py/detectron_bbox_utils.py:192-223.  Both copy to the host, sample with np.random.choice and copy back.
+ *   proposal (B,P,4) DEVICE, rows with y2 == 0 padding; gt_bbox (B,M,5) DEVICE [x1,y1,x2,y2,class], class -1
+ *   padding, class -2 "ignore".  With add_gt_to_proposal every non-padding gt box (the ignore rows included) joins
+ *   the candidates behind the valid proposals, in order.
+ *   mt_state: the DEVICE int32[625] of sd_rpn_anchor_target, advanced in place exactly as numpy advances it, images in
+ *     order: per image one permutation(n) for the foreground list and one for the background list, each only when
+ *     its list is not empty (n == 1 draws nothing; n >= 2 draws whatever the number of rows taken, also 0: checked by
+ *     running numpy).  The first `size` entries of a permutation are the rows, foreground first, then background.
+ *   Matching.  mode 0: the ignore rows are dropped, first maximum over the rest, the label is that gt's class value.
+ *     mode 1: the ignore rows stay in place with class -1; for cid = 1 .. num_reg_class - 1 with at least one gt:
+ *     first maximum, and the first maximum after the winner is set to -1 (a class with one gt: second IoU -1, second
+ *     box = that gt); a class takes over where its maximum is strictly greater than the running one, which starts
+ *     at 0 (IoU 0 leaves class 0, gt row 0, second IoU 0).
+ *   Sampling.  fg quota = round-half-even(fg_fraction * image_rois); fg: max >= fg_thresh; bg: bg_thresh_lo <= max <
+ *     bg_thresh_hi.  The thresholds compare as numpy 2 compares them: in float32 in mode 0 (a float32 array against a
+ *     python float), in double in mode 1 (the running maxima are float64 arrays).
+ *   Outputs, S = image_rois: sampled_proposal (B,S,4), bbox_cls (B,S) (background rows 0), bbox_target /
+ *     bbox_target_weight (B,S,4*num_reg_class): columns 4c .. 4c+3 of class c > 0 (c = label > 0 when num_reg_class
+ *     == 2) hold the float32 encoding against the matched gt / ones, everything else +0.0.  mode 1 also
+ *     bbox_sec_cls (the assigned class, 0 where the second IoU < fg_thresh), bbox_sec_target / _weight against the
+ *     second gt; in mode 0 the three pointers are not used and may be NULL.  count (B) int32: rows filled; rows >=
+ *     count[b] are +0.0 in every output (-1: the generator stalled, see csrc/mt19937.h; all rows are zero).
+ *     The dx / dy columns reproduce numpy bit for bit; dw / dh go through logf, numpy's float32 log is not correctly
+ *     rounded either: they agree to the last bits, not bit for bit.
+ *   Preconditions the reference enforces by raising, NOT emulated here: at least one non-padding gt per image (mode
+ *     0: one non-ignore gt; without one every candidate gets IoU 0, label 0), classes < num_reg_class (a larger one
+ *     never matches in mode 1 and writes no target columns in mode 0), and every image filling all image_rois rows
+ *     (its np.array stacking fails otherwise; here count reports the short image).
+ *   Limits: P + M <= 4096 rows per image, 1 <= M <= 1024, image_rois <= 1024, 2 <= num_reg_class <= 1024.
+ *   Four kernels, no memset node, no host synchronisation, graph-capturable, integer arithmetic only between
+ *   workgroups; the workspace needs no clearing.
+ * sd_emd_loss_fwd / _bwd: DoublePredBboxHead.emd_loss (models/crowdhuman/builder.py:254-306) with the CustomOp
+ *   `softmax_entropy` (softmax_entropy_op.py:8-31) inside it.  R rows, K classes, D = 4 * num_reg_class columns.
+ *     ce(x, y) = -logf(softmax(x)[(int)y] + 1e-10f), 0 when y names no column;  sl1 = MXNet's smooth_l1 with
+ *     sigma = smooth_l1_scalar (0.5 sigma^2 v^2 for |v| <= 1 / sigma^2, |v| - 0.5 / sigma^2 beyond)
+ *     L1 = ce(x1, y1) + ce(x2, y2) + sum_d (w1 sl1(d1 - t1) + w2 sl1(d2 - t2))
+ *     L2 = ce(x1, y2) + ce(x2, y1) + sum_d (w2 sl1(d1 - t2) + w1 sl1(d2 - t1))
+ *     loss[0] = sum_r min(L1, L2) / R;  pairing[r] (optional, may be NULL) = 1 when L1 <= L2, else 2 (a tie goes to
+ *     the first pairing, as mx.sym.minimum's backward sends it to the left operand).
+ *   The backward writes all four gradients once, only the winning pairing contributing, scaled by grad_scale / R:
+ *     (softmax(x) - onehot(y)) for the two logits, w * sl1'(d - t) for the two deltas, with the labels / targets /
+ *     weights the winning pairing gave each head.  It recomputes the pairing with the forward's code (equal bits).
+ *   One launch each; the forward's sum has a fixed order (no float atomics): repeated calls and graph replay give
+ *   equal bits; 4-byte alignment suffices and changes nothing.  R * max(K, D) <= 2^31 - 1 (SD_ERR_UNSUPPORTED beyond);
+ *   R == 0 succeeds without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int num_reg_class;
+  int add_gt_to_proposal;
+  int image_rois;
+  double fg_fraction, fg_thresh, bg_thresh_hi, bg_thresh_lo;
+  double bbox_target_std[4];
+} sd_crowdhuman_target_param;
+size_t sd_crowdhuman_target_workspace_bytes(int B, int P, int M);
+int sd_crowdhuman_target(const float* proposal, const float* gt_bbox, int B, int P, int M, int mode,
+                         const sd_crowdhuman_target_param* param_host, int32_t* mt_state,
+                         float* sampled_proposal, float* bbox_cls, float* bbox_target, float* bbox_target_weight,
+                         float* bbox_sec_cls, float* bbox_sec_target, float* bbox_sec_target_weight, int32_t* count,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int sd_emd_loss_fwd(const float* cls_logit, const float* cls_sec_logit, const float* cls_label,
+                    const float* cls_sec_label, const float* bbox_delta, const float* bbox_sec_delta,
+                    const float* bbox_target, const float* bbox_sec_target, const float* bbox_weight,
+                    const float* bbox_sec_weight, int R, int K, int D, float smooth_l1_scalar, float* loss,
+                    int32_t* pairing, void* stream);
+int sd_emd_loss_bwd(const float* cls_logit, const float* cls_sec_logit, const float* cls_label,
+                    const float* cls_sec_label, const float* bbox_delta, const float* bbox_sec_delta,
+                    const float* bbox_target, const float* bbox_sec_target, const float* bbox_weight,
+                    const float* bbox_sec_weight, int R, int K, int D, float smooth_l1_scalar, float grad_scale,
+                    float* d_cls_logit, float* d_cls_sec_logit, float* d_bbox_delta, float* d_bbox_sec_delta,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_Quantization_int8  (mx.sym.contrib.Quantization_int8; utils/graph_optimize.py:attach_quantize_node puts

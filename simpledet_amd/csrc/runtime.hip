@@ -58,10 +58,12 @@ Knob g_knobs[] = {
     {"dcn_coord", 0, false},             // 1 LDS-plane offset gradient (default), 0 per-lane gathers
     {"dcn_fused", 0, false},             // 1 (default): the col-free entry points sample inside the GEMM; 0: im2col + GEMM
     {"dcn_fused_tile", 0, false},        // pixels per tile of the fused kernels (1..96), 0 = balanced over the CUs (default): partial-tile tests
+    {"crowdhuman_front", 0, false},      // 0 (default): ch_finish traces each front entry back through the swaps; 1: LDS replay
 #ifdef SD_PROFILING
     // ---- profiling build only (tools/libsimpledet_ops_hip_prof.so): results are WRONG when != 0 ----
     {"roi_align_fwd_ablate", 0, false},
     {"roi_pool_fwd_ablate", 0, false},
+    {"crowdhuman_target_stop", 0, false}, // k in 1..3: sd_crowdhuman_target launches its first k kernels only
     {"roi_align_bwd_ablate", 0, false},
     {"roi_align_dbg_lo", 0, false},      // device buffer for per-wave phase clocks
     {"roi_align_dbg_hi", 0, false},

@@ -2707,14 +2707,171 @@ def _build_ops(mx):
             return []
 
     ops["reppoints_decode"] = (RepPointsDecodeProp, None)
+
+    # ---- the CrowdHuman double-prediction head (registered only by install(..., crowdhuman=True)):
+    #      bbox_target:       proposal, gt_bbox -> sampled_proposal, bbox_cls, bbox_target, bbox_target_weight
+    #      doublebbox_target: ... and bbox_sec_cls, bbox_sec_target, bbox_sec_target_weight
+    #      emd_loss:          the two logits, labels, deltas, targets and weights -> output (1,) ----
+    class CrowdHumanTarget(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            from . import ops as sd_ops
+            _no_add(req)
+            prop_, gt = in_data[:2]
+            _wait(prop_, gt)
+            g = self.g
+            B, P, M = int(prop_.shape[0]), int(prop_.shape[1]), int(gt.shape[1])
+            prm = sd_ops.CrowdHumanTargetParam()
+            prm.num_reg_class, prm.add_gt_to_proposal, prm.image_rois = g["num_class"], int(g["add_gt_to_proposal"]), \
+                g["image_rois"]
+            prm.fg_fraction, prm.fg_thresh = g["fg_fraction"], g["fg_thresh"]
+            prm.bg_thresh_hi, prm.bg_thresh_lo = g["bg_thresh_hi"], g["bg_thresh_lo"]
+            for i, v in enumerate(g["bbox_target_std"]):
+                prm.bbox_target_std[i] = v
+            key = "mt19937:" + str(prop_.context)
+            if key not in _state["rng"]:
+                # numpy's global RandomState, which the reference's np.random.choice draws from: one stream per
+                # device, taken over where the process's generator stands at the first call
+                import numpy as np
+                st = np.random.get_state()
+                words = [int(k) - (1 << 32) if int(k) >= (1 << 31) else int(k) for k in st[1]] + [int(st[2])]
+                _state["rng"][key] = _state["mx"].nd.array(words, ctx=prop_.context, dtype="int32")
+            rng = _state["rng"][key]
+            lib().cdll.sd_crowdhuman_target_workspace_bytes.restype = ctypes.c_size_t
+            wsb = lib().cdll.sd_crowdhuman_target_workspace_bytes(B, P, M)
+            ws = _scratch(prop_, wsb)
+            count = _scratch(prop_, 4 * B)     # rows filled per image; the reference has no such output
+            outs = [_ptr(o) for o in out_data] + [None] * (7 - len(out_data))
+            _call("sd_crowdhuman_target", _ptr(prop_), _ptr(gt), B, P, M, g["mode"], ctypes.byref(prm), _ptr(rng), *outs,
+                  _ptr(count), _ptr(ws), ctypes.c_size_t(wsb), None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(req)):       # bbox_target.py:180-182: zeros
+                self.assign(in_grad[i], req[i], 0)
+
+    def _crowdhuman_target_prop(mode):
+        outputs = ["sampled_proposal", "bbox_cls", "bbox_target", "bbox_target_weight"]
+        if mode == 1:
+            outputs += ["bbox_sec_cls", "bbox_sec_target", "bbox_sec_target_weight"]
+
+        class CrowdHumanTargetProp(CustomOpProp):
+            def __init__(self, num_class, add_gt_to_proposal, image_rois, fg_fraction, fg_thresh, bg_thresh_hi,
+                         bg_thresh_lo, bbox_target_std, xywh="True"):
+                super().__init__(need_top_grad=False)
+                # (xywh: the reference's operator prints it and never reads it, bbox_target.py:12-81)
+                self.g = dict(mode=mode, num_class=int(num_class), add_gt_to_proposal=_bool(add_gt_to_proposal),
+                              image_rois=int(image_rois), fg_fraction=float(fg_fraction), fg_thresh=float(fg_thresh),
+                              bg_thresh_hi=float(bg_thresh_hi), bg_thresh_lo=float(bg_thresh_lo),
+                              bbox_target_std=_tuple(bbox_target_std, 4))
+                if len(self.g["bbox_target_std"]) != 4 or not 1 <= self.g["image_rois"] <= 1024:
+                    raise ValueError("crowdhuman target: bbox_target_std has 4 entries and image_rois is in [1, 1024]")
+
+            def list_arguments(self):
+                return ["proposal", "gt_bbox"]
+
+            def list_outputs(self):
+                return list(outputs)
+
+            def infer_shape(self, in_shape):
+                p, gt = tuple(in_shape[0]), tuple(in_shape[1])
+                if len(p) != 3 or p[2] != 4 or len(gt) != 3 or gt[2] != 5 or gt[0] != p[0]:
+                    raise ValueError("crowdhuman target: proposal (B, P, 4) and gt_bbox (B, M, 5), got %s and %s" % (p, gt))
+                if gt[1] < 1 or gt[1] > 1024 or p[1] + gt[1] > 4096:
+                    raise ValueError("crowdhuman target: 1 <= M <= 1024 and P + M <= 4096, got P = %d, M = %d" % (p[1], gt[1]))
+                B, S, W = p[0], self.g["image_rois"], 4 * self.g["num_class"]
+                outs = [(B, S, 4), (B, S), (B, S, W), (B, S, W)]
+                return [p, gt], outs + ([(B, S), (B, S, W), (B, S, W)] if mode == 1 else []), []
+
+            def create_operator(self, ctx, shapes, dtypes):
+                return CrowdHumanTarget(self.g)
+
+            def declare_backward_dependency(self, out_grad, in_data, out_data):
+                return []
+
+        return CrowdHumanTargetProp
+
+    class EmdLoss(CustomOp):
+        def __init__(self, g):
+            super().__init__()
+            self.g = g
+
+        @staticmethod
+        def _dims(in_data):
+            R, K = int(in_data[0].shape[0]), int(in_data[0].shape[1])
+            return R, K, int(in_data[4].shape[1])
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data[:10])
+            R, K, D = self._dims(in_data)
+            _call("sd_emd_loss_fwd", *[_ptr(t) for t in in_data[:10]], R, K, D, float(self.g["smooth_l1_scalar"]),
+                  _ptr(out_data[0]), None, None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            # MakeLoss: the head gradient is not read.  Labels, targets and weights get zeros (the reference's target
+            # operator blocks the gradient)
+            grads = (0, 1, 4, 5)          # cls_logit, cls_sec_logit, bbox_delta, bbox_sec_delta
+            _require_write([req[i] for i in grads], ["emd_loss gradient"] * 4)
+            _wait(*in_data[:10])
+            R, K, D = self._dims(in_data)
+            if any(_req(req[i]) == REQ["null"] for i in grads):
+                raise RuntimeError("emd_loss writes all four gradients (req='null' on one of them)")
+            _call("sd_emd_loss_bwd", *[_ptr(t) for t in in_data[:10]], R, K, D, float(self.g["smooth_l1_scalar"]),
+                  float(self.g["grad_scale"]), *[_ptr(in_grad[i]) for i in grads], None)
+            for i in (2, 3, 6, 7, 8, 9):
+                if len(req) > i:
+                    self.assign(in_grad[i], req[i], 0)
+            _sync()
+
+    class EmdLossProp(CustomOpProp):
+        def __init__(self, smooth_l1_scalar="1.0", grad_scale="1.0"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(smooth_l1_scalar=float(smooth_l1_scalar), grad_scale=float(grad_scale))
+            if not self.g["smooth_l1_scalar"] > 0:
+                raise ValueError("emd_loss: smooth_l1_scalar must be positive")
+
+        def list_arguments(self):
+            return ["cls_logit", "cls_sec_logit", "cls_label", "cls_sec_label", "bbox_delta", "bbox_sec_delta",
+                    "bbox_target", "bbox_sec_target", "bbox_weight", "bbox_sec_weight"]
+
+        def list_outputs(self):
+            return ["output"]
+
+        def infer_shape(self, in_shape):
+            x, d = tuple(in_shape[0]), tuple(in_shape[4])
+            if len(x) != 2 or len(d) != 2 or d[0] != x[0]:
+                raise ValueError("emd_loss: cls_logit (R, K) and bbox_delta (R, 4 K'), got %s and %s" % (x, d))
+            want = [x, x, (x[0],), (x[0],), d, d, d, d, d, d]
+            for i, (w, s) in enumerate(zip(want, in_shape)):
+                if s and _numel(tuple(s)) != _numel(w):
+                    raise ValueError("emd_loss: %s is %s, expected %s" % (self.list_arguments()[i], tuple(s), w))
+            return [tuple(s) if s else w for w, s in zip(want, in_shape)], [(1,)], []
+
+        def create_operator(self, ctx, shapes, dtypes):
+            return EmdLoss(self.g)
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return list(in_data)
+
+    ops["bbox_target"] = (_crowdhuman_target_prop(0), None)
+    ops["doublebbox_target"] = (_crowdhuman_target_prop(1), None)
+    ops["emd_loss"] = (EmdLossProp, None)
     return ops
 
 
 # ------------------------------------------------------------------------------- registration ----
 def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
              mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False, reppoints=False,
-             msrcnn=False, reppoints_decode=False):
+             msrcnn=False, reppoints_decode=False, crowdhuman=False):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
+    crowdhuman: also sd_bbox_target, sd_doublebbox_target and sd_emd_loss (opt-in: patch_crowdhuman puts them in place
+    of the Python CustomOps bbox_target / doublebbox_target and of the emd_loss subgraph, softmax_entropy included, of
+    the CrowdHuman train graphs);
     retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
     proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
     bbox_post: also BboxPostProcessing (opt-in: it replaces the reference's own CustomOp of Mask R-CNN's
@@ -2778,6 +2935,10 @@ def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss
         table.pop("MaskIoULoss")
     if not reppoints_decode:
         table.pop("reppoints_decode")
+    if not crowdhuman:
+        table.pop("bbox_target")
+        table.pop("doublebbox_target")
+        table.pop("emd_loss")
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2813,7 +2974,7 @@ def _namespaces(mx, ns):
 
 def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
             group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False,
-            reppoints=False, msrcnn=False, reppoints_decode=False):
+            reppoints=False, msrcnn=False, reppoints_decode=False, crowdhuman=False):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2905,11 +3066,21 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     because it changes which operators that graph holds, and independent of `reppoints` (which keeps meaning the
     train head alone).  A head with p.fp16 set or beyond the op's limits goes back to the reference's method; where the
     builder module is not importable nothing is rebound; `_state["fallbacks"]` says so in both cases.  A default
-    install() afterwards puts the reference's method back."""
+    install() afterwards puts the reference's method back.
+
+    `crowdhuman=True` also registers `sd_bbox_target`, `sd_doublebbox_target` and `sd_emd_loss` and rebinds, in
+    `models.crowdhuman.builder`, `FPNRpnHeadwithIgnore.get_sampled_proposal`, `DoublePredFPNRpnHead.get_sampled_proposal`
+    and `DoublePredBboxHead.emd_loss` (patch_crowdhuman) so that a CrowdHuman train graph holds ONE device target node
+    in place of the Python CustomOp (two device-to-host copies and numpy sampling in the middle of every step) and ONE
+    `sd_emd_loss` node per emd_loss call (two with refine_mode) in place of four softmax_entropy CustomOps, four
+    smooth_l1 and the arithmetic around them.  The targets draw from a device copy of numpy's global generator, taken
+    where it stands at the first call.  Where the builder module is not importable nothing is rebound and
+    `_state["fallbacks"]` says so; a default install() afterwards puts the reference's methods back.  The test-time
+    graph is not touched."""
     props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
                      group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
                      fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints, msrcnn=msrcnn,
-                     reppoints_decode=reppoints_decode)
+                     reppoints_decode=reppoints_decode, crowdhuman=crowdhuman)
     mx = _state["mx"]
     _state["proposal"] = bool(proposal)
     _state["retina_loss"] = bool(retina_loss)
@@ -3060,7 +3231,114 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
         if sys.modules.get(_REPPOINTS_BUILDER) is not None:
             unpatch_reppoints_decode(sys.modules[_REPPOINTS_BUILDER])
         _state["reppoints_decode_patched"] = False
+    if crowdhuman:
+        _state["crowdhuman_patched"] = patch_crowdhuman(mx=mx)
+        if not _state["crowdhuman_patched"]:
+            _state["fallbacks"].append(("emd_loss", None, "%s is not importable" % _CROWDHUMAN_BUILDER))
+    else:
+        import sys
+        if sys.modules.get(_CROWDHUMAN_BUILDER) is not None:
+            unpatch_crowdhuman(sys.modules[_CROWDHUMAN_BUILDER])
+        _state["crowdhuman_patched"] = False
     return props
+
+
+_CROWDHUMAN_BUILDER = "models.crowdhuman.builder"
+_CROWDHUMAN_METHODS = (("FPNRpnHeadwithIgnore", "get_sampled_proposal"), ("DoublePredFPNRpnHead", "get_sampled_proposal"),
+                       ("DoublePredBboxHead", "emd_loss"))
+
+
+def patch_crowdhuman(builder_module=None, mx=None):
+    """Route the CrowdHuman train head to the device ops WITHOUT editing the reference: rebinds, in
+    models/crowdhuman/builder.py,
+      FPNRpnHeadwithIgnore.get_sampled_proposal (:360-400) and DoublePredFPNRpnHead.get_sampled_proposal (:406-450) to
+        methods that read the same fields of `self.p`, call the reference's own `self.get_all_proposal` and emit
+        mx.sym.Custom(op_type='sd_bbox_target' / 'sd_doublebbox_target', name='subsample_proposal') with the
+        reference's parameters, followed by the reference's reshapes; the return tuples are the reference's;
+      DoublePredBboxHead.emd_loss (:254-306) to a method of the same signature that emits ONE
+        mx.sym.Custom(op_type='sd_emd_loss', name=prefix + 'cls_reg_loss') with smooth_l1_scalar =
+        p.regress_target.smooth_l1_scalar or 1.0 and grad_scale = 128.0 if p.fp16 else 1.0.
+    install(crowdhuman=True) calls this when the builder module is importable; returns True when the three methods
+    were rebound.  The originals are kept as `_sd_reference_<method>` (a second install() keeps the first ones); a
+    default install() afterwards puts them back (unpatch_crowdhuman)."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        import importlib
+        try:
+            module = importlib.import_module(_CROWDHUMAN_BUILDER)
+        except ModuleNotFoundError as e:
+            if e.name is None or not _CROWDHUMAN_BUILDER.startswith(e.name):
+                raise
+            return False
+        return patch_crowdhuman(module, mx)
+    classes = [getattr(builder_module, c, None) for c, _ in _CROWDHUMAN_METHODS]
+    if any(c is None for c in classes):
+        return False
+    originals = [c.__dict__.get("_sd_reference_" + m) or getattr(c, m) for c, (_, m) in zip(classes, _CROWDHUMAN_METHODS)]
+
+    def registered(name):
+        if name in (_state.get("table") or {}):
+            return True
+        _state.setdefault("fallbacks", []).append((name, None, "%s%s is not registered" % (_PREFIX, name)))
+        return False
+
+    def reshape(sym):
+        X = getattr(builder_module, "X", None)       # the builder's own `import mxnext as X`
+        return X.reshape(sym, (-3, -2)) if X is not None else mx.sym.reshape(sym, shape=(-3, -2))
+
+    def sampled(op, original):
+        def get_sampled_proposal(self, conv_fpn_feat, gt_bbox, im_info):
+            if not registered(op):
+                return original(self, conv_fpn_feat, gt_bbox, im_info)
+            p = self.p
+            (proposal, proposal_score) = self.get_all_proposal(conv_fpn_feat, im_info)
+            sym = mx.sym.Custom(
+                proposal=proposal, gt_bbox=gt_bbox, op_type=_PREFIX + op, name="subsample_proposal",
+                num_class=_param_str(p.bbox_target.num_reg_class),
+                add_gt_to_proposal=_param_str(not p.subsample_proposal.proposal_wo_gt),
+                image_rois=_param_str(p.subsample_proposal.image_roi),
+                fg_fraction=_param_str(p.subsample_proposal.fg_fraction),
+                fg_thresh=_param_str(p.subsample_proposal.fg_thr),
+                bg_thresh_hi=_param_str(p.subsample_proposal.bg_thr_hi),
+                bg_thresh_lo=_param_str(p.subsample_proposal.bg_thr_lo),
+                bbox_target_std=_param_str(p.bbox_target.std))
+            return (sym[0],) + tuple(reshape(sym[i]) for i in range(1, 7 if op == "doublebbox_target" else 4))
+        return get_sampled_proposal
+
+    def emd_loss(self, cls_logit, cls_label, cls_sec_logit, cls_sec_label, bbox_delta, bbox_target, bbox_sec_delta,
+                 bbox_sec_target, bbox_weight, bbox_sec_weight, prefix=""):
+        if not registered("emd_loss"):
+            return originals[2](self, cls_logit, cls_label, cls_sec_logit, cls_sec_label, bbox_delta, bbox_target,
+                                bbox_sec_delta, bbox_sec_target, bbox_weight, bbox_sec_weight, prefix=prefix)
+        p = self.p
+        smooth_l1_scalar = p.regress_target.smooth_l1_scalar or 1.0
+        scale_loss_shift = 128.0 if p.fp16 else 1.0
+        return mx.sym.Custom(cls_logit=cls_logit, cls_sec_logit=cls_sec_logit, cls_label=cls_label,
+                             cls_sec_label=cls_sec_label, bbox_delta=bbox_delta, bbox_sec_delta=bbox_sec_delta,
+                             bbox_target=bbox_target, bbox_sec_target=bbox_sec_target, bbox_weight=bbox_weight,
+                             bbox_sec_weight=bbox_sec_weight, op_type=_PREFIX + "emd_loss",
+                             smooth_l1_scalar=_param_str(smooth_l1_scalar),
+                             grad_scale=_param_str(1.0 * scale_loss_shift), name=prefix + "cls_reg_loss")
+
+    new = [sampled("bbox_target", originals[0]), sampled("doublebbox_target", originals[1]), emd_loss]
+    for c, (_, m), orig, fn in zip(classes, _CROWDHUMAN_METHODS, originals, new):
+        fn.__name__ = m
+        setattr(c, "_sd_reference_" + m, orig)
+        setattr(c, m, fn)
+    return True
+
+
+def unpatch_crowdhuman(builder_module):
+    """Put the reference's three methods back (and forget them: the classes are as they were)."""
+    done = False
+    for cname, m in _CROWDHUMAN_METHODS:
+        cls = getattr(builder_module, cname, None)
+        original = cls.__dict__.get("_sd_reference_" + m) if cls is not None else None
+        if original is not None:
+            setattr(cls, m, original)
+            delattr(cls, "_sd_reference_" + m)
+            done = True
+    return done
 
 
 # models/maskrcnn/builder.py:65-84 and the copy of the class in models/msrcnn/builder.py:170-189

@@ -1326,6 +1326,155 @@ def maskiou_loss_backward(iou_pred, cls, iou_target, weight, weight_sum, grad_sc
 
 
 # --------------------------------------------------------------------------------------------------
+# The CrowdHuman double-prediction head (models/crowdhuman: bbox_target.py, bbox_sec_target.py,
+# softmax_entropy_op.py, builder.py:254-306)
+# --------------------------------------------------------------------------------------------------
+class CrowdHumanTargetParam(ctypes.Structure):
+    """sd_crowdhuman_target_param"""
+    _fields_ = [("num_reg_class", ctypes.c_int), ("add_gt_to_proposal", ctypes.c_int), ("image_rois", ctypes.c_int),
+                ("fg_fraction", ctypes.c_double), ("fg_thresh", ctypes.c_double), ("bg_thresh_hi", ctypes.c_double),
+                ("bg_thresh_lo", ctypes.c_double), ("bbox_target_std", ctypes.c_double * 4)]
+
+
+CrowdHumanTargets = collections.namedtuple(
+    "CrowdHumanTargets", "sampled_proposal bbox_cls bbox_target bbox_target_weight bbox_sec_cls bbox_sec_target "
+                         "bbox_sec_target_weight count")
+
+
+def crowdhuman_target_workspace_bytes(B, P, M):
+    lib().cdll.sd_crowdhuman_target_workspace_bytes.restype = ctypes.c_size_t
+    return int(lib().cdll.sd_crowdhuman_target_workspace_bytes(int(B), int(P), int(M)))
+
+
+def crowdhuman_target(proposal, gt_bbox, mt_state, *, num_reg_class, image_rois, fg_fraction, fg_thresh,
+                      bg_thresh_hi, bg_thresh_lo, bbox_target_std, add_gt_to_proposal=True, double=True,
+                      workspace=None):
+    """The CustomOps `doublebbox_target` (double=True: models/crowdhuman/bbox_sec_target.py) and `bbox_target`
+    (double=False: models/crowdhuman/bbox_target.py) on the device: proposal (B, P, 4) with y2 == 0 padding, gt_bbox
+    (B, M, 5) with class -1 padding and -2 ignore rows -> CrowdHumanTargets(sampled_proposal (B, S, 4), bbox_cls
+    (B, S), bbox_target / bbox_target_weight (B, S, 4 * num_reg_class), the three second outputs (None when not
+    double), count (B,) int32 = rows filled; the rows behind are zero).  mt_state: mt19937_state(...), advanced in
+    place like np.random over the two np.random.choice calls per image.  No host synchronisation."""
+    _chk(proposal, "proposal", ndim=3)
+    _chk(gt_bbox, "gt_bbox", ndim=3)
+    _chk(mt_state, "mt_state", dtype=torch.int32, ndim=1)
+    if mt_state.numel() != 625:
+        raise ValueError("mt_state must hold 625 int32 words")
+    B, P, _four = proposal.shape
+    M = int(gt_bbox.shape[1])
+    if _four != 4 or tuple(gt_bbox.shape) != (B, M, 5):
+        raise ValueError("proposal must be (B, P, 4) and gt_bbox (B, M, 5), got %s and %s"
+                         % (tuple(proposal.shape), tuple(gt_bbox.shape)))
+    prm = CrowdHumanTargetParam()
+    prm.num_reg_class, prm.add_gt_to_proposal, prm.image_rois = int(num_reg_class), int(bool(add_gt_to_proposal)), \
+        int(image_rois)
+    prm.fg_fraction, prm.fg_thresh = float(fg_fraction), float(fg_thresh)
+    prm.bg_thresh_hi, prm.bg_thresh_lo = float(bg_thresh_hi), float(bg_thresh_lo)
+    std = [float(v) for v in bbox_target_std]
+    if len(std) != 4:
+        raise ValueError("bbox_target_std must have 4 entries")
+    for i, v in enumerate(std):
+        prm.bbox_target_std[i] = v
+    dev, S, W = proposal.device, int(image_rois), 4 * int(num_reg_class)
+    f32 = dict(device=dev, dtype=torch.float32)
+    outs = [torch.empty((B, S, 4), **f32), torch.empty((B, S), **f32), torch.empty((B, S, W), **f32),
+            torch.empty((B, S, W), **f32)]
+    sec = [torch.empty((B, S), **f32), torch.empty((B, S, W), **f32), torch.empty((B, S, W), **f32)] if double \
+        else [None, None, None]
+    count = torch.empty((B,), device=dev, dtype=torch.int32)
+    ws = _workspace(dev, crowdhuman_target_workspace_bytes(B, P, M), workspace)
+    lib().call("sd_crowdhuman_target", _p(proposal), _p(gt_bbox), B, P, M, 1 if double else 0, ctypes.byref(prm),
+               _p(mt_state), *[_p(t) for t in outs + sec], _p(count), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return CrowdHumanTargets(*(outs + sec + [count]))
+
+
+def _emd_args(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
+              bbox_sec_target, bbox_weight, bbox_sec_weight):
+    _chk(cls_logit, "cls_logit", ndim=2)
+    R, K = int(cls_logit.shape[0]), int(cls_logit.shape[1])
+    _chk(bbox_delta, "bbox_delta", ndim=2)
+    D = int(bbox_delta.shape[1])
+    for t, name, n in ((cls_sec_logit, "cls_sec_logit", R * K), (cls_label, "cls_label", R),
+                       (cls_sec_label, "cls_sec_label", R), (bbox_delta, "bbox_delta", R * D),
+                       (bbox_sec_delta, "bbox_sec_delta", R * D), (bbox_target, "bbox_target", R * D),
+                       (bbox_sec_target, "bbox_sec_target", R * D), (bbox_weight, "bbox_weight", R * D),
+                       (bbox_sec_weight, "bbox_sec_weight", R * D)):
+        _chk(t, name)
+        if t.numel() != n:
+            raise ValueError("%s needs %d floats, got %d" % (name, n, t.numel()))
+    ptrs = [_p(t) for t in (cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
+                            bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)]
+    return R, K, D, ptrs
+
+
+def emd_loss_forward(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
+                     bbox_sec_target, bbox_weight, bbox_sec_weight, smooth_l1_scalar=1.0, *, loss=None, pairing=None,
+                     return_pairing=False):
+    """DoublePredBboxHead.emd_loss (models/crowdhuman/builder.py:254-306) in one launch: logits (R, K), labels (R,),
+    deltas / targets / weights (R, 4 K') -> loss (1,) = mean over the rows of min(L1, L2), the sums of the two ways
+    to pair the heads with the labels.  return_pairing: also pairing (R,) int32, 1 where L1 <= L2, else 2."""
+    R, K, D, ptrs = _emd_args(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
+                              bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)
+    dev = cls_logit.device
+    loss = _ce_out(loss, "loss", 1, dev, (1,))
+    if return_pairing or pairing is not None:
+        if pairing is None:
+            pairing = torch.empty((R,), device=dev, dtype=torch.int32)
+        _chk(pairing, "pairing", dtype=torch.int32)
+        if pairing.numel() != R:
+            raise ValueError("pairing needs %d int32, got %d" % (R, pairing.numel()))
+    if R == 0:
+        loss.zero_()
+    lib().call("sd_emd_loss_fwd", *ptrs, R, K, D, float(smooth_l1_scalar), _p(loss), _p(pairing), _stream())
+    return (loss, pairing) if return_pairing else loss
+
+
+def emd_loss_backward(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
+                      bbox_sec_target, bbox_weight, bbox_sec_weight, smooth_l1_scalar=1.0, grad_scale=1.0, *,
+                      d_cls_logit=None, d_cls_sec_logit=None, d_bbox_delta=None, d_bbox_sec_delta=None):
+    """The four gradients of emd_loss_forward, written once: (d_cls_logit, d_cls_sec_logit, d_bbox_delta,
+    d_bbox_sec_delta); only the winning pairing of a row contributes, scaled by grad_scale / R."""
+    R, K, D, ptrs = _emd_args(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
+                              bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)
+    dev = cls_logit.device
+    d_cls_logit = _ce_out(d_cls_logit, "d_cls_logit", R * K, dev, (R, K))
+    d_cls_sec_logit = _ce_out(d_cls_sec_logit, "d_cls_sec_logit", R * K, dev, (R, K))
+    d_bbox_delta = _ce_out(d_bbox_delta, "d_bbox_delta", R * D, dev, (R, D))
+    d_bbox_sec_delta = _ce_out(d_bbox_sec_delta, "d_bbox_sec_delta", R * D, dev, (R, D))
+    lib().call("sd_emd_loss_bwd", *ptrs, R, K, D, float(smooth_l1_scalar), float(grad_scale), _p(d_cls_logit),
+               _p(d_cls_sec_logit), _p(d_bbox_delta), _p(d_bbox_sec_delta), _stream())
+    return d_cls_logit, d_cls_sec_logit, d_bbox_delta, d_bbox_sec_delta
+
+
+class EmdLossFunction(torch.autograd.Function):
+    """loss = EmdLossFunction.apply(cls_logit, cls_sec_logit, bbox_delta, bbox_sec_delta, cls_label, cls_sec_label,
+    bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight, smooth_l1_scalar, grad_scale).  Like the reference's
+    MakeLoss node the backward does not look at the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, cls_logit, cls_sec_logit, bbox_delta, bbox_sec_delta, cls_label, cls_sec_label, bbox_target,
+                bbox_sec_target, bbox_weight, bbox_sec_weight, smooth_l1_scalar, grad_scale):
+        ts = [t.contiguous() for t in (cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
+                                       bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)]
+        ctx.save_for_backward(*ts)
+        ctx.scalar, ctx.grad_scale = float(smooth_l1_scalar), float(grad_scale)
+        return emd_loss_forward(*ts, ctx.scalar)
+
+    @staticmethod
+    def backward(ctx, _out_grad):
+        g1, g2, gd1, gd2 = emd_loss_backward(*ctx.saved_tensors, ctx.scalar, ctx.grad_scale)
+        return (g1, g2, gd1, gd2) + (None,) * 8
+
+
+def emd_loss(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
+             bbox_sec_target, bbox_weight, bbox_sec_weight, smooth_l1_scalar=1.0, grad_scale=1.0):
+    """emd_loss_forward with autograd to the two logits and the two deltas (the argument order of the forward)."""
+    return EmdLossFunction.apply(cls_logit, cls_sec_logit, bbox_delta, bbox_sec_delta, cls_label, cls_sec_label,
+                                 bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight, smooth_l1_scalar,
+                                 grad_scale)
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_Quantization_int8  (operator_cxx/contrib/quantization_int8{-inl.h,.cu}; utils/graph_optimize.py)
 # --------------------------------------------------------------------------------------------------
 QUANT_GRAD_MODES = ("ste", "clip")
