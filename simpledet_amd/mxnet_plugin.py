@@ -34,8 +34,11 @@ the stream MXNet orders the op's outputs on -- `install(stream=<int | callable>,
 launches; the FCompute shim of INTEGRATION.md (B) is that design inside MXNet (`ctx.get_stream<gpu>()`,
 roi_align_v2-inl.h:182).
 """
+import collections
 import ctypes
+import importlib
 import os
+import sys
 from ast import literal_eval
 
 from ._lib import SD_ERR_UNSUPPORTED, SimpleDetOpsError, lib
@@ -2865,80 +2868,31 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def register(mx=None, retina=False, proposal=False, bbox_post=False, retina_loss=False, group_norm=False,
-             mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False, reppoints=False,
-             msrcnn=False, reppoints_decode=False, crowdhuman=False):
+def _feature_flags(given):
+    """{flag: bool} over FEATURE_FLAGS from the keywords a caller gave; an unknown one is a TypeError"""
+    unknown = sorted(set(given) - set(FEATURE_FLAGS))
+    if unknown:
+        raise TypeError("unknown feature flag(s) %s; the flags are %s" % (", ".join(unknown), ", ".join(FEATURE_FLAGS)))
+    return {flag: bool(given.get(flag, False)) for flag in FEATURE_FLAGS}
+
+
+def register(mx=None, **features):
     """Register every CustomOp (op_type = 'sd_' + reference op name).  Returns {name: PropClass}.
-    crowdhuman: also sd_bbox_target, sd_doublebbox_target and sd_emd_loss (opt-in: patch_crowdhuman puts them in place
-    of the Python CustomOps bbox_target / doublebbox_target and of the emd_loss subgraph, softmax_entropy included, of
-    the CrowdHuman train graphs);
-    retina: also _contrib_GenProposalRetina (opt-in: it replaces a native operator of existing graphs);
-    proposal: also _contrib_Proposal_v2 and _contrib_Proposal (opt-in for the same reason);
-    bbox_post: also BboxPostProcessing (opt-in: it replaces the reference's own CustomOp of Mask R-CNN's
-    test graphs);
-    retina_loss: also _contrib_FocalLoss and _contrib_BBoxNorm (opt-in: they replace native operators of
-    existing RetinaNet / RepPoints train graphs);
-    group_norm: also _contrib_GroupNorm (opt-in: it replaces a native operator of the GN Mask R-CNN, RepPoints
-    and EfficientNet graphs);
-    mask_loss: also _contrib_SigmoidCrossEntropy and the fused MaskLoss (opt-in: they replace a native operator,
-    and a subgraph, of the Mask R-CNN train graphs);
-    quant_int8: also _contrib_Quantization_int8 (opt-in: it replaces the native operator that
-    utils/graph_optimize.py:attach_quantize_node puts into the int8 graphs);
-    fcos: also sd_fcos_target and sd_fcos_loss (opt-in: patch_fcos_loss puts them in place of the target and loss
-    subgraphs of the FCOS train graph);
-    fcos_decode: also sd_fcos_decode (opt-in: patch_fcos_decode puts it in place of the sigmoids and the two Python
-    CustomOps of the FCOS test graph);
-    tsd_pool: also _contrib_DeformablePSROIPooling and sd_fpn_deform_roi_pool (opt-in: the first replaces a native
-    operator, patch_tsd_pool puts the second in place of the two get_roi_feature subgraphs of the TSD graphs);
-    reppoints: also sd_reppoints_target and sd_reppoints_box_loss (opt-in: patch_reppoints_loss puts them in place of
-    both assigners and both box-loss subgraphs of the RepPoints train graphs);
-    msrcnn: also sd_MsrcnnMaskLoss and sd_MaskIoULoss (opt-in: patch_msrcnn_loss puts them in place of the mask-loss
-    and MaskIoU-loss subgraphs, the Python CustomOp maskiou_compute included, of the Mask Scoring R-CNN train graphs);
-    reppoints_decode: also sd_reppoints_decode (opt-in: patch_reppoints_decode puts it in place of the per-level
-    sigmoid / max / topk / take / clip subgraphs of the RepPoints test graphs)."""
+    The operators that would change what an existing graph holds -- they replace a native operator, a CustomOp of the
+    reference's own or a subgraph of one of its builders -- are opt-in: each keyword of FEATURE_FLAGS set to True
+    also registers the operators its _FEATURES entry gates (one line per flag there; INTEGRATION.md has the detail).
+    An unknown keyword raises TypeError."""
+    flags = _feature_flags(features)
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
     _state["mx"] = mx
     table = _build_ops(mx)
     _state["all_ops"] = {name: (None, where) for name, (_, where) in table.items()}
-    if not retina:
-        table.pop("_contrib_GenProposalRetina")
-    if not proposal:
-        table.pop("_contrib_Proposal_v2")
-        table.pop("_contrib_Proposal")
-    if not bbox_post:
-        table.pop("BboxPostProcessing")
-    if not retina_loss:
-        table.pop("_contrib_FocalLoss")
-        table.pop("_contrib_BBoxNorm")
-    if not group_norm:
-        table.pop("_contrib_GroupNorm")
-    if not mask_loss:
-        table.pop("_contrib_SigmoidCrossEntropy")
-        table.pop("MaskLoss")
-    if not quant_int8:
-        table.pop("_contrib_Quantization_int8")
-    if not fcos:
-        table.pop("fcos_target")
-        table.pop("fcos_loss")
-    if not fcos_decode:
-        table.pop("fcos_decode")
-    if not tsd_pool:
-        table.pop("_contrib_DeformablePSROIPooling")
-        table.pop("fpn_deform_roi_pool")
-    if not reppoints:
-        table.pop("reppoints_target")
-        table.pop("reppoints_box_loss")
-    if not msrcnn:
-        table.pop("MsrcnnMaskLoss")
-        table.pop("MaskIoULoss")
-    if not reppoints_decode:
-        table.pop("reppoints_decode")
-    if not crowdhuman:
-        table.pop("bbox_target")
-        table.pop("doublebbox_target")
-        table.pop("emd_loss")
+    for feature in _FEATURES.values():
+        if not flags[feature.flag]:
+            for name in feature.ops:
+                table.pop(name)
     out = {}
     for name, (prop, _) in table.items():
         out[name] = mx.operator.register(_PREFIX + name)(prop)
@@ -2972,9 +2926,7 @@ def _namespaces(mx, ns):
     return out
 
 
-def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_post=False, retina_loss=False,
-            group_norm=False, mask_loss=False, quant_int8=False, fcos=False, fcos_decode=False, tsd_pool=False,
-            reppoints=False, msrcnn=False, reppoints_decode=False, crowdhuman=False):
+def install(mx=None, stream=None, sync=True, **features):
     """register() + alias the reference's symbol constructors to mx.sym.Custom, e.g.
     mx.sym.contrib.ROIAlign_v2(data=d, rois=r, pooled_size=(7,7), spatial_scale=0.25) builds
     mx.sym.Custom(d, r, op_type='sd__contrib_ROIAlign_v2', pooled_size='(7, 7)', ...) and returns
@@ -2989,102 +2941,23 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     evaluated per call) and whether forward() / backward() synchronise it before they return (the module
     docstring has the ordering contract; sync=False is for a host that orders the outputs on `stream` itself).
 
-    `retina=True` also replaces `_contrib_GenProposalRetina` (models/retinanet/builder.py:358-389); it is
-    opt-in because it changes which operator existing RetinaNet graphs hold.  iou_loss / batch_wise_anchor
-    calls fall back to the native constructor (sd_supports).
-
-    `proposal=True` also replaces `_contrib_Proposal_v2` (models/tridentnet/builder.py:239-255) and
-    `_contrib_Proposal`, and lets patch_mxnext rebind `X.proposal` when its probe sees `_contrib_Proposal`;
-    opt-in because it changes which operator existing TridentNet / C4 graphs hold.
-
-    `bbox_post=True` also registers `sd_BboxPostProcessing` and rebinds
-    `models.maskrcnn.builder.BboxPostProcessor.get_post_processing` (patch_bbox_post) so that Mask R-CNN test
-    graphs hold it in place of the reference's numpy CustomOp; opt-in because it changes which operator those
-    graphs hold.  A `nms.type` other than "nms" or a max_det_per_image outside the kernels' limits falls back
-    to the reference's method and is listed in `_state["fallbacks"]`.
-
-    `retina_loss=True` also replaces `_contrib_FocalLoss` and `_contrib_BBoxNorm` (models/retinanet/builder.py:294-332,
-    models/RepPoints/builder.py:404,439,472) and lets patch_mxnext bind `X.focal_loss` / `X.bbox_norm` to the
-    aliases; opt-in because it changes which operators existing RetinaNet / RepPoints train graphs hold.
-
-    `group_norm=True` also replaces `_contrib_GroupNorm` (mx.sym.contrib.GroupNorm: the normaliser of
-    config/scratch/mask_r50v1b_fpn_gn_scratch_2x.py and of the RepPoints / EfficientNet configs) and lets patch_mxnext
-    bind `X.group_norm` to the alias where mxnext has one; opt-in because it changes which operator those graphs hold.
-    mean / var keep the reference's declared shape (N, C); the first N * G floats are written.
-
-    `mask_loss=True` also replaces `_contrib_SigmoidCrossEntropy` (mx.sym.contrib.SigmoidCrossEntropy: the mask loss
-    of models/maskrcnn/builder.py:307-312 and models/msrcnn/builder.py:418-423), registers the fused `sd_MaskLoss`
-    and rebinds `models.maskrcnn.builder.MaskFasterRcnnHead.get_loss` (patch_mask_loss) so that Mask R-CNN train
-    graphs hold ONE node in place of split / stack / gather_nd / concat / reshape / SigmoidCrossEntropy; opt-in
-    because it changes which operators those graphs hold.  models/msrcnn/builder.py is not patched by this flag (its
-    get_loss also returns the gathered sigmoid): it gets the aliased operator only; `msrcnn=True` is its flag.
-
-    `quant_int8=True` also replaces `_contrib_Quantization_int8` (mx.sym.contrib.Quantization_int8: the node
-    utils/graph_optimize.py:162,169,182 attaches in front of every quantised operator's data and weight; config/int8/);
-    opt-in because it changes which operator those graphs hold.  `minmax` stays the operator's auxiliary state; the
-    step state (countdown, init) lives on the device with the operator instance.  Per-channel weights, a
-    quant_mode other than "minmax" and a grad_mode other than "ste" / "clip" fall back to the native constructor.
-
-    `fcos=True` also registers `sd_fcos_target` and `sd_fcos_loss` and rebinds
-    `models.FCOS.builder.FCOSFPNHead.get_loss` (patch_fcos_loss) so that the FCOS train graph holds these two nodes
-    in place of make_fcos_gt's ~60 nodes with their two Python CustomOps, the five reshapes and the concat per
-    logit tensor, and the three loss subgraphs with their pass-through CustomOps; opt-in because it changes which
-    operators that graph holds.  The three outputs keep the reference's order (centerness, cls, offset).
-
-    `fcos_decode=True` also registers `sd_fcos_decode` and rebinds `models.FCOS.builder.FCOSFPNHead.get_all_proposal`
-    (patch_fcos_decode) so that the FCOS test graph holds this ONE node in place of the ten sigmoid nodes, the five
-    Python CustomOps get_proposal_single_stage, the concat and the Python CustomOp get_batch_proposal; opt-in because
-    it changes which operators that graph holds, and independent of `fcos` (which keeps meaning the train head
-    alone).  Where the builder module is not importable nothing is rebound and `_state["fallbacks"]` says so.
-
-    `tsd_pool=True` also replaces `_contrib_DeformablePSROIPooling` (mx.sym.contrib.DeformablePSROIPooling; parameter
-    sets that sd_deform_psroi_pool_supported refuses for one class fall back to the native constructor), registers `sd_fpn_deform_roi_pool` and
-    rebinds `FPNRoIAlign_DeltaC.get_roi_feature` and `FPNRoIAlign_DeltaR.get_roi_feature` of models/TSD/poolings.py
-    (patch_tsd_pool) so that a TSD graph holds TWO nodes in place of 2 x (level rule, eight masks, four
-    DeformablePSROIPooling, add_n); opt-in because it changes which operators those graphs hold.
-
-    `reppoints=True` also registers `sd_reppoints_target` and `sd_reppoints_box_loss` and rebinds
-    `models.RepPoints.builder.RepPointsHead.get_loss` (patch_reppoints_loss) so that a RepPoints train graph holds
-    these two nodes in place of _gen_points, _offset_to_boxes, both _point_target subgraphs, _offset_to_pts,
-    _points2bbox, smooth_l1, BBoxNorm and MakeLoss of both box branches; the focal loss on the concatenated class
-    logits stays the node it was.  A default install() afterwards puts the reference's method back.
-
-    `msrcnn=True` also registers `sd_MsrcnnMaskLoss` and `sd_MaskIoULoss` and rebinds
-    `models.msrcnn.builder.MaskFasterRcnnHead.get_loss` and `MaskIoUConvHead.get_loss` (patch_msrcnn_loss) so that a
-    Mask Scoring R-CNN train graph holds these two nodes in place of both split / stack / gather_nd / concat chains,
-    Activation(sigmoid), reshape / SigmoidCrossEntropy, the Python CustomOp `maskiou_compute` (a host round trip in
-    the middle of every step) and the loss arithmetic behind it; the conv / FC tower `_get_output` stays the
-    reference's.  Opt-in because it changes which operators those graphs hold, and independent of `mask_loss`, which
-    keeps its meaning (the Mask R-CNN builder and the aliased operator).  Where the builder module is not importable
-    nothing is rebound and `_state["fallbacks"]` says so; a default install() afterwards puts the reference's
-    methods back.  The test-time path (get_maskiou_prediction) is not touched.
-
-    `reppoints_decode=True` also registers `sd_reppoints_decode` and rebinds
-    `models.RepPoints.builder.RepPointsHead.get_prediction` (patch_reppoints_decode) so that a RepPoints test graph
-    holds this ONE node in place of, per level, two transposes and reshapes, the sigmoid, max and topk and, per image,
-    the slice / take / scale / add / clip chains, and of the padded column and the two concats behind them; opt-in
-    because it changes which operators that graph holds, and independent of `reppoints` (which keeps meaning the
-    train head alone).  A head with p.fp16 set or beyond the op's limits goes back to the reference's method; where the
-    builder module is not importable nothing is rebound; `_state["fallbacks"]` says so in both cases.  A default
-    install() afterwards puts the reference's method back.
-
-    `crowdhuman=True` also registers `sd_bbox_target`, `sd_doublebbox_target` and `sd_emd_loss` and rebinds, in
-    `models.crowdhuman.builder`, `FPNRpnHeadwithIgnore.get_sampled_proposal`, `DoublePredFPNRpnHead.get_sampled_proposal`
-    and `DoublePredBboxHead.emd_loss` (patch_crowdhuman) so that a CrowdHuman train graph holds ONE device target node
-    in place of the Python CustomOp (two device-to-host copies and numpy sampling in the middle of every step) and ONE
-    `sd_emd_loss` node per emd_loss call (two with refine_mode) in place of four softmax_entropy CustomOps, four
-    smooth_l1 and the arithmetic around them.  The targets draw from a device copy of numpy's global generator, taken
-    where it stands at the first call.  Where the builder module is not importable nothing is rebound and
-    `_state["fallbacks"]` says so; a default install() afterwards puts the reference's methods back.  The test-time
-    graph is not touched."""
-    props = register(mx, retina=retina, proposal=proposal, bbox_post=bbox_post, retina_loss=retina_loss,
-                     group_norm=group_norm, mask_loss=mask_loss, quant_int8=quant_int8, fcos=fcos,
-                     fcos_decode=fcos_decode, tsd_pool=tsd_pool, reppoints=reppoints, msrcnn=msrcnn,
-                     reppoints_decode=reppoints_decode, crowdhuman=crowdhuman)
+    `features`: the keywords of FEATURE_FLAGS, all off by default because each changes which operators existing
+    graphs hold; an unknown keyword raises TypeError.  `<flag>=True` also registers and aliases the operators its
+    _FEATURES entry gates and, where the entry names builder classes, rebinds their methods (the `patch_*` function of
+    the flag says to what) so that the reference's builders emit the device nodes without a reference file being
+    edited.  A rebound method keeps the one it replaced on its class as `_sd_reference_<method>` (a second install()
+    keeps the first) and hands a call the device op does not take, or whose op is not registered, back to it;
+    `_state["fallbacks"]` says why, and also where a flag's builder module is not importable and nothing was rebound
+    (for the flags whose entry has a fallback).  `_state["<flag>_patched"]` tells whether the methods were rebound.
+    A default install() afterwards puts things back: the native constructors, the reference's methods, and no
+    `_sd_reference_<method>` left on a builder class.  One line per flag sits in _FEATURES; INTEGRATION.md has the
+    operators' arguments, limits and the reference lines they stand for."""
+    flags = _feature_flags(features)
+    props = register(mx, **flags)
     mx = _state["mx"]
-    _state["proposal"] = bool(proposal)
-    _state["retina_loss"] = bool(retina_loss)
-    _state["group_norm"] = bool(group_norm)
+    for feature in _FEATURES.values():
+        if not feature.builders and feature.state:        # what patch_mxnext reads
+            _state[feature.state] = flags[feature.flag]
     _state["fallbacks"] = []
     _state["stream"], _state["sync"] = stream, bool(sync)
 
@@ -3164,131 +3037,106 @@ def install(mx=None, stream=None, sync=True, retina=False, proposal=False, bbox_
     # ... and the mxnext wrappers the reference's builders go through, explicitly (not relying on
     # mxnext looking `mx.sym.*` up at call time)
     _state["mxnext_patched"] = patch_mxnext(mx=mx)
-    if bbox_post:
-        _state["bbox_post_patched"] = patch_bbox_post(mx=mx)
-    else:   # a default install() after an opt-in one builds the reference's node again
-        import sys
-        for m in _BBOX_POST_BUILDERS:
-            if sys.modules.get(m) is not None:
-                unpatch_bbox_post(sys.modules[m])
-        _state["bbox_post_patched"] = False
-    if mask_loss:
-        _state["mask_loss_patched"] = patch_mask_loss(mx=mx)
-    else:
-        import sys
-        if sys.modules.get(_MASK_LOSS_BUILDER) is not None:
-            unpatch_mask_loss(sys.modules[_MASK_LOSS_BUILDER])
-        _state["mask_loss_patched"] = False
-    if fcos:
-        _state["fcos_patched"] = patch_fcos_loss(mx=mx)
-    else:
-        import sys
-        if sys.modules.get(_FCOS_BUILDER) is not None:
-            unpatch_fcos_loss(sys.modules[_FCOS_BUILDER])
-        _state["fcos_patched"] = False
-    if fcos_decode:
-        _state["fcos_decode_patched"] = patch_fcos_decode(mx=mx)
-        if not _state["fcos_decode_patched"]:
-            _state["fallbacks"].append(("fcos_decode", None, "%s.FCOSFPNHead is not importable" % _FCOS_BUILDER))
-    else:
-        import sys
-        if sys.modules.get(_FCOS_BUILDER) is not None:
-            unpatch_fcos_decode(sys.modules[_FCOS_BUILDER])
-        _state["fcos_decode_patched"] = False
-    if tsd_pool:
-        _state["tsd_pool_patched"] = patch_tsd_pool(mx=mx)
-        if not _state["tsd_pool_patched"]:
-            _state["fallbacks"].append(("fpn_deform_roi_pool", None, "%s is not importable" % _TSD_POOLINGS))
-    else:
-        import sys
-        if sys.modules.get(_TSD_POOLINGS) is not None:
-            unpatch_tsd_pool(sys.modules[_TSD_POOLINGS])
-        _state["tsd_pool_patched"] = False
-    if reppoints:
-        _state["reppoints_patched"] = patch_reppoints_loss(mx=mx)
-        if not _state["reppoints_patched"]:
-            _state["fallbacks"].append(("reppoints_box_loss", None, "%s.RepPointsHead is not importable" % _REPPOINTS_BUILDER))
-    else:
-        import sys
-        if sys.modules.get(_REPPOINTS_BUILDER) is not None:
-            unpatch_reppoints_loss(sys.modules[_REPPOINTS_BUILDER])
-        _state["reppoints_patched"] = False
-    if msrcnn:
-        _state["msrcnn_patched"] = patch_msrcnn_loss(mx=mx)
-        if not _state["msrcnn_patched"]:
-            _state["fallbacks"].append(("MaskIoULoss", None, "%s is not importable" % _MSRCNN_BUILDER))
-    else:
-        import sys
-        if sys.modules.get(_MSRCNN_BUILDER) is not None:
-            unpatch_msrcnn_loss(sys.modules[_MSRCNN_BUILDER])
-        _state["msrcnn_patched"] = False
-    if reppoints_decode:
-        _state["reppoints_decode_patched"] = patch_reppoints_decode(mx=mx)
-        if not _state["reppoints_decode_patched"]:
-            _state["fallbacks"].append(("reppoints_decode", None, "%s.RepPointsHead is not importable" % _REPPOINTS_BUILDER))
-    else:
-        import sys
-        if sys.modules.get(_REPPOINTS_BUILDER) is not None:
-            unpatch_reppoints_decode(sys.modules[_REPPOINTS_BUILDER])
-        _state["reppoints_decode_patched"] = False
-    if crowdhuman:
-        _state["crowdhuman_patched"] = patch_crowdhuman(mx=mx)
-        if not _state["crowdhuman_patched"]:
-            _state["fallbacks"].append(("emd_loss", None, "%s is not importable" % _CROWDHUMAN_BUILDER))
-    else:
-        import sys
-        if sys.modules.get(_CROWDHUMAN_BUILDER) is not None:
-            unpatch_crowdhuman(sys.modules[_CROWDHUMAN_BUILDER])
-        _state["crowdhuman_patched"] = False
+    for feature in _FEATURES.values():
+        if not feature.builders:
+            continue
+        if flags[feature.flag]:
+            _state[feature.state] = _rebind(feature, mx=mx)
+            if feature.fallback and not _state[feature.state]:
+                name, why = feature.fallback
+                _state["fallbacks"].append((name, None, why % feature.builders[0]))
+        else:   # a default install() after an opt-in one builds the reference's nodes again
+            for module in feature.builders:
+                if sys.modules.get(module) is not None:
+                    _restore(feature, sys.modules[module])
+            _state[feature.state] = False
     return props
 
 
-_CROWDHUMAN_BUILDER = "models.crowdhuman.builder"
+# ---------------------------------------------------------------------------- opt-in features ----
+# One entry of _FEATURES (at the end of this section) per opt-in flag of register() / install():
+#   flag      the keyword;                      summary   the flag's line of documentation
+#   ops       the _build_ops names it gates;    state     the _state key install() reports it under
+#   builders  the reference module(s) whose classes it rebinds;  methods  the (class, method) pairs in each of them
+#   maker     maker(mx, builder_module, originals) -> the replacement methods, in the order of `methods`
+#   fallback  (operator, "... %s ..." over builders[0]) recorded in _state["fallbacks"] when nothing was rebound
+#   lenient   any exception from importing a builder module means "not there" (bbox_post alone)
+_Feature = collections.namedtuple("_Feature", "flag ops summary state builders methods maker fallback lenient",
+                                  defaults=(None, (), (), None, None, False))
+
+
+def _import_builder(name, lenient=False):
+    """The reference module `name`, or None where the reference tree is not on the path: a ModuleNotFoundError for
+    the module or one of its parent packages.  A missing dependency OF the builder, or any other error raised inside
+    it, is the caller's to see -- unless `lenient`."""
+    try:
+        return importlib.import_module(name)
+    except Exception as e:
+        if lenient or (isinstance(e, ModuleNotFoundError) and e.name is not None and name.startswith(e.name)):
+            return None
+        raise
+
+
+def _rebind(feature, builder_module=None, mx=None):
+    """Put the feature's replacement methods on its builder classes: in `builder_module`, or in every module of
+    feature.builders that imports.  False where a class is missing (nothing is touched then).  The method a
+    replacement stands for is kept on its class as `_sd_reference_<method>`; a second call keeps the first one."""
+    mx = mx or _state["mx"]
+    if builder_module is None:
+        modules = [_import_builder(name, feature.lenient) for name in feature.builders]
+        return any([_rebind(feature, module, mx) for module in modules if module is not None])
+    classes = [getattr(builder_module, c, None) for c, _ in feature.methods]
+    if any(c is None for c in classes):
+        return False
+    originals = [c.__dict__.get("_sd_reference_" + m) or getattr(c, m) for c, (_, m) in zip(classes, feature.methods)]
+    replacements = feature.maker(mx, builder_module, originals)
+    for c, (_, m), original, fn in zip(classes, feature.methods, originals, replacements):
+        fn.__name__ = m
+        setattr(c, "_sd_reference_" + m, original)
+        setattr(c, m, fn)
+    return True
+
+
+def _restore(feature, builder_module):
+    """Put the reference's methods back and forget them: the classes are as they were.  True when one was restored."""
+    done = False
+    for cname, m in feature.methods:
+        cls = getattr(builder_module, cname, None)
+        original = cls.__dict__.get("_sd_reference_" + m) if cls is not None else None
+        if original is not None:
+            setattr(cls, m, original)
+            delattr(cls, "_sd_reference_" + m)
+            done = True
+    return done
+
+
+def _fell_back(name, why):
+    """records in _state["fallbacks"] why (if at all) a rebound method hands this call to the reference's; returns why"""
+    if why:
+        _state.setdefault("fallbacks", []).append((name, None, why))
+    return why
+
+
+def _registered(name, why=None):
+    """whether install() registered sd_<name>; if not, the fallback is recorded (`why`: a feature's own wording)"""
+    if name in (_state.get("table") or {}):
+        return True
+    _fell_back(name, why or "%s%s is not registered" % (_PREFIX, name))
+    return False
+
+
 _CROWDHUMAN_METHODS = (("FPNRpnHeadwithIgnore", "get_sampled_proposal"), ("DoublePredFPNRpnHead", "get_sampled_proposal"),
                        ("DoublePredBboxHead", "emd_loss"))
 
 
-def patch_crowdhuman(builder_module=None, mx=None):
-    """Route the CrowdHuman train head to the device ops WITHOUT editing the reference: rebinds, in
-    models/crowdhuman/builder.py,
-      FPNRpnHeadwithIgnore.get_sampled_proposal (:360-400) and DoublePredFPNRpnHead.get_sampled_proposal (:406-450) to
-        methods that read the same fields of `self.p`, call the reference's own `self.get_all_proposal` and emit
-        mx.sym.Custom(op_type='sd_bbox_target' / 'sd_doublebbox_target', name='subsample_proposal') with the
-        reference's parameters, followed by the reference's reshapes; the return tuples are the reference's;
-      DoublePredBboxHead.emd_loss (:254-306) to a method of the same signature that emits ONE
-        mx.sym.Custom(op_type='sd_emd_loss', name=prefix + 'cls_reg_loss') with smooth_l1_scalar =
-        p.regress_target.smooth_l1_scalar or 1.0 and grad_scale = 128.0 if p.fp16 else 1.0.
-    install(crowdhuman=True) calls this when the builder module is importable; returns True when the three methods
-    were rebound.  The originals are kept as `_sd_reference_<method>` (a second install() keeps the first ones); a
-    default install() afterwards puts them back (unpatch_crowdhuman)."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_CROWDHUMAN_BUILDER)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _CROWDHUMAN_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_crowdhuman(module, mx)
-    classes = [getattr(builder_module, c, None) for c, _ in _CROWDHUMAN_METHODS]
-    if any(c is None for c in classes):
-        return False
-    originals = [c.__dict__.get("_sd_reference_" + m) or getattr(c, m) for c, (_, m) in zip(classes, _CROWDHUMAN_METHODS)]
-
-    def registered(name):
-        if name in (_state.get("table") or {}):
-            return True
-        _state.setdefault("fallbacks", []).append((name, None, "%s%s is not registered" % (_PREFIX, name)))
-        return False
-
+def _crowdhuman_methods(mx, builder_module, originals):
     def reshape(sym):
         X = getattr(builder_module, "X", None)       # the builder's own `import mxnext as X`
         return X.reshape(sym, (-3, -2)) if X is not None else mx.sym.reshape(sym, shape=(-3, -2))
 
     def sampled(op, original):
         def get_sampled_proposal(self, conv_fpn_feat, gt_bbox, im_info):
-            if not registered(op):
+            if not _registered(op):
                 return original(self, conv_fpn_feat, gt_bbox, im_info)
             p = self.p
             (proposal, proposal_score) = self.get_all_proposal(conv_fpn_feat, im_info)
@@ -3307,7 +3155,7 @@ def patch_crowdhuman(builder_module=None, mx=None):
 
     def emd_loss(self, cls_logit, cls_label, cls_sec_logit, cls_sec_label, bbox_delta, bbox_target, bbox_sec_delta,
                  bbox_sec_target, bbox_weight, bbox_sec_weight, prefix=""):
-        if not registered("emd_loss"):
+        if not _registered("emd_loss"):
             return originals[2](self, cls_logit, cls_label, cls_sec_logit, cls_sec_label, bbox_delta, bbox_target,
                                 bbox_sec_delta, bbox_sec_target, bbox_weight, bbox_sec_weight, prefix=prefix)
         p = self.p
@@ -3320,29 +3168,44 @@ def patch_crowdhuman(builder_module=None, mx=None):
                              smooth_l1_scalar=_param_str(smooth_l1_scalar),
                              grad_scale=_param_str(1.0 * scale_loss_shift), name=prefix + "cls_reg_loss")
 
-    new = [sampled("bbox_target", originals[0]), sampled("doublebbox_target", originals[1]), emd_loss]
-    for c, (_, m), orig, fn in zip(classes, _CROWDHUMAN_METHODS, originals, new):
-        fn.__name__ = m
-        setattr(c, "_sd_reference_" + m, orig)
-        setattr(c, m, fn)
-    return True
+    return [sampled("bbox_target", originals[0]), sampled("doublebbox_target", originals[1]), emd_loss]
+
+
+def patch_crowdhuman(builder_module=None, mx=None):
+    """Route the CrowdHuman train head to the device ops WITHOUT editing the reference: rebinds, in
+    models/crowdhuman/builder.py,
+      FPNRpnHeadwithIgnore.get_sampled_proposal (:360-400) and DoublePredFPNRpnHead.get_sampled_proposal (:406-450) to
+        methods that read the same fields of `self.p`, call the reference's own `self.get_all_proposal` and emit
+        mx.sym.Custom(op_type='sd_bbox_target' / 'sd_doublebbox_target', name='subsample_proposal') with the
+        reference's parameters, followed by the reference's reshapes; the return tuples are the reference's;
+      DoublePredBboxHead.emd_loss (:254-306) to a method of the same signature that emits ONE
+        mx.sym.Custom(op_type='sd_emd_loss', name=prefix + 'cls_reg_loss') with smooth_l1_scalar =
+        p.regress_target.smooth_l1_scalar or 1.0 and grad_scale = 128.0 if p.fp16 else 1.0.
+    install(crowdhuman=True) calls this when the builder module is importable; returns True when the three methods
+    were rebound.  The originals are kept as `_sd_reference_<method>` (a second install() keeps the first ones); a
+    default install() afterwards puts them back (unpatch_crowdhuman)."""
+    return _rebind(_FEATURES["crowdhuman"], builder_module, mx)
 
 
 def unpatch_crowdhuman(builder_module):
     """Put the reference's three methods back (and forget them: the classes are as they were)."""
-    done = False
-    for cname, m in _CROWDHUMAN_METHODS:
-        cls = getattr(builder_module, cname, None)
-        original = cls.__dict__.get("_sd_reference_" + m) if cls is not None else None
-        if original is not None:
-            setattr(cls, m, original)
-            delattr(cls, "_sd_reference_" + m)
-            done = True
-    return done
+    return _restore(_FEATURES["crowdhuman"], builder_module)
 
 
-# models/maskrcnn/builder.py:65-84 and the copy of the class in models/msrcnn/builder.py:170-189
-_BBOX_POST_BUILDERS = ("models.maskrcnn.builder", "models.msrcnn.builder")
+def _bbox_post_methods(mx, builder_module, originals):
+    def get_post_processing(self, cls_score, bbox_xyxy):
+        p = self.p
+        params = {"max_det_per_image": _param_str(p.max_det_per_image),
+                  "min_det_score": _param_str(p.min_det_score), "nms_type": _param_str(p.nms.type),
+                  "nms_thr": _param_str(p.nms.thr)}
+        if not _registered("BboxPostProcessing") or \
+                _fell_back("BboxPostProcessing", _state["table"]["BboxPostProcessing"][0].sd_supports(params)):
+            return originals[0](self, cls_score, bbox_xyxy)
+        sym = mx.sym.Custom(cls_score=cls_score, bbox_xyxy=bbox_xyxy, op_type=_PREFIX + "BboxPostProcessing",
+                            **params)
+        return sym[0], sym[1], sym[2]
+
+    return [get_post_processing]
 
 
 def patch_bbox_post(builder_module=None, mx=None):
@@ -3354,51 +3217,25 @@ def patch_bbox_post(builder_module=None, mx=None):
     importable; returns True when a class was patched.  The original method is kept as
     `_sd_reference_get_post_processing` (a second install() keeps the first original) and is what a call the
     kernels do not take goes back to."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        done = False
-        for name in _BBOX_POST_BUILDERS:
-            try:
-                done = patch_bbox_post(importlib.import_module(name), mx) or done
-            except Exception:
-                pass
-        return done
-    cls = getattr(builder_module, "BboxPostProcessor", None)
-    if cls is None:
-        return False
-    original = cls.__dict__.get("_sd_reference_get_post_processing") or cls.get_post_processing
-
-    def get_post_processing(self, cls_score, bbox_xyxy):
-        p = self.p
-        params = {"max_det_per_image": _param_str(p.max_det_per_image),
-                  "min_det_score": _param_str(p.min_det_score), "nms_type": _param_str(p.nms.type),
-                  "nms_thr": _param_str(p.nms.thr)}
-        prop = (_state.get("table") or {}).get("BboxPostProcessing")
-        why = prop[0].sd_supports(params) if prop else "sd_BboxPostProcessing is not registered"
-        if why:
-            _state.setdefault("fallbacks", []).append(("BboxPostProcessing", None, why))
-            return original(self, cls_score, bbox_xyxy)
-        sym = mx.sym.Custom(cls_score=cls_score, bbox_xyxy=bbox_xyxy, op_type=_PREFIX + "BboxPostProcessing",
-                            **params)
-        return sym[0], sym[1], sym[2]
-
-    cls._sd_reference_get_post_processing = original
-    cls.get_post_processing = get_post_processing
-    return True
+    return _rebind(_FEATURES["bbox_post"], builder_module, mx)
 
 
 def unpatch_bbox_post(builder_module):
     """Put the reference's get_post_processing back."""
-    cls = getattr(builder_module, "BboxPostProcessor", None)
-    original = cls.__dict__.get("_sd_reference_get_post_processing") if cls is not None else None
-    if original is None:
-        return False
-    cls.get_post_processing = original
-    return True
+    return _restore(_FEATURES["bbox_post"], builder_module)
 
 
-_MASK_LOSS_BUILDER = "models.maskrcnn.builder"
+def _mask_loss_methods(mx, builder_module, originals):
+    def get_loss(self, conv_feat, mask_target, mask_ind):
+        if not _registered("MaskLoss"):
+            return originals[0](self, conv_feat, mask_target, mask_ind)
+        mask_fcn_logit = self.get_output(conv_feat)
+        scale_loss_shift = 128.0 if self.pMask.fp16 else 1.0
+        sym = mx.sym.Custom(logits=mask_fcn_logit, cls=mask_ind, target=mask_target, op_type=_PREFIX + "MaskLoss",
+                            grad_scale=_param_str(1.0 * scale_loss_shift), name="mask_loss")
+        return (sym[0],)
+
+    return [get_loss]
 
 
 def patch_mask_loss(builder_module=None, mx=None):
@@ -3415,49 +3252,35 @@ def patch_mask_loss(builder_module=None, mx=None):
     models/msrcnn/builder.py is NOT patched by this flag: its get_loss also returns the gathered sigmoid (the MaskIoU
     head reads it), so it keeps its subgraph and gets the aliased SigmoidCrossEntropy only; install(msrcnn=True)
     (patch_msrcnn_loss) is what moves that model's head onto the device."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_MASK_LOSS_BUILDER)
-        except ModuleNotFoundError as e:
-            # the reference tree is not on the path: nothing to patch.  A missing dependency OF the builder, or
-            # any other error raised inside it, is the caller's to see
-            if e.name is None or not _MASK_LOSS_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_mask_loss(module, mx)
-    cls = getattr(builder_module, "MaskFasterRcnnHead", None)
-    if cls is None:
-        return False
-    original = cls.__dict__.get("_sd_reference_get_loss") or cls.get_loss
-
-    def get_loss(self, conv_feat, mask_target, mask_ind):
-        if "MaskLoss" not in (_state.get("table") or {}):
-            _state.setdefault("fallbacks", []).append(("MaskLoss", None, "sd_MaskLoss is not registered"))
-            return original(self, conv_feat, mask_target, mask_ind)
-        mask_fcn_logit = self.get_output(conv_feat)
-        scale_loss_shift = 128.0 if self.pMask.fp16 else 1.0
-        sym = mx.sym.Custom(logits=mask_fcn_logit, cls=mask_ind, target=mask_target, op_type=_PREFIX + "MaskLoss",
-                            grad_scale=_param_str(1.0 * scale_loss_shift), name="mask_loss")
-        return (sym[0],)
-
-    cls._sd_reference_get_loss = original
-    cls.get_loss = get_loss
-    return True
+    return _rebind(_FEATURES["mask_loss"], builder_module, mx)
 
 
 def unpatch_mask_loss(builder_module):
     """Put the reference's get_loss back."""
-    cls = getattr(builder_module, "MaskFasterRcnnHead", None)
-    original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
-    if original is None:
-        return False
-    cls.get_loss = original
-    return True
+    return _restore(_FEATURES["mask_loss"], builder_module)
 
 
-_MSRCNN_BUILDER = "models.msrcnn.builder"
+def _msrcnn_methods(mx, builder_module, originals):
+    def mask_get_loss(self, conv_feat, mask_target, mask_ind):
+        if not _registered("MsrcnnMaskLoss"):
+            return originals[0](self, conv_feat, mask_target, mask_ind)
+        mask_fcn_logit = self.get_output(conv_feat)
+        scale_loss_shift = 128.0 if self.pMask.fp16 else 1.0
+        sym = mx.sym.Custom(logits=mask_fcn_logit, cls=mask_ind, target=mask_target,
+                            op_type=_PREFIX + "MsrcnnMaskLoss", grad_scale=_param_str(1.0 * scale_loss_shift),
+                            name="mask_loss")
+        return (sym[0],), sym[1]
+
+    def iou_get_loss(self, conv_feat, mask_pred_logits, mask_target, mask_inds, mask_ratio):
+        if not _registered("MaskIoULoss"):
+            return originals[1](self, conv_feat, mask_pred_logits, mask_target, mask_inds, mask_ratio)
+        iou_pred_logits = self._get_output(mask_pred_logits, conv_feat)
+        sym = mx.sym.Custom(iou_pred=iou_pred_logits, prob=mask_pred_logits, target=mask_target, ratio=mask_ratio,
+                            cls=mask_inds, op_type=_PREFIX + "MaskIoULoss", grad_scale=_param_str(1.0),
+                            name="iou_head_loss")
+        return (sym[0],)
+
+    return [mask_get_loss, iou_get_loss]
 
 
 def patch_msrcnn_loss(builder_module=None, mx=None):
@@ -3476,71 +3299,53 @@ def patch_msrcnn_loss(builder_module=None, mx=None):
     importable; returns True when both classes were patched.  The original methods are kept as
     `_sd_reference_get_loss` (a second install() keeps the first originals); a default install() afterwards puts
     them back (unpatch_msrcnn_loss)."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_MSRCNN_BUILDER)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _MSRCNN_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_msrcnn_loss(module, mx)
-    mask_cls = getattr(builder_module, "MaskFasterRcnnHead", None)
-    iou_cls = getattr(builder_module, "MaskIoUConvHead", None)
-    if mask_cls is None or iou_cls is None:
-        return False
-    mask_original = mask_cls.__dict__.get("_sd_reference_get_loss") or mask_cls.get_loss
-    iou_original = iou_cls.__dict__.get("_sd_reference_get_loss") or iou_cls.get_loss
-
-    def registered(name):
-        if name in (_state.get("table") or {}):
-            return True
-        _state.setdefault("fallbacks", []).append((name, None, "%s%s is not registered" % (_PREFIX, name)))
-        return False
-
-    def mask_get_loss(self, conv_feat, mask_target, mask_ind):
-        if not registered("MsrcnnMaskLoss"):
-            return mask_original(self, conv_feat, mask_target, mask_ind)
-        mask_fcn_logit = self.get_output(conv_feat)
-        scale_loss_shift = 128.0 if self.pMask.fp16 else 1.0
-        sym = mx.sym.Custom(logits=mask_fcn_logit, cls=mask_ind, target=mask_target,
-                            op_type=_PREFIX + "MsrcnnMaskLoss", grad_scale=_param_str(1.0 * scale_loss_shift),
-                            name="mask_loss")
-        return (sym[0],), sym[1]
-
-    def iou_get_loss(self, conv_feat, mask_pred_logits, mask_target, mask_inds, mask_ratio):
-        if not registered("MaskIoULoss"):
-            return iou_original(self, conv_feat, mask_pred_logits, mask_target, mask_inds, mask_ratio)
-        iou_pred_logits = self._get_output(mask_pred_logits, conv_feat)
-        sym = mx.sym.Custom(iou_pred=iou_pred_logits, prob=mask_pred_logits, target=mask_target, ratio=mask_ratio,
-                            cls=mask_inds, op_type=_PREFIX + "MaskIoULoss", grad_scale=_param_str(1.0),
-                            name="iou_head_loss")
-        return (sym[0],)
-
-    mask_get_loss.__name__ = iou_get_loss.__name__ = "get_loss"
-    mask_cls._sd_reference_get_loss = mask_original
-    mask_cls.get_loss = mask_get_loss
-    iou_cls._sd_reference_get_loss = iou_original
-    iou_cls.get_loss = iou_get_loss
-    return True
+    return _rebind(_FEATURES["msrcnn"], builder_module, mx)
 
 
 def unpatch_msrcnn_loss(builder_module):
     """Put the reference's two get_loss methods back (and forget them: the classes are as they were)."""
-    done = False
-    for name in ("MaskFasterRcnnHead", "MaskIoUConvHead"):
-        cls = getattr(builder_module, name, None)
-        original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
-        if original is not None:
-            cls.get_loss = original
-            del cls._sd_reference_get_loss
-            done = True
-    return done
+    return _restore(_FEATURES["msrcnn"], builder_module)
 
 
-_FCOS_BUILDER = "models.FCOS.builder"
 _FCOS_CONFIG = "config.fcos_r50v1_fpn_1x"     # where the reference's own CustomOpProps read throwout_param (input.py:88)
+
+
+def _fcos_level_inputs(head, conv_fpn_feat):
+    """(strides, {cls_logit_i, centerness_logit_i, offset_logit_i: the head's per-level outputs}): the first 3 * L
+    inputs of sd_fcos_loss and sd_fcos_decode, in their order"""
+    centerness_logit_dict, cls_logit_dict, offset_logit_dict = head.get_output(conv_fpn_feat)
+    strides = tuple(head.p.FCOSParam.stride)
+    inputs = {}
+    for prefix, d in (("cls_logit_%d", cls_logit_dict), ("centerness_logit_%d", centerness_logit_dict),
+                      ("offset_logit_%d", offset_logit_dict)):
+        for i, stride in enumerate(strides):
+            inputs[prefix % i] = d[stride]
+    return strides, inputs
+
+
+def _fcos_loss_methods(mx, builder_module, originals):
+    def get_loss(self, conv_fpn_feat, gt_bbox, im_info):
+        throwout = getattr(sys.modules.get(_FCOS_CONFIG), "throwout_param", None)
+        if not _registered("fcos_loss", "sd_fcos_target / sd_fcos_loss are not registered") or \
+                _fell_back("fcos_loss", "%s.throwout_param is not set" % _FCOS_CONFIG if throwout is None else ""):
+            return originals[0](self, conv_fpn_feat, gt_bbox, im_info)
+        p = self.p
+        strides, inputs = _fcos_level_inputs(self, conv_fpn_feat)
+        ignore = {"ignore_offset": _param_str(p.loss_setting.ignore_offset),
+                  "ignore_label": _param_str(p.loss_setting.ignore_label)}
+        # the reference binds the two inputs by name as well (builder.py:193-194)
+        targets = mx.sym.Custom(gt_bbox=mx.sym.var("gt_bbox"), im_info=mx.sym.var("im_info"),
+                                op_type=_PREFIX + "fcos_target", name="fcos_target",
+                                data_size=_param_str(tuple(throwout.data_size)), stride=_param_str(tuple(throwout.stride)),
+                                num_classifier=_param_str(p.FCOSParam.num_classifier), **ignore)
+        for i, name in enumerate(("centerness", "offset", "cls_id", "state")):
+            inputs[name] = targets[i]
+        loss = mx.sym.Custom(op_type=_PREFIX + "fcos_loss", name="fcos_loss", num_levels=_param_str(len(strides)),
+                             alpha=_param_str(p.loss_setting.focal_loss_alpha),
+                             gamma=_param_str(p.loss_setting.focal_loss_gamma), **ignore, **inputs)
+        return loss[0], loss[1], loss[2]
+
+    return [get_loss]
 
 
 def patch_fcos_loss(builder_module=None, mx=None):
@@ -3555,65 +3360,29 @@ def patch_fcos_loss(builder_module=None, mx=None):
     num_classifier and the level order from p.FCOSParam.  install(fcos=True) calls this when the builder module is
     importable; returns True when the class was patched.  The original method is kept as `_sd_reference_get_loss`
     (a second install() keeps the first original); a default install() afterwards puts it back."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_FCOS_BUILDER)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _FCOS_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_fcos_loss(module, mx)
-    cls = getattr(builder_module, "FCOSFPNHead", None)
-    if cls is None:
-        return False
-    original = cls.__dict__.get("_sd_reference_get_loss") or cls.get_loss
-
-    def get_loss(self, conv_fpn_feat, gt_bbox, im_info):
-        import sys
-        throwout = getattr(sys.modules.get(_FCOS_CONFIG), "throwout_param", None)
-        table = _state.get("table") or {}
-        why = ("sd_fcos_target / sd_fcos_loss are not registered" if "fcos_loss" not in table else
-               "%s.throwout_param is not set" % _FCOS_CONFIG if throwout is None else "")
-        if why:
-            _state.setdefault("fallbacks", []).append(("fcos_loss", None, why))
-            return original(self, conv_fpn_feat, gt_bbox, im_info)
-        p = self.p
-        centerness_logit_dict, cls_logit_dict, offset_logit_dict = self.get_output(conv_fpn_feat)
-        strides = tuple(p.FCOSParam.stride)
-        ignore = {"ignore_offset": _param_str(p.loss_setting.ignore_offset),
-                  "ignore_label": _param_str(p.loss_setting.ignore_label)}
-        # the reference binds the two inputs by name as well (builder.py:193-194)
-        targets = mx.sym.Custom(gt_bbox=mx.sym.var("gt_bbox"), im_info=mx.sym.var("im_info"),
-                                op_type=_PREFIX + "fcos_target", name="fcos_target",
-                                data_size=_param_str(tuple(throwout.data_size)), stride=_param_str(tuple(throwout.stride)),
-                                num_classifier=_param_str(p.FCOSParam.num_classifier), **ignore)
-        inputs = {}
-        for prefix, d in (("cls_logit_%d", cls_logit_dict), ("centerness_logit_%d", centerness_logit_dict),
-                          ("offset_logit_%d", offset_logit_dict)):
-            for i, stride in enumerate(strides):
-                inputs[prefix % i] = d[stride]
-        for i, name in enumerate(("centerness", "offset", "cls_id", "state")):
-            inputs[name] = targets[i]
-        loss = mx.sym.Custom(op_type=_PREFIX + "fcos_loss", name="fcos_loss", num_levels=_param_str(len(strides)),
-                             alpha=_param_str(p.loss_setting.focal_loss_alpha),
-                             gamma=_param_str(p.loss_setting.focal_loss_gamma), **ignore, **inputs)
-        return loss[0], loss[1], loss[2]
-
-    cls._sd_reference_get_loss = original
-    cls.get_loss = get_loss
-    return True
+    return _rebind(_FEATURES["fcos"], builder_module, mx)
 
 
 def unpatch_fcos_loss(builder_module):
     """Put the reference's get_loss back."""
-    cls = getattr(builder_module, "FCOSFPNHead", None)
-    original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
-    if original is None:
-        return False
-    cls.get_loss = original
-    return True
+    return _restore(_FEATURES["fcos"], builder_module)
+
+
+def _fcos_decode_methods(mx, builder_module, originals):
+    def get_all_proposal(self, conv_fpn_feat, im_info):
+        if not _registered("fcos_decode"):
+            return originals[0](self, conv_fpn_feat, im_info)
+        p = self.p
+        strides, inputs = _fcos_level_inputs(self, conv_fpn_feat)
+        inputs["im_info"] = im_info
+        out = mx.sym.Custom(op_type=_PREFIX + "fcos_decode", name="fcos_decode", stride=_param_str(strides),
+                            pre_nms_top_n=_param_str(int(p.proposal.pre_nms_top_n)),
+                            pre_nms_thresh=_param_str(p.proposal.pre_nms_thresh), input_logits="1", **inputs)
+        bboxes, score = out[0], out[1]
+        self._proposal = score, bboxes
+        return score, bboxes
+
+    return [get_all_proposal]
 
 
 def patch_fcos_decode(builder_module=None, mx=None):
@@ -3627,65 +3396,16 @@ def patch_fcos_decode(builder_module=None, mx=None):
     install(fcos_decode=True) calls this when the builder module is importable; returns True when the class was
     patched.  The original method is kept as `_sd_reference_get_all_proposal` (a second install() keeps the first
     original); a default install() afterwards puts it back."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_FCOS_BUILDER)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _FCOS_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_fcos_decode(module, mx)
-    cls = getattr(builder_module, "FCOSFPNHead", None)
-    if cls is None:
-        return False
-    original = cls.__dict__.get("_sd_reference_get_all_proposal") or cls.get_all_proposal
-
-    def get_all_proposal(self, conv_fpn_feat, im_info):
-        table = _state.get("table") or {}
-        if "fcos_decode" not in table:
-            _state.setdefault("fallbacks", []).append(("fcos_decode", None, "sd_fcos_decode is not registered"))
-            return original(self, conv_fpn_feat, im_info)
-        p = self.p
-        centerness_logit_dict, cls_logit_dict, offset_logit_dict = self.get_output(conv_fpn_feat)
-        strides = tuple(p.FCOSParam.stride)
-        inputs = {}
-        for prefix, d in (("cls_logit_%d", cls_logit_dict), ("centerness_logit_%d", centerness_logit_dict),
-                          ("offset_logit_%d", offset_logit_dict)):
-            for i, stride in enumerate(strides):
-                inputs[prefix % i] = d[stride]
-        inputs["im_info"] = im_info
-        out = mx.sym.Custom(op_type=_PREFIX + "fcos_decode", name="fcos_decode", stride=_param_str(strides),
-                            pre_nms_top_n=_param_str(int(p.proposal.pre_nms_top_n)),
-                            pre_nms_thresh=_param_str(p.proposal.pre_nms_thresh), input_logits="1", **inputs)
-        bboxes, score = out[0], out[1]
-        self._proposal = score, bboxes
-        return score, bboxes
-
-    cls._sd_reference_get_all_proposal = original
-    cls.get_all_proposal = get_all_proposal
-    return True
+    return _rebind(_FEATURES["fcos_decode"], builder_module, mx)
 
 
 def unpatch_fcos_decode(builder_module):
     """Put the reference's get_all_proposal back."""
-    cls = getattr(builder_module, "FCOSFPNHead", None)
-    original = cls.__dict__.get("_sd_reference_get_all_proposal") if cls is not None else None
-    if original is None:
-        return False
-    cls.get_all_proposal = original
-    return True
-
-
-_REPPOINTS_BUILDER = "models.RepPoints.builder"
+    return _restore(_FEATURES["fcos_decode"], builder_module)
 
 
 def _reppoints_unsupported(p):
     """why the device ops do not take this head, or ''"""
-    table = _state.get("table") or {}
-    if "reppoints_box_loss" not in table:
-        return "sd_reppoints_target / sd_reppoints_box_loss are not registered"
     if p.fp16:
         return "fp16: the device ops are float32"
     if not 1 <= len(p.point_generate.stride) <= 8:
@@ -3699,42 +3419,13 @@ def _reppoints_unsupported(p):
     return ""
 
 
-def patch_reppoints_loss(builder_module=None, mx=None):
-    """Route the RepPoints training head to the device ops WITHOUT editing the reference: rebinds
-    `RepPointsHead.get_loss` of models/RepPoints/builder.py:311-484 -- per level _gen_points, _offset_to_boxes and two
-    _offset_to_pts, per image _point_assign and _iou_assign, three _points2bbox, two smooth_l1 / BBoxNorm / MakeLoss
-    chains -- to a method that calls `self.get_output(conv_feat)` and emits
-        sd_reppoints_target(the L init point maps, gt_bbox, moment_transfer)
-        sd_reppoints_box_loss(the L init and L refine point maps, moment_transfer, the five targets)
-    and keeps the class branch as it is: the per-level transpose and reshape, the concat and X.focal_loss on
-    label_refine.  Every parameter is read from self.p as the reference reads it.  Returns the reference's five
-    outputs in order: cls_loss, pts_init_loss, pts_refine_loss and label_refine twice behind BlockGrad.  A head
-    with p.fp16 set, or beyond the limits of the device ops, goes back to the original method
-    (`_state["fallbacks"]` records why).  install(reppoints=True) calls this when the builder module is importable;
-    returns True when the class was patched.  The original is kept as `_sd_reference_get_loss` (a second install()
-    keeps the first original); a default install() afterwards puts it back."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_REPPOINTS_BUILDER)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _REPPOINTS_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_reppoints_loss(module, mx)
-    cls = getattr(builder_module, "RepPointsHead", None)
-    if cls is None:
-        return False
-    original = cls.__dict__.get("_sd_reference_get_loss") or cls.get_loss
-    X = builder_module.X
-
+def _reppoints_loss_methods(mx, builder_module, originals):
     def get_loss(self, conv_feat, gt_bbox):
         p = self.p
-        why = _reppoints_unsupported(p)
-        if why:
-            _state.setdefault("fallbacks", []).append(("reppoints_box_loss", None, why))
-            return original(self, conv_feat, gt_bbox)
+        if not _registered("reppoints_box_loss", "sd_reppoints_target / sd_reppoints_box_loss are not registered") or \
+                _fell_back("reppoints_box_loss", _reppoints_unsupported(p)):
+            return originals[0](self, conv_feat, gt_bbox)
+        X = builder_module.X                         # the builder's own `import mxnext as X`
         stride = tuple(p.point_generate.stride)
         pts_out_inits, pts_out_refines, cls_outs = self.get_output(conv_feat)
         geometry = {"stride": _param_str(stride), "num_points": _param_str(p.point_generate.num_points),
@@ -3765,26 +3456,33 @@ def patch_reppoints_loss(builder_module=None, mx=None):
         points_refine_labels = X.block_grad(points_labels_refine, name="point_refine_labels")
         return cls_loss, loss[0], loss[1], points_init_labels, points_refine_labels
 
-    cls._sd_reference_get_loss = original
-    cls.get_loss = get_loss
-    return True
+    return [get_loss]
+
+
+def patch_reppoints_loss(builder_module=None, mx=None):
+    """Route the RepPoints training head to the device ops WITHOUT editing the reference: rebinds
+    `RepPointsHead.get_loss` of models/RepPoints/builder.py:311-484 -- per level _gen_points, _offset_to_boxes and two
+    _offset_to_pts, per image _point_assign and _iou_assign, three _points2bbox, two smooth_l1 / BBoxNorm / MakeLoss
+    chains -- to a method that calls `self.get_output(conv_feat)` and emits
+        sd_reppoints_target(the L init point maps, gt_bbox, moment_transfer)
+        sd_reppoints_box_loss(the L init and L refine point maps, moment_transfer, the five targets)
+    and keeps the class branch as it is: the per-level transpose and reshape, the concat and X.focal_loss on
+    label_refine.  Every parameter is read from self.p as the reference reads it.  Returns the reference's five
+    outputs in order: cls_loss, pts_init_loss, pts_refine_loss and label_refine twice behind BlockGrad.  A head
+    with p.fp16 set, or beyond the limits of the device ops, goes back to the original method
+    (`_state["fallbacks"]` records why).  install(reppoints=True) calls this when the builder module is importable;
+    returns True when the class was patched.  The original is kept as `_sd_reference_get_loss` (a second install()
+    keeps the first original); a default install() afterwards puts it back."""
+    return _rebind(_FEATURES["reppoints"], builder_module, mx)
 
 
 def unpatch_reppoints_loss(builder_module):
     """Put the reference's get_loss back."""
-    cls = getattr(builder_module, "RepPointsHead", None)
-    original = cls.__dict__.get("_sd_reference_get_loss") if cls is not None else None
-    if original is None:
-        return False
-    cls.get_loss = original
-    return True
+    return _restore(_FEATURES["reppoints"], builder_module)
 
 
 def _reppoints_decode_unsupported(p):
     """why the device op does not take this head's test graph, or ''"""
-    table = _state.get("table") or {}
-    if "reppoints_decode" not in table:
-        return "sd_reppoints_decode is not registered"
     if p.fp16:
         return "fp16: the device op is float32"
     if not 1 <= len(p.point_generate.stride) <= 8:
@@ -3794,6 +3492,25 @@ def _reppoints_decode_unsupported(p):
     if int(p.proposal.pre_nms_top_n) > 16384:
         return "pre_nms_top_n=%s, the limit is 16384" % (p.proposal.pre_nms_top_n,)
     return ""
+
+
+def _reppoints_decode_methods(mx, builder_module, originals):
+    def get_prediction(self, conv_feat, im_info):
+        p = self.p
+        if not _registered("reppoints_decode") or _fell_back("reppoints_decode", _reppoints_decode_unsupported(p)):
+            return originals[0](self, conv_feat, im_info)
+        stride = tuple(p.point_generate.stride)
+        _, pts_out_refines, cls_outs = self.get_output(conv_feat)
+        inputs = {"cls_logit_%d" % i: cls_outs["stride%s" % s] for i, s in enumerate(stride)}
+        inputs.update({"pts_refine_%d" % i: pts_out_refines["stride%s" % s] for i, s in enumerate(stride)})
+        out = mx.sym.Custom(op_type=_PREFIX + "reppoints_decode", name="reppoints_decode", **inputs, im_info=im_info,
+                            moment_transfer=self.moment_transfer, stride=_param_str(stride),
+                            pre_nms_top_n=_param_str(int(p.proposal.pre_nms_top_n)),
+                            transform=_param_str(p.point_generate.transform),
+                            num_points=_param_str(p.point_generate.num_points), input_logits="1")
+        return out[0], out[1]
+
+    return [get_prediction]
 
 
 def patch_reppoints_decode(builder_module=None, mx=None):
@@ -3810,87 +3527,18 @@ def patch_reppoints_decode(builder_module=None, mx=None):
     the builder module is importable; returns True when the class was patched.  The original method is kept as
     `_sd_reference_get_prediction` (a second install() keeps the first original); a default install() afterwards
     puts it back."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_REPPOINTS_BUILDER)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _REPPOINTS_BUILDER.startswith(e.name):
-                raise
-            return False
-        return patch_reppoints_decode(module, mx)
-    cls = getattr(builder_module, "RepPointsHead", None)
-    if cls is None:
-        return False
-    original = cls.__dict__.get("_sd_reference_get_prediction") or cls.get_prediction
-
-    def get_prediction(self, conv_feat, im_info):
-        p = self.p
-        why = _reppoints_decode_unsupported(p)
-        if why:
-            _state.setdefault("fallbacks", []).append(("reppoints_decode", None, why))
-            return original(self, conv_feat, im_info)
-        stride = tuple(p.point_generate.stride)
-        _, pts_out_refines, cls_outs = self.get_output(conv_feat)
-        inputs = {"cls_logit_%d" % i: cls_outs["stride%s" % s] for i, s in enumerate(stride)}
-        inputs.update({"pts_refine_%d" % i: pts_out_refines["stride%s" % s] for i, s in enumerate(stride)})
-        out = mx.sym.Custom(op_type=_PREFIX + "reppoints_decode", name="reppoints_decode", **inputs, im_info=im_info,
-                            moment_transfer=self.moment_transfer, stride=_param_str(stride),
-                            pre_nms_top_n=_param_str(int(p.proposal.pre_nms_top_n)),
-                            transform=_param_str(p.point_generate.transform),
-                            num_points=_param_str(p.point_generate.num_points), input_logits="1")
-        return out[0], out[1]
-
-    cls._sd_reference_get_prediction = original
-    cls.get_prediction = get_prediction
-    return True
+    return _rebind(_FEATURES["reppoints_decode"], builder_module, mx)
 
 
 def unpatch_reppoints_decode(builder_module):
     """Put the reference's get_prediction back."""
-    cls = getattr(builder_module, "RepPointsHead", None)
-    original = cls.__dict__.get("_sd_reference_get_prediction") if cls is not None else None
-    if original is None:
-        return False
-    cls.get_prediction = original
-    return True
+    return _restore(_FEATURES["reppoints_decode"], builder_module)
 
 
-_TSD_POOLINGS = "models.TSD.poolings"
-_TSD_EXTRACTORS = (("FPNRoIAlign_DeltaC", "delta_c"), ("FPNRoIAlign_DeltaR", "delta_r"))
-
-
-def patch_tsd_pool(builder_module=None, mx=None):
-    """Route TSD's two RoI extractors to the fused op WITHOUT editing the reference: rebinds
-    `FPNRoIAlign_DeltaC.get_roi_feature` and `FPNRoIAlign_DeltaR.get_roi_feature` of models/TSD/poolings.py:51-174
-    (fpn_roi_assign_offset -> per stride the masked rois and offsets, a concat with the batch column and
-    DeformablePSROIPooling -> add_n) to a method that emits ONE
-        sd_fpn_deform_roi_pool(the level features, rois (B,R,4), trans reshaped to (B*R,2,P,P) | (B*R,2))
-    node and returns the same (B*R, C, out, out) symbol (fp16 graphs: cast to fp32 before, back to fp16 after, as
-    :71-76, 104-105).  get_roi_feature_test calls get_roi_feature (:109-110, 173-174), so test graphs follow.
-    install(tsd_pool=True) calls this when the module is importable; returns True when both classes were patched.
-    The originals are kept as `_sd_reference_get_roi_feature`; a default install() afterwards puts them back."""
-    mx = mx or _state["mx"]
-    if builder_module is None:
-        import importlib
-        try:
-            module = importlib.import_module(_TSD_POOLINGS)
-        except ModuleNotFoundError as e:
-            if e.name is None or not _TSD_POOLINGS.startswith(e.name):
-                raise
-            return False
-        return patch_tsd_pool(module, mx)
-    classes = [getattr(builder_module, n, None) for n, _ in _TSD_EXTRACTORS]
-    if any(c is None for c in classes):
-        return False
-
+def _tsd_pool_methods(mx, builder_module, originals):
     def make(original, tag, per_roi):
         def get_roi_feature(self, conv_fpn_feat, rois, trans, image_rois, batch_image):
-            table = _state.get("table") or {}
-            if "fpn_deform_roi_pool" not in table:
-                _state.setdefault("fallbacks", []).append(("fpn_deform_roi_pool", None,
-                                                           "sd_fpn_deform_roi_pool is not registered"))
+            if not _registered("fpn_deform_roi_pool"):
                 return original(self, conv_fpn_feat, rois, trans, image_rois, batch_image)
             p = self.p
             strides = tuple(int(s) for s in p.stride)
@@ -3915,24 +3563,93 @@ def patch_tsd_pool(builder_module=None, mx=None):
             return roi_feat
         return get_roi_feature
 
-    for cls, (_, tag) in zip(classes, _TSD_EXTRACTORS):
-        original = cls.__dict__.get("_sd_reference_get_roi_feature") or cls.get_roi_feature
-        cls._sd_reference_get_roi_feature = original
-        cls.get_roi_feature = make(original, tag, tag == "delta_r")
-    return True
+    return [make(originals[0], "delta_c", False), make(originals[1], "delta_r", True)]
+
+
+def patch_tsd_pool(builder_module=None, mx=None):
+    """Route TSD's two RoI extractors to the fused op WITHOUT editing the reference: rebinds
+    `FPNRoIAlign_DeltaC.get_roi_feature` and `FPNRoIAlign_DeltaR.get_roi_feature` of models/TSD/poolings.py:51-174
+    (fpn_roi_assign_offset -> per stride the masked rois and offsets, a concat with the batch column and
+    DeformablePSROIPooling -> add_n) to a method that emits ONE
+        sd_fpn_deform_roi_pool(the level features, rois (B,R,4), trans reshaped to (B*R,2,P,P) | (B*R,2))
+    node and returns the same (B*R, C, out, out) symbol (fp16 graphs: cast to fp32 before, back to fp16 after, as
+    :71-76, 104-105).  get_roi_feature_test calls get_roi_feature (:109-110, 173-174), so test graphs follow.
+    install(tsd_pool=True) calls this when the module is importable; returns True when both classes were patched.
+    The originals are kept as `_sd_reference_get_roi_feature`; a default install() afterwards puts them back."""
+    return _rebind(_FEATURES["tsd_pool"], builder_module, mx)
 
 
 def unpatch_tsd_pool(builder_module):
     """Put the reference's two get_roi_feature methods back."""
-    done = False
-    for n, _ in _TSD_EXTRACTORS:
-        cls = getattr(builder_module, n, None)
-        original = cls.__dict__.get("_sd_reference_get_roi_feature") if cls is not None else None
-        if original is not None:
-            cls.get_roi_feature = original
-            done = True
-    return done
+    return _restore(_FEATURES["tsd_pool"], builder_module)
 
+
+# The opt-in features, in the order install() handles them (the order of their _state["fallbacks"] entries).  Two
+# differences between the entries are kept on purpose: only the features from fcos_decode on record a fallback when
+# their builder is not importable (bbox_post, mask_loss and fcos never did, and default users would see new entries),
+# and bbox_post alone imports leniently (a msrcnn builder that fails to import for a reason of its own must not break
+# install(bbox_post=True) for Mask R-CNN).
+_FEATURES = {f.flag: f for f in (
+    _Feature("retina", ("_contrib_GenProposalRetina",),
+             "RetinaNet's test-time decode (models/retinanet/builder.py:358-389) in place of the native operator; "
+             "iou_loss / batch_wise_anchor calls stay native"),
+    _Feature("proposal", ("_contrib_Proposal_v2", "_contrib_Proposal"),
+             "the TridentNet / C4 proposal operators in place of the native ones, and X.proposal where mxnext builds "
+             "_contrib_Proposal", state="proposal"),
+    _Feature("bbox_post", ("BboxPostProcessing",),
+             "Mask R-CNN's and Mask Scoring R-CNN's test-time per-class NMS in place of the reference's numpy CustomOp",
+             state="bbox_post_patched", builders=("models.maskrcnn.builder", "models.msrcnn.builder"),
+             methods=(("BboxPostProcessor", "get_post_processing"),), maker=_bbox_post_methods, lenient=True),
+    _Feature("retina_loss", ("_contrib_FocalLoss", "_contrib_BBoxNorm"),
+             "the RetinaNet / RepPoints train losses in place of the native operators, and X.focal_loss / X.bbox_norm",
+             state="retina_loss"),
+    _Feature("group_norm", ("_contrib_GroupNorm",),
+             "the normaliser of the GN Mask R-CNN, RepPoints and EfficientNet graphs in place of the native operator, "
+             "and X.group_norm where mxnext has one", state="group_norm"),
+    _Feature("mask_loss", ("_contrib_SigmoidCrossEntropy", "MaskLoss"),
+             "the aliased SigmoidCrossEntropy, and ONE fused node in place of Mask R-CNN's mask-loss subgraph",
+             state="mask_loss_patched", builders=("models.maskrcnn.builder",),
+             methods=(("MaskFasterRcnnHead", "get_loss"),), maker=_mask_loss_methods),
+    _Feature("quant_int8", ("_contrib_Quantization_int8",),
+             "the fake-quantise node utils/graph_optimize.py attaches in the int8 graphs, in place of the native "
+             "operator; per-channel weights and other quant / grad modes stay native"),
+    _Feature("fcos", ("fcos_target", "fcos_loss"),
+             "two nodes in place of the target and loss subgraphs of the FCOS train graph",
+             state="fcos_patched", builders=("models.FCOS.builder",), methods=(("FCOSFPNHead", "get_loss"),),
+             maker=_fcos_loss_methods),
+    _Feature("fcos_decode", ("fcos_decode",),
+             "ONE node in place of the sigmoids and the Python CustomOps of the FCOS test graph (independent of fcos)",
+             state="fcos_decode_patched", builders=("models.FCOS.builder",),
+             methods=(("FCOSFPNHead", "get_all_proposal"),), maker=_fcos_decode_methods,
+             fallback=("fcos_decode", "%s.FCOSFPNHead is not importable")),
+    _Feature("tsd_pool", ("_contrib_DeformablePSROIPooling", "fpn_deform_roi_pool"),
+             "the aliased DeformablePSROIPooling, and ONE fused node per TSD RoI extractor",
+             state="tsd_pool_patched", builders=("models.TSD.poolings",),
+             methods=(("FPNRoIAlign_DeltaC", "get_roi_feature"), ("FPNRoIAlign_DeltaR", "get_roi_feature")),
+             maker=_tsd_pool_methods, fallback=("fpn_deform_roi_pool", "%s is not importable")),
+    _Feature("reppoints", ("reppoints_target", "reppoints_box_loss"),
+             "two nodes in place of both assigners and both box-loss subgraphs of the RepPoints train graphs",
+             state="reppoints_patched", builders=("models.RepPoints.builder",),
+             methods=(("RepPointsHead", "get_loss"),), maker=_reppoints_loss_methods,
+             fallback=("reppoints_box_loss", "%s.RepPointsHead is not importable")),
+    _Feature("msrcnn", ("MsrcnnMaskLoss", "MaskIoULoss"),
+             "two nodes in place of the mask-loss and MaskIoU-loss subgraphs of the Mask Scoring R-CNN train graphs "
+             "(independent of mask_loss)",
+             state="msrcnn_patched", builders=("models.msrcnn.builder",),
+             methods=(("MaskFasterRcnnHead", "get_loss"), ("MaskIoUConvHead", "get_loss")), maker=_msrcnn_methods,
+             fallback=("MaskIoULoss", "%s is not importable")),
+    _Feature("reppoints_decode", ("reppoints_decode",),
+             "ONE node in place of the per-level decode subgraphs of the RepPoints test graphs (independent of reppoints)",
+             state="reppoints_decode_patched", builders=("models.RepPoints.builder",),
+             methods=(("RepPointsHead", "get_prediction"),), maker=_reppoints_decode_methods,
+             fallback=("reppoints_decode", "%s.RepPointsHead is not importable")),
+    _Feature("crowdhuman", ("bbox_target", "doublebbox_target", "emd_loss"),
+             "ONE device target node in place of the Python CustomOp, and ONE node per emd_loss call, in the CrowdHuman "
+             "train graphs",
+             state="crowdhuman_patched", builders=("models.crowdhuman.builder",), methods=_CROWDHUMAN_METHODS,
+             maker=_crowdhuman_methods, fallback=("emd_loss", "%s is not importable")),
+)}
+FEATURE_FLAGS = tuple(_FEATURES)
 
 def _head_op(mx, sym):
     """(operator name, attrs) of the node behind a symbol: real MXNet through the graph JSON (a

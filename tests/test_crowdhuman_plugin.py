@@ -37,9 +37,7 @@ def test_default_install_registers_nothing_new():
     try:
         assert not any(n in props for n in NEW) and not any("sd_" + n in mx.registry for n in NEW)
         assert mxnet_plugin._state["crowdhuman_patched"] is False
-        mx2, props2, _ = _fresh(retina=True, proposal=True, bbox_post=True, retina_loss=True, group_norm=True,
-                                mask_loss=True, quant_int8=True, fcos=True, fcos_decode=True, tsd_pool=True,
-                                reppoints=True, msrcnn=True, reppoints_decode=True)
+        mx2, props2, _ = _fresh(**{f: True for f in mxnet_plugin.FEATURE_FLAGS if f != "crowdhuman"})
         assert not any(n in props2 for n in NEW) and not any("sd_" + n in mx2.registry for n in NEW)
     finally:
         mxnet_plugin._state.update(registered=False)

@@ -34,8 +34,8 @@ def plugin():
 
 
 def test_default_and_fcos_installs_register_nothing_new():
-    for flags in ({}, dict(fcos=True), dict(retina=True, proposal=True, bbox_post=True, retina_loss=True,
-                                            group_norm=True, mask_loss=True, quant_int8=True, fcos=True)):
+    from simpledet_amd.mxnet_plugin import FEATURE_FLAGS
+    for flags in ({}, dict(fcos=True), {f: True for f in FEATURE_FLAGS if f != "fcos_decode"}):
         mx, props, mxnet_plugin = _fresh(**flags)
         try:
             assert "fcos_decode" not in props and "sd_fcos_decode" not in mx.registry

@@ -40,8 +40,7 @@ def test_default_install_registers_nothing_new():
         assert "fcos_target" not in props and "fcos_loss" not in props
         assert "sd_fcos_target" not in mx.registry and "sd_fcos_loss" not in mx.registry
         assert mxnet_plugin._state["fcos_patched"] is False
-        mx2, props2, _ = _fresh(retina=True, proposal=True, bbox_post=True, retina_loss=True, group_norm=True,
-                                mask_loss=True, quant_int8=True)
+        mx2, props2, _ = _fresh(**{f: True for f in mxnet_plugin.FEATURE_FLAGS if f != "fcos"})
         assert "fcos_target" not in props2 and "sd_fcos_loss" not in mx2.registry
     finally:
         mxnet_plugin._state.update(registered=False)

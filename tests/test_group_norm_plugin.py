@@ -40,7 +40,7 @@ def test_default_install_registers_nothing_new_and_leaves_the_graph_alone():
         assert node[0] == "native GroupNorm"
         assert not hasattr(mx.sym.contrib, "_sd_reference_GroupNorm")
         # the other opt-in flags do not bring it in either
-        mx2, props2, _ = _fresh(retina=True, proposal=True, bbox_post=True, retina_loss=True)
+        mx2, props2, _ = _fresh(**{f: True for f in mxnet_plugin.FEATURE_FLAGS if f != "group_norm"})
         assert "_contrib_GroupNorm" not in props2 and mx2.sym.contrib.GroupNorm is _native
         # an mxnext-level wrapper is left alone without the flag
         X = types.SimpleNamespace(group_norm=_native)

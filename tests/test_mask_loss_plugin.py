@@ -52,7 +52,7 @@ def test_default_install_registers_nothing_new_and_leaves_the_graph_alone():
         assert mx.sym.contrib.SigmoidCrossEntropy(v("a"), v("b"), grad_scale=1.0, name="mask_loss")[0] \
             == "native SigmoidCrossEntropy"
         # the other opt-in flags do not bring it in either
-        mx2, props2, _ = _fresh(retina=True, proposal=True, bbox_post=True, retina_loss=True, group_norm=True)
+        mx2, props2, _ = _fresh(**{f: True for f in mxnet_plugin.FEATURE_FLAGS if f != "mask_loss"})
         assert "_contrib_SigmoidCrossEntropy" not in props2 and mx2.sym.contrib.SigmoidCrossEntropy is _native
     finally:
         mxnet_plugin._state.update(registered=False)

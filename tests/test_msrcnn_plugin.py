@@ -39,9 +39,8 @@ def plugin():
 
 
 def test_the_flag_is_opt_in_and_independent_of_mask_loss():
-    for flags in ({}, dict(mask_loss=True), dict(retina=True, proposal=True, bbox_post=True, retina_loss=True,
-                                                  group_norm=True, mask_loss=True, quant_int8=True, fcos=True,
-                                                  fcos_decode=True, tsd_pool=True, reppoints=True)):
+    from simpledet_amd.mxnet_plugin import FEATURE_FLAGS
+    for flags in ({}, dict(mask_loss=True), {f: True for f in FEATURE_FLAGS if f != "msrcnn"}):
         mx, props, plug = _fresh(**flags)
         try:
             assert "MsrcnnMaskLoss" not in props and "MaskIoULoss" not in props
@@ -59,7 +58,8 @@ def test_the_flag_is_opt_in_and_independent_of_mask_loss():
 
 def test_an_unimportable_builder_lands_in_the_fallbacks(monkeypatch):
     from simpledet_amd import mxnet_plugin
-    monkeypatch.setattr(mxnet_plugin, "_MSRCNN_BUILDER", "models.msrcnn.no_such_builder")
+    entry = mxnet_plugin._FEATURES["msrcnn"]
+    monkeypatch.setitem(mxnet_plugin._FEATURES, "msrcnn", entry._replace(builders=("models.msrcnn.no_such_builder",)))
     mx, props, plug = _fresh(msrcnn=True)
     try:
         assert "sd_MsrcnnMaskLoss" in mx.registry and "sd_MaskIoULoss" in mx.registry       # registered all the same
@@ -71,7 +71,7 @@ def test_an_unimportable_builder_lands_in_the_fallbacks(monkeypatch):
         import types
         broken = types.ModuleType("sd_test_broken_builder")
         monkeypatch.setitem(sys.modules, "sd_test_broken_builder", broken)
-        monkeypatch.setattr(plug, "_MSRCNN_BUILDER", "sd_test_broken_builder")
+        monkeypatch.setitem(plug._FEATURES, "msrcnn", entry._replace(builders=("sd_test_broken_builder",)))
         assert plug.patch_msrcnn_loss(mx=mx) is False
     finally:
         plug._state.update(registered=False)

@@ -46,8 +46,7 @@ def test_default_install_registers_nothing_new_and_leaves_the_constructor_alone(
         v = mx.sym.Variable
         assert mx.sym.contrib.Quantization_int8(data=v("d"), minmax=v("m"), **ACT_ATTRS)[0].startswith("native")
         assert not hasattr(mx.sym.contrib, "_sd_reference_Quantization_int8")
-        mx2, props2, _ = _fresh(retina=True, proposal=True, bbox_post=True, retina_loss=True, group_norm=True,
-                                mask_loss=True)
+        mx2, props2, _ = _fresh(**{f: True for f in mxnet_plugin.FEATURE_FLAGS if f != "quant_int8"})
         assert NAME not in props2 and mx2.sym.contrib.Quantization_int8 is _native
     finally:
         mxnet_plugin._state.update(registered=False)

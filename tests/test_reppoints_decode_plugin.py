@@ -37,9 +37,8 @@ def plugin():
 
 
 def test_default_and_other_installs_register_nothing_new():
-    for flags in ({}, dict(reppoints=True), dict(retina=True, proposal=True, bbox_post=True, retina_loss=True,
-                                                 group_norm=True, mask_loss=True, quant_int8=True, fcos=True,
-                                                 fcos_decode=True, tsd_pool=True, reppoints=True, msrcnn=True)):
+    from simpledet_amd.mxnet_plugin import FEATURE_FLAGS
+    for flags in ({}, dict(reppoints=True), {f: True for f in FEATURE_FLAGS if f != "reppoints_decode"}):
         mx, props, mxnet_plugin = _fresh(**flags)
         try:
             assert "reppoints_decode" not in props and "sd_reppoints_decode" not in mx.registry

@@ -47,8 +47,8 @@ def _find(sym, op_type):
 
 
 def test_default_installs_register_nothing_new():
-    for flags in ({}, dict(retina=True, proposal=True, bbox_post=True, retina_loss=True, group_norm=True,
-                           mask_loss=True, quant_int8=True, fcos=True, fcos_decode=True)):
+    from simpledet_amd.mxnet_plugin import FEATURE_FLAGS
+    for flags in ({}, {f: True for f in FEATURE_FLAGS if f != "tsd_pool"}):
         mx = mx_stub.make_stub()
         plug, props = _install(mx, **flags)
         try:
