@@ -232,9 +232,30 @@ constexpr int kBandNP = 4;              // passes a wave keeps in registers (one
 constexpr int kBandMaxUnits = 512;      // virtual units ((level, image, band) x rounds of items) of one launch
 constexpr int kBandFillCost = 140, kBandPlaneCost = 60, kBandSetupCost = 1500;  // cost model, in item times
 constexpr int kBandSub = 4;             // list segments per unit (pre-pass workgroups per (level, image))
+constexpr int kBandXcdDefault = 1;      // roi_align_fwd_xcd when not set
 constexpr int kBandFallbackWGs = 0;    // (no separate exact-path blocks: the band workgroups do that work last)
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+
+// Share index of band workgroup wg among nwg (roi_align_fwd_xcd >= 1).  Block b runs on XCD b % kNumXCD, and a
+// workgroup starts where its share of the cost prefix falls; with the shares dealt XCD-major, XCD x owns the x-th
+// eighth of the prefix, so the workgroups that share a unit (and the units of neighbouring bands) write their
+// channel runs through ONE L2: a cache line two grabs share leaves it once, whole, not as two partial write-backs.
+__host__ __device__ constexpr int band_xcd_slot(int wg, int nwg) {
+  return nwg % kNumXCD == 0 ? (wg % kNumXCD) * (nwg / kNumXCD) + wg / kNumXCD : wg;
+}
+constexpr bool band_xcd_slot_is_bijection(int nwg) {
+  bool seen[1024] = {};
+  if (nwg > 1024) return false;
+  for (int wg = 0; wg < nwg; ++wg) {
+    const int s = band_xcd_slot(wg, nwg);
+    if (s < 0 || s >= nwg || seen[s]) return false;
+    seen[s] = true;
+  }
+  return true;
+}
+static_assert(band_xcd_slot_is_bijection(256) && band_xcd_slot_is_bijection(250) && band_xcd_slot(9, 256) == 33,
+              "every share is taken by exactly one workgroup");
 
 struct BandPlan {
   int owned[SD_MAX_FPN_LEVELS];      // rows a band owns (H: the whole plane is one band)
@@ -250,7 +271,8 @@ struct BandPlan {
   int tail;                          // last per cent of a unit's channels handed out in small pieces
   int tail_planes;                   // planes of such a piece (<= G)
   int pool;
-  uint4* rowent;    // [B*R][pool]  {lo0 | step0 << 20 | empty << 31, lo1 | step1 << 20, a0, a1}
+  int xcd;                           // roi_align_fwd_xcd: 0 shares linear in blockIdx, 1 XCD-contiguous shares, 2 + levels interleaved
+  uint4* rowent;   // [B*R][pool]  {lo0 | step0 << 20 | empty << 31, lo1 | step1 << 20, a0, a1}
   uint4* colent;    // [B*R][pool]  {left0 | dup0 << 12 | left1 << 13 | dup1 << 25 | empty << 26, -, b0, b1}
   float2* rowval;   // [B*R][pool]  sample coordinates (float arg-max outputs only)
   float2* colval;

@@ -587,11 +587,34 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
   constexpr int NB = kBandMaxUnits / kWave;
   __shared__ int s_tot[NB], s_ctot[NB];
   {
+    // roi_align_fwd_xcd = 2: the table is built in an order that interleaves the levels -- unit j of the n_l units of
+    // level l has key (j + 1/2) / n_l, and its place is the number of smaller keys (ties: level, then j), a closed
+    // form per level.  With XCD-contiguous shares every XCD's slice of the cost prefix then holds a like share of
+    // every level's fill bytes (in unit order the P2-only slices, 75 % of the fill bytes, fall to five XCDs).
+    // The places go through the band buffer (nothing else is in it yet); chan_ctr, v_unit and the search for the
+    // next unit index the table as before, so every unit is still finished by whoever visits it.
+    int* perm = reinterpret_cast<int*>(band_smem);
+    if (P.xcd >= 2) {   // (uniform)
+      if (tid < P.nunits) {
+        const int l = level_of(tid), j = tid - P.unit_base[l], nl = a.B * P.nbands[l];
+        int rank = j;
+        for (int k = 0; k < a.L.nlvl; ++k) {
+          if (a.L.stride[k] < 0 || k == l) continue;
+          // units j' of level k with (2 j' + 1) nl < (2 j + 1) nk (k > l), <= (k < l)
+          const int nk = a.B * P.nbands[k], t = (2 * j + 1) * nk - (k > l ? 1 : 0), m = t / nl;
+          const int below = (m + 1) >> 1;
+          rank += below < nk ? below : nk;
+        }
+        perm[rank] = tid;
+      }
+      __syncthreads();
+    }
     // phase A: rounds per unit, scanned inside the wave
-    const int u = wave * kWave + lane;
+    const int place = wave * kWave + lane;
+    const int u = P.xcd >= 2 && place < P.nunits ? perm[place] : place;
     int cnt = 0, rounds = 0, lv = 0, incl = 0;
     if (wave < NB) {
-      if (u < P.nunits) {
+      if ((unsigned)u < (unsigned)P.nunits) {
         lv = level_of(u);
 #pragma unroll
         for (int j = 0; j < kBandSub; ++j) cnt += P.seg[u * kBandSub + j].y;
@@ -647,7 +670,8 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
   int vu = 0;
   {
     // the last virtual unit whose start is <= this workgroup's share of the cost (v_start ascends)
-    const long pos = (long)v_start[nvu] * (2 * wg + 1) / (2 * nwg);
+    const int share = P.xcd >= 1 ? band_xcd_slot(wg, nwg) : wg;
+    const long pos = (long)v_start[nvu] * (2 * share + 1) / (2 * nwg);
     int below = 0;
     for (int k = lane; k < nvu; k += kWave) below += v_start[k] <= pos ? 1 : 0;
     below = wave_sum_i32(below);
@@ -961,6 +985,9 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
             return v2f{t.x, t.y};
           };
           v2f t000 = rd(A0[i]), t001 = rd(A1[i]), t010 = rd(A2[i]), t011 = rd(A3[i]);
+          // (a lane's A4/A5 and A6/A7 rows mostly repeat its A0..A3 rows.  Reading them only where they differ --
+          // exec-masked reads, the other lanes' pairs selected with v_cndmask -- made the step slower at every
+          // share mapping: profiles/fwd_xcd_rowshare_ab.txt; the code is kept as profiles/fwd_rowshare.patch)
           v2f t100 = rd(A4[i]), t101 = rd(A5[i]), t110 = rd(A6[i]), t111 = rd(A7[i]);
           if (anyd[i]) {  // coincident (left, right) columns: both taps are the left pixel
             if (flags[i] & 2) { t000.y = t000.x; t010.y = t010.x; t100.y = t100.x; t110.y = t110.x; }
@@ -1449,6 +1476,10 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     P.gbias = 0;
     P.tail = 0;
     P.tail_planes = 8;
+    // roi_align_fwd_xcd: how the workgroups' shares of the cost prefix map to blocks (see band_xcd_slot and the
+    // kernel's unit table).  Any value computes the same bytes.
+    P.xcd = tuning("roi_align_fwd_xcd", kBandXcdDefault);
+    P.xcd = P.xcd < 0 ? 0 : (P.xcd > 2 ? 2 : P.xcd);
     {
       // virtual units = sum over units of ceil(items / CAP) <= units + floor(all items / CAP), and a RoI
       // has at most POOL items: beyond the table's size the launch goes to the tiled kernels (the
@@ -1537,8 +1568,9 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
 #undef SD_FWD_BAND
       char tail_note[96] = "";
       if (tail) snprintf(tail_note, sizeof(tail_note), " (tail tasks: %d coordinate table + %d backward plan)", ncoord, nbwd);
-      note_dispatch("sd::%s<%d> + sd::roi_align_fwd_band<%d,%s,%s>%s", merged && !tail ? "roi_prep_merged_kernel" : "roi_fwd_prep_kernel",
-                    POOL, POOL, a.amax8 ? "true" : "false", a.half_io ? "true" : "false", tail_note);
+      note_dispatch("sd::%s<%d> + sd::roi_align_fwd_band<%d,%s,%s>%s [roi_align_fwd_xcd = %d]",
+                    merged && !tail ? "roi_prep_merged_kernel" : "roi_fwd_prep_kernel",
+                    POOL, POOL, a.amax8 ? "true" : "false", a.half_io ? "true" : "false", tail_note, P.xcd);
       SD_LAUNCH_CHECK();
       return SD_OK;
     }
