@@ -297,8 +297,20 @@ __device__ __forceinline__ bool codes_name_third(unsigned code) {
   const unsigned z = code ^ 0x02020202u;
   return (ge5 | ((z - 0x01010101u) & ~z & 0x80808080u)) != 0u;
 }
-struct __attribute__((packed, aligned(2))) H4u {
-  __half x, y, z, w;
+// n / d for n < 2^31 as a multiplication: m = ceil(2^s / d), s = 32 + ceil(log2 d) (m <= 2^33, n * m < 2^64;
+// exact while n * d < 2^s, which n < 2^31 guarantees)
+__device__ __forceinline__ unsigned bwd_div_magic(unsigned n, unsigned long long m, int s) {
+  return (unsigned)(((unsigned long long)n * m) >> s);
+}
+static void bwd_set_magic(unsigned d, unsigned long long& m, int& s) {
+  int l = 0;
+  while ((1u << l) < d) ++l;
+  s = 32 + l;
+  m = ((1ULL << s) + d - 1) / d;
+}
+struct __attribute__((packed, aligned(2))) U2h {   // four halves as two words, only 2-byte aligned
+  unsigned x, y;
+  __device__ operator uint2() const { return make_uint2(x, y); }
 };
 template <int PH, int PW, int THREADS, int TCH, int MODE, bool HALF = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))  // <= 64 VGPRs: four 512-thread workgroups per CU
@@ -322,24 +334,31 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
   // ---- block -> (level, image, band, channel) ----
+  // One dependent kernel-argument load and no integer division on the way to the unit's header: the launch slot
+  // is a count over block_end[] (one scalar load, no loop), everything that depends on it sits in one BwdSlot,
+  // and the two quotients are multiplications by the launcher's reciprocals (bwd_set_magic).
   int li = 0;
-  while (li + 1 < a.nlaunch && (int)blockIdx.x >= a.block_end[li]) ++li;
-  const int lvl = a.order[li];
-  const int b0 = (int)blockIdx.x - (li ? a.block_end[li - 1] : 0);
-  const int H = a.L.H[lvl], W = a.L.W[lvl];
-  const int nbands = a.nbands[lvl];
+#pragma unroll
+  for (int i = 0; i + 1 < SD_MAX_FPN_LEVELS; ++i) li += (i + 1 < a.nlaunch && (int)blockIdx.x >= a.block_end[i]) ? 1 : 0;
+  const BwdSlot& sl = a.slot[li];
+  const int lvl = sl.lvl;
+  const int b0 = (int)blockIdx.x - sl.block0;
+  const int H = sl.H, W = sl.W;
+  const int nbands = sl.nbands, band_rows = sl.band_rows;
   int u, c;
   if (a.C % kNumXCD == 0) {  // an XCD keeps a contiguous channel range: dY/argmax lines stay in one L2
     const int xcd = b0 % kNumXCD, j = b0 / kNumXCD, per = a.C / kNumXCD;
-    c = xcd * per + (j % per);
-    u = j / per;
+    u = (int)bwd_div_magic((unsigned)j, a.chan_magic, a.chan_shift);   // j / per
+    c = xcd * per + (j - u * per);
   } else {
-    c = b0 % a.C;
-    u = b0 / a.C;
+    u = (int)bwd_div_magic((unsigned)b0, a.chan_magic, a.chan_shift);  // b0 / C
+    c = b0 - u * a.C;
   }
-  const int img = u / nbands, band = u % nbands;
-  const int row0 = band * a.band_rows[lvl];
-  const int row1 = iminr(row0 + a.band_rows[lvl], H);
+  const int img = (int)bwd_div_magic((unsigned)u, sl.band_magic, sl.band_shift);   // u / nbands
+  const int band = u - img * nbands;
+  const long unit = sl.unit_base + u;   // the (level, image, band) unit in the workspace
+  const int row0 = band * band_rows;
+  const int row1 = iminr(row0 + band_rows, H);
   const int band_elems = (row1 - row0) * W;
   const int plane_pad = (band_elems + 3) & ~3;
   float* plane = smem;
@@ -348,40 +367,6 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   int* nlist = list + a.R;  // [0] count [1] bound [2] max|dY| bits, first chunk [3] non-finite, first chunk [4] max|dY| bits, all [5] range statistic [6] non-finite, all
   int* plane_i = reinterpret_cast<int*>(smem);
   const unsigned plane_lds = lds_offset_of(smem);
-
-  // the RoI boxes (or the unit's list) are in flight while the band is zeroed
-  int* wcnt = nlist + 8;  // [THREADS / 64] scratch of the list builder
-  const int* wl = nullptr;
-  int wl_n = 0, wl_bound = 0, wl_first = 0;
-  float4 rb0 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (TAPS || a.ws_list) {   // (the tap tables come with the lists: MODE 1 carries no list builder)
-    wl = a.ws_list + (long)(a.unit_base[li] + u) * (a.R + 2);
-    wl_n = wl[0];
-    wl_bound = wl[1];
-    if (tid < wl_n) wl_first = wl[2 + tid];
-  } else if (tid < a.R) {
-    rb0 = *reinterpret_cast<const float4*>(a.rois + ((long)img * a.R + tid) * 4);
-  }
-  {
-    float4* p4 = reinterpret_cast<float4*>(smem);
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < plane_pad / 4; i += THREADS) p4[i] = z;
-  }
-  if (tid < 8) nlist[tid] = 0;
-  if (TAPS || wl) {
-    if (tid < wl_n) list[tid] = wl_first;
-    for (int i = tid + THREADS; i < wl_n; i += THREADS) list[i] = wl[2 + i];
-    __syncthreads();  // (nlist cleared)
-    if (tid == 0) {
-      nlist[0] = wl_n;
-      nlist[1] = wl_bound;
-    }
-    __syncthreads();
-  } else if constexpr (!TAPS) {
-    __syncthreads();
-    bwd_band_list<PH, PW, THREADS>(a, lvl, img, nbands, row0, row1, rb0, list, nlist, wcnt);
-  }
-  const int nl = *nlist;
 
   // wave-uniform bases + 32-bit lane offsets (the launcher checks R*C*PP < 2^31)
   const int roi_stride = a.C * PP;
@@ -400,55 +385,138 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
     unsigned code;  // their four arg-max codes, one per byte (255: nothing pooled); FLT: 0 = item present
     int j, b0;      // RoI slot (in the list / in the streamed chunk), first bin
   };
-  auto load_item = [&](int t, int cb, int nli, Item& it) {
-    it.code = 0xffffffffu;
-    it.j = 0;
-    it.b0 = 0;
-    it.g = make_float4(0.f, 0.f, 0.f, 0.f);
+  // An item stays RAW until it is scattered: every lane issues the same loads -- no branch, a lane past the chunk's
+  // end repeats the chunk's last item and nobody uses it -- and nothing here touches a loaded register, so the loads
+  // of the next item stay in flight behind the scatter of the current one.  The last lane of a RoI (TAIL: PP % 4
+  // != 0) fetches the gradients of bins PP-4 .. PP-1, of which only the last PP % 4 are its own (the others belong
+  // to its neighbour), and the code word at 4 * (GP - 1), whose low PP % 4 bytes are codes and the rest row padding;
+  // b0 = PP - 4 marks it, and own_item() sorts that out from b0 alone when the item is used.  fp16 gradients stay
+  // the four halves they are (in g.x, g.y) until then.
+  constexpr int KEEP = TAIL ? PP % 4 : 4;  // bins of its own that the last lane of a RoI holds, in the HIGH slots
+  // lane item t (inside the chunk) of RoI r
+  auto load_item_of = [&](int t, int r, Item& it) {
+    const int j = t / GP, g = t - j * GP;
+    it.j = j;
+    it.b0 = (TAIL && g == GP - 1) ? PP - 4 : 4 * g;
+    const int o = r * roi_stride + it.b0;
+    if constexpr (HALF) {
+      const uint2 h = *reinterpret_cast<const U2h*>(dyb + o);
+      it.g = make_float4(__uint_as_float(h.x), __uint_as_float(h.y), 0.f, 0.f);
+    } else {
+      const F4u v = *reinterpret_cast<const F4u*>(dyb + o);
+      it.g = make_float4(v.x, v.y, v.z, v.w);
+    }
     it.x = it.y = make_float4(-1.f, -1.f, -1.f, -1.f);
-    if (t < nli) {
-      const int j = t / GP, g = t - j * GP;
-      const int r = list[cb + j];
-      it.j = j;
-      it.b0 = 4 * g;
-      unsigned code = FLT ? 0u : *reinterpret_cast<const unsigned*>(amb + r * am_stride + 4 * g);
-      // bins PP-4 .. PP-1 are fetched by the last lane of a RoI, only the last PP % 4 belong to it
-      constexpr int KEEP = TAIL ? PP % 4 : 1;
-      // four gradients at element offset o (fp16: 8 bytes, converted)
-      auto load_g = [&](int o) {
-        if constexpr (HALF) {
-          const H4u h = *reinterpret_cast<const H4u*>(dyb + o);
-          F4u v;
-          v.x = __half2float(h.x); v.y = __half2float(h.y); v.z = __half2float(h.z); v.w = __half2float(h.w);
-          return v;
+    it.code = 0u;
+    if (FLT) {
+      const F4u vx = *reinterpret_cast<const F4u*>(axb + o), vy = *reinterpret_cast<const F4u*>(ayb + o);
+      it.x = make_float4(vx.x, vx.y, vx.z, vx.w);
+      it.y = make_float4(vy.x, vy.y, vy.z, vy.w);
+    } else {
+      it.code = *reinterpret_cast<const unsigned*>(amb + r * am_stride + 4 * g);
+    }
+  };
+  // lane item min(t, nli - 1) of the chunk of nli >= 1 lane items at list slot cb
+  auto load_item = [&](int t, int cb, int nli, Item& it) {
+    t = iminr(t, nli - 1);
+    load_item_of(t, list[cb + t / GP], it);
+  };
+
+  // the RoI boxes (or the unit's list) are in flight while the band is zeroed
+  int* wcnt = nlist + 8;  // [THREADS / 64] scratch of the list builder
+  const int* wl = nullptr;
+  int wl_n = 0, wl_bound = 0, wl_first = 0;
+  float4 rb0 = make_float4(0.f, 0.f, 0.f, 0.f);
+  // TAPS: a chunk's main-table entries are contiguous in the workspace (list order) and depend on neither the list
+  // nor the items, so a chunk is NT float4 per lane: all loads issued at once (load_tap), one wait where they are
+  // written to LDS (store_tap).  The first chunk's leave right behind the unit's header, with the list words.
+  constexpr int NT = TAPS ? (TCH * (TS / 4) + THREADS - 1) / THREADS : 1;
+  const float4* taps_main =
+      TAPS ? reinterpret_cast<const float4*>(a.ws_taps + unit * a.R * (2 * NE)) : nullptr;
+  // (every lane loads: one past the chunk's end repeats its last float4 -- or the unit's first, if the list is empty:
+  // a unit's block is never shorter than that -- and does not store it)
+  static_assert(NT <= 2, "a chunk's tap table is at most two float4 per lane");
+  // (k: the lane's float4 number k of the chunk, 0 .. NT-1)
+  auto load_tap = [&](int cb, int ncur, int k) {
+    return taps_main[cb * (TS / 4) + imaxr(iminr(tid + k * THREADS, ncur * (TS / 4) - 1), 0)];
+  };
+  auto store_tap = [&](int ncur, int k, const float4& v) {
+    if (tid + k * THREADS < ncur * (TS / 4)) reinterpret_cast<float4*>(tab)[tid + k * THREADS] = v;
+  };
+  float4 ta = make_float4(0.f, 0.f, 0.f, 0.f), tb = ta;
+  int r_first = 0;
+  Item cur;
+  cur.g = cur.x = cur.y = make_float4(0.f, 0.f, 0.f, 0.f);
+  cur.code = 0u;
+  cur.j = cur.b0 = 0;
+  if (TAPS || a.ws_list) {   // (the tap tables come with the lists: MODE 1 carries no list builder)
+    wl = a.ws_list + unit * (a.R + 2);
+    wl_n = wl[0];
+    wl_bound = wl[1];
+    // the first chunk's items take their RoI from the list in global memory: their loads leave a round trip behind
+    // the header, with the tables in flight, not behind the list's way through LDS
+    // (no branch: an empty unit fetches the image's RoI 0 for nothing)
+    const int t_first = imaxr(iminr(tid, iminr(TCH, wl_n) * GP - 1), 0);
+    if (TAPS) r_first = wl[2 + t_first / GP];
+    if (tid < wl_n) wl_first = wl[2 + tid];
+    if constexpr (TAPS) {
+      ta = load_tap(0, iminr(TCH, wl_n), 0);
+      if (NT > 1) tb = load_tap(0, iminr(TCH, wl_n), 1);
+    }
+    if (TAPS) load_item_of(t_first, wl_n > 0 ? r_first : 0, cur);
+  } else if (tid < a.R) {
+    rb0 = *reinterpret_cast<const float4*>(a.rois + ((long)img * a.R + tid) * 4);
+  }
+  {
+    float4* p4 = reinterpret_cast<float4*>(smem);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < plane_pad / 4; i += THREADS) p4[i] = z;
+  }
+  if (TAPS || wl) {   // the count and the bound are wave uniform from the header: one barrier publishes everything
+    if (tid < 8) nlist[tid] = tid == 0 ? wl_n : tid == 1 ? wl_bound : 0;
+    if (tid < wl_n) list[tid] = wl_first;
+    for (int i = tid + THREADS; i < wl_n; i += THREADS) list[i] = wl[2 + i];
+    if constexpr (TAPS) {
+      store_tap(iminr(TCH, wl_n), 0, ta);
+      if (NT > 1) store_tap(iminr(TCH, wl_n), 1, tb);
+    }
+    __syncthreads();
+  } else if constexpr (!TAPS) {
+    if (tid < 8) nlist[tid] = 0;
+    __syncthreads();
+    bwd_band_list<PH, PW, THREADS>(a, lvl, img, nbands, row0, row1, rb0, list, nlist, wcnt);
+  }
+  const int nl = (TAPS || wl) ? wl_n : *nlist;
+
+  // The item as its lane owns it: fp16 gradients converted; the last lane of a RoI keeps its PP % 4 bins in the
+  // high slots (bins PP-4 .. PP-1 in order) and the slots in front of them hold nothing -- code 255, coordinates
+  // -1; their gradients stay (they are the neighbour's, so every maximum over the stream is what it was).
+  auto own_item = [&](Item& it) {
+    if constexpr (HALF) {
+      const unsigned h01 = __float_as_uint(it.g.x), h23 = __float_as_uint(it.g.y);
+      const float2 f01 = __half22float2(*reinterpret_cast<const __half2*>(&h01));
+      const float2 f23 = __half22float2(*reinterpret_cast<const __half2*>(&h23));
+      it.g = make_float4(f01.x, f01.y, f23.x, f23.y);
+    }
+    if constexpr (TAIL) {
+      if (it.b0 == PP - 4) {
+        if (FLT) {
+          it.x.x = it.y.x = -1.f;
+          if (KEEP < 3) it.x.y = it.y.y = -1.f;
+          if (KEEP < 2) it.x.z = it.y.z = -1.f;
         } else {
-          return *reinterpret_cast<const F4u*>(dyb + o);
-        }
-      };
-      auto tail4 = [](const F4u& v, float fill) {
-        const float gg[4] = {v.x, v.y, v.z, v.w};
-        return make_float4(gg[4 - KEEP], KEEP > 1 ? gg[KEEP > 1 ? 5 - KEEP : 0] : fill,
-                           KEEP > 2 ? gg[KEEP > 2 ? 6 - KEEP : 0] : fill, fill);
-      };
-      if (TAIL && g == GP - 1) {
-        const int o = r * roi_stride + (PP - 4);
-        it.g = tail4(load_g(o), 0.f);
-        if (FLT) {
-          it.x = tail4(*reinterpret_cast<const F4u*>(axb + o), -1.f);
-          it.y = tail4(*reinterpret_cast<const F4u*>(ayb + o), -1.f);
-        }
-        code |= FLT ? 0u : 0xffffffffu << (8 * KEEP);  // the padding bytes of the row are not codes
-      } else {
-        const int o = r * roi_stride + 4 * g;
-        const F4u v = load_g(o);
-        it.g = make_float4(v.x, v.y, v.z, v.w);
-        if (FLT) {
-          const F4u vx = *reinterpret_cast<const F4u*>(axb + o), vy = *reinterpret_cast<const F4u*>(ayb + o);
-          it.x = make_float4(vx.x, vx.y, vx.z, vx.w);
-          it.y = make_float4(vy.x, vy.y, vy.z, vy.w);
+          it.code = (it.code << (8 * (4 - KEEP))) | (0xffffffffu >> (8 * KEEP));
         }
       }
-      it.code = code;
+    }
+  };
+  // the gradient of the first bin an item owns (what the range statistic samples)
+  auto first_g = [&](const Item& it) {
+    if constexpr (TAIL) {
+      const float gg[4] = {it.g.x, it.g.y, it.g.z, it.g.w};
+      return it.b0 == PP - 4 ? gg[4 - KEEP] : it.g.x;
+    } else {
+      return it.g.x;
     }
   };
   auto scatter_item = [&](const Item& it, int slot) {
@@ -515,7 +583,7 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
   // An item one of whose codes names candidate 2 (third = true_type; the caller tests the four code bytes at
   // once, codes_name_third) fetches that entry from the unit's side table in global memory: rare, divergent, cold.
   const float2* side = TAPS ? reinterpret_cast<const float2*>(
-                                  a.ws_taps + (long)(a.unit_base[li] + u) * a.R * (2 * NE) + (long)a.R * TS)
+                                  a.ws_taps + unit * a.R * (2 * NE) + (long)a.R * TS)
                             : nullptr;
   auto scatter_taps = [&](const Item& it, int slot, int cb, auto third) {
     if (it.code == 0xffffffffu || (SD_ABLATE(a, 1))) return;  // (profiling build, 1: no scatter)
@@ -562,14 +630,8 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
     }
   };
 
-  auto stage_tables = [&](int cb, int ncur) {
-    if (FLT) return;
-    if (TAPS) {  // the chunk's main-table entries are contiguous in the workspace (list order)
-      const float4* src = reinterpret_cast<const float4*>(
-          a.ws_taps + (long)(a.unit_base[li] + u) * a.R * (2 * NE) + (long)cb * TS);
-      for (int i = tid; i < ncur * (TS / 4); i += THREADS) reinterpret_cast<float4*>(tab)[i] = src[i];
-      return;
-    }
+  auto stage_tables = [&](int cb, int ncur) {   // the coordinate table (MODE 0; the tap tables: load_tap / store_tap)
+    if (FLT || TAPS) return;
     for (int i = tid; i < ncur * (TS / 2); i += THREADS) {
       const int j = i / (TS / 2), e2 = i - j * (TS / 2);
       const float2 v = *reinterpret_cast<const float2*>(cob + list[cb + j] * CW + 2 * e2);
@@ -608,11 +670,16 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
     fx_scale = ldexpf(1.f, S);
     fx_inv = ldexpf(1.f, -S);
   };
-  Item cur;
   const int tch = FLT ? (nl > 0 ? nl : 1) : TCH;  // no tables to stage: the whole list is one chunk
-  load_item(tid, 0, iminr(tch, nl) * GP, cur);
-  stage_tables(0, iminr(tch, nl));
-  unsigned m_all = absbits4(cur.g);
+  const int nli0 = iminr(tch, nl) * GP;
+  if (!TAPS && nl > 0) load_item(tid, 0, nli0, cur);
+  stage_tables(0, iminr(tch, nl));   // (the tap tables are in LDS already)
+  unsigned m_all = 0u;
+  if (tid < nli0) {
+    Item own = cur;
+    own_item(own);
+    m_all = absbits4(own.g);
+  }
   if (use_fx) wave_max_to(m_all, 2, 3);
   __syncthreads();
   float gmax_used = 0.f;
@@ -637,16 +704,26 @@ void roi_align_bwd_packed4(BwdFusedArgs a) {
       const int nli = ncur * GP;  // lane items of this chunk
       const int trip0 = (cb / tch) * chunk_trips;
       if (cb > 0 || attempt > 0) {
+        if constexpr (TAPS) {
+          ta = load_tap(cb, ncur, 0);
+          if (NT > 1) tb = load_tap(cb, ncur, 1);
+        }
         load_item(tid, cb, nli, cur);
         __syncthreads();  // the previous chunk's tables are no longer read
-        stage_tables(cb, ncur);
+        if constexpr (TAPS) {
+          store_tap(ncur, 0, ta);
+          if (NT > 1) store_tap(ncur, 1, tb);
+        } else {
+          stage_tables(cb, ncur);
+        }
         __syncthreads();
       }
       for (int t = tid; t < nli; t += THREADS) {
         Item nxt;
         load_item(t + THREADS, cb, nli, nxt);
+        own_item(cur);
         m_all = umaxr(m_all, absbits4(cur.g));
-        if (((trip0 + t / THREADS) & e_mask) == 0) e_acc += fx_range_sample(cur.g.x);   // (wave uniform)
+        if (((trip0 + t / THREADS) & e_mask) == 0) e_acc += fx_range_sample(first_g(cur));   // (wave uniform)
         if (TAPS) {
           if (codes_name_third(cur.code)) scatter_taps(cur, cur.j, cb, std::true_type{});
           else scatter_taps(cur, cur.j, cb, std::false_type{});
@@ -1028,6 +1105,8 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
     a.block_end[i] = (int)total;
   }
   a.nlaunch = nl;
+  // the kernel's block decode divides by the channels of a block run and by a level's bands
+  bwd_set_magic((unsigned)(a.C % kNumXCD == 0 ? a.C / kNumXCD : a.C), a.chan_magic, a.chan_shift);
   if (total == 0) return SD_OK;
   if (total >= (1L << 31)) return SD_ERR_UNSUPPORTED;
   // RoI lists (and tap tables) of the (level, image, band) units, once per launch instead of once
@@ -1041,6 +1120,18 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
       ub += (long)a.B * a.nbands[a.order[i]];
     }
     if (nl < SD_MAX_FPN_LEVELS) a.unit_base[nl] = (int)ub;
+  }
+  for (int i = 0; i < nl; ++i) {   // what a workgroup of launch slot i needs to find its unit
+    const int l = a.order[i];
+    BwdSlot& sl = a.slot[i];
+    sl.lvl = l;
+    sl.block0 = i ? a.block_end[i - 1] : 0;
+    sl.unit_base = a.unit_base[i];
+    sl.H = a.L.H[l];
+    sl.W = a.L.W[l];
+    sl.nbands = a.nbands[l];
+    sl.band_rows = a.band_rows[l];
+    bwd_set_magic((unsigned)a.nbands[l], sl.band_magic, sl.band_shift);
   }
   a.lists_units = 0;
   a.pix_bound_words = 0;

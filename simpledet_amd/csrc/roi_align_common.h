@@ -312,6 +312,12 @@ struct BwdArgs {
 // fused backward (every level of the pyramid in ONE launch): workgroup = (level, image, row band,
 // channel); the band of the gradient plane lives in LDS and is written to HBM exactly once with 16-B
 // stores: no zero-fill pass, no global atomics, no per-level launch boundary / tail.
+// Launch slot i of roi_align_bwd_packed4 (levels in launch order): the level, its first workgroup and unit, its
+// geometry and bands, and the reciprocal of the band count (bwd_div_magic)
+struct BwdSlot {
+  int lvl, block0, unit_base, H, W, nbands, band_rows, band_shift;
+  unsigned long long band_magic;
+};
 struct BwdFusedArgs {
   RoiLevels L;
   const float* dy;
@@ -344,6 +350,11 @@ struct BwdFusedArgs {
   int float_adds;                    // 1: every workgroup sums with fp32 compare-and-swap adds (tuning key roi_align_bwd_fx = 0)
   int pix_bound_words;               // list pre-pass: LDS words for the per-cell (4 x 4 pixels) weight bound of a band, of the
                                      // largest level that gets one; 0: the bands keep the summed bound
+  // roi_align_bwd_packed4's block decode: one record per launch slot, and the reciprocal (bwd_div_magic) of the
+  // channels of a block run (C / 8 with whole XCDs, else C)
+  BwdSlot slot[SD_MAX_FPN_LEVELS];
+  unsigned long long chan_magic;
+  int chan_shift;
 };
 constexpr int kTapMainWords = 4, kTapSideWords = 2;   // words per axis bin in the main / side tap table of a RoI
 constexpr int kPixBoundMaxWords = 10240;  // 40 KB of difference array at most
