@@ -13,7 +13,7 @@
 //               replacing the running assignment only where it is strictly greater; the fg / bg flags
 //   ch_lists    one workgroup per image: the ordered lists np.where would return (the candidate list of the reference is
 //               the raw rows with the padding dropped, so the ORDER of the raw rows is the order of its indices)
-//   ch_sample   ONE workgroup, images in order, the producer / consumer MT19937 of mt19937.h: per non-empty list one
+//   ch_sample   ONE workgroup, images in order, mt19937.h's producer / consumer MT19937 (mt_consume): per non-empty list one
 //               permutation(n), every accepted draw j_i recorded (n - 1 <= 4095 16-bit words per list)
 //   ch_finish   one workgroup per image, one thread per output row: the wanted FRONT entry p of the permutation is
 //               traced back through the recorded swaps (the swaps in reverse order of execution, i = 1 .. n - 1:
@@ -22,7 +22,9 @@
 // sd_emd_loss_fwd / _bwd: one row per thread; the forward is one workgroup with a fixed-order sum.
 #include "common.h"
 #include "bbox_iou.h"
+#include "loss_common.h"
 #include "mt19937.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -60,35 +62,21 @@ struct ChArgs {
 // non-padding gt rows (class != -1), order preserved, into LDS: box, class, raw row; returns their number
 template <int THREADS>
 __device__ int ch_load_gt(const ChArgs& a, int img, float4* gbox, float* gcls, int* graw, int* wsum) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int n_gt = 0;
-  for (int base = 0; base < a.M; base += THREADS) {
-    const int j = base + tid;
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    float c = -1.f;
-    if (j < a.M) {
-      const float* p = a.gt + ((long)img * a.M + j) * 5;
-      g = make_float4(p[0], p[1], p[2], p[3]);
-      c = p[4];
-    }
-    const bool ok = j < a.M && c != -1.f;
-    const unsigned long long m = __ballot(ok);
-    __syncthreads();
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int off = n_gt, tot = 0;
-    for (int w = 0; w < THREADS / kWave; ++w) {
-      if (w < wave) off += wsum[w];
-      tot += wsum[w];
-    }
-    if (ok) {
-      const int k = off + __popcll(m & ((1ull << lane) - 1));
-      gbox[k] = g;
-      gcls[k] = c;
-      graw[k] = j;
-    }
-    n_gt += tot;
-  }
+  float4 g;
+  float c;
+  const int n_gt = block_compact_rows<THREADS>(
+      a.M, wsum,
+      [&](int j) {
+        const float* p = a.gt + ((long)img * a.M + j) * 5;
+        g = make_float4(p[0], p[1], p[2], p[3]);
+        c = p[4];
+        return c != -1.f;
+      },
+      [&](int j, int k) {
+        gbox[k] = g;
+        gcls[k] = c;
+        graw[k] = j;
+      });
   __syncthreads();
   return n_gt;
 }
@@ -170,24 +158,17 @@ __global__ __launch_bounds__(kChT) void ch_match_kernel(ChArgs a) {
 // the ordered fg / bg lists of an image (one workgroup of 1024 threads per image)
 __global__ __launch_bounds__(1024) void ch_lists_kernel(ChArgs a) {
   __shared__ int wcnt[2][16];
-  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = blockIdx.x, tid = threadIdx.x;
   int run0 = 0, run1 = 0;
   for (int base = 0; base < a.N; base += 1024) {
     const int r = base + tid;
     const int f = r < a.N ? (int)a.flag[(long)img * a.N + r] : 0;
-    const unsigned long long mf = __ballot((f & 1) != 0), mb = __ballot((f & 2) != 0);
-    __syncthreads();
-    if (lane == 0) { wcnt[0][wave] = __popcll(mf); wcnt[1][wave] = __popcll(mb); }
-    __syncthreads();
-    int off0 = run0, off1 = run1, tot0 = 0, tot1 = 0;
-    for (int w = 0; w < 16; ++w) {
-      if (w < wave) { off0 += wcnt[0][w]; off1 += wcnt[1][w]; }
-      tot0 += wcnt[0][w]; tot1 += wcnt[1][w];
-    }
-    const unsigned long long lt = (1ull << lane) - 1;
-    if (f & 1) a.fg_list[(long)img * a.N + off0 + __popcll(mf & lt)] = r;
-    if (f & 2) a.bg_list[(long)img * a.N + off1 + __popcll(mb & lt)] = r;
-    run0 += tot0; run1 += tot1;
+    const bool flag[2] = {(f & 1) != 0, (f & 2) != 0};
+    int off[2] = {run0, run1}, tot[2];
+    block_scan_flags<1024, 2>(flag, wcnt, off, tot);
+    if (f & 1) a.fg_list[(long)img * a.N + off[0]] = r;
+    if (f & 2) a.bg_list[(long)img * a.N + off[1]] = r;
+    run0 += tot[0]; run1 += tot[1];
   }
   if (tid == 0) {
     a.counts[img * 2] = run0;
@@ -198,46 +179,21 @@ __global__ __launch_bounds__(1024) void ch_lists_kernel(ChArgs a) {
 // permutation(n) of the legacy RandomState: every accepted draw j of step i = n - 1 .. 1 goes to jrec[n - 1 - i]
 // and the generator advances by exactly the draws numpy consumes.  n <= kChMaxCand: batch by batch.
 __device__ void ch_sample(MtStream& m, int n, unsigned short* jrec, int lane) {
-  int i = n - 1;
-  const unsigned long long lt = (1ull << lane) - 1;
-  while (i >= 1) {
-    mt_st(m.ctl + 4, m.pos > 624 ? m.pos - 624 : 0);
-    if (!mt_need(m, kWave)) return;
-    const unsigned mask = mt_mask(i);
-    const int lo = (int)(mask >> 1) + 1;
-    unsigned v;
-    bool acc;
-    unsigned long long bits;
-    int consumed;
-    const int K = mt_batch(m, i, lo, mask, lane, v, acc, bits, consumed);
-    if (acc) jrec[(n - 1) - (i - __popcll(bits & lt))] = (unsigned short)v;
-    i -= K;
-    m.pos += consumed;
-  }
+  mt_permutation_draws(m, n, lane, [](int, int) { return 1; },
+                       [&](int step, unsigned v) { jrec[step] = (unsigned short)v; });
 }
 
 __global__ __launch_bounds__(kMtThreads) void ch_sample_kernel(ChArgs a) {
-  __shared__ unsigned ring[kMtRing], tring[kMtRing];
-  __shared__ __attribute__((aligned(16))) int ctl[8];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  mt_open(ring, tring, ctl, a.mt);
-  __syncthreads();   // (the only barrier: before the waves part)
-  if (wave >= 1) {
-    mt_produce(ring, tring, ctl, wave - 1, lane);
-    return;
-  }
-  MtStream m{ring, tring, ctl, a.mt[624]};
-  const int pos0 = m.pos;
-  for (int img = 0; img < a.B && !mt_ld(ctl + 6); ++img) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int overrun = mt_consume(a.mt, a.B, [&](MtStream& m, int img) {
     // npr.choice(inds, size, replace=False) = inds[permutation(n)[:size]] whenever the list is not empty, whatever
     // the size (also 0, also n); permutation(1) draws nothing
     for (int l = 0; l < 2; ++l) {
       const int n = a.counts[img * 2 + l];
       if (n >= 2) ch_sample(m, n, a.jrec + ((long)img * 2 + l) * kChMaxCand, lane);
     }
-  }
-  const bool overrun = mt_close(m, pos0, a.mt, lane);
-  if (lane == 0) a.counts[a.B * 2] = overrun ? 1 : 0;
+  });
+  if (overrun != kMtProducer && lane == 0) a.counts[a.B * 2] = overrun;
 }
 
 // bbox_transform_inv (operator_py/detectron_bbox_utils.py:205-219) on float32 boxes: every operation in float32
@@ -375,17 +331,6 @@ struct EmdArgs {
   float *gx1, *gx2, *gd1, *gd2;
 };
 
-// mshadow_op::smooth_l1_loss / smooth_l1_gradient
-__device__ __forceinline__ float emd_sl1(float v, float bsq, float ibsq) {
-  if (v > ibsq) return v - 0.5f * ibsq;
-  if (v < -ibsq) return -v - 0.5f * ibsq;
-  return 0.5f * v * v * bsq;
-}
-__device__ __forceinline__ float emd_sl1_grad(float v, float bsq, float ibsq) {
-  if (v > ibsq) return 1.0f;
-  if (v < -ibsq) return -1.0f;
-  return bsq * v;
-}
 // the column a float label names (mx.nd.one_hot: none outside [0, K))
 __device__ __forceinline__ int emd_col(float y, int K) { return y >= 0.f && y < (float)K ? (int)y : -1; }
 
@@ -416,8 +361,8 @@ __device__ __forceinline__ int emd_row(const EmdArgs& a, int r, float& lmin) {
   for (int d = 0; d < a.D; ++d) {
     const float p1 = a.d1[o + d], p2 = a.d2[o + d], t1 = a.t1[o + d], t2 = a.t2[o + d];
     const float w1 = a.w1[o + d], w2 = a.w2[o + d];
-    reg1 += w1 * emd_sl1(p1 - t1, a.bsq, a.ibsq) + w2 * emd_sl1(p2 - t2, a.bsq, a.ibsq);
-    reg2 += w2 * emd_sl1(p1 - t2, a.bsq, a.ibsq) + w1 * emd_sl1(p2 - t1, a.bsq, a.ibsq);
+    reg1 += w1 * smooth_l1(p1 - t1, a.bsq, a.ibsq) + w2 * smooth_l1(p2 - t2, a.bsq, a.ibsq);
+    reg2 += w2 * smooth_l1(p1 - t2, a.bsq, a.ibsq) + w1 * smooth_l1(p2 - t1, a.bsq, a.ibsq);
   }
   const float L1 = cls1 + reg1, L2 = cls2 + reg2;
   const bool first = L1 <= L2;
@@ -465,10 +410,10 @@ __global__ __launch_bounds__(kChT) void emd_loss_bwd_kernel(EmdArgs a) {
   for (int d = 0; d < a.D; ++d) {
     const float p1 = a.d1[o + d], p2 = a.d2[o + d], t1 = a.t1[o + d], t2 = a.t2[o + d];
     const float w1 = a.w1[o + d], w2 = a.w2[o + d];
-    a.gd1[o + d] = first ? (a.g * w1) * emd_sl1_grad(p1 - t1, a.bsq, a.ibsq)
-                         : (a.g * w2) * emd_sl1_grad(p1 - t2, a.bsq, a.ibsq);
-    a.gd2[o + d] = first ? (a.g * w2) * emd_sl1_grad(p2 - t2, a.bsq, a.ibsq)
-                         : (a.g * w1) * emd_sl1_grad(p2 - t1, a.bsq, a.ibsq);
+    a.gd1[o + d] = first ? (a.g * w1) * smooth_l1_grad(p1 - t1, a.bsq, a.ibsq)
+                         : (a.g * w2) * smooth_l1_grad(p1 - t2, a.bsq, a.ibsq);
+    a.gd2[o + d] = first ? (a.g * w2) * smooth_l1_grad(p2 - t2, a.bsq, a.ibsq)
+                         : (a.g * w1) * smooth_l1_grad(p2 - t1, a.bsq, a.ibsq);
   }
 }
 

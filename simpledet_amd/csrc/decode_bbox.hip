@@ -8,6 +8,7 @@
 // order (ballot + prefix popcount) straight into the (P, Nmax, 5) layout sd_soft_nms_batched reads,
 // so bbox head output -> decode -> filter -> soft-NMS never leaves the device.
 #include "common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void det_filter_kernel(FilterArgs a) {
     }
     const unsigned long long bal = __ballot(take);
     if (take) {
-      const int pos = m + __popcll(bal & ((1ull << lane) - 1));
+      const int pos = m + lanes_before(bal, lane);
       const float4 b = *reinterpret_cast<const float4*>(
           a.bbox + ((long)n * a.R + r) * 4 * a.Kb + (a.Kb == 1 ? 0 : cid * 4));
       float* o = d + (long)pos * 5;

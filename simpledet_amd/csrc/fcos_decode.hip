@@ -51,7 +51,7 @@
 //   6. fcos_decode_score_kernel  fills score (N, R, 81) from those pairs with coalesced stores.
 // Every element of bbox, score, cls_id and stage_out is written by every call.  Loads are scalar, so any 4-byte
 // aligned pointer gives the same bits.  Arithmetic: -ffp-contract=off, correctly rounded divide and sqrt (Makefile).
-#include "fcos_common.h"
+#include "loss_common.h"
 #include "select_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
@@ -98,8 +98,8 @@ __device__ __forceinline__ void dc_scores(const DecodeArgs& a, const float* __re
                                           float* cls, float* fused) {
   float t = ct[hw];
   if (a.logits) {
-    craw = fcos_sigmoid(craw);
-    t = fcos_sigmoid(t);
+    craw = sigmoid_f32(craw);
+    t = sigmoid_f32(t);
   }
   *cls = craw;
   *fused = craw * t;
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void fcos_decode_score_kernel(DecodeArgs a) {
 
 __global__ __launch_bounds__(256) void fcos_sigmoid_kernel(const float* __restrict__ x, float* __restrict__ p, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    p[i] = fcos_sigmoid(x[i]);
+    p[i] = sigmoid_f32(x[i]);
 }
 
 struct DecodeWs {

@@ -29,7 +29,8 @@
 // rounded divide / sqrt).  Where the reference multiplies by a 0/1 mask and adds, the per-box loop selects
 // (equal bits for finite boxes); the two places where a NaN target can meet a zero mask -- the final centerness
 // and the forward sums -- keep the multiplication, so a degenerate box's NaN goes where the reference's goes.
-#include "fcos_common.h"
+#include "loss_common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -62,24 +63,6 @@ struct FcosTargetArgs {
   float ignore_offset, ignore_label;
   FcosGrid g;
 };
-
-// fixed-order sums over the workgroup (wave butterflies, then the four waves left to right)
-__device__ __forceinline__ float block_sum_f32(float v, float* sh) {
-  v = wave_sum_f32(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
-  __syncthreads();
-  const float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ int block_sum_i32(int v, int* sh) {
-  v = wave_sum_i32(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
-  __syncthreads();
-  const int r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
 
 // mxnet_op one_hot: j = static_cast<int>(cls - 1); a class only for 0 <= j < K
 __device__ __forceinline__ int fcos_class(float cls, int K) {
@@ -165,9 +148,9 @@ __global__ __launch_bounds__(kFcT) void fcos_target_kernel(FcosTargetArgs a) {
     cc = c != il && c > 0.f;
     cm = c * ((b0 != io && c > 0.f) ? 1.0f : 0.0f);   // loss.py:169-175
   }
-  fg = block_sum_i32(fg, shi);
-  cc = block_sum_i32(cc, shi);
-  cm = block_sum_f32(cm, shf);
+  fg = block_sum_i32<kFcT>(fg, shi);
+  cc = block_sum_i32<kFcT>(cc, shi);
+  cm = block_sum_f32<kFcT>(cm, shf);
   if (threadIdx.x == 0) {
     const int b = blockIdx.y * gridDim.x + blockIdx.x;
     a.part_i[2 * b] = fg;
@@ -188,9 +171,9 @@ __global__ __launch_bounds__(kFcT) void fcos_state_kernel(const int* __restrict_
     cc += part_i[2 * b + 1];
     cm += part_f[b];
   }
-  fg = block_sum_i32(fg, shi);
-  cc = block_sum_i32(cc, shi);
-  cm = block_sum_f32(cm, shf);
+  fg = block_sum_i32<kFcT>(fg, shi);
+  cc = block_sum_i32<kFcT>(cc, shi);
+  cm = block_sum_f32<kFcT>(cm, shf);
   if (threadIdx.x == 0) {
     state[0] = fg;
     state[1] = cc;
@@ -225,28 +208,20 @@ __device__ __forceinline__ int fcos_level(const FcosLossArgs& a, int j) {
   return l;
 }
 
-template <int GAMMA>
-__device__ __forceinline__ float fcos_pow(float r, float gamma) {
-  if (GAMMA == 2) return r * r;
-  if (GAMMA == 1) return r;
-  if (GAMMA == 0) return 1.0f;
-  return powf(r, gamma);
-}
-
 // make_sigmoid_focal_loss (loss.py:86-106) for one unmasked element; pos = (label == 1).
 // The label enters as a 0/1 factor there: the branch not taken is a product with 0 added to the other.
 struct FocalTerms { float a, logp, minus_log, p; };
 template <int GAMMA>
 __device__ __forceinline__ FocalTerms fcos_focal_terms(const FcosLossArgs& a, float x, bool pos) {
   FocalTerms t;
-  t.p = fcos_sigmoid(x);
+  t.p = sigmoid_f32(x);
   const float ge = x >= 0.f ? 1.0f : 0.0f;
   const float minus_logits_mask = (-1.0f * x) * ge;
   const float negative_abs = x - (2.0f * x) * ge;
   t.minus_log = minus_logits_mask - logf(1.0f + expf(negative_abs));
   const float pc = t.p > 1.0f ? 1.0f : t.p < 1e-5f ? 1e-5f : t.p;
   t.logp = logf(pc);
-  t.a = pos ? a.alpha * fcos_pow<GAMMA>(1.0f - t.p, a.gamma) : a.one_minus_alpha * fcos_pow<GAMMA>(t.p, a.gamma);
+  t.a = pos ? a.alpha * pow_gamma<GAMMA>(1.0f - t.p, a.gamma) : a.one_minus_alpha * pow_gamma<GAMMA>(t.p, a.gamma);
   return t;
 }
 template <int GAMMA>
@@ -321,15 +296,15 @@ __global__ __launch_bounds__(kFcT) void fcos_loss_fwd_kernel(FcosLossArgs a) {
   for (unsigned i = blockIdx.x * kFcT + threadIdx.x; i < nloc; i += step) {
     const int n = (int)(i / a.HW), j = (int)(i - (unsigned)n * a.HW);
     const FcosLoc q = fcos_load_loc(a, n, j);
-    const float p = fcos_sigmoid(q.x_ctr);
+    const float p = sigmoid_f32(q.x_ctr);
     const float bce = (-q.c) * logf(fcos_clip(p, 1e-5f, 1.0f)) - (1.0f - q.c) * logf(fcos_clip(1.0f - p, 1e-5f, 1.0f));
     s_ctr += bce * q.maskc;
     const IouTerms r = fcos_iou_terms(q);
     s_off += (-logf(r.I1 / r.U1)) * (q.c * q.maski);
   }
-  s_ctr = block_sum_f32(s_ctr, sh);
-  s_cls = block_sum_f32(s_cls, sh);
-  s_off = block_sum_f32(s_off, sh);
+  s_ctr = block_sum_f32<kFcT>(s_ctr, sh);
+  s_cls = block_sum_f32<kFcT>(s_cls, sh);
+  s_off = block_sum_f32<kFcT>(s_off, sh);
   if (threadIdx.x == 0) {
     a.part[3 * blockIdx.x] = s_ctr;
     a.part[3 * blockIdx.x + 1] = s_cls;
@@ -347,9 +322,9 @@ __global__ __launch_bounds__(kFcT) void fcos_loss_final_kernel(const float* __re
     s1 += part[3 * b + 1];
     s2 += part[3 * b + 2];
   }
-  s0 = block_sum_f32(s0, sh);
-  s1 = block_sum_f32(s1, sh);
-  s2 = block_sum_f32(s2, sh);
+  s0 = block_sum_f32<kFcT>(s0, sh);
+  s1 = block_sum_f32<kFcT>(s1, sh);
+  s2 = block_sum_f32<kFcT>(s2, sh);
   if (threadIdx.x == 0) {
     losses[0] = s0 / ((float)state[1] + 1e-30f);
     losses[1] = s1 / ((float)state[0] + 1.0f);
@@ -406,7 +381,7 @@ __global__ __launch_bounds__(kFcT) void fcos_loss_bwd_kernel(FcosLossArgs a) {
     const int n = (int)(i / a.HW), j = (int)(i - (unsigned)n * a.HW);
     const int l = fcos_level(a, j), p = j - a.begin[l], hw = a.hw[l];
     const FcosLoc q = fcos_load_loc(a, n, j);
-    const float pc = fcos_sigmoid(q.x_ctr);
+    const float pc = sigmoid_f32(q.x_ctr);
     a.dctr[l][(long)n * hw + p] = ((pc - q.c) * q.maskc) / norm_ctr;
     float g[4] = {0.f, 0.f, 0.f, 0.f};
     if (q.maski != 0.f) {

@@ -21,6 +21,7 @@
 //                   positive in it does not run both sides.
 //   bbox_norm_bwd   gdata = gout / max(1, count + 1)              (bbox_norm-inl.h:116-126)
 #include "common.h"
+#include "loss_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -39,18 +40,17 @@ template <bool VEC>
 __global__ __launch_bounds__(kFlT) void focal_sigmoid_kernel(const float* __restrict__ x,
                                                              float* __restrict__ y, long n) {
   const long step = (long)gridDim.x * kFlT;
-  auto sig = [](float a) { return 1.0f / (1.0f + expf(-a)); };
   if (VEC) {
     const float4* x4 = reinterpret_cast<const float4*>(x);
     float4* y4 = reinterpret_cast<float4*>(y);
     const long n4 = n >> 2;
     for (long i = (long)blockIdx.x * kFlT + threadIdx.x; i < n4; i += step) {
       const float4 v = x4[i];
-      y4[i] = make_float4(sig(v.x), sig(v.y), sig(v.z), sig(v.w));
+      y4[i] = make_float4(sigmoid_f32(v.x), sigmoid_f32(v.y), sigmoid_f32(v.z), sigmoid_f32(v.w));
     }
-    for (long i = (n4 << 2) + (long)blockIdx.x * kFlT + threadIdx.x; i < n; i += step) y[i] = sig(x[i]);
+    for (long i = (n4 << 2) + (long)blockIdx.x * kFlT + threadIdx.x; i < n; i += step) y[i] = sigmoid_f32(x[i]);
   } else {
-    for (long i = (long)blockIdx.x * kFlT + threadIdx.x; i < n; i += step) y[i] = sig(x[i]);
+    for (long i = (long)blockIdx.x * kFlT + threadIdx.x; i < n; i += step) y[i] = sigmoid_f32(x[i]);
   }
 }
 
@@ -86,15 +86,6 @@ struct FocalArgs {
   int normalization;
 };
 
-// GAMMA: 0 / 1 / 2 multiply-only, -1 powf
-template <int GAMMA>
-__device__ __forceinline__ float focal_pow(float r, float gamma) {
-  if (GAMMA == 2) return r * r;
-  if (GAMMA == 1) return r;
-  if (GAMMA == 0) return 1.0f;
-  return powf(r, gamma);
-}
-
 // one element of :192-230 before the ograd product; `cls` is int(label - 1) or -1 (no class), ignore = (label == -1)
 template <int GAMMA>
 __device__ __forceinline__ float focal_elem(const FocalArgs& a, float p, bool pos) {
@@ -105,7 +96,7 @@ __device__ __forceinline__ float focal_elem(const FocalArgs& a, float p, bool po
   const float t = (a.gamma * q) * logf(q + eps);
   // positive: t + p - 1; negative: t - p
   const float inner = pos ? (t + p) - 1.0f : t - p;
-  const float v = ((pos ? a.alpha : a.one_minus_alpha) * focal_pow<GAMMA>(r, a.gamma)) * inner;
+  const float v = ((pos ? a.alpha : a.one_minus_alpha) * pow_gamma<GAMMA>(r, a.gamma)) * inner;
   return pos ? v : -v;
 }
 

@@ -32,6 +32,7 @@
 // left to right, the partials in index order): no floating-point atomics anywhere, two calls give equal bits.
 // Every workspace word that is read was written by a kernel of the same call: nothing to clear, no memset node.
 #include "common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 #include <type_traits>
@@ -153,11 +154,8 @@ struct GnDx {
 // order.  `slot`: four floats of LDS that no other reduction in flight uses.
 template <int TG>
 __device__ __forceinline__ float gn_group_sum(float v, float* slot) {
-  v = wave_sum_f32(v);
-  if (TG == kWave) return v;
-  if ((threadIdx.x & (kWave - 1)) == 0) slot[threadIdx.x / kWave] = v;
-  __syncthreads();
-  return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+  if constexpr (TG == kWave) return wave_sum_f32(v);
+  else return block_sum_f32<TG, false>(v, slot);   // (no barrier behind the read: every reduction in flight has its own slot)
 }
 template <int TG>
 __device__ __forceinline__ void gn_group_sync() {

@@ -41,11 +41,11 @@ namespace sd {
 
 // the logit of element e of the gathered row, for the sigmoid alone (the row's cls names a plane)
 __device__ __forceinline__ float msr_prob_at(const CeMask& s, unsigned e, float t, float x) {
-  if (t != -1.0f) return ce_prob(x);                       // counted: the loss already loaded it
+  if (t != -1.0f) return sigmoid_f32(x);                       // counted: the loss already loaded it
   const unsigned r = e / s.P;
   const int c = mask_class(s.cls[r], s.K);                 // the row's class, looked up once
   if (c < 0) return 0.0f;                                  // a rejected row: +0.0, logits not read
-  return ce_prob(s.logits[((size_t)r * s.K + (unsigned)c) * s.P + (e - r * s.P)]);   // ignored by the loss, still predicted
+  return sigmoid_f32(s.logits[((size_t)r * s.K + (unsigned)c) * s.P + (e - r * s.P)]);   // ignored by the loss, still predicted
 }
 
 // mask-loss forward: the units of the fused mask loss, and prob next to them
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kCeT) void msr_mask_fwd_kernel(CeMask s, CeUnits g,
     if (!cnt) continue;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     if (VEC) {   // one RoI; x holds its plane whenever cls names one, whatever the targets are
-      if (mask_class(s.cls[e0 / s.P], s.K) >= 0) p = make_float4(ce_prob(x.x), ce_prob(x.y), ce_prob(x.z), ce_prob(x.w));
+      if (mask_class(s.cls[e0 / s.P], s.K) >= 0) p = make_float4(sigmoid_f32(x.x), sigmoid_f32(x.y), sigmoid_f32(x.z), sigmoid_f32(x.w));
     } else {
       p.x = msr_prob_at(s, e0, t.x, x.x);
       if (cnt > 1) p.y = msr_prob_at(s, e0 + 1, t.y, x.y);

@@ -1,7 +1,8 @@
 // MT19937 of numpy's legacy RandomState on the device: producer waves and a consumer wave.  Shared by the RPN
 // anchor targets (rpn_target.hip) and the CrowdHuman RoI targets (crowdhuman_head.hip); the code is the RPN's of
 // round 6, moved here so that both draw from one implementation: the stream, the producer, mt_need and mt_trip as
-// they were, mt_batch / mt_open / mt_close cut out of rpn_sample and rpn_sample_kernel, statement for statement.
+// they were, mt_batch / mt_open / mt_close, the draw loop (mt_permutation_draws) and the kernel's shell (mt_consume)
+// cut out of rpn_sample and rpn_sample_kernel, statement for statement.
 //
 // Until round 5 ONE wave twisted the state and consumed it (2.7 ms for two images: a lone wave pays
 // ~12 clocks per dependent instruction, and twist and rejection chain were one dependency chain).  The generator's
@@ -220,6 +221,66 @@ __device__ __forceinline__ bool mt_close(MtStream& m, int pos0, int* mt, int lan
   const bool overrun = mt_ld(m.ctl + 6) != 0;
   mt_st(m.ctl + 5, 1);
   return overrun;
+}
+
+// permutation(n) of the legacy RandomState, consumer wave: Fisher-Yates step s = 0 .. n - 2 swaps position
+// i = n - 1 - s with an accepted draw v, handed to record(s, v) by the lane that holds it; the generator advances by
+// exactly the draws numpy consumes.  trip_size(i, s): batches of 64 draws in the next dependent step -- 2, 8 or 16
+// (mt_trip: accepts counted, not recorded) or 1 (mt_batch: every accept recorded; also the fall-back when a trip
+// would leave its mask's segment).  A constant 1 compiles the trips out.  False when the stream overran.
+template <typename TripSize, typename Record>
+__device__ __forceinline__ bool mt_permutation_draws(MtStream& m, int n, int lane, TripSize trip_size, Record record) {
+  int i = n - 1;
+  const unsigned long long lt = (1ull << lane) - 1;
+  while (i >= 1) {
+    // the consumer no longer needs anything before the block its last draw came from (the final state is that block)
+    mt_st(m.ctl + 4, m.pos > 624 ? m.pos - 624 : 0);
+    const int nb = trip_size(i, (n - 1) - i);
+    if (!mt_need(m, nb * kWave)) return false;
+    const unsigned mask = mt_mask(i);
+    const int lo = (int)(mask >> 1) + 1;  // steps i in [lo, mask] share this rejection mask
+    if (nb > 1) {
+      const int K = nb == 16 ? mt_trip<16>(m, i, lo, mask, lane) : nb == 8 ? mt_trip<8>(m, i, lo, mask, lane)
+                                                                          : mt_trip<2>(m, i, lo, mask, lane);
+      if (K >= 0) {
+        i -= K;
+        m.pos += nb * kWave;
+        continue;
+      }
+    }
+    unsigned v;
+    bool acc;
+    unsigned long long bits;
+    int consumed;
+    const int K = mt_batch(m, i, lo, mask, lane, v, acc, bits, consumed);
+    if (acc) record((n - 1) - (i - __popcll(bits & lt)), v);  // 0-based index of this swap
+    i -= K;
+    m.pos += consumed;
+  }
+  return true;
+}
+
+// The shell of a sampling kernel (ONE workgroup of kMtThreads): ring and control words in LDS, mt_open, the kernel's
+// only barrier, then the waves part.  Waves 1 .. kMtProd produce until the consumer closes the stream and get
+// kMtProducer back.  Wave 0 calls body(m, img) for the images in order (the generator state carries from image to
+// image) until one stalls the stream, writes back the state numpy would hold now (mt_close) and gets 1 if the stream
+// overran (the sample is not valid), 0 if not.
+constexpr int kMtProducer = -1;
+template <typename Body>
+__device__ __forceinline__ int mt_consume(int* mt, int B, Body body) {
+  __shared__ unsigned ring[kMtRing], tring[kMtRing];
+  __shared__ __attribute__((aligned(16))) int ctl[8];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  mt_open(ring, tring, ctl, mt);
+  __syncthreads();   // (the only barrier: before the waves part)
+  if (wave >= 1) {
+    mt_produce(ring, tring, ctl, wave - 1, lane);
+    return kMtProducer;
+  }
+  MtStream m{ring, tring, ctl, mt[624]};
+  const int pos0 = m.pos;
+  for (int img = 0; img < B && !mt_ld(ctl + 6); ++img) body(m, img);
+  return mt_close(m, pos0, mt, lane) ? 1 : 0;
 }
 
 }  // namespace sd

@@ -20,6 +20,7 @@
 //                         Kept boxes are written straight to out/score; the tail is zero padded.
 // No host round trip, no device synchronisation, one stream.
 #include "select_common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(ScanArgs a) {
     if (a.nb > 32 && lane == 0) kw[rb] = keepmask;  // LDS copy only for the generic path
     // PrepareOutput (nms.cu:207-233) for the boxes kept in this block
     if (keepmask & (1ull << lane)) {
-      const int rank = nkeep + __popcll(keepmask & ((1ull << lane) - 1));
+      const int rank = nkeep + lanes_before(keepmask, lane);
       if (rank < a.post) {
         reinterpret_cast<float4*>(out)[rank] = bx;
         score[rank] = sc;
@@ -642,7 +643,7 @@ __global__ __launch_bounds__(256) void topk_compact_kernel(PropArgs a) {
         const int i = i0 + u * 256 + tid;
         int r = rank;
         for (int w = 0; w < wave; ++w) r += tcount[u][w];
-        r += __popcll(beq[u] & ((1ull << lane) - 1));
+        r += lanes_before(beq[u], lane);
         const bool eq = (beq[u] >> lane) & 1ull;
         bal[u] = __ballot(i < hi && (kk[u] < Tkey || (eq && r < s.want)));
         rank += tcount[u][0] + tcount[u][1] + tcount[u][2] + tcount[u][3];
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(256) void topk_compact_kernel(PropArgs a) {
     for (int u = 0; u < 8; ++u) {
       const int i = i0 + u * 256 + tid;
       if ((bal[u] >> lane) & 1ull) {
-        const int pos = base + __popcll(bal[u] & ((1ull << lane) - 1));
+        const int pos = base + lanes_before(bal[u], lane);
         if (pos < a.P2) cand[pos] = ((unsigned long long)kk[u] << 32) | (unsigned)i;
       }
       base += __popcll(bal[u]);

@@ -8,7 +8,7 @@
 //   1. pt_assign_kernel   one workgroup per image: order-preserving compaction of the valid gt
 //                         boxes and of the rois with y2 > 0 (+ appended gt), IoU of every candidate
 //                         against the gt boxes held in LDS, first-maximum arg-max, then the fg / neg
-//                         / bg index lists in candidate order (block-wide prefix scans).
+//                         / bg index lists in candidate order (the scans of wg_common.h).
 //   2. pt_sample_kernel   ONE workgroup, images in order: replays the reference's random_shuffle
 //                         calls bit for bit from the glibc state kept in device memory (the draw
 //                         count is data dependent, so the state has to live where the data is):
@@ -20,6 +20,7 @@
 // Float parity: IoU and the delta arithmetic use the reference's operation order with IEEE divide
 // (bit exact); log() is the device logf, within 1 ulp of glibc logf (tests: 1e-6 relative).
 #include "common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -63,26 +64,6 @@ struct PtArgs {
   int* kept_index;
 };
 
-// block-wide exclusive prefix sum of a 0/1 flag in thread order; returns this thread's offset and
-// the block total (all threads must call)
-template <int THREADS>
-__device__ __forceinline__ int block_scan_flag(bool flag, int* wave_sums, int* total) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const unsigned long long b = __ballot(flag);
-  const int within = __popcll(b & ((1ull << lane) - 1));
-  __syncthreads();  // wave_sums may still be read from a previous call
-  if (lane == 0) wave_sums[wave] = __popcll(b);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < THREADS / kWave; ++w) {
-    const int v = wave_sums[w];
-    if (w < wave) off += v;
-    tot += v;
-  }
-  *total = tot;
-  return off + within;
-}
-
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void pt_assign_kernel(PtArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -97,37 +78,32 @@ __global__ __launch_bounds__(THREADS) void pt_assign_kernel(PtArgs a) {
   int* gtsrc = ws.gtsrc + (long)img * a.Mws;
 
   // ---- valid gt boxes (cls != -1), order preserved (proposal_target-inl.h:155-162) ----
-  int n_gt = 0;
-  for (int base = 0; base < a.M; base += THREADS) {
-    const int j = base + tid;
-    float g[5] = {0, 0, 0, 0, -1};
-    if (j < a.M)
-      for (int k = 0; k < 5; ++k) g[k] = a.gt[((long)img * a.M + j) * 5 + k];
-    const bool ok = j < a.M && g[4] != -1.f;
-    int tot;
-    const int off = block_scan_flag<THREADS>(ok, wave_sums, &tot);
-    if (ok) {
-      const float4 b = make_float4(g[0], g[1], g[2], g[3]);
-      gbox[n_gt + off] = b;
-      garea[n_gt + off] = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
-      gtbox[n_gt + off] = b;
-      gtcls[n_gt + off] = g[4];
-      gtsrc[n_gt + off] = j;
-    }
-    n_gt += tot;
-  }
+  float4 g;
+  float gc;
+  int n_gt = block_compact_rows<THREADS>(
+      a.M, wave_sums,
+      [&](int j) {
+        const float* p = a.gt + ((long)img * a.M + j) * 5;
+        g = make_float4(p[0], p[1], p[2], p[3]);
+        gc = p[4];
+        return gc != -1.f;
+      },
+      [&](int j, int k) {
+        gbox[k] = g;
+        garea[k] = (g.z - g.x + 1.f) * (g.w - g.y + 1.f);
+        gtbox[k] = g;
+        gtcls[k] = gc;
+        gtsrc[k] = j;
+      });
   // ---- candidate rois: y2 > 0 in order (:171-175), then every valid gt box (:177-185) ----
-  int n_cand = 0;
-  for (int base = 0; base < a.N; base += THREADS) {
-    const int j = base + tid;
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < a.N) r = reinterpret_cast<const float4*>(a.rois)[(long)img * a.N + j];
-    const bool ok = j < a.N && r.w > 0.f;
-    int tot;
-    const int off = block_scan_flag<THREADS>(ok, wave_sums, &tot);
-    if (ok) cand[n_cand + off] = r;
-    n_cand += tot;
-  }
+  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);   // (left undefined, the row is kept in scratch across the scan)
+  int n_cand = block_compact_rows<THREADS>(
+      a.N, wave_sums,
+      [&](int j) {
+        r = reinterpret_cast<const float4*>(a.rois)[(long)img * a.N + j];
+        return r.w > 0.f;
+      },
+      [&](int, int k) { cand[k] = r; });
   __syncthreads();
   if (!a.p.proposal_without_gt) {
     if (a.valid_ranges && a.filter_scales) {
@@ -135,20 +111,15 @@ __global__ __launch_bounds__(THREADS) void pt_assign_kernel(PtArgs a) {
       // its area lies in [valid_min^2, valid_max^2]; order preserved
       const float v0 = a.valid_ranges[2 * img], v1 = a.valid_ranges[2 * img + 1];
       const float vmin = v0 * v0, vmax = v1 * v1;
-      for (int base = 0; base < n_gt; base += THREADS) {
-        const int j = base + tid;
-        bool ok = false;
-        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (j < n_gt) {
-          b = gbox[j];
-          const float w = (float)((double)(b.z - b.x) + 1.0), h = (float)((double)(b.w - b.y) + 1.0);
-          ok = !(w * h < vmin || w * h > vmax);
-        }
-        int tot;
-        const int off = block_scan_flag<THREADS>(ok, wave_sums, &tot);
-        if (ok) cand[n_cand + off] = b;
-        n_cand += tot;
-      }
+      float4 b;
+      n_cand = block_compact_rows<THREADS>(
+          n_gt, wave_sums,
+          [&](int j) {
+            b = gbox[j];
+            const float w = (float)((double)(b.z - b.x) + 1.0), h = (float)((double)(b.w - b.y) + 1.0);
+            return !(w * h < vmin || w * h > vmax);
+          },
+          [&](int, int k) { cand[k] = b; }, n_cand);
     } else {
       for (int j = tid; j < n_gt; j += THREADS) cand[n_cand + j] = gbox[j];
       n_cand += n_gt;

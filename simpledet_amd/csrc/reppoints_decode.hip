@@ -6,7 +6,7 @@
 // reshape, three take, concat, scale, add and four clip chains; then a padded column and the concat of the levels.
 // Per level l and image i, with p = y*W + x and s = stride_l:
 //   builder.py:518      score[p, c] = cls[i, c, y, x] (input_logits = 0) or 1.0f / (1.0f + expf(-cls)) per element
-//                       (input_logits = 1; fcos_common.h: the expression sd_fcos_sigmoid computes, equal bits).  The
+//                       (input_logits = 1; loss_common.h sigmoid_f32: the expression sd_fcos_sigmoid computes, equal bits).  The
 //                       sigmoid is NOT taken of the maximum logit: nothing says expf is monotone to the last bit.
 //   builder.py:519      m[p] = max_c score[p, c]
 //   builder.py:520      the K_l best m in descending order, K_l = k_l > 0 ? k_l : H_l*W_l (MXNet topk, k < 1 = all).
@@ -39,7 +39,7 @@
 //                        rows coalesced.
 // Every element of both outputs is written by every call.  Loads are scalar, so any 4-byte aligned pointer gives
 // the same bits.  Arithmetic: -ffp-contract=off, correctly rounded divide and sqrt (Makefile).
-#include "fcos_common.h"
+#include "loss_common.h"
 #include "reppoints_common.h"
 #include "select_common.h"
 #include "../../include/simpledet_ops.h"
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kRdT) void rd_max_kernel(RdArgs a) {
 #pragma unroll
     for (int u = 0; u < kRdUnroll; ++u) {
       const int c = c0 + u * kRdWaves;
-      if (c < C) best = fmaxr(best, a.logits ? fcos_sigmoid(v[u]) : v[u]);
+      if (c < C) best = fmaxr(best, a.logits ? sigmoid_f32(v[u]) : v[u]);
     }
   }
   sm[wave][lane] = best;
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kRdT) void rd_gather_kernel(RdArgs a) {
     if (q > 0) {
       const int l = sl[j], HW = a.H[l] * a.W[l];
       v = a.cls[l][((long)img * a.C + (q - 1)) * HW + sp[j]];
-      if (a.logits) v = fcos_sigmoid(v);
+      if (a.logits) v = sigmoid_f32(v);
     }
     os[e] = v;
   }

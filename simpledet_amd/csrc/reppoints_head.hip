@@ -27,6 +27,8 @@
 // arithmetic is the reference's float32 expressions one operation at a time (-ffp-contract=off, correctly rounded
 // divide / sqrt); the sums over the points of a set run sequentially in point order.
 #include "reppoints_common.h"
+#include "loss_common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -52,23 +54,6 @@ __device__ __forceinline__ int rp_level(const RpLevels& g, int j) {
   int l = 0;
   while (l + 1 < g.L && j >= g.begin[l + 1]) ++l;
   return l;
-}
-
-__device__ __forceinline__ int rp_block_sum_i32(int v, int* sh) {
-  v = wave_sum_i32(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
-  __syncthreads();
-  const int r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float rp_block_sum_f32(float v, float* sh) {
-  v = wave_sum_f32(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
-  __syncthreads();
-  const float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
 }
 
 // ------------------------------------------------------------------------------- points -> box --
@@ -242,8 +227,8 @@ __global__ __launch_bounds__(kRpT) void rp_assign_kernel(RpTargetArgs a) {
     o[2] = as > 0.f ? g[2] : 0.f; o[3] = as > 0.f ? g[3] : 0.f;
     cr = 1.0f <= lr;
   }
-  ci = rp_block_sum_i32(ci, shi);
-  cr = rp_block_sum_i32(cr, shi);
+  ci = block_sum_i32<kRpT>(ci, shi);
+  cr = block_sum_i32<kRpT>(cr, shi);
   if (threadIdx.x == 0) {
     const int b = blockIdx.y * gridDim.x + blockIdx.x;
     a.part[2 * b] = ci;
@@ -258,8 +243,8 @@ __global__ __launch_bounds__(kRpT) void rp_state_kernel(const int* __restrict__ 
     ci += part[2 * b];
     cr += part[2 * b + 1];
   }
-  ci = rp_block_sum_i32(ci, shi);
-  cr = rp_block_sum_i32(cr, shi);
+  ci = block_sum_i32<kRpT>(ci, shi);
+  cr = block_sum_i32<kRpT>(cr, shi);
   if (threadIdx.x == 0) {
     state[0] = ci;
     state[1] = cr;
@@ -283,19 +268,8 @@ struct RpLossArgs {
   RpLevels g;
 };
 
-// mshadow_op::smooth_l1_loss / smooth_l1_gradient with sigma = 3 (X.smooth_l1(scalar=3.0))
-__device__ __forceinline__ float rp_smooth_l1(float a) {
-  const float bsq = 3.0f * 3.0f, ibsq = 1.0f / bsq;
-  if (a > ibsq) return a - 0.5f * ibsq;
-  if (a < -ibsq) return -a - 0.5f * ibsq;
-  return 0.5f * a * a * bsq;
-}
-__device__ __forceinline__ float rp_smooth_l1_grad(float a) {
-  const float bsq = 3.0f * 3.0f, ibsq = 1.0f / bsq;
-  if (a > ibsq) return 1.0f;
-  if (a < -ibsq) return -1.0f;
-  return bsq * a;
-}
+// smooth_l1 / smooth_l1_grad (loss_common.h) with sigma = 3 (X.smooth_l1(scalar=3.0))
+constexpr float kRpBsq = 9.0f, kRpIbsq = 1.0f / 9.0f;
 
 struct RpLoc { int n, j, l, p, hw; float s, cx, cy; };
 __device__ __forceinline__ RpLoc rp_loc(const RpLevels& g, unsigned i) {
@@ -340,7 +314,7 @@ __global__ __launch_bounds__(kRpT) void rp_loss_fwd_kernel(RpLossArgs a) {
     const float* g = a.gtb[st] + (long)i * 4;
     float* o = a.loss[st] + (long)i * 4;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = rp_smooth_l1((box[e] - g[e]) / nt) * w;
+    for (int e = 0; e < 4; ++e) o[e] = smooth_l1((box[e] - g[e]) / nt, kRpBsq, kRpIbsq) * w;
   }
 }
 
@@ -393,7 +367,7 @@ __global__ __launch_bounds__(kRpT) void rp_loss_bwd_kernel(RpLossArgs a) {
       const float w = a.label[st][i] > 0.f ? 1.0f : 0.0f;
       const float* g = a.gtb[st] + (long)i * 4;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) gb[e] = ((g0 * w) * rp_smooth_l1_grad((box[e] - g[e]) / nt)) / nt;
+      for (int e = 0; e < 4; ++e) gb[e] = ((g0 * w) * smooth_l1_grad((box[e] - g[e]) / nt, kRpBsq, kRpIbsq)) / nt;
       if (TR == kRpMoment) {
         acc[2 * st] = rp_moment_bwd<K>(x, e0, gb[0], gb[2], dx);
         acc[2 * st + 1] = rp_moment_bwd<K>(y, e1, gb[1], gb[3], dy);
@@ -415,7 +389,7 @@ __global__ __launch_bounds__(kRpT) void rp_loss_bwd_kernel(RpLossArgs a) {
   if (TR == kRpMoment) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float v = rp_block_sum_f32(acc[c], sh);
+      const float v = block_sum_f32<kRpT>(acc[c], sh);
       if (threadIdx.x == 0) a.part[4 * blockIdx.x + c] = v;
     }
   }
@@ -429,7 +403,7 @@ __global__ __launch_bounds__(kRpT) void rp_dmt_kernel(const float* __restrict__ 
   if (moment) {
     for (int b = threadIdx.x; b < blocks; b += kRpT)
       for (int c = 0; c < 4; ++c) s[c] += part[4 * b + c];
-    for (int c = 0; c < 4; ++c) s[c] = rp_block_sum_f32(s[c], sh);
+    for (int c = 0; c < 4; ++c) s[c] = block_sum_f32<kRpT>(s[c], sh);
   }
   if (threadIdx.x == 0) {
     for (int k = 0; k < 2; ++k) {

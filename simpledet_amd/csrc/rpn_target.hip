@@ -18,8 +18,8 @@
 //   rpn_label     label -1/0/1 per anchor (:462-477, including the reference's own looseness: every
 //                 anchor whose overlap EQUALS a gt's maximum and is >= min_pos_thr is positive --
 //                 with min_pos_thr = 0 a gt box nothing overlaps makes every valid anchor positive),
-//                 per-block fg / bg counts; rpn_scan + rpn_lists turn them into the ordered index
-//                 lists np.where would return
+//                 per-block fg / bg counts; rpn_scan + rpn_lists (block_scan_flags, wg_common.h) turn them
+//                 into the ordered index lists np.where would return
 //   rpn_sample    ONE workgroup, images in order (the generator state carries from image to image); round 6: five
 //                 waves that meet through LDS counters only --
 //                 * four PRODUCER waves make MT19937's raw sequence (X[j] = X[j-227] ^ tw(X[j-624], X[j-623]):
@@ -39,6 +39,7 @@
 #include "common.h"
 #include "bbox_iou.h"
 #include "mt19937.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -119,32 +120,18 @@ __device__ __forceinline__ AnchorRef rpn_anchor(const RpnArgs& a, int n, bool po
 // valid gt rows (gt[:,0] != -1), order preserved, into LDS; returns their number (all threads)
 template <int THREADS>
 __device__ int rpn_load_gt(const RpnArgs& a, int img, float4* gbox, int* wsum, float* gcls = nullptr) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int n_gt = 0;
-  for (int base = 0; base < a.M; base += THREADS) {
-    const int j = base + tid;
-    float4 g = make_float4(-1.f, 0.f, 0.f, 0.f);
-    if (j < a.M) {
-      const float* p = a.gt + ((long)img * a.M + j) * a.G;
-      g = make_float4(p[0], p[1], p[2], p[3]);
-    }
-    const bool ok = j < a.M && g.x != -1.f;
-    const unsigned long long m = __ballot(ok);
-    __syncthreads();
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int off = n_gt, tot = 0;
-    for (int w = 0; w < THREADS / kWave; ++w) {
-      if (w < wave) off += wsum[w];
-      tot += wsum[w];
-    }
-    if (ok) {
-      const int k = off + __popcll(m & ((1ull << lane) - 1));
-      gbox[k] = g;
-      if (gcls) gcls[k] = a.gt[((long)img * a.M + j) * a.G + 4];  // (retina: the class column, G = 5)
-    }
-    n_gt += tot;
-  }
+  float4 g;
+  const int n_gt = block_compact_rows<THREADS>(
+      a.M, wsum,
+      [&](int j) {
+        const float* p = a.gt + ((long)img * a.M + j) * a.G;
+        g = make_float4(p[0], p[1], p[2], p[3]);
+        return g.x != -1.f;
+      },
+      [&](int j, int k) {
+        gbox[k] = g;
+        if (gcls) gcls[k] = a.gt[((long)img * a.M + j) * a.G + 4];  // (retina: the class column, G = 5)
+      });
   __syncthreads();
   return n_gt;
 }
@@ -279,18 +266,15 @@ __global__ __launch_bounds__(1024) void rpn_scan_kernel(RpnArgs a) {
 
 __global__ __launch_bounds__(kRpnT) void rpn_lists_kernel(RpnArgs a) {
   __shared__ int wcnt[2][kRpnT / kWave];
-  const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.x * kRpnT + tid;
+  const int img = blockIdx.y;
+  const int n = blockIdx.x * kRpnT + threadIdx.x;
   const int lab = n < a.N ? (int)a.label[(long)img * a.N + n] : -1;
-  const unsigned long long mf = __ballot(lab == 1), mb = __ballot(lab == 0);
-  if (lane == 0) { wcnt[0][wave] = __popcll(mf); wcnt[1][wave] = __popcll(mb); }
-  __syncthreads();
-  int off0 = a.blk[((long)img * a.nblk + blockIdx.x) * 2];
-  int off1 = a.blk[((long)img * a.nblk + blockIdx.x) * 2 + 1];
-  for (int wv = 0; wv < wave; ++wv) { off0 += wcnt[0][wv]; off1 += wcnt[1][wv]; }
-  const unsigned long long lt = (1ull << lane) - 1;
-  if (lab == 1) a.fg_list[(long)img * a.N + off0 + __popcll(mf & lt)] = n;
-  if (lab == 0) a.bg_list[(long)img * a.N + off1 + __popcll(mb & lt)] = n;
+  const bool flag[2] = {lab == 1, lab == 0};
+  int off[2] = {0, 0}, tot[2];
+  block_scan_flags<kRpnT, 2, false>(flag, wcnt, off, tot);   // (one scan per workgroup: no barrier in front)
+  const int* blk = a.blk + ((long)img * a.nblk + blockIdx.x) * 2;   // this workgroup's offsets from rpn_scan
+  if (lab == 1) a.fg_list[(long)img * a.N + blk[0] + off[0]] = n;
+  if (lab == 0) a.bg_list[(long)img * a.N + blk[1] + off[1]] = n;
 }
 
 // ---- MT19937 (numpy legacy RandomState): producer waves and a consumer wave, mt19937.h -------------
@@ -300,40 +284,17 @@ constexpr int kRpnMaxKeep = 1024;
 // (choice(inds, n - keep, replace=False) disables the FIRST n - keep): fills surv[0..keep) with the
 // list positions that survive and advances the generator by exactly the draws numpy consumes.
 __device__ void rpn_sample(MtStream& m, int n, int keep, int* jrec, int* hp, int* hv, int* surv, int lane) {
-  int i = n - 1;
-  const unsigned long long lt = (1ull << lane) - 1;
-  while (i >= 1) {
-    // the consumer no longer needs anything before the block its last draw came from (the final state is that block)
-    mt_st(m.ctl + 4, m.pos > 624 ? m.pos - 624 : 0);
-    // Trip size by mask: the unsettled candidates of an L-draw trip number ~L * (L / 2) / mask -- a handful for 1024
-    // draws from mask 2^17 on (where four fifths of the draws are spent), for 512 from 2^15, for 128 from 2^11;
-    // below that, and inside the recorded swaps, batch by batch.
-    const bool past = (n - 1) - i >= keep;
-    const int nb = !past || i < 1024 ? 1 : i < 16384 ? 2 : i < 65536 ? 8 : 16;
-    if (!mt_need(m, nb * kWave)) return;
-    const unsigned mask = mt_mask(i);
-    const int lo = (int)(mask >> 1) + 1;  // steps i in [lo, mask] share this rejection mask
-    if (nb > 1) {
-      const int K = nb == 16 ? mt_trip<16>(m, i, lo, mask, lane) : nb == 8 ? mt_trip<8>(m, i, lo, mask, lane)
-                                                                          : mt_trip<2>(m, i, lo, mask, lane);
-      if (K >= 0) {
-        i -= K;
-        m.pos += nb * kWave;
-        continue;
-      }
-    }
-    unsigned v;
-    bool acc;
-    unsigned long long bits;
-    int consumed;
-    const int K = mt_batch(m, i, lo, mask, lane, v, acc, bits, consumed);
-    if (acc) {
-      const int step = (n - 1) - (i - __popcll(bits & lt));  // 0-based index of this swap
-      if (step < keep) jrec[step] = (int)v;
-    }
-    i -= K;
-    m.pos += consumed;
-  }
+  // Trip size by mask: the unsettled candidates of an L-draw trip number ~L * (L / 2) / mask -- a handful for 1024
+  // draws from mask 2^17 on (where four fifths of the draws are spent), for 512 from 2^15, for 128 from 2^11;
+  // below that, and inside the recorded swaps, batch by batch.
+  auto trip_size = [&](int i, int step) {
+    const bool past = step >= keep;
+    return !past || i < 1024 ? 1 : i < 16384 ? 2 : i < 65536 ? 8 : 16;
+  };
+  auto record = [&](int step, unsigned v) {
+    if (step < keep) jrec[step] = (int)v;
+  };
+  if (!mt_permutation_draws(m, n, lane, trip_size, record)) return;
   wave_lds_sync();
   // replay the first `keep` swaps on a sparse array: position p holds p unless a swap wrote it
   for (int s = 0; s < keep; ++s) {
@@ -363,21 +324,11 @@ __device__ void rpn_sample(MtStream& m, int n, int keep, int* jrec, int* hp, int
   }
 }
 
-__global__ __launch_bounds__((1 + kMtProd) * kWave) void rpn_sample_kernel(RpnArgs a) {
-  __shared__ unsigned ring[kMtRing], tring[kMtRing];
-  __shared__ __attribute__((aligned(16))) int ctl[8];
+__global__ __launch_bounds__(kMtThreads) void rpn_sample_kernel(RpnArgs a) {
   __shared__ int jrec[kRpnMaxKeep], hp[kRpnMaxKeep], hv[kRpnMaxKeep], surv[kRpnMaxKeep];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  mt_open(ring, tring, ctl, a.mt);
-  __syncthreads();   // (the only barrier: before the waves part)
-  if (wave >= 1) {
-    mt_produce(ring, tring, ctl, wave - 1, lane);
-    return;
-  }
-  MtStream m{ring, tring, ctl, a.mt[624]};
-  const int pos0 = m.pos;
+  const int lane = threadIdx.x & (kWave - 1);
   const int num = a.p.image_anchor;
-  for (int img = 0; img < a.B && !mt_ld(ctl + 6); ++img) {
+  const int overrun = mt_consume(a.mt, a.B, [&](MtStream& m, int img) {
     int* c = a.counts + img * 4;
     const int n_fg = c[0], n_bg = c[1];
     int fg_left = n_fg;
@@ -400,9 +351,8 @@ __global__ __launch_bounds__((1 + kMtProd) * kWave) void rpn_sample_kernel(RpnAr
       if (lane == 0) c[3] = 1;
     }
     wave_lds_sync();
-  }
-  // the state numpy would hold now goes back; then the producers may leave
-  if (mt_close(m, pos0, a.mt, lane) && lane == 0) a.counts[a.B * 4] = 1;   // overrun: the sample is not valid
+  });
+  if (overrun == 1 && lane == 0) a.counts[a.B * 4] = 1;   // the sample is not valid
 }
 
 // nonlinear_transform (operator_py/bbox_transform.py:52-77) on a float64 anchor / float32 gt box
@@ -673,7 +623,7 @@ extern "C" int sd_rpn_anchor_target(const float* im_info, const float* gt_bbox, 
   hipLaunchKernelGGL(rpn_label_kernel, grid, dim3(kRpnT), lds, st, a);
   hipLaunchKernelGGL(rpn_scan_kernel, dim3(B), dim3(1024), 0, st, a);
   hipLaunchKernelGGL(rpn_lists_kernel, grid, dim3(kRpnT), 0, st, a);
-  hipLaunchKernelGGL(rpn_sample_kernel, dim3(1), dim3((1 + kMtProd) * kWave), 0, st, a);
+  hipLaunchKernelGGL(rpn_sample_kernel, dim3(1), dim3(kMtThreads), 0, st, a);
   hipLaunchKernelGGL(rpn_encode_kernel, grid, dim3(kRpnT), 0, st, a);
   SD_LAUNCH_CHECK();
   return SD_OK;

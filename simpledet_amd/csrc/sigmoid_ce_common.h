@@ -5,6 +5,7 @@
 // sigmoid_ce.hip.
 #pragma once
 #include "common.h"
+#include "loss_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -26,9 +27,6 @@ __device__ __forceinline__ float ce_grad(float x, float t, float count_sum, floa
   const float g = (float)(1.0 / (1.0 + (double)expf(-x)) - (double)t);
   return (g / count_sum) * scale;
 }
-
-// MXNet's Activation(act_type='sigmoid') in fp32 (mshadow_op::sigmoid): the Mask Scoring R-CNN mask_pred_prob
-__device__ __forceinline__ float ce_prob(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // (int)cls when it names a plane, -1 otherwise (NaN fails both comparisons)
 __device__ __forceinline__ int mask_class(float c, unsigned K) {
@@ -230,7 +228,7 @@ static __global__ __launch_bounds__(kCeT) void ce_rows_kernel(const float* __res
 
 // fused backward, second pass: a workgroup per plane (r, kk) of d_logits, every plane written exactly once.
 // VST: 16-byte stores; VLD: 16-byte loads of the selected plane, its targets and (DP) its d_prob row.
-// DP: the selected plane also receives d_prob * (p * (1 - p)), p = ce_prob(x) -- the gradient that arrives
+// DP: the selected plane also receives d_prob * (p * (1 - p)), p = sigmoid_f32(x) -- the gradient that arrives
 // through the gathered sigmoid (msrcnn_head.hip); at an ignored element (t == -1) that term stands alone.
 template <bool VST, bool VLD, bool DP>
 __global__ __launch_bounds__(kCeT) void mask_loss_bwd_kernel(const float* __restrict__ logits,
@@ -265,7 +263,7 @@ __global__ __launch_bounds__(kCeT) void mask_loss_bwd_kernel(const float* __rest
           if (t.z != -1.0f) d.z = ce_grad(x.z, t.z, cs, scale);
           if (t.w != -1.0f) d.w = ce_grad(x.w, t.w, cs, scale);
           if (DP) {
-            const float4 p = make_float4(ce_prob(x.x), ce_prob(x.y), ce_prob(x.z), ce_prob(x.w));
+            const float4 p = make_float4(sigmoid_f32(x.x), sigmoid_f32(x.y), sigmoid_f32(x.z), sigmoid_f32(x.w));
             d.x = d.x + g.x * (p.x * (1.0f - p.x));
             d.y = d.y + g.y * (p.y * (1.0f - p.y));
             d.z = d.z + g.z * (p.z * (1.0f - p.z));
@@ -283,7 +281,7 @@ __global__ __launch_bounds__(kCeT) void mask_loss_bwd_kernel(const float* __rest
             const float x = logits[base + i];
             const float g = dp[i];
             if (t != -1.0f) d = ce_grad(x, t, cs, scale);
-            const float p = ce_prob(x);
+            const float p = sigmoid_f32(x);
             d = d + g * (p * (1.0f - p));
           } else if (t != -1.0f) {
             d = ce_grad(logits[base + i], t, cs, scale);

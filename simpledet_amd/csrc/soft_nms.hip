@@ -16,6 +16,7 @@
 // Arithmetic follows the Cython-generated C expression by expression: "+ 1" is a DOUBLE add there
 // (the literal becomes 1.0), products of two such terms are double products narrowed on assignment.
 #include "common.h"
+#include "wg_common.h"
 #include "../../include/simpledet_ops.h"
 #include <math.h>
 
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(THREADS) void soft_nms_kernel(SoftArgs a) {
         if (!ovl && s == s) c = better(c, cand_of(s, pos));
       }
       const unsigned long long bal = __ballot(ovl);
-      if (ovl) QL[nq + __popcll(bal & ((1ull << lane) - 1))] = pos;
+      if (ovl) QL[nq + lanes_before(bal, lane)] = pos;
       nq += __popcll(bal);
       if (lane == 0) FW[chunk] = 0ull;
     }

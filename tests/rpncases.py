@@ -27,6 +27,15 @@ CASES = {
 }
 
 
+def rows_past_one_workgroup(threads):
+    """(M, valid rows of image 0, valid rows of image 1) of a gt list LONGER than the `threads` rows a
+    workgroup compacts per trip: valid rows at both ends of the first trip, around its wave boundary and on
+    either side of the trip boundary, everything else padding; image 1 holds its last row only.  The
+    compaction must carry its running total from trip to trip and keep the rows in order."""
+    M = threads + 65
+    return M, (0, 62, 63, 64, 65, threads - 1, threads, threads + 1, threads + 64), (M - 1,)
+
+
 def inputs(case):
     """[(im_info float32 (3,), gt_bbox float32 (100, 5))] for the images of a case"""
     out = []

@@ -443,6 +443,60 @@ def _pt_check(ops, oracle, rois, gt, seed=1, **kw):
     return want
 
 
+def _pt_long_gt_case():
+    """B = 2, more gt rows than the 1024 a workgroup of pt_assign_kernel compacts per trip
+    (rpncases.rows_past_one_workgroup), 64 proposals.  The nine boxes of image 0 differ in place, size and
+    class, and every one joins the candidates; with image_rois = 256 every foreground is kept, in candidate order:
+    a dropped or misplaced row changes labels, targets or indices."""
+    from .rpncases import rows_past_one_workgroup
+    M, rows0, rows1 = rows_past_one_workgroup(1024)
+    rs = np.random.RandomState(31)
+    gt = -np.ones((2, M, 5), np.float32)
+    rois = np.zeros((2, 64, 4), np.float32)
+    for b, rows in enumerate((rows0, rows1)):
+        boxes = []
+        for k, r in enumerate(rows):
+            x1, y1 = 20 + 100 * k, 30 + 40 * k
+            gt[b, r] = (x1, y1, x1 + 60 + 5 * k, y1 + 50 + 4 * k, 1 + k)
+            boxes.append(gt[b, r, :4])
+        for i in range(60):   # four rows stay all-zero padding (y2 == 0)
+            near = boxes[i % len(boxes)] + np.round(rs.uniform(-6, 6, 4))
+            far = np.array([3000 + 10 * i, 50, 3100 + 10 * i, 90 + i])
+            rois[b, i if i < 30 else i + 4] = near if i % 3 else far
+    return rois, gt
+
+
+def test_proposal_target_long_gt_list_case_tells_a_dropped_or_misplaced_row(oracle):
+    """the oracle on the padded list == on its valid rows alone; without any one row, or with two rows
+    exchanged, the expected values change"""
+    rois, gt = _pt_long_gt_case()
+
+    def run(g):
+        return oracle.proposal_target(rois, g, oracle.make_pt_param(81, 2, 256), rng=oracle.GlibcRand(1))
+    want = run(gt)
+    assert gt.shape[1] == 1024 + 65 and want[6] == 0 and (want[1][0] > 0).any() and (want[1][1] > 0).any()
+    dense = np.stack([np.concatenate([g[g[:, 4] != -1], g[g[:, 4] == -1]]) for g in gt])[:, :16]
+    for a, b in zip(want[:6], run(dense)[:6]):
+        np.testing.assert_array_equal(a, b)
+    rows = np.where(gt[0, :, 4] != -1)[0]
+    same = lambda got: all(np.array_equal(a, b) for a, b in zip(want[:6], got[:6]))
+    for r in rows:
+        other = gt.copy()
+        other[0, r] = -1
+        assert not same(run(other)), r
+    for r, s in zip(rows[:-1], rows[1:]):
+        other = gt.copy()
+        other[0, [r, s]] = other[0, [s, r]]
+        assert not same(run(other)), (r, s)
+
+
+@pytest.mark.gpu
+def test_proposal_target_long_gt_list_crosses_the_workgroup_width(ops, oracle):
+    """M = 1024 + 65 gt rows: the valid-gt loader of pt_assign_kernel takes two trips"""
+    rois, gt = _pt_long_gt_case()
+    _pt_check(ops, oracle, rois, gt, image_rois=256)
+
+
 @pytest.mark.gpu
 def test_proposal_target_baseline_config(ops, oracle):
     rois, gt = synth.proposal_target_inputs(0, 2, 2000, 100)

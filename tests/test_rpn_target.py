@@ -80,7 +80,63 @@ def test_zero_overlap_gt_quirk_is_in_the_fixture():
     assert (lab == 1).sum() == 128 and (lab == 0).sum() == 0
 
 
+def _long_gt_case():
+    """B = 2, more gt rows than the 256 a workgroup of csrc/rpn_target.hip (kRpnT) compacts per trip
+    (rpncases.rows_past_one_workgroup), on a 8 x 10 grid of 6 anchors: two workgroups per image.  The nine
+    boxes of image 0 all differ, so a dropped or overwritten row changes labels or targets."""
+    M, rows0, rows1 = rpncases.rows_past_one_workgroup(256)
+    cfg = dict(stride=16, short=8, long=10, scales=(2, 4), aspects=(0.5, 1.0, 2.0), allowed_border=16,
+               pos_thr=0.7, neg_thr=0.3, min_pos_thr=0.0, image_anchor=64, pos_fraction=0.5)
+    gt = -np.ones((2, M, 5), np.float32)
+    for b, rows in enumerate((rows0, rows1)):
+        for k, r in enumerate(rows):
+            x1, y1 = 8 + 48 * (k % 3) + k, 6 + 38 * (k // 3)
+            gt[b, r] = (x1, y1, x1 + 30 + 3 * k, y1 + 28 + 2 * k, 1 + k)
+    return cfg, np.array([[128, 160, 1.0]] * 2, np.float32), gt
+
+
+def _long_gt_expected(gt, seed=21):
+    from oracle import rpn_target as orc
+    cfg, im_info, _ = _long_gt_case()
+    rs = np.random.RandomState(seed)
+    return [orc.rpn_target_flat(im_info[b], gt[b], cfg, rs)[:3] for b in range(2)], rs.get_state()[2]
+
+
+def test_long_gt_list_case_tells_a_dropped_row():
+    """the oracle on the padded list == on its valid rows alone; without any one row the expected values change"""
+    _, _, gt = _long_gt_case()
+    want, pos = _long_gt_expected(gt)
+    assert gt.shape[1] == 256 + 65 and (want[0][0] == 1).any() and (want[1][0] == 1).any()
+    dense = np.stack([np.concatenate([g[g[:, 0] != -1], g[g[:, 0] == -1]]) for g in gt])
+    got, pos2 = _long_gt_expected(dense)
+    assert pos == pos2 and all(np.array_equal(a, b) for w, g in zip(want, got) for a, b in zip(w, g))
+    rows = np.where(gt[0, :, 0] != -1)[0]
+    for r in rows:
+        other = gt.copy()
+        other[0, r] = -1
+        assert not all(np.array_equal(a, b) for a, b in zip(want[0], _long_gt_expected(other)[0][0])), r
+
+
 # ------------------------------------------------------------------------------------------ GPU --
+@pytest.mark.gpu
+def test_hip_long_gt_list_crosses_the_workgroup_width(ops):
+    """M = 256 + 65 gt rows: the valid-gt loader of rpn_overlap / rpn_label takes two trips"""
+    import torch
+    cfg, im_info, gt = _long_gt_case()
+    want, pos = _long_gt_expected(gt)
+    p = ops.rpn_target_param(cfg["stride"], cfg["short"], cfg["long"], cfg["scales"], cfg["aspects"],
+                             cfg["allowed_border"], cfg["pos_thr"], cfg["neg_thr"], cfg["min_pos_thr"],
+                             cfg["image_anchor"], cfg["pos_fraction"])
+    state = ops.mt19937_state(seed=21)
+    cls, tgt, wgt = ops.rpn_anchor_target(torch.from_numpy(im_info).cuda(), torch.from_numpy(gt).cuda(), p, state,
+                                          layout=0)
+    for b in range(2):
+        np.testing.assert_array_equal(cls[b].cpu().numpy(), want[b][0])
+        np.testing.assert_array_equal(tgt[b].cpu().numpy(), want[b][1])
+        np.testing.assert_array_equal(wgt[b].cpu().numpy(), want[b][2])
+    assert int(state[624]) == pos
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(rpncases.CASES))
 def test_hip_reproduces_reference(ops, name):
