@@ -265,6 +265,15 @@ int sd_fpn_roi_align_bwd_packed_plan(const float* out_grad, const float* rois, c
                                      int B, int C, int R, int pooled_h, int pooled_w,
                                      float roi_canonical_scale, float roi_canonical_level, const void* plan,
                                      size_t plan_bytes, void* stream);
+/* How the band forward staffs its virtual units with whole workgroups (knob roi_align_fwd_staff = 1): unit v has
+ * n[v] channel reservations of t[v] cost units each; m_out[v] = workgroups that start on it, sum = nwg.  The smallest
+ * T with sum_v ceil(n[v] / floor((T - setup) / t[v])) <= nwg gives m; workgroups left over go one at a time to the
+ * unit that then finishes last (all of them at once when that unit already has a workgroup per reservation).
+ * m_out is all zero where the rule does not apply (nvu > nwg, no work, products past 2^30): the kernel then keeps
+ * the midpoint rule.  _ref runs on the host (host pointers), _dev runs the kernel's own form in one wave (device
+ * pointers); both exist for the tests. */
+int sd_band_staffing_ref(const int* n, const int* t, int nvu, int nwg, int setup, int* m_out);
+int sd_band_staffing_dev(const int* n, const int* t, int nvu, int nwg, int setup, int* m_out, void* stream);
 /* assign_layer_fpn CustomOp (models/FPN/assign_layer_fpn.py:10-73): rois (n_rois,4) ->
  * rois_per_level (nlvl, n_rois, 4) zero-masked, and optionally level (n_rois) int32 (-1 = none) */
 int sd_fpn_roi_assign(const float* rois, int n_rois, const int* strides_host, int nlvl,

@@ -233,6 +233,7 @@ constexpr int kBandMaxUnits = 512;      // virtual units ((level, image, band) x
 constexpr int kBandFillCost = 140, kBandPlaneCost = 60, kBandSetupCost = 1500;  // cost model, in item times
 constexpr int kBandSub = 4;             // list segments per unit (pre-pass workgroups per (level, image))
 constexpr int kBandXcdDefault = 1;      // roi_align_fwd_xcd when not set
+constexpr int kBandStaffDefault = 0;    // roi_align_fwd_staff when not set
 constexpr int kBandFallbackWGs = 0;    // (no separate exact-path blocks: the band workgroups do that work last)
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -257,6 +258,151 @@ constexpr bool band_xcd_slot_is_bijection(int nwg) {
 static_assert(band_xcd_slot_is_bijection(256) && band_xcd_slot_is_bijection(250) && band_xcd_slot(9, 256) == 33,
               "every share is taken by exactly one workgroup");
 
+// ---- integer-aware staffing (roi_align_fwd_staff = 1).  A workgroup takes a unit's channels in whole reservations,
+// so a unit v of n[v] reservations of t[v] cost units each, started on by m workgroups, ends after ceil(n / m)
+// reservations, not n / m.  The midpoint rule staffs in proportion to n t and leaves the rounding to chance; this
+// one finds the smallest D = T - setup with sum_v ceil(n[v] / floor(D / t[v])) <= nwg (binary search: the sum falls as
+// D grows), m[v] follows, and what is left of nwg goes one workgroup at a time to the unit that finishes last
+// (ties: the first) -- all of it at once when that unit already has a workgroup per reservation: nothing can
+// end sooner then, and the extra workgroups move on at once.  The SAME function runs on the host (Lanes = one serial
+// "lane") and in one wave of the kernel (lane l owns units l, l + 64, ...: only the sums and maxima cross lanes).
+// False (m untouched): more units than workgroups, no work at all, or products that do not fit -- the caller keeps
+// the midpoint rule.  `setup` moves every finish alike and so leaves m as it is; it is part of T only.
+struct BandStaffSerial {
+  static constexpr int kLanes = 1;
+  __host__ __device__ static int lane() { return 0; }
+  __host__ __device__ static int sum(int v) { return v; }
+  __host__ __device__ static unsigned maxu(unsigned v) { return v; }
+  __host__ __device__ static float rcp(float x) { return 1.0f / x; }
+};
+#if defined(__HIPCC__)
+struct BandStaffWave {   // one whole wave, every lane active
+  static constexpr int kLanes = kWave;
+  __device__ static int lane() { return (int)(threadIdx.x & (kWave - 1)); }
+  __device__ static int sum(int v) { return wave_sum_i32(v); }
+  __device__ static unsigned maxu(unsigned v) { return wave_max_u32(v); }
+  __device__ static float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+};
+#endif
+// floor(a / b) for a <= 2^30, 1 <= b <= 2^30 from an approximate reciprocal rb of b: the float estimate is off by a
+// few units at most and is walked to the exact quotient, so the result does not depend on how rb was rounded (the
+// kernel's search does two divisions per step and unit; an integer division is some forty dependent instructions)
+__host__ __device__ inline unsigned band_udiv(unsigned a, unsigned b, float rb) {
+  unsigned q = (unsigned)((float)a * rb);
+  while (q * b > a) --q;
+  while ((q + 1) * b <= a) ++q;
+  return q;
+}
+// workgroups that end n reservations of t by D (>= t): ceil(n / floor(D / t)); rt ~ 1 / t
+template <class Lanes>
+__host__ __device__ inline int band_staff_need(int n, int t, float rt, int D) {
+  if (n <= 0) return 0;
+  const unsigned k = band_udiv((unsigned)D, (unsigned)t, rt);
+  return (int)band_udiv((unsigned)n + k - 1, k, Lanes::rcp((float)k));
+}
+// (the loops over a lane's units unroll when OWN says how many there are; the memory form's cannot, which clang remarks on)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"
+// OWN > 0: a lane owns at most OWN units and keeps them in registers (the kernel: 1 up to 64 units, else 8);
+// OWN = 0: it walks its units in memory (the host)
+template <class Lanes, int OWN = 0>
+__host__ __device__ inline bool band_staffing(const int* n, const int* t, int nvu, int nwg, int setup, int* m) {
+  (void)setup;
+  constexpr bool REG = OWN > 0;
+  constexpr int NR = REG ? OWN : 1;
+  const int l0 = Lanes::lane();
+  if (nvu <= 0 || nvu > nwg || nvu > (1 << 20) || (REG && nvu > OWN * Lanes::kLanes)) return false;
+  const int own = REG ? OWN : (nvu - l0 + Lanes::kLanes - 1) / Lanes::kLanes;
+  int rn[NR], rtt[NR], rm[NR];
+  float rr[NR];
+  if (REG) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int v = l0 + i * Lanes::kLanes;
+      rn[i] = v < nvu ? n[v] : 0;    // (a unit without reservations takes no part)
+      rtt[i] = v < nvu ? t[v] : 1;
+      rr[i] = Lanes::rcp((float)rtt[i]);
+      rm[i] = 0;
+    }
+  }
+  auto N = [&](int i) { return REG ? rn[i] : n[l0 + i * Lanes::kLanes]; };
+  auto TT = [&](int i) { return REG ? rtt[i] : t[l0 + i * Lanes::kLanes]; };
+  auto RT = [&](int i) { return REG ? rr[i] : Lanes::rcp((float)t[l0 + i * Lanes::kLanes]); };
+  auto M = [&](int i) -> int& { return REG ? rm[i] : m[l0 + i * Lanes::kLanes]; };
+  // the search interval.  Below: one reservation of the dearest unit (every floor is >= 1), and the even share of
+  // all work (ceil(n / floor(D / t)) >= n t / D).  Above: the dearest whole unit (one workgroup each, nvu <= nwg), and
+  // tmax + all work / (nwg - nvu) (ceil(n / floor(D / t)) <= n t / (D - t) + 1).
+  unsigned tmax = 0, whole = 0, bad = 0;
+  long work = 0;
+#pragma unroll
+  for (int i = 0; i < (REG ? NR : own); ++i) {
+    if (N(i) <= 0) continue;
+    const long w = (long)N(i) * TT(i);
+    if (TT(i) <= 0 || w > (1L << 30)) { bad = 1; continue; }
+    tmax = (unsigned)TT(i) > tmax ? (unsigned)TT(i) : tmax;
+    whole = (unsigned)w > whole ? (unsigned)w : whole;
+    work += w >> 8;   // (in 256ths: the sum of a million units of 2^30 fits)
+  }
+  bad = Lanes::maxu(bad);
+  tmax = Lanes::maxu(tmax);
+  whole = Lanes::maxu(whole);
+  if (bad || whole == 0) return false;
+  const long hi_w = (long)Lanes::sum((int)(work >> 16)), lo_w = (long)Lanes::sum((int)(work & 0xffff));
+  work = (hi_w << 16) + lo_w;   // all work / 256, every term rounded down
+  int lo = (int)tmax, hi = (int)whole;
+  {
+    const long even = work * 256 / nwg;   // <= all work / nwg
+    if (even > lo) lo = even < hi ? (int)even : hi;
+    if (nvu < nwg) {
+      const long up = (long)tmax + ((work + nvu) * 256 + (nwg - nvu) - 1) / (nwg - nvu);   // >= tmax + all work / (nwg - nvu)
+      if (up < hi) hi = up > lo ? (int)up : lo;
+    }
+  }
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    int s = 0;
+#pragma unroll
+    for (int i = 0; i < (REG ? NR : own); ++i) s += band_staff_need<Lanes>(N(i), TT(i), RT(i), mid);
+    s = Lanes::sum(s);
+    if (s <= nwg) hi = mid; else lo = mid + 1;
+  }
+  int s = 0;
+#pragma unroll
+  for (int i = 0; i < (REG ? NR : own); ++i) {
+    M(i) = band_staff_need<Lanes>(N(i), TT(i), RT(i), lo);
+    s += M(i);
+  }
+  int spare = nwg - Lanes::sum(s);
+  while (spare > 0) {
+    // the unit that finishes last: largest ceil(n / m) t, then the smallest v; bit 0 says it cannot end sooner
+    unsigned fin = 0, who = 0;
+#pragma unroll
+    for (int i = 0; i < (REG ? NR : own); ++i) {
+      if (N(i) <= 0) continue;
+      const unsigned mi = (unsigned)M(i);
+      const unsigned f = band_udiv((unsigned)N(i) + mi - 1, mi, Lanes::rcp((float)mi)) * (unsigned)TT(i);
+      if (f > fin) {
+        fin = f;
+        who = ((unsigned)((1 << 21) - (l0 + i * Lanes::kLanes)) << 1) | (M(i) >= N(i) ? 1u : 0u);
+      }
+    }
+    const unsigned best = Lanes::maxu(fin);
+    who = Lanes::maxu(fin == best ? who : 0u);
+    const int v = (1 << 21) - (int)(who >> 1), give = (who & 1) ? spare : 1;
+#pragma unroll
+    for (int i = 0; i < (REG ? NR : own); ++i)
+      if (l0 + i * Lanes::kLanes == v) M(i) += give;
+    spare -= give;
+  }
+  if (REG) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+      if (l0 + i * Lanes::kLanes < nvu) m[l0 + i * Lanes::kLanes] = rm[i];
+  }
+  return true;
+}
+#pragma clang diagnostic pop
+
 struct BandPlan {
   int owned[SD_MAX_FPN_LEVELS];      // rows a band owns (H: the whole plane is one band)
   int rows[SD_MAX_FPN_LEVELS];       // rows a band loads (owned + halo; H for whole planes)
@@ -272,6 +418,9 @@ struct BandPlan {
   int tail_planes;                   // planes of such a piece (<= G)
   int pool;
   int xcd;                           // roi_align_fwd_xcd: 0 shares linear in blockIdx, 1 XCD-contiguous shares, 2 + levels interleaved
+  int gres[SD_MAX_FPN_LEVELS];       // channels of one reservation (grab rounded up to whole fills)
+  int nres[SD_MAX_FPN_LEVELS];       // reservations of a unit: ceil(C / gres)
+  int staff;                         // roi_align_fwd_staff: 0 start units by the midpoint of a share of the cost prefix, 1 band_staffing
   uint4* rowent;   // [B*R][pool]  {lo0 | step0 << 20 | empty << 31, lo1 | step1 << 20, a0, a1}
   uint4* colent;    // [B*R][pool]  {left0 | dup0 << 12 | left1 << 13 | dup1 << 25 | empty << 26, -, b0, b1}
   float2* rowval;   // [B*R][pool]  sample coordinates (float arg-max outputs only)

@@ -558,7 +558,7 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
   // whatever the estimate was worth), and when the unit runs dry moves to the unit with the most
   // work left ----
   __shared__ int v_unit[kBandMaxUnits], v_first[kBandMaxUnits], v_items[kBandMaxUnits];
-  __shared__ int v_cost[kBandMaxUnits], v_start[kBandMaxUnits + 1];
+  __shared__ int v_cost[kBandMaxUnits], v_start_cost[kBandMaxUnits + 1];
   __shared__ int2 s_grab[2];  // reservations {first channel, channels}
   __shared__ int s_pick;
   const int wg = (int)blockIdx.x - kBandFallbackWGs, nwg = (int)gridDim.x - kBandFallbackWGs;
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
   };
   // The table of virtual units and their cost prefix: one wave does it (lane = unit, 64 at a time,
   // wave scans: no workgroup barriers on the start-up path), the others wait at one barrier.
-  __shared__ int s_nvu;
+  __shared__ int s_nvu, s_staffed;
   auto wave_incl_scan = [&](int v) {
 #pragma unroll
     for (int o = 1; o < kWave; o <<= 1) {
@@ -625,6 +625,9 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
     }
     __syncthreads();
     // phase B: the virtual units of this wave's units, behind those of the waves before it
+    // (the band buffer is free from here on: the places of roi_align_fwd_xcd = 2 were read in phase A, no fill is out yet)
+    int* staff_n = reinterpret_cast<int*>(band_smem);
+    int *staff_t = staff_n + kBandMaxUnits, *staff_m = staff_t + kBandMaxUnits, *staff_start = staff_m + kBandMaxUnits;
     int total = 0;
 #pragma unroll
     for (int b = 0; b < NB; ++b) total += s_tot[b];
@@ -644,6 +647,10 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
         // share of the workgroups, finish early and their workgroups then join the fine-grained units)
         const int cst = kBandFillCost / P.g[lv] + kBandPlaneCost + it;
         v_cost[vb + r] = P.g[lv] > 1 ? cst + cst * P.gbias / 100 : cst;
+        if (P.staff == 1) {   // what band_staffing reads: reservations of the unit and the cost of one (see below)
+          staff_n[vb + r] = P.nres[lv];
+          staff_t[vb + r] = P.gres[lv] * v_cost[vb + r];
+        }
       }
     }
     __syncthreads();
@@ -660,18 +667,40 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
       int run = cincl - mine;
 #pragma unroll
       for (int b = 0; b < NB; ++b) run += b < wave ? s_ctot[b] : 0;
-      if (v < n) v_start[v] = run;
-      if (v == n - 1 || (n == 0 && v == 0)) v_start[n] = n == 0 ? 0 : run + mine;
+      if (v < n) v_start_cost[v] = run;
+      if (v == n - 1 || (n == 0 && v == 0)) v_start_cost[n] = n == 0 ? 0 : run + mine;
     }
     if (tid == 0) s_nvu = n;
+    // roi_align_fwd_staff = 1: whole workgroups per virtual unit by band_staffing (roi_align_common.h) instead of the
+    // midpoint of a share of the prefix above.  Wave 0 does it while the others wait at the barrier below: lane =
+    // virtual unit, in registers; m and its prefix go through the band buffer.  Where the rule does not apply
+    // (more virtual units than workgroups) the prefix above decides as before.
+    if (tid == 0) s_staffed = 0;
+    if (P.staff == 1 && wave == 0 && n > 0 && n <= nwg) {   // (uniform in the wave)
+      const bool used = n <= kWave ? band_staffing<BandStaffWave, 1>(staff_n, staff_t, n, nwg, kBandSetupCost, staff_m)
+                                   : band_staffing<BandStaffWave, NB>(staff_n, staff_t, n, nwg, kBandSetupCost, staff_m);
+      if (used) {
+        wave_lds_sync();
+        int run = 0;   // exclusive prefix of m: workgroup slot s starts on the last unit whose prefix is <= s
+        for (int k0 = 0; k0 < n; k0 += kWave) {
+          const int k = k0 + lane, mk = k < n ? staff_m[k] : 0, incl = wave_incl_scan(mk);
+          if (k < n) staff_start[k] = run + incl - mk;
+          run += __shfl(incl, kWave - 1);
+        }
+        if (lane == 0) s_staffed = 1;
+      }
+    }
   }
   __syncthreads();
   const int nvu = s_nvu;
+  const bool staffed = s_staffed != 0;
   int vu = 0;
   {
-    // the last virtual unit whose start is <= this workgroup's share of the cost (v_start ascends)
+    // the last virtual unit whose start is <= this workgroup's share of the cost (v_start ascends), or, staffed,
+    // whose prefix of workgroups is <= its slot
     const int share = P.xcd >= 1 ? band_xcd_slot(wg, nwg) : wg;
-    const long pos = (long)v_start[nvu] * (2 * share + 1) / (2 * nwg);
+    const int* v_start = staffed ? reinterpret_cast<const int*>(band_smem) + 3 * kBandMaxUnits : v_start_cost;   // (staff_start)
+    const long pos = staffed ? share : (long)v_start[nvu] * (2 * share + 1) / (2 * nwg);
     int below = 0;
     for (int k = lane; k < nvu; k += kWave) below += v_start[k] <= pos ? 1 : 0;
     below = wave_sum_i32(below);
@@ -682,7 +711,7 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
 #ifdef SD_PROFILING
   const long long t_begin = __builtin_readcyclecounter();
   long long t_setup = 0, t_wait = 0, t_comp = 0, t_mark = t_begin;
-  int dbg_count = 0, dbg_units = 0, dbg_fills = 0;
+  int dbg_count = 0, dbg_units = 0, dbg_fills = 0, dbg_res = 0, dbg_allres = 0, dbg_allfills = 0, dbg_vu0 = -1;
 #endif
   // takes the next (up to) G channels of virtual unit v: first channel, or >= C when it has run dry
   auto grab = [&](int v, int G) {
@@ -773,10 +802,12 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
   dbg_count += nitems;
   ++dbg_units;
   dbg_fills = 0;
+  dbg_res = 1;
+  if (dbg_vu0 < 0) dbg_vu0 = vu;
   t_mark = __builtin_readcyclecounter();
   if (a.dbg && lane == 0 && wave == 0 && dbg_units <= 3) {  // per visit: level, fills, items, start tick
     long long* d = a.dbg + ((long)gridDim.x * kBandWaves + (long)blockIdx.x * 4 + (dbg_units - 1)) * 8;
-    d[0] = lvl; d[2] = nitems; d[3] = t_mark; d[4] = 1;
+    d[0] = lvl; d[2] = nitems; d[3] = t_mark; d[4] = 1; d[6] = vu;
   }
 #endif
   const TIn* gbase = reinterpret_cast<const TIn*>(a.L.data[lvl]) + (long)img * a.C * HW + (long)r0 * W;  // channel 0 of the band
@@ -948,6 +979,9 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
           cend = b.x + b.y < a.C ? b.x + b.y : a.C;
           slot ^= 1;
           regrab = true;
+#ifdef SD_PROFILING
+          ++dbg_res;
+#endif
         }
       }
       if (knext < a.C) {
@@ -1053,10 +1087,18 @@ __global__ __launch_bounds__(kBandThreads) void roi_align_fwd_band(BandArgs A, B
 #ifdef SD_PROFILING
   if (a.dbg && lane == 0 && wave == 0 && dbg_units <= 3) {
     long long* d = a.dbg + ((long)gridDim.x * kBandWaves + (long)blockIdx.x * 4 + (dbg_units - 1)) * 8;
-    d[1] = dbg_fills; d[5] = __builtin_readcyclecounter();
+    d[1] = dbg_fills; d[5] = __builtin_readcyclecounter(); d[7] = dbg_res;
   }
+  dbg_allres += dbg_res;
+  dbg_allfills += dbg_fills;
 #endif
   }  // visits
+#ifdef SD_PROFILING
+  if (a.dbg && lane == 0 && wave == 0) {   // fourth record of the block: the workgroup as a whole
+    long long* d = a.dbg + ((long)gridDim.x * kBandWaves + (long)blockIdx.x * 4 + 3) * 8;
+    d[0] = __builtin_readcyclecounter(); d[1] = dbg_allres; d[2] = dbg_allfills; d[3] = dbg_vu0; d[4] = 2; d[5] = s_staffed;
+  }
+#endif
   {
     // ---- exact per-element path for the few RoIs the bands do not take (and the constant output
     // of the RoIs that pool nothing), after the band work: workgroup = (RoI slot, channel slice).
@@ -1470,12 +1512,30 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     int wg = 0;
     P.nunits = units;
     // channels a workgroup reserves at a time: 4 (single-channel grabs +7 %: the 196-byte rows of
-    // neighbouring channels merge in one CU's L2); no cost bias for multi-plane units and no shrinking
-    // reservations at a unit's end (15 / 30 % and 1..8-plane tails: measured, no effect -- round 3)
-    P.grab = 4;
+    // neighbouring channels merge in one CU's L2), 2 for the fp32 packed arg-max forward (a unit's workgroups end
+    // within half the time of one another, -2 us at the benchmark's shape, single channels lose it again:
+    // profiles/fwd_staffing_ab.txt; the other forms were not measured and keep 4); no cost bias for multi-plane units
+    // and no shrinking reservations at a unit's end (15 / 30 % and 1..8-plane tails: measured, no effect -- round 3,
+    // and again with the clocks of profiles/fwd_finish_clocks.txt)
+    // (knobs roi_align_fwd_grab / _tail / _tail_planes: the same three values for A/B; any setting computes the same bytes.
+    // Re-measured with the per-workgroup clocks of profiles/fwd_finish_clocks.txt: profiles/fwd_staffing_ab.txt)
+    auto knob_in = [](const char* key, int dflt, int lo, int hi) {
+      const int v = tuning(key, dflt);
+      return v < lo ? lo : (v > hi ? hi : v);
+    };
+    P.grab = knob_in("roi_align_fwd_grab", 0, 0, 64);   // (0: the launcher's choice)
+    if (P.grab == 0) P.grab = a.amax8 && !a.half_io ? 2 : 4;
     P.gbias = 0;
-    P.tail = 0;
-    P.tail_planes = 8;
+    P.tail = knob_in("roi_align_fwd_tail", 0, 0, 100);
+    P.tail_planes = knob_in("roi_align_fwd_tail_planes", 8, 1, 8);
+    // roi_align_fwd_staff: which virtual unit a workgroup starts on -- 0 where the midpoint of its share of the cost
+    // prefix falls, 1 whole workgroups per unit so that units end together after whole reservations (band_staffing)
+    P.staff = knob_in("roi_align_fwd_staff", kBandStaffDefault, 0, 1);
+    for (int l = 0; l < a.L.nlvl; ++l) {   // a level's reservation in channels, and reservations per unit
+      const int g = P.g[l] > 0 ? P.g[l] : 1;
+      P.gres[l] = (P.grab + g - 1) / g * g;
+      P.nres[l] = (a.C + P.gres[l] - 1) / P.gres[l];
+    }
     // roi_align_fwd_xcd: how the workgroups' shares of the cost prefix map to blocks (see band_xcd_slot and the
     // kernel's unit table).  Any value computes the same bytes.
     P.xcd = tuning("roi_align_fwd_xcd", kBandXcdDefault);
@@ -1568,9 +1628,11 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
 #undef SD_FWD_BAND
       char tail_note[96] = "";
       if (tail) snprintf(tail_note, sizeof(tail_note), " (tail tasks: %d coordinate table + %d backward plan)", ncoord, nbwd);
-      note_dispatch("sd::%s<%d> + sd::roi_align_fwd_band<%d,%s,%s>%s [roi_align_fwd_xcd = %d]",
+      note_dispatch("sd::%s<%d> + sd::roi_align_fwd_band<%d,%s,%s>%s [roi_align_fwd_xcd = %d] [roi_align_fwd_staff = %d] "
+                    "[reservations: grab %d, tail %d %% in pieces of %d planes]",
                     merged && !tail ? "roi_prep_merged_kernel" : "roi_fwd_prep_kernel",
-                    POOL, POOL, a.amax8 ? "true" : "false", a.half_io ? "true" : "false", tail_note, P.xcd);
+                    POOL, POOL, a.amax8 ? "true" : "false", a.half_io ? "true" : "false", tail_note, P.xcd, P.staff,
+                    P.grab, P.tail, P.tail_planes);
       SD_LAUNCH_CHECK();
       return SD_OK;
     }
@@ -1613,6 +1675,34 @@ int check_dims(int B, int C, int R, int ph, int pw) {
 }  // namespace sd
 
 using namespace sd;
+
+namespace sd {
+__global__ __launch_bounds__(kWave) void band_staffing_test_kernel(const int* n, const int* t, int nvu, int nwg, int setup, int* m) {
+  // the kernel's two register forms, and the form that walks memory beyond them
+  const bool used = nvu <= kWave ? band_staffing<BandStaffWave, 1>(n, t, nvu, nwg, setup, m)
+                  : nvu <= kBandMaxUnits ? band_staffing<BandStaffWave, kBandMaxUnits / kWave>(n, t, nvu, nwg, setup, m)
+                                         : band_staffing<BandStaffWave, 0>(n, t, nvu, nwg, setup, m);
+  if (!used)
+    for (int v = threadIdx.x; v < nvu; v += kWave) m[v] = 0;
+}
+}  // namespace sd
+
+extern "C" int sd_band_staffing_ref(const int* n, const int* t, int nvu, int nwg, int setup, int* m_out) {
+  SD_REQUIRE(nvu >= 0 && nwg >= 0, "negative count (nvu=%d nwg=%d)", nvu, nwg);
+  SD_REQUIRE((n && t && m_out) || nvu == 0, "null pointer");
+  if (!band_staffing<BandStaffSerial>(n, t, nvu, nwg, setup, m_out))
+    for (int v = 0; v < nvu; ++v) m_out[v] = 0;
+  return SD_OK;
+}
+
+extern "C" int sd_band_staffing_dev(const int* n, const int* t, int nvu, int nwg, int setup, int* m_out, void* stream) {
+  SD_REQUIRE(nvu >= 0 && nwg >= 0, "negative count (nvu=%d nwg=%d)", nvu, nwg);
+  SD_REQUIRE((n && t && m_out) || nvu == 0, "null pointer");
+  if (nvu == 0) return SD_OK;
+  hipLaunchKernelGGL(band_staffing_test_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, n, t, nvu, nwg, setup, m_out);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
 
 extern "C" int sd_roi_align_v2_fwd(const float* data, const float* rois, float* out,
                                    float* maxidx_x, float* maxidx_y, int B, int C, int H, int W,

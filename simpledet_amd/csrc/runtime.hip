@@ -37,6 +37,10 @@ Knob g_knobs[] = {
     {"roi_align_fwd_quad", 0, false},    // 1 (default): single-level float arg-max forward with four channel-last planes per workgroup when they fit (the C4 family); 0: the band kernel
     {"roi_align_plan_tail", 0, false},   // 1 (default): the band forward's pre-pass builds only what that kernel reads; the coordinate table and the backward's plan are tasks in the band kernel's tail; 0: all of it in the (merged) pre-pass launch
     {"roi_align_fwd_xcd", 0, false},     // band forward, which share of the cost prefix a block starts on: 0 linear in blockIdx; 1 XCD-contiguous (a unit's workgroups write through one L2); 2 the same, unit table interleaving the levels (default 1)
+    {"roi_align_fwd_staff", 0, false},   // band forward, which virtual unit a workgroup starts on: 0 where the midpoint of its share of the cost prefix falls; 1 whole workgroups per unit, chosen so that the units end together after whole reservations (band_staffing, roi_align_common.h)
+    {"roi_align_fwd_grab", 0, false},    // band forward: channels a workgroup reserves at a time, rounded up to whole fills (default 0: 2 for the fp32 packed arg-max forward, else 4)
+    {"roi_align_fwd_tail", 0, false},    // band forward: last per cent of a unit's channels handed out in smaller pieces (default 0)
+    {"roi_align_fwd_tail_planes", 0, false}, // band forward: planes of such a piece, 1..8 (default 8: whole fills)
     {"roi_align_bwd", 0, false},         // 2 (default) fused all-level kernel; 1 per-level LDS planes; 0 global atomics
     {"roi_align_bwd_flt4", 0, false},    // 1 (default): single-level float arg-max backward with four channel planes per workgroup when they fit
     {"roi_align_bwd_fx", 0, false},      // 1 (default): band sums in 32-bit fixed point (bit-reproducible); 0: fp32 compare-and-swap adds, hardware order

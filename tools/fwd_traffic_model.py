@@ -117,7 +117,10 @@ def xcd_slot(wg, nwg):
     return (wg % NXCD) * (nwg // NXCD) + wg // NXCD if nwg % NXCD == 0 else wg
 
 
-def model(rois, shapes, strides, C, P=7, xcd=0, reads="all", empty_cost=1):
+def virtual_units(rois, shapes, strides, C, P=7, xcd=0):
+    """the kernel's table of virtual units in table order: per entry the unit's lists (`unit`, with its planes per
+    fill `g` and its `level`), the first item and the items of the round, and the cost the prefix is built from;
+    also the number of units"""
     B, R = rois.shape[:2]
     plan = band_plan(shapes, C, R, P)
     level = fpn_level(rois, strides)
@@ -146,7 +149,8 @@ def model(rois, shapes, strides, C, P=7, xcd=0, reads="all", empty_cost=1):
                 left0 = np.where(cc[ri] >= 1, c0s[0][ri], 0)     # (items, P) columns of the RoI's bins
                 left1 = np.where(cc[ri] >= 2, c1s[0][ri], 0)
                 per_unit[(l, img * pl["nbands"] + b)] = dict(
-                    n=img * R + idx[ri], p=pi, rows=np.stack([lo0, hi0, lo1, hi1], 1), left0=left0, left1=left1, g=pl["g"])
+                    n=img * R + idx[ri], p=pi, rows=np.stack([lo0, hi0, lo1, hi1], 1), left0=left0, left1=left1, g=pl["g"],
+                    level=l)
     # ---- virtual units, cost prefix, start unit of every workgroup
     nper = [B * pl["nbands"] for pl in plan]
     vus = []
@@ -156,6 +160,12 @@ def model(rois, shapes, strides, C, P=7, xcd=0, reads="all", empty_cost=1):
         for r in range(-(-cnt // cap)):
             it = min(cap, cnt - r * cap)
             vus.append(dict(unit=u, first=r * cap, items=it, cost=SETUP_COST + (FILL_COST // u["g"] + PLANE_COST + it) * C))
+    return vus, len(per_unit)
+
+
+def model(rois, shapes, strides, C, P=7, xcd=0, reads="all", empty_cost=1):
+    vus, nunits = virtual_units(rois, shapes, strides, C, P, xcd)
+    ipp = WAVE // P
     start = np.concatenate([[0], np.cumsum([v["cost"] for v in vus])])
     wgs = [[] for _ in vus]
     for wg in range(NWG):
@@ -218,7 +228,7 @@ def model(rois, shapes, strides, C, P=7, xcd=0, reads="all", empty_cost=1):
     written = LINE * len(np.unique(np.concatenate(keys)))
     items = sum(v["items"] for v in vus)
     return dict(written_bytes=written, lds_active=lds_active, lds_conflict=lds_active - lds_min, items=items,
-                units=len(per_unit), virtual_units=len(vus), output_bytes=items * C * (4 * P + P),
+                units=nunits, virtual_units=len(vus), output_bytes=items * C * (4 * P + P),
                 lds_per_item_channel=lds_active / float(items * C))
 
 
