@@ -67,7 +67,8 @@ const char* sd_last_dispatch(void);
  * So were the sd_fcos_* entry points (FCOS targets and losses; sd_fcos_decode and sd_fcos_sigmoid, the test-time
  * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*, and
  * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head), and sd_reppoints_decode (the
- * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head).
+ * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head),
+ * and sd_scale_bias_act_* (the merged-BN affine and _contrib_BroadcastScale).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1383,6 +1384,51 @@ int sd_reppoints_decode(const float* const* cls_ptrs_host, const float* const* p
                         const float* moment_transfer, const int* H_host, const int* W_host, const int* stride_host,
                         const int* k_host, int L, int N, int C, int num_points, int transform, int input_logits,
                         float* cls_score, float* bbox_xyxy, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_BroadcastScale and the merged-BN affine  (mx.sym.contrib.BroadcastScale; what
+ *   utils/graph_optimize.py:merge_bn puts behind every Convolution of a fixbn backbone: BroadcastScale(gamma) ->
+ *   broadcast_add(beta) [-> elemwise add of the shortcut] -> relu), fp32 and fp16, NCHW.  Additions only: the ABI
+ *   version stays 12.
+ *   replaces BroadcastScaleOp::Forward / Backward  operator_cxx/contrib/broadcast_scale-inl.h:57-103 and the
+ *   upstream broadcast_add, elemwise add and relu nodes behind it (two to four launches each way, every one
+ *   reading and writing the whole activation) by one launch each way.
+ *   x / residual / y / dy / dx / dres (N,C,HxW) contiguous, gamma / beta / dbeta (C).
+ *   sd_scale_bias_act_fwd, per element of plane (n, c), every step rounded on its own (no fused multiply-add):
+ *       t = x * gamma[c];  u = t + beta[c] (beta NULL: u = t);  v = u + residual (residual NULL: v = u);
+ *       y = act ? (v > 0 ? v : 0) : v            mshadow_op::relu: NaN and -0.0 give +0.0
+ *     _contrib_BroadcastScale itself is beta = residual = NULL, act = 0.
+ *   sd_scale_bias_act_bwd (y is read only under act, x never):
+ *       g1 = act ? dy * (y > 0 ? 1 : 0) : dy     the product form: an infinite dy over a dead unit gives NaN
+ *       dres = g1 (NULL: skipped);  dx = g1 * gamma[c];  dbeta[c] = sum over n, hw of g1 (NULL: skipped; float32)
+ *     dx, dres and dbeta are written (kWriteTo).  There is no gradient for gamma: the reference's Backward writes
+ *     none (:83-103).
+ *   The *_f16 entry points take halves for every tensor but dbeta; each step above is the float operation on the
+ *   half operands rounded once to half (round to nearest even) before the next step -- mshadow's half_t and numpy's
+ *   float16 arithmetic -- and dbeta sums the half g1 values in float32.
+ *   y may be x or residual; dx and dres may each be dy: an element depends on its own index only.
+ *   Pointers need element alignment only.  16-byte stores from the first 16-byte boundary of y (dx), a capped grid
+ *   of 2048 workgroups striding the rest; an input (or dres) on another phase is moved by element accesses; the
+ *   bits do not depend on any pointer's phase.  dbeta is a two-stage sum in a fixed order through the workspace
+ *   (sd_scale_bias_act_workspace_bytes, monotone in N and C, no clearing needed; only a call with dbeta != NULL
+ *   looks at it): no floating-point atomics, two calls give equal bits.  sd_last_dispatch() names the kernels
+ *   taken, the grid and the tile count.  Kernels only, no host synchronisation, graph-capturable.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a negative size, act outside {0, 1}, a null
+ *   x / gamma / y (dy / gamma / dx), y == NULL with act = 1 in the backward, a pointer off its element alignment;
+ *   SD_ERR_WORKSPACE: dbeta != NULL with a NULL or too small workspace; SD_ERR_UNSUPPORTED: N*C*HxW > 2^31 - 1
+ *   elements.  N = 0, C = 0 or HxW = 0 succeed without a launch (no pointer is looked at, nothing is written;
+ *   sd_scale_bias_act_workspace_bytes returns its minimum for them and for invalid sizes).
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_scale_bias_act_workspace_bytes(int N, int C, long HxW);
+int sd_scale_bias_act_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
+                          int N, int C, long HxW, int act, void* stream);
+int sd_scale_bias_act_bwd(const float* dy, const float* y, const float* gamma, float* dx, float* dres, float* dbeta,
+                          int N, int C, long HxW, int act, void* workspace, size_t workspace_bytes, void* stream);
+int sd_scale_bias_act_fwd_f16(const void* x, const void* gamma, const void* beta, const void* residual, void* y,
+                              int N, int C, long HxW, int act, void* stream);
+int sd_scale_bias_act_bwd_f16(const void* dy, const void* y, const void* gamma, void* dx, void* dres, float* dbeta,
+                              int N, int C, long HxW, int act, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 #ifdef __cplusplus
 }

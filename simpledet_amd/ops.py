@@ -1096,6 +1096,154 @@ def group_norm(x, gamma, beta, num_group=32, eps=1e-5, return_stats=False):
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_BroadcastScale and the merged-BN affine  (operator_cxx/contrib/broadcast_scale-inl.h;
+# utils/graph_optimize.py:merge_bn -> BroadcastScale, broadcast_add, the shortcut's add, relu)
+# --------------------------------------------------------------------------------------------------
+_SBA_DTYPES = (torch.float32, torch.float16)
+
+
+def scale_bias_act_workspace_bytes(N, C, HxW):
+    return int(lib().cdll.sd_scale_bias_act_workspace_bytes(int(N), int(C), ctypes.c_long(int(HxW))))
+
+
+def _sba_act(act):
+    if act is None or act == 0:
+        return 0
+    if act == "relu" or act == 1:
+        return 1
+    raise ValueError("act must be None or 'relu', got %r" % (act,))
+
+
+def _sba_dims(x, gamma, name="data"):
+    if not isinstance(x, torch.Tensor) or x.dtype not in _SBA_DTYPES:
+        raise TypeError("%s must be a float32 or float16 torch.Tensor" % name)
+    _chk(x, name, dtype=x.dtype)
+    if x.dim() < 2:
+        raise ValueError("%s should be (batch, channel, ...), got shape %s" % (name, tuple(x.shape)))
+    N, C = int(x.shape[0]), int(x.shape[1])
+    gamma = _sba_param(gamma, "gamma", x, C)
+    return N, C, (x.numel() // (N * C) if N * C else 0), gamma
+
+
+def _sba_param(p, name, x, C):
+    """(C,) or (1,C,1,1) of x's dtype -> the flat view"""
+    _chk(p, name, dtype=x.dtype)
+    if p.numel() != C or (p.dim() != 1 and (p.dim() < 2 or p.shape[1] != C)):
+        raise ValueError("%s must have shape (%d,) or (1,%d,1,...), got %s" % (name, C, C, tuple(p.shape)))
+    return p.reshape(-1)
+
+
+def _sba_like(t, name, x):
+    _chk(t, name, dtype=x.dtype)
+    if tuple(t.shape) != tuple(x.shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(x.shape), tuple(t.shape)))
+    return t
+
+
+def scale_bias_act_forward(x, gamma, beta=None, residual=None, act=None, out=None):
+    """y = act((x * gamma[c] + beta[c]) + residual), every step rounded on its own: the nodes merge_bn leaves
+    behind a convolution, in one launch.  x (N,C,...) NCHW float32 or float16, gamma / beta (C,) or (1,C,1,1),
+    residual like x; beta and residual may be None; act None or "relu" (v > 0 ? v : 0).  out: the output buffer
+    (it may be x or residual: the in-place forms)."""
+    N, C, HxW, gamma = _sba_dims(x, gamma)
+    beta = None if beta is None else _sba_param(beta, "beta", x, C)
+    residual = None if residual is None else _sba_like(residual, "residual", x)
+    y = torch.empty_like(x) if out is None else _sba_like(out, "out", x)
+    fn = "sd_scale_bias_act_fwd" if x.dtype == torch.float32 else "sd_scale_bias_act_fwd_f16"
+    lib().call(fn, _p(x), _p(gamma), _p(beta), _p(residual), _p(y), N, C, ctypes.c_long(HxW), _sba_act(act),
+               _stream())
+    return y
+
+
+def scale_bias_act_backward(dy, y, gamma, act=None, dx=None, dres=None, dbeta=None, need_dres=False,
+                            need_dbeta=False, workspace=None):
+    """dy, y (the forward's output; read only under act, may be None without) -> dx, dres, dbeta.
+    g1 = dy * (y > 0) under act, dy otherwise; dx = g1 * gamma[c]; dres = g1 (need_dres or a dres buffer);
+    dbeta[c] = sum of g1, always float32 (need_dbeta or a dbeta buffer).  dx and dres may be dy.  There is no
+    gradient for gamma (the reference writes none)."""
+    N, C, HxW, gamma = _sba_dims(dy, gamma, "dy")
+    a = _sba_act(act)
+    if a:
+        if y is None:
+            raise ValueError("act='relu' needs y, the forward's output")
+        _sba_like(y, "y", dy)
+    else:
+        y = None
+    dx = torch.empty_like(dy) if dx is None else _sba_like(dx, "dx", dy)
+    if dres is None and need_dres:
+        dres = torch.empty_like(dy)
+    elif dres is not None:
+        _sba_like(dres, "dres", dy)
+    if dbeta is None and need_dbeta:
+        dbeta = torch.empty(C, device=dy.device, dtype=torch.float32)
+    elif dbeta is not None:
+        _chk(dbeta, "dbeta", ndim=1)
+        if dbeta.shape[0] != C:
+            raise ValueError("dbeta must have %d entries, got %d" % (C, dbeta.shape[0]))
+    ws = None
+    if dbeta is not None:
+        if N * HxW == 0:   # a sum over nothing (the entry point writes nothing on an empty problem)
+            dbeta.zero_()
+        ws = _workspace(dy.device, scale_bias_act_workspace_bytes(N, C, HxW), workspace)
+    fn = "sd_scale_bias_act_bwd" if dy.dtype == torch.float32 else "sd_scale_bias_act_bwd_f16"
+    lib().call(fn, _p(dy), _p(y), _p(gamma), _p(dx), _p(dres), _p(dbeta), N, C, ctypes.c_long(HxW), a, _p(ws),
+               ctypes.c_size_t(ws.numel() if ws is not None else 0), _stream())
+    return dx, dres, dbeta
+
+
+class ScaleBiasActFunction(torch.autograd.Function):
+    """y = ScaleBiasActFunction.apply(x, gamma, beta, residual, act); gamma's gradient is None."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, act):
+        y = scale_bias_act_forward(x, gamma, beta, residual, act)
+        ctx.act = _sba_act(act)
+        ctx.beta_shape = None if beta is None else beta.shape
+        ctx.beta_dtype = None if beta is None else beta.dtype
+        ctx.save_for_backward(gamma, y if ctx.act else None)   # x is never kept
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        gamma, y = ctx.saved_tensors
+        need_x, _, need_b, need_r, _ = ctx.needs_input_grad
+        need_b = need_b and ctx.beta_shape is not None
+        dx, dres, dbeta = scale_bias_act_backward(dy.contiguous(), y, gamma, ctx.act, need_dres=need_r,
+                                                  need_dbeta=need_b)
+        if dbeta is not None:
+            dbeta = dbeta.to(ctx.beta_dtype).reshape(ctx.beta_shape)
+        return dx if need_x else None, None, dbeta, dres, None
+
+
+def scale_bias_act(x, gamma, beta=None, residual=None, act=None):
+    """The fused merged-BN node with autograd: act((x * gamma + beta) + residual), gamma / beta per channel.
+    Gradients reach x, beta and residual; gamma's is None (BroadcastScaleOp::Backward writes none)."""
+    return ScaleBiasActFunction.apply(x, gamma, beta, residual, act)
+
+
+class BroadcastScaleFunction(torch.autograd.Function):
+    """y = BroadcastScaleFunction.apply(x, scaler); scaler's gradient is None."""
+
+    @staticmethod
+    def forward(ctx, x, scaler):
+        ctx.save_for_backward(scaler)
+        return scale_bias_act_forward(x, scaler)
+
+    @staticmethod
+    def backward(ctx, dy):
+        scaler, = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return scale_bias_act_backward(dy.contiguous(), None, scaler)[0], None
+
+
+def broadcast_scale(x, scaler):
+    """mx.sym.contrib.BroadcastScale(data, scaler) with autograd (broadcast_scale-inl.h:57-103):
+    x (N,C,...), scaler (C,) or (1,C,1,1) -> x * scaler over the channel axis."""
+    return BroadcastScaleFunction.apply(x, scaler)
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_SigmoidCrossEntropy and the fused Mask R-CNN mask loss  (operator_cxx/contrib/
 # sigmoid_cross_entropy{-inl.h,.cu}; models/maskrcnn/builder.py:278-313)
 # --------------------------------------------------------------------------------------------------
