@@ -68,7 +68,8 @@ const char* sd_last_dispatch(void);
  * decode): additions only.  So were sd_deform_psroi_pool_* and sd_fpn_deform_roi_pool_*, and
  * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head), and sd_reppoints_decode (the
  * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head),
- * and sd_scale_bias_act_* (the merged-BN affine and _contrib_BroadcastScale).
+ * and sd_scale_bias_act_* (the merged-BN affine and _contrib_BroadcastScale), and sd_rpn_loss_* / sd_rcnn_loss_*
+ * (the Faster / Mask R-CNN loss heads).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1429,6 +1430,61 @@ int sd_scale_bias_act_fwd_f16(const void* x, const void* gamma, const void* beta
 int sd_scale_bias_act_bwd_f16(const void* dy, const void* y, const void* gamma, void* dx, void* dres, float* dbeta,
                               int N, int C, long HxW, int act, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The Faster / Mask R-CNN loss heads (config/faster_r50v1_fpn_1x.py and its family), fp32: RpnHead.get_loss
+ *   (symbol/builder.py:163-206), FPNRpnHead.get_loss (models/FPN/builder.py:156-237) and BboxHead.get_loss
+ *   (symbol/builder.py:405-446) -- SoftmaxOutput, smooth_l1 behind MakeLoss, and the four numbers the AccWithIgnore
+ *   and L1 metrics (core/detection_metric.py:40-66,134-156) compute.  Additions only: the ABI version stays 12.
+ *   Upstream's SoftmaxOutput, smooth_l1 and MakeLoss are not vendored with the reference; DESIGN 4.23 is the
+ *   specification and says what rests on memory of upstream.
+ *   Softmax row: m = max x, e_c = expf(x_c - m), s = sum e_c, p_c = e_c / s (IEEE divide).
+ *   Class gradient: (p_c - [c == (int)label]) * (cls_grad_scale / (float)max(1, state.valid)); a row whose
+ *     (int)label equals ignore_label (RPN only) gets zeros; a label outside [0, C) hits no class.
+ *   Box part: v = delta - target; reg_loss = weight * smooth_l1(v, sigma) (a product: weight 0 against a NaN delta
+ *     gives NaN); d_delta = smooth_l1'(v) * (weight * reg_grad_scale).
+ *   State block, int32[4] on the device, written by every forward: {valid, correct, fg, reg_sum (the bits of a
+ *     float)} -- valid: labels != ignore (RPN), R (R-CNN); correct: valid rows whose first arg-max over p equals
+ *     (int)label; fg: valid rows with (int)label != 0; reg_sum: the sum of reg_loss in a fixed order (per-workgroup
+ *     partials in the workspace, then one workgroup), so two calls and a graph replay give equal bits.  The words
+ *     of a half that is not computed are 0.
+ *   sd_rpn_loss_fwd / _bwd: two HOST tables of L <= SD_MAX_FPN_LEVELS device pointers (the convention of
+ *     sd_fcos_loss_fwd; read during the call only) -- cls_logit[l] (N, 2A, H_l, W_l), bbox_delta[l]
+ *     (N, 4A, H_l, W_l) -- and hw_host, the L sizes H_l * W_l with sum HW; cls_label (N, A * HW), reg_target and
+ *     reg_weight (N, 4A, HW): sd_rpn_anchor_target's layout 1.  The label of level l, anchor a, position p is at
+ *     a * HW + off_l + p, its logits are channels a and A + a of the level.  prob (N, 2, A, HW) and reg_loss
+ *     (N, 4A, HW) are in the reference's concat layout; either may be NULL (not stored).  A NULL cls table
+ *     (delta table) leaves that half out altogether, its inputs are not looked at.  The forward is one launch and
+ *     one finishing workgroup; the backward one launch that writes every level's gradients, a half whose gradient
+ *     table is NULL left out.  L = 1 is the C4 head.
+ *   sd_rcnn_loss_fwd / _bwd: cls_logit (R, K), cls_label (R,), bbox_delta / bbox_target / bbox_weight (R, D); a wave
+ *     per row.  normalization = 'batch': the backward's normaliser is the state's valid = R.  NULL cls_logit
+ *     (bbox_delta) in the forward, NULL d_cls_logit (d_bbox_delta) in the backward leave the half out.
+ *   No memset, no host read, graph-capturable.  Pointers need element alignment only.
+ *   SD_ERR_INVALID_ARG: L outside 1..8, A < 1, K < 1, a negative size, sigma <= 0, a fractional ignore_label, a
+ *   null pointer of a computed half, neither half given; SD_ERR_UNSUPPORTED: K > 1024, more than 2^31 - 1
+ *   elements; SD_ERR_WORKSPACE: a NULL or too small workspace (forward only).  An empty problem succeeds without
+ *   a launch and writes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_rpn_loss_workspace_bytes(int N, int A, long HW);
+size_t sd_rcnn_loss_workspace_bytes(int R);
+int sd_rpn_loss_fwd(const float* const* cls_ptrs_host, const float* const* delta_ptrs_host, const long* hw_host,
+                    int L, const float* cls_label, const float* reg_target, const float* reg_weight, int N, int A,
+                    float ignore_label, float sigma, float* prob, float* reg_loss, int32_t* state, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int sd_rpn_loss_bwd(const float* const* cls_ptrs_host, const float* const* delta_ptrs_host, const long* hw_host,
+                    int L, const float* cls_label, const float* reg_target, const float* reg_weight, int N, int A,
+                    float ignore_label, float sigma, float cls_grad_scale, float reg_grad_scale,
+                    const int32_t* state, float* const* dcls_ptrs_host, float* const* ddelta_ptrs_host,
+                    void* stream);
+int sd_rcnn_loss_fwd(const float* cls_logit, const float* cls_label, const float* bbox_delta,
+                     const float* bbox_target, const float* bbox_weight, int R, int K, int D, float sigma,
+                     float* prob, float* reg_loss, int32_t* state, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int sd_rcnn_loss_bwd(const float* cls_logit, const float* cls_label, const float* bbox_delta,
+                     const float* bbox_target, const float* bbox_weight, int R, int K, int D, float sigma,
+                     float cls_grad_scale, float reg_grad_scale, const int32_t* state, float* d_cls_logit,
+                     float* d_bbox_delta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,4 +33,18 @@ __device__ __forceinline__ float smooth_l1_grad(float v, float bsq, float ibsq) 
   return bsq * v;
 }
 
+// SoftmaxOutput's row of two classes (the RPN heads): m = max, e_c = expf(x_c - m), s = e_0 + e_1, p_c = e_c / s
+__device__ __forceinline__ void softmax2(float x0, float x1, float& p0, float& p1) {
+  const float m = fmaxr(x0, x1);
+  const float e0 = expf(x0 - m), e1 = expf(x1 - m);
+  const float s = e0 + e1;
+  p0 = e0 / s;
+  p1 = e1 / s;
+}
+
+// SoftmaxOutput's gradient of one class: (p - [the label names this class]) * (grad_scale / norm)
+__device__ __forceinline__ float softmax_ce_grad(float p, bool hit, float scale) {
+  return (p - (hit ? 1.0f : 0.0f)) * scale;
+}
+
 }  // namespace sd

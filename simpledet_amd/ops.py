@@ -1623,6 +1623,303 @@ def emd_loss(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbo
 
 
 # --------------------------------------------------------------------------------------------------
+# The Faster / Mask R-CNN loss heads  (symbol/builder.py RpnHead / BboxHead .get_loss, models/FPN/builder.py
+# FPNRpnHead.get_loss; core/detection_metric.py AccWithIgnore / L1)
+# --------------------------------------------------------------------------------------------------
+RpnLossOut = collections.namedtuple("RpnLossOut", "prob reg_loss state")
+
+
+def rpn_loss_workspace_bytes(N, A, HW):
+    return int(lib().cdll.sd_rpn_loss_workspace_bytes(int(N), int(A), ctypes.c_long(int(HW))))
+
+
+def rcnn_loss_workspace_bytes(R):
+    return int(lib().cdll.sd_rcnn_loss_workspace_bytes(int(R)))
+
+
+def loss_state(device=None):
+    """A zeroed state block of the loss heads: int32[4] = {valid, correct, fg, the bits of the float reg_sum}."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    return torch.zeros(4, device=device, dtype=torch.int32)
+
+
+def _loss_metrics(state):
+    _chk(state, "state", dtype=torch.int32)
+    if state.numel() < 4:
+        raise ValueError("state must hold 4 int32 words")
+    s = state.reshape(-1)
+    return s[1:2], s[0:1], s[3:4].view(torch.float32), s[2:3]
+
+
+def rpn_loss_metrics(state):
+    """(acc numerator, acc denominator, L1 numerator, L1 denominator) of the config's RpnAcc / RpnL1 metrics
+    (AccWithIgnore and L1, core/detection_metric.py:40-66,134-156) as one-element device views of the state block:
+    correct, valid (int32), reg_sum (float32), fg (int32).  Nothing is copied and no big tensor is touched."""
+    return _loss_metrics(state)
+
+
+def rcnn_loss_metrics(state):
+    """The same four numbers for RcnnAcc / RcnnL1; they are the reference's as long as no label is -1 (the metric
+    drops such rows, normalization='batch' counts them: valid = R)."""
+    return _loss_metrics(state)
+
+
+def _loss_opts(normalization, want, smooth_alpha, out_grad):
+    if normalization != want:
+        raise NotImplementedError("normalization=%r is not built (this head is %r)" % (normalization, want))
+    if smooth_alpha:
+        raise NotImplementedError("smooth_alpha is not built")
+    if out_grad:
+        raise NotImplementedError("out_grad is not built")
+
+
+def _rpn_loss_levels(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight):
+    """(N, A, HW, hw table) of the level lists; either list may be None (that half is left out)"""
+    lead = cls_logits if cls_logits is not None else bbox_deltas
+    if lead is None or len(lead) == 0:
+        raise ValueError("cls_logits or bbox_deltas must hold one tensor per level")
+    L = len(lead)
+    if L > 8 or (cls_logits is not None and bbox_deltas is not None and len(cls_logits) != len(bbox_deltas)):
+        raise ValueError("cls_logits and bbox_deltas need one tensor per level each, 8 levels at the most")
+    per = 2 if cls_logits is not None else 4
+    _chk(lead[0], "level 0")
+    if lead[0].dim() < 3 or int(lead[0].shape[1]) % per:
+        raise ValueError("level tensors should be (N, %dA, H, W), got %s" % (per, tuple(lead[0].shape)))
+    N, A = int(lead[0].shape[0]), int(lead[0].shape[1]) // per
+    hws = []
+    for i in range(L):
+        hw = lead[i].numel() // (N * per * A) if N * A else 0
+        for lst, c, name in ((cls_logits, 2 * A, "cls_logits"), (bbox_deltas, 4 * A, "bbox_deltas")):
+            if lst is None:
+                continue
+            _chk(lst[i], "%s[%d]" % (name, i))
+            if lst[i].dim() < 3 or int(lst[i].shape[0]) != N or int(lst[i].shape[1]) != c or lst[i].numel() != N * c * hw:
+                raise ValueError("%s[%d] should be (%d, %d, H, W) with H * W = %d, got %s"
+                                 % (name, i, N, c, hw, tuple(lst[i].shape)))
+        hws.append(hw)
+    HW = sum(hws)
+    if cls_logits is not None:
+        _chk(cls_label, "cls_label")
+        if cls_label.numel() != N * A * HW:
+            raise ValueError("cls_label needs %d floats, got %d" % (N * A * HW, cls_label.numel()))
+    if bbox_deltas is not None:
+        for t, name in ((reg_target, "reg_target"), (reg_weight, "reg_weight")):
+            _chk(t, name)
+            if t.numel() != N * 4 * A * HW:
+                raise ValueError("%s needs %d floats, got %d" % (name, N * 4 * A * HW, t.numel()))
+    return N, A, HW, (ctypes.c_long * L)(*hws)
+
+
+def rpn_loss_forward(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight, *, ignore_label=-1.0, sigma=3.0,
+                     normalization="valid", smooth_alpha=0.0, out_grad=False, want_prob=True, want_reg_loss=True,
+                     prob=None, reg_loss=None, state=None, workspace=None):
+    """The RPN losses of RpnHead / FPNRpnHead.get_loss over per-level tensors, no reshape and no concat:
+    cls_logits[l] (N, 2A, H_l, W_l), bbox_deltas[l] (N, 4A, H_l, W_l), cls_label (N, A * HW), reg_target /
+    reg_weight (N, 4A, HW) -- rpn_anchor_target(layout=1)'s outputs.  Returns RpnLossOut: prob (N, 2, A, HW) =
+    SoftmaxOutput's output, reg_loss (N, 4A, HW) = weight * smooth_l1(delta - target, sigma), and the state block
+    (rpn_loss_metrics).  A list that is None leaves its half out; want_prob / want_reg_loss = False skips the store
+    of the big tensor but keeps the state."""
+    _loss_opts(normalization, "valid", smooth_alpha, out_grad)
+    N, A, HW, hws = _rpn_loss_levels(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight)
+    lead = cls_logits if cls_logits is not None else bbox_deltas
+    dev = lead[0].device
+    if cls_logits is not None and (want_prob or prob is not None):
+        prob = _fcos_out(prob, "prob", (N, 2, A, HW), dev)
+    else:
+        prob = None
+    if bbox_deltas is not None and (want_reg_loss or reg_loss is not None):
+        reg_loss = _fcos_out(reg_loss, "reg_loss", (N, 4 * A, HW), dev)
+    else:
+        reg_loss = None
+    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    if N * A * HW == 0:
+        state.zero_()
+        return RpnLossOut(prob, reg_loss, state)
+    ws = _workspace(dev, rpn_loss_workspace_bytes(N, A, HW), workspace)
+    lib().call("sd_rpn_loss_fwd", None if cls_logits is None else _parr(cls_logits),
+               None if bbox_deltas is None else _parr(bbox_deltas), hws, len(lead), _p(cls_label), _p(reg_target),
+               _p(reg_weight), N, A, float(ignore_label), float(sigma), _p(prob), _p(reg_loss), _p(state), _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return RpnLossOut(prob, reg_loss, state)
+
+
+def _grad_levels(given, like, name):
+    if given is None:
+        given = [torch.empty_like(t) for t in like]
+    if len(given) != len(like):
+        raise ValueError("%s needs one tensor per level" % name)
+    for g, t in zip(given, like):
+        _chk(g, name)
+        if g.numel() != t.numel():
+            raise ValueError("%s must have the sizes of the inputs" % name)
+    return list(given)
+
+
+def rpn_loss_backward(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight, state, *, cls_grad_scale=1.0,
+                      reg_grad_scale=1.0, ignore_label=-1.0, sigma=3.0, normalization="valid", smooth_alpha=0.0,
+                      out_grad=False, d_cls=None, d_delta=None):
+    """The gradients of rpn_loss_forward in ONE launch, written into per-level tensors of the inputs' shapes:
+    (d_cls list, d_delta list); the list of a half that is None is None.  The class gradient is
+    (p - onehot) * cls_grad_scale / max(1, state valid), zeros where the label is ignore_label; the box gradient
+    smooth_l1'(delta - target) * (weight * reg_grad_scale).  No top gradient enters."""
+    _loss_opts(normalization, "valid", smooth_alpha, out_grad)
+    N, A, HW, hws = _rpn_loss_levels(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight)
+    d_cls = None if cls_logits is None else _grad_levels(d_cls, cls_logits, "d_cls")
+    d_delta = None if bbox_deltas is None else _grad_levels(d_delta, bbox_deltas, "d_delta")
+    if N * A * HW == 0:
+        return d_cls, d_delta
+    if cls_logits is not None:
+        _chk(state, "state", dtype=torch.int32)
+    lead = cls_logits if cls_logits is not None else bbox_deltas
+    lib().call("sd_rpn_loss_bwd", None if cls_logits is None else _parr(cls_logits),
+               None if bbox_deltas is None else _parr(bbox_deltas), hws, len(lead), _p(cls_label), _p(reg_target),
+               _p(reg_weight), N, A, float(ignore_label), float(sigma), float(cls_grad_scale), float(reg_grad_scale),
+               _p(state), None if d_cls is None else _parr(d_cls), None if d_delta is None else _parr(d_delta),
+               _stream())
+    return d_cls, d_delta
+
+
+class RpnLossFunction(torch.autograd.Function):
+    """prob, reg_loss, state = RpnLossFunction.apply(cls_label, reg_target, reg_weight, cls_grad_scale,
+    reg_grad_scale, ignore_label, sigma, L, *cls_logits, *bbox_deltas).  Like the reference's SoftmaxOutput and
+    MakeLoss nodes the backward does not look at the incoming gradients."""
+
+    @staticmethod
+    def forward(ctx, cls_label, reg_target, reg_weight, cls_grad_scale, reg_grad_scale, ignore_label, sigma, L,
+                *levels):
+        if len(levels) != 2 * L:
+            raise ValueError("expected %d level tensors, got %d" % (2 * L, len(levels)))
+        levels = [t.contiguous() for t in levels]
+        fixed = [t.contiguous() for t in (cls_label, reg_target, reg_weight)]
+        ctx.kw = dict(ignore_label=ignore_label, sigma=sigma)
+        ctx.gs, ctx.L = (cls_grad_scale, reg_grad_scale), L
+        out = rpn_loss_forward(levels[:L], levels[L:], *fixed, **ctx.kw)
+        ctx.save_for_backward(out.state, *fixed, *levels)
+        ctx.mark_non_differentiable(out.state)
+        return out.prob, out.reg_loss, out.state
+
+    @staticmethod
+    def backward(ctx, _dprob, _dreg, _dstate):
+        state, label, target, weight = ctx.saved_tensors[:4]
+        levels, L = list(ctx.saved_tensors[4:]), ctx.L
+        d_cls, d_delta = rpn_loss_backward(levels[:L], levels[L:], label, target, weight, state,
+                                           cls_grad_scale=ctx.gs[0], reg_grad_scale=ctx.gs[1], **ctx.kw)
+        return (None,) * 8 + tuple(d_cls) + tuple(d_delta)
+
+
+def rpn_loss(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight, *, cls_grad_scale=1.0, reg_grad_scale=1.0,
+             ignore_label=-1.0, sigma=3.0):
+    """rpn_loss_forward with autograd over the two lists of level tensors: RpnLossOut(prob, reg_loss, state).
+    reg_grad_scale is the head's 1 / (batch_image * image_anchor); both scales carry fp16's 128."""
+    L = len(cls_logits)
+    return RpnLossOut(*RpnLossFunction.apply(cls_label, reg_target, reg_weight, float(cls_grad_scale),
+                                             float(reg_grad_scale), float(ignore_label), float(sigma), L,
+                                             *cls_logits, *bbox_deltas))
+
+
+def _rcnn_loss_args(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight):
+    R = K = D = None
+    if cls_logit is not None:
+        _chk(cls_logit, "cls_logit", ndim=2)
+        R, K = int(cls_logit.shape[0]), int(cls_logit.shape[1])
+        _chk(cls_label, "cls_label")
+        if cls_label.numel() != R:
+            raise ValueError("cls_label needs %d floats, got %d" % (R, cls_label.numel()))
+    if bbox_delta is not None:
+        _chk(bbox_delta, "bbox_delta", ndim=2)
+        if R is not None and int(bbox_delta.shape[0]) != R:
+            raise ValueError("bbox_delta should have %d rows, got %d" % (R, int(bbox_delta.shape[0])))
+        R, D = int(bbox_delta.shape[0]), int(bbox_delta.shape[1])
+        for t, name in ((bbox_target, "bbox_target"), (bbox_weight, "bbox_weight")):
+            _chk(t, name)
+            if t.numel() != R * D:
+                raise ValueError("%s needs %d floats, got %d" % (name, R * D, t.numel()))
+    if R is None:
+        raise ValueError("cls_logit or bbox_delta must be given")
+    return R, K if K is not None else 1, D if D is not None else 0
+
+
+def rcnn_loss_forward(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight, *, smooth_l1_scalar=1.0,
+                      normalization="batch", smooth_alpha=0.0, out_grad=False, want_prob=True, want_reg_loss=True,
+                      prob=None, reg_loss=None, state=None, workspace=None):
+    """The R-CNN losses of BboxHead.get_loss: cls_logit (R, K), cls_label (R,), bbox_delta / bbox_target /
+    bbox_weight (R, D) -> RpnLossOut(prob (R, K), reg_loss (R, D), state).  cls_logit or bbox_delta may be None
+    (that half is left out)."""
+    _loss_opts(normalization, "batch", smooth_alpha, out_grad)
+    R, K, D = _rcnn_loss_args(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight)
+    dev = (cls_logit if cls_logit is not None else bbox_delta).device
+    if cls_logit is not None and (want_prob or prob is not None):
+        prob = _fcos_out(prob, "prob", (R, K), dev)
+    else:
+        prob = None
+    if bbox_delta is not None and (want_reg_loss or reg_loss is not None):
+        reg_loss = _fcos_out(reg_loss, "reg_loss", (R, D), dev)
+    else:
+        reg_loss = None
+    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    if R == 0:
+        state.zero_()
+        return RpnLossOut(prob, reg_loss, state)
+    ws = _workspace(dev, rcnn_loss_workspace_bytes(R), workspace)
+    lib().call("sd_rcnn_loss_fwd", _p(cls_logit), _p(cls_label), _p(bbox_delta), _p(bbox_target), _p(bbox_weight),
+               R, K, D, float(smooth_l1_scalar), _p(prob), _p(reg_loss), _p(state), _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return RpnLossOut(prob, reg_loss, state)
+
+
+def rcnn_loss_backward(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight, state, *, cls_grad_scale=1.0,
+                       reg_grad_scale=1.0, smooth_l1_scalar=1.0, normalization="batch", smooth_alpha=0.0,
+                       out_grad=False, d_cls_logit=None, d_bbox_delta=None):
+    """The gradients of rcnn_loss_forward in one launch: (d_cls_logit, d_bbox_delta), None for a half that is None.
+    (p - onehot) * cls_grad_scale / R and smooth_l1'(delta - target) * (weight * reg_grad_scale)."""
+    _loss_opts(normalization, "batch", smooth_alpha, out_grad)
+    R, K, D = _rcnn_loss_args(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight)
+    dev = (cls_logit if cls_logit is not None else bbox_delta).device
+    if cls_logit is not None:
+        d_cls_logit = _ce_out(d_cls_logit, "d_cls_logit", R * K, dev, (R, K))
+        _chk(state, "state", dtype=torch.int32)
+    else:
+        d_cls_logit = None
+    d_bbox_delta = None if bbox_delta is None else _ce_out(d_bbox_delta, "d_bbox_delta", R * D, dev, (R, D))
+    if R == 0:
+        return d_cls_logit, d_bbox_delta
+    lib().call("sd_rcnn_loss_bwd", _p(cls_logit), _p(cls_label), _p(bbox_delta), _p(bbox_target), _p(bbox_weight),
+               R, K, D, float(smooth_l1_scalar), float(cls_grad_scale), float(reg_grad_scale), _p(state),
+               _p(d_cls_logit), _p(d_bbox_delta) if D else None, _stream())
+    return d_cls_logit, d_bbox_delta
+
+
+class RcnnLossFunction(torch.autograd.Function):
+    """prob, reg_loss, state = RcnnLossFunction.apply(cls_logit, bbox_delta, cls_label, bbox_target, bbox_weight,
+    cls_grad_scale, reg_grad_scale, smooth_l1_scalar); the backward does not look at the incoming gradients."""
+
+    @staticmethod
+    def forward(ctx, cls_logit, bbox_delta, cls_label, bbox_target, bbox_weight, cls_grad_scale, reg_grad_scale,
+                smooth_l1_scalar):
+        ts = [t.contiguous() for t in (cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight)]
+        ctx.gs, ctx.scalar = (float(cls_grad_scale), float(reg_grad_scale)), float(smooth_l1_scalar)
+        out = rcnn_loss_forward(*ts, smooth_l1_scalar=ctx.scalar)
+        ctx.save_for_backward(out.state, *ts)
+        ctx.mark_non_differentiable(out.state)
+        return out.prob, out.reg_loss, out.state
+
+    @staticmethod
+    def backward(ctx, _dprob, _dreg, _dstate):
+        state = ctx.saved_tensors[0]
+        gx, gd = rcnn_loss_backward(*ctx.saved_tensors[1:], state, cls_grad_scale=ctx.gs[0],
+                                    reg_grad_scale=ctx.gs[1], smooth_l1_scalar=ctx.scalar)
+        return (gx, gd) + (None,) * 6
+
+
+def rcnn_loss(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight, *, cls_grad_scale=1.0, reg_grad_scale=1.0,
+              smooth_l1_scalar=1.0):
+    """rcnn_loss_forward with autograd to cls_logit and bbox_delta: RpnLossOut(prob, reg_loss, state).
+    reg_grad_scale is the head's 1 / batch_roi; both scales carry fp16's 128 and the cascade's stage weight."""
+    return RpnLossOut(*RcnnLossFunction.apply(cls_logit, bbox_delta, cls_label, bbox_target, bbox_weight,
+                                              cls_grad_scale, reg_grad_scale, smooth_l1_scalar))
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_Quantization_int8  (operator_cxx/contrib/quantization_int8{-inl.h,.cu}; utils/graph_optimize.py)
 # --------------------------------------------------------------------------------------------------
 QUANT_GRAD_MODES = ("ste", "clip")
