@@ -1486,6 +1486,86 @@ int sd_rcnn_loss_bwd(const float* cls_logit, const float* cls_label, const float
                      float cls_grad_scale, float reg_grad_scale, const int32_t* state, float* d_cls_logit,
                      float* d_bbox_delta, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * _contrib_SyncBatchNorm  (mx.sym.contrib.SyncBatchNorm; every normalizer_factory(type="syncbn") site), fp32 and
+ *   fp16, NCHW.  Additions only: the ABI version stays 12.
+ *   replaces SyncBatchNorm::Forward / Backward  operator_cxx/contrib/sync_batch_norm-inl.h:246-535 (three to
+ *   five tensor passes, two device-to-host copies, a host barrier and a host-side add, two copies back, per layer
+ *   and direction: :325-351, :464-494) by two entry points per direction with the exchange of a (2, C) float32
+ *   block between them.  The exchange itself is the caller's (simpledet_amd/dist.py:all_gather_stats); with one
+ *   rank there is none.
+ *   x / y / dy / dx (N,C,HxW) contiguous (2-D data: HxW = 1); gamma / beta / mean / var / moving_* / dgamma / dbeta
+ *   (C) float32.  n = N * HxW, the same on each of the W ranks (SharedND::MeanReady divides by ndev, :146-158).
+ *   g = fix_gamma ? 1 : gamma[c].  Every float32 step is rounded on its own.
+ *   Training forward:
+ *     sd_sync_bn_stats      part (2,C): part[0,c] = the mean of the rank's n elements, part[1,c] = their biased
+ *                           variance about that mean.  x is read once.
+ *     sd_sync_bn_apply      parts (W,2,C) in rank order (W = 1: parts is part).  Per channel in double, ranks in
+ *                           order: m = (sum_r mean_r) / W;  v = (sum_r (var_r + (mean_r - m)^2)) / W;
+ *                           mean = (float)m, var = (float)v, both written (W = 1: the bits of part).  Then
+ *                           inv = 1.0f / sqrtf(var + eps);  y = (g * (x - mean)) * inv + beta[c]        (:354-357)
+ *   Inference forward, sd_sync_bn_infer_fwd (:359-363):
+ *       a = g / sqrtf(moving_var + eps);  b = beta - (g * moving_mean) / sqrtf(moving_var + eps);  y = a * x + b
+ *   Training backward:
+ *     sd_sync_bn_bwd_stats  bpart (2,C): bpart[0,c] = sum dy, bpart[1,c] = sum dy * (x - mean)           (:476-477)
+ *     sd_sync_bn_bwd_apply  bparts (W,2,C).  Per channel in double, ranks in order: SG = sum_r bpart_r[0],
+ *                           SP = sum_r bpart_r[1];  sg = (float)(SG / (W * n)), sp = (float)(SP / (W * n));
+ *                           inv = 1.0f / sqrtf(var + eps);  a = g * inv;  b = -(g * sp) * ((inv * inv) * inv);
+ *                           c = -(g * sg) * inv;  dx = (dy * a + b * (x - mean)) + c
+ *                           (:496-513 with its averaged sums and scale = 1 / n multiplied out).
+ *                           dbeta[c] = bparts[rank][0][c];  dgamma[c] = fix_gamma ? 0 : bparts[rank][1][c] * inv
+ *                           -- per rank, as the reference: the gradient all-reduce sums them.  NULL together: skipped.
+ *                           moving_mean / moving_var (NULL together: skipped) are updated HERE, in the backward, with
+ *                           the biased variance, as :471-472: moving = moving * momentum + stat * (1.0f - momentum).
+ *   Departures from the reference: (1) the variance is taken about the mean (its fp32 E[x^2] - mean^2, :333-334 and
+ *   :353, cancels when |mean| >> sigma); (2) y multiplies by inv where the reference divides per element; (3) dgamma
+ *   is (sum dy * (x - mean)) * inv where the reference sums dy * (x - mean) / sqrt(var + eps) (:503); (4) gamma is
+ *   never written (the reference's slope = 1.f under fix_gamma stores ones into the input, :320).  Not provided:
+ *   kAddTo, the backward under use_global_stats, gradients arriving on mean / var.
+ *   The *_f16 entry points take halves for x / y / dy / dx and compute in float32, rounding the result to half once:
+ *   the bits of cast -> the fp32 entry point -> cast.
+ *   Sums are defined on items of 8 (HxW % 8 == 0), 4 (HxW % 4 == 0) or 1 elements, whatever the element type and
+ *   the pointers; 16-byte accesses where the data pointers are 16-byte aligned, element accesses otherwise
+ *   (element alignment suffices; no bit depends on it).  A channel of more than 256 * 8 items (256 * 4 of 8) is
+ *   split over workgroups and its partials are merged in double in a fixed order; sd_last_dispatch() says
+ *   "(split)" then.  No floating-point atomics: two calls give equal bits.  The workspace
+ *   (sd_sync_bn_workspace_bytes, one size for every entry point, monotone in N and C) needs no clearing.  Kernels
+ *   only, no host read, graph-capturable; every grid depends on the shapes alone.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a negative size, W < 1, rank outside
+ *   0..W-1, dgamma / dbeta or moving_mean / moving_var given half, a null pointer, a pointer off its element
+ *   alignment; SD_ERR_WORKSPACE: a NULL or too small workspace; SD_ERR_UNSUPPORTED: N*C*HxW > 2^31 - 1.  N = 0,
+ *   C = 0 or HxW = 0 succeed without a launch (nothing is written; the query returns its minimum).
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_sync_bn_workspace_bytes(int N, int C, long HxW);
+int sd_sync_bn_stats(const float* x, float* part, int N, int C, long HxW, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int sd_sync_bn_apply(const float* x, const float* parts, int W, const float* gamma, const float* beta, float* y,
+                     float* mean, float* var, int N, int C, long HxW, float eps, int fix_gamma, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int sd_sync_bn_infer_fwd(const float* x, const float* gamma, const float* beta, const float* moving_mean,
+                         const float* moving_var, float* y, int N, int C, long HxW, float eps, int fix_gamma,
+                         void* stream);
+int sd_sync_bn_bwd_stats(const float* dy, const float* x, const float* mean, float* bpart, int N, int C, long HxW,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int sd_sync_bn_bwd_apply(const float* dy, const float* x, const float* mean, const float* var, const float* gamma,
+                         const float* bparts, int W, int rank, float* dx, float* dgamma, float* dbeta,
+                         float* moving_mean, float* moving_var, float momentum, int N, int C, long HxW, float eps,
+                         int fix_gamma, void* workspace, size_t workspace_bytes, void* stream);
+int sd_sync_bn_stats_f16(const void* x, float* part, int N, int C, long HxW, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int sd_sync_bn_apply_f16(const void* x, const float* parts, int W, const float* gamma, const float* beta, void* y,
+                         float* mean, float* var, int N, int C, long HxW, float eps, int fix_gamma, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int sd_sync_bn_infer_fwd_f16(const void* x, const float* gamma, const float* beta, const float* moving_mean,
+                             const float* moving_var, void* y, int N, int C, long HxW, float eps, int fix_gamma,
+                             void* stream);
+int sd_sync_bn_bwd_stats_f16(const void* dy, const void* x, const float* mean, float* bpart, int N, int C, long HxW,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int sd_sync_bn_bwd_apply_f16(const void* dy, const void* x, const float* mean, const float* var, const float* gamma,
+                             const float* bparts, int W, int rank, void* dx, float* dgamma, float* dbeta,
+                             float* moving_mean, float* moving_var, float momentum, int N, int C, long HxW, float eps,
+                             int fix_gamma, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

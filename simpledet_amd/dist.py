@@ -2,8 +2,11 @@
 
 Every op on the path is per image (RoIAlign batch index = roi / R, ProposalTarget and NMS loop over
 images, soft-NMS is per (image, class)), so images -- and at test time (image, class) problems --
-shard across ranks with NO data-path collective.  The only exchange of a training step is the
-gradient all-reduce, which the reference does with KVStore 'nccl' (detection_train.py:42-43,
+shard across ranks with no data-path collective -- with one exception: a graph normalised by
+_contrib_SyncBatchNorm exchanges a (2, C) float32 block of per-channel statistics per layer and
+direction (all_gather_stats below, between the two kernels of simpledet_amd/csrc/sync_bn.hip; the
+reference does it with a host barrier, sync_batch_norm-inl.h:325-351).  The other exchange of a training
+step is the gradient all-reduce, which the reference does with KVStore 'nccl' (detection_train.py:42-43,
 gradients pre-scaled by 1/num_device :266).  Here: torch.distributed, backend "nccl" (= RCCL over
 xGMI on MI355X) or "gloo" (CPU tests), gradients coalesced into a few large flat buckets (xGMI is
 point to point: ring all-reduce is per-link bound, so few large messages beat many small ones) and
@@ -226,6 +229,25 @@ class _null:
 
     def __exit__(self, *a):
         return False
+
+
+def all_gather_stats(part, group=None):
+    """The SyncBatchNorm exchange: every rank's `part` (2, C) float32 stacked in rank order -> (parts (W, 2, C),
+    rank), the same `parts` on every rank.  One all_gather_into_tensor on the backend's device (RCCL), a plain
+    all_gather on gloo (through the host where `part` lives on a device: gloo gathers CPU tensors only).  With
+    no process group initialised: (part[None], 0) and no collective."""
+    if not dist.is_initialized():
+        return part[None], 0
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    part = part.contiguous()
+    if dist.get_backend(group) == "gloo":
+        src = part.cpu()
+        rows = [torch.empty_like(src) for _ in range(world)]
+        dist.all_gather(rows, src, group=group)
+        return torch.stack(rows).to(part.device), rank
+    parts = torch.empty((world,) + tuple(part.shape), dtype=part.dtype, device=part.device)
+    dist.all_gather_into_tensor(parts, part, group=group)
+    return parts, rank
 
 
 def gather_ragged(local_list, world=None):

@@ -1244,6 +1244,190 @@ def broadcast_scale(x, scaler):
 
 
 # --------------------------------------------------------------------------------------------------
+# _contrib_SyncBatchNorm  (operator_cxx/contrib/sync_batch_norm-inl.h)
+# --------------------------------------------------------------------------------------------------
+def sync_bn_workspace_bytes(N, C, HxW):
+    return int(lib().cdll.sd_sync_bn_workspace_bytes(int(N), int(C), ctypes.c_long(int(HxW))))
+
+
+def _sbn_dims(x, name="data"):
+    if not isinstance(x, torch.Tensor) or x.dtype not in _SBA_DTYPES:
+        raise TypeError("%s must be a float32 or float16 torch.Tensor" % name)
+    if x.dim() < 2:
+        raise ValueError("%s should be (batch, channel, ...), got shape %s" % (name, tuple(x.shape)))
+    _chk(x, name, dtype=x.dtype)
+    N, C = int(x.shape[0]), int(x.shape[1])
+    return N, C, (x.numel() // (N * C) if N * C else 0)
+
+
+def _sbn_vec(t, name, C, lead=()):
+    """a float32 per-channel array of shape lead + (C,)"""
+    _chk(t, name)
+    if tuple(t.shape) != tuple(lead) + (C,):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(lead) + (C,), tuple(t.shape)))
+    return t
+
+
+def _sbn_parts(t, name, C):
+    _chk(t, name, ndim=3)
+    if t.shape[0] < 1 or tuple(t.shape[1:]) != (2, C):
+        raise ValueError("%s must have shape (W, 2, %d) with W >= 1, got %s" % (name, C, tuple(t.shape)))
+    return int(t.shape[0])
+
+
+def _sbn_new(x, shape):
+    return torch.empty(shape, device=x.device, dtype=torch.float32)
+
+
+def _sbn_fn(name, x):
+    return name if x.dtype == torch.float32 else name + "_f16"
+
+
+def sync_bn_stats(x, part=None, workspace=None):
+    """sd_sync_bn_stats: x (N,C,...) -> part (2,C) float32 = the rank's per-channel mean and biased variance about
+    that mean."""
+    N, C, HxW = _sbn_dims(x)
+    part = _sbn_new(x, (2, C)) if part is None else _sbn_vec(part, "part", C, (2,))
+    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
+    lib().call(_sbn_fn("sd_sync_bn_stats", x), _p(x), _p(part), N, C, ctypes.c_long(HxW), _p(ws),
+               ctypes.c_size_t(ws.numel()), _stream())
+    return part
+
+
+def sync_bn_apply(x, parts, gamma, beta, eps=1e-3, fix_gamma=True, y=None, mean=None, var=None, workspace=None):
+    """sd_sync_bn_apply: parts (W,2,C), the ranks' statistics in rank order -> y, mean (C), var (C)."""
+    N, C, HxW = _sbn_dims(x)
+    W = _sbn_parts(parts, "parts", C)
+    _sbn_vec(gamma, "gamma", C)
+    _sbn_vec(beta, "beta", C)
+    y = torch.empty_like(x) if y is None else _sba_like(y, "y", x)
+    mean = _sbn_new(x, (C,)) if mean is None else _sbn_vec(mean, "mean", C)
+    var = _sbn_new(x, (C,)) if var is None else _sbn_vec(var, "var", C)
+    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
+    lib().call(_sbn_fn("sd_sync_bn_apply", x), _p(x), _p(parts), W, _p(gamma), _p(beta), _p(y), _p(mean), _p(var), N,
+               C, ctypes.c_long(HxW), float(eps), int(bool(fix_gamma)), _p(ws), ctypes.c_size_t(ws.numel()),
+               _stream())
+    return y, mean, var
+
+
+def sync_bn_infer_forward(x, gamma, beta, moving_mean, moving_var, eps=1e-3, fix_gamma=True, y=None):
+    """sd_sync_bn_infer_fwd: the scale-shift of the moving statistics (sync_batch_norm-inl.h:359-363)."""
+    N, C, HxW = _sbn_dims(x)
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_var, "moving_var")):
+        _sbn_vec(t, name, C)
+    y = torch.empty_like(x) if y is None else _sba_like(y, "y", x)
+    lib().call(_sbn_fn("sd_sync_bn_infer_fwd", x), _p(x), _p(gamma), _p(beta), _p(moving_mean), _p(moving_var),
+               _p(y), N, C, ctypes.c_long(HxW), float(eps), int(bool(fix_gamma)), _stream())
+    return y
+
+
+def sync_bn_bwd_stats(dy, x, mean, bpart=None, workspace=None):
+    """sd_sync_bn_bwd_stats: -> bpart (2,C) float32 = sum dy and sum dy * (x - mean) over the rank's elements."""
+    N, C, HxW = _sbn_dims(x)
+    _sba_like(dy, "dy", x)
+    _sbn_vec(mean, "mean", C)
+    bpart = _sbn_new(x, (2, C)) if bpart is None else _sbn_vec(bpart, "bpart", C, (2,))
+    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
+    lib().call(_sbn_fn("sd_sync_bn_bwd_stats", x), _p(dy), _p(x), _p(mean), _p(bpart), N, C, ctypes.c_long(HxW),
+               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return bpart
+
+
+def sync_bn_bwd_apply(dy, x, mean, var, gamma, bparts, rank=0, eps=1e-3, fix_gamma=True, dx=None, dgamma=None,
+                      dbeta=None, param_grads=True, moving_mean=None, moving_var=None, momentum=0.9,
+                      workspace=None):
+    """sd_sync_bn_bwd_apply: bparts (W,2,C) in rank order -> dx, dgamma, dbeta (this rank's, written not
+    accumulated; None with param_grads=False).  moving_mean / moving_var, when given, are updated in place."""
+    N, C, HxW = _sbn_dims(x)
+    _sba_like(dy, "dy", x)
+    W = _sbn_parts(bparts, "bparts", C)
+    if not 0 <= int(rank) < W:
+        raise ValueError("rank %d is outside 0..%d" % (rank, W - 1))
+    for t, name in ((mean, "mean"), (var, "var"), (gamma, "gamma")):
+        _sbn_vec(t, name, C)
+    dx = torch.empty_like(x) if dx is None else _sba_like(dx, "dx", x)
+    if param_grads:
+        dgamma = _sbn_new(x, (C,)) if dgamma is None else _sbn_vec(dgamma, "dgamma", C)
+        dbeta = _sbn_new(x, (C,)) if dbeta is None else _sbn_vec(dbeta, "dbeta", C)
+        if N * HxW == 0:   # sums over nothing (the entry point writes nothing on an empty problem)
+            dgamma.zero_()
+            dbeta.zero_()
+    elif dgamma is not None or dbeta is not None:
+        raise ValueError("param_grads=False takes no dgamma / dbeta")
+    if (moving_mean is None) != (moving_var is None):
+        raise ValueError("moving_mean and moving_var go together")
+    if moving_mean is not None:
+        _sbn_vec(moving_mean, "moving_mean", C)
+        _sbn_vec(moving_var, "moving_var", C)
+    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
+    lib().call(_sbn_fn("sd_sync_bn_bwd_apply", x), _p(dy), _p(x), _p(mean), _p(var), _p(gamma), _p(bparts), W,
+               int(rank), _p(dx), _p(dgamma), _p(dbeta), _p(moving_mean), _p(moving_var), float(momentum), N, C,
+               ctypes.c_long(HxW), float(eps), int(bool(fix_gamma)), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    return dx, dgamma, dbeta
+
+
+def _sbn_gather(gather, part):
+    """gather(part) -> (parts (W,2,C) in rank order, rank); None: one rank, no collective"""
+    if gather is None:
+        return part[None], 0
+    parts, rank = gather(part)
+    return parts.contiguous(), int(rank)
+
+
+def sync_batch_norm_forward(x, gamma, beta, *, eps=1e-3, fix_gamma=True, gather=None, workspace=None):
+    """mx.sym.contrib.SyncBatchNorm training forward -> (y, mean, var): the statistics, the exchange
+    (gather: part -> (parts, rank), e.g. simpledet_amd.dist.all_gather_stats), the element rule.  With
+    gather=None the two launches follow back to back and can be captured in a graph."""
+    part = sync_bn_stats(x, workspace=workspace)
+    parts, _ = _sbn_gather(gather, part)
+    return sync_bn_apply(x, parts, gamma, beta, eps, fix_gamma, workspace=workspace)
+
+
+def sync_batch_norm_backward(dy, x, mean, var, gamma, *, eps=1e-3, fix_gamma=True, gather=None, param_grads=True,
+                             moving_mean=None, moving_var=None, momentum=0.9, workspace=None):
+    """mx.sym.contrib.SyncBatchNorm training backward -> (dx, dgamma, dbeta); dgamma / dbeta are this rank's
+    share.  moving_mean / moving_var are updated here, as in the reference (sync_batch_norm-inl.h:471-472)."""
+    bpart = sync_bn_bwd_stats(dy, x, mean, workspace=workspace)
+    bparts, rank = _sbn_gather(gather, bpart)
+    return sync_bn_bwd_apply(dy, x, mean, var, gamma, bparts, rank, eps, fix_gamma, param_grads=param_grads,
+                             moving_mean=moving_mean, moving_var=moving_var, momentum=momentum, workspace=workspace)
+
+
+class SyncBatchNormFunction(torch.autograd.Function):
+    """y, mean, var = SyncBatchNormFunction.apply(x, gamma, beta, eps, fix_gamma, gather, moving_mean, moving_var,
+    momentum); mean and var carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, fix_gamma, gather, moving_mean, moving_var, momentum):
+        y, mean, var = sync_batch_norm_forward(x, gamma, beta, eps=eps, fix_gamma=fix_gamma, gather=gather)
+        ctx.save_for_backward(x, gamma, mean, var)
+        ctx.conf = (float(eps), bool(fix_gamma), gather, moving_mean, moving_var, float(momentum))
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, _dmean, _dvar):
+        x, gamma, mean, var = ctx.saved_tensors
+        eps, fix_gamma, gather, mm, mv, momentum = ctx.conf
+        need = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dx, dgamma, dbeta = sync_batch_norm_backward(dy.contiguous(), x, mean, var, gamma, eps=eps,
+                                                     fix_gamma=fix_gamma, gather=gather, param_grads=need,
+                                                     moving_mean=mm, moving_var=mv, momentum=momentum)
+        return (dx if ctx.needs_input_grad[0] else None, dgamma if ctx.needs_input_grad[1] else None,
+                dbeta if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
+
+
+def sync_batch_norm(x, gamma, beta, eps=1e-3, fix_gamma=True, gather=None, moving_mean=None, moving_var=None,
+                    momentum=0.9, return_stats=False):
+    """mx.sym.contrib.SyncBatchNorm(data, gamma, beta, eps=1e-3, momentum=0.9, fix_gamma=True) in training, with
+    autograd: y, or (y, mean, var) with return_stats=True (output_mean_var).  moving_mean / moving_var, when given,
+    move in the backward."""
+    y, mean, var = SyncBatchNormFunction.apply(x, gamma, beta, float(eps), bool(fix_gamma), gather, moving_mean,
+                                               moving_var, float(momentum))
+    return (y, mean, var) if return_stats else y
+
+
+# --------------------------------------------------------------------------------------------------
 # _contrib_SigmoidCrossEntropy and the fused Mask R-CNN mask loss  (operator_cxx/contrib/
 # sigmoid_cross_entropy{-inl.h,.cu}; models/maskrcnn/builder.py:278-313)
 # --------------------------------------------------------------------------------------------------
