@@ -277,7 +277,14 @@ int sd_fpn_roi_align_bwd_packed_plan(const float* out_grad, const float* rois, c
 int sd_band_staffing_ref(const int* n, const int* t, int nvu, int nwg, int setup, int* m_out);
 int sd_band_staffing_dev(const int* n, const int* t, int nvu, int nwg, int setup, int* m_out, void* stream);
 /* assign_layer_fpn CustomOp (models/FPN/assign_layer_fpn.py:10-73): rois (n_rois,4) ->
- * rois_per_level (nlvl, n_rois, 4) zero-masked, and optionally level (n_rois) int32 (-1 = none) */
+ * rois_per_level (nlvl, n_rois, 4) zero-masked, and optionally level (n_rois) int32 (-1 = none).
+ * The rule is floor(level0 + log2(sqrt(area) / scale0 + 1e-6)) in float32.  A few arguments just under a power of
+ * two make level0 + log2 an exact tie, so that the last bit of log2 picks the level (default pyramid: z = 2 - 3 ulp
+ * and z = 0.5 - 1 / - 3 ulp).  There the spec is the correctly rounded log2f: the CPU oracle's (glibc) and the
+ * fixture's (tests/golden/fpn_assign_thresholds.npz, the reference's Python class on numpy); the reference's own
+ * CPU and CUDA log2 need not agree with each other at those arguments.  Strides are powers of two: with another
+ * stride the reference feeds a non-integer k_min through 2 ** t and astype('uint8'); no config does, and nothing
+ * here defines or tests it. */
 int sd_fpn_roi_assign(const float* rois, int n_rois, const int* strides_host, int nlvl,
                       float roi_canonical_scale, float roi_canonical_level, float* rois_per_level,
                       int32_t* level, void* stream);

@@ -13,7 +13,12 @@ where they lie):
   fpn_assign.npz   models/FPN/assign_layer_fpn.py:17-41  AssignLayerFPNOperator.forward, run with a
                    float32 numpy shim of the eight mx.nd functions it calls (sqrt, floor, log2,
                    clip, zeros_like, expand_dims, broadcast_like, where)
-  py_nms.npz       operator_py/nms.py:41-75   nms  (pure numpy hard NMS, suppress IoU > thresh)
+  fpn_assign_thresholds.npz   the same class and shim on the RoIs of tests/fpn_level_cases.py (the areas
+                   within 400 ulp of every level threshold of two pyramids, where the last bit of log2
+                   decides the level; numpy's float32 log2 is the correctly rounded one there, which
+                   tests/test_fpn_level_thresholds.py asserts).  Holds the parameters, the SHA-256 of the
+                   RoIs and one int8 level per RoI; written with fixed time stamps (same bytes every run)
+  py_nms.npz       operator_py/nms.py:41-75  nms  (pure numpy hard NMS, suppress IoU > thresh)
   cython_nms.npz   operator_py/cython/cpu_nms.pyx soft_nms / greedy_nms and bbox.pyx
                    bbox_overlaps_cython, compiled by oracle/build_ref.py into oracle/_ref
   top_proposal.npz models/FPN/get_top_proposal.py:10-67  GetTopProposalOperator.forward and
@@ -80,7 +85,8 @@ def make_anchors():
     np.savez_compressed(os.path.join(HERE, "anchors.npz"), **out)
 
 
-def make_fpn_assign():
+def _assign_layer_fpn():
+    """-> (the reference's AssignLayerFPNOperator over a float32 numpy shim of mx.nd, A: ndarray -> shim array)"""
     f32 = np.float32
 
     class _Arr(np.ndarray):
@@ -119,6 +125,12 @@ def make_fpn_assign():
     mx = types.SimpleNamespace(nd=_ND, operator=_Operator)
     env = load_defs(os.path.join(REF, "models", "FPN", "assign_layer_fpn.py"),
                     ["AssignLayerFPNOperator"], {"mx": mx, "np": np})
+    return env["AssignLayerFPNOperator"], A
+
+
+def make_fpn_assign():
+    f32 = np.float32
+    op_cls, A = _assign_layer_fpn()
     from simpledet_amd import synth
     rois = np.concatenate([synth.random_rois(s, 1, 256) for s in range(4)], 0)  # (4,256,4)
     # sizes straddling every level boundary exactly (sqrt(area) = 112, 224, 448 +- 1 px)
@@ -127,11 +139,54 @@ def make_fpn_assign():
         edge.append([10, 20, 10 + s - 1, 20 + s - 1])
     rois[0, :len(edge)] = np.asarray(edge, f32)
     strides = (4, 8, 16, 32)
-    op = env["AssignLayerFPNOperator"](strides, 224, 4)
+    op = op_cls(strides, 224, 4)
     outs = [np.zeros_like(rois) for _ in strides]
     op.forward(True, ["write"] * 4, [A(rois)], outs, [])
     np.savez_compressed(os.path.join(HERE, "fpn_assign.npz"), rois=rois,
                         strides=np.asarray(strides), per_level=np.stack(outs))
+
+
+def save_npz_reproducible(path, **arrays):
+    """np.savez_compressed with a fixed member time stamp: the same arrays give the same bytes"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def make_fpn_assign_thresholds():
+    """the reference's class on the RoIs of tests/fpn_level_cases.py (both pyramids: every level threshold +-400
+    ulp of area, then the special rows): one int8 level per RoI, read off the masked per-level outputs"""
+    from tests import fpn_level_cases as cases
+    op_cls, A = _assign_layer_fpn()
+    out = {"half": np.array(cases.HALF), "numpy_version": np.array(np.__version__)}
+    for name in sorted(cases.PYRAMIDS):
+        strides, scale0, lvl0, thr = cases.PYRAMIDS[name]
+        rois = cases.rois(name)
+        outs = [np.zeros_like(rois) for _ in strides]
+        with np.errstate(invalid="ignore"):
+            op_cls(strides, scale0, lvl0).forward(True, ["write"] * len(strides), [A(rois)], outs, [])
+        level = np.full(rois.shape[1], -1, np.int8)
+        taken = np.zeros(rois.shape[1], np.int32)
+        for l, o in enumerate(outs):
+            m = (o[0] != 0).any(1)                      # no RoI of the cases is all zeros
+            assert np.array_equal(o[0][m], rois[0][m])
+            level[m] = l
+            taken += m
+        assert taken.max() == 1
+        out[name + "/strides"] = np.asarray(strides, np.int32)
+        out[name + "/canonical"] = np.asarray([scale0, lvl0], np.int32)
+        out[name + "/thresholds"] = np.asarray(thr, np.float64)          # rows of (c, RoI width)
+        out[name + "/rois_sha256"] = np.array(cases.sha256(rois))
+        out[name + "/level"] = level
+        print(name, rois.shape[1], "RoIs, per level", [int((level == l).sum()) for l in range(-1, len(strides))])
+    save_npz_reproducible(os.path.join(HERE, "fpn_assign_thresholds.npz"), **out)
 
 
 def make_py_nms():
@@ -244,11 +299,13 @@ def make_top_proposal():
 
 
 if __name__ == "__main__":
-    make_top_proposal()
-    make_anchors()
-    make_fpn_assign()
-    make_py_nms()
-    make_cython_nms()
+    makers = (make_top_proposal, make_anchors, make_fpn_assign, make_fpn_assign_thresholds, make_py_nms,
+              make_cython_nms)
+    only = sys.argv[1:]          # e.g. `make_golden.py fpn_assign_thresholds`; none: all of them
+    assert all("make_" + n in [m.__name__ for m in makers] for n in only), only
+    for m in makers:
+        if not only or m.__name__[len("make_"):] in only:
+            m()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")

@@ -103,6 +103,16 @@ def test_oracle_fpn_assign_levels(oracle):
     # negative area -> sqrt = nan -> matches no stride (all outputs zero)
     _, lvl = oracle.fpn_roi_assign(np.array([[[50, 50, 10, 200]]], np.float32), STRIDES)
     assert lvl.tolist() == [[-1]]
+    # the last float32 area below each threshold and the first at or above it (tests/fpn_level_cases.py: one ulp of
+    # area apart; which is which comes from log2 in double, rounded once)
+    from . import fpn_level_cases as cases
+    for name in sorted(cases.PYRAMIDS):
+        strides = list(cases.PYRAMIDS[name][0])
+        for c, below, above, l_below, l_above in cases.boundary_rows(name):
+            assert l_above == l_below + 1
+            assert np.array_equal(cases.area_of(above).view(np.int32) - cases.area_of(below).view(np.int32), 1)
+            _, lvl = oracle.fpn_roi_assign(np.array([[below, above]], np.float32), strides)
+            assert lvl.tolist() == [[l_below, l_above]], "%s c=%g" % (name, c)
 
 
 def test_oracle_fpn_equals_assigned_level(oracle):
