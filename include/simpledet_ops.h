@@ -69,7 +69,7 @@ const char* sd_last_dispatch(void);
  * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head), and sd_reppoints_decode (the
  * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head),
  * and sd_scale_bias_act_* (the merged-BN affine and _contrib_BroadcastScale), and sd_rpn_loss_* / sd_rcnn_loss_*
- * (the Faster / Mask R-CNN loss heads).
+ * (the Faster / Mask R-CNN loss heads), and sd_fpn_topdown_* (the FPN top-down pathway).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1572,6 +1572,51 @@ int sd_sync_bn_bwd_apply_f16(const void* dy, const void* x, const float* mean, c
                              const float* bparts, int W, int rank, void* dx, float* dgamma, float* dbeta,
                              float* moving_mean, float* moving_var, float momentum, int N, int C, long HxW, float eps,
                              int fix_gamma, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The FPN top-down pathway  (UpSampling(scale=2, sample_type=nearest) -> slice_like(., lateral) -> add_n with two
+ *   inputs: the merge every FPN-style neck of the reference builds per level, models/FPN/builder.py:444-524,
+ *   models/retinanet/builder.py:498-543, models/FCOS/builder.py:338-386, ...), fp32 and fp16, NCHW.  Additions
+ *   only: the ABI version stays 12.  The three operators are upstream MXNet's; their arithmetic is restated here.
+ *   replaces three nodes forward and three backward per level, each reading and writing a whole tensor and keeping
+ *   the up-sampled and the clipped intermediate alive for the backward, by one launch each way for the whole chain.
+ *   Level 0 is the coarsest; 2 <= L <= 6.  hs / ws (host, L entries) are the levels' heights and widths; every
+ *   tensor of level l is (N,C,hs[l],ws[l]) contiguous.  lateral / out / g / d_lateral are HOST tables of L - 1 device
+ *   pointers, entry k for level k + 1.
+ *   sd_fpn_topdown_fwd:  out_l[n,c,y,x] = p_{l-1}[n,c,y>>1,x>>1] + lateral_l[n,c,y,x],  p_0 = top, p_l = out_l
+ *     -- the crop from the origin that slice_like makes; hs[l] <= 2 hs[l-1] and ws[l] <= 2 ws[l-1] are required, and
+ *     the crop may take more than one row or column.
+ *   sd_fpn_topdown_bwd (needs no forward tensor):  D_{L-1} = g_{L-1};  D_l = g_l + S_l (l = L-2 .. 1);  d_top = S_0;
+ *     d_lateral_l = D_l.  S_l[i,j] starts at +0.0f and adds D_{l+1}[2i+a, 2j+b] in the order (a,b) = (0,0), (0,1),
+ *     (1,0), (1,1), a position at or beyond hs[l+1], ws[l+1] left out (mshadow's pool<red::sum>, the backward of
+ *     upstream's UpSampling, under the crop); an element whose whole window is cropped away is written as +0.0.
+ *     g_l of an inner level may be NULL (that output had no other consumer: D_l = S_l, no add); g_{L-1} may not.
+ *     Any d_lateral_l, or the table itself, may be NULL and is then not stored; d_lateral_{L-1} is a plain copy of
+ *     g_{L-1} (a second launch), which only a caller that needs the buffer asks for.  Everything is written
+ *     (kWriteTo).
+ *   The *_f16 entry points take halves everywhere.  Forward: the float sum of the two halves rounded once to half,
+ *   and the next level reads the rounded half.  Backward: the window sum and the add of g_l are fp32 with ONE
+ *   rounding to half per stored element, and the next level reads the rounded half (cast -> fp32 level -> cast).
+ *   So an L-level call equals L - 1 chained two-level calls bit for bit: forward in both dtypes, backward in fp32
+ *   and, in fp16, wherever the inner g_l are NULL (a chain has to round S_l to half before an add outside it).
+ *   A workgroup owns a plane and a tile of level 0 with every finer element that maps onto it; inner levels pass
+ *   through LDS, so every tensor is read or written once.  Pointers need element alignment only: 16-byte stores
+ *   from the first 16-byte boundary of each output run, 16 / 8-byte loads where an input's phase allows and
+ *   element loads where not; no bit depends on any pointer's phase.  No workspace, no atomics, no host read,
+ *   graph-capturable; two calls give equal bits.  sd_last_dispatch() names the kernel, the grid and the tiling.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: L outside 2..6, a negative N or C, a null
+ *   hs / ws / top / table / required pointer, a dimension < 1, a level larger than twice the one before, a pointer
+ *   off its element alignment, an output range that overlaps an input range; SD_ERR_UNSUPPORTED: more than
+ *   2^31 - 1 elements in one tensor.  N = 0 or C = 0 succeed without a launch (no pointer but hs / ws is looked at).
+ * ---------------------------------------------------------------------------------------------- */
+int sd_fpn_topdown_fwd(const float* top, const float* const* lateral, float* const* out, int N, int C, const int* hs,
+                       const int* ws, int L, void* stream);
+int sd_fpn_topdown_bwd(const float* const* g, float* d_top, float* const* d_lateral, int N, int C, const int* hs,
+                       const int* ws, int L, void* stream);
+int sd_fpn_topdown_fwd_f16(const void* top, const void* const* lateral, void* const* out, int N, int C, const int* hs,
+                           const int* ws, int L, void* stream);
+int sd_fpn_topdown_bwd_f16(const void* const* g, void* d_top, void* const* d_lateral, int N, int C, const int* hs,
+                           const int* ws, int L, void* stream);
 
 #ifdef __cplusplus
 }

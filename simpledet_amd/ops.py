@@ -60,7 +60,7 @@ def _iarr(vals):
 
 
 def _parr(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1241,6 +1241,136 @@ def broadcast_scale(x, scaler):
     """mx.sym.contrib.BroadcastScale(data, scaler) with autograd (broadcast_scale-inl.h:57-103):
     x (N,C,...), scaler (C,) or (1,C,1,1) -> x * scaler over the channel axis."""
     return BroadcastScaleFunction.apply(x, scaler)
+
+
+# --------------------------------------------------------------------------------------------------
+# The FPN top-down pathway  (UpSampling(scale=2, nearest) -> slice_like -> add_n per level:
+# models/FPN/builder.py:444-524, models/retinanet/builder.py:498-543, ...)
+# --------------------------------------------------------------------------------------------------
+FPN_TOPDOWN_MAX_LEVELS = 6
+
+
+def _ftd_shapes(shapes):
+    """[(N,C,H_0,W_0), ..]: level 0 the coarsest, each level at most twice the one before -> N, C, hs, ws"""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    if not 2 <= len(shapes) <= FPN_TOPDOWN_MAX_LEVELS:
+        raise ValueError("fpn_topdown takes 2..%d levels (top and 1..%d laterals), got %d"
+                         % (FPN_TOPDOWN_MAX_LEVELS, FPN_TOPDOWN_MAX_LEVELS - 1, len(shapes)))
+    if any(len(s) != 4 for s in shapes):
+        raise ValueError("fpn_topdown: every level should be (N,C,H,W), got %s" % (shapes,))
+    N, C = shapes[0][:2]
+    for l, s in enumerate(shapes):
+        if s[:2] != (N, C):
+            raise ValueError("fpn_topdown: level %d has (N,C) = %s, level 0 %s" % (l, s[:2], (N, C)))
+        if l and (s[2] > 2 * shapes[l - 1][2] or s[3] > 2 * shapes[l - 1][3]):
+            raise ValueError("fpn_topdown: level %d (%d x %d) is larger than twice level %d (%d x %d)"
+                             % (l, s[2], s[3], l - 1, shapes[l - 1][2], shapes[l - 1][3]))
+    return N, C, [s[2] for s in shapes], [s[3] for s in shapes]
+
+
+def _ftd_tensor(t, name, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype not in _SBA_DTYPES:
+        raise TypeError("%s must be a float32 or float16 torch.Tensor" % name)
+    _chk(t, name, dtype=dtype or t.dtype, ndim=4)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def fpn_topdown_forward(top, laterals, outs=None):
+    """The whole top-down pathway in one launch: out_l = up2(p_{l-1})[:H_l, :W_l] + lateral_l with p_0 = top and
+    p_l = out_l, nearest neighbour (y >> 1, x >> 1), the crop from the origin that slice_like makes.
+    top (N,C,H_0,W_0), laterals [lateral_1 .. lateral_{L-1}] from coarse to fine, float32 or float16, each level at
+    most twice the one before.  outs: the output buffers (none may overlap an input).  Returns [out_1 .. out_{L-1}]."""
+    _ftd_tensor(top, "top", None)
+    laterals = list(laterals)
+    for k, t in enumerate(laterals):
+        _ftd_tensor(t, "laterals[%d]" % k, top.dtype)
+    shapes = [top.shape] + [t.shape for t in laterals]
+    N, C, hs, ws = _ftd_shapes(shapes)
+    if outs is None:
+        outs = [torch.empty_like(t) for t in laterals]
+    else:
+        outs = list(outs)
+        if len(outs) != len(laterals):
+            raise ValueError("outs must have %d entries, got %d" % (len(laterals), len(outs)))
+        for k, t in enumerate(outs):
+            _ftd_tensor(t, "outs[%d]" % k, top.dtype, laterals[k].shape)
+    fn = "sd_fpn_topdown_fwd" if top.dtype == torch.float32 else "sd_fpn_topdown_fwd_f16"
+    lib().call(fn, _p(top), _parr(laterals), _parr(outs), N, C, _iarr(hs), _iarr(ws), len(shapes), _stream())
+    return outs
+
+
+def fpn_topdown_backward(grads, shapes, d_top=None, d_laterals=None, want_finest=False):
+    """The pathway's backward in one launch, from the gradients alone (no forward tensor).
+    grads [g_1 .. g_{L-1}]: the gradients the consumers of out_l send; an inner one may be None (that output had no
+    other consumer), the finest may not.  shapes: the L input shapes, top first.
+    D_{L-1} = g_{L-1}; D_l = g_l + S_l; d_top = S_0; d_lateral_l = D_l, S_l the 2 x 2 window sums of D_{l+1} under
+    the crop.  d_top / d_laterals: output buffers; an entry of d_laterals may be None (a fresh buffer) or False (not
+    wanted: not stored, returned as None).  The finest lateral gradient is grads[-1] itself, no copy, unless
+    want_finest or a buffer asks for one.  Returns (d_top, [d_lateral_1 .. d_lateral_{L-1}])."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    N, C, hs, ws = _ftd_shapes(shapes)
+    L = len(shapes)
+    grads = list(grads)
+    if len(grads) != L - 1:
+        raise ValueError("grads must have %d entries, got %d" % (L - 1, len(grads)))
+    if grads[-1] is None:
+        raise ValueError("the gradient of the finest level must be given")
+    g_fin = _ftd_tensor(grads[-1], "grads[%d]" % (L - 2), None, shapes[-1])
+    for k, t in enumerate(grads[:-1]):
+        if t is not None:
+            _ftd_tensor(t, "grads[%d]" % k, g_fin.dtype, shapes[k + 1])
+    d_top = (torch.empty(shapes[0], device=g_fin.device, dtype=g_fin.dtype) if d_top is None
+             else _ftd_tensor(d_top, "d_top", g_fin.dtype, shapes[0]))
+    d_laterals = [None] * (L - 1) if d_laterals is None else list(d_laterals)
+    if len(d_laterals) != L - 1:
+        raise ValueError("d_laterals must have %d entries, got %d" % (L - 1, len(d_laterals)))
+    table, result = [], []
+    for k, t in enumerate(d_laterals):
+        finest = k == L - 2
+        if t is False:
+            buf = ret = None
+        elif t is None:
+            if finest and not want_finest:
+                buf, ret = None, g_fin
+            else:
+                buf = ret = torch.empty(shapes[k + 1], device=g_fin.device, dtype=g_fin.dtype)
+        else:
+            buf = ret = _ftd_tensor(t, "d_laterals[%d]" % k, g_fin.dtype, shapes[k + 1])
+        table.append(buf)
+        result.append(ret)
+    fn = "sd_fpn_topdown_bwd" if g_fin.dtype == torch.float32 else "sd_fpn_topdown_bwd_f16"
+    lib().call(fn, _parr(grads), _p(d_top), _parr(table), N, C, _iarr(hs), _iarr(ws), L, _stream())
+    return d_top, result
+
+
+class FpnTopdownFunction(torch.autograd.Function):
+    """outs = FpnTopdownFunction.apply(top, lateral_1, .., lateral_{L-1}); nothing is saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, top, *laterals):
+        ctx.shapes = [tuple(top.shape)] + [tuple(t.shape) for t in laterals]
+        ctx.set_materialize_grads(False)
+        return tuple(fpn_topdown_forward(top, laterals))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        grads = [None if g is None else g.contiguous() for g in grads]
+        if all(g is None for g in grads):
+            return (None,) * len(ctx.shapes)
+        if grads[-1] is None:     # the finest output went unused: its gradient is zero
+            ref = next(g for g in grads if g is not None)
+            grads[-1] = torch.zeros(ctx.shapes[-1], device=ref.device, dtype=ref.dtype)
+        need = ctx.needs_input_grad
+        d_top, d_lat = fpn_topdown_backward(grads, ctx.shapes, d_laterals=[None if n else False for n in need[1:]])
+        return (d_top if need[0] else None,) + tuple(d_lat)
+
+
+def fpn_topdown(top, laterals):
+    """The FPN top-down pathway with autograd: [out_1 .. out_{L-1}] of fpn_topdown_forward; the backward is
+    fpn_topdown_backward on the incoming gradients, and no forward tensor is kept alive for it."""
+    return list(FpnTopdownFunction.apply(top, *laterals))
 
 
 # --------------------------------------------------------------------------------------------------
