@@ -19,22 +19,18 @@ one operator: inputs (top, lateral_1 .. lateral_{L-1}), outputs (out_1 .. out_{L
      a wrapper installed before them.
 
 Like merged_bn it stays out of mxnet_plugin's tables: no flag of `mxnet_plugin.install()`, its own entry points, and
-only the plugin's helpers borrowed (the pointer path, the stream / sync state -- one state for all: the last
+only what _mx_adapter.py holds shared (the pointer path, the stream / sync state -- one state for all: the last
 install() call of any of the modules sets it).  `import mxnet` happens inside the entry points.
 
 Limits: scale 2 and nearest only, NCHW, kWriteTo only, and the sums' node names are not kept by
 rewrite() (the fused node has L-1 outputs under one name, `<last sum>_topdown`).
 """
-import ctypes
 import importlib
 import json
 
-from . import mxnet_plugin as _plugin
-from ._lib import lib
-from .merged_bn import ADD_OPS, _attrs, _constructor, _is_f16
-from .mxnet_plugin import REQ, _call, _iarr, _no_add, _ptr, _req, _require_write, _scratch, _sync, _wait
+from ._mx_adapter import ADD_OPS, REQ, _PREFIX, _attrs, _call, _constructor, _iarr, _is_f16, _mx, _no_add, _ptr, _req, \
+    _require_write, _scratch, _state, _sync, _table, _wait, prop_base, register_ops
 
-_PREFIX = "sd_"
 FPN_TOPDOWN = "fpn_topdown"
 MAX_LEVELS = 6
 _own = {"installed": False, "props": {}}
@@ -54,13 +50,9 @@ def _check_levels(shapes, what="fpn_topdown"):
     return shapes
 
 
-def _table(arrs):
-    return (ctypes.c_void_p * len(arrs))(*[None if a is None else _ptr(a).value for a in arrs])
-
-
 # ---------------------------------------------------------------------------------- operators ----
 def _build_ops(mx):
-    CustomOp, CustomOpProp = mx.operator.CustomOp, mx.operator.CustomOpProp
+    CustomOp, Prop = mx.operator.CustomOp, prop_base(mx)
 
     class FpnTopdown(CustomOp):
         def __init__(self, L, f16):
@@ -96,7 +88,7 @@ def _build_ops(mx):
                   shapes[0][1], _iarr([s[2] for s in shapes]), _iarr([s[3] for s in shapes]), self.L, None)
             _sync()
 
-    class FpnTopdownProp(CustomOpProp):
+    class FpnTopdownProp(Prop):
         def __init__(self, num_levels="4"):
             super().__init__(need_top_grad=True)
             self.L = int(num_levels)
@@ -133,23 +125,10 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def _mx(mx=None):
-    if mx is not None:
-        return mx
-    if _plugin._state.get("mx") is not None:
-        return _plugin._state["mx"]
-    import mxnet  # (lazy: MXNet is only needed here)
-    return mxnet
-
-
 def register(mx=None):
     """Register `sd_fpn_topdown`.  Returns {name: PropClass}."""
     mx = _mx(mx)
-    lib()  # fail loudly now if the HIP library is missing
-    _plugin._state["mx"] = mx
-    props = {name: mx.operator.register(_PREFIX + name)(prop) for name, prop in _build_ops(mx).items()}
-    _own["props"] = props
-    return props
+    return register_ops(mx, _build_ops(mx), _own)
 
 
 def install(mx=None, stream=None, sync=True):
@@ -157,7 +136,7 @@ def install(mx=None, stream=None, sync=True):
     no native constructor to alias: the node enters a graph through rewrite() or fpn_topdown()."""
     mx = _mx(mx)
     props = register(mx)
-    _plugin._state["stream"], _plugin._state["sync"] = stream, bool(sync)
+    _state["stream"], _state["sync"] = stream, bool(sync)
     _own["installed"] = True
     return props
 

@@ -15,35 +15,20 @@ add] -> relu: two to four element-wise nodes at full resolution.  This module
      `utils.graph_optimize.merge_bn` to it (the three scripts import the function at call time).
 
 It stays out of mxnet_plugin's tables on purpose: it is no flag of `mxnet_plugin.install()`, has its own entry
-points, and borrows only the plugin's helpers (the pointer path, the stream / sync state -- one state for both:
-the last install() call of either module sets it).  `import mxnet` happens inside the entry points.
+points, and shares only what _mx_adapter.py holds (the pointer path, the alias path, the stream / sync state -- one
+for both: the last install() call of either module sets it).  `import mxnet` happens inside the entry points.
 """
 import ctypes
 import importlib
 import json
 import logging
 
-from . import mxnet_plugin as _plugin
-from ._lib import lib
-from .mxnet_plugin import REQ, _call, _namespaces, _no_add, _ptr, _req, _require_write, _scratch, _sync, _wait
+from ._mx_adapter import ADD_OPS, REQ, _PREFIX, _attrs, _bool, _call, _constructor, _is_f16, _mx, _no_add, _numel, \
+    _ptr, _req, _require_write, _scratch, _state, _sync, _wait, _ws, drop_alias, prop_base, put_alias, register_ops
 
-_PREFIX = "sd_"
 BROADCAST_SCALE = "_contrib_BroadcastScale"
 SCALE_BIAS_ACT = "scale_bias_act"
 _own = {"installed": False, "props": {}}
-
-ADD_OPS = ("elemwise_add", "_Plus", "_plus", "add_n", "ElementWiseSum")
-
-
-def _bool(v):
-    return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
-
-
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= int(s)
-    return n
 
 
 def _param_shape(given, data, name):
@@ -57,14 +42,9 @@ def _param_shape(given, data, name):
     return given
 
 
-def _is_f16(dtypes):
-    import numpy as np
-    return bool(dtypes) and dtypes[0] is not None and np.dtype(dtypes[0]) == np.float16
-
-
 # ---------------------------------------------------------------------------------- operators ----
 def _build_ops(mx):
-    CustomOp, CustomOpProp = mx.operator.CustomOp, mx.operator.CustomOpProp
+    CustomOp, Prop = mx.operator.CustomOp, prop_base(mx)
 
     class ScaleBiasAct(CustomOp):
         """forward / backward of both nodes: BroadcastScale is the form without bias, residual and act"""
@@ -111,15 +91,14 @@ def _build_ops(mx):
                 esz = 2 if self.f16 else 4
                 dx = in_grad[0] if want_x else _scratch(dy, esz * _numel(dy.shape))
                 dres = in_grad[2 + self.with_bias] if want_r else None
-                dbeta = ws = None
-                wsb = 0
+                dbeta = ws = wsp = None
+                wsn = ctypes.c_size_t(0)
                 if want_b:
-                    wsb = int(lib().cdll.sd_scale_bias_act_workspace_bytes(N, C, ctypes.c_long(HxW)))
-                    ws = _scratch(dy, wsb)
+                    ws, wsp, wsn = _ws(dy, "sd_scale_bias_act_workspace_bytes", N, C, ctypes.c_long(HxW))
                     # the sum is float32; a half graph gets it rounded once into its beta gradient
                     dbeta = _scratch(dy, 4 * C) if self.f16 else in_grad[2]
                 _call("sd_scale_bias_act_bwd" + self.sfx, _ptr(dy), _ptr(y), _ptr(gamma), _ptr(dx), _ptr(dres),
-                      _ptr(dbeta), N, C, ctypes.c_long(HxW), self.act, _ptr(ws), ctypes.c_size_t(wsb), None)
+                      _ptr(dbeta), N, C, ctypes.c_long(HxW), self.act, wsp, wsn, None)
                 if want_b and self.f16:
                     _call("sd_cast_f32_to_f16", _ptr(dbeta), _ptr(in_grad[2]), ctypes.c_size_t(C), REQ["write"], None)
             _sync()
@@ -128,15 +107,12 @@ def _build_ops(mx):
                 # store to it); zeros are what a buffer that was cleared once holds, and what fixed_param implies
                 self.assign(in_grad[1], req[1], 0)
 
-    class _Base(CustomOpProp):
+    class _Base(Prop):
         what = ""
         act, with_bias, with_residual = 0, False, False
 
         def __init__(self):
             super().__init__(need_top_grad=True)
-
-        def list_outputs(self):
-            return ["output"]
 
         def infer_shape(self, in_shape):
             d = tuple(int(s) for s in in_shape[0])
@@ -168,9 +144,7 @@ def _build_ops(mx):
 
     class BroadcastScaleProp(_Base):
         what = "BroadcastScale"
-
-        def list_arguments(self):
-            return ["data", "scaler"]
+        ARGS = ("data", "scaler")
 
     class ScaleBiasActProp(_Base):
         what = "scale_bias_act"
@@ -190,23 +164,10 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def _mx(mx=None):
-    if mx is not None:
-        return mx
-    if _plugin._state.get("mx") is not None:
-        return _plugin._state["mx"]
-    import mxnet  # (lazy: MXNet is only needed here)
-    return mxnet
-
-
 def register(mx=None):
     """Register `sd__contrib_BroadcastScale` and `sd_scale_bias_act`.  Returns {name: PropClass}."""
     mx = _mx(mx)
-    lib()  # fail loudly now if the HIP library is missing
-    _plugin._state["mx"] = mx
-    props = {name: mx.operator.register(_PREFIX + name)(prop) for name, prop in _build_ops(mx).items()}
-    _own["props"] = props
-    return props
+    return register_ops(mx, _build_ops(mx), _own)
 
 
 def _broadcast_scale_ctor(mx, original):
@@ -234,12 +195,8 @@ def install(mx=None, stream=None, sync=True):
     `stream` / `sync` are the plugin's (mxnet_plugin.install has the ordering contract)."""
     mx = _mx(mx)
     props = register(mx)
-    _plugin._state["stream"], _plugin._state["sync"] = stream, bool(sync)
-    for target in _namespaces(mx, "contrib"):
-        cur = getattr(target, "BroadcastScale", None)
-        original = cur._sd_original if getattr(cur, "_sd_alias", False) else cur     # a second install() keeps the first
-        setattr(target, "BroadcastScale", _broadcast_scale_ctor(mx, original))
-        setattr(target, "_sd_reference_BroadcastScale", original)
+    _state["stream"], _state["sync"] = stream, bool(sync)
+    put_alias(mx, "contrib", "BroadcastScale", lambda original: _broadcast_scale_ctor(mx, original))
     _own["installed"] = True
     return props
 
@@ -247,16 +204,7 @@ def install(mx=None, stream=None, sync=True):
 def uninstall(mx=None):
     """Put the native `BroadcastScale` constructors back.  (MXNet has no way to drop a registered CustomOp: the two
     op types stay known, and nothing builds them any more.)"""
-    mx = _mx(mx)
-    for target in _namespaces(mx, "contrib"):
-        cur = getattr(target, "__dict__", {}).get("BroadcastScale")
-        if getattr(cur, "_sd_alias", False):
-            if cur._sd_original is None:
-                delattr(target, "BroadcastScale")
-            else:
-                setattr(target, "BroadcastScale", cur._sd_original)
-        if "_sd_reference_BroadcastScale" in getattr(target, "__dict__", {}):
-            delattr(target, "_sd_reference_BroadcastScale")
+    drop_alias(_mx(mx), "contrib", "BroadcastScale")
     _own["installed"] = False
 
 
@@ -275,10 +223,6 @@ def scale_bias_act(data, gamma, beta=None, residual=None, act=None, name=None, m
 
 
 # ------------------------------------------------------------------------------------ fusion ----
-def _attrs(node):
-    return node.get("attrs") or node.get("attr") or node.get("param") or {}
-
-
 def _is_relu(node):
     return node["op"] == "relu" or (node["op"] == "Activation" and _attrs(node).get("act_type") == "relu")
 
@@ -394,14 +338,6 @@ def _expand_bn(jgraph, merged, shape_of):
     out["heads"] = [entry(e) for e in jgraph.get("heads", [])]
     out["arg_nodes"] = [i for i, n in enumerate(new_nodes) if n["op"] == "null"]
     return out
-
-
-def _constructor(mx, op):
-    if op.startswith("_contrib_"):
-        return getattr(mx.sym.contrib, op[len("_contrib_"):])
-    if op.startswith("_"):
-        return getattr(mx.sym._internal, op)
-    return getattr(mx.sym, op)
 
 
 def _build_symbol(mx, jgraph, plans):

@@ -13,6 +13,11 @@ Python CustomOp `assign_layer_fpn`).  Its only run-time extension hook is `mx.op
   2. `install()` aliases the reference names to `mx.sym.Custom(op_type=...)` so symbol/builder.py,
      models/ and config/ run unchanged.
 
+Layout: the helpers every adapter module shares (state, pointer path, workspace, prop base, alias path) live in
+_mx_adapter.py and are re-exported here; the operators come one function per family (`_roi_pool_ops` ...
+`_crowdhuman_ops`, each returning {name: (PropClass, where)}), merged by `_build_ops`; then registration, and the
+opt-in features.
+
 `import mxnet` happens inside `register()`: importing this module never needs MXNet (it is absent
 in the build container; tests drive the adapter through a tiny stub of the mx.operator interface).
 
@@ -39,111 +44,19 @@ import ctypes
 import importlib
 import os
 import sys
-from ast import literal_eval
 
 from ._lib import SD_ERR_UNSUPPORTED, SimpleDetOpsError, lib
-
-REQ = {"null": 0, "write": 1, "inplace": 2, "add": 3}
-_PREFIX = "sd_"
-_state = {"mx": None, "registered": False, "rng": {}, "stream": None, "sync": True}
-
-
-# ------------------------------------------------------------------------------------ helpers ----
-def _ptr(nd):
-    """Raw device pointer of an mx.nd.NDArray (MXNDArrayGetData), or of any object that exposes
-    `data_ptr()` (the test stub wraps torch tensors)."""
-    if nd is None:
-        return None
-    if hasattr(nd, "data_ptr"):
-        return ctypes.c_void_p(nd.data_ptr())
-    mx = _state["mx"]
-    p = ctypes.c_void_p()
-    rc = mx.base._LIB.MXNDArrayGetData(nd.handle, ctypes.byref(p))
-    if rc != 0:
-        raise RuntimeError("MXNDArrayGetData failed")
-    return p
-
-
-def _wait(*arrs):
-    for a in arrs:
-        if a is not None and hasattr(a, "wait_to_read"):
-            a.wait_to_read()
-
-
-def _req(r):
-    return REQ[r] if isinstance(r, str) else int(r)
-
-
-def _stream():
-    """hipStream_t the adapter launches on: install(stream=...) -- None = the NULL stream, an int / c_void_p, or
-    a callable evaluated per call (e.g. `lambda: torch.cuda.current_stream().cuda_stream`)."""
-    st = _state.get("stream")
-    if callable(st):
-        st = st()
-    if st is None or isinstance(st, ctypes.c_void_p):
-        return st
-    return ctypes.c_void_p(int(st))
-
-
-def _call(name, *args):
-    """lib().call with the adapter's stream in place of a trailing None where the entry point's last parameter is
-    `void* stream` (read off include/simpledet_ops.h)."""
-    proto = lib().protos.get(name)
-    if args and args[-1] is None and proto and proto[1] and proto[1][-1][0] == "stream":
-        args = args[:-1] + (_stream(),)
-    return lib().call(name, *args)
-
-
-def _sync():
-    if _state.get("sync", True):
-        lib().call("sd_stream_synchronize", _stream())
-
-
-def _tuple(v, n=None, typ=float):
-    t = literal_eval(v) if isinstance(v, str) else v
-    if not isinstance(t, (tuple, list)):
-        t = (t,) * (n or 1)
-    return tuple(typ(x) for x in t)
-
-
-def _bool(v):
-    if isinstance(v, str):
-        return v.strip().lower() in ("1", "true", "yes")
-    return bool(v)
-
-
-def _iarr(vals):
-    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
-
-
-def _darr(vals):
-    return (ctypes.c_double * len(vals))(*[float(v) for v in vals])
-
-
-def _scratch(like, nbytes):
-    """Device scratch owned by MXNet (an NDArray on the same context)."""
-    mx = _state["mx"]
-    return mx.nd.empty(((int(nbytes) + 3) // 4,), ctx=like.context, dtype="float32")
-
-
-def _no_add(req):
-    """forward outputs: kWriteTo / kWriteInplace / kNullOp only.  The kernels overwrite their
-    outputs, so honouring kAddTo would need a temporary; no graph of the reference requests it
-    (MXNet uses kAddTo for gradients), hence it is refused loudly instead of silently ignored."""
-    for r in req:
-        if _req(r) == REQ["add"]:
-            raise RuntimeError("forward outputs do not support req='add' (kAddTo)")
-
-
-def _require_write(req, names):
-    for r, n in zip(req, names):
-        if _req(r) not in (REQ["write"], REQ["null"]):
-            raise RuntimeError("%s requires kWriteTo (got req=%s)" % (n, r))
+# the shared helpers, under the names this module has always had them (tests, tools and the satellites reach them here)
+from ._mx_adapter import (IN_DATA, OUT_DATA, OUT_GRAD, REQ, _PREFIX, _bool, _call, _darr, _iarr,  # noqa: F401
+                          _is_symbol, _namespaces, _no_add, _numel, _param_str, _ptr, _req, _require_write, _scratch,
+                          _state, _stream, _sync, _table, _tuple, _wait, _ws, alias_ctor, drop_alias, op_base,
+                          prop_base, put_alias, register_ops)
 
 
 # ---------------------------------------------------------------------------------- operators ----
-def _build_ops(mx):
-    CustomOp, CustomOpProp = mx.operator.CustomOp, mx.operator.CustomOpProp
+def _roi_pool_ops(mx):
+    """RoI pooling: ROIAlign_v2, ROIPooling_v1, assign_layer_fpn, the fused FPN extractor, the deformable pools"""
+    CustomOp, Op, Prop = mx.operator.CustomOp, op_base(mx), prop_base(mx)
     ops = {}
 
     # ---- _contrib_ROIAlign_v2: 2 inputs, 3 outputs (1 visible) ----
@@ -159,11 +72,10 @@ def _build_ops(mx):
             _wait(data, rois)
             B, C, H, W = data.shape
             R = rois.shape[1]
-            wsb = lib().cdll.sd_roi_align_v2_workspace_bytes(B, R)
-            ws = _scratch(data, wsb)
+            ws, wsp, wsn = _ws(data, "sd_roi_align_v2_workspace_bytes", B, R)
             _call("sd_roi_align_v2_fwd_ws", _ptr(data), _ptr(rois), _ptr(out_data[0]),
                        _ptr(out_data[1]), _ptr(out_data[2]), B, C, H, W, R, self.ph, self.pw,
-                       float(self.scale), _ptr(ws), ctypes.c_size_t(wsb), None)
+                       float(self.scale), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -176,7 +88,14 @@ def _build_ops(mx):
                        _req(req[1]), B, C, H, W, R, self.ph, self.pw, float(self.scale), None)
             _sync()
 
-    class ROIAlignV2Prop(CustomOpProp):
+    class ROIAlignV2Prop(Prop):
+        ARGS = ("data", "rois")
+        OUTS = ("output", "maxidx_x", "maxidx_y")
+        num_visible_outputs = 1
+        OP, OP_ARGS = ROIAlignV2, ("pooled_size", "spatial_scale")
+        # ROIAlignGrad_v2 (roi_align_v2-inl.h:206-218): dY, rois, maxidx_x, maxidx_y
+        DEPS = ((OUT_GRAD, 0), (IN_DATA, 1), (OUT_DATA, 1), (OUT_DATA, 2))
+
         def __init__(self, pooled_size, spatial_scale):
             super().__init__(need_top_grad=True)
             self.pooled_size = _tuple(pooled_size, 2, int)
@@ -186,14 +105,6 @@ def _build_ops(mx):
             if not 0.0 <= self.spatial_scale <= 1.0:
                 raise ValueError("spatial_scale must be in [0, 1]")
 
-        def list_arguments(self):
-            return ["data", "rois"]
-
-        def list_outputs(self):
-            return ["output", "maxidx_x", "maxidx_y"]
-
-        num_visible_outputs = 1
-
         def infer_shape(self, in_shape):
             d, b = in_shape
             if len(d) != 4:
@@ -202,13 +113,6 @@ def _build_ops(mx):
                 raise ValueError("bbox should be a 3D tensor of shape [batch, rois, 4]")
             o = (b[0], b[1], d[1], self.pooled_size[0], self.pooled_size[1])
             return [d, b], [o, o, o]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return ROIAlignV2(self.pooled_size, self.spatial_scale)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            # ROIAlignGrad_v2 (roi_align_v2-inl.h:206-218): dY, rois, maxidx_x, maxidx_y
-            return [out_grad[0], in_data[1], out_data[1], out_data[2]]
 
     ops["_contrib_ROIAlign_v2"] = (ROIAlignV2Prop, ("contrib", "ROIAlign_v2"))
 
@@ -238,19 +142,17 @@ def _build_ops(mx):
                        rois.shape[0], self.ph, self.pw, float(self.scale), None)
             _sync()
 
-    class ROIPoolingV1Prop(CustomOpProp):
+    class ROIPoolingV1Prop(Prop):
+        ARGS = ("data", "rois")
+        OUTS = ("output", "maxidx")
+        num_visible_outputs = 1
+        OP, OP_ARGS = ROIPoolingV1, ("pooled_size", "spatial_scale")
+        DEPS = ((OUT_GRAD, 0), (IN_DATA, 1), (OUT_DATA, 1))
+
         def __init__(self, pooled_size, spatial_scale):
             super().__init__(need_top_grad=True)
             self.pooled_size = _tuple(pooled_size, 2, int)
             self.spatial_scale = float(spatial_scale)
-
-        def list_arguments(self):
-            return ["data", "rois"]
-
-        def list_outputs(self):
-            return ["output", "maxidx"]
-
-        num_visible_outputs = 1
 
         def infer_shape(self, in_shape):
             d, b = in_shape
@@ -261,13 +163,447 @@ def _build_ops(mx):
             o = (b[0], d[1], self.pooled_size[0], self.pooled_size[1])
             return [d, b], [o, o]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return ROIPoolingV1(self.pooled_size, self.spatial_scale)
+    ops["ROIPooling_v1"] = (ROIPoolingV1Prop, (None, "ROIPooling_v1"))
+
+    # ---- assign_layer_fpn (models/FPN/assign_layer_fpn.py): 1 input, len(rcnn_stride) outputs ----
+    class AssignLayerFPN(CustomOp):
+        def __init__(self, strides, scale0, lvl0):
+            super().__init__()
+            self.strides, self.scale0, self.lvl0 = strides, scale0, lvl0
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            rois = in_data[0]
+            _wait(rois)
+            n = 1
+            for s in rois.shape[:-1]:
+                n *= int(s)
+            mx_ = _state["mx"]
+            per = mx_.nd.empty((len(self.strides),) + tuple(rois.shape), ctx=rois.context)
+            _call("sd_fpn_roi_assign", _ptr(rois), n, _iarr(self.strides), len(self.strides),
+                       float(self.scale0), float(self.lvl0), _ptr(per), None, None)
+            _sync()
+            for i in range(len(self.strides)):
+                self.assign(out_data[i], req[i], per[i])
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            self.assign(in_grad[0], req[0], 0)
+
+    class AssignLayerFPNProp(Prop):
+        ARGS = ("rois",)
+        OP, OP_ARGS = AssignLayerFPN, ("rcnn_stride", "roi_canonical_scale", "roi_canonical_level")
+
+        def __init__(self, rcnn_stride, roi_canonical_scale, roi_canonical_level):
+            super().__init__(need_top_grad=False)
+            self.rcnn_stride = _tuple(rcnn_stride, typ=int)
+            self.roi_canonical_scale = int(roi_canonical_scale)
+            self.roi_canonical_level = int(roi_canonical_level)
+
+        def list_outputs(self):
+            return ["rois_s{}".format(s) for s in self.rcnn_stride]
+
+        def infer_shape(self, in_shape):
+            return [in_shape[0]], [in_shape[0]] * len(self.rcnn_stride)
+
+    ops["assign_layer_fpn"] = (AssignLayerFPNProp, None)
+
+    def _fpn_packed(pooled):
+        return tuple(pooled) in ((7, 7), (14, 14))
+
+    # ---- fpn_roi_align: the whole FPNRoiAlign.get_roi_feature subgraph (models/FPN/builder.py:
+    #      567-610: assign -> per level ROIAlign_v2 -> add_n) as ONE op: feats..., rois -> output ----
+    class FPNRoIAlign(CustomOp):
+        """outputs: output, then the op's private forward -> backward state.  7x7 / 14x14 pooling:
+        one-byte arg-max + the per-RoI coordinate / tap table (sd_fpn_roi_align_fwd_packed);
+        other sizes: the reference's two fp32 arg-max planes."""
+
+        def __init__(self, strides, pooled, scale0, lvl0, fp16=False):
+            super().__init__()
+            self.strides, self.pooled, self.scale0, self.lvl0 = strides, pooled, scale0, lvl0
+            self.packed = _fpn_packed(pooled)
+            self.fp16 = fp16  # fp16 feature maps in, fp16 output out (packed pooling sizes only)
+
+        def _levels(self, feats):
+            ptrs = (ctypes.c_void_p * len(feats))(*[_ptr(f).value for f in feats])
+            return ptrs, _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            feats, rois = in_data[:-1], in_data[-1]
+            _wait(*in_data)
+            B, C = feats[0].shape[:2]
+            ptrs, Hs, Ws = self._levels(feats)
+            ws, wsp, wsn = _ws(rois, "sd_fpn_roi_align_workspace_bytes", B, rois.shape[1])
+            fn = "sd_fpn_roi_align_fwd_packed" if self.packed else "sd_fpn_roi_align_fwd"
+
+            def run(name, level_ptrs, out0):
+                _call(name, level_ptrs, Hs, Ws, _iarr(self.strides), len(feats), _ptr(rois),
+                           _ptr(out0), _ptr(out_data[1]), _ptr(out_data[2]), B, C, rois.shape[1],
+                           self.pooled[0], self.pooled[1], float(self.scale0), float(self.lvl0),
+                           wsp, wsn, None)
+
+            if not self.fp16 and self.packed and is_train:
+                # training: ONE rois-only pre-pass for the step -- the backward's band lists / tap
+                # tables are built here, into the op's fourth (private) output
+                plan = out_data[3]
+                _call(fn + "_plan", ptrs, Hs, Ws, _iarr(self.strides), len(feats), _ptr(rois),
+                           _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), B, C, rois.shape[1],
+                           self.pooled[0], self.pooled[1], float(self.scale0), float(self.lvl0),
+                           wsp, wsn, _ptr(plan), ctypes.c_size_t(plan.size), None)
+                self._planned = True
+            elif not self.fp16:
+                self._planned = False
+                run(fn, ptrs, out_data[0])
+            else:
+                try:
+                    run(fn + "_f16", ptrs, out_data[0])
+                except SimpleDetOpsError as e:
+                    if e.code != SD_ERR_UNSUPPORTED:
+                        raise
+                    # a shape the band-resident kernel does not take: the casts the reference graph
+                    # carries itself (models/FPN/builder.py:581-586, 607-608) around the fp32 op
+                    f32 = [_scratch(rois, f.size * 4).reshape(f.shape) for f in feats]
+                    for f, g in zip(feats, f32):
+                        _call("sd_cast_f16_to_f32", _ptr(f), _ptr(g), ctypes.c_size_t(f.size), None)
+                    o32 = _scratch(rois, out_data[0].size * 4).reshape(out_data[0].shape)
+                    p32 = (ctypes.c_void_p * len(f32))(*[_ptr(g).value for g in f32])
+                    run(fn, p32, o32)
+                    _call("sd_cast_f32_to_f16", _ptr(o32), _ptr(out_data[0]),
+                               ctypes.c_size_t(o32.size), REQ["write"], None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            feats, rois = in_data[:-1], in_data[-1]
+            _wait(out_grad[0], rois, *out_data[1:])
+            rq = {_req(r) for r in req[:-1]}
+            if len(rq) != 1:
+                raise RuntimeError("fpn_roi_align: all feature gradients must share one req")
+            B, C = feats[0].shape[:2]
+            req_data = rq.pop()
+            og, grads16 = out_grad[0], None
+            if self.fp16 and self.packed:
+                # the backward kernel's fp16-I/O instance: the graph's to_fp32 / to_fp16 casts
+                # (models/FPN/builder.py:581-586, 607-608) happen inside the kernel
+                ptrs16, Hs16, Ws16 = self._levels(in_grad[:-1])
+                ws, wsp, wsn = _ws(rois, "sd_fpn_roi_align_bwd_workspace_bytes", Hs16, Ws16, len(feats), B,
+                                         rois.shape[1])
+                try:
+                    _call("sd_fpn_roi_align_bwd_packed_f16", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
+                               _ptr(out_data[2]), ptrs16, Hs16, Ws16, _iarr(self.strides), len(feats), req_data,
+                               B, C, rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
+                               float(self.lvl0), wsp, wsn, None)
+                    _sync()
+                    self.assign(in_grad[-1], req[-1], 0)
+                    return
+                except SimpleDetOpsError as e:
+                    if e.code != SD_ERR_UNSUPPORTED:
+                        raise
+            if self.fp16:
+                # the sums are formed by the fp32 kernel: the graph's to_fp32 / to_fp16 casts
+                # (models/FPN/builder.py:581-586, 607-608) happen here, at the op boundary
+                og = _scratch(rois, out_grad[0].size * 4).reshape(out_grad[0].shape)
+                _call("sd_cast_f16_to_f32", _ptr(out_grad[0]), _ptr(og), ctypes.c_size_t(out_grad[0].size), None)
+                grads16 = in_grad[:-1]
+                in_grad = [_scratch(rois, g.size * 4).reshape(g.shape) for g in grads16] + [in_grad[-1]]
+                rq = {REQ["write"]}
+            else:
+                rq = {req_data}
+            ptrs, Hs, Ws = self._levels(in_grad[:-1])
+            out_grad = [og]
+            if self.packed and not self.fp16 and getattr(self, "_planned", False):
+                plan = out_data[3]   # lists / tap tables left by this op's forward
+                _call("sd_fpn_roi_align_bwd_packed_plan", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
+                           _ptr(out_data[2]), ptrs, Hs, Ws, _iarr(self.strides), len(feats), rq.pop(), B, C,
+                           rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
+                           float(self.lvl0), _ptr(plan), ctypes.c_size_t(plan.size), None)
+            elif self.packed:  # with the workspace the per-band RoI lists are built once, not per channel
+                ws, wsp, wsn = _ws(rois, "sd_fpn_roi_align_bwd_workspace_bytes", Hs, Ws, len(feats), B, rois.shape[1])
+                _call("sd_fpn_roi_align_bwd_packed_ws", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
+                           _ptr(out_data[2]), ptrs, Hs, Ws, _iarr(self.strides), len(feats), rq.pop(), B, C,
+                           rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
+                           float(self.lvl0), wsp, wsn, None)
+            else:
+                _call("sd_fpn_roi_align_bwd", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
+                           _ptr(out_data[2]), ptrs, Hs, Ws, _iarr(self.strides), len(feats), rq.pop(), B, C,
+                           rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
+                           float(self.lvl0), None)
+            if self.fp16:
+                for g32, g16 in zip(in_grad[:-1], grads16):
+                    _call("sd_cast_f32_to_f16", _ptr(g32), _ptr(g16), ctypes.c_size_t(g16.size), req_data, None)
+            _sync()
+            self.assign(in_grad[-1], req[-1], 0)
+
+    class FPNRoIAlignProp(Prop):
+        num_visible_outputs = 1
+        OP, OP_ARGS = FPNRoIAlign, ("rcnn_stride", "pooled_size", "scale0", "lvl0", "fp16")
+
+        def __init__(self, rcnn_stride, pooled_size="(7, 7)", roi_canonical_scale="224",
+                     roi_canonical_level="4", fp16="False"):
+            super().__init__(need_top_grad=True)
+            self.rcnn_stride = _tuple(rcnn_stride, typ=int)
+            self.pooled_size = _tuple(pooled_size, 2, int)
+            self.scale0, self.lvl0 = float(roi_canonical_scale), float(roi_canonical_level)
+            self.packed = _fpn_packed(self.pooled_size)
+            self.fp16 = _bool(fp16)
+            if self.fp16 and not self.packed:
+                raise ValueError("fpn_roi_align: fp16 I/O is provided for 7x7 and 14x14 pooling")
+
+        def list_arguments(self):
+            return ["data_s{}".format(s) for s in self.rcnn_stride] + ["rois"]
+
+        def list_outputs(self):
+            # packed: output, then private forward -> backward state (arg-max codes, coordinate table,
+            # the backward's band lists / tap tables built by the forward's pre-pass)
+            return ["output", "argmax", "coords", "plan"] if self.packed else ["output", "maxidx_x", "maxidx_y"]
+
+        def infer_shape(self, in_shape):
+            feats, b = in_shape[:-1], in_shape[-1]
+            if len(b) != 3 or b[2] != 4:
+                raise ValueError("bbox should be a 3D tensor of shape [batch, rois, 4]")
+            o = (b[0], b[1], feats[0][1], self.pooled_size[0], self.pooled_size[1])
+            if self.packed:
+                stride = int(lib().cdll.sd_fpn_roi_align_argmax_stride(*self.pooled_size))
+                pb = int(lib().cdll.sd_fpn_roi_align_plan_bytes(_iarr([f[2] for f in feats]),
+                                                                _iarr([f[3] for f in feats]), len(feats),
+                                                                int(b[0]), int(b[1])))
+                return in_shape, [o, (b[0], b[1], feats[0][1], stride),
+                                  (b[0], b[1], 9 * (self.pooled_size[0] + self.pooled_size[1])),
+                                  ((pb + 15) // 16 * 16,)]
+            return in_shape, [o, o, o]
+
+        def infer_type(self, in_type):
+            import numpy as np
+            f32 = np.float32
+            if self.fp16:  # feature maps fp16, rois fp32 -> output fp16; the state keeps its types
+                return [np.float16] * (len(in_type) - 1) + [f32], [np.float16, np.uint8, f32, np.uint8], []
+            if self.packed:
+                return in_type, [f32, np.uint8, f32, np.uint8], []
+            return in_type, [f32, f32, f32], []
 
         def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [out_grad[0], in_data[1], out_data[1]]
+            return [out_grad[0], in_data[-1]] + list(out_data[1:])
 
-    ops["ROIPooling_v1"] = (ROIPoolingV1Prop, (None, "ROIPooling_v1"))
+    ops["fpn_roi_align"] = (FPNRoIAlignProp, None)
+
+    def _dpsroi_supported(ncls, pooled, samples):
+        """the set forward AND backward take: the library's predicate, not a copy of its limits"""
+        if min(ncls, pooled, samples) < 1 or max(ncls, pooled, samples) > 4096:
+            return False
+        return bool(lib().cdll.sd_deform_psroi_pool_supported(int(ncls), int(pooled), int(samples)))
+
+    # ---- _contrib_DeformablePSROIPooling (upstream MXNet; models/TSD/poolings.py:87-100, 151-164):
+    #      data, rois[, trans] -> output, top_count (1 visible) ----
+    class DeformablePSROIPooling(Op):
+        def _tail(self, data, rois, trans):
+            g = self.g
+            B, C, H, W = data.shape
+            ncls = 1 if g["no_trans"] else trans.shape[1] // 2
+            return (B, C, H, W, rois.shape[0], ncls, float(g["spatial_scale"]), g["output_dim"], g["group_size"],
+                    g["pooled_size"], g["part_size"], g["sample_per_part"], float(g["trans_std"]), int(g["no_trans"]),
+                    None)
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            data, rois = in_data[:2]
+            trans = None if self.g["no_trans"] else in_data[2]
+            _wait(*in_data)
+            _call("sd_deform_psroi_pool_fwd", _ptr(data), _ptr(rois), _ptr(trans), _ptr(out_data[0]),
+                  _ptr(out_data[1]), *self._tail(data, rois, trans))
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            data, rois = in_data[:2]
+            no_trans = self.g["no_trans"]
+            trans = None if no_trans else in_data[2]
+            _wait(out_grad[0], out_data[1], *in_data)
+            _call("sd_deform_psroi_pool_bwd", _ptr(out_grad[0]), _ptr(data), _ptr(rois), _ptr(trans),
+                  _ptr(out_data[1]), _ptr(in_grad[0]), _ptr(in_grad[1]), None if no_trans else _ptr(in_grad[2]),
+                  _req(req[0]), _req(req[1]), REQ["null"] if no_trans else _req(req[2]),
+                  *self._tail(data, rois, trans))
+            _sync()
+
+    class DeformablePSROIPoolingProp(Prop):
+        OUTS = ("output", "top_count")
+        num_visible_outputs = 1
+        OP = DeformablePSROIPooling
+        PARAMS = ("spatial_scale", "output_dim", "group_size", "pooled_size", "part_size", "sample_per_part",
+                  "trans_std", "no_trans")
+
+        def __init__(self, spatial_scale, output_dim, group_size, pooled_size, part_size="0", sample_per_part="1",
+                     trans_std="0.0", no_trans="False"):
+            super().__init__(need_top_grad=True)
+            params = dict(spatial_scale=spatial_scale, output_dim=output_dim, group_size=group_size,
+                          pooled_size=pooled_size, part_size=part_size, sample_per_part=sample_per_part,
+                          trans_std=trans_std, no_trans=no_trans)
+            why = self.sd_supports({k: str(v) for k, v in params.items()})
+            if why:
+                raise ValueError("DeformablePSROIPooling: " + why)
+            self.g = dict(spatial_scale=float(spatial_scale), output_dim=int(output_dim), group_size=int(group_size),
+                          pooled_size=int(pooled_size), part_size=int(part_size), sample_per_part=int(sample_per_part),
+                          trans_std=float(trans_std), no_trans=_bool(no_trans))
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls back to
+            the native constructor)."""
+            for k in params:
+                if k not in cls.PARAMS:
+                    return "parameter %r is not one this operator takes" % k
+            try:
+                float(params["spatial_scale"])
+                float(params.get("trans_std", "0.0"))
+                od, G, P = int(params["output_dim"]), int(params["group_size"]), int(params["pooled_size"])
+                part, S = int(params.get("part_size", "0")), int(params.get("sample_per_part", "1"))
+            except Exception as e:
+                return "missing or unparsable parameter (%s)" % e
+            if od < 1 or G < 1 or P < 1 or S < 1 or part < 0:
+                return "output_dim, group_size, pooled_size, sample_per_part must be >= 1 and part_size >= 0"
+            # the library's own predicate, here for ONE class: the class count is known only from the offsets' shape
+            # (infer_shape asks again with it, and can only raise by then)
+            if not _dpsroi_supported(1, P, S):
+                return ("pooled_size %d with sample_per_part %d: the RoI's tap table and the backward's sums do not "
+                        "fit in LDS (sd_deform_psroi_pool_supported)" % (P, S))
+            return ""
+
+        def list_arguments(self):
+            return ["data", "rois"] if self.g["no_trans"] else ["data", "rois", "trans"]
+
+        def infer_shape(self, in_shape):
+            g = self.g
+            d, b = in_shape[:2]
+            if len(d) != 4:
+                raise ValueError("data should be a 4D tensor")
+            if len(b) != 2 or b[1] != 5:
+                raise ValueError("bbox should be a 2D tensor of shape [batch, 5]")
+            if d[1] != g["output_dim"] * g["group_size"] ** 2:
+                raise ValueError("data has %d channels, output_dim * group_size^2 = %d"
+                                 % (d[1], g["output_dim"] * g["group_size"] ** 2))
+            if not g["no_trans"]:
+                t = in_shape[2]
+                part = g["part_size"] or g["pooled_size"]
+                if len(t) != 4 or t[0] != b[0] or t[1] % 2 or t[1] < 2 or tuple(t[2:]) != (part, part):
+                    raise ValueError("trans should have shape (rois, 2 * num_classes, %d, %d)" % (part, part))
+                if g["output_dim"] % (t[1] // 2):
+                    raise ValueError("output_dim is not a multiple of num_classes")
+                if not _dpsroi_supported(t[1] // 2, g["pooled_size"], g["sample_per_part"]):
+                    raise ValueError("DeformablePSROIPooling: %d classes with pooled_size %d and sample_per_part %d do "
+                                     "not fit the kernels' LDS (sd_deform_psroi_pool_supported)"
+                                     % (t[1] // 2, g["pooled_size"], g["sample_per_part"]))
+            o = (b[0], g["output_dim"], g["pooled_size"], g["pooled_size"])
+            return list(in_shape), [o, o]
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [out_grad[0]] + list(in_data) + [out_data[1]]
+
+    ops["_contrib_DeformablePSROIPooling"] = (DeformablePSROIPoolingProp, ("contrib", "DeformablePSROIPooling"))
+
+    # ---- fpn_deform_roi_pool: the whole FPNRoIAlign_DeltaC / DeltaR.get_roi_feature subgraph
+    #      (models/TSD/poolings.py:51-174: fpn_roi_assign_offset -> per level DeformablePSROIPooling on masked
+    #      rois / offsets -> add_n) as ONE op: feats..., rois (B,R,4), trans (B*R,2,P,P) | (B*R,2) -> output ----
+    class FPNDeformRoIPool(Op):
+        def _levels(self, feats):
+            ptrs = (ctypes.c_void_p * len(feats))(*[_ptr(f).value for f in feats])
+            return ptrs, _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
+
+        def _tail(self, feats, rois, trans):
+            g = self.g
+            B, C = feats[0].shape[:2]
+            return (B, C, rois.shape[1], g["pooled_size"], g["pooled_size"] if len(trans.shape) == 4 else 1,
+                    g["sample_per_part"], float(g["trans_std"]), float(g["scale0"]), float(g["lvl0"]), None)
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            feats, rois, trans = in_data[:-2], in_data[-2], in_data[-1]
+            _wait(*in_data)
+            ptrs, Hs, Ws = self._levels(feats)
+            _call("sd_fpn_deform_roi_pool_fwd", ptrs, Hs, Ws, _iarr(self.g["stride"]), len(feats), _ptr(rois),
+                  _ptr(trans), _ptr(out_data[0]), _ptr(out_data[1]), *self._tail(feats, rois, trans))
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            feats, rois, trans = in_data[:-2], in_data[-2], in_data[-1]
+            _wait(out_grad[0], out_data[1], *in_data)
+            rq = {_req(r) for r in req[:-2]}
+            if len(rq) != 1:
+                raise RuntimeError("fpn_deform_roi_pool: all feature gradients must share one req")
+            ptrs, Hs, Ws = self._levels(feats)
+            dptrs = self._levels(in_grad[:-2])[0]
+            _call("sd_fpn_deform_roi_pool_bwd", _ptr(out_grad[0]), ptrs, dptrs, Hs, Ws, _iarr(self.g["stride"]),
+                  len(feats), _ptr(rois), _ptr(trans), _ptr(out_data[1]), _ptr(in_grad[-1]), rq.pop(),
+                  _req(req[-1]), *self._tail(feats, rois, trans))
+            _sync()
+            self.assign(in_grad[-2], req[-2], 0)
+
+    class FPNDeformRoIPoolProp(Prop):
+        OUTS = ("output", "top_count")
+        num_visible_outputs = 1
+        OP = FPNDeformRoIPool
+
+        def __init__(self, rcnn_stride, pooled_size="7", sample_per_part="4", trans_std="0.1",
+                     roi_canonical_scale="224", roi_canonical_level="4"):
+            super().__init__(need_top_grad=True)
+            self.g = dict(stride=_tuple(rcnn_stride, typ=int), pooled_size=int(pooled_size),
+                          sample_per_part=int(sample_per_part), trans_std=float(trans_std),
+                          scale0=float(roi_canonical_scale), lvl0=float(roi_canonical_level))
+            g = self.g
+            if not 1 <= len(g["stride"]) <= 5:
+                raise ValueError("fpn_deform_roi_pool: 1 to 5 levels, got %d" % len(g["stride"]))
+            if not _dpsroi_supported(1, g["pooled_size"], g["sample_per_part"]):
+                raise ValueError("fpn_deform_roi_pool: pooled_size %d with sample_per_part %d does not fit the kernels' "
+                                 "LDS (sd_deform_psroi_pool_supported)" % (g["pooled_size"], g["sample_per_part"]))
+
+        def list_arguments(self):
+            return ["data_s{}".format(s) for s in self.g["stride"]] + ["rois", "trans"]
+
+        def infer_shape(self, in_shape):
+            feats, b, t = in_shape[:-2], in_shape[-2], in_shape[-1]
+            P = self.g["pooled_size"]
+            if len(feats) != len(self.g["stride"]):
+                raise ValueError("one feature map per stride expected")
+            if len(b) != 3 or b[2] != 4:
+                raise ValueError("bbox should be a 3D tensor of shape [batch, rois, 4]")
+            n = b[0] * b[1]
+            if tuple(t) not in ((n, 2, P, P), (n, 2)):
+                raise ValueError("trans should have shape (%d, 2, %d, %d) or (%d, 2), got %s" % (n, P, P, n, tuple(t)))
+            for f in feats:
+                if len(f) != 4 or tuple(f[:2]) != (b[0], feats[0][1]):
+                    raise ValueError("every level should be (batch, C, H, W)")
+            return list(in_shape), [(n, feats[0][1], P, P), (n, len(feats), P, P)]
+
+        def declare_backward_dependency(self, out_grad, in_data, out_data):
+            return [out_grad[0]] + list(in_data) + [out_data[1]]
+
+    ops["fpn_deform_roi_pool"] = (FPNDeformRoIPoolProp, None)
+    return ops
+
+
+def _target_ops(mx):
+    """ProposalTarget, ProposalTarget_v2, ProposalMaskTarget"""
+    CustomOp, Prop = mx.operator.CustomOp, prop_base(mx)
+    ops = {}
+
+    def target_param(p):
+        """the C ABI's ProposalTargetParam from a prop's parsed parameters"""
+        from .ops import ProposalTargetParam
+        cp = ProposalTargetParam()
+        cp.num_classes, cp.batch_images, cp.image_rois = p["num_classes"], p["batch_images"], p["image_rois"]
+        cp.fg_fraction, cp.fg_thresh = p["fg_fraction"], p["fg_thresh"]
+        cp.bg_thresh_hi, cp.bg_thresh_lo = p["bg_thresh_hi"], p["bg_thresh_lo"]
+        cp.proposal_without_gt, cp.class_agnostic = int(p["proposal_without_gt"]), int(p["class_agnostic"])
+        for i in range(4):
+            cp.bbox_mean[i], cp.bbox_std[i], cp.bbox_weight[i] = (p["bbox_mean"][i], p["bbox_std"][i],
+                                                                   p["bbox_weight"][i])
+        return cp
+
+    def rand_state(context):
+        """libc's global rand() state of a process that never called srand (seed 1): one stream per device,
+        shared by every ProposalTarget / ProposalMaskTarget node like the libc global is"""
+        key = str(context)
+        if key not in _state["rng"]:
+            host = (ctypes.c_int32 * 33)()
+            _call("sd_glibc_srand_host", ctypes.c_uint32(1), host)
+            _state["rng"][key] = _state["mx"].nd.array(list(host), ctx=context, dtype="int32")
+        return _state["rng"][key]
 
     # ---- ProposalTarget: 2 inputs, 5 outputs (4 visible unless output_iou) ----
     class ProposalTarget(CustomOp):
@@ -277,7 +613,6 @@ def _build_ops(mx):
 
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
-            from .ops import ProposalTargetParam
             _require_write(req[:4], ["roi_output", "label", "bbox_target", "bbox_weight"])
             rois, gt = in_data[0], in_data[1]
             vr = in_data[2] if len(in_data) > 2 else None  # ProposalTarget_v2: valid_ranges
@@ -286,33 +621,17 @@ def _build_ops(mx):
             B = p["batch_images"]
             N = int(_numel(rois.shape) // (B * 4))
             M = int(_numel(gt.shape) // (B * 5))
-            cp = ProposalTargetParam()
-            cp.num_classes, cp.batch_images, cp.image_rois = p["num_classes"], B, p["image_rois"]
-            cp.fg_fraction, cp.fg_thresh = p["fg_fraction"], p["fg_thresh"]
-            cp.bg_thresh_hi, cp.bg_thresh_lo = p["bg_thresh_hi"], p["bg_thresh_lo"]
-            cp.proposal_without_gt, cp.class_agnostic = int(p["proposal_without_gt"]), int(p["class_agnostic"])
-            for i in range(4):
-                cp.bbox_mean[i], cp.bbox_std[i], cp.bbox_weight[i] = (p["bbox_mean"][i], p["bbox_std"][i],
-                                                                       p["bbox_weight"][i])
-            key = str(rois.context)
-            if key not in _state["rng"]:
-                # libc's global rand() state of a process that never called srand (seed 1): one
-                # stream per device, shared by every ProposalTarget node like the libc global is
-                host = (ctypes.c_int32 * 33)()
-                _call("sd_glibc_srand_host", ctypes.c_uint32(1), host)
-                _state["rng"][key] = _state["mx"].nd.array(list(host), ctx=rois.context, dtype="int32")
-            rng = _state["rng"][key]
-            wsb = lib().cdll.sd_proposal_target_workspace_bytes(B, N, M)
-            ws = _scratch(rois, wsb)
+            cp, rng = target_param(p), rand_state(rois.context)
+            ws, wsp, wsn = _ws(rois, "sd_proposal_target_workspace_bytes", B, N, M)
             if vr is not None:
                 _call("sd_proposal_target_v2", _ptr(rois), _ptr(gt), _ptr(vr),
                            int(p.get("filter_scales", False)), N, M, ctypes.byref(cp), _ptr(rng),
                            _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), _ptr(out_data[3]),
-                           _ptr(out_data[4]), None, _ptr(ws), ctypes.c_size_t(wsb), None)
+                           _ptr(out_data[4]), None, wsp, wsn, None)
             else:
                 _call("sd_proposal_target", _ptr(rois), _ptr(gt), N, M, ctypes.byref(cp), _ptr(rng),
                            _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), _ptr(out_data[3]),
-                           _ptr(out_data[4]), None, _ptr(ws), ctypes.c_size_t(wsb), None)
+                           _ptr(out_data[4]), None, wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -320,13 +639,11 @@ def _build_ops(mx):
             for i in range(len(in_grad)):
                 self.assign(in_grad[i], req[i], 0)
 
-    def _numel(shape):
-        n = 1
-        for s in shape:
-            n *= int(s)
-        return n
+    class ProposalTargetProp(Prop):
+        ARGS = ("rois", "gt_boxes")
+        OUTS = ("roi_output", "label", "bbox_target", "bbox_weight", "match_gt_iou")
+        OP, OP_ARGS = ProposalTarget, ("p",)
 
-    class ProposalTargetProp(CustomOpProp):
         def __init__(self, num_classes, batch_images, image_rois, fg_thresh, bg_thresh_hi,
                      bg_thresh_lo, fg_fraction="0.25", proposal_without_gt="False",
                      class_agnostic="False", output_iou="False", bbox_mean="(0,0,0,0)",
@@ -342,27 +659,17 @@ def _build_ops(mx):
                           bbox_weight=_tuple(bbox_weight, 4))
             self.num_visible_outputs = 5 if self.p["output_iou"] else 4
 
-        def list_arguments(self):
-            return ["rois", "gt_boxes"]
-
-        def list_outputs(self):
-            return ["roi_output", "label", "bbox_target", "bbox_weight", "match_gt_iou"]
-
         def infer_shape(self, in_shape):
             p = self.p
             B, S, K = p["batch_images"], p["image_rois"], p["num_classes"]
             return in_shape, [(B, S, 4), (B, S), (B, S, K * 4), (B, S, K * 4), (B, S)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return ProposalTarget(self.p)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
     ops["ProposalTarget"] = (ProposalTargetProp, (None, "ProposalTarget"))
 
     # ---- ProposalTarget_v2 (proposal_target_v2-inl.h): + valid_ranges input, filter_scales ----
     class ProposalTargetV2Prop(ProposalTargetProp):
+        ARGS = ("rois", "gt_boxes", "valid_ranges")
+
         def __init__(self, num_classes, batch_images, image_rois, fg_thresh, bg_thresh_hi,
                      bg_thresh_lo, proposal_without_gt, fg_fraction="0.25", class_agnostic="False",
                      ohem="False", output_iou="False", bbox_mean="(0,0,0,0)",
@@ -376,9 +683,6 @@ def _build_ops(mx):
                 raise ValueError("ProposalTarget_v2: image_rois=-1 is undefined in the reference")
             self.p["filter_scales"] = _bool(filter_scales)
 
-        def list_arguments(self):
-            return ["rois", "gt_boxes", "valid_ranges"]
-
     ops["ProposalTarget_v2"] = (ProposalTargetV2Prop, (None, "ProposalTarget_v2"))
 
     # ---- ProposalMaskTarget (proposal_mask_target-inl.h): rois, gt_boxes, gt_polys [, valid_ranges]
@@ -390,7 +694,6 @@ def _build_ops(mx):
 
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
-            from .ops import ProposalTargetParam
             _require_write(req[:6], ["roi_output", "label", "bbox_target", "bbox_weight", "match_gt_iou",
                                      "mask_target"])
             rois, gt, polys = in_data[0], in_data[1], in_data[2]
@@ -401,39 +704,23 @@ def _build_ops(mx):
             N = int(_numel(rois.shape) // (B * 4))
             M = int(_numel(gt.shape) // (B * 5))
             L = int(polys.shape[2])
-            cp = ProposalTargetParam()
-            cp.num_classes, cp.batch_images, cp.image_rois = p["num_classes"], B, p["image_rois"]
-            cp.fg_fraction, cp.fg_thresh = p["fg_fraction"], p["fg_thresh"]
-            cp.bg_thresh_hi, cp.bg_thresh_lo = p["bg_thresh_hi"], p["bg_thresh_lo"]
-            cp.proposal_without_gt, cp.class_agnostic = int(p["proposal_without_gt"]), int(p["class_agnostic"])
-            for i in range(4):
-                cp.bbox_mean[i], cp.bbox_std[i], cp.bbox_weight[i] = (p["bbox_mean"][i], p["bbox_std"][i],
-                                                                       p["bbox_weight"][i])
-            key = str(rois.context)
-            if key not in _state["rng"]:
-                host = (ctypes.c_int32 * 33)()
-                _call("sd_glibc_srand_host", ctypes.c_uint32(1), host)
-                _state["rng"][key] = _state["mx"].nd.array(list(host), ctx=rois.context, dtype="int32")
-            rng = _state["rng"][key]
+            cp, rng = target_param(p), rand_state(rois.context)
             if p["output_ratio"]:  # proposal_mask_target-inl.h:159-161: the seventh output, kWriteTo
                 _require_write(req[6:7], ["mask_ratio"])
                 mp = p["max_raster_pixels"]
-                wsb = lib().cdll.sd_proposal_mask_target_ratio_workspace_bytes(
-                    B, N, M, p["image_rois"], ctypes.c_float(p["fg_fraction"]), mp)
-                ws = _scratch(rois, wsb)
+                ws, wsp, wsn = _ws(rois, "sd_proposal_mask_target_ratio_workspace_bytes", B, N, M, p["image_rois"],
+                                         ctypes.c_float(p["fg_fraction"]), mp)
                 _call("sd_proposal_mask_target_ratio", _ptr(rois), _ptr(gt), _ptr(polys), _ptr(vr),
                            int(p["filter_scales"]), N, M, L, p["mask_size"], ctypes.byref(cp), _ptr(rng),
                            _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), _ptr(out_data[3]),
-                           _ptr(out_data[4]), _ptr(out_data[5]), _ptr(out_data[6]), mp, None, _ptr(ws),
-                           ctypes.c_size_t(wsb), None)
+                           _ptr(out_data[4]), _ptr(out_data[5]), _ptr(out_data[6]), mp, None, wsp, wsn, None)
                 _sync()
                 return
-            wsb = lib().cdll.sd_proposal_target_workspace_bytes(B, N, M)
-            ws = _scratch(rois, wsb)
+            ws, wsp, wsn = _ws(rois, "sd_proposal_target_workspace_bytes", B, N, M)
             _call("sd_proposal_mask_target", _ptr(rois), _ptr(gt), _ptr(polys), _ptr(vr),
                        int(p["filter_scales"]), N, M, L, p["mask_size"], ctypes.byref(cp), _ptr(rng),
                        _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), _ptr(out_data[3]),
-                       _ptr(out_data[4]), _ptr(out_data[5]), None, _ptr(ws), ctypes.c_size_t(wsb), None)
+                       _ptr(out_data[4]), _ptr(out_data[5]), None, wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -441,6 +728,8 @@ def _build_ops(mx):
                 self.assign(in_grad[i], req[i], 0)
 
     class ProposalMaskTargetProp(ProposalTargetProp):
+        OP, OP_ARGS = ProposalMaskTarget, ("p",)
+
         def __init__(self, num_classes, batch_images, image_rois, mask_size, fg_thresh,
                      bg_thresh_hi, bg_thresh_lo, proposal_without_gt, fg_fraction="0.25",
                      class_agnostic="False", ohem="False", output_ratio="False", output_iou="False",
@@ -491,10 +780,15 @@ def _build_ops(mx):
                 out.append((B, FG))  # -inl.h:453-456
             return in_shape, out
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return ProposalMaskTarget(self.p)
-
     ops["ProposalMaskTarget"] = (ProposalMaskTargetProp, (None, "ProposalMaskTarget"))
+    return ops
+
+
+def _proposal_ops(mx):
+    """anchors and proposals: GenAnchor, NMS, Proposal_v3 / _v2 / v1, GenProposalRetina, get_top_proposal, DecodeBBox,
+    BboxPostProcessing"""
+    CustomOp, Op, Prop = mx.operator.CustomOp, op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- _contrib_GenAnchor: 1 input (shape only), 1 output ----
     class GenAnchor(CustomOp):
@@ -513,17 +807,14 @@ def _build_ops(mx):
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
             self.assign(in_grad[0], req[0], 0)
 
-    class GenAnchorProp(CustomOpProp):
+    class GenAnchorProp(Prop):
+        ARGS = ("cls_prob",)
+        OP, OP_ARGS = GenAnchor, ("scales", "ratios", "stride")
+
         def __init__(self, scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16"):
             super().__init__(need_top_grad=False)
             self.scales, self.ratios = _tuple(scales), _tuple(ratios)
             self.stride = int(feature_stride)
-
-        def list_arguments(self):
-            return ["cls_prob"]
-
-        def list_outputs(self):
-            return ["output"]
 
         def infer_shape(self, in_shape):
             d = in_shape[0]
@@ -531,12 +822,6 @@ def _build_ops(mx):
                 raise ValueError("cls_prob should be a 4D tensor")
             A = len(self.scales) * len(self.ratios)
             return in_shape, [(d[2] * d[3] * A, 4)]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return GenAnchor(self.scales, self.ratios, self.stride)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
 
     ops["_contrib_GenAnchor"] = (GenAnchorProp, ("contrib", "GenAnchor"))
 
@@ -551,8 +836,7 @@ def _build_ops(mx):
             rois = in_data[0]
             _wait(rois)
             B, N, _ = rois.shape
-            wsb = lib().cdll.sd_nms_workspace_bytes(B, N, self.pre)
-            ws = _scratch(rois, wsb)
+            ws, wsp, wsn = _ws(rois, "sd_nms_workspace_bytes", B, N, self.pre)
             pre = min(self.pre if self.pre > 0 else N, N)
             if self.post > pre:
                 # NMSProp::InferShape always declares (B, post, .) but the op writes min(post, pre)
@@ -562,14 +846,17 @@ def _build_ops(mx):
                 self.assign(out_data[0], "write", 0)
                 self.assign(out_data[1], "write", 0)
             _call("sd_nms", _ptr(rois), B, N, self.pre, self.post, float(self.thr), 0,
-                       int(self.sorted), _ptr(out_data[0]), _ptr(out_data[1]), None, _ptr(ws),
-                       ctypes.c_size_t(wsb), None)
+                       int(self.sorted), _ptr(out_data[0]), _ptr(out_data[1]), None, wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
             self.assign(in_grad[0], req[0], 0)  # nms.cu:379-381
 
-    class NMSProp(CustomOpProp):
+    class NMSProp(Prop):
+        ARGS = ("rois",)
+        OUTS = ("output", "score")
+        OP, OP_ARGS = NMS, ("pre", "post", "thr", "sorted")
+
         def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
                      output_score="False", already_sorted="False", workspace="256"):
             super().__init__(need_top_grad=False)
@@ -578,74 +865,379 @@ def _build_ops(mx):
             self.sorted = _bool(already_sorted)
             self.num_visible_outputs = 2 if _bool(output_score) else 1
 
-        def list_arguments(self):
-            return ["rois"]
-
-        def list_outputs(self):
-            return ["output", "score"]
-
         def infer_shape(self, in_shape):
             d = in_shape[0]
             if len(d) != 3 or d[2] != 5:
                 raise ValueError("Input:[bbox] must be (batch, rois, 5)")
             return in_shape, [(d[0], self.post, 4), (d[0], self.post, 1)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return NMS(self.pre, self.post, self.thr, self.sorted)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
     ops["_contrib_NMS"] = (NMSProp, ("contrib", "NMS"))
 
-    # ---- assign_layer_fpn (models/FPN/assign_layer_fpn.py): 1 input, len(rcnn_stride) outputs ----
-    class AssignLayerFPN(CustomOp):
-        def __init__(self, strides, scale0, lvl0):
+    # ---- _contrib_Proposal_v3: cls_prob, bbox_pred, im_info -> output [, score] ----
+    class ProposalV3(Op):
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            cls_prob, bbox_pred, im_info = in_data
+            _wait(cls_prob, bbox_pred, im_info)
+            g = self.g
+            B, A2, H, W = cls_prob.shape
+            A = A2 // 2
+            ws, wsp, wsn = _ws(cls_prob, "sd_proposal_v3_workspace_bytes", B, A, H, W, g["pre"])
+            count = A * H * W
+            pre = min(g["pre"] if g["pre"] > 0 else count, count)
+            if g["is_train"] and g["post"] > pre:
+                # same quirk as _contrib_NMS (proposal_v3.cu:474-479,626-632): declared
+                # (B, post, .), written min(post, pre) rows per image, packed; tail zeroed here
+                self.assign(out_data[0], "write", 0)
+                self.assign(out_data[1], "write", 0)
+            fa = lambda v: (ctypes.c_float * len(v))(*v)
+            _call("sd_proposal_v3_iou" if g["iou_loss"] else "sd_proposal_v3",
+                       _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info),
+                       _ptr(out_data[0]), _ptr(out_data[1]), B, A, H, W, g["pre"], g["post"],
+                       float(g["thr"]), g["min_size"], fa(g["scales"]), len(g["scales"]),
+                       fa(g["ratios"]), len(g["ratios"]), g["stride"], int(g["is_train"]), wsp, wsn, None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(3):
+                self.assign(in_grad[i], req[i], 0)
+
+    class ProposalV3Prop(Prop):
+        ARGS = ("cls_prob", "bbox_pred", "im_info")
+        OUTS = ("output", "score")
+        OP = ProposalV3
+
+        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
+                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)",
+                     feature_stride="16", output_score="False", iou_loss="False", is_train="False",
+                     workspace="256"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(pre=int(rpn_pre_nms_top_n), post=int(rpn_post_nms_top_n),
+                          thr=float(threshold), min_size=int(rpn_min_size), scales=_tuple(scales),
+                          ratios=_tuple(ratios), stride=int(feature_stride),
+                          is_train=_bool(is_train), iou_loss=_bool(iou_loss))  # proposal_v3.cu:536
+            self.num_visible_outputs = 2 if _bool(output_score) else 1
+
+        def infer_shape(self, in_shape):
+            d = in_shape[0]
+            if len(d) != 4:
+                raise ValueError("cls_prob should be (batch, 2 * num_anchors, H, W)")
+            g = self.g
+            A = d[1] // 2
+            if A != len(g["scales"]) * len(g["ratios"]):
+                raise ValueError("num_anchors != len(ratios) * len(scales)")
+            count = A * d[2] * d[3]
+            post = g["post"]  # ProposalProp_v3::InferShape (proposal_v3-inl.h:199-218)
+            return [d, (d[0], 4 * A, d[2], d[3]), (d[0], 3)], [(d[0], post, 4), (d[0], post, 1)]
+
+    ops["_contrib_Proposal_v3"] = (ProposalV3Prop, ("contrib", "Proposal_v3"))
+
+    # ---- _contrib_Proposal_v2 (cls_prob, bbox_pred, im_info, valid_ranges) and _contrib_Proposal
+    #      (cls_prob, bbox_pred, im_info) -> output [, score]  (registered only by install(...,
+    #      proposal=True)) ----
+    class ProposalV12(Op):
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _wait(*in_data)
+            g = self.g
+            cls_prob, bbox_pred, im_info = in_data[:3]
+            B, A2, H, W = cls_prob.shape
+            A = A2 // 2
+            fn = "sd_proposal_v2" if g["v2"] else "sd_proposal"
+            ws, wsp, wsn = _ws(cls_prob, fn + "_workspace_bytes", B, A, H, W, g["pre"])
+            fa = lambda v: (ctypes.c_float * len(v))(*v)
+            common = (B, A, H, W, g["pre"], g["post"], float(g["thr"]), g["min_size"], fa(g["scales"]),
+                      len(g["scales"]), fa(g["ratios"]), len(g["ratios"]), g["stride"])
+            if g["v2"]:
+                _call(fn, _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(in_data[3]),
+                      _ptr(out_data[0]), _ptr(out_data[1]), *common, int(g["filter_scales"]),
+                      int(g["iou_loss"]), wsp, wsn, None)
+            else:
+                _call(fn, _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(out_data[0]),
+                      _ptr(out_data[1]), *common, int(g["is_train"]), int(g["iou_loss"]), wsp, wsn, None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(len(in_grad)):  # proposal_v2.cu:617-639, proposal.cu: all zeros
+                self.assign(in_grad[i], req[i], 0)
+
+    class _ProposalV12Prop(Prop):
+        OUTS = ("output", "score")
+        OP = ProposalV12
+        V2 = True
+
+        def _init(self, rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                  feature_stride, output_score, iou_loss, is_train="False", filter_scales="False"):
+            super().__init__(need_top_grad=False)
+            self.g = dict(pre=int(rpn_pre_nms_top_n), post=int(rpn_post_nms_top_n), thr=float(threshold),
+                          min_size=int(rpn_min_size), scales=_tuple(scales), ratios=_tuple(ratios),
+                          stride=int(feature_stride), iou_loss=_bool(iou_loss), is_train=_bool(is_train),
+                          filter_scales=_bool(filter_scales), v2=self.V2)
+            self.num_visible_outputs = 2 if _bool(output_score) else 1
+
+        def list_arguments(self):
+            return ["cls_prob", "bbox_pred", "im_info"] + (["valid_ranges"] if self.V2 else [])
+
+        def infer_shape(self, in_shape):
+            # ProposalProp(_v2)::InferShape (proposal_v2-inl.h:199-220, proposal-inl.h:199-217)
+            d = in_shape[0]
+            if len(d) != 4:
+                raise ValueError("cls_prob should be (batch, 2 * num_anchors, H, W)")
+            g = self.g
+            A = d[1] // 2
+            if A != len(g["scales"]) * len(g["ratios"]):
+                raise ValueError("num_anchors != len(ratios) * len(scales)")
+            ins = [d, (d[0], 4 * A, d[2], d[3]), (d[0], 3)] + ([(d[0], 2)] if self.V2 else [])
+            return ins, [(d[0], g["post"], 4), (d[0], g["post"], 1)]
+
+    class ProposalV2Prop(_ProposalV12Prop):
+        V2 = True
+
+        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
+                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16",
+                     output_score="False", iou_loss="False", workspace="256", filter_scales="False"):
+            # defaults: proposal_v2-inl.h:141-183
+            self._init(rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                       feature_stride, output_score, iou_loss, filter_scales=filter_scales)
+
+    class ProposalV1Prop(_ProposalV12Prop):
+        V2 = False
+
+        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
+                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16",
+                     output_score="False", iou_loss="False", workspace="256", is_train="False"):
+            # defaults: proposal-inl.h:141-183
+            self._init(rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
+                       feature_stride, output_score, iou_loss, is_train=is_train)
+
+    ops["_contrib_Proposal_v2"] = (ProposalV2Prop, ("contrib", "Proposal_v2"))
+    ops["_contrib_Proposal"] = (ProposalV1Prop, ("contrib", "Proposal"))
+
+    # ---- _contrib_GenProposalRetina: cls_prob, bbox_pred, im_info, anchors -> output, scores ----
+    #      (registered only by install(..., retina=True))
+    class GenProposalRetina(Op):
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            cls_prob, bbox_pred, im_info, anchors = in_data
+            _wait(cls_prob, bbox_pred, im_info, anchors)
+            g = self.g
+            B, AK, H, W = cls_prob.shape
+            ws, wsp, wsn = _ws(cls_prob, "sd_gen_proposal_retina_workspace_bytes", B, AK, H, W)
+            fa = lambda v: (ctypes.c_float * len(v))(*v)
+            _call("sd_gen_proposal_retina", _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(anchors),
+                  _ptr(out_data[0]), _ptr(out_data[1]), B, AK, H, W, g["A"], g["pre"], g["min_size"],
+                  float(g["thresh"]), fa(g["mean"]), fa(g["std"]), int(g["iou_loss"]), int(g["one_hot"]),
+                  int(g["bwa"]), wsp, wsn, None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(4):  # generate_proposal_retina.cu:471-493
+                self.assign(in_grad[i], req[i], 0)
+
+    class GenProposalRetinaProp(Prop):
+        ARGS = ("cls_prob", "bbox_pred", "im_info", "anchors")
+        OUTS = ("output", "scores")
+        OP = GenProposalRetina
+        PARAMS = ("rpn_pre_nms_top_n", "rpn_min_size", "feature_stride", "num_anchors", "thresh", "anchor_mean",
+                  "anchor_std", "iou_loss", "output_one_hot", "batch_wise_anchor", "workspace")
+
+        def __init__(self, num_anchors, rpn_pre_nms_top_n="6000", rpn_min_size="16", feature_stride="16",
+                     thresh="0", anchor_mean="(0,0,0,0)", anchor_std="(1,1,1,1)", iou_loss="False",
+                     output_one_hot="True", batch_wise_anchor="False", workspace="256"):
+            # defaults: generate_proposal_retina-inl.h:62-89
+            super().__init__(need_top_grad=False)
+            why = self.sd_supports(dict(num_anchors=num_anchors, rpn_pre_nms_top_n=rpn_pre_nms_top_n,
+                                        iou_loss=iou_loss, batch_wise_anchor=batch_wise_anchor,
+                                        anchor_mean=anchor_mean, anchor_std=anchor_std))
+            if why:
+                raise ValueError("GenProposalRetina: " + why)
+            self.g = dict(A=int(num_anchors), pre=int(rpn_pre_nms_top_n), min_size=int(rpn_min_size),
+                          thresh=float(thresh), mean=_tuple(anchor_mean, 4), std=_tuple(anchor_std, 4),
+                          iou_loss=_bool(iou_loss), one_hot=_bool(output_one_hot), bwa=_bool(batch_wise_anchor))
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls
+            back to the native constructor)."""
+            for k in params:
+                if k not in cls.PARAMS:
+                    return "parameter %r is not one this operator takes" % k
+            try:
+                A = int(params.get("num_anchors", "0"))
+                pre = int(params.get("rpn_pre_nms_top_n", "6000"))
+                _tuple(params.get("anchor_mean", "(0,0,0,0)"), 4)
+                _tuple(params.get("anchor_std", "(1,1,1,1)"), 4)
+            except Exception as e:
+                return "unparsable parameter (%s)" % e
+            if A <= 0:
+                return "num_anchors must be > 0"
+            if not 0 < pre <= 16384:
+                return "rpn_pre_nms_top_n=%d outside 1..16384" % pre
+            # the class count is only known from the input shape: the reference reads out of bounds for
+            # K > 1 in both of these (generate_proposal_retina.cu:161-209, :383)
+            if _bool(params.get("iou_loss", "False")):
+                return "iou_loss is taken only for one class, unknown when the graph is built"
+            if _bool(params.get("batch_wise_anchor", "False")):
+                return "batch_wise_anchor is taken only for one class or one image, unknown when the graph is built"
+            return ""
+
+        def infer_shape(self, in_shape):
+            # GenProposalRetinaProp::InferShape (generate_proposal_retina-inl.h:106-140)
+            d = in_shape[0]
+            if len(d) != 4:
+                raise ValueError("cls_prob should be (batch, num_anchors * num_classes, H, W)")
+            g = self.g
+            A = g["A"]
+            if d[1] % A:
+                raise ValueError("cls_prob channels (%d) are not a multiple of num_anchors (%d)" % (d[1], A))
+            anchors = (d[0], d[2] * d[3] * A, 4) if g["bwa"] else (d[2] * d[3] * A, 4)
+            oc = d[1] // A + 1 if g["one_hot"] else 1
+            return ([d, (d[0], 4 * A, d[2], d[3]), (d[0], 3), anchors],
+                    [(d[0], g["pre"], 4), (d[0], g["pre"], oc)])
+
+    ops["_contrib_GenProposalRetina"] = (GenProposalRetinaProp, ("contrib", "GenProposalRetina"))
+
+    # ---- get_top_proposal (models/FPN/get_top_proposal.py): bbox, score -> top_n of each ----
+    class GetTopProposal(CustomOp):
+        def __init__(self, top_n):
             super().__init__()
-            self.strides, self.scale0, self.lvl0 = strides, scale0, lvl0
+            self.top_n = top_n
 
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
-            rois = in_data[0]
-            _wait(rois)
-            n = 1
-            for s in rois.shape[:-1]:
-                n *= int(s)
-            mx_ = _state["mx"]
-            per = mx_.nd.empty((len(self.strides),) + tuple(rois.shape), ctx=rois.context)
-            _call("sd_fpn_roi_assign", _ptr(rois), n, _iarr(self.strides), len(self.strides),
-                       float(self.scale0), float(self.lvl0), _ptr(per), None, None)
+            bbox, score = in_data
+            _wait(bbox, score)
+            _call("sd_get_top_proposal", _ptr(bbox), _ptr(score), bbox.shape[0], bbox.shape[1],
+                       self.top_n, _ptr(out_data[0]), _ptr(out_data[1]), None)
             _sync()
-            for i in range(len(self.strides)):
-                self.assign(out_data[i], req[i], per[i])
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
             self.assign(in_grad[0], req[0], 0)
+            self.assign(in_grad[1], req[1], 0)
 
-    class AssignLayerFPNProp(CustomOpProp):
-        def __init__(self, rcnn_stride, roi_canonical_scale, roi_canonical_level):
+    class GetTopProposalProp(Prop):
+        ARGS = ("bbox", "score")
+        OUTS = ("bbox", "score")
+        OP, OP_ARGS = GetTopProposal, ("top_n",)
+
+        def __init__(self, top_n):
             super().__init__(need_top_grad=False)
-            self.rcnn_stride = _tuple(rcnn_stride, typ=int)
-            self.roi_canonical_scale = int(roi_canonical_scale)
-            self.roi_canonical_level = int(roi_canonical_level)
-
-        def list_arguments(self):
-            return ["rois"]
-
-        def list_outputs(self):
-            return ["rois_s{}".format(s) for s in self.rcnn_stride]
+            self.top_n = int(top_n)
 
         def infer_shape(self, in_shape):
-            return [in_shape[0]], [in_shape[0]] * len(self.rcnn_stride)
+            b = in_shape[0]
+            return in_shape, [(b[0], self.top_n, b[2]), (b[0], self.top_n, 1)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return AssignLayerFPN(self.rcnn_stride, self.roi_canonical_scale,
-                                  self.roi_canonical_level)
+    ops["get_top_proposal"] = (GetTopProposalProp, None)
 
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
+    # ---- _contrib_DecodeBBox: rois, bbox_pred, im_info -> output ----
+    class DecodeBBox(Op):
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _require_write(req[:1], ["output"])
+            rois, pred, info = in_data
+            _wait(rois, pred, info)
+            g = self.g
+            fa = lambda v: (ctypes.c_float * 4)(*v)
+            _call("sd_decode_bbox", _ptr(rois), _ptr(pred), _ptr(info), _ptr(out_data[0]),
+                       rois.shape[0], rois.shape[1], pred.shape[2] // 4, fa(g["mean"]), fa(g["std"]),
+                       int(g["agnostic"]), int(g["xyxy"]), None)
+            _sync()
 
-    ops["assign_layer_fpn"] = (AssignLayerFPNProp, None)
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            for i in range(3):
+                self.assign(in_grad[i], req[i], 0)
+
+    class DecodeBBoxProp(Prop):
+        ARGS = ("rois", "bbox_pred", "im_info")
+        OP = DecodeBBox
+
+        def __init__(self, bbox_mean="(0,0,0,0)", bbox_std="(0.1,0.1,0.2,0.2)",
+                     class_agnostic="True", bbox_decode_type="xywh"):
+            super().__init__(need_top_grad=False)
+            if bbox_decode_type not in ("xywh", "xyxy"):
+                raise ValueError("bbox_decode_type must be 'xywh' or 'xyxy'")
+            self.g = dict(mean=_tuple(bbox_mean, 4), std=_tuple(bbox_std, 4),
+                          agnostic=_bool(class_agnostic), xyxy=bbox_decode_type == "xyxy")
+
+        def infer_shape(self, in_shape):
+            d = in_shape[1]
+            out = (d[0], d[1], 4) if self.g["agnostic"] else tuple(d)
+            return in_shape, [out]
+
+    ops["_contrib_DecodeBBox"] = (DecodeBBoxProp, ("contrib", "DecodeBBox"))
+
+    # ---- BboxPostProcessing (models/maskrcnn/bbox_post_processing.py:35-111): cls_score, bbox_xyxy ->
+    # post_score, post_bbox_xyxy, post_cls.  The reference's is itself a Python CustomOp reached through
+    # mx.sym.Custom, so there is no constructor to alias: patch_bbox_post rebinds the builder method ----
+    class BboxPostProcessing(Op):
+        def forward(self, is_train, req, in_data, out_data, aux):
+            _no_add(req)
+            _require_write(req[:3], ["post_score", "post_bbox_xyxy", "post_cls"])
+            score, bbox = in_data
+            _wait(score, bbox)
+            g = self.g
+            B, R, K = score.shape
+            Kb = bbox.shape[2] // 4
+            ws, wsp, wsn = _ws(score, "sd_bbox_post_processing_workspace_bytes", B, R, K, Kb, g["max_det"])
+            _call("sd_bbox_post_processing", _ptr(score), _ptr(bbox), B, R, K, Kb, g["min_score"], g["thr"],
+                  g["max_det"], _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), wsp, wsn, None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            self.assign(in_grad[0], req[0], 0)
+            self.assign(in_grad[1], req[1], 0)
+
+    class BboxPostProcessingProp(Prop):
+        ARGS = ("cls_score", "bbox_xyxy")
+        OUTS = ("post_score", "post_bbox_xyxy", "post_cls")
+        OP = BboxPostProcessing
+        LIMITS = dict(rows=4096, classes=256, max_det=1024)
+
+        def __init__(self, max_det_per_image, min_det_score, nms_type, nms_thr):
+            super().__init__(need_top_grad=False)
+            # parsed as BboxPostProcessingProp.__init__ does (bbox_post_processing.py:81-86)
+            self.g = dict(max_det=int(max_det_per_image), min_score=float(min_det_score),
+                          nms_type=str(nms_type), thr=float(nms_thr))
+            if self.g["nms_type"] != "nms":
+                raise NotImplementedError("BboxPostProcessing: nms_type %r (the reference takes 'nms' only)"
+                                          % self.g["nms_type"])
+
+        @classmethod
+        def sd_supports(cls, params):
+            """'' when the kernels take this parameter set, else the reason (patch_bbox_post then hands the
+            call back to the reference's method)."""
+            try:
+                top = int(params["max_det_per_image"])
+                float(params["min_det_score"])
+                float(params["nms_thr"])
+            except Exception as e:
+                return "unparsable parameter (%s)" % e
+            if str(params.get("nms_type")) != "nms":
+                return "nms_type %r is not 'nms'" % (params.get("nms_type"),)
+            if not 0 <= top <= cls.LIMITS["max_det"]:
+                return "max_det_per_image=%d outside 0..%d" % (top, cls.LIMITS["max_det"])
+            return ""
+
+        def infer_shape(self, in_shape):
+            s, b = in_shape[0], in_shape[1]
+            if len(s) != 3 or len(b) != 3:
+                raise ValueError("cls_score should be (batch, rois, classes), bbox_xyxy (batch, rois, 4 or 4 * classes)")
+            if s[1] > self.LIMITS["rows"] or s[2] > self.LIMITS["classes"] or b[2] not in (4, 4 * s[2]):
+                raise ValueError("BboxPostProcessing: cls_score %s / bbox_xyxy %s outside rois <= %d, classes <= %d, "
+                                 "boxes (.,.,4) or (.,.,4 * classes)" % (tuple(s), tuple(b), self.LIMITS["rows"],
+                                                                         self.LIMITS["classes"]))
+            top = self.g["max_det"]
+            return [s, b], [(s[0], top, 1), (s[0], top, 4), (s[0], top, 1)]
+
+    ops["BboxPostProcessing"] = (BboxPostProcessingProp, None)
+    return ops
+
+
+def _deform_conv_ops(mx):
+    """DeformableConvolution"""
+    Op, Prop = op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- _contrib_DeformableConvolution: data, offset, weight[, bias] -> output.  Upstream MXNet 1.6
     #      DeformableConvolutionParam: kernel, stride, dilate, pad, num_filter, num_group,
@@ -653,18 +1245,7 @@ def _build_ops(mx):
     #      models/dcn/builder.py:14-17 (no_bias=True), models/RepPoints/builder.py:215-245 (bias),
     #      models/sepc/sepc_dconv.py:12-16 (num_group / bias passed through),
     #      models/tridentnet/resnet_v1.py:85-90 (weight / bias shared between branches) ----
-    class DeformConv(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def _ws(self, x):
-            g = self.g
-            N, C, H, W = x.shape
-            n = lib().cdll.sd_deform_conv_workspace_bytes(N, C, H, W, g["kh"], g["kw"], g["pad"],
-                                                          g["stride"], g["dil"])
-            return _scratch(x, n), n
-
+    class DeformConv(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             x, off, w = in_data[:3]
@@ -678,12 +1259,11 @@ def _build_ops(mx):
             # deformable sampling fused into the GEMM (a few MB of workspace instead of N*C*9*Ho*Wo*4 bytes;
             # shapes the fused kernel does not take run im2col + GEMM behind the same entry point)
             keep = 1 if (is_train and g["cache_col"]) else 0
-            n = int(lib().cdll.sd_deform_convolution_fwd_workspace_bytes(
-                N, C, H, W, g["F"], g["kh"], g["kw"], g["pad"], g["stride"], g["dil"], g["dg"], g["G"], keep))
-            ws = _scratch(x, n)
+            ws, wsp, wsn = _ws(x, "sd_deform_convolution_fwd_workspace_bytes", N, C, H, W, g["F"], g["kh"], g["kw"],
+                               g["pad"], g["stride"], g["dil"], g["dg"], g["G"], keep)
             _call("sd_deform_convolution_fwd", _ptr(x), _ptr(off), _ptr(w), _ptr(b), _ptr(out_data[0]), N, C,
                        H, W, g["F"], g["kh"], g["kw"], g["pad"], g["stride"], g["dil"], g["dg"], g["G"], keep,
-                       _ptr(ws), ctypes.c_size_t(n), None)
+                       wsp, wsn, None)
             self._fwd_ws = (ws, tuple(x.shape)) if keep else None
             _sync()
 
@@ -692,7 +1272,8 @@ def _build_ops(mx):
             _wait(out_grad[0], *in_data)
             g = self.g
             N, C, H, W = x.shape
-            ws, n = self._ws(x)
+            ws, wsp, wsn = _ws(x, "sd_deform_conv_workspace_bytes", N, C, H, W, g["kh"], g["kw"], g["pad"], g["stride"],
+                               g["dil"])
             kept = getattr(self, "_fwd_ws", None)
             self._fwd_ws = None
             col = None
@@ -703,10 +1284,14 @@ def _build_ops(mx):
                        _ptr(in_grad[0]), _ptr(in_grad[1]), _ptr(in_grad[2]), _ptr(in_grad[3]) if has_b else None,
                        _req(req[0]), _req(req[1]), _req(req[2]), _req(req[3]) if has_b else REQ["null"],
                        N, C, H, W, g["F"], g["kh"], g["kw"], g["pad"], g["stride"], g["dil"], g["dg"], g["G"],
-                       _ptr(ws), ctypes.c_size_t(n), None)
+                       wsp, wsn, None)
             _sync()
 
-    class DeformConvProp(CustomOpProp):
+    class DeformConvProp(Prop):
+        OP = DeformConv
+        # (the bias itself is not needed by the backward: deformable_convolution-inl.h Backward reads
+        # out_grad, data, offset, weight)
+        DEPS = ((OUT_GRAD, 0), (IN_DATA, 0), (IN_DATA, 1), (IN_DATA, 2))
         # the op's own parameter names (+ cache_col, this adapter's attribute); anything else, and any
         # value the kernels do not take, makes install()'s alias hand the call back to the constructor it
         # replaced (sd_supports) -- the graph then holds the native operator for that node
@@ -760,9 +1345,6 @@ def _build_ops(mx):
         def list_arguments(self):
             return ["data", "offset", "weight"] + (["bias"] if self.g["bias"] else [])
 
-        def list_outputs(self):
-            return ["output"]
-
         def infer_shape(self, in_shape):
             g = self.g
             d = in_shape[0]
@@ -779,689 +1361,20 @@ def _build_ops(mx):
             ins = [d, off, w] + ([(g["F"],)] if g["bias"] else [])
             return ins, [(d[0], g["F"], Ho, Wo)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return DeformConv(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            # (the bias itself is not needed by the backward: deformable_convolution-inl.h Backward reads
-            # out_grad, data, offset, weight)
-            return [out_grad[0], in_data[0], in_data[1], in_data[2]]
-
     ops["_contrib_DeformableConvolution"] = (DeformConvProp, ("contrib", "DeformableConvolution"))
+    return ops
 
-    def _fpn_packed(pooled):
-        return tuple(pooled) in ((7, 7), (14, 14))
 
-    # ---- fpn_roi_align: the whole FPNRoiAlign.get_roi_feature subgraph (models/FPN/builder.py:
-    #      567-610: assign -> per level ROIAlign_v2 -> add_n) as ONE op: feats..., rois -> output ----
-    class FPNRoIAlign(CustomOp):
-        """outputs: output, then the op's private forward -> backward state.  7x7 / 14x14 pooling:
-        one-byte arg-max + the per-RoI coordinate / tap table (sd_fpn_roi_align_fwd_packed);
-        other sizes: the reference's two fp32 arg-max planes."""
-
-        def __init__(self, strides, pooled, scale0, lvl0, fp16=False):
-            super().__init__()
-            self.strides, self.pooled, self.scale0, self.lvl0 = strides, pooled, scale0, lvl0
-            self.packed = _fpn_packed(pooled)
-            self.fp16 = fp16  # fp16 feature maps in, fp16 output out (packed pooling sizes only)
-
-        def _levels(self, feats):
-            ptrs = (ctypes.c_void_p * len(feats))(*[_ptr(f).value for f in feats])
-            return ptrs, _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            feats, rois = in_data[:-1], in_data[-1]
-            _wait(*in_data)
-            B, C = feats[0].shape[:2]
-            ptrs, Hs, Ws = self._levels(feats)
-            wsb = lib().cdll.sd_fpn_roi_align_workspace_bytes(B, rois.shape[1])
-            ws = _scratch(rois, wsb)
-            fn = "sd_fpn_roi_align_fwd_packed" if self.packed else "sd_fpn_roi_align_fwd"
-
-            def run(name, level_ptrs, out0):
-                _call(name, level_ptrs, Hs, Ws, _iarr(self.strides), len(feats), _ptr(rois),
-                           _ptr(out0), _ptr(out_data[1]), _ptr(out_data[2]), B, C, rois.shape[1],
-                           self.pooled[0], self.pooled[1], float(self.scale0), float(self.lvl0),
-                           _ptr(ws), ctypes.c_size_t(wsb), None)
-
-            if not self.fp16 and self.packed and is_train:
-                # training: ONE rois-only pre-pass for the step -- the backward's band lists / tap
-                # tables are built here, into the op's fourth (private) output
-                plan = out_data[3]
-                _call(fn + "_plan", ptrs, Hs, Ws, _iarr(self.strides), len(feats), _ptr(rois),
-                           _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), B, C, rois.shape[1],
-                           self.pooled[0], self.pooled[1], float(self.scale0), float(self.lvl0),
-                           _ptr(ws), ctypes.c_size_t(wsb), _ptr(plan), ctypes.c_size_t(plan.size), None)
-                self._planned = True
-            elif not self.fp16:
-                self._planned = False
-                run(fn, ptrs, out_data[0])
-            else:
-                try:
-                    run(fn + "_f16", ptrs, out_data[0])
-                except SimpleDetOpsError as e:
-                    if e.code != SD_ERR_UNSUPPORTED:
-                        raise
-                    # a shape the band-resident kernel does not take: the casts the reference graph
-                    # carries itself (models/FPN/builder.py:581-586, 607-608) around the fp32 op
-                    f32 = [_scratch(rois, f.size * 4).reshape(f.shape) for f in feats]
-                    for f, g in zip(feats, f32):
-                        _call("sd_cast_f16_to_f32", _ptr(f), _ptr(g), ctypes.c_size_t(f.size), None)
-                    o32 = _scratch(rois, out_data[0].size * 4).reshape(out_data[0].shape)
-                    p32 = (ctypes.c_void_p * len(f32))(*[_ptr(g).value for g in f32])
-                    run(fn, p32, o32)
-                    _call("sd_cast_f32_to_f16", _ptr(o32), _ptr(out_data[0]),
-                               ctypes.c_size_t(o32.size), REQ["write"], None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            feats, rois = in_data[:-1], in_data[-1]
-            _wait(out_grad[0], rois, *out_data[1:])
-            rq = {_req(r) for r in req[:-1]}
-            if len(rq) != 1:
-                raise RuntimeError("fpn_roi_align: all feature gradients must share one req")
-            B, C = feats[0].shape[:2]
-            req_data = rq.pop()
-            og, grads16 = out_grad[0], None
-            if self.fp16 and self.packed:
-                # the backward kernel's fp16-I/O instance: the graph's to_fp32 / to_fp16 casts
-                # (models/FPN/builder.py:581-586, 607-608) happen inside the kernel
-                ptrs16, Hs16, Ws16 = self._levels(in_grad[:-1])
-                lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes.restype = ctypes.c_size_t
-                wsb = lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes(Hs16, Ws16, len(feats), B, rois.shape[1])
-                ws = _scratch(rois, wsb)
-                try:
-                    _call("sd_fpn_roi_align_bwd_packed_f16", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
-                               _ptr(out_data[2]), ptrs16, Hs16, Ws16, _iarr(self.strides), len(feats), req_data,
-                               B, C, rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
-                               float(self.lvl0), _ptr(ws), ctypes.c_size_t(wsb), None)
-                    _sync()
-                    self.assign(in_grad[-1], req[-1], 0)
-                    return
-                except SimpleDetOpsError as e:
-                    if e.code != SD_ERR_UNSUPPORTED:
-                        raise
-            if self.fp16:
-                # the sums are formed by the fp32 kernel: the graph's to_fp32 / to_fp16 casts
-                # (models/FPN/builder.py:581-586, 607-608) happen here, at the op boundary
-                og = _scratch(rois, out_grad[0].size * 4).reshape(out_grad[0].shape)
-                _call("sd_cast_f16_to_f32", _ptr(out_grad[0]), _ptr(og), ctypes.c_size_t(out_grad[0].size), None)
-                grads16 = in_grad[:-1]
-                in_grad = [_scratch(rois, g.size * 4).reshape(g.shape) for g in grads16] + [in_grad[-1]]
-                rq = {REQ["write"]}
-            else:
-                rq = {req_data}
-            ptrs, Hs, Ws = self._levels(in_grad[:-1])
-            out_grad = [og]
-            if self.packed and not self.fp16 and getattr(self, "_planned", False):
-                plan = out_data[3]   # lists / tap tables left by this op's forward
-                _call("sd_fpn_roi_align_bwd_packed_plan", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
-                           _ptr(out_data[2]), ptrs, Hs, Ws, _iarr(self.strides), len(feats), rq.pop(), B, C,
-                           rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
-                           float(self.lvl0), _ptr(plan), ctypes.c_size_t(plan.size), None)
-            elif self.packed:  # with the workspace the per-band RoI lists are built once, not per channel
-                lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes.restype = ctypes.c_size_t
-                wsb = lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes(Hs, Ws, len(feats), B, rois.shape[1])
-                ws = _scratch(rois, wsb)
-                _call("sd_fpn_roi_align_bwd_packed_ws", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
-                           _ptr(out_data[2]), ptrs, Hs, Ws, _iarr(self.strides), len(feats), rq.pop(), B, C,
-                           rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
-                           float(self.lvl0), _ptr(ws), ctypes.c_size_t(wsb), None)
-            else:
-                _call("sd_fpn_roi_align_bwd", _ptr(out_grad[0]), _ptr(rois), _ptr(out_data[1]),
-                           _ptr(out_data[2]), ptrs, Hs, Ws, _iarr(self.strides), len(feats), rq.pop(), B, C,
-                           rois.shape[1], self.pooled[0], self.pooled[1], float(self.scale0),
-                           float(self.lvl0), None)
-            if self.fp16:
-                for g32, g16 in zip(in_grad[:-1], grads16):
-                    _call("sd_cast_f32_to_f16", _ptr(g32), _ptr(g16), ctypes.c_size_t(g16.size), req_data, None)
-            _sync()
-            self.assign(in_grad[-1], req[-1], 0)
-
-    class FPNRoIAlignProp(CustomOpProp):
-        def __init__(self, rcnn_stride, pooled_size="(7, 7)", roi_canonical_scale="224",
-                     roi_canonical_level="4", fp16="False"):
-            super().__init__(need_top_grad=True)
-            self.rcnn_stride = _tuple(rcnn_stride, typ=int)
-            self.pooled_size = _tuple(pooled_size, 2, int)
-            self.scale0, self.lvl0 = float(roi_canonical_scale), float(roi_canonical_level)
-            self.packed = _fpn_packed(self.pooled_size)
-            self.fp16 = _bool(fp16)
-            if self.fp16 and not self.packed:
-                raise ValueError("fpn_roi_align: fp16 I/O is provided for 7x7 and 14x14 pooling")
-
-        def list_arguments(self):
-            return ["data_s{}".format(s) for s in self.rcnn_stride] + ["rois"]
-
-        def list_outputs(self):
-            # packed: output, then private forward -> backward state (arg-max codes, coordinate table,
-            # the backward's band lists / tap tables built by the forward's pre-pass)
-            return ["output", "argmax", "coords", "plan"] if self.packed else ["output", "maxidx_x", "maxidx_y"]
-
-        num_visible_outputs = 1
-
-        def infer_shape(self, in_shape):
-            feats, b = in_shape[:-1], in_shape[-1]
-            if len(b) != 3 or b[2] != 4:
-                raise ValueError("bbox should be a 3D tensor of shape [batch, rois, 4]")
-            o = (b[0], b[1], feats[0][1], self.pooled_size[0], self.pooled_size[1])
-            if self.packed:
-                stride = int(lib().cdll.sd_fpn_roi_align_argmax_stride(*self.pooled_size))
-                lib().cdll.sd_fpn_roi_align_plan_bytes.restype = ctypes.c_size_t
-                pb = int(lib().cdll.sd_fpn_roi_align_plan_bytes(_iarr([f[2] for f in feats]),
-                                                                _iarr([f[3] for f in feats]), len(feats),
-                                                                int(b[0]), int(b[1])))
-                return in_shape, [o, (b[0], b[1], feats[0][1], stride),
-                                  (b[0], b[1], 9 * (self.pooled_size[0] + self.pooled_size[1])),
-                                  ((pb + 15) // 16 * 16,)]
-            return in_shape, [o, o, o]
-
-        def infer_type(self, in_type):
-            import numpy as np
-            f32 = np.float32
-            if self.fp16:  # feature maps fp16, rois fp32 -> output fp16; the state keeps its types
-                return [np.float16] * (len(in_type) - 1) + [f32], [np.float16, np.uint8, f32, np.uint8], []
-            if self.packed:
-                return in_type, [f32, np.uint8, f32, np.uint8], []
-            return in_type, [f32, f32, f32], []
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return FPNRoIAlign(self.rcnn_stride, self.pooled_size, self.scale0, self.lvl0, self.fp16)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [out_grad[0], in_data[-1]] + list(out_data[1:])
-
-    ops["fpn_roi_align"] = (FPNRoIAlignProp, None)
-
-    def _dpsroi_supported(ncls, pooled, samples):
-        """the set forward AND backward take: the library's predicate, not a copy of its limits"""
-        if min(ncls, pooled, samples) < 1 or max(ncls, pooled, samples) > 4096:
-            return False
-        return bool(lib().cdll.sd_deform_psroi_pool_supported(int(ncls), int(pooled), int(samples)))
-
-    # ---- _contrib_DeformablePSROIPooling (upstream MXNet; models/TSD/poolings.py:87-100, 151-164):
-    #      data, rois[, trans] -> output, top_count (1 visible) ----
-    class DeformablePSROIPooling(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def _tail(self, data, rois, trans):
-            g = self.g
-            B, C, H, W = data.shape
-            ncls = 1 if g["no_trans"] else trans.shape[1] // 2
-            return (B, C, H, W, rois.shape[0], ncls, float(g["spatial_scale"]), g["output_dim"], g["group_size"],
-                    g["pooled_size"], g["part_size"], g["sample_per_part"], float(g["trans_std"]), int(g["no_trans"]),
-                    None)
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            data, rois = in_data[:2]
-            trans = None if self.g["no_trans"] else in_data[2]
-            _wait(*in_data)
-            _call("sd_deform_psroi_pool_fwd", _ptr(data), _ptr(rois), _ptr(trans), _ptr(out_data[0]),
-                  _ptr(out_data[1]), *self._tail(data, rois, trans))
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            data, rois = in_data[:2]
-            no_trans = self.g["no_trans"]
-            trans = None if no_trans else in_data[2]
-            _wait(out_grad[0], out_data[1], *in_data)
-            _call("sd_deform_psroi_pool_bwd", _ptr(out_grad[0]), _ptr(data), _ptr(rois), _ptr(trans),
-                  _ptr(out_data[1]), _ptr(in_grad[0]), _ptr(in_grad[1]), None if no_trans else _ptr(in_grad[2]),
-                  _req(req[0]), _req(req[1]), REQ["null"] if no_trans else _req(req[2]),
-                  *self._tail(data, rois, trans))
-            _sync()
-
-    class DeformablePSROIPoolingProp(CustomOpProp):
-        PARAMS = ("spatial_scale", "output_dim", "group_size", "pooled_size", "part_size", "sample_per_part",
-                  "trans_std", "no_trans")
-
-        def __init__(self, spatial_scale, output_dim, group_size, pooled_size, part_size="0", sample_per_part="1",
-                     trans_std="0.0", no_trans="False"):
-            super().__init__(need_top_grad=True)
-            params = dict(spatial_scale=spatial_scale, output_dim=output_dim, group_size=group_size,
-                          pooled_size=pooled_size, part_size=part_size, sample_per_part=sample_per_part,
-                          trans_std=trans_std, no_trans=no_trans)
-            why = self.sd_supports({k: str(v) for k, v in params.items()})
-            if why:
-                raise ValueError("DeformablePSROIPooling: " + why)
-            self.g = dict(spatial_scale=float(spatial_scale), output_dim=int(output_dim), group_size=int(group_size),
-                          pooled_size=int(pooled_size), part_size=int(part_size), sample_per_part=int(sample_per_part),
-                          trans_std=float(trans_std), no_trans=_bool(no_trans))
-
-        @classmethod
-        def sd_supports(cls, params):
-            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls back to
-            the native constructor)."""
-            for k in params:
-                if k not in cls.PARAMS:
-                    return "parameter %r is not one this operator takes" % k
-            try:
-                float(params["spatial_scale"])
-                float(params.get("trans_std", "0.0"))
-                od, G, P = int(params["output_dim"]), int(params["group_size"]), int(params["pooled_size"])
-                part, S = int(params.get("part_size", "0")), int(params.get("sample_per_part", "1"))
-            except Exception as e:
-                return "missing or unparsable parameter (%s)" % e
-            if od < 1 or G < 1 or P < 1 or S < 1 or part < 0:
-                return "output_dim, group_size, pooled_size, sample_per_part must be >= 1 and part_size >= 0"
-            # the library's own predicate, here for ONE class: the class count is known only from the offsets' shape
-            # (infer_shape asks again with it, and can only raise by then)
-            if not _dpsroi_supported(1, P, S):
-                return ("pooled_size %d with sample_per_part %d: the RoI's tap table and the backward's sums do not "
-                        "fit in LDS (sd_deform_psroi_pool_supported)" % (P, S))
-            return ""
-
-        def list_arguments(self):
-            return ["data", "rois"] if self.g["no_trans"] else ["data", "rois", "trans"]
-
-        def list_outputs(self):
-            return ["output", "top_count"]
-
-        num_visible_outputs = 1
-
-        def infer_shape(self, in_shape):
-            g = self.g
-            d, b = in_shape[:2]
-            if len(d) != 4:
-                raise ValueError("data should be a 4D tensor")
-            if len(b) != 2 or b[1] != 5:
-                raise ValueError("bbox should be a 2D tensor of shape [batch, 5]")
-            if d[1] != g["output_dim"] * g["group_size"] ** 2:
-                raise ValueError("data has %d channels, output_dim * group_size^2 = %d"
-                                 % (d[1], g["output_dim"] * g["group_size"] ** 2))
-            if not g["no_trans"]:
-                t = in_shape[2]
-                part = g["part_size"] or g["pooled_size"]
-                if len(t) != 4 or t[0] != b[0] or t[1] % 2 or t[1] < 2 or tuple(t[2:]) != (part, part):
-                    raise ValueError("trans should have shape (rois, 2 * num_classes, %d, %d)" % (part, part))
-                if g["output_dim"] % (t[1] // 2):
-                    raise ValueError("output_dim is not a multiple of num_classes")
-                if not _dpsroi_supported(t[1] // 2, g["pooled_size"], g["sample_per_part"]):
-                    raise ValueError("DeformablePSROIPooling: %d classes with pooled_size %d and sample_per_part %d do "
-                                     "not fit the kernels' LDS (sd_deform_psroi_pool_supported)"
-                                     % (t[1] // 2, g["pooled_size"], g["sample_per_part"]))
-            o = (b[0], g["output_dim"], g["pooled_size"], g["pooled_size"])
-            return list(in_shape), [o, o]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return DeformablePSROIPooling(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [out_grad[0]] + list(in_data) + [out_data[1]]
-
-    ops["_contrib_DeformablePSROIPooling"] = (DeformablePSROIPoolingProp, ("contrib", "DeformablePSROIPooling"))
-
-    # ---- fpn_deform_roi_pool: the whole FPNRoIAlign_DeltaC / DeltaR.get_roi_feature subgraph
-    #      (models/TSD/poolings.py:51-174: fpn_roi_assign_offset -> per level DeformablePSROIPooling on masked
-    #      rois / offsets -> add_n) as ONE op: feats..., rois (B,R,4), trans (B*R,2,P,P) | (B*R,2) -> output ----
-    class FPNDeformRoIPool(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def _levels(self, feats):
-            ptrs = (ctypes.c_void_p * len(feats))(*[_ptr(f).value for f in feats])
-            return ptrs, _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
-
-        def _tail(self, feats, rois, trans):
-            g = self.g
-            B, C = feats[0].shape[:2]
-            return (B, C, rois.shape[1], g["pooled_size"], g["pooled_size"] if len(trans.shape) == 4 else 1,
-                    g["sample_per_part"], float(g["trans_std"]), float(g["scale0"]), float(g["lvl0"]), None)
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            feats, rois, trans = in_data[:-2], in_data[-2], in_data[-1]
-            _wait(*in_data)
-            ptrs, Hs, Ws = self._levels(feats)
-            _call("sd_fpn_deform_roi_pool_fwd", ptrs, Hs, Ws, _iarr(self.g["stride"]), len(feats), _ptr(rois),
-                  _ptr(trans), _ptr(out_data[0]), _ptr(out_data[1]), *self._tail(feats, rois, trans))
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            feats, rois, trans = in_data[:-2], in_data[-2], in_data[-1]
-            _wait(out_grad[0], out_data[1], *in_data)
-            rq = {_req(r) for r in req[:-2]}
-            if len(rq) != 1:
-                raise RuntimeError("fpn_deform_roi_pool: all feature gradients must share one req")
-            ptrs, Hs, Ws = self._levels(feats)
-            dptrs = self._levels(in_grad[:-2])[0]
-            _call("sd_fpn_deform_roi_pool_bwd", _ptr(out_grad[0]), ptrs, dptrs, Hs, Ws, _iarr(self.g["stride"]),
-                  len(feats), _ptr(rois), _ptr(trans), _ptr(out_data[1]), _ptr(in_grad[-1]), rq.pop(),
-                  _req(req[-1]), *self._tail(feats, rois, trans))
-            _sync()
-            self.assign(in_grad[-2], req[-2], 0)
-
-    class FPNDeformRoIPoolProp(CustomOpProp):
-        def __init__(self, rcnn_stride, pooled_size="7", sample_per_part="4", trans_std="0.1",
-                     roi_canonical_scale="224", roi_canonical_level="4"):
-            super().__init__(need_top_grad=True)
-            self.g = dict(stride=_tuple(rcnn_stride, typ=int), pooled_size=int(pooled_size),
-                          sample_per_part=int(sample_per_part), trans_std=float(trans_std),
-                          scale0=float(roi_canonical_scale), lvl0=float(roi_canonical_level))
-            g = self.g
-            if not 1 <= len(g["stride"]) <= 5:
-                raise ValueError("fpn_deform_roi_pool: 1 to 5 levels, got %d" % len(g["stride"]))
-            if not _dpsroi_supported(1, g["pooled_size"], g["sample_per_part"]):
-                raise ValueError("fpn_deform_roi_pool: pooled_size %d with sample_per_part %d does not fit the kernels' "
-                                 "LDS (sd_deform_psroi_pool_supported)" % (g["pooled_size"], g["sample_per_part"]))
-
-        def list_arguments(self):
-            return ["data_s{}".format(s) for s in self.g["stride"]] + ["rois", "trans"]
-
-        def list_outputs(self):
-            return ["output", "top_count"]
-
-        num_visible_outputs = 1
-
-        def infer_shape(self, in_shape):
-            feats, b, t = in_shape[:-2], in_shape[-2], in_shape[-1]
-            P = self.g["pooled_size"]
-            if len(feats) != len(self.g["stride"]):
-                raise ValueError("one feature map per stride expected")
-            if len(b) != 3 or b[2] != 4:
-                raise ValueError("bbox should be a 3D tensor of shape [batch, rois, 4]")
-            n = b[0] * b[1]
-            if tuple(t) not in ((n, 2, P, P), (n, 2)):
-                raise ValueError("trans should have shape (%d, 2, %d, %d) or (%d, 2), got %s" % (n, P, P, n, tuple(t)))
-            for f in feats:
-                if len(f) != 4 or tuple(f[:2]) != (b[0], feats[0][1]):
-                    raise ValueError("every level should be (batch, C, H, W)")
-            return list(in_shape), [(n, feats[0][1], P, P), (n, len(feats), P, P)]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return FPNDeformRoIPool(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [out_grad[0]] + list(in_data) + [out_data[1]]
-
-    ops["fpn_deform_roi_pool"] = (FPNDeformRoIPoolProp, None)
-
-    # ---- _contrib_Proposal_v3: cls_prob, bbox_pred, im_info -> output [, score] ----
-    class ProposalV3(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            cls_prob, bbox_pred, im_info = in_data
-            _wait(cls_prob, bbox_pred, im_info)
-            g = self.g
-            B, A2, H, W = cls_prob.shape
-            A = A2 // 2
-            wsb = lib().cdll.sd_proposal_v3_workspace_bytes(B, A, H, W, g["pre"])
-            ws = _scratch(cls_prob, wsb)
-            count = A * H * W
-            pre = min(g["pre"] if g["pre"] > 0 else count, count)
-            if g["is_train"] and g["post"] > pre:
-                # same quirk as _contrib_NMS (proposal_v3.cu:474-479,626-632): declared
-                # (B, post, .), written min(post, pre) rows per image, packed; tail zeroed here
-                self.assign(out_data[0], "write", 0)
-                self.assign(out_data[1], "write", 0)
-            fa = lambda v: (ctypes.c_float * len(v))(*v)
-            _call("sd_proposal_v3_iou" if g["iou_loss"] else "sd_proposal_v3",
-                       _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info),
-                       _ptr(out_data[0]), _ptr(out_data[1]), B, A, H, W, g["pre"], g["post"],
-                       float(g["thr"]), g["min_size"], fa(g["scales"]), len(g["scales"]),
-                       fa(g["ratios"]), len(g["ratios"]), g["stride"], int(g["is_train"]), _ptr(ws),
-                       ctypes.c_size_t(wsb), None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            for i in range(3):
-                self.assign(in_grad[i], req[i], 0)
-
-    class ProposalV3Prop(CustomOpProp):
-        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
-                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)",
-                     feature_stride="16", output_score="False", iou_loss="False", is_train="False",
-                     workspace="256"):
-            super().__init__(need_top_grad=False)
-            self.g = dict(pre=int(rpn_pre_nms_top_n), post=int(rpn_post_nms_top_n),
-                          thr=float(threshold), min_size=int(rpn_min_size), scales=_tuple(scales),
-                          ratios=_tuple(ratios), stride=int(feature_stride),
-                          is_train=_bool(is_train), iou_loss=_bool(iou_loss))  # proposal_v3.cu:536
-            self.num_visible_outputs = 2 if _bool(output_score) else 1
-
-        def list_arguments(self):
-            return ["cls_prob", "bbox_pred", "im_info"]
-
-        def list_outputs(self):
-            return ["output", "score"]
-
-        def infer_shape(self, in_shape):
-            d = in_shape[0]
-            if len(d) != 4:
-                raise ValueError("cls_prob should be (batch, 2 * num_anchors, H, W)")
-            g = self.g
-            A = d[1] // 2
-            if A != len(g["scales"]) * len(g["ratios"]):
-                raise ValueError("num_anchors != len(ratios) * len(scales)")
-            count = A * d[2] * d[3]
-            post = g["post"]  # ProposalProp_v3::InferShape (proposal_v3-inl.h:199-218)
-            return [d, (d[0], 4 * A, d[2], d[3]), (d[0], 3)], [(d[0], post, 4), (d[0], post, 1)]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return ProposalV3(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    ops["_contrib_Proposal_v3"] = (ProposalV3Prop, ("contrib", "Proposal_v3"))
-
-    # ---- _contrib_Proposal_v2 (cls_prob, bbox_pred, im_info, valid_ranges) and _contrib_Proposal
-    #      (cls_prob, bbox_pred, im_info) -> output [, score]  (registered only by install(...,
-    #      proposal=True)) ----
-    class ProposalV12(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            _wait(*in_data)
-            g = self.g
-            cls_prob, bbox_pred, im_info = in_data[:3]
-            B, A2, H, W = cls_prob.shape
-            A = A2 // 2
-            fn = "sd_proposal_v2" if g["v2"] else "sd_proposal"
-            getattr(lib().cdll, fn + "_workspace_bytes").restype = ctypes.c_size_t
-            wsb = getattr(lib().cdll, fn + "_workspace_bytes")(B, A, H, W, g["pre"])
-            ws = _scratch(cls_prob, wsb)
-            fa = lambda v: (ctypes.c_float * len(v))(*v)
-            common = (B, A, H, W, g["pre"], g["post"], float(g["thr"]), g["min_size"], fa(g["scales"]),
-                      len(g["scales"]), fa(g["ratios"]), len(g["ratios"]), g["stride"])
-            if g["v2"]:
-                _call(fn, _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(in_data[3]),
-                      _ptr(out_data[0]), _ptr(out_data[1]), *common, int(g["filter_scales"]),
-                      int(g["iou_loss"]), _ptr(ws), ctypes.c_size_t(wsb), None)
-            else:
-                _call(fn, _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(out_data[0]),
-                      _ptr(out_data[1]), *common, int(g["is_train"]), int(g["iou_loss"]), _ptr(ws),
-                      ctypes.c_size_t(wsb), None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            for i in range(len(in_grad)):  # proposal_v2.cu:617-639, proposal.cu: all zeros
-                self.assign(in_grad[i], req[i], 0)
-
-    class _ProposalV12Prop(CustomOpProp):
-        V2 = True
-
-        def _init(self, rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
-                  feature_stride, output_score, iou_loss, is_train="False", filter_scales="False"):
-            super().__init__(need_top_grad=False)
-            self.g = dict(pre=int(rpn_pre_nms_top_n), post=int(rpn_post_nms_top_n), thr=float(threshold),
-                          min_size=int(rpn_min_size), scales=_tuple(scales), ratios=_tuple(ratios),
-                          stride=int(feature_stride), iou_loss=_bool(iou_loss), is_train=_bool(is_train),
-                          filter_scales=_bool(filter_scales), v2=self.V2)
-            self.num_visible_outputs = 2 if _bool(output_score) else 1
-
-        def list_arguments(self):
-            return ["cls_prob", "bbox_pred", "im_info"] + (["valid_ranges"] if self.V2 else [])
-
-        def list_outputs(self):
-            return ["output", "score"]
-
-        def infer_shape(self, in_shape):
-            # ProposalProp(_v2)::InferShape (proposal_v2-inl.h:199-220, proposal-inl.h:199-217)
-            d = in_shape[0]
-            if len(d) != 4:
-                raise ValueError("cls_prob should be (batch, 2 * num_anchors, H, W)")
-            g = self.g
-            A = d[1] // 2
-            if A != len(g["scales"]) * len(g["ratios"]):
-                raise ValueError("num_anchors != len(ratios) * len(scales)")
-            ins = [d, (d[0], 4 * A, d[2], d[3]), (d[0], 3)] + ([(d[0], 2)] if self.V2 else [])
-            return ins, [(d[0], g["post"], 4), (d[0], g["post"], 1)]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return ProposalV12(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    class ProposalV2Prop(_ProposalV12Prop):
-        V2 = True
-
-        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
-                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16",
-                     output_score="False", iou_loss="False", workspace="256", filter_scales="False"):
-            # defaults: proposal_v2-inl.h:141-183
-            self._init(rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
-                       feature_stride, output_score, iou_loss, filter_scales=filter_scales)
-
-    class ProposalV1Prop(_ProposalV12Prop):
-        V2 = False
-
-        def __init__(self, rpn_pre_nms_top_n="6000", rpn_post_nms_top_n="300", threshold="0.7",
-                     rpn_min_size="16", scales="(4,8,16,32)", ratios="(0.5,1,2)", feature_stride="16",
-                     output_score="False", iou_loss="False", workspace="256", is_train="False"):
-            # defaults: proposal-inl.h:141-183
-            self._init(rpn_pre_nms_top_n, rpn_post_nms_top_n, threshold, rpn_min_size, scales, ratios,
-                       feature_stride, output_score, iou_loss, is_train=is_train)
-
-    ops["_contrib_Proposal_v2"] = (ProposalV2Prop, ("contrib", "Proposal_v2"))
-    ops["_contrib_Proposal"] = (ProposalV1Prop, ("contrib", "Proposal"))
-
-    # ---- _contrib_GenProposalRetina: cls_prob, bbox_pred, im_info, anchors -> output, scores ----
-    #      (registered only by install(..., retina=True))
-    class GenProposalRetina(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            cls_prob, bbox_pred, im_info, anchors = in_data
-            _wait(cls_prob, bbox_pred, im_info, anchors)
-            g = self.g
-            B, AK, H, W = cls_prob.shape
-            lib().cdll.sd_gen_proposal_retina_workspace_bytes.restype = ctypes.c_size_t
-            wsb = lib().cdll.sd_gen_proposal_retina_workspace_bytes(B, AK, H, W)
-            ws = _scratch(cls_prob, wsb)
-            fa = lambda v: (ctypes.c_float * len(v))(*v)
-            _call("sd_gen_proposal_retina", _ptr(cls_prob), _ptr(bbox_pred), _ptr(im_info), _ptr(anchors),
-                  _ptr(out_data[0]), _ptr(out_data[1]), B, AK, H, W, g["A"], g["pre"], g["min_size"],
-                  float(g["thresh"]), fa(g["mean"]), fa(g["std"]), int(g["iou_loss"]), int(g["one_hot"]),
-                  int(g["bwa"]), _ptr(ws), ctypes.c_size_t(wsb), None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            for i in range(4):  # generate_proposal_retina.cu:471-493
-                self.assign(in_grad[i], req[i], 0)
-
-    class GenProposalRetinaProp(CustomOpProp):
-        PARAMS = ("rpn_pre_nms_top_n", "rpn_min_size", "feature_stride", "num_anchors", "thresh", "anchor_mean",
-                  "anchor_std", "iou_loss", "output_one_hot", "batch_wise_anchor", "workspace")
-
-        def __init__(self, num_anchors, rpn_pre_nms_top_n="6000", rpn_min_size="16", feature_stride="16",
-                     thresh="0", anchor_mean="(0,0,0,0)", anchor_std="(1,1,1,1)", iou_loss="False",
-                     output_one_hot="True", batch_wise_anchor="False", workspace="256"):
-            # defaults: generate_proposal_retina-inl.h:62-89
-            super().__init__(need_top_grad=False)
-            why = self.sd_supports(dict(num_anchors=num_anchors, rpn_pre_nms_top_n=rpn_pre_nms_top_n,
-                                        iou_loss=iou_loss, batch_wise_anchor=batch_wise_anchor,
-                                        anchor_mean=anchor_mean, anchor_std=anchor_std))
-            if why:
-                raise ValueError("GenProposalRetina: " + why)
-            self.g = dict(A=int(num_anchors), pre=int(rpn_pre_nms_top_n), min_size=int(rpn_min_size),
-                          thresh=float(thresh), mean=_tuple(anchor_mean, 4), std=_tuple(anchor_std, 4),
-                          iou_loss=_bool(iou_loss), one_hot=_bool(output_one_hot), bwa=_bool(batch_wise_anchor))
-
-        @classmethod
-        def sd_supports(cls, params):
-            """'' when the kernels take this parameter set, else the reason (install()'s alias then falls
-            back to the native constructor)."""
-            for k in params:
-                if k not in cls.PARAMS:
-                    return "parameter %r is not one this operator takes" % k
-            try:
-                A = int(params.get("num_anchors", "0"))
-                pre = int(params.get("rpn_pre_nms_top_n", "6000"))
-                _tuple(params.get("anchor_mean", "(0,0,0,0)"), 4)
-                _tuple(params.get("anchor_std", "(1,1,1,1)"), 4)
-            except Exception as e:
-                return "unparsable parameter (%s)" % e
-            if A <= 0:
-                return "num_anchors must be > 0"
-            if not 0 < pre <= 16384:
-                return "rpn_pre_nms_top_n=%d outside 1..16384" % pre
-            # the class count is only known from the input shape: the reference reads out of bounds for
-            # K > 1 in both of these (generate_proposal_retina.cu:161-209, :383)
-            if _bool(params.get("iou_loss", "False")):
-                return "iou_loss is taken only for one class, unknown when the graph is built"
-            if _bool(params.get("batch_wise_anchor", "False")):
-                return "batch_wise_anchor is taken only for one class or one image, unknown when the graph is built"
-            return ""
-
-        def list_arguments(self):
-            return ["cls_prob", "bbox_pred", "im_info", "anchors"]
-
-        def list_outputs(self):
-            return ["output", "scores"]
-
-        def infer_shape(self, in_shape):
-            # GenProposalRetinaProp::InferShape (generate_proposal_retina-inl.h:106-140)
-            d = in_shape[0]
-            if len(d) != 4:
-                raise ValueError("cls_prob should be (batch, num_anchors * num_classes, H, W)")
-            g = self.g
-            A = g["A"]
-            if d[1] % A:
-                raise ValueError("cls_prob channels (%d) are not a multiple of num_anchors (%d)" % (d[1], A))
-            anchors = (d[0], d[2] * d[3] * A, 4) if g["bwa"] else (d[2] * d[3] * A, 4)
-            oc = d[1] // A + 1 if g["one_hot"] else 1
-            return ([d, (d[0], 4 * A, d[2], d[3]), (d[0], 3), anchors],
-                    [(d[0], g["pre"], 4), (d[0], g["pre"], oc)])
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return GenProposalRetina(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    ops["_contrib_GenProposalRetina"] = (GenProposalRetinaProp, ("contrib", "GenProposalRetina"))
+def _retina_norm_ops(mx):
+    """FocalLoss, BBoxNorm, GroupNorm, Quantization_int8"""
+    CustomOp, Op, Prop = mx.operator.CustomOp, op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- _contrib_FocalLoss / _contrib_BBoxNorm: data, label -> output ----
     #      (registered only by install(..., retina_loss=True))
     NORMALIZATION = {"null": 0, "batch": 1, "valid": 2}
 
-    def _loss_scratch(like):
-        lib().cdll.sd_focal_loss_workspace_bytes.restype = ctypes.c_size_t
-        wsb = int(lib().cdll.sd_focal_loss_workspace_bytes())
-        return _scratch(like, wsb), wsb
-
-    class FocalLoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class FocalLoss(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             data = in_data[0]
@@ -1478,13 +1391,15 @@ def _build_ops(mx):
             _wait(label, out, ograd)
             if _req(req[0]) != REQ["null"]:
                 B, nbox, nclass = out.shape
-                ws, wsb = _loss_scratch(out)
+                ws, wsp, wsn = _ws(out, "sd_focal_loss_workspace_bytes")
                 _call("sd_focal_loss_bwd", _ptr(out), _ptr(label), _ptr(ograd), _ptr(in_grad[0]), B, nbox, nclass,
-                      float(g["alpha"]), float(g["gamma"]), float(g["grad_scale"]), g["normalization"], _ptr(ws),
-                      ctypes.c_size_t(wsb), None)
+                      float(g["alpha"]), float(g["gamma"]), float(g["grad_scale"]), g["normalization"], wsp, wsn, None)
             _sync()
 
-    class FocalLossProp(CustomOpProp):
+    class FocalLossProp(Prop):
+        ARGS = ("data", "label")
+        OP = FocalLoss
+
         def __init__(self, alpha="0.25", gamma="2.0", grad_scale="1.0", normalization="null", out_grad="False",
                      workspace="256"):
             # defaults: focal_loss-inl.h:59-80.  `workspace` (MB of temporaries in the reference) is accepted and unused.
@@ -1495,12 +1410,6 @@ def _build_ops(mx):
             self.g = dict(alpha=float(alpha), gamma=float(gamma), grad_scale=float(grad_scale),
                           normalization=NORMALIZATION[normalization], out_grad=out_grad)
 
-        def list_arguments(self):
-            return ["data", "label"]
-
-        def list_outputs(self):
-            return ["output"]
-
         def infer_shape(self, in_shape):
             # FocalLossProp::InferShape (focal_loss-inl.h:258-272): data (B, nbox, nclass), label (B, nbox)
             d = in_shape[0]
@@ -1508,13 +1417,12 @@ def _build_ops(mx):
                 raise ValueError("FocalLoss: data should be (batch, box, class)")
             return [d, (d[0], d[1])], [d]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return FocalLoss(self.g)
-
         def declare_backward_dependency(self, out_grad, in_data, out_data):
             # focal_loss-inl.h:314-324
             deps = [in_data[1], out_data[0]]
             return deps + [out_grad[0]] if self.g["out_grad"] else deps
+
+    ops["_contrib_FocalLoss"] = (FocalLossProp, ("contrib", "FocalLoss"))
 
     class BBoxNorm(CustomOp):
         def forward(self, is_train, req, in_data, out_data, aux):
@@ -1526,26 +1434,24 @@ def _build_ops(mx):
             _wait(gout, label)
             if _req(req[0]) != REQ["null"]:
                 B = gout.shape[0]
-                ws, wsb = _loss_scratch(gout)
+                ws, wsp, wsn = _ws(gout, "sd_focal_loss_workspace_bytes")    # (the two losses share one size)
                 _call("sd_bbox_norm_bwd", _ptr(gout), _ptr(label), _ptr(in_grad[0]), B,
                       ctypes.c_long(_numel(gout.shape) // B if B else 0),
-                      ctypes.c_long(_numel(label.shape) // B if B else 0), _ptr(ws), ctypes.c_size_t(wsb), None)
+                      ctypes.c_long(_numel(label.shape) // B if B else 0), wsp, wsn, None)
             if len(req) > 1:
                 self.assign(in_grad[1], req[1], 0)         # :128
             _sync()
 
-    class BBoxNormProp(CustomOpProp):
+    class BBoxNormProp(Prop):
+        ARGS = ("data", "label")
+        OP, OP_ARGS = BBoxNorm, ()
+        DEPS = ((IN_DATA, 1), (OUT_GRAD, 0))  # bbox_norm-inl.h:212-217
+
         def __init__(self, normalization="null"):
             # bbox_norm-inl.h:52-65: the parameter is declared and never read by the operator
             super().__init__(need_top_grad=True)
             if normalization not in NORMALIZATION:
                 raise ValueError("BBoxNorm: normalization must be one of %s" % sorted(NORMALIZATION))
-
-        def list_arguments(self):
-            return ["data", "label"]
-
-        def list_outputs(self):
-            return ["output"]
 
         def infer_shape(self, in_shape):
             # BBoxNormProp::InferShape: data (B, 4A, npos), label (B, A * npos); the output has data's shape
@@ -1555,26 +1461,17 @@ def _build_ops(mx):
             label = tuple(in_shape[1]) if len(in_shape) > 1 and in_shape[1] else (d[0], _numel(d[1:]) // 4)
             return [d, label], [d]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return BBoxNorm()
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [in_data[1], out_grad[0]]               # bbox_norm-inl.h:212-217
+    ops["_contrib_BBoxNorm"] = (BBoxNormProp, ("contrib", "BBoxNorm"))
 
     # ---- _contrib_GroupNorm: data, gamma, beta -> output, mean, var (1 visible) ----
     #      (registered only by install(..., group_norm=True))
-    class GroupNorm(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class GroupNorm(Op):
         def _dims(self, data):
             N, C = int(data.shape[0]), int(data.shape[1])
             return N, C, (_numel(data.shape) // (N * C) if N * C else 0), self.g["num_group"]
 
-        def _ws(self, like, dims):
-            wsb = int(lib().cdll.sd_group_norm_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2]), dims[3]))
-            return _scratch(like, wsb), wsb
+        def _workspace(self, like, dims):
+            return _ws(like, "sd_group_norm_workspace_bytes", dims[0], dims[1], ctypes.c_long(dims[2]), dims[3])
 
         def forward(self, is_train, req, in_data, out_data, aux):
             # group_norm-inl.h:88-122.  mean / var are declared (N, C) and receive N * G floats (:199-200): the
@@ -1583,10 +1480,9 @@ def _build_ops(mx):
             data, gamma, beta = in_data[:3]
             _wait(data, gamma, beta)
             N, C, HxW, G = dims = self._dims(data)
-            ws, wsb = self._ws(data, dims)
+            ws, wsp, wsn = self._workspace(data, dims)
             _call("sd_group_norm_fwd", _ptr(data), _ptr(gamma), _ptr(beta), _ptr(out_data[0]), _ptr(out_data[1]),
-                  _ptr(out_data[2]), N, C, ctypes.c_long(HxW), G, float(self.g["eps"]), _ptr(ws),
-                  ctypes.c_size_t(wsb), None)
+                  _ptr(out_data[2]), N, C, ctypes.c_long(HxW), G, float(self.g["eps"]), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -1602,28 +1498,26 @@ def _build_ops(mx):
             if want_dx or want[0]:
                 # (a frozen input with trainable gamma / beta: dX goes to scratch, as the reference always writes it)
                 dx = in_grad[0] if want_dx else _scratch(data, 4 * _numel(data.shape))
-                ws, wsb = self._ws(data, dims)
+                ws, wsp, wsn = self._workspace(data, dims)
                 _call("sd_group_norm_bwd", _ptr(out_grad[0]), _ptr(data), _ptr(out_data[1]), _ptr(out_data[2]),
                       _ptr(gamma), _ptr(dx), _ptr(in_grad[1]) if want[0] else None,
-                      _ptr(in_grad[2]) if want[0] else None, N, C, ctypes.c_long(HxW), G, _ptr(ws),
-                      ctypes.c_size_t(wsb), None)
+                      _ptr(in_grad[2]) if want[0] else None, N, C, ctypes.c_long(HxW), G, wsp, wsn, None)
             _sync()
 
-    class GroupNormProp(CustomOpProp):
+    class GroupNormProp(Prop):
+        ARGS = ("data", "gamma", "beta")
+        OUTS = ("output", "mean", "var")
+        num_visible_outputs = 1
+        OP = GroupNorm
+        # group_norm-inl.h:211-220
+        DEPS = ((OUT_GRAD, 0), (OUT_DATA, 1), (OUT_DATA, 2), (IN_DATA, 0), (IN_DATA, 1))
+
         def __init__(self, num_group="32", eps="1e-5"):
             # defaults: group_norm-inl.h:70-77
             super().__init__(need_top_grad=True)
             self.g = dict(num_group=int(num_group), eps=float(eps))
             if self.g["num_group"] <= 0:
                 raise ValueError("GroupNorm: num_group must be positive, got %d" % self.g["num_group"])
-
-        def list_arguments(self):
-            return ["data", "gamma", "beta"]
-
-        def list_outputs(self):
-            return ["output", "mean", "var"]
-
-        num_visible_outputs = 1
 
         def infer_shape(self, in_shape):
             # GroupNormProp::InferShape (group_norm-inl.h:185-202): gamma / beta (C,); mean / var (N, C)
@@ -1634,13 +1528,6 @@ def _build_ops(mx):
                 raise ValueError("GroupNorm: channels (%d) are not divisible by num_group (%d)"
                                  % (d[1], self.g["num_group"]))
             return [d, (d[1],), (d[1],)], [d, (d[0], d[1]), (d[0], d[1])]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return GroupNorm(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            # group_norm-inl.h:211-220
-            return [out_grad[0], out_data[1], out_data[2], in_data[0], in_data[1]]
 
     ops["_contrib_GroupNorm"] = (GroupNormProp, ("contrib", "GroupNorm"))
     # ---- _contrib_Quantization_int8: data -> output, aux minmax ----
@@ -1664,11 +1551,10 @@ def _build_ops(mx):
                 self.state = _state["mx"].nd.array([self.q["delay_quant"], 1], ctx=data.context, dtype="int32")
             n = _numel(data.shape)
             if n and _req(req[0]) != REQ["null"]:
-                wsb = int(lib().cdll.sd_quant_int8_workspace_bytes(ctypes.c_long(n)))
-                ws = _scratch(data, wsb)
+                ws, wsp, wsn = _ws(data, "sd_quant_int8_workspace_bytes", ctypes.c_long(n))
                 _call("sd_quant_int8_fwd", _ptr(data), _ptr(out_data[0]), _ptr(minmax), _ptr(self.state),
                       ctypes.c_long(n), int(self.q["is_weight"]), int(bool(is_train)), int(self.q["fix_act_scale"]),
-                      float(self.q["ema_decay"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+                      float(self.q["ema_decay"]), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -1682,7 +1568,11 @@ def _build_ops(mx):
                       _ptr(aux[0]) if clip else None, _ptr(in_grad[0]), ctypes.c_long(n), int(clip), r, None)
             _sync()
 
-    class QuantizationInt8Prop(CustomOpProp):
+    class QuantizationInt8Prop(Prop):
+        ARGS = ("data",)
+        AUX = ("minmax",)
+        OP, OP_ARGS = QuantizationInt8, ("q",)
+        DEPS = ((OUT_GRAD, 0), (IN_DATA, 0))
         PARAMS = ("quant_mode", "is_weight", "is_weight_perchannel", "delay_quant", "ema_decay", "grad_mode",
                   "fix_act_scale")
 
@@ -1719,15 +1609,6 @@ def _build_ops(mx):
                 return "delay_quant=%d / ema_decay=%g out of range" % (delay, decay)
             return ""
 
-        def list_arguments(self):
-            return ["data"]
-
-        def list_outputs(self):
-            return ["output"]
-
-        def list_auxiliary_states(self):
-            return ["minmax"]
-
         def infer_shape(self, in_shape):
             # Quantization_int8Prop::InferShape: data of rank 2 or 4, the output has its shape, the aux is (1,)
             d = tuple(in_shape[0])
@@ -1735,203 +1616,26 @@ def _build_ops(mx):
                 raise ValueError("Quantization_int8: data should be 2D or 4D, got shape %s" % (d,))
             return [d], [d], [(1,)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return QuantizationInt8(self.q)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [out_grad[0], in_data[0]]
-
     ops["_contrib_Quantization_int8"] = (QuantizationInt8Prop, ("contrib", "Quantization_int8"))
-    ops["_contrib_FocalLoss"] = (FocalLossProp, ("contrib", "FocalLoss"))
-    ops["_contrib_BBoxNorm"] = (BBoxNormProp, ("contrib", "BBoxNorm"))
+    return ops
 
-    # ---- get_top_proposal (models/FPN/get_top_proposal.py): bbox, score -> top_n of each ----
-    class GetTopProposal(CustomOp):
-        def __init__(self, top_n):
-            super().__init__()
-            self.top_n = top_n
 
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            bbox, score = in_data
-            _wait(bbox, score)
-            _call("sd_get_top_proposal", _ptr(bbox), _ptr(score), bbox.shape[0], bbox.shape[1],
-                       self.top_n, _ptr(out_data[0]), _ptr(out_data[1]), None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            self.assign(in_grad[0], req[0], 0)
-            self.assign(in_grad[1], req[1], 0)
-
-    class GetTopProposalProp(CustomOpProp):
-        def __init__(self, top_n):
-            super().__init__(need_top_grad=False)
-            self.top_n = int(top_n)
-
-        def list_arguments(self):
-            return ["bbox", "score"]
-
-        def list_outputs(self):
-            return ["bbox", "score"]
-
-        def infer_shape(self, in_shape):
-            b = in_shape[0]
-            return in_shape, [(b[0], self.top_n, b[2]), (b[0], self.top_n, 1)]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return GetTopProposal(self.top_n)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    ops["get_top_proposal"] = (GetTopProposalProp, None)
-
-    # ---- _contrib_DecodeBBox: rois, bbox_pred, im_info -> output ----
-    class DecodeBBox(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            _require_write(req[:1], ["output"])
-            rois, pred, info = in_data
-            _wait(rois, pred, info)
-            g = self.g
-            fa = lambda v: (ctypes.c_float * 4)(*v)
-            _call("sd_decode_bbox", _ptr(rois), _ptr(pred), _ptr(info), _ptr(out_data[0]),
-                       rois.shape[0], rois.shape[1], pred.shape[2] // 4, fa(g["mean"]), fa(g["std"]),
-                       int(g["agnostic"]), int(g["xyxy"]), None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            for i in range(3):
-                self.assign(in_grad[i], req[i], 0)
-
-    class DecodeBBoxProp(CustomOpProp):
-        def __init__(self, bbox_mean="(0,0,0,0)", bbox_std="(0.1,0.1,0.2,0.2)",
-                     class_agnostic="True", bbox_decode_type="xywh"):
-            super().__init__(need_top_grad=False)
-            if bbox_decode_type not in ("xywh", "xyxy"):
-                raise ValueError("bbox_decode_type must be 'xywh' or 'xyxy'")
-            self.g = dict(mean=_tuple(bbox_mean, 4), std=_tuple(bbox_std, 4),
-                          agnostic=_bool(class_agnostic), xyxy=bbox_decode_type == "xyxy")
-
-        def list_arguments(self):
-            return ["rois", "bbox_pred", "im_info"]
-
-        def list_outputs(self):
-            return ["output"]
-
-        def infer_shape(self, in_shape):
-            d = in_shape[1]
-            out = (d[0], d[1], 4) if self.g["agnostic"] else tuple(d)
-            return in_shape, [out]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return DecodeBBox(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    ops["_contrib_DecodeBBox"] = (DecodeBBoxProp, ("contrib", "DecodeBBox"))
-
-    # ---- BboxPostProcessing (models/maskrcnn/bbox_post_processing.py:35-111): cls_score, bbox_xyxy ->
-    # post_score, post_bbox_xyxy, post_cls.  The reference's is itself a Python CustomOp reached through
-    # mx.sym.Custom, so there is no constructor to alias: patch_bbox_post rebinds the builder method ----
-    class BboxPostProcessing(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def forward(self, is_train, req, in_data, out_data, aux):
-            _no_add(req)
-            _require_write(req[:3], ["post_score", "post_bbox_xyxy", "post_cls"])
-            score, bbox = in_data
-            _wait(score, bbox)
-            g = self.g
-            B, R, K = score.shape
-            Kb = bbox.shape[2] // 4
-            wsb = lib().cdll.sd_bbox_post_processing_workspace_bytes(B, R, K, Kb, g["max_det"])
-            ws = _scratch(score, wsb)
-            _call("sd_bbox_post_processing", _ptr(score), _ptr(bbox), B, R, K, Kb, g["min_score"], g["thr"],
-                  g["max_det"], _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), _ptr(ws),
-                  ctypes.c_size_t(wsb), None)
-            _sync()
-
-        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
-            self.assign(in_grad[0], req[0], 0)
-            self.assign(in_grad[1], req[1], 0)
-
-    class BboxPostProcessingProp(CustomOpProp):
-        LIMITS = dict(rows=4096, classes=256, max_det=1024)
-
-        def __init__(self, max_det_per_image, min_det_score, nms_type, nms_thr):
-            super().__init__(need_top_grad=False)
-            # parsed as BboxPostProcessingProp.__init__ does (bbox_post_processing.py:81-86)
-            self.g = dict(max_det=int(max_det_per_image), min_score=float(min_det_score),
-                          nms_type=str(nms_type), thr=float(nms_thr))
-            if self.g["nms_type"] != "nms":
-                raise NotImplementedError("BboxPostProcessing: nms_type %r (the reference takes 'nms' only)"
-                                          % self.g["nms_type"])
-
-        @classmethod
-        def sd_supports(cls, params):
-            """'' when the kernels take this parameter set, else the reason (patch_bbox_post then hands the
-            call back to the reference's method)."""
-            try:
-                top = int(params["max_det_per_image"])
-                float(params["min_det_score"])
-                float(params["nms_thr"])
-            except Exception as e:
-                return "unparsable parameter (%s)" % e
-            if str(params.get("nms_type")) != "nms":
-                return "nms_type %r is not 'nms'" % (params.get("nms_type"),)
-            if not 0 <= top <= cls.LIMITS["max_det"]:
-                return "max_det_per_image=%d outside 0..%d" % (top, cls.LIMITS["max_det"])
-            return ""
-
-        def list_arguments(self):
-            return ["cls_score", "bbox_xyxy"]
-
-        def list_outputs(self):
-            return ["post_score", "post_bbox_xyxy", "post_cls"]
-
-        def infer_shape(self, in_shape):
-            s, b = in_shape[0], in_shape[1]
-            if len(s) != 3 or len(b) != 3:
-                raise ValueError("cls_score should be (batch, rois, classes), bbox_xyxy (batch, rois, 4 or 4 * classes)")
-            if s[1] > self.LIMITS["rows"] or s[2] > self.LIMITS["classes"] or b[2] not in (4, 4 * s[2]):
-                raise ValueError("BboxPostProcessing: cls_score %s / bbox_xyxy %s outside rois <= %d, classes <= %d, "
-                                 "boxes (.,.,4) or (.,.,4 * classes)" % (tuple(s), tuple(b), self.LIMITS["rows"],
-                                                                         self.LIMITS["classes"]))
-            top = self.g["max_det"]
-            return [s, b], [(s[0], top, 1), (s[0], top, 4), (s[0], top, 1)]
-
-        def create_operator(self, ctx, shapes, dtypes):
-            return BboxPostProcessing(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    ops["BboxPostProcessing"] = (BboxPostProcessingProp, None)
+def _mask_loss_ops(mx):
+    """SigmoidCrossEntropy, MaskLoss and the Mask Scoring R-CNN pair"""
+    Op, Prop = op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- _contrib_SigmoidCrossEntropy: data, label -> output, loss, loss_sum, count, count_sum (1 visible) and
     #      the fused MaskLoss: logits, cls, target -> output, count_sum (1 visible)
     #      (registered only by install(..., mask_loss=True)) ----
-    class SigmoidCrossEntropy(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class SigmoidCrossEntropy(Op):
         @staticmethod
         def _rows(data):
             n = int(data.shape[0])
             return n, (_numel(data.shape) // n if n else 0)
 
-        def _ws(self, like, n, k):
-            wsb = int(lib().cdll.sd_sigmoid_ce_workspace_bytes(ctypes.c_long(n), ctypes.c_long(k)))
-            return _scratch(like, wsb), wsb
+        def _workspace(self, like, n, k):
+            return _ws(like, "sd_sigmoid_ce_workspace_bytes", ctypes.c_long(n), ctypes.c_long(k))
 
         def forward(self, is_train, req, in_data, out_data, aux):
             # sigmoid_cross_entropy-inl.h:68-92: all five outputs are plain stores
@@ -1939,10 +1643,10 @@ def _build_ops(mx):
             data, label = in_data[:2]
             _wait(data, label)
             n, k = self._rows(data)
-            ws, wsb = self._ws(data, n, k)
+            ws, wsp, wsn = self._workspace(data, n, k)
             _call("sd_sigmoid_ce_fwd", _ptr(data), _ptr(label), _ptr(out_data[0]), _ptr(out_data[1]),
                   _ptr(out_data[2]), _ptr(out_data[3]), _ptr(out_data[4]), ctypes.c_long(n), ctypes.c_long(k),
-                  _ptr(ws), ctypes.c_size_t(wsb), None)
+                  wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -1953,15 +1657,21 @@ def _build_ops(mx):
             _wait(data, label)
             if _req(req[0]) != REQ["null"]:
                 n, k = self._rows(data)
-                ws, wsb = self._ws(data, n, k)
+                ws, wsp, wsn = self._workspace(data, n, k)
                 _call("sd_sigmoid_ce_bwd", _ptr(data), _ptr(label), _ptr(in_grad[0]), _ptr(out_data[3]),
-                      _ptr(out_data[4]), ctypes.c_long(n), ctypes.c_long(k), float(self.g["grad_scale"]), _ptr(ws),
-                      ctypes.c_size_t(wsb), None)
+                      _ptr(out_data[4]), ctypes.c_long(n), ctypes.c_long(k), float(self.g["grad_scale"]), wsp, wsn,
+                      None)
             if len(req) > 1:
                 self.assign(in_grad[1], req[1], 0)
             _sync()
 
-    class SigmoidCrossEntropyProp(CustomOpProp):
+    class SigmoidCrossEntropyProp(Prop):
+        ARGS = ("data", "label")
+        OUTS = ("output", "loss", "loss_sum", "count", "count_sum")
+        num_visible_outputs = 1
+        OP = SigmoidCrossEntropy
+        DEPS = ((IN_DATA, 0), (IN_DATA, 1), (OUT_DATA, 3), (OUT_DATA, 4))  # :200-206
+
         def __init__(self, grad_scale="1.0", normalization="valid"):
             # defaults: sigmoid_cross_entropy-inl.h:52-60.  `normalization` is parsed and never used by the
             # reference's operator (the division by the count always happens): accepted and unused here as well
@@ -1969,14 +1679,6 @@ def _build_ops(mx):
             if normalization not in ("null", "valid"):
                 raise ValueError("SigmoidCrossEntropy: normalization must be 'null' or 'valid'")
             self.g = dict(grad_scale=float(grad_scale), normalization=normalization)
-
-        def list_arguments(self):
-            return ["data", "label"]
-
-        def list_outputs(self):
-            return ["output", "loss", "loss_sum", "count", "count_sum"]
-
-        num_visible_outputs = 1
 
         def infer_shape(self, in_shape):
             # SigmoidCrossEntropyProp::InferShape (:152-172): out / loss_sum / count_sum (n,), loss / count as data
@@ -1989,34 +1691,23 @@ def _build_ops(mx):
             o = (d[0],)
             return [d, label], [o, d, o, d, o]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return SigmoidCrossEntropy(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [in_data[0], in_data[1], out_data[3], out_data[4]]     # :200-206
-
-    class MaskLoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class MaskLoss(Op):
         @staticmethod
         def _dims(logits):
             R, K = int(logits.shape[0]), int(logits.shape[1])
             return R, K, (_numel(logits.shape) // (R * K) if R * K else 0)
 
-        def _ws(self, like, dims):
-            wsb = int(lib().cdll.sd_mask_loss_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2])))
-            return _scratch(like, wsb), wsb
+        def _workspace(self, like, dims):
+            return _ws(like, "sd_mask_loss_workspace_bytes", dims[0], dims[1], ctypes.c_long(dims[2]))
 
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             logits, cls, target = in_data[:3]
             _wait(logits, cls, target)
             R, K, P = dims = self._dims(logits)
-            ws, wsb = self._ws(logits, dims)
+            ws, wsp, wsn = self._workspace(logits, dims)
             _call("sd_mask_loss_fwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(out_data[0]), _ptr(out_data[1]),
-                  R, K, ctypes.c_long(P), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  R, K, ctypes.c_long(P), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -2025,26 +1716,24 @@ def _build_ops(mx):
             _wait(logits, cls, target)
             if _req(req[0]) != REQ["null"]:
                 R, K, P = dims = self._dims(logits)
-                ws, wsb = self._ws(logits, dims)
+                ws, wsp, wsn = self._workspace(logits, dims)
                 _call("sd_mask_loss_bwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(in_grad[0]), R, K,
-                      ctypes.c_long(P), float(self.g["grad_scale"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+                      ctypes.c_long(P), float(self.g["grad_scale"]), wsp, wsn, None)
             for i in (1, 2):
                 if len(req) > i:
                     self.assign(in_grad[i], req[i], 0)
             _sync()
 
-    class MaskLossProp(CustomOpProp):
+    class MaskLossProp(Prop):
+        ARGS = ("logits", "cls", "target")
+        OUTS = ("output", "count_sum")
+        num_visible_outputs = 1
+        OP = MaskLoss
+        DEPS = ((IN_DATA, 0), (IN_DATA, 1), (IN_DATA, 2))
+
         def __init__(self, grad_scale="1.0"):
             super().__init__(need_top_grad=False)
             self.g = dict(grad_scale=float(grad_scale))
-
-        def list_arguments(self):
-            return ["logits", "cls", "target"]
-
-        def list_outputs(self):
-            return ["output", "count_sum"]
-
-        num_visible_outputs = 1
 
         def infer_shape(self, in_shape):
             # logits (R, K, h, w); cls R floats in any shape (the builder's mask_label is (batch, fg)); target R*h*w
@@ -2057,36 +1746,25 @@ def _build_ops(mx):
                 raise ValueError("MaskLoss: cls %s / target %s do not match logits %s" % (cls, target, d))
             return [d, cls, target], [(1,), (1,)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return MaskLoss(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [in_data[0], in_data[1], in_data[2]]
-
     ops["_contrib_SigmoidCrossEntropy"] = (SigmoidCrossEntropyProp, ("contrib", "SigmoidCrossEntropy"))
     ops["MaskLoss"] = (MaskLossProp, None)
 
     # ---- the Mask Scoring R-CNN training head (registered only by install(..., msrcnn=True)):
     #      MsrcnnMaskLoss: logits, cls, target -> output (the mask loss), mask_pred_prob (the gathered sigmoid)
     #      MaskIoULoss:    iou_pred, prob, target, ratio, cls -> output, iou_target, weight, weight_sum (1 visible) ----
-    class MsrcnnMaskLoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
-        def _ws(self, like, dims):
-            wsb = int(lib().cdll.sd_msrcnn_mask_loss_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2])))
-            return _scratch(like, wsb), wsb
+    class MsrcnnMaskLoss(Op):
+        def _workspace(self, like, dims):
+            return _ws(like, "sd_msrcnn_mask_loss_workspace_bytes", dims[0], dims[1], ctypes.c_long(dims[2]))
 
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             logits, cls, target = in_data[:3]
             _wait(logits, cls, target)
             R, K, P = dims = MaskLoss._dims(logits)
-            ws, wsb = self._ws(logits, dims)
+            ws, wsp, wsn = self._workspace(logits, dims)
             count_sum = _scratch(logits, 4)      # the reference's hidden output; nothing downstream reads it
             _call("sd_msrcnn_mask_loss_fwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(out_data[0]),
-                  _ptr(count_sum), _ptr(out_data[1]), R, K, ctypes.c_long(P), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  _ptr(count_sum), _ptr(out_data[1]), R, K, ctypes.c_long(P), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -2098,25 +1776,23 @@ def _build_ops(mx):
             _wait(logits, cls, target, d_prob)
             if _req(req[0]) != REQ["null"]:
                 R, K, P = dims = MaskLoss._dims(logits)
-                ws, wsb = self._ws(logits, dims)
+                ws, wsp, wsn = self._workspace(logits, dims)
                 _call("sd_msrcnn_mask_loss_bwd", _ptr(logits), _ptr(cls), _ptr(target), _ptr(d_prob),
-                      _ptr(in_grad[0]), R, K, ctypes.c_long(P), float(self.g["grad_scale"]), _ptr(ws),
-                      ctypes.c_size_t(wsb), None)
+                      _ptr(in_grad[0]), R, K, ctypes.c_long(P), float(self.g["grad_scale"]), wsp, wsn, None)
             for i in (1, 2):
                 if len(req) > i:
                     self.assign(in_grad[i], req[i], 0)
             _sync()
 
-    class MsrcnnMaskLossProp(CustomOpProp):
+    class MsrcnnMaskLossProp(Prop):
+        ARGS = ("logits", "cls", "target")
+        OUTS = ("output", "mask_pred_prob")
+        OP = MsrcnnMaskLoss
+        DEPS = ((OUT_GRAD, 1), (IN_DATA, 0), (IN_DATA, 1), (IN_DATA, 2))
+
         def __init__(self, grad_scale="1.0"):
             super().__init__(need_top_grad=True)
             self.g = dict(grad_scale=float(grad_scale))
-
-        def list_arguments(self):
-            return ["logits", "cls", "target"]
-
-        def list_outputs(self):
-            return ["output", "mask_pred_prob"]
 
         def infer_shape(self, in_shape):
             # as MaskLoss; mask_pred_prob is the gathered plane of every RoI: (R, h, w)
@@ -2129,17 +1805,7 @@ def _build_ops(mx):
                 raise ValueError("MsrcnnMaskLoss: cls %s / target %s do not match logits %s" % (cls, target, d))
             return [d, cls, target], [(1,), (d[0],) + d[2:]]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return MsrcnnMaskLoss(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [out_grad[1], in_data[0], in_data[1], in_data[2]]
-
-    class MaskIoULoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class MaskIoULoss(Op):
         @staticmethod
         def _dims(iou_pred, prob):
             R, K = int(iou_pred.shape[0]), int(iou_pred.shape[1])
@@ -2150,11 +1816,10 @@ def _build_ops(mx):
             iou_pred, prob, target, ratio, cls = in_data[:5]
             _wait(iou_pred, prob, target, ratio, cls)
             R, K, P = self._dims(iou_pred, prob)
-            wsb = int(lib().cdll.sd_maskiou_loss_workspace_bytes(R, K, ctypes.c_long(P)))
-            ws = _scratch(iou_pred, wsb)
+            ws, wsp, wsn = _ws(iou_pred, "sd_maskiou_loss_workspace_bytes", R, K, ctypes.c_long(P))
             _call("sd_maskiou_loss_fwd", _ptr(iou_pred), _ptr(prob), _ptr(target), _ptr(ratio), _ptr(cls),
                   _ptr(out_data[1]), _ptr(out_data[2]), _ptr(out_data[0]), _ptr(out_data[3]), R, K, ctypes.c_long(P),
-                  _ptr(ws), ctypes.c_size_t(wsb), None)
+                  wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -2172,18 +1837,16 @@ def _build_ops(mx):
                     self.assign(in_grad[i], req[i], 0)
             _sync()
 
-    class MaskIoULossProp(CustomOpProp):
+    class MaskIoULossProp(Prop):
+        ARGS = ("iou_pred", "prob", "target", "ratio", "cls")
+        OUTS = ("output", "iou_target", "weight", "weight_sum")
+        num_visible_outputs = 1
+        OP = MaskIoULoss
+        DEPS = ((IN_DATA, 0), (IN_DATA, 4), (OUT_DATA, 1), (OUT_DATA, 2), (OUT_DATA, 3))
+
         def __init__(self, grad_scale="1.0"):
             super().__init__(need_top_grad=False)
             self.g = dict(grad_scale=float(grad_scale))
-
-        def list_arguments(self):
-            return ["iou_pred", "prob", "target", "ratio", "cls"]
-
-        def list_outputs(self):
-            return ["output", "iou_target", "weight", "weight_sum"]
-
-        num_visible_outputs = 1
 
         def infer_shape(self, in_shape):
             # iou_pred (R, K); prob / target R * h * w floats; ratio and cls R floats in any shape (the builder's
@@ -2203,14 +1866,15 @@ def _build_ops(mx):
                                  % (target, ratio, cls, prob))
             return [d, prob, target, ratio, cls], [(1,), (R,), (R,), (1,)]
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return MaskIoULoss(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return [in_data[0], in_data[4], out_data[1], out_data[2], out_data[3]]
-
     ops["MsrcnnMaskLoss"] = (MsrcnnMaskLossProp, None)
     ops["MaskIoULoss"] = (MaskIoULossProp, None)
+    return ops
+
+
+def _fcos_ops(mx):
+    """the FCOS training head and test-time decode"""
+    Op, Prop = op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- the FCOS training head (registered only by install(..., fcos=True)):
     #      fcos_target: gt_bbox, im_info -> centerness, offset, cls_id (int32), state (int32[4])
@@ -2218,11 +1882,7 @@ def _build_ops(mx):
     def _fcos_strides(v):
         return _tuple(v, typ=int)
 
-    class FCOSTarget(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class FCOSTarget(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             gt, info = in_data[:2]
@@ -2230,19 +1890,22 @@ def _build_ops(mx):
             g = self.g
             N, M = int(gt.shape[0]), int(gt.shape[1])
             HW = int(out_data[0].shape[1])
-            wsb = int(lib().cdll.sd_fcos_target_workspace_bytes(N, ctypes.c_long(HW)))
-            ws = _scratch(gt, wsb)
+            ws, wsp, wsn = _ws(gt, "sd_fcos_target_workspace_bytes", N, ctypes.c_long(HW))
             _call("sd_fcos_target", _ptr(gt), _ptr(info), _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]),
                   None, _ptr(out_data[3]), N, M, g["num_classifier"], g["data_size"][0], g["data_size"][1],
                   _iarr(g["stride"]), None, None, len(g["stride"]), float(g["ignore_offset"]),
-                  float(g["ignore_label"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  float(g["ignore_label"]), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
             for i in range(len(req)):       # targets carry no gradient (the reference blocks it)
                 self.assign(in_grad[i], req[i], 0)
 
-    class FCOSTargetProp(CustomOpProp):
+    class FCOSTargetProp(Prop):
+        ARGS = ("gt_bbox", "im_info")
+        OUTS = ("centerness", "offset", "cls_id", "state")
+        OP = FCOSTarget
+
         def __init__(self, data_size, stride, num_classifier, ignore_offset="-1", ignore_label="-1"):
             super().__init__(need_top_grad=False)
             self.g = dict(data_size=_tuple(data_size, typ=int), stride=_fcos_strides(stride),
@@ -2250,12 +1913,6 @@ def _build_ops(mx):
                           ignore_label=float(ignore_label))
             if len(self.g["data_size"]) != 2 or not 1 <= len(self.g["stride"]) <= 5:
                 raise ValueError("fcos_target: data_size is (h, w) and stride has 1 to 5 entries")
-
-        def list_arguments(self):
-            return ["gt_bbox", "im_info"]
-
-        def list_outputs(self):
-            return ["centerness", "offset", "cls_id", "state"]
 
         def infer_shape(self, in_shape):
             # PreMakeFCOSGTProp.infer_shape (models/FCOS/input.py:99-107)
@@ -2271,17 +1928,7 @@ def _build_ops(mx):
             import numpy as np
             return [in_type[0]] * 2, [in_type[0], in_type[0], np.int32, np.int32], []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return FCOSTarget(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    class FCOSLoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class FCOSLoss(Op):
         def _tables(self, in_data):
             L = self.g["num_levels"]
             cls, ctr, off = in_data[:L], in_data[L:2 * L], in_data[2 * L:3 * L]
@@ -2295,11 +1942,11 @@ def _build_ops(mx):
             _wait(*in_data)
             L, N, K, hws, tab, (cls, ctr, off), (cen, offs, cid, state) = self._tables(in_data)
             g = self.g
-            wsb = int(lib().cdll.sd_fcos_loss_workspace_bytes(N, K, ctypes.c_long(sum(hws))))
-            ws, losses = _scratch(cls[0], wsb), _scratch(cls[0], 12)
+            ws, wsp, wsn = _ws(cls[0], "sd_fcos_loss_workspace_bytes", N, K, ctypes.c_long(sum(hws)))
+            losses = _scratch(cls[0], 12)
             _call("sd_fcos_loss_fwd", tab(cls), tab(ctr), tab(off), (ctypes.c_long * L)(*hws), L, _ptr(cen),
                   _ptr(offs), _ptr(cid), _ptr(state), _ptr(losses), N, K, g["alpha"], g["gamma"],
-                  float(g["ignore_offset"]), float(g["ignore_label"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  float(g["ignore_offset"]), float(g["ignore_label"]), wsp, wsn, None)
             _sync()
             for i in range(3):
                 self.assign(out_data[i], req[i], losses[i:i + 1])
@@ -2324,7 +1971,10 @@ def _build_ops(mx):
                 self.assign(in_grad[i], req[i], 0)
             _sync()
 
-    class FCOSLossProp(CustomOpProp):
+    class FCOSLossProp(Prop):
+        OUTS = ("centerness_loss", "cls_loss", "offset_loss")
+        OP = FCOSLoss
+
         def __init__(self, num_levels, alpha="0.25", gamma="2.0", ignore_offset="-1", ignore_label="-1"):
             super().__init__(need_top_grad=False)
             self.g = dict(num_levels=int(num_levels), alpha=float(alpha), gamma=float(gamma),
@@ -2336,9 +1986,6 @@ def _build_ops(mx):
             L = self.g["num_levels"]
             return (["cls_logit_%d" % i for i in range(L)] + ["centerness_logit_%d" % i for i in range(L)]
                     + ["offset_logit_%d" % i for i in range(L)] + ["centerness", "offset", "cls_id", "state"])
-
-        def list_outputs(self):
-            return ["centerness_loss", "cls_loss", "offset_loss"]
 
         def infer_shape(self, in_shape):
             L = self.g["num_levels"]
@@ -2362,9 +2009,6 @@ def _build_ops(mx):
             L = self.g["num_levels"]
             return [in_type[0]] * (3 * L + 2) + [np.int32, np.int32], [in_type[0]] * 3, []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return FCOSLoss(self.g)
-
         def declare_backward_dependency(self, out_grad, in_data, out_data):
             return list(in_data)
 
@@ -2373,11 +2017,7 @@ def _build_ops(mx):
 
     # ---- the FCOS test-time decode (registered only by install(..., fcos_decode=True)):
     #      fcos_decode: 3 * L level tensors (class logits, centerness logits, offsets) + im_info -> bbox, score, cls_id
-    class FCOSDecode(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class FCOSDecode(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             _wait(*in_data)
@@ -2388,18 +2028,20 @@ def _build_ops(mx):
             Hs, Ws = [int(c.shape[2]) for c in cls], [int(c.shape[3]) for c in cls]
             tab = lambda arrs: (ctypes.c_void_p * L)(*[_ptr(a).value for a in arrs])
             hws = (ctypes.c_long * L)(*[h * w for h, w in zip(Hs, Ws)])
-            wsb = int(lib().cdll.sd_fcos_decode_workspace_bytes(N, C, L, hws, g["pre_nms_top_n"]))
-            ws = _scratch(cls[0], wsb)
+            ws, wsp, wsn = _ws(cls[0], "sd_fcos_decode_workspace_bytes", N, C, L, hws, g["pre_nms_top_n"])
             _call("sd_fcos_decode", tab(cls), tab(ctr), tab(off), _ptr(info), _iarr(Hs), _iarr(Ws), _iarr(g["stride"]),
                   L, N, C, g["pre_nms_top_n"], float(g["pre_nms_thresh"]), int(g["input_logits"]), _ptr(out_data[0]),
-                  _ptr(out_data[1]), _ptr(out_data[2]), None, _ptr(ws), ctypes.c_size_t(wsb), None)
+                  _ptr(out_data[1]), _ptr(out_data[2]), None, wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
             for i in range(len(req)):       # the reference's CustomOps have an empty backward (utils.py:70,127)
                 self.assign(in_grad[i], req[i], 0)
 
-    class FCOSDecodeProp(CustomOpProp):
+    class FCOSDecodeProp(Prop):
+        OUTS = ("bbox", "score", "cls_id")
+        OP = FCOSDecode
+
         def __init__(self, stride, pre_nms_top_n, pre_nms_thresh, input_logits="1"):
             super().__init__(need_top_grad=False)
             self.g = dict(stride=_fcos_strides(stride), pre_nms_top_n=int(pre_nms_top_n),
@@ -2412,9 +2054,6 @@ def _build_ops(mx):
             L = self.g["num_levels"]
             return (["cls_logit_%d" % i for i in range(L)] + ["centerness_logit_%d" % i for i in range(L)]
                     + ["offset_logit_%d" % i for i in range(L)] + ["im_info"])
-
-        def list_outputs(self):
-            return ["bbox", "score", "cls_id"]
 
         def infer_shape(self, in_shape):
             L = self.g["num_levels"]
@@ -2434,13 +2073,14 @@ def _build_ops(mx):
         def infer_type(self, in_type):
             return [in_type[0]] * (3 * self.g["num_levels"] + 1), [in_type[0]] * 3, []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return FCOSDecode(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
     ops["fcos_decode"] = (FCOSDecodeProp, None)
+    return ops
+
+
+def _reppoints_ops(mx):
+    """the RepPoints training head and test-time decode"""
+    Op, Prop = op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- the RepPoints training head (registered only by install(..., reppoints=True)):
     #      reppoints_target:   L init point maps, gt_bbox, moment_transfer -> label_init, gt_init, label_refine,
@@ -2469,11 +2109,7 @@ def _build_ops(mx):
                 raise ValueError("%s: level %d should be (N, %d, H, W), got %s" % (who, i, c, sh))
         return n, sum(sh[2] * sh[3] for sh in shapes)
 
-    class RepPointsTarget(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class RepPointsTarget(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             _wait(*in_data)
@@ -2482,20 +2118,22 @@ def _build_ops(mx):
             maps, gt, mt = in_data[:L], in_data[L], in_data[L + 1]
             N, P, Hs, Ws, st = _rp_levels(g, maps)
             M = int(gt.shape[1])
-            wsb = int(lib().cdll.sd_reppoints_target_workspace_bytes(N, M, ctypes.c_long(P)))
-            ws = _scratch(gt, wsb)
+            ws, wsp, wsn = _ws(gt, "sd_reppoints_target_workspace_bytes", N, M, ctypes.c_long(P))
             tab = (ctypes.c_void_p * L)(*[_ptr(a).value for a in maps])
             _call("sd_reppoints_target", tab, Hs, Ws, st, L, _ptr(gt), _ptr(mt), _ptr(out_data[0]), _ptr(out_data[1]),
                   _ptr(out_data[2]), _ptr(out_data[3]), _ptr(out_data[4]), N, M, g["num_points"],
                   _RP_TRANSFORMS[g["transform"]], g["target_scale"], g["num_pos"], g["pos_iou_thr"], g["neg_iou_thr"],
-                  g["min_pos_iou"], _ptr(ws), ctypes.c_size_t(wsb), None)
+                  g["min_pos_iou"], wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
             for i in range(len(req)):       # targets carry no gradient (box_iou, topk and take of gt rows)
                 self.assign(in_grad[i], req[i], 0)
 
-    class RepPointsTargetProp(CustomOpProp):
+    class RepPointsTargetProp(Prop):
+        OUTS = ("label_init", "gt_init", "label_refine", "gt_refine", "state")
+        OP = RepPointsTarget
+
         def __init__(self, stride, num_points="9", transform="moment", target_scale="4", num_pos="1",
                      pos_iou_thr="0.5", neg_iou_thr="0.5", min_pos_iou="0.0"):
             super().__init__(need_top_grad=False)
@@ -2507,9 +2145,6 @@ def _build_ops(mx):
 
         def list_arguments(self):
             return ["pts_init_%d" % i for i in range(len(self.g["stride"]))] + ["gt_bbox", "moment_transfer"]
-
-        def list_outputs(self):
-            return ["label_init", "gt_init", "label_refine", "gt_refine", "state"]
 
         def infer_shape(self, in_shape):
             L = len(self.g["stride"])
@@ -2526,17 +2161,7 @@ def _build_ops(mx):
             import numpy as np
             return [in_type[0]] * len(in_type), [in_type[0]] * 4 + [np.int32], []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return RepPointsTarget(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
-    class RepPointsBoxLoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class RepPointsBoxLoss(Op):
         def _args(self, in_data):
             g = self.g
             L = len(g["stride"])
@@ -2564,17 +2189,19 @@ def _build_ops(mx):
                 if len(reqs) != 1:
                     raise RuntimeError("RepPointsBoxLoss writes every gradient in one launch: req must be the same "
                                        "('write', 'add' or 'null') for the 2 * L point maps and moment_transfer")
-                wsb = int(lib().cdll.sd_reppoints_box_loss_workspace_bytes(N, ctypes.c_long(P)))
-                ws = _scratch(pi[0], wsb)
+                ws, wsp, wsn = _ws(pi[0], "sd_reppoints_box_loss_workspace_bytes", N, ctypes.c_long(P))
                 _call("sd_reppoints_box_loss_bwd", tab(pi), tab(pr), Hs, Ws, st, L, _ptr(mt), _ptr(li), _ptr(gi),
                       _ptr(lr), _ptr(gr), _ptr(state), tab(in_grad[:L]), tab(in_grad[L:2 * L]), _ptr(in_grad[2 * L]),
                       N, g["num_points"], _RP_TRANSFORMS[g["transform"]], g["scale"], g["grad_scale_init"],
-                      g["grad_scale_refine"], reqs.pop(), _ptr(ws), ctypes.c_size_t(wsb), None)
+                      g["grad_scale_refine"], reqs.pop(), wsp, wsn, None)
             for i in range(2 * L + 1, len(req)):
                 self.assign(in_grad[i], req[i], 0)
             _sync()
 
-    class RepPointsBoxLossProp(CustomOpProp):
+    class RepPointsBoxLossProp(Prop):
+        OUTS = ("pts_init_loss", "pts_refine_loss")
+        OP = RepPointsBoxLoss
+
         def __init__(self, stride, num_points="9", transform="moment", scale="4", grad_scale_init="0.5",
                      grad_scale_refine="1.0"):
             super().__init__(need_top_grad=False)
@@ -2586,9 +2213,6 @@ def _build_ops(mx):
             L = len(self.g["stride"])
             return (["pts_init_%d" % i for i in range(L)] + ["pts_refine_%d" % i for i in range(L)]
                     + ["moment_transfer", "label_init", "gt_init", "label_refine", "gt_refine", "state"])
-
-        def list_outputs(self):
-            return ["pts_init_loss", "pts_refine_loss"]
 
         def infer_shape(self, in_shape):
             L = len(self.g["stride"])
@@ -2609,9 +2233,6 @@ def _build_ops(mx):
             import numpy as np
             return [in_type[0]] * (len(in_type) - 1) + [np.int32], [in_type[0]] * 2, []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return RepPointsBoxLoss(self.g)
-
         def declare_backward_dependency(self, out_grad, in_data, out_data):
             return list(in_data)
 
@@ -2621,11 +2242,7 @@ def _build_ops(mx):
     # ---- the RepPoints test-time decode (registered only by install(..., reppoints_decode=True)):
     #      reppoints_decode: L class logit maps, L refine point maps, im_info, moment_transfer -> cls_score (N, R, C + 1),
     #                        bbox_xyxy (N, R, 4) ----
-    class RepPointsDecode(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class RepPointsDecode(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             _no_add(req)
             _wait(*in_data)
@@ -2637,11 +2254,10 @@ def _build_ops(mx):
             tab = lambda arrs: (ctypes.c_void_p * L)(*[_ptr(a).value for a in arrs])
             hws = (ctypes.c_long * L)(*[h * w for h, w in zip(Hs, Ws)])
             ks = _iarr(_rp_topk_table(g))
-            wsb = int(lib().cdll.sd_reppoints_decode_workspace_bytes(N, C, L, hws, ks))
-            ws = _scratch(cls[0], wsb)
+            ws, wsp, wsn = _ws(cls[0], "sd_reppoints_decode_workspace_bytes", N, C, L, hws, ks)
             _call("sd_reppoints_decode", tab(cls), tab(pts), _ptr(info), _ptr(mt), _iarr(Hs), _iarr(Ws),
                   _iarr(g["stride"]), ks, L, N, C, g["num_points"], _RP_TRANSFORMS[g["transform"]],
-                  int(g["input_logits"]), _ptr(out_data[0]), _ptr(out_data[1]), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  int(g["input_logits"]), _ptr(out_data[0]), _ptr(out_data[1]), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -2652,7 +2268,10 @@ def _build_ops(mx):
         """rows kept per level (builder.py:499-502): pre_nms_top_n where the stride is <= 32, else all (-1)"""
         return [g["pre_nms_top_n"] if s <= 32 else -1 for s in g["stride"]]
 
-    class RepPointsDecodeProp(CustomOpProp):
+    class RepPointsDecodeProp(Prop):
+        OUTS = ("cls_score", "bbox_xyxy")
+        OP = RepPointsDecode
+
         def __init__(self, stride, pre_nms_top_n, transform="moment", num_points="9", input_logits="1"):
             super().__init__(need_top_grad=False)
             self.g = dict(stride=_tuple(stride, typ=int), pre_nms_top_n=int(pre_nms_top_n), transform=str(transform),
@@ -2666,9 +2285,6 @@ def _build_ops(mx):
         def list_arguments(self):
             L = len(self.g["stride"])
             return ["cls_logit_%d" % i for i in range(L)] + ["pts_refine_%d" % i for i in range(L)] + ["im_info", "moment_transfer"]
-
-        def list_outputs(self):
-            return ["cls_score", "bbox_xyxy"]
 
         def infer_shape(self, in_shape):
             g = self.g
@@ -2703,23 +2319,20 @@ def _build_ops(mx):
         def infer_type(self, in_type):
             return [in_type[0]] * (2 * len(self.g["stride"]) + 2), [in_type[0]] * 2, []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return RepPointsDecode(self.g)
-
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            return []
-
     ops["reppoints_decode"] = (RepPointsDecodeProp, None)
+    return ops
+
+
+def _crowdhuman_ops(mx):
+    """the CrowdHuman double-prediction head"""
+    Op, Prop = op_base(mx), prop_base(mx)
+    ops = {}
 
     # ---- the CrowdHuman double-prediction head (registered only by install(..., crowdhuman=True)):
     #      bbox_target:       proposal, gt_bbox -> sampled_proposal, bbox_cls, bbox_target, bbox_target_weight
     #      doublebbox_target: ... and bbox_sec_cls, bbox_sec_target, bbox_sec_target_weight
     #      emd_loss:          the two logits, labels, deltas, targets and weights -> output (1,) ----
-    class CrowdHumanTarget(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class CrowdHumanTarget(Op):
         def forward(self, is_train, req, in_data, out_data, aux):
             from . import ops as sd_ops
             _no_add(req)
@@ -2743,13 +2356,11 @@ def _build_ops(mx):
                 words = [int(k) - (1 << 32) if int(k) >= (1 << 31) else int(k) for k in st[1]] + [int(st[2])]
                 _state["rng"][key] = _state["mx"].nd.array(words, ctx=prop_.context, dtype="int32")
             rng = _state["rng"][key]
-            lib().cdll.sd_crowdhuman_target_workspace_bytes.restype = ctypes.c_size_t
-            wsb = lib().cdll.sd_crowdhuman_target_workspace_bytes(B, P, M)
-            ws = _scratch(prop_, wsb)
+            ws, wsp, wsn = _ws(prop_, "sd_crowdhuman_target_workspace_bytes", B, P, M)
             count = _scratch(prop_, 4 * B)     # rows filled per image; the reference has no such output
             outs = [_ptr(o) for o in out_data] + [None] * (7 - len(out_data))
             _call("sd_crowdhuman_target", _ptr(prop_), _ptr(gt), B, P, M, g["mode"], ctypes.byref(prm), _ptr(rng), *outs,
-                  _ptr(count), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  _ptr(count), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -2761,7 +2372,10 @@ def _build_ops(mx):
         if mode == 1:
             outputs += ["bbox_sec_cls", "bbox_sec_target", "bbox_sec_target_weight"]
 
-        class CrowdHumanTargetProp(CustomOpProp):
+        class CrowdHumanTargetProp(Prop):
+            ARGS, OUTS = ("proposal", "gt_bbox"), tuple(outputs)
+            OP = CrowdHumanTarget
+
             def __init__(self, num_class, add_gt_to_proposal, image_rois, fg_fraction, fg_thresh, bg_thresh_hi,
                          bg_thresh_lo, bbox_target_std, xywh="True"):
                 super().__init__(need_top_grad=False)
@@ -2773,12 +2387,6 @@ def _build_ops(mx):
                 if len(self.g["bbox_target_std"]) != 4 or not 1 <= self.g["image_rois"] <= 1024:
                     raise ValueError("crowdhuman target: bbox_target_std has 4 entries and image_rois is in [1, 1024]")
 
-            def list_arguments(self):
-                return ["proposal", "gt_bbox"]
-
-            def list_outputs(self):
-                return list(outputs)
-
             def infer_shape(self, in_shape):
                 p, gt = tuple(in_shape[0]), tuple(in_shape[1])
                 if len(p) != 3 or p[2] != 4 or len(gt) != 3 or gt[2] != 5 or gt[0] != p[0]:
@@ -2789,19 +2397,9 @@ def _build_ops(mx):
                 outs = [(B, S, 4), (B, S), (B, S, W), (B, S, W)]
                 return [p, gt], outs + ([(B, S), (B, S, W), (B, S, W)] if mode == 1 else []), []
 
-            def create_operator(self, ctx, shapes, dtypes):
-                return CrowdHumanTarget(self.g)
-
-            def declare_backward_dependency(self, out_grad, in_data, out_data):
-                return []
-
         return CrowdHumanTargetProp
 
-    class EmdLoss(CustomOp):
-        def __init__(self, g):
-            super().__init__()
-            self.g = g
-
+    class EmdLoss(Op):
         @staticmethod
         def _dims(in_data):
             R, K = int(in_data[0].shape[0]), int(in_data[0].shape[1])
@@ -2831,19 +2429,16 @@ def _build_ops(mx):
                     self.assign(in_grad[i], req[i], 0)
             _sync()
 
-    class EmdLossProp(CustomOpProp):
+    class EmdLossProp(Prop):
+        ARGS = ("cls_logit", "cls_sec_logit", "cls_label", "cls_sec_label", "bbox_delta", "bbox_sec_delta",
+                "bbox_target", "bbox_sec_target", "bbox_weight", "bbox_sec_weight")
+        OP = EmdLoss
+
         def __init__(self, smooth_l1_scalar="1.0", grad_scale="1.0"):
             super().__init__(need_top_grad=False)
             self.g = dict(smooth_l1_scalar=float(smooth_l1_scalar), grad_scale=float(grad_scale))
             if not self.g["smooth_l1_scalar"] > 0:
                 raise ValueError("emd_loss: smooth_l1_scalar must be positive")
-
-        def list_arguments(self):
-            return ["cls_logit", "cls_sec_logit", "cls_label", "cls_sec_label", "bbox_delta", "bbox_sec_delta",
-                    "bbox_target", "bbox_sec_target", "bbox_weight", "bbox_sec_weight"]
-
-        def list_outputs(self):
-            return ["output"]
 
         def infer_shape(self, in_shape):
             x, d = tuple(in_shape[0]), tuple(in_shape[4])
@@ -2855,9 +2450,6 @@ def _build_ops(mx):
                     raise ValueError("emd_loss: %s is %s, expected %s" % (self.list_arguments()[i], tuple(s), w))
             return [tuple(s) if s else w for w, s in zip(want, in_shape)], [(1,)], []
 
-        def create_operator(self, ctx, shapes, dtypes):
-            return EmdLoss(self.g)
-
         def declare_backward_dependency(self, out_grad, in_data, out_data):
             return list(in_data)
 
@@ -2865,6 +2457,32 @@ def _build_ops(mx):
     ops["doublebbox_target"] = (_crowdhuman_target_prop(1), None)
     ops["emd_loss"] = (EmdLossProp, None)
     return ops
+
+
+_FAMILIES = (_roi_pool_ops, _target_ops, _proposal_ops, _deform_conv_ops, _retina_norm_ops, _mask_loss_ops, _fcos_ops,
+             _reppoints_ops, _crowdhuman_ops)
+# the table's order -- the order the operators were added in: registration, aliasing and _state["table"] follow it,
+# and a new operator goes at the end
+_TABLE_ORDER = (
+    "_contrib_ROIAlign_v2", "ROIPooling_v1", "ProposalTarget", "ProposalTarget_v2", "ProposalMaskTarget",
+    "_contrib_GenAnchor", "_contrib_NMS", "assign_layer_fpn", "_contrib_DeformableConvolution", "fpn_roi_align",
+    "_contrib_DeformablePSROIPooling", "fpn_deform_roi_pool", "_contrib_Proposal_v3", "_contrib_Proposal_v2",
+    "_contrib_Proposal", "_contrib_GenProposalRetina", "_contrib_GroupNorm", "_contrib_Quantization_int8",
+    "_contrib_FocalLoss", "_contrib_BBoxNorm", "get_top_proposal", "_contrib_DecodeBBox", "BboxPostProcessing",
+    "_contrib_SigmoidCrossEntropy", "MaskLoss", "MsrcnnMaskLoss", "MaskIoULoss", "fcos_target", "fcos_loss",
+    "fcos_decode", "reppoints_target", "reppoints_box_loss", "reppoints_decode", "bbox_target", "doublebbox_target",
+    "emd_loss")
+
+
+def _build_ops(mx):
+    """{name: (PropClass, where)} of every operator, opt-in ones included: the families' tables, in _TABLE_ORDER.
+    `where` is (namespace, attribute) of the reference constructor install() aliases, or None."""
+    found = {}
+    for family in _FAMILIES:
+        found.update(family(mx))
+    if set(found) != set(_TABLE_ORDER):
+        raise RuntimeError("_TABLE_ORDER and the families disagree on %s" % sorted(set(found) ^ set(_TABLE_ORDER)))
+    return {name: found[name] for name in _TABLE_ORDER}
 
 
 # ------------------------------------------------------------------------------- registration ----
@@ -2886,16 +2504,13 @@ def register(mx=None, **features):
     if mx is None:
         import mxnet as mx  # noqa: F811  (lazy: MXNet is only needed here)
     lib()  # fail loudly now if the HIP library is missing
-    _state["mx"] = mx
     table = _build_ops(mx)
     _state["all_ops"] = {name: (None, where) for name, (_, where) in table.items()}
     for feature in _FEATURES.values():
         if not flags[feature.flag]:
             for name in feature.ops:
                 table.pop(name)
-    out = {}
-    for name, (prop, _) in table.items():
-        out[name] = mx.operator.register(_PREFIX + name)(prop)
+    out = register_ops(mx, {name: prop for name, (prop, _) in table.items()})
     _state["registered"] = True
     _state["table"] = table
     return out
@@ -2904,26 +2519,6 @@ def register(mx=None, **features):
 def _build_ops_names():
     """{name: (None, (namespace, attribute) or None)} of every operator _build_ops knows, opt-in ones included"""
     return _state.get("all_ops") or {}
-
-
-def _namespaces(mx, ns):
-    """Every namespace object the reference reaches an operator through: `mx.sym` (= `mx.symbol`) or
-    `mx.sym.contrib`, and for contrib operators also the old `mx.contrib.symbol` / `mx.contrib.sym`
-    module, which MXNet 1.x still fills with the same constructors as separate attributes
-    (models/tridentnet/resnet_v1.py:85 builds its DeformableConvolution through it)."""
-    out = []
-
-    def add(t):
-        if t is not None and all(t is not o for o in out):
-            out.append(t)
-    for root in (getattr(mx, "sym", None), getattr(mx, "symbol", None)):
-        if root is not None:
-            add(getattr(root, ns) if ns else root)
-    if ns == "contrib":
-        old = getattr(mx, "contrib", None)
-        for a in ("symbol", "sym"):
-            add(getattr(old, a, None) if old is not None else None)
-    return out
 
 
 def install(mx=None, stream=None, sync=True, **features):
@@ -2961,76 +2556,19 @@ def install(mx=None, stream=None, sync=True, **features):
     _state["fallbacks"] = []
     _state["stream"], _state["sync"] = stream, bool(sync)
 
-    def make(name, prop, original):
-        def ctor(*args, **kwargs):
-            # MXNet's generated constructors skip inputs / attributes given as None
-            # (models/sepc/sepc_dconv.py:13: `bias=bias if not no_bias else None`)
-            kwargs = {k: v for k, v in kwargs.items() if v is not None}
-            name_kw = kwargs.pop("name", None)
-            params = {k: _param_str(v) for k, v in kwargs.items() if not _is_symbol(mx, v)}
-            inputs = {k: v for k, v in kwargs.items() if _is_symbol(mx, v)}
-            supports = getattr(prop, "sd_supports", None)
-            why = supports(params) if supports is not None else ""
-            if why:
-                if original is None:
-                    raise ValueError("%s: %s (and no native constructor to fall back to)" % (name, why))
-                _state["fallbacks"].append((name, name_kw, why))
-                native = {k: v for k, v in kwargs.items() if k != "cache_col"}
-                if name_kw is not None:
-                    native["name"] = name_kw
-                return original(*args, **native)
-            p = prop(**params)
-            if args and inputs:
-                # MXNet composes a variadic operator (Custom is `*data`) from positional OR keyword Symbols, never
-                # both (Symbol._compose raises TypeError) -- and the reference mixes them for the built-in it
-                # believes it is calling (models/sepc/sepc_dconv.py:12-16: DeformableConvolution(x, offset,
-                # weight=weight, bias=bias, ...)): positional inputs take the operator's argument names in order
-                names = list(p.list_arguments())
-                if len(args) > len(names):
-                    raise TypeError("%s takes %d inputs (%s), %d given positionally" % (name, len(names), names, len(args)))
-                for k, v in zip(names, args):
-                    if k in inputs:
-                        raise TypeError("%s: input '%s' given positionally and by keyword" % (name, k))
-                    inputs[k] = v
-                # keyword composition matches by name; keep the operator's own order for readability of the graph
-                inputs = {k: inputs[k] for k in names if k in inputs} | {k: v for k, v in inputs.items() if k not in names}
-                args = ()
-            sym = mx.sym.Custom(*args, op_type=_PREFIX + name, name=name_kw, **inputs, **params)
-            nvis = getattr(p, "num_visible_outputs", len(p.list_outputs()))
-            nout = len(p.list_outputs())
-            if nvis == nout:
-                return sym
-            return sym[0] if nvis == 1 else mx.sym.Group([sym[i] for i in range(nvis)])
-        ctor.__name__ = name
-        ctor._sd_alias = True
-        ctor._sd_original = original
-        return ctor
+    def record(*fallback):
+        _state["fallbacks"].append(fallback)
 
-    for name, (prop, where) in _state["table"].items():
-        if where is None:
-            continue
-        ns, attr = where
-        for target in _namespaces(mx, ns):
-            cur = getattr(target, attr, None)
-            # a second install(): the first one's original stays the original
-            original = cur._sd_original if getattr(cur, "_sd_alias", False) else cur
-            setattr(target, attr, make(name, props[name], original))
-            setattr(target, "_sd_reference_" + attr, original)
+    for name, (_, where) in _state["table"].items():
+        if where is not None:
+            # (cache_col is this adapter's own attribute of DeformableConvolution: no native constructor sees it)
+            put_alias(mx, *where, lambda original: alias_ctor(mx, name, props[name], original, record,
+                                                              native_drop=("cache_col",)))
     # an alias an earlier opt-in install() left for an operator that is not in the table now: the constructor it
     # replaced is put back
     for name, (_, where) in _build_ops_names().items():
-        if where is None or name in _state["table"]:
-            continue
-        ns, attr = where
-        for target in _namespaces(mx, ns):
-            cur = getattr(target, "__dict__", {}).get(attr)
-            if getattr(cur, "_sd_alias", False):
-                if cur._sd_original is None:
-                    delattr(target, attr)
-                else:
-                    setattr(target, attr, cur._sd_original)
-                if "_sd_reference_" + attr in getattr(target, "__dict__", {}):
-                    delattr(target, "_sd_reference_" + attr)
+        if where is not None and name not in _state["table"]:
+            drop_alias(mx, *where)
     # the fused FPN extractor has no single reference symbol to alias: rebind the builder method
     # that emits the subgraph (no reference file is edited)
     _state["fpn_patched"] = patch_fpn_roi_align(mx=mx)
@@ -3871,20 +3409,3 @@ def patch_fpn_roi_align(builder_module=None, mx=None):
     cls.get_roi_feature = get_roi_feature
     cls._sd_patched = True
     return True
-
-
-def _param_str(v):
-    """keyword argument -> the string MXNet's front end would send (str(value)); numpy scalars
-    are unwrapped first (numpy 2 prints np.float32(0.25) for repr)."""
-    if isinstance(v, str):
-        return v
-    if isinstance(v, (tuple, list)):
-        return "(" + ", ".join(_param_str(x) for x in v) + ("," if len(v) == 1 else "") + ")"
-    if hasattr(v, "item") and not isinstance(v, (bool, int, float)):
-        v = v.item()
-    return repr(v) if isinstance(v, float) else str(v)
-
-
-def _is_symbol(mx, v):
-    sym_t = getattr(getattr(mx, "sym", None), "Symbol", None)
-    return sym_t is not None and isinstance(v, sym_t)

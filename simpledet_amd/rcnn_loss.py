@@ -17,33 +17,21 @@ concats per tensor.  This module
 Left to the reference: heads that override get_loss themselves (Cascade R-CNN, TridentNet, the OHEM and
 mask-rcnn variants in symbol/component.py) and the FPN head with `nnvm_rpn_target` (its labels come from a
 compiled graph).  Like merged_bn it stays out of mxnet_plugin's tables: it is no flag of `mxnet_plugin.install()`,
-and borrows only the plugin's helpers (pointer path, stream / sync state).  `import mxnet` happens inside the
-entry points.
+and shares only what _mx_adapter.py holds (pointer path, stream / sync state) and the plugin's fallback record.
+`import mxnet` happens inside the entry points.
 """
 import ctypes
 import importlib
 
-from . import mxnet_plugin as _plugin
-from ._lib import lib
-from .mxnet_plugin import REQ, _bool, _call, _no_add, _param_str, _ptr, _req, _require_write, _scratch, _sync, _wait
+from ._mx_adapter import REQ, _PREFIX, _bool, _call, _mx, _no_add, _numel, _param_str, _ptr, _req, _require_write, \
+    _scratch, _state, _sync, _table, _wait, _ws, prop_base, register_ops
+from .mxnet_plugin import _fell_back
 
-_PREFIX = "sd_"
 OPS = ("rpn_cls_loss", "rpn_reg_loss", "bbox_cls_loss", "bbox_reg_loss")
 # (module, class, method) of the builders patch_builders() rebinds
 METHODS = (("symbol.builder", "RpnHead", "get_loss"), ("models.FPN.builder", "FPNRpnHead", "get_loss"),
            ("symbol.builder", "BboxHead", "get_loss"))
 _own = {"installed": False, "props": {}}
-
-
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= int(s)
-    return n
-
-
-def _table(arrs):
-    return (ctypes.c_void_p * len(arrs))(*[_ptr(a).value for a in arrs])
 
 
 def _softmax_opts(what, normalization, want, smooth_alpha, out_grad):
@@ -55,7 +43,7 @@ def _softmax_opts(what, normalization, want, smooth_alpha, out_grad):
 
 # ---------------------------------------------------------------------------------- operators ----
 def _build_ops(mx):
-    CustomOp, CustomOpProp = mx.operator.CustomOp, mx.operator.CustomOpProp
+    CustomOp, Prop = mx.operator.CustomOp, prop_base(mx)
 
     class _Loss(CustomOp):
         """one half of a head: n_grad leading inputs get gradients, the rest (labels, targets, weights) zeros"""
@@ -104,13 +92,12 @@ def _build_ops(mx):
             _wait(*in_data)
             levels, N, A, hws, HW = self._dims(in_data)
             self.state = _scratch(levels[0], 16)
-            wsb = int(lib().cdll.sd_rpn_loss_workspace_bytes(N, A, ctypes.c_long(HW)))
-            ws = _scratch(levels[0], wsb)
+            ws, wsp, wsn = _ws(levels[0], "sd_rpn_loss_workspace_bytes", N, A, ctypes.c_long(HW))
             tabs, fixed = self._inputs(in_data)
             out = _ptr(out_data[0]) if _req(req[0]) != REQ["null"] else None
             _call("sd_rpn_loss_fwd", tabs[0], tabs[1], hws, len(levels), *fixed, N, A, float(self.g["ignore_label"]),
                   float(self.g["sigma"]), None if self.box else out, out if self.box else None, _ptr(self.state),
-                  _ptr(ws), ctypes.c_size_t(wsb), None)
+                  wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -142,11 +129,10 @@ def _build_ops(mx):
             _wait(*in_data)
             ptrs, R, K, D = self._args(in_data)
             self.state = _scratch(in_data[0], 16)
-            wsb = int(lib().cdll.sd_rcnn_loss_workspace_bytes(R))
-            ws = _scratch(in_data[0], wsb)
+            ws, wsp, wsn = _ws(in_data[0], "sd_rcnn_loss_workspace_bytes", R)
             out = _ptr(out_data[0]) if _req(req[0]) != REQ["null"] else None
             _call("sd_rcnn_loss_fwd", *ptrs, R, K, D, float(self.g["sigma"]), None if self.box else out,
-                  out if self.box else None, _ptr(self.state), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  out if self.box else None, _ptr(self.state), wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -159,14 +145,11 @@ def _build_ops(mx):
                   None if self.box else g, g if self.box else None, None)
             self._finish(req, in_grad)
 
-    class _Prop(CustomOpProp):
+    class _Prop(Prop):
         what = ""
 
         def __init__(self):
             super().__init__(need_top_grad=False)
-
-        def list_outputs(self):
-            return ["output"]
 
         def declare_backward_dependency(self, out_grad, in_data, out_data):
             return list(in_data)
@@ -239,15 +222,12 @@ def _build_ops(mx):
             return RpnLoss(self.g, box=True)
 
     class BboxClsLossProp(_Prop):
-        what = "bbox_cls_loss"
+        what, ARGS = "bbox_cls_loss", ("cls_logit", "cls_label")
 
         def __init__(self, grad_scale="1.0", normalization="batch", smooth_alpha="0", out_grad="False"):
             super().__init__()
             _softmax_opts(self.what, normalization, "batch", smooth_alpha, out_grad)
             self.g = dict(grad_scale=float(grad_scale), sigma=1.0)
-
-        def list_arguments(self):
-            return ["cls_logit", "cls_label"]
 
         def infer_shape(self, in_shape):
             x = tuple(int(s) for s in in_shape[0])
@@ -259,16 +239,13 @@ def _build_ops(mx):
             return RcnnLoss(self.g, box=False)
 
     class BboxRegLossProp(_Prop):
-        what = "bbox_reg_loss"
+        what, ARGS = "bbox_reg_loss", ("bbox_delta", "bbox_target", "bbox_weight")
 
         def __init__(self, grad_scale="1.0", scalar="1.0"):
             super().__init__()
             self.g = dict(grad_scale=float(grad_scale), sigma=float(scalar))
             if not self.g["sigma"] > 0:
                 raise ValueError("bbox_reg_loss: scalar must be positive")
-
-        def list_arguments(self):
-            return ["bbox_delta", "bbox_target", "bbox_weight"]
 
         def infer_shape(self, in_shape):
             d = tuple(int(s) for s in in_shape[0])
@@ -284,23 +261,10 @@ def _build_ops(mx):
 
 
 # ------------------------------------------------------------------------------- registration ----
-def _mx(mx=None):
-    if mx is not None:
-        return mx
-    if _plugin._state.get("mx") is not None:
-        return _plugin._state["mx"]
-    import mxnet  # (lazy: MXNet is only needed here)
-    return mxnet
-
-
 def register(mx=None):
     """Register the four CustomOps.  Returns {name: PropClass}."""
     mx = _mx(mx)
-    lib()  # fail loudly now if the HIP library is missing
-    _plugin._state["mx"] = mx
-    props = {name: mx.operator.register(_PREFIX + name)(prop) for name, prop in _build_ops(mx).items()}
-    _own["props"] = props
-    return props
+    return register_ops(mx, _build_ops(mx), _own)
 
 
 def install(mx=None, stream=None, sync=True):
@@ -308,7 +272,7 @@ def install(mx=None, stream=None, sync=True):
     changes only with patch_builders()."""
     mx = _mx(mx)
     props = register(mx)
-    _plugin._state["stream"], _plugin._state["sync"] = stream, bool(sync)
+    _state["stream"], _state["sync"] = stream, bool(sync)
     _own["installed"] = True
     return props
 
@@ -348,7 +312,7 @@ def _methods(mx, modules, originals):
         p = self.p
         if p.nnvm_rpn_target:
             # the labels come out of a compiled graph that wants the reference's reshaped tensors: left as it is
-            _plugin._fell_back("rpn_cls_loss", "nnvm_rpn_target builds its own label graph")
+            _fell_back("rpn_cls_loss", "nnvm_rpn_target builds its own label graph")
             return originals[1](self, conv_fpn_feat, gt_bbox, im_info)
         X = X_of(modules[1])
         cls_logit_dict, bbox_delta_dict = self.get_output(conv_fpn_feat)

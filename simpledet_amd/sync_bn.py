@@ -19,35 +19,18 @@ defaults are those of sync_batch_norm-inl.h:49-76,556-662.
   * gamma is never written: under fix_gamma the reference stores ones into it (:320), this operator reads 1.
 
 It stays out of mxnet_plugin's tables on purpose, like merged_bn.py: it is no flag of `mxnet_plugin.install()`, and
-borrows only the plugin's helpers (the pointer path, the stream / sync state -- one state for both).
+shares only what _mx_adapter.py holds (the pointer path, the alias path, the stream / sync state -- one state for both).
 """
 import ctypes
 
-from . import mxnet_plugin as _plugin
 from ._lib import lib
-from .mxnet_plugin import REQ, _call, _is_symbol, _namespaces, _no_add, _param_str, _ptr, _req, _require_write, \
-    _scratch, _sync, _wait
+from ._mx_adapter import IN_DATA, OUT_DATA, OUT_GRAD, REQ, _bool, _call, _is_f16, _mx, _no_add, _numel, _ptr, _req, \
+    _require_write, _scratch, _state, _stream, _sync, _wait, _ws, alias_ctor, drop_alias, prop_base, put_alias, \
+    register_ops
 
-_PREFIX = "sd_"
 SYNC_BN = "_contrib_SyncBatchNorm"
 _own = {"installed": False, "props": {}}
 fallbacks = []      # (operator, node name, why) of every call install()'s alias handed to the native constructor
-
-
-def _bool(v):
-    return v.strip().lower() in ("1", "true", "yes") if isinstance(v, str) else bool(v)
-
-
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= int(s)
-    return n
-
-
-def _is_f16(dtypes):
-    import numpy as np
-    return bool(dtypes) and dtypes[0] is not None and np.dtype(dtypes[0]) == np.float16
 
 
 def _as_torch(nd):
@@ -71,7 +54,7 @@ class _Holder:
 
 
 def _build_ops(mx):
-    CustomOp, CustomOpProp = mx.operator.CustomOp, mx.operator.CustomOpProp
+    CustomOp, Prop = mx.operator.CustomOp, prop_base(mx)
 
     class SyncBatchNorm(CustomOp):
         def __init__(self, p, f16):
@@ -86,9 +69,8 @@ def _build_ops(mx):
             return N, C, (_numel(shape) // (N * C) if N * C else 0)
 
         @staticmethod
-        def _ws(like, dims):
-            wsb = int(lib().cdll.sd_sync_bn_workspace_bytes(dims[0], dims[1], ctypes.c_long(dims[2])))
-            return _scratch(like, wsb), wsb
+        def _workspace(like, dims):
+            return _ws(like, "sd_sync_bn_workspace_bytes", dims[0], dims[1], ctypes.c_long(dims[2]))
 
         def _exchange(self, part):
             """part (2, C) on the device -> (the array holding parts (W, 2, C), W, rank)"""
@@ -102,7 +84,7 @@ def _build_ops(mx):
                 raise RuntimeError("SyncBatchNorm: ndev=%d, but the initialised process group has %d rank(s)"
                                    % (ndev, world))
             # the statistics kernel ran on the adapter's stream, the collective runs on torch's
-            lib().call("sd_stream_synchronize", _plugin._stream())
+            lib().call("sd_stream_synchronize", _stream())
             parts, rank = dist.all_gather_stats(_as_torch(part).reshape(2, -1))
             if parts.is_cuda:
                 import torch
@@ -122,14 +104,13 @@ def _build_ops(mx):
                       _ptr(out_data[0]), N, C, ctypes.c_long(HxW), float(self.p["eps"]), fix, None)
                 _sync()
                 return
-            ws, wsb = self._ws(data, dims)
+            ws, wsp, wsn = self._workspace(data, dims)
             part = _scratch(data, 4 * 2 * C)
-            _call("sd_sync_bn_stats" + self.sfx, _ptr(data), _ptr(part), N, C, ctypes.c_long(HxW), _ptr(ws),
-                  ctypes.c_size_t(wsb), None)
+            _call("sd_sync_bn_stats" + self.sfx, _ptr(data), _ptr(part), N, C, ctypes.c_long(HxW), wsp, wsn, None)
             parts, W, _ = self._exchange(part)
             _call("sd_sync_bn_apply" + self.sfx, _ptr(data), _ptr(parts), W, _ptr(gamma), _ptr(beta),
                   _ptr(out_data[0]), _ptr(out_data[1]), _ptr(out_data[2]), N, C, ctypes.c_long(HxW),
-                  float(self.p["eps"]), fix, _ptr(ws), ctypes.c_size_t(wsb), None)
+                  float(self.p["eps"]), fix, wsp, wsn, None)
             _sync()
 
         def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -144,10 +125,10 @@ def _build_ops(mx):
             N, C, HxW = dims = self._dims(data.shape)
             want_dx = _req(req[0]) != REQ["null"]
             want_g, want_b = [_req(r) != REQ["null"] for r in req[1:3]]
-            ws, wsb = self._ws(data, dims)
+            ws, wsp, wsn = self._workspace(data, dims)
             bpart = _scratch(data, 4 * 2 * C)
             _call("sd_sync_bn_bwd_stats" + self.sfx, _ptr(dy), _ptr(data), _ptr(mean), _ptr(bpart), N, C,
-                  ctypes.c_long(HxW), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  ctypes.c_long(HxW), wsp, wsn, None)
             bparts, W, rank = self._exchange(bpart)
             # (a frozen input: dX goes to scratch; the moving statistics move whatever is frozen)
             dx = in_grad[0] if want_dx else _scratch(data, self.esz * _numel(data.shape))
@@ -158,10 +139,12 @@ def _build_ops(mx):
             _call("sd_sync_bn_bwd_apply" + self.sfx, _ptr(dy), _ptr(data), _ptr(mean), _ptr(var), _ptr(gamma),
                   _ptr(bparts), W, rank, _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(mmean), _ptr(mvar),
                   float(self.p["momentum"]), N, C, ctypes.c_long(HxW), float(self.p["eps"]),
-                  int(self.p["fix_gamma"]), _ptr(ws), ctypes.c_size_t(wsb), None)
+                  int(self.p["fix_gamma"]), wsp, wsn, None)
             _sync()
 
-    class SyncBatchNormProp(CustomOpProp):
+    class SyncBatchNormProp(Prop):
+        ARGS, OUTS, AUX = ("data", "gamma", "beta"), ("output", "mean", "var"), ("moving_mean", "moving_var")
+        DEPS = ((OUT_GRAD, 0), (OUT_DATA, 1), (OUT_DATA, 2), (IN_DATA, 0), (IN_DATA, 1))      # :624-634
         PARAMS = ("eps", "momentum", "fix_gamma", "use_global_stats", "output_mean_var", "ndev", "key")
 
         def __init__(self, eps="1e-3", momentum="0.9", fix_gamma="True", use_global_stats="False",
@@ -189,15 +172,6 @@ def _build_ops(mx):
                 return "use_global_stats=True (its backward is not provided)"
             return ""
 
-        def list_arguments(self):
-            return ["data", "gamma", "beta"]
-
-        def list_outputs(self):
-            return ["output", "mean", "var"]
-
-        def list_auxiliary_states(self):
-            return ["moving_mean", "moving_var"]
-
         def infer_shape(self, in_shape):
             # SyncBatchNormProp::InferShape (:556-574)
             d = tuple(int(s) for s in in_shape[0])
@@ -216,67 +190,21 @@ def _build_ops(mx):
         def create_operator(self, ctx, shapes, dtypes):
             return SyncBatchNorm(self.p, _is_f16(dtypes))
 
-        def declare_backward_dependency(self, out_grad, in_data, out_data):
-            # :624-634
-            return [out_grad[0], out_data[1], out_data[2], in_data[0], in_data[1]]
-
     return {SYNC_BN: SyncBatchNormProp}
 
 
 # ------------------------------------------------------------------------------- registration ----
-def _mx(mx=None):
-    if mx is not None:
-        return mx
-    if _plugin._state.get("mx") is not None:
-        return _plugin._state["mx"]
-    import mxnet  # (lazy: MXNet is only needed here)
-    return mxnet
-
-
 def register(mx=None):
     """Register `sd__contrib_SyncBatchNorm`.  Returns {name: PropClass}."""
     mx = _mx(mx)
-    lib()  # fail loudly now if the HIP library is missing
-    _plugin._state["mx"] = mx
-    props = {name: mx.operator.register(_PREFIX + name)(prop) for name, prop in _build_ops(mx).items()}
-    _own["props"] = props
-    return props
+    return register_ops(mx, _build_ops(mx), _own)
 
 
 def _ctor(mx, prop, original):
-    def SyncBatchNorm(*args, **kwargs):
-        kwargs = {k: v for k, v in kwargs.items() if v is not None}
-        name = kwargs.pop("name", None)
-        params = {k: _param_str(v) for k, v in kwargs.items() if not _is_symbol(mx, v)}
-        inputs = {k: v for k, v in kwargs.items() if _is_symbol(mx, v)}
-        why = prop.sd_supports(params)
-        if why:
-            if original is None:
-                raise ValueError("SyncBatchNorm: %s (and no native constructor to fall back to)" % why)
-            fallbacks.append((SYNC_BN, name, why))
-            native = dict(kwargs)
-            if name is not None:
-                native["name"] = name
-            return original(*args, **native)
-        p = prop(**params)
-        names = p.list_arguments() + p.list_auxiliary_states()
-        if len(args) > len(names):
-            raise TypeError("SyncBatchNorm takes %d inputs (%s), %d given positionally" % (len(names), names, len(args)))
-        for k, v in zip(names, args):
-            if k in inputs:
-                raise TypeError("SyncBatchNorm: input '%s' given positionally and by keyword" % k)
-            inputs[k] = v
-        unknown = [k for k in inputs if k not in names]
-        if unknown:
-            raise TypeError("SyncBatchNorm: unknown inputs %s" % unknown)
-        inputs = {k: inputs[k] for k in names if k in inputs}
-        sym = mx.sym.Custom(op_type=_PREFIX + SYNC_BN, name=name, **inputs, **params)
-        if p.num_visible_outputs == 1:
-            return sym[0]
-        return mx.sym.Group([sym[i] for i in range(3)])
-    SyncBatchNorm._sd_alias = True
-    SyncBatchNorm._sd_original = original
-    return SyncBatchNorm
+    """the alias of `SyncBatchNorm`: the moving statistics are inputs too, every positional input is named, and an
+    input the operator does not have is an error"""
+    return alias_ctor(mx, SYNC_BN, prop, original, lambda *fallback: fallbacks.append(fallback), label="SyncBatchNorm",
+                      aux_inputs=True, positionals="always", unknown_inputs="error", group_all=True)
 
 
 def install(mx=None, stream=None, sync=True):
@@ -285,13 +213,9 @@ def install(mx=None, stream=None, sync=True):
     are the plugin's (mxnet_plugin.install has the ordering contract)."""
     mx = _mx(mx)
     props = register(mx)
-    _plugin._state["stream"], _plugin._state["sync"] = stream, bool(sync)
+    _state["stream"], _state["sync"] = stream, bool(sync)
     del fallbacks[:]
-    for target in _namespaces(mx, "contrib"):
-        cur = getattr(target, "SyncBatchNorm", None)
-        original = cur._sd_original if getattr(cur, "_sd_alias", False) else cur     # a second install() keeps the first
-        setattr(target, "SyncBatchNorm", _ctor(mx, props[SYNC_BN], original))
-        setattr(target, "_sd_reference_SyncBatchNorm", original)
+    put_alias(mx, "contrib", "SyncBatchNorm", lambda original: _ctor(mx, props[SYNC_BN], original))
     _own["installed"] = True
     return props
 
@@ -299,14 +223,5 @@ def install(mx=None, stream=None, sync=True):
 def uninstall(mx=None):
     """Put the native `SyncBatchNorm` constructors back.  (MXNet has no way to drop a registered CustomOp: the op
     type stays known, and nothing builds it any more.)"""
-    mx = _mx(mx)
-    for target in _namespaces(mx, "contrib"):
-        cur = getattr(target, "__dict__", {}).get("SyncBatchNorm")
-        if getattr(cur, "_sd_alias", False):
-            if cur._sd_original is None:
-                delattr(target, "SyncBatchNorm")
-            else:
-                setattr(target, "SyncBatchNorm", cur._sd_original)
-        if "_sd_reference_SyncBatchNorm" in getattr(target, "__dict__", {}):
-            delattr(target, "_sd_reference_SyncBatchNorm")
+    drop_alias(_mx(mx), "contrib", "SyncBatchNorm")
     _own["installed"] = False
