@@ -5,6 +5,7 @@ the boundary.  There is NO CPU fallback: if the shared library is missing or a s
 import fails loudly.
 """
 import ctypes
+import operator
 import os
 import re
 
@@ -26,6 +27,53 @@ _SCALARS = {
     "uint64_t": ctypes.c_uint64,
     "unsigned": ctypes.c_uint,
 }
+
+
+_FLOATS = (ctypes.c_float, ctypes.c_double)
+_INTS = tuple(set(_SCALARS.values()) - set(_FLOATS))
+
+
+class _Bound:
+    """One symbol, bound: the foreign function and its marshalling, laid out once from the prototype -- which
+    parameters are pointers, which floats, which integers (`const char*` needs nothing).  Calling it converts
+    each argument by its parameter's kind and makes the foreign call:
+      pointer   anything with data_ptr() (a tensor; duck-typed, this module needs no torch) becomes its address;
+                None stays NULL; everything else -- an int, a c_void_p, a ctypes array, a byref -- passes as it is
+      float     float(v)
+      integer   an int passes; anything else goes through __index__ (numpy / torch integer scalars, bools), so
+                a float is refused with TypeError
+    A ctypes scalar (c_size_t(n), c_float(x), ...) passes through the last two untouched.  The slots are walked
+    kind by kind, inline: a Python-level converter call per argument cost the 21-argument forward 1.3 us."""
+    __slots__ = ("name", "fn", "names", "pointers", "floats", "ints", "stream")
+
+    def __init__(self, name, fn, args):
+        self.name, self.fn = name, fn
+        self.names = tuple(n for n, _ in args)
+        self.pointers = tuple(i for i, (_, t) in enumerate(args) if t is ctypes.c_void_p)
+        self.floats = tuple(i for i, (_, t) in enumerate(args) if t in _FLOATS)
+        self.ints = tuple(i for i, (_, t) in enumerate(args) if t in _INTS)
+        self.stream = bool(args) and args[-1] == ("stream", ctypes.c_void_p)
+
+    def __call__(self, args):
+        if len(args) != len(self.names):
+            raise TypeError("%s takes %d arguments (%s), got %d"
+                            % (self.name, len(self.names), ", ".join(self.names), len(args)))
+        a = list(args)
+        for i in self.pointers:
+            v = a[i]
+            if v is not None:
+                ptr = getattr(v, "data_ptr", None)
+                if ptr is not None:
+                    a[i] = ptr()
+        for i in self.floats:
+            v = a[i]
+            if v.__class__ is not float and not isinstance(v, ctypes._SimpleCData):
+                a[i] = float(v)
+        for i in self.ints:
+            v = a[i]
+            if v.__class__ is not int and not isinstance(v, ctypes._SimpleCData):
+                a[i] = operator.index(v)
+        return self.fn(*a)
 
 
 def parse_header(path=HEADER):
@@ -72,7 +120,12 @@ SD_ERR_UNSUPPORTED = -2
 
 
 class _Lib:
-    def __init__(self):
+    def __init__(self, cdll=None):
+        """cdll: a library that is loaded already (the marshaller's test binds a recording stand-in);
+        None loads LIB_PATH and checks its ABI version."""
+        if cdll is not None:
+            self._bind(cdll)
+            return
         if not os.path.exists(LIB_PATH):
             raise ImportError(
                 "simpledet_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; "
@@ -84,16 +137,7 @@ class _Lib:
             import torch  # noqa: F401
         except Exception:  # pragma: no cover - torch is optional for pure-C users
             pass
-        self.cdll = ctypes.CDLL(LIB_PATH)
-        self.protos = parse_header()
-        for name, (restype, args) in self.protos.items():
-            try:
-                fn = getattr(self.cdll, name)
-            except AttributeError as e:
-                raise ImportError("simpledet_amd: %s does not export %s (header/library mismatch)"
-                                  % (LIB_PATH, name)) from e
-            fn.restype = restype
-            fn.argtypes = [t for _, t in args]
+        self._bind(ctypes.CDLL(LIB_PATH))
         # buffer layouts and size contracts are part of the ABI: a library older or newer than the
         # header this wrapper marshals for is refused
         want = header_abi_version()
@@ -102,15 +146,41 @@ class _Lib:
             raise ImportError("simpledet_amd: %s has ABI version %d, include/simpledet_ops.h %d: rebuild "
                               "(`make -C simpledet_amd/csrc`)" % (LIB_PATH, got, want))
 
-    def call(self, name, *args):
-        """Call an int-returning entry point; raise SimpleDetOpsError on a non-zero code."""
-        rc = getattr(self.cdll, name)(*args)
+    def _bind(self, cdll):
+        """restype, argtypes and the marshalling (_Bound) of every symbol, all from the header's prototypes"""
+        self.cdll = cdll
+        self.protos = parse_header()
+        self.bound = {}
+        for name, (restype, args) in self.protos.items():
+            try:
+                fn = getattr(cdll, name)
+            except AttributeError as e:
+                raise ImportError("simpledet_amd: %s does not export %s (header/library mismatch)"
+                                  % (LIB_PATH, name)) from e
+            fn.restype = restype
+            fn.argtypes = [t for _, t in args]
+            self.bound[name] = _Bound(name, fn, args)
+
+    def entry(self, name):
+        """the _Bound of a symbol the header declares: entry(name)(args) marshals `args` and calls it"""
+        try:
+            return self.bound[name]
+        except KeyError:
+            raise AttributeError("include/simpledet_ops.h declares no %s" % name) from None
+
+    def check(self, name, rc):
+        """raise SimpleDetOpsError for the non-zero code `rc` an entry point returned"""
         if rc != 0:
             msg = self.cdll.sd_last_error()
             err = SimpleDetOpsError("%s failed (%d): %s" % (name, rc, (msg or b"").decode()))
             err.code = int(rc)
             raise err
         return rc
+
+    def call(self, name, *args):
+        """Call an int-returning entry point, its arguments marshalled by the prototype (_Bound: tensors and
+        plain numbers go in as they are); raise SimpleDetOpsError on a non-zero code."""
+        return self.check(name, self.entry(name)(args))
 
     def set_tuning(self, key, value):
         self.call("sd_set_tuning", key.encode(), int(value))

@@ -97,9 +97,7 @@ def _ws(like, query, *args):
     include/simpledet_ops.h declares it) and `args` that function's arguments.  Returns (the scratch array on
     `like`'s context -- keep it referenced until the call is issued --, its pointer, its size as c_size_t): the last
     two are what the entry point takes."""
-    fn = getattr(lib().cdll, query)
-    fn.restype = lib().protos[query][0]
-    nbytes = int(fn(*args))
+    nbytes = int(getattr(lib().cdll, query)(*args))
     ws = _scratch(like, nbytes)
     return ws, _ptr(ws), ctypes.c_size_t(nbytes)
 

@@ -8,6 +8,7 @@ Function names/arguments mirror the reference operators (operator_cxx/, see each
 """
 import collections
 import ctypes
+import math
 
 import torch
 
@@ -24,8 +25,30 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _workspace(dev, wsb, workspace):
-    """the caller's uint8 workspace when it holds the wsb bytes the call needs, a fresh one when there is none"""
+# The marshalling lives in _lib: every argument is converted by the type the header gives its parameter, so the
+# calls below pass tensors (or None), Python numbers, ctypes arrays and byref()s as they are.  _p and _stream
+# remain for callers outside this module that wrap their arguments themselves.
+def _call(name, *args):
+    """lib().call, with the current torch stream appended where the entry point's last parameter is `void* stream`"""
+    L = lib()
+    entry = L.entry(name)
+    if entry.stream:
+        args += (_stream(),)
+    return L.check(name, entry(args))
+
+
+def _query(name, *args):
+    """The value of a function that returns no status: a *_workspace_bytes / *_plan_bytes size, a stride, a count.
+    Its arguments are ints, ctypes arrays and byref()s, which ctypes takes by the argument and return types _lib
+    set from the header."""
+    return int(getattr(lib().cdll, name)(*args))
+
+
+def _ws(dev, workspace, need, *args):
+    """The uint8 workspace of a call: `need` names its size query (`args` that query's arguments) or, where there
+    is none, is the byte count itself.  The caller's tensor when it holds that much, a fresh one when there is
+    none."""
+    wsb = _query(need, *args) if isinstance(need, str) else need
     if workspace is None:
         return torch.empty(wsb, device=dev, dtype=torch.uint8)
     if workspace.numel() < wsb:
@@ -33,7 +56,16 @@ def _workspace(dev, wsb, workspace):
     return workspace
 
 
-def _chk(t, name, dtype=torch.float32, ndim=None):
+def _req_of(r):
+    return REQ[r] if isinstance(r, str) else int(r)
+
+
+def _fn(name, t):
+    """the entry point of t's dtype: `name` for float32, its `_f16` twin otherwise"""
+    return name if t.dtype == torch.float32 else name + "_f16"
+
+
+def _chk(t, name, dtype=torch.float32, ndim=None, shape=None, numel=None, at_least=None):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     if not t.is_cuda:
@@ -44,7 +76,23 @@ def _chk(t, name, dtype=torch.float32, ndim=None):
         raise ValueError("%s should be a %dD tensor, got shape %s" % (name, ndim, tuple(t.shape)))
     if not t.is_contiguous():
         raise ValueError("%s must be contiguous" % name)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if numel is not None and t.numel() != numel:
+        raise ValueError("%s needs %d elements, got %d" % (name, numel, t.numel()))
+    if at_least is not None and t.numel() < at_least:
+        raise ValueError("%s needs at least %d elements, got %d" % (name, at_least, t.numel()))
     return t
+
+
+def _out(t, name, shape, dev, dtype=torch.float32, flat=False):
+    """An output: a fresh tensor of `shape` when the caller gave none, else the caller's, checked -- of that shape,
+    or with flat=True of any shape that holds as many elements (the entry points take flat buffers)."""
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=dtype)
+    if flat:
+        return _chk(t, name, dtype, numel=math.prod(shape))
+    return _chk(t, name, dtype, shape=shape)
 
 
 def _pair(v):
@@ -85,10 +133,8 @@ def roi_align_v2_forward(data, rois, pooled_size, spatial_scale):
     out = torch.empty(shape, device=data.device, dtype=torch.float32)
     mx = torch.empty(shape, device=data.device, dtype=torch.float32)
     my = torch.empty(shape, device=data.device, dtype=torch.float32)
-    wsb = lib().cdll.sd_roi_align_v2_workspace_bytes(B, R)
-    ws = torch.empty(wsb, device=data.device, dtype=torch.uint8)
-    lib().call("sd_roi_align_v2_fwd_ws", _p(data), _p(rois), _p(out), _p(mx), _p(my), B, C, H, W, R,
-               ph, pw, float(spatial_scale), _p(ws), ctypes.c_size_t(wsb), _stream())
+    ws = _ws(data.device, None, "sd_roi_align_v2_workspace_bytes", B, R)
+    _call("sd_roi_align_v2_fwd_ws", data, rois, out, mx, my, B, C, H, W, R, ph, pw, spatial_scale, ws, ws.numel())
     return out, mx, my
 
 
@@ -104,17 +150,15 @@ def roi_align_v2_backward(out_grad, rois, maxidx_x, maxidx_y, data_shape, spatia
     if (Bo, Co) != (B, C) or rois.shape[:2] != (B, R):
         raise ValueError("shape mismatch between out_grad %s, rois %s and data %s"
                          % (tuple(out_grad.shape), tuple(rois.shape), (B, C, H, W)))
-    rd = REQ[req_data] if isinstance(req_data, str) else int(req_data)
-    rr = REQ[req_rois] if isinstance(req_rois, str) else int(req_rois)
+    rd, rr = _req_of(req_data), _req_of(req_rois)
     if d_data is None:
         if rd == REQ["add"]:
             raise ValueError("req_data='add' needs the d_data tensor to accumulate into")
         d_data = torch.empty((B, C, H, W), device=out_grad.device, dtype=torch.float32)
     _chk(d_data, "d_data", ndim=4)
     d_rois = torch.empty_like(rois) if rr != 0 else None
-    lib().call("sd_roi_align_v2_bwd", _p(out_grad), _p(rois), _p(maxidx_x), _p(maxidx_y),
-               _p(d_data), _p(d_rois), rd, rr, B, C, H, W, R, ph, pw, float(spatial_scale),
-               _stream())
+    _call("sd_roi_align_v2_bwd", out_grad, rois, maxidx_x, maxidx_y, d_data, d_rois, rd, rr, B, C, H, W, R, ph, pw,
+          spatial_scale)
     return d_data, d_rois
 
 
@@ -131,10 +175,25 @@ def fpn_roi_assign(rois, rcnn_stride, roi_canonical_scale=224, roi_canonical_lev
     n = len(rcnn_stride)
     per = torch.empty((n, B, R, 4), device=rois.device, dtype=torch.float32)
     level = torch.empty((B, R), device=rois.device, dtype=torch.int32)
-    lib().call("sd_fpn_roi_assign", _p(rois), B * R, _iarr(rcnn_stride), n,
-               float(roi_canonical_scale), float(roi_canonical_level), _p(per), _p(level),
-               _stream())
+    _call("sd_fpn_roi_assign", rois, B * R, _iarr(rcnn_stride), n, roi_canonical_scale, roi_canonical_level, per,
+          level)
     return [per[i] for i in range(n)], level
+
+
+def _fpn_levels(feats, rois, rcnn_stride, dtype=torch.float32):
+    """The argument check of the FPN extractors: one (B,C,H_l,W_l) map of `dtype` per stride, rois (B,R,..) of the
+    same batch -> B, C, R and the H_l / W_l tables as the entry points take them."""
+    _chk(rois, "rois", ndim=3)
+    if len(feats) != len(rcnn_stride):
+        raise ValueError("one feature map per stride expected")
+    B, C = feats[0].shape[:2]
+    for i, f in enumerate(feats):
+        _chk(f, "feats[%d]" % i, dtype=dtype, ndim=4)
+        if tuple(f.shape[:2]) != (B, C):
+            raise ValueError("all levels must share (B,C)")
+    if rois.shape[0] != B:
+        raise ValueError("rois batch mismatch")
+    return B, C, rois.shape[1], _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
 
 
 def fpn_roi_align_forward(feats, rois, rcnn_stride, pooled_size, roi_canonical_scale=224,
@@ -143,40 +202,49 @@ def fpn_roi_align_forward(feats, rois, rcnn_stride, pooled_size, roi_canonical_s
 
     feats: list of (B,C,H_l,W_l); rois (B,R,4) -> out, maxidx_x, maxidx_y (B,R,C,ph,pw).
     """
-    _chk(rois, "rois", ndim=3)
-    if len(feats) != len(rcnn_stride):
-        raise ValueError("one feature map per stride expected")
-    B, C = feats[0].shape[:2]
-    for i, f in enumerate(feats):
-        _chk(f, "feats[%d]" % i, ndim=4)
-        if tuple(f.shape[:2]) != (B, C):
-            raise ValueError("all levels must share (B,C)")
-    if rois.shape[0] != B:
-        raise ValueError("rois batch mismatch")
+    B, C, R, Hs, Ws = _fpn_levels(feats, rois, rcnn_stride)
     ph, pw = _pair(pooled_size)
-    R = rois.shape[1]
     shape = (B, R, C, ph, pw)
     out = torch.empty(shape, device=rois.device, dtype=torch.float32)
     mx = torch.empty(shape, device=rois.device, dtype=torch.float32)
     my = torch.empty(shape, device=rois.device, dtype=torch.float32)
-    wsb = lib().cdll.sd_fpn_roi_align_workspace_bytes(B, R)
-    ws = torch.empty(wsb, device=rois.device, dtype=torch.uint8)
-    lib().call("sd_fpn_roi_align_fwd", _parr(feats), _iarr([f.shape[2] for f in feats]),
-               _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride), len(feats), _p(rois),
-               _p(out), _p(mx), _p(my), B, C, R, ph, pw, float(roi_canonical_scale),
-               float(roi_canonical_level), _p(ws), ctypes.c_size_t(wsb), _stream())
+    ws = _ws(rois.device, None, "sd_fpn_roi_align_workspace_bytes", B, R)
+    _call("sd_fpn_roi_align_fwd", _parr(feats), Hs, Ws, _iarr(rcnn_stride), len(feats), rois, out, mx, my, B, C, R,
+          ph, pw, roi_canonical_scale, roi_canonical_level, ws, ws.numel())
     return out, mx, my
 
 
 def argmax_stride(ph, pw):
     """bytes per (RoI, channel) row of the packed arg-max (sd_fpn_roi_align_argmax_stride)."""
-    return int(lib().cdll.sd_fpn_roi_align_argmax_stride(int(ph), int(pw)))
+    return _query("sd_fpn_roi_align_argmax_stride", int(ph), int(pw))
 
 
 def argmax_codes(argmax, pooled_size):
     """(B,R,C,S) packed arg-max -> (B,R,C,ph,pw) codes (drops the row padding)."""
     ph, pw = _pair(pooled_size)
     return argmax[..., :ph * pw].reshape(tuple(argmax.shape[:3]) + (ph, pw))
+
+
+def _packed_forward(fn, feats, rois, rcnn_stride, pooled_size, scale, level, dtype=torch.float32, plan=False):
+    """The three packed forwards behind one body: the argument check, out (of the maps' dtype) / arg-max / coords,
+    the workspace and the call of entry point `fn` -> out, (argmax, coords[, plan_buf])."""
+    B, C, R, Hs, Ws = _fpn_levels(feats, rois, rcnn_stride, dtype)
+    ph, pw = _pair(pooled_size)
+    dev = rois.device
+    out = torch.empty((B, R, C, ph, pw), device=dev, dtype=dtype)
+    amax = torch.empty((B, R, C, argmax_stride(ph, pw)), device=dev, dtype=torch.uint8)
+    coords = torch.empty((B, R, 9 * (ph + pw)), device=dev, dtype=torch.float32)
+    ws = _ws(dev, None, "sd_fpn_roi_align_workspace_bytes", B, R)
+    state = (amax, coords)
+    tail = ()
+    if plan:
+        # one rois-only pre-pass for the whole step: the backward's band lists / tap tables are built
+        # here too and travel to fpn_roi_align_backward_packed as the third element of the state
+        plan_buf = _ws(dev, None, "sd_fpn_roi_align_plan_bytes", Hs, Ws, len(feats), B, R)
+        state, tail = state + (plan_buf,), (plan_buf, plan_buf.numel())
+    _call(fn, _parr(feats), Hs, Ws, _iarr(rcnn_stride), len(feats), rois, out, amax, coords, B, C, R, ph, pw, scale,
+          level, ws, ws.numel(), *tail)
+    return out, state
 
 
 def fpn_roi_align_forward_packed(feats, rois, rcnn_stride, pooled_size, roi_canonical_scale=224,
@@ -186,40 +254,8 @@ def fpn_roi_align_forward_packed(feats, rois, rcnn_stride, pooled_size, roi_cano
     nothing pooled; unpack with argmax_codes()), coords (B,R,9*(ph+pw)) 4-byte
     words: per RoI 3*(ph+pw) fp32 sample coordinates, then 3*(ph+pw) {neighbours, fraction} pairs.  (argmax, coords) are state between this op's forward and backward
     only; fpn_roi_align_backward_packed decodes them."""
-    _chk(rois, "rois", ndim=3)
-    if len(feats) != len(rcnn_stride):
-        raise ValueError("one feature map per stride expected")
-    B, C = feats[0].shape[:2]
-    for i, f in enumerate(feats):
-        _chk(f, "feats[%d]" % i, ndim=4)
-        if tuple(f.shape[:2]) != (B, C):
-            raise ValueError("all levels must share (B,C)")
-    if rois.shape[0] != B:
-        raise ValueError("rois batch mismatch")
-    ph, pw = _pair(pooled_size)
-    R = rois.shape[1]
-    shape = (B, R, C, ph, pw)
-    out = torch.empty(shape, device=rois.device, dtype=torch.float32)
-    amax = torch.empty((B, R, C, argmax_stride(ph, pw)), device=rois.device, dtype=torch.uint8)
-    coords = torch.empty((B, R, 9 * (ph + pw)), device=rois.device, dtype=torch.float32)
-    wsb = lib().cdll.sd_fpn_roi_align_workspace_bytes(B, R)
-    ws = torch.empty(wsb, device=rois.device, dtype=torch.uint8)
-    if plan:
-        # one rois-only pre-pass for the whole step: the backward's band lists / tap tables are built
-        # here too and travel to fpn_roi_align_backward_packed as the third element of the state
-        Hs, Ws = _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
-        pb = lib().cdll.sd_fpn_roi_align_plan_bytes(Hs, Ws, len(feats), B, R)
-        plan_buf = torch.empty(pb, device=rois.device, dtype=torch.uint8)
-        lib().call("sd_fpn_roi_align_fwd_packed_plan", _parr(feats), Hs, Ws, _iarr(rcnn_stride), len(feats),
-                   _p(rois), _p(out), _p(amax), _p(coords), B, C, R, ph, pw, float(roi_canonical_scale),
-                   float(roi_canonical_level), _p(ws), ctypes.c_size_t(wsb), _p(plan_buf),
-                   ctypes.c_size_t(pb), _stream())
-        return out, (amax, coords, plan_buf)
-    lib().call("sd_fpn_roi_align_fwd_packed", _parr(feats), _iarr([f.shape[2] for f in feats]),
-               _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride), len(feats), _p(rois),
-               _p(out), _p(amax), _p(coords), B, C, R, ph, pw, float(roi_canonical_scale),
-               float(roi_canonical_level), _p(ws), ctypes.c_size_t(wsb), _stream())
-    return out, (amax, coords)
+    return _packed_forward("sd_fpn_roi_align_fwd_packed_plan" if plan else "sd_fpn_roi_align_fwd_packed", feats, rois,
+                           rcnn_stride, pooled_size, roi_canonical_scale, roi_canonical_level, plan=plan)
 
 
 def fpn_roi_align_forward_packed_f16(feats, rois, rcnn_stride, pooled_size, roi_canonical_scale=224,
@@ -227,38 +263,18 @@ def fpn_roi_align_forward_packed_f16(feats, rois, rcnn_stride, pooled_size, roi_
     """fp16 I/O variant of fpn_roi_align_forward_packed: feats fp16 (B,C,H_l,W_l), rois fp32 (B,R,4)
     -> out fp16 (B,R,C,ph,pw), (argmax, coords).  Bit-equal to feats.float() -> the fp32 op ->
     out.half() (models/FPN/builder.py:581-586, 607-608 wraps the op in exactly those casts)."""
-    _chk(rois, "rois", ndim=3)
-    if len(feats) != len(rcnn_stride):
-        raise ValueError("one feature map per stride expected")
-    B, C = feats[0].shape[:2]
-    for i, f in enumerate(feats):
-        _chk(f, "feats[%d]" % i, dtype=torch.float16, ndim=4)
-        if tuple(f.shape[:2]) != (B, C):
-            raise ValueError("all levels must share (B,C)")
-    if rois.shape[0] != B:
-        raise ValueError("rois batch mismatch")
-    ph, pw = _pair(pooled_size)
-    R = rois.shape[1]
-    out = torch.empty((B, R, C, ph, pw), device=rois.device, dtype=torch.float16)
-    amax = torch.empty((B, R, C, argmax_stride(ph, pw)), device=rois.device, dtype=torch.uint8)
-    coords = torch.empty((B, R, 9 * (ph + pw)), device=rois.device, dtype=torch.float32)
-    wsb = lib().cdll.sd_fpn_roi_align_workspace_bytes(B, R)
-    ws = torch.empty(wsb, device=rois.device, dtype=torch.uint8)
     try:
-        lib().call("sd_fpn_roi_align_fwd_packed_f16", _parr(feats), _iarr([f.shape[2] for f in feats]),
-                   _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride), len(feats), _p(rois),
-                   _p(out), _p(amax), _p(coords), B, C, R, ph, pw, float(roi_canonical_scale),
-                   float(roi_canonical_level), _p(ws), ctypes.c_size_t(wsb), _stream())
+        return _packed_forward("sd_fpn_roi_align_fwd_packed_f16", feats, rois, rcnn_stride, pooled_size,
+                               roi_canonical_scale, roi_canonical_level, dtype=torch.float16)
     except SimpleDetOpsError as e:
         if e.code != SD_ERR_UNSUPPORTED:
             raise
-        # shapes the band-resident kernel does not take (too many units, W < 2, ...): the graph's own
-        # cast -> fp32 op -> cast (models/FPN/builder.py:581-586, 607-608), same bits
-        f32 = [cast_f16_to_f32(f) for f in feats]
-        o32, (amax, coords) = fpn_roi_align_forward_packed(f32, rois, rcnn_stride, pooled_size,
-                                                           roi_canonical_scale, roi_canonical_level)
-        cast_f32_to_f16(o32, out)
-    return out, (amax, coords)
+    # shapes the band-resident kernel does not take (too many units, W < 2, ...): the graph's own
+    # cast -> fp32 op -> cast (models/FPN/builder.py:581-586, 607-608), same bits
+    f32 = [cast_f16_to_f32(f) for f in feats]
+    o32, state = fpn_roi_align_forward_packed(f32, rois, rcnn_stride, pooled_size, roi_canonical_scale,
+                                              roi_canonical_level)
+    return cast_f32_to_f16(o32), state
 
 
 def fpn_roi_align_backward_packed(out_grad, rois, argmax, feat_shapes, rcnn_stride,
@@ -273,7 +289,7 @@ def fpn_roi_align_backward_packed(out_grad, rois, argmax, feat_shapes, rcnn_stri
     B, R, C, ph, pw = out_grad.shape
     if tuple(argmax.shape) != (B, R, C, argmax_stride(ph, pw)):
         raise ValueError("argmax must be (B,R,C,%d) uint8" % argmax_stride(ph, pw))
-    rd = REQ[req_data] if isinstance(req_data, str) else int(req_data)
+    rd = _req_of(req_data)
     if d_feats is None:
         if rd == REQ["add"]:
             raise ValueError("req_data='add' needs d_feats")
@@ -283,33 +299,31 @@ def fpn_roi_align_backward_packed(out_grad, rois, argmax, feat_shapes, rcnn_stri
         _chk(f, "d_feats[%d]" % i, ndim=4)
     hs, ws_ = _iarr([f.shape[2] for f in d_feats]), _iarr([f.shape[3] for f in d_feats])
     if plan_buf is not None:
-        lib().call("sd_fpn_roi_align_bwd_packed_plan", _p(out_grad), _p(rois), _p(argmax), _p(coords),
-                   _parr(d_feats), hs, ws_, _iarr(rcnn_stride), len(d_feats), rd, B, C, R, ph, pw,
-                   float(roi_canonical_scale), float(roi_canonical_level), _p(plan_buf),
-                   ctypes.c_size_t(plan_buf.numel()), _stream())
+        _call("sd_fpn_roi_align_bwd_packed_plan", out_grad, rois, argmax, coords, _parr(d_feats), hs, ws_,
+              _iarr(rcnn_stride), len(d_feats), rd, B, C, R, ph, pw, roi_canonical_scale, roi_canonical_level,
+              plan_buf, plan_buf.numel())
         return d_feats
-    lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes.restype = ctypes.c_size_t
-    wsb = lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes(hs, ws_, len(d_feats), B, R)
-    work = torch.empty((max(int(wsb), 4) + 3) // 4, device=out_grad.device, dtype=torch.int32)
-    lib().call("sd_fpn_roi_align_bwd_packed_ws", _p(out_grad), _p(rois), _p(argmax), _p(coords),
-               _parr(d_feats), hs, ws_,
-               _iarr(rcnn_stride), len(d_feats), rd, B, C, R, ph, pw, float(roi_canonical_scale),
-               float(roi_canonical_level), _p(work), ctypes.c_size_t(work.numel() * 4), _stream())
+    # the entry point wants its workspace 4-byte aligned, 16 for the tap tables (roi_align_bwd.hip); every tensor of
+    # the torch allocator is, and the query answers in multiples of 16, so the common uint8 helper serves.  An empty
+    # problem (B or R zero) asks for nothing and gets NULL, which the header allows.
+    work = _ws(out_grad.device, None, "sd_fpn_roi_align_bwd_workspace_bytes", hs, ws_, len(d_feats), B, R)
+    _call("sd_fpn_roi_align_bwd_packed_ws", out_grad, rois, argmax, coords, _parr(d_feats), hs, ws_,
+          _iarr(rcnn_stride), len(d_feats), rd, B, C, R, ph, pw, roi_canonical_scale, roi_canonical_level, work,
+          work.numel())
     return d_feats
 
 
 def cast_f16_to_f32(src, out=None):
     _chk(src, "src", dtype=torch.float16)
     out = torch.empty(src.shape, device=src.device, dtype=torch.float32) if out is None else out
-    lib().call("sd_cast_f16_to_f32", _p(src), _p(out), ctypes.c_size_t(src.numel()), _stream())
+    _call("sd_cast_f16_to_f32", src, out, src.numel())
     return out
 
 
 def cast_f32_to_f16(src, out=None, req="write"):
     _chk(src, "src")
     out = torch.empty(src.shape, device=src.device, dtype=torch.float16) if out is None else out
-    lib().call("sd_cast_f32_to_f16", _p(src), _p(out), ctypes.c_size_t(src.numel()),
-               REQ[req] if isinstance(req, str) else int(req), _stream())
+    _call("sd_cast_f32_to_f16", src, out, src.numel(), _req_of(req))
     return out
 
 
@@ -322,7 +336,7 @@ def fpn_roi_align_backward_packed_f16(out_grad, rois, argmax, feat_shapes, rcnn_
     op-boundary casts of the reference's fp16 graphs around the fp32 kernel (same bits)."""
     _chk(out_grad, "out_grad", dtype=torch.float16, ndim=5)
     _chk(rois, "rois", ndim=3)
-    rd = REQ[req_data] if isinstance(req_data, str) else int(req_data)
+    rd = _req_of(req_data)
     if d_feats is None:
         if rd == REQ["add"]:
             raise ValueError("req_data='add' needs d_feats")
@@ -333,14 +347,11 @@ def fpn_roi_align_backward_packed_f16(out_grad, rois, argmax, feat_shapes, rcnn_
         am, coords = argmax[0], argmax[1]
         B, R, C, ph, pw = out_grad.shape
         hs, ws_ = _iarr([f.shape[2] for f in d_feats]), _iarr([f.shape[3] for f in d_feats])
-        lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes.restype = ctypes.c_size_t
-        wsb = lib().cdll.sd_fpn_roi_align_bwd_workspace_bytes(hs, ws_, len(d_feats), B, R)
-        work = torch.empty((max(int(wsb), 4) + 3) // 4, device=out_grad.device, dtype=torch.int32)
+        work = _ws(out_grad.device, None, "sd_fpn_roi_align_bwd_workspace_bytes", hs, ws_, len(d_feats), B, R)
         try:
-            lib().call("sd_fpn_roi_align_bwd_packed_f16", _p(out_grad), _p(rois), _p(am), _p(coords),
-                       _parr(d_feats), hs, ws_, _iarr(rcnn_stride), len(d_feats), rd, B, C, R, ph, pw,
-                       float(roi_canonical_scale), float(roi_canonical_level), _p(work),
-                       ctypes.c_size_t(work.numel() * 4), _stream())
+            _call("sd_fpn_roi_align_bwd_packed_f16", out_grad, rois, am, coords, _parr(d_feats), hs, ws_,
+                  _iarr(rcnn_stride), len(d_feats), rd, B, C, R, ph, pw, roi_canonical_scale, roi_canonical_level,
+                  work, work.numel())
             return d_feats
         except SimpleDetOpsError as e:
             if e.code != SD_ERR_UNSUPPORTED:
@@ -360,7 +371,7 @@ def fpn_roi_align_backward(out_grad, rois, maxidx_x, maxidx_y, feat_shapes, rcnn
     _chk(maxidx_x, "maxidx_x", ndim=5)
     _chk(maxidx_y, "maxidx_y", ndim=5)
     B, R, C, ph, pw = out_grad.shape
-    rd = REQ[req_data] if isinstance(req_data, str) else int(req_data)
+    rd = _req_of(req_data)
     if d_feats is None:
         if rd == REQ["add"]:
             raise ValueError("req_data='add' needs d_feats")
@@ -368,10 +379,9 @@ def fpn_roi_align_backward(out_grad, rois, maxidx_x, maxidx_y, feat_shapes, rcnn
                    for s in feat_shapes]
     for i, f in enumerate(d_feats):
         _chk(f, "d_feats[%d]" % i, ndim=4)
-    lib().call("sd_fpn_roi_align_bwd", _p(out_grad), _p(rois), _p(maxidx_x), _p(maxidx_y),
-               _parr(d_feats), _iarr([f.shape[2] for f in d_feats]),
-               _iarr([f.shape[3] for f in d_feats]), _iarr(rcnn_stride), len(d_feats), rd, B, C, R,
-               ph, pw, float(roi_canonical_scale), float(roi_canonical_level), _stream())
+    _call("sd_fpn_roi_align_bwd", out_grad, rois, maxidx_x, maxidx_y, _parr(d_feats),
+          _iarr([f.shape[2] for f in d_feats]), _iarr([f.shape[3] for f in d_feats]), _iarr(rcnn_stride),
+          len(d_feats), rd, B, C, R, ph, pw, roi_canonical_scale, roi_canonical_level)
     return d_feats
 
 
@@ -390,8 +400,7 @@ def roi_pool_v1_forward(data, rois, pooled_size, spatial_scale):
     K = rois.shape[0]
     out = torch.empty((K, C, ph, pw), device=data.device, dtype=torch.float32)
     idx = torch.empty_like(out)
-    lib().call("sd_roi_pool_v1_fwd", _p(data), _p(rois), _p(out), _p(idx), B, C, H, W, K, ph, pw,
-               float(spatial_scale), _stream())
+    _call("sd_roi_pool_v1_fwd", data, rois, out, idx, B, C, H, W, K, ph, pw, spatial_scale)
     return out, idx
 
 
@@ -405,15 +414,13 @@ def roi_pool_v1_backward(out_grad, rois, maxidx, data_shape, spatial_scale, req_
     K, Co, ph, pw = out_grad.shape
     if Co != C or rois.shape[0] != K:
         raise ValueError("shape mismatch")
-    rd = REQ[req_data] if isinstance(req_data, str) else int(req_data)
-    rr = REQ[req_rois] if isinstance(req_rois, str) else int(req_rois)
+    rd, rr = _req_of(req_data), _req_of(req_rois)
     if d_data is None:
         if rd == REQ["add"]:
             raise ValueError("req_data='add' needs the d_data tensor to accumulate into")
         d_data = torch.empty((B, C, H, W), device=out_grad.device, dtype=torch.float32)
     d_rois = torch.empty_like(rois) if rr != 0 else None
-    lib().call("sd_roi_pool_v1_bwd", _p(out_grad), _p(rois), _p(maxidx), _p(d_data), _p(d_rois), rd,
-               rr, B, C, H, W, K, ph, pw, float(spatial_scale), _stream())
+    _call("sd_roi_pool_v1_bwd", out_grad, rois, maxidx, d_data, d_rois, rd, rr, B, C, H, W, K, ph, pw, spatial_scale)
     return d_data, d_rois
 
 
@@ -421,19 +428,11 @@ def roi_pool_v1_backward(out_grad, rois, maxidx, data_shape, spatial_scale, req_
 # _contrib_DeformablePSROIPooling (upstream MXNet) and TSD's fused FPN extractor
 # (models/TSD/poolings.py:51-174)
 # --------------------------------------------------------------------------------------------------
-def _req_of(r):
-    return REQ[r] if isinstance(r, str) else int(r)
-
-
 def _grad_buf(t, name, shape, rd, dev):
-    if t is None:
-        if rd == REQ["add"]:
-            raise ValueError("req 'add' needs the %s tensor to accumulate into" % name)
-        return torch.empty(shape, device=dev, dtype=torch.float32)
-    _chk(t, name)
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    return t
+    """_out for a gradient written under req `rd`: 'add' has nothing to add to in a fresh tensor"""
+    if t is None and rd == REQ["add"]:
+        raise ValueError("req 'add' needs the %s tensor to accumulate into" % name)
+    return _out(t, name, shape, dev)
 
 
 def _dpsroi_dims(data, rois, trans, output_dim, pooled_size, part_size, no_trans):
@@ -461,11 +460,11 @@ def deform_psroi_pool_forward(data, rois, trans=None, *, spatial_scale, output_d
     K, P, ncls = _dpsroi_dims(data, rois, trans, output_dim, pooled_size, part_size, no_trans)
     B, C, H, W = data.shape
     shape = (K, int(output_dim), P, P)
-    out = _grad_buf(out, "out", shape, 0, data.device)
-    top_count = _grad_buf(top_count, "top_count", shape, 0, data.device)
-    lib().call("sd_deform_psroi_pool_fwd", _p(data), _p(rois), None if no_trans else _p(trans), _p(out),
-               _p(top_count), B, C, H, W, K, ncls, float(spatial_scale), int(output_dim), int(group_size), P,
-               int(part_size), int(sample_per_part), float(trans_std), int(bool(no_trans)), _stream())
+    out = _out(out, "out", shape, data.device)
+    top_count = _out(top_count, "top_count", shape, data.device)
+    _call("sd_deform_psroi_pool_fwd", data, rois, None if no_trans else trans, out, top_count, B, C, H, W, K, ncls,
+          spatial_scale, int(output_dim), int(group_size), P, int(part_size), int(sample_per_part), trans_std,
+          bool(no_trans))
     return out, top_count
 
 
@@ -488,10 +487,9 @@ def deform_psroi_pool_backward(out_grad, data, rois, trans, top_count, *, spatia
     if rt:
         d_trans = _grad_buf(d_trans, "d_trans", tuple(trans.shape), rt, data.device)
     d_rois = torch.empty_like(rois) if rr == REQ["write"] else None
-    lib().call("sd_deform_psroi_pool_bwd", _p(out_grad), _p(data), _p(rois), None if no_trans else _p(trans),
-               _p(top_count), _p(d_data) if rd else None, _p(d_rois), _p(d_trans) if rt else None, rd, rr, rt,
-               B, C, H, W, K, ncls, float(spatial_scale), int(output_dim), int(group_size), P, int(part_size),
-               int(sample_per_part), float(trans_std), int(bool(no_trans)), _stream())
+    _call("sd_deform_psroi_pool_bwd", out_grad, data, rois, None if no_trans else trans, top_count,
+          d_data if rd else None, d_rois, d_trans if rt else None, rd, rr, rt, B, C, H, W, K, ncls, spatial_scale,
+          int(output_dim), int(group_size), P, int(part_size), int(sample_per_part), trans_std, bool(no_trans))
     return (d_data if rd else None), d_rois, (d_trans if rt else None)
 
 
@@ -525,16 +523,8 @@ def _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size):
     _chk(rois, "rois", ndim=3)
     if rois.shape[2] != 4:
         raise ValueError("rois should be a 3D tensor of shape [batch, rois, 4]")
-    if len(feats) != len(rcnn_stride):
-        raise ValueError("one feature map per stride expected")
-    B, C = feats[0].shape[:2]
-    for i, f in enumerate(feats):
-        _chk(f, "feats[%d]" % i, ndim=4)
-        if tuple(f.shape[:2]) != (B, C):
-            raise ValueError("all levels must share (B,C)")
-    if rois.shape[0] != B:
-        raise ValueError("rois batch mismatch")
-    R, P = rois.shape[1], int(pooled_size)
+    B, C, R, Hs, Ws = _fpn_levels(feats, rois, rcnn_stride)
+    P = int(pooled_size)
     _chk(trans, "trans")
     if tuple(trans.shape) == (B * R, 2, P, P):
         tpart = P
@@ -542,7 +532,7 @@ def _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size):
         tpart = 1
     else:
         raise ValueError("trans should have shape (B*R, 2, P, P) or (B*R, 2), got %s" % (tuple(trans.shape),))
-    return B, C, R, P, tpart
+    return B, C, R, P, tpart, Hs, Ws
 
 
 def fpn_deform_roi_pool_forward(feats, rois, trans, rcnn_stride, pooled_size, sample_per_part=4, trans_std=0.1,
@@ -551,13 +541,11 @@ def fpn_deform_roi_pool_forward(feats, rois, trans, rcnn_stride, pooled_size, sa
 
     feats: list of (B,C,H_l,W_l); rois (B,R,4); trans (B*R,2,P,P) (DeltaC) or (B*R,2) (DeltaR)
     -> out (B*R,C,P,P), top_count (B*R,nlvl,P,P)."""
-    B, C, R, P, tpart = _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size)
-    out = _grad_buf(out, "out", (B * R, C, P, P), 0, rois.device)
-    top_count = _grad_buf(top_count, "top_count", (B * R, len(feats), P, P), 0, rois.device)
-    lib().call("sd_fpn_deform_roi_pool_fwd", _parr(feats), _iarr([f.shape[2] for f in feats]),
-               _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride), len(feats), _p(rois), _p(trans), _p(out),
-               _p(top_count), B, C, R, P, tpart, int(sample_per_part), float(trans_std),
-               float(roi_canonical_scale), float(roi_canonical_level), _stream())
+    B, C, R, P, tpart, Hs, Ws = _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size)
+    out = _out(out, "out", (B * R, C, P, P), rois.device)
+    top_count = _out(top_count, "top_count", (B * R, len(feats), P, P), rois.device)
+    _call("sd_fpn_deform_roi_pool_fwd", _parr(feats), Hs, Ws, _iarr(rcnn_stride), len(feats), rois, trans, out,
+          top_count, B, C, R, P, tpart, int(sample_per_part), trans_std, roi_canonical_scale, roi_canonical_level)
     return out, top_count
 
 
@@ -565,7 +553,7 @@ def fpn_deform_roi_pool_backward(out_grad, feats, rois, trans, top_count, rcnn_s
                                  sample_per_part=4, trans_std=0.1, roi_canonical_scale=224, roi_canonical_level=4,
                                  req_data="write", req_trans="write", d_feats=None, d_trans=None):
     """-> [d_feat per level] (None when req_data null), d_trans (None when req_trans null)"""
-    B, C, R, P, tpart = _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size)
+    B, C, R, P, tpart, Hs, Ws = _fpn_dpool_dims(feats, rois, trans, rcnn_stride, pooled_size)
     _chk(out_grad, "out_grad", ndim=4)
     _chk(top_count, "top_count", ndim=4)
     if tuple(out_grad.shape) != (B * R, C, P, P) or tuple(top_count.shape) != (B * R, len(feats), P, P):
@@ -578,11 +566,9 @@ def fpn_deform_roi_pool_backward(out_grad, feats, rois, trans, top_count, rcnn_s
                    for i, (d, f) in enumerate(zip(d_feats, feats))]
     if rt:
         d_trans = _grad_buf(d_trans, "d_trans", tuple(trans.shape), rt, rois.device)
-    lib().call("sd_fpn_deform_roi_pool_bwd", _p(out_grad), _parr(feats), _parr(d_feats) if rd else None,
-               _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats]), _iarr(rcnn_stride),
-               len(feats), _p(rois), _p(trans), _p(top_count), _p(d_trans) if rt else None, rd, rt, B, C, R, P,
-               tpart, int(sample_per_part), float(trans_std), float(roi_canonical_scale),
-               float(roi_canonical_level), _stream())
+    _call("sd_fpn_deform_roi_pool_bwd", out_grad, _parr(feats), _parr(d_feats) if rd else None, Hs, Ws,
+          _iarr(rcnn_stride), len(feats), rois, trans, top_count, d_trans if rt else None, rd, rt, B, C, R, P, tpart,
+          int(sample_per_part), trans_std, roi_canonical_scale, roi_canonical_level)
     return (d_feats if rd else None), (d_trans if rt else None)
 
 
@@ -624,8 +610,8 @@ def gen_anchor(height, width, feature_stride, scales, ratios, device=None):
     device = device or torch.device("cuda", torch.cuda.current_device())
     A = len(scales) * len(ratios)
     out = torch.empty((int(height) * int(width) * A, 4), device=device, dtype=torch.float32)
-    lib().call("sd_gen_anchor", _p(out), int(height), int(width), int(feature_stride),
-               _darr(scales), len(scales), _darr(ratios), len(ratios), _stream())
+    _call("sd_gen_anchor", out, int(height), int(width), int(feature_stride), _darr(scales), len(scales),
+          _darr(ratios), len(ratios))
     return out
 
 
@@ -636,13 +622,8 @@ def gen_anchor_levels(shapes, strides, scales, ratios, device=None):
     device = device or torch.device("cuda", torch.cuda.current_device())
     A = len(scales) * len(ratios)
     outs = [torch.empty((int(h) * int(w) * A, 4), device=device, dtype=torch.float32) for h, w in shapes]
-    n = len(outs)
-    ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-    hs = (ctypes.c_int * n)(*[int(h) for h, _ in shapes])
-    ws = (ctypes.c_int * n)(*[int(w) for _, w in shapes])
-    st = (ctypes.c_int * n)(*[int(v) for v in strides])
-    lib().call("sd_gen_anchor_levels", ptrs, hs, ws, st, n, _darr(scales), len(scales), _darr(ratios),
-               len(ratios), _stream())
+    _call("sd_gen_anchor_levels", _parr(outs), _iarr([h for h, _ in shapes]), _iarr([w for _, w in shapes]),
+          _iarr(strides), len(outs), _darr(scales), len(scales), _darr(ratios), len(ratios))
     return outs
 
 
@@ -663,7 +644,7 @@ def glibc_rand_state(seed=1, device=None):
     """Device copy of libc's rand() state after srand(seed) (33 int32).  seed=1 is the state of a
     process that never called srand -- what the reference op sees (no srand anywhere in it)."""
     host = (ctypes.c_int32 * 33)()
-    lib().call("sd_glibc_srand_host", ctypes.c_uint32(seed), host)
+    _call("sd_glibc_srand_host", seed, host)
     device = device or torch.device("cuda", torch.cuda.current_device())
     return torch.tensor(list(host), dtype=torch.int32, device=device)
 
@@ -724,19 +705,16 @@ def proposal_target(rois, gt_boxes, num_classes, batch_images, image_rois, fg_fr
     bw = torch.empty((B, S, K4), device=dev, dtype=torch.float32)
     iou = torch.empty((B, S), device=dev, dtype=torch.float32)
     kept = torch.empty((B, S), device=dev, dtype=torch.int32) if return_index else None
-    wsb = lib().cdll.sd_proposal_target_workspace_bytes(B, N, M)
-    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    ws = _ws(dev, None, "sd_proposal_target_workspace_bytes", B, N, M)
     if valid_ranges is not None:
         _chk(valid_ranges, "valid_ranges", ndim=2)
         if tuple(valid_ranges.shape) != (B, 2):
             raise ValueError("valid_ranges must be (B,2)")
-        lib().call("sd_proposal_target_v2", _p(rois), _p(gt_boxes), _p(valid_ranges),
-                   int(bool(filter_scales)), N, M, ctypes.byref(p), _p(rng_state), _p(ro), _p(lb),
-                   _p(bt), _p(bw), _p(iou), _p(kept), _p(ws), ctypes.c_size_t(wsb), _stream())
+        _call("sd_proposal_target_v2", rois, gt_boxes, valid_ranges, bool(filter_scales), N, M, ctypes.byref(p),
+              rng_state, ro, lb, bt, bw, iou, kept, ws, ws.numel())
     else:
-        lib().call("sd_proposal_target", _p(rois), _p(gt_boxes), N, M, ctypes.byref(p), _p(rng_state),
-                   _p(ro), _p(lb), _p(bt), _p(bw), _p(iou), _p(kept), _p(ws), ctypes.c_size_t(wsb),
-                   _stream())
+        _call("sd_proposal_target", rois, gt_boxes, N, M, ctypes.byref(p), rng_state, ro, lb, bt, bw, iou, kept, ws,
+              ws.numel())
     res = (ro, lb, bt, bw, iou)
     return res + (kept,) if return_index else res
 
@@ -787,20 +765,16 @@ def proposal_mask_target(rois, gt_boxes, gt_polys, num_classes, batch_images, im
     kept = torch.empty((B, S), device=dev, dtype=torch.int32) if return_index else None
     if output_ratio:
         ratio = torch.empty((B, FG), device=dev, dtype=torch.float32)
-        wsb = lib().cdll.sd_proposal_mask_target_ratio_workspace_bytes(
-            B, N, M, S, ctypes.c_float(float(fg_fraction)), int(max_raster_pixels))
-        ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-        lib().call("sd_proposal_mask_target_ratio", _p(rois), _p(gt_boxes), _p(gt_polys), _p(valid_ranges),
-                   int(bool(filter_scales)), N, M, L, int(mask_size), ctypes.byref(p), _p(rng_state), _p(ro),
-                   _p(lb), _p(bt), _p(bw), _p(iou), _p(mask), _p(ratio), int(max_raster_pixels), _p(kept),
-                   _p(ws), ctypes.c_size_t(wsb), _stream())
+        ws = _ws(dev, None, "sd_proposal_mask_target_ratio_workspace_bytes", B, N, M, S, fg_fraction,
+                 int(max_raster_pixels))
+        _call("sd_proposal_mask_target_ratio", rois, gt_boxes, gt_polys, valid_ranges, bool(filter_scales), N, M, L,
+              int(mask_size), ctypes.byref(p), rng_state, ro, lb, bt, bw, iou, mask, ratio, int(max_raster_pixels),
+              kept, ws, ws.numel())
         res = (ro, lb, bt, bw, iou, mask, ratio)
         return res + (kept,) if return_index else res
-    wsb = lib().cdll.sd_proposal_target_workspace_bytes(B, N, M)
-    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-    lib().call("sd_proposal_mask_target", _p(rois), _p(gt_boxes), _p(gt_polys), _p(valid_ranges),
-               int(bool(filter_scales)), N, M, L, int(mask_size), ctypes.byref(p), _p(rng_state), _p(ro),
-               _p(lb), _p(bt), _p(bw), _p(iou), _p(mask), _p(kept), _p(ws), ctypes.c_size_t(wsb), _stream())
+    ws = _ws(dev, None, "sd_proposal_target_workspace_bytes", B, N, M)
+    _call("sd_proposal_mask_target", rois, gt_boxes, gt_polys, valid_ranges, bool(filter_scales), N, M, L,
+          int(mask_size), ctypes.byref(p), rng_state, ro, lb, bt, bw, iou, mask, kept, ws, ws.numel())
     res = (ro, lb, bt, bw, iou, mask)
     return res + (kept,) if return_index else res
 
@@ -851,7 +825,7 @@ def mt19937_state(seed=None, numpy_state=None, device=None):
         key, pos = numpy_state[1], int(numpy_state[2])
         vals = [int(k) - (1 << 32) if int(k) >= (1 << 31) else int(k) for k in key] + [pos]
         return torch.tensor(vals, dtype=torch.int32, device=device)
-    lib().call("sd_mt19937_seed_host", ctypes.c_uint32(int(seed)), host)
+    _call("sd_mt19937_seed_host", int(seed), host)
     return torch.tensor(list(host), dtype=torch.int32, device=device)
 
 
@@ -866,7 +840,7 @@ def rpn_anchor_target(im_info, gt_bbox, param, mt_state, layout=1):
     if mt_state.numel() != 625:
         raise ValueError("mt_state must hold 625 int32 words")
     B, M, G = gt_bbox.shape
-    N = int(lib().cdll.sd_rpn_target_num_anchors(ctypes.byref(param)))
+    N = _query("sd_rpn_target_num_anchors", ctypes.byref(param))
     if N < 0:
         raise ValueError("bad rpn target parameters")
     A = param.n_scales * param.n_aspects
@@ -879,11 +853,9 @@ def rpn_anchor_target(im_info, gt_bbox, param, mt_state, layout=1):
         cls = torch.empty((B, N), device=dev, dtype=torch.float32)
         tgt = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
         wgt = torch.empty_like(tgt)
-    lib().cdll.sd_rpn_target_workspace_bytes.restype = ctypes.c_size_t
-    wsb = lib().cdll.sd_rpn_target_workspace_bytes(ctypes.byref(param), B, M)
-    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-    lib().call("sd_rpn_anchor_target", _p(im_info), _p(gt_bbox), B, M, G, ctypes.byref(param), _p(mt_state),
-               _p(cls), _p(tgt), _p(wgt), int(layout), _p(ws), ctypes.c_size_t(wsb), _stream())
+    ws = _ws(dev, None, "sd_rpn_target_workspace_bytes", ctypes.byref(param), B, M)
+    _call("sd_rpn_anchor_target", im_info, gt_bbox, B, M, G, ctypes.byref(param), mt_state, cls, tgt, wgt,
+          int(layout), ws, ws.numel())
     return cls, tgt, wgt
 
 
@@ -899,7 +871,7 @@ def retina_anchor_target(im_info, gt_bbox, param, layout=1, workspace=None):
     B, M, G = gt_bbox.shape
     if G != 5 or im_info.shape != (B, 3):
         raise ValueError("gt_bbox must be (B,M,5) and im_info (B,3)")
-    N = int(lib().cdll.sd_rpn_target_num_anchors(ctypes.byref(param)))
+    N = _query("sd_rpn_target_num_anchors", ctypes.byref(param))
     if N < 0:
         raise ValueError("bad anchor target parameters")
     A = param.n_scales * param.n_aspects
@@ -908,12 +880,9 @@ def retina_anchor_target(im_info, gt_bbox, param, layout=1, workspace=None):
     tgt = torch.empty((B, 4 * A, N // A) if layout == 1 else (B, N, 4), device=dev, dtype=torch.float32)
     wgt = torch.empty_like(tgt)
     fg = torch.empty((B,), device=dev, dtype=torch.float32)
-    lib().cdll.sd_retina_target_workspace_bytes.restype = ctypes.c_size_t
-    wsb = int(lib().cdll.sd_retina_target_workspace_bytes(ctypes.byref(param), B, M))
-    workspace = _workspace(dev, wsb, workspace)
-    lib().call("sd_retina_anchor_target", _p(im_info), _p(gt_bbox), B, M, ctypes.byref(param), _p(cls),
-               _p(tgt), _p(wgt), _p(fg), int(layout), _p(workspace), ctypes.c_size_t(workspace.numel()),
-               _stream())
+    ws = _ws(dev, workspace, "sd_retina_target_workspace_bytes", ctypes.byref(param), B, M)
+    _call("sd_retina_anchor_target", im_info, gt_bbox, B, M, ctypes.byref(param), cls, tgt, wgt, fg, int(layout), ws,
+          ws.numel())
     return cls, tgt, wgt, fg
 
 
@@ -925,8 +894,7 @@ NORMALIZATION = {"null": 0, "batch": 1, "valid": 2}
 
 
 def focal_loss_workspace_bytes():
-    lib().cdll.sd_focal_loss_workspace_bytes.restype = ctypes.c_size_t
-    return int(lib().cdll.sd_focal_loss_workspace_bytes())
+    return _query("sd_focal_loss_workspace_bytes")
 
 
 def focal_loss_forward(data, out=None):
@@ -938,7 +906,7 @@ def focal_loss_forward(data, out=None):
         _chk(out, "out")
         if out.shape != data.shape:
             raise ValueError("out must have the shape of data")
-    lib().call("sd_focal_loss_fwd", _p(data), _p(out), ctypes.c_long(data.numel()), _stream())
+    _call("sd_focal_loss_fwd", data, out, data.numel())
     return out
 
 
@@ -965,10 +933,9 @@ def focal_loss_backward(out, label, ograd=None, *, alpha=0.25, gamma=2.0, grad_s
         _chk(gdata, "gdata", ndim=3)
         if gdata.shape != out.shape:
             raise ValueError("gdata must have the shape of out")
-    ws = _workspace(out.device, focal_loss_workspace_bytes(), workspace)
-    lib().call("sd_focal_loss_bwd", _p(out), _p(label), _p(ograd), _p(gdata), B, nbox, nclass,
-               float(alpha), float(gamma), float(grad_scale), NORMALIZATION[normalization], _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(out.device, workspace, "sd_focal_loss_workspace_bytes")
+    _call("sd_focal_loss_bwd", out, label, ograd, gdata, B, nbox, nclass, alpha, gamma, grad_scale,
+          NORMALIZATION[normalization], ws, ws.numel())
     return gdata
 
 
@@ -986,10 +953,9 @@ def bbox_norm_backward(gout, label, gdata=None, workspace=None):
         _chk(gdata, "gdata")
         if gdata.shape != gout.shape:
             raise ValueError("gdata must have the shape of gout")
-    ws = _workspace(gout.device, focal_loss_workspace_bytes(), workspace)
-    lib().call("sd_bbox_norm_bwd", _p(gout), _p(label), _p(gdata), B,
-               ctypes.c_long(gout.numel() // B if B else 0), ctypes.c_long(label.numel() // B if B else 0),
-               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(gout.device, workspace, "sd_focal_loss_workspace_bytes")
+    _call("sd_bbox_norm_bwd", gout, label, gdata, B, gout.numel() // B if B else 0, label.numel() // B if B else 0,
+          ws, ws.numel())
     return gdata
 
 
@@ -997,8 +963,7 @@ def bbox_norm_backward(gout, label, gdata=None, workspace=None):
 # _contrib_GroupNorm  (operator_cxx/contrib/group_norm{-inl.h,.cu}, group_norm_helper.cu)
 # --------------------------------------------------------------------------------------------------
 def group_norm_workspace_bytes(N, C, HxW, num_group):
-    fn = lib().cdll.sd_group_norm_workspace_bytes
-    return int(fn(int(N), int(C), ctypes.c_long(int(HxW)), int(num_group)))
+    return _query("sd_group_norm_workspace_bytes", int(N), int(C), int(HxW), int(num_group))
 
 
 def _gn_dims(x, gamma, num_group):
@@ -1015,16 +980,6 @@ def _gn_dims(x, gamma, num_group):
     return N, C, (x.numel() // (N * C) if N * C else 0), G
 
 
-def _gn_out(t, name, like=None, shape=None, at_least=None):
-    """an output the caller passed: float32, on the device, contiguous, of the given shape or size"""
-    _chk(t, name)
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if at_least is not None and t.numel() < at_least:
-        raise ValueError("%s needs at least %d floats, got %d" % (name, at_least, t.numel()))
-    return t
-
-
 def group_norm_forward(x, gamma, beta, num_group=32, eps=1e-5, y=None, mu=None, rsig=None, workspace=None):
     """_contrib_GroupNorm forward (group_norm.cu:71-91,198-233): x (N,C,...) NCHW, gamma / beta (C,)
     -> y (the shape of x), mu (N,G), rsig (N,G) = 1 / sqrt(biased variance + eps), the variance taken about
@@ -1034,13 +989,13 @@ def group_norm_forward(x, gamma, beta, num_group=32, eps=1e-5, y=None, mu=None, 
     _chk(beta, "beta", ndim=1)
     if beta.shape[0] != C:
         raise ValueError("beta must have %d entries, got %d" % (C, beta.shape[0]))
-    y = torch.empty_like(x) if y is None else _gn_out(y, "y", shape=x.shape)
-    mu = torch.empty((N, G), device=x.device, dtype=torch.float32) if mu is None else _gn_out(mu, "mu", at_least=N * G)
+    y = _out(y, "y", x.shape, x.device)
+    # mu / rsig the caller passes may be larger than (N,G): only their size is checked
+    mu = torch.empty((N, G), device=x.device, dtype=torch.float32) if mu is None else _chk(mu, "mu", at_least=N * G)
     rsig = (torch.empty((N, G), device=x.device, dtype=torch.float32) if rsig is None
-            else _gn_out(rsig, "rsig", at_least=N * G))
-    ws = _workspace(x.device, group_norm_workspace_bytes(*dims), workspace)
-    lib().call("sd_group_norm_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(mu), _p(rsig), N, C, ctypes.c_long(HxW), G,
-               float(eps), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+            else _chk(rsig, "rsig", at_least=N * G))
+    ws = _ws(x.device, workspace, "sd_group_norm_workspace_bytes", *dims)
+    _call("sd_group_norm_fwd", x, gamma, beta, y, mu, rsig, N, C, HxW, G, eps, ws, ws.numel())
     return y, mu, rsig
 
 
@@ -1050,21 +1005,20 @@ def group_norm_backward(dy, x, mu, rsig, gamma, num_group=32, dx=None, dgamma=No
     (their first N*G floats are read), gamma (C,) -> dx, dgamma, dbeta (written, not accumulated).
     param_grads=False skips dgamma / dbeta and returns None for them."""
     N, C, HxW, G = dims = _gn_dims(x, gamma, num_group)
-    _gn_out(dy, "dy", shape=x.shape)
-    _gn_out(mu, "mu", at_least=N * G)
-    _gn_out(rsig, "rsig", at_least=N * G)
-    dx = torch.empty_like(x) if dx is None else _gn_out(dx, "dx", shape=x.shape)
+    _chk(dy, "dy", shape=x.shape)
+    _chk(mu, "mu", at_least=N * G)
+    _chk(rsig, "rsig", at_least=N * G)
+    dx = _out(dx, "dx", x.shape, x.device)
     if param_grads:
-        dgamma = torch.empty_like(gamma) if dgamma is None else _gn_out(dgamma, "dgamma", shape=gamma.shape)
-        dbeta = torch.empty_like(gamma) if dbeta is None else _gn_out(dbeta, "dbeta", shape=gamma.shape)
+        dgamma = _out(dgamma, "dgamma", gamma.shape, x.device)
+        dbeta = _out(dbeta, "dbeta", gamma.shape, x.device)
         if N * HxW == 0:   # sums over nothing (the entry point writes nothing on an empty problem)
             dgamma.zero_()
             dbeta.zero_()
     elif dgamma is not None or dbeta is not None:
         raise ValueError("param_grads=False takes no dgamma / dbeta")
-    ws = _workspace(x.device, group_norm_workspace_bytes(*dims), workspace)
-    lib().call("sd_group_norm_bwd", _p(dy), _p(x), _p(mu), _p(rsig), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), N, C,
-               ctypes.c_long(HxW), G, _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(x.device, workspace, "sd_group_norm_workspace_bytes", *dims)
+    _call("sd_group_norm_bwd", dy, x, mu, rsig, gamma, dx, dgamma, dbeta, N, C, HxW, G, ws, ws.numel())
     return dx, dgamma, dbeta
 
 
@@ -1103,7 +1057,7 @@ _SBA_DTYPES = (torch.float32, torch.float16)
 
 
 def scale_bias_act_workspace_bytes(N, C, HxW):
-    return int(lib().cdll.sd_scale_bias_act_workspace_bytes(int(N), int(C), ctypes.c_long(int(HxW))))
+    return _query("sd_scale_bias_act_workspace_bytes", int(N), int(C), int(HxW))
 
 
 def _sba_act(act):
@@ -1126,18 +1080,11 @@ def _sba_dims(x, gamma, name="data"):
 
 
 def _sba_param(p, name, x, C):
-    """(C,) or (1,C,1,1) of x's dtype -> the flat view"""
+    """(C,) or (1,C,1,1) of x's dtype -> the flat view (two shapes and a reshape: more than _chk's shape= does)"""
     _chk(p, name, dtype=x.dtype)
     if p.numel() != C or (p.dim() != 1 and (p.dim() < 2 or p.shape[1] != C)):
         raise ValueError("%s must have shape (%d,) or (1,%d,1,...), got %s" % (name, C, C, tuple(p.shape)))
     return p.reshape(-1)
-
-
-def _sba_like(t, name, x):
-    _chk(t, name, dtype=x.dtype)
-    if tuple(t.shape) != tuple(x.shape):
-        raise ValueError("%s must have shape %s, got %s" % (name, tuple(x.shape), tuple(t.shape)))
-    return t
 
 
 def scale_bias_act_forward(x, gamma, beta=None, residual=None, act=None, out=None):
@@ -1147,11 +1094,9 @@ def scale_bias_act_forward(x, gamma, beta=None, residual=None, act=None, out=Non
     (it may be x or residual: the in-place forms)."""
     N, C, HxW, gamma = _sba_dims(x, gamma)
     beta = None if beta is None else _sba_param(beta, "beta", x, C)
-    residual = None if residual is None else _sba_like(residual, "residual", x)
-    y = torch.empty_like(x) if out is None else _sba_like(out, "out", x)
-    fn = "sd_scale_bias_act_fwd" if x.dtype == torch.float32 else "sd_scale_bias_act_fwd_f16"
-    lib().call(fn, _p(x), _p(gamma), _p(beta), _p(residual), _p(y), N, C, ctypes.c_long(HxW), _sba_act(act),
-               _stream())
+    residual = None if residual is None else _chk(residual, "residual", x.dtype, shape=x.shape)
+    y = _out(out, "out", x.shape, x.device, x.dtype)
+    _call(_fn("sd_scale_bias_act_fwd", x), x, gamma, beta, residual, y, N, C, HxW, _sba_act(act))
     return y
 
 
@@ -1166,14 +1111,12 @@ def scale_bias_act_backward(dy, y, gamma, act=None, dx=None, dres=None, dbeta=No
     if a:
         if y is None:
             raise ValueError("act='relu' needs y, the forward's output")
-        _sba_like(y, "y", dy)
+        _chk(y, "y", dy.dtype, shape=dy.shape)
     else:
         y = None
-    dx = torch.empty_like(dy) if dx is None else _sba_like(dx, "dx", dy)
-    if dres is None and need_dres:
-        dres = torch.empty_like(dy)
-    elif dres is not None:
-        _sba_like(dres, "dres", dy)
+    dx = _out(dx, "dx", dy.shape, dy.device, dy.dtype)
+    if dres is not None or need_dres:
+        dres = _out(dres, "dres", dy.shape, dy.device, dy.dtype)
     if dbeta is None and need_dbeta:
         dbeta = torch.empty(C, device=dy.device, dtype=torch.float32)
     elif dbeta is not None:
@@ -1184,10 +1127,9 @@ def scale_bias_act_backward(dy, y, gamma, act=None, dx=None, dres=None, dbeta=No
     if dbeta is not None:
         if N * HxW == 0:   # a sum over nothing (the entry point writes nothing on an empty problem)
             dbeta.zero_()
-        ws = _workspace(dy.device, scale_bias_act_workspace_bytes(N, C, HxW), workspace)
-    fn = "sd_scale_bias_act_bwd" if dy.dtype == torch.float32 else "sd_scale_bias_act_bwd_f16"
-    lib().call(fn, _p(dy), _p(y), _p(gamma), _p(dx), _p(dres), _p(dbeta), N, C, ctypes.c_long(HxW), a, _p(ws),
-               ctypes.c_size_t(ws.numel() if ws is not None else 0), _stream())
+        ws = _ws(dy.device, workspace, "sd_scale_bias_act_workspace_bytes", N, C, HxW)
+    _call(_fn("sd_scale_bias_act_bwd", dy), dy, y, gamma, dx, dres, dbeta, N, C, HxW, a, ws,
+          ws.numel() if ws is not None else 0)
     return dx, dres, dbeta
 
 
@@ -1269,12 +1211,10 @@ def _ftd_shapes(shapes):
 
 
 def _ftd_tensor(t, name, dtype, shape=None):
+    """_chk for a 4D level that may be float32 or float16: of `dtype`, or with dtype None of either"""
     if not isinstance(t, torch.Tensor) or t.dtype not in _SBA_DTYPES:
         raise TypeError("%s must be a float32 or float16 torch.Tensor" % name)
-    _chk(t, name, dtype=dtype or t.dtype, ndim=4)
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    return t
+    return _chk(t, name, dtype=dtype or t.dtype, ndim=4, shape=shape)
 
 
 def fpn_topdown_forward(top, laterals, outs=None):
@@ -1296,8 +1236,7 @@ def fpn_topdown_forward(top, laterals, outs=None):
             raise ValueError("outs must have %d entries, got %d" % (len(laterals), len(outs)))
         for k, t in enumerate(outs):
             _ftd_tensor(t, "outs[%d]" % k, top.dtype, laterals[k].shape)
-    fn = "sd_fpn_topdown_fwd" if top.dtype == torch.float32 else "sd_fpn_topdown_fwd_f16"
-    lib().call(fn, _p(top), _parr(laterals), _parr(outs), N, C, _iarr(hs), _iarr(ws), len(shapes), _stream())
+    _call(_fn("sd_fpn_topdown_fwd", top), top, _parr(laterals), _parr(outs), N, C, _iarr(hs), _iarr(ws), len(shapes))
     return outs
 
 
@@ -1340,8 +1279,7 @@ def fpn_topdown_backward(grads, shapes, d_top=None, d_laterals=None, want_finest
             buf = ret = _ftd_tensor(t, "d_laterals[%d]" % k, g_fin.dtype, shapes[k + 1])
         table.append(buf)
         result.append(ret)
-    fn = "sd_fpn_topdown_bwd" if g_fin.dtype == torch.float32 else "sd_fpn_topdown_bwd_f16"
-    lib().call(fn, _parr(grads), _p(d_top), _parr(table), N, C, _iarr(hs), _iarr(ws), L, _stream())
+    _call(_fn("sd_fpn_topdown_bwd", g_fin), _parr(grads), d_top, _parr(table), N, C, _iarr(hs), _iarr(ws), L)
     return d_top, result
 
 
@@ -1377,7 +1315,7 @@ def fpn_topdown(top, laterals):
 # _contrib_SyncBatchNorm  (operator_cxx/contrib/sync_batch_norm-inl.h)
 # --------------------------------------------------------------------------------------------------
 def sync_bn_workspace_bytes(N, C, HxW):
-    return int(lib().cdll.sd_sync_bn_workspace_bytes(int(N), int(C), ctypes.c_long(int(HxW))))
+    return _query("sd_sync_bn_workspace_bytes", int(N), int(C), int(HxW))
 
 
 def _sbn_dims(x, name="data"):
@@ -1390,14 +1328,6 @@ def _sbn_dims(x, name="data"):
     return N, C, (x.numel() // (N * C) if N * C else 0)
 
 
-def _sbn_vec(t, name, C, lead=()):
-    """a float32 per-channel array of shape lead + (C,)"""
-    _chk(t, name)
-    if tuple(t.shape) != tuple(lead) + (C,):
-        raise ValueError("%s must have shape %s, got %s" % (name, tuple(lead) + (C,), tuple(t.shape)))
-    return t
-
-
 def _sbn_parts(t, name, C):
     _chk(t, name, ndim=3)
     if t.shape[0] < 1 or tuple(t.shape[1:]) != (2, C):
@@ -1405,22 +1335,13 @@ def _sbn_parts(t, name, C):
     return int(t.shape[0])
 
 
-def _sbn_new(x, shape):
-    return torch.empty(shape, device=x.device, dtype=torch.float32)
-
-
-def _sbn_fn(name, x):
-    return name if x.dtype == torch.float32 else name + "_f16"
-
-
 def sync_bn_stats(x, part=None, workspace=None):
     """sd_sync_bn_stats: x (N,C,...) -> part (2,C) float32 = the rank's per-channel mean and biased variance about
     that mean."""
     N, C, HxW = _sbn_dims(x)
-    part = _sbn_new(x, (2, C)) if part is None else _sbn_vec(part, "part", C, (2,))
-    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
-    lib().call(_sbn_fn("sd_sync_bn_stats", x), _p(x), _p(part), N, C, ctypes.c_long(HxW), _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    part = _out(part, "part", (2, C), x.device)
+    ws = _ws(x.device, workspace, "sd_sync_bn_workspace_bytes", N, C, HxW)
+    _call(_fn("sd_sync_bn_stats", x), x, part, N, C, HxW, ws, ws.numel())
     return part
 
 
@@ -1428,15 +1349,14 @@ def sync_bn_apply(x, parts, gamma, beta, eps=1e-3, fix_gamma=True, y=None, mean=
     """sd_sync_bn_apply: parts (W,2,C), the ranks' statistics in rank order -> y, mean (C), var (C)."""
     N, C, HxW = _sbn_dims(x)
     W = _sbn_parts(parts, "parts", C)
-    _sbn_vec(gamma, "gamma", C)
-    _sbn_vec(beta, "beta", C)
-    y = torch.empty_like(x) if y is None else _sba_like(y, "y", x)
-    mean = _sbn_new(x, (C,)) if mean is None else _sbn_vec(mean, "mean", C)
-    var = _sbn_new(x, (C,)) if var is None else _sbn_vec(var, "var", C)
-    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
-    lib().call(_sbn_fn("sd_sync_bn_apply", x), _p(x), _p(parts), W, _p(gamma), _p(beta), _p(y), _p(mean), _p(var), N,
-               C, ctypes.c_long(HxW), float(eps), int(bool(fix_gamma)), _p(ws), ctypes.c_size_t(ws.numel()),
-               _stream())
+    _chk(gamma, "gamma", shape=(C,))
+    _chk(beta, "beta", shape=(C,))
+    y = _out(y, "y", x.shape, x.device, x.dtype)
+    mean = _out(mean, "mean", (C,), x.device)
+    var = _out(var, "var", (C,), x.device)
+    ws = _ws(x.device, workspace, "sd_sync_bn_workspace_bytes", N, C, HxW)
+    _call(_fn("sd_sync_bn_apply", x), x, parts, W, gamma, beta, y, mean, var, N, C, HxW, eps, bool(fix_gamma), ws,
+          ws.numel())
     return y, mean, var
 
 
@@ -1444,22 +1364,21 @@ def sync_bn_infer_forward(x, gamma, beta, moving_mean, moving_var, eps=1e-3, fix
     """sd_sync_bn_infer_fwd: the scale-shift of the moving statistics (sync_batch_norm-inl.h:359-363)."""
     N, C, HxW = _sbn_dims(x)
     for t, name in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_var, "moving_var")):
-        _sbn_vec(t, name, C)
-    y = torch.empty_like(x) if y is None else _sba_like(y, "y", x)
-    lib().call(_sbn_fn("sd_sync_bn_infer_fwd", x), _p(x), _p(gamma), _p(beta), _p(moving_mean), _p(moving_var),
-               _p(y), N, C, ctypes.c_long(HxW), float(eps), int(bool(fix_gamma)), _stream())
+        _chk(t, name, shape=(C,))
+    y = _out(y, "y", x.shape, x.device, x.dtype)
+    _call(_fn("sd_sync_bn_infer_fwd", x), x, gamma, beta, moving_mean, moving_var, y, N, C, HxW, eps,
+          bool(fix_gamma))
     return y
 
 
 def sync_bn_bwd_stats(dy, x, mean, bpart=None, workspace=None):
     """sd_sync_bn_bwd_stats: -> bpart (2,C) float32 = sum dy and sum dy * (x - mean) over the rank's elements."""
     N, C, HxW = _sbn_dims(x)
-    _sba_like(dy, "dy", x)
-    _sbn_vec(mean, "mean", C)
-    bpart = _sbn_new(x, (2, C)) if bpart is None else _sbn_vec(bpart, "bpart", C, (2,))
-    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
-    lib().call(_sbn_fn("sd_sync_bn_bwd_stats", x), _p(dy), _p(x), _p(mean), _p(bpart), N, C, ctypes.c_long(HxW),
-               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    _chk(dy, "dy", x.dtype, shape=x.shape)
+    _chk(mean, "mean", shape=(C,))
+    bpart = _out(bpart, "bpart", (2, C), x.device)
+    ws = _ws(x.device, workspace, "sd_sync_bn_workspace_bytes", N, C, HxW)
+    _call(_fn("sd_sync_bn_bwd_stats", x), dy, x, mean, bpart, N, C, HxW, ws, ws.numel())
     return bpart
 
 
@@ -1469,16 +1388,16 @@ def sync_bn_bwd_apply(dy, x, mean, var, gamma, bparts, rank=0, eps=1e-3, fix_gam
     """sd_sync_bn_bwd_apply: bparts (W,2,C) in rank order -> dx, dgamma, dbeta (this rank's, written not
     accumulated; None with param_grads=False).  moving_mean / moving_var, when given, are updated in place."""
     N, C, HxW = _sbn_dims(x)
-    _sba_like(dy, "dy", x)
+    _chk(dy, "dy", x.dtype, shape=x.shape)
     W = _sbn_parts(bparts, "bparts", C)
     if not 0 <= int(rank) < W:
         raise ValueError("rank %d is outside 0..%d" % (rank, W - 1))
     for t, name in ((mean, "mean"), (var, "var"), (gamma, "gamma")):
-        _sbn_vec(t, name, C)
-    dx = torch.empty_like(x) if dx is None else _sba_like(dx, "dx", x)
+        _chk(t, name, shape=(C,))
+    dx = _out(dx, "dx", x.shape, x.device, x.dtype)
     if param_grads:
-        dgamma = _sbn_new(x, (C,)) if dgamma is None else _sbn_vec(dgamma, "dgamma", C)
-        dbeta = _sbn_new(x, (C,)) if dbeta is None else _sbn_vec(dbeta, "dbeta", C)
+        dgamma = _out(dgamma, "dgamma", (C,), x.device)
+        dbeta = _out(dbeta, "dbeta", (C,), x.device)
         if N * HxW == 0:   # sums over nothing (the entry point writes nothing on an empty problem)
             dgamma.zero_()
             dbeta.zero_()
@@ -1487,12 +1406,11 @@ def sync_bn_bwd_apply(dy, x, mean, var, gamma, bparts, rank=0, eps=1e-3, fix_gam
     if (moving_mean is None) != (moving_var is None):
         raise ValueError("moving_mean and moving_var go together")
     if moving_mean is not None:
-        _sbn_vec(moving_mean, "moving_mean", C)
-        _sbn_vec(moving_var, "moving_var", C)
-    ws = _workspace(x.device, sync_bn_workspace_bytes(N, C, HxW), workspace)
-    lib().call(_sbn_fn("sd_sync_bn_bwd_apply", x), _p(dy), _p(x), _p(mean), _p(var), _p(gamma), _p(bparts), W,
-               int(rank), _p(dx), _p(dgamma), _p(dbeta), _p(moving_mean), _p(moving_var), float(momentum), N, C,
-               ctypes.c_long(HxW), float(eps), int(bool(fix_gamma)), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+        _chk(moving_mean, "moving_mean", shape=(C,))
+        _chk(moving_var, "moving_var", shape=(C,))
+    ws = _ws(x.device, workspace, "sd_sync_bn_workspace_bytes", N, C, HxW)
+    _call(_fn("sd_sync_bn_bwd_apply", x), dy, x, mean, var, gamma, bparts, W, int(rank), dx, dgamma, dbeta,
+          moving_mean, moving_var, momentum, N, C, HxW, eps, bool(fix_gamma), ws, ws.numel())
     return dx, dgamma, dbeta
 
 
@@ -1562,11 +1480,11 @@ def sync_batch_norm(x, gamma, beta, eps=1e-3, fix_gamma=True, gather=None, movin
 # sigmoid_cross_entropy{-inl.h,.cu}; models/maskrcnn/builder.py:278-313)
 # --------------------------------------------------------------------------------------------------
 def sigmoid_cross_entropy_workspace_bytes(n, k):
-    return int(lib().cdll.sd_sigmoid_ce_workspace_bytes(ctypes.c_long(int(n)), ctypes.c_long(int(k))))
+    return _query("sd_sigmoid_ce_workspace_bytes", int(n), int(k))
 
 
 def mask_loss_workspace_bytes(R, K, P):
-    return int(lib().cdll.sd_mask_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
+    return _query("sd_mask_loss_workspace_bytes", int(R), int(K), int(P))
 
 
 def _ce_rows(data, label):
@@ -1580,15 +1498,6 @@ def _ce_rows(data, label):
     return n, (data.numel() // n if n else 0)
 
 
-def _ce_out(t, name, numel, dev, shape):
-    if t is None:
-        return torch.empty(shape, device=dev, dtype=torch.float32)
-    _chk(t, name)
-    if t.numel() != numel:
-        raise ValueError("%s needs %d floats, got %d" % (name, numel, t.numel()))
-    return t
-
-
 def sigmoid_cross_entropy_forward(data, label, *, full=False, out=None, loss=None, loss_sum=None, count=None,
                                   count_sum=None, workspace=None):
     """SigmoidCrossEntropy forward (sigmoid_cross_entropy.cu:44-104): data / label (n, ...) rows -> out, loss_sum,
@@ -1597,20 +1506,19 @@ def sigmoid_cross_entropy_forward(data, label, *, full=False, out=None, loss=Non
     ignores its element whatever the logit is.  out is NOT scaled by grad_scale (only the gradient is)."""
     n, k = _ce_rows(data, label)
     dev = data.device
-    out = _ce_out(out, "out", n, dev, (n,))
-    loss_sum = _ce_out(loss_sum, "loss_sum", n, dev, (n,))
-    count_sum = _ce_out(count_sum, "count_sum", n, dev, (n,))
+    out = _out(out, "out", (n,), dev, flat=True)
+    loss_sum = _out(loss_sum, "loss_sum", (n,), dev, flat=True)
+    count_sum = _out(count_sum, "count_sum", (n,), dev, flat=True)
     if full or loss is not None or count is not None:
-        loss = _ce_out(loss, "loss", n * k, dev, data.shape)
-        count = _ce_out(count, "count", n * k, dev, data.shape)
+        loss = _out(loss, "loss", data.shape, dev, flat=True)
+        count = _out(count, "count", data.shape, dev, flat=True)
     if n * k == 0:        # rows of nothing: an empty sum over an empty count (the entry point writes nothing)
         out.zero_()
         loss_sum.zero_()
         count_sum.fill_(1e-5)
         return (out, loss, loss_sum, count, count_sum) if loss is not None else (out, loss_sum, count_sum)
-    ws = _workspace(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
-    lib().call("sd_sigmoid_ce_fwd", _p(data), _p(label), _p(out), _p(loss), _p(loss_sum), _p(count), _p(count_sum),
-               ctypes.c_long(n), ctypes.c_long(k), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_sigmoid_ce_workspace_bytes", n, k)
+    _call("sd_sigmoid_ce_fwd", data, label, out, loss, loss_sum, count, count_sum, n, k, ws, ws.numel())
     if loss is not None:
         return out, loss, loss_sum, count, count_sum
     return out, loss_sum, count_sum
@@ -1623,16 +1531,15 @@ def sigmoid_cross_entropy_backward(data, label, grad_scale=1.0, *, d_data=None, 
     no part in it.  Returns (d_data, count_sum); `count` (full size) is written only when passed in."""
     n, k = _ce_rows(data, label)
     dev = data.device
-    d_data = _ce_out(d_data, "d_data", n * k, dev, data.shape)
-    count_sum = _ce_out(count_sum, "count_sum", n, dev, (n,))
+    d_data = _out(d_data, "d_data", data.shape, dev, flat=True)
+    count_sum = _out(count_sum, "count_sum", (n,), dev, flat=True)
     if count is not None:
-        count = _ce_out(count, "count", n * k, dev, data.shape)
+        count = _chk(count, "count", numel=n * k)
     if n * k == 0:
         count_sum.fill_(1e-5)
         return d_data, count_sum
-    ws = _workspace(dev, sigmoid_cross_entropy_workspace_bytes(n, k), workspace)
-    lib().call("sd_sigmoid_ce_bwd", _p(data), _p(label), _p(d_data), _p(count), _p(count_sum), ctypes.c_long(n),
-               ctypes.c_long(k), float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_sigmoid_ce_workspace_bytes", n, k)
+    _call("sd_sigmoid_ce_bwd", data, label, d_data, count, count_sum, n, k, grad_scale, ws, ws.numel())
     return d_data, count_sum
 
 
@@ -1657,15 +1564,14 @@ def mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, workspac
     the gathered row.  A cls that is NaN, negative or >= K ignores its RoI.  Returns (out, count_sum), (1,) each."""
     R, K, P = _mask_dims(logits, cls, target)
     dev = logits.device
-    out = _ce_out(out, "out", 1, dev, (1,))
-    count_sum = _ce_out(count_sum, "count_sum", 1, dev, (1,))
+    out = _out(out, "out", (1,), dev, flat=True)
+    count_sum = _out(count_sum, "count_sum", (1,), dev, flat=True)
     if R * K * P == 0:    # an empty sum over an empty count (the entry point writes nothing)
         out.zero_()
         count_sum.fill_(1e-5)
         return out, count_sum
-    ws = _workspace(dev, mask_loss_workspace_bytes(R, K, P), workspace)
-    lib().call("sd_mask_loss_fwd", _p(logits), _p(cls), _p(target), _p(out), _p(count_sum), R, K, ctypes.c_long(P),
-               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_mask_loss_workspace_bytes", R, K, P)
+    _call("sd_mask_loss_fwd", logits, cls, target, out, count_sum, R, K, P, ws, ws.numel())
     return out, count_sum
 
 
@@ -1673,10 +1579,9 @@ def mask_loss_backward(logits, cls, target, grad_scale=1.0, *, d_logits=None, wo
     """Backward of mask_loss_forward: ALL of d_logits (the shape of logits) is written once -- +0.0 in the planes
     that are not selected and in ignored RoIs, the SigmoidCrossEntropy gradient in plane int(cls[r])."""
     R, K, P = _mask_dims(logits, cls, target)
-    d_logits = _ce_out(d_logits, "d_logits", R * K * P, logits.device, logits.shape)
-    ws = _workspace(logits.device, mask_loss_workspace_bytes(R, K, P), workspace)
-    lib().call("sd_mask_loss_bwd", _p(logits), _p(cls), _p(target), _p(d_logits), R, K, ctypes.c_long(P),
-               float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    d_logits = _out(d_logits, "d_logits", logits.shape, logits.device, flat=True)
+    ws = _ws(logits.device, workspace, "sd_mask_loss_workspace_bytes", R, K, P)
+    _call("sd_mask_loss_bwd", logits, cls, target, d_logits, R, K, P, grad_scale, ws, ws.numel())
     return d_logits
 
 
@@ -1684,11 +1589,11 @@ def mask_loss_backward(logits, cls, target, grad_scale=1.0, *, d_logits=None, wo
 # The Mask Scoring R-CNN training head  (models/msrcnn/builder.py:143-168, :383-424; models/msrcnn/maskiou_compute.py)
 # --------------------------------------------------------------------------------------------------
 def msrcnn_mask_loss_workspace_bytes(R, K, P):
-    return int(lib().cdll.sd_msrcnn_mask_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
+    return _query("sd_msrcnn_mask_loss_workspace_bytes", int(R), int(K), int(P))
 
 
 def maskiou_loss_workspace_bytes(R, K, P):
-    return int(lib().cdll.sd_maskiou_loss_workspace_bytes(int(R), int(K), ctypes.c_long(int(P))))
+    return _query("sd_maskiou_loss_workspace_bytes", int(R), int(K), int(P))
 
 
 def msrcnn_mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, prob=None, workspace=None):
@@ -1698,17 +1603,16 @@ def msrcnn_mask_loss_forward(logits, cls, target, *, out=None, count_sum=None, p
     RoI whose cls is NaN, negative or >= K.  Returns (out, count_sum, prob)."""
     R, K, P = _mask_dims(logits, cls, target)
     dev = logits.device
-    out = _ce_out(out, "out", 1, dev, (1,))
-    count_sum = _ce_out(count_sum, "count_sum", 1, dev, (1,))
-    prob = _ce_out(prob, "prob", R * P, dev, (R,) + tuple(logits.shape[2:]))
+    out = _out(out, "out", (1,), dev, flat=True)
+    count_sum = _out(count_sum, "count_sum", (1,), dev, flat=True)
+    prob = _out(prob, "prob", (R,) + tuple(logits.shape[2:]), dev, flat=True)
     if R * K * P == 0:    # an empty sum over an empty count (the entry point writes nothing)
         out.zero_()
         count_sum.fill_(1e-5)
         prob.zero_()
         return out, count_sum, prob
-    ws = _workspace(dev, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
-    lib().call("sd_msrcnn_mask_loss_fwd", _p(logits), _p(cls), _p(target), _p(out), _p(count_sum), _p(prob), R, K,
-               ctypes.c_long(P), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_msrcnn_mask_loss_workspace_bytes", R, K, P)
+    _call("sd_msrcnn_mask_loss_fwd", logits, cls, target, out, count_sum, prob, R, K, P, ws, ws.numel())
     return out, count_sum, prob
 
 
@@ -1718,13 +1622,10 @@ def msrcnn_mask_loss_backward(logits, cls, target, d_prob=None, grad_scale=1.0, 
     gradient that reached prob (None: none did; the result is then mask_loss_backward's, bit for bit)."""
     R, K, P = _mask_dims(logits, cls, target)
     if d_prob is not None:
-        _chk(d_prob, "d_prob")
-        if d_prob.numel() != R * P:
-            raise ValueError("d_prob needs %d floats, got %d" % (R * P, d_prob.numel()))
-    d_logits = _ce_out(d_logits, "d_logits", R * K * P, logits.device, logits.shape)
-    ws = _workspace(logits.device, msrcnn_mask_loss_workspace_bytes(R, K, P), workspace)
-    lib().call("sd_msrcnn_mask_loss_bwd", _p(logits), _p(cls), _p(target), _p(d_prob), _p(d_logits), R, K,
-               ctypes.c_long(P), float(grad_scale), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+        _chk(d_prob, "d_prob", numel=R * P)
+    d_logits = _out(d_logits, "d_logits", logits.shape, logits.device, flat=True)
+    ws = _ws(logits.device, workspace, "sd_msrcnn_mask_loss_workspace_bytes", R, K, P)
+    _call("sd_msrcnn_mask_loss_bwd", logits, cls, target, d_prob, d_logits, R, K, P, grad_scale, ws, ws.numel())
     return d_logits
 
 
@@ -1757,18 +1658,17 @@ def maskiou_loss_forward(iou_pred, prob, target, ratio, cls, *, iou_target=None,
     whose cls names a column."""
     R, K, P = _maskiou_dims(iou_pred, cls, prob, target, ratio)
     dev = iou_pred.device
-    iou_target = _ce_out(iou_target, "iou_target", R, dev, (R,))
-    weight = _ce_out(weight, "weight", R, dev, (R,))
-    loss = _ce_out(loss, "loss", 1, dev, (1,))
-    weight_sum = _ce_out(weight_sum, "weight_sum", 1, dev, (1,))
+    iou_target = _out(iou_target, "iou_target", (R,), dev, flat=True)
+    weight = _out(weight, "weight", (R,), dev, flat=True)
+    loss = _out(loss, "loss", (1,), dev, flat=True)
+    weight_sum = _out(weight_sum, "weight_sum", (1,), dev, flat=True)
     if R * K * P == 0:    # nothing to look at: empty sums (the entry point writes nothing)
         for t in (iou_target, weight, loss, weight_sum):
             t.zero_()
         return iou_target, weight, loss, weight_sum
-    ws = _workspace(dev, maskiou_loss_workspace_bytes(R, K, P), workspace)
-    lib().call("sd_maskiou_loss_fwd", _p(iou_pred), _p(prob), _p(target), _p(ratio), _p(cls), _p(iou_target),
-               _p(weight), _p(loss), _p(weight_sum), R, K, ctypes.c_long(P), _p(ws), ctypes.c_size_t(ws.numel()),
-               _stream())
+    ws = _ws(dev, workspace, "sd_maskiou_loss_workspace_bytes", R, K, P)
+    _call("sd_maskiou_loss_fwd", iou_pred, prob, target, ratio, cls, iou_target, weight, loss, weight_sum, R, K, P,
+          ws, ws.numel())
     return iou_target, weight, loss, weight_sum
 
 
@@ -1778,12 +1678,9 @@ def maskiou_loss_backward(iou_pred, cls, iou_target, weight, weight_sum, grad_sc
     ratio."""
     R, K, _ = _maskiou_dims(iou_pred, cls)
     for t, name, n in ((iou_target, "iou_target", R), (weight, "weight", R), (weight_sum, "weight_sum", 1)):
-        _chk(t, name)
-        if t.numel() != n:
-            raise ValueError("%s needs %d floats, got %d" % (name, n, t.numel()))
-    d_iou_pred = _ce_out(d_iou_pred, "d_iou_pred", R * K, iou_pred.device, iou_pred.shape)
-    lib().call("sd_maskiou_loss_bwd", _p(iou_pred), _p(cls), _p(iou_target), _p(weight), _p(weight_sum),
-               _p(d_iou_pred), R, K, float(grad_scale), _stream())
+        _chk(t, name, numel=n)
+    d_iou_pred = _out(d_iou_pred, "d_iou_pred", iou_pred.shape, iou_pred.device, flat=True)
+    _call("sd_maskiou_loss_bwd", iou_pred, cls, iou_target, weight, weight_sum, d_iou_pred, R, K, grad_scale)
     return d_iou_pred
 
 
@@ -1804,8 +1701,7 @@ CrowdHumanTargets = collections.namedtuple(
 
 
 def crowdhuman_target_workspace_bytes(B, P, M):
-    lib().cdll.sd_crowdhuman_target_workspace_bytes.restype = ctypes.c_size_t
-    return int(lib().cdll.sd_crowdhuman_target_workspace_bytes(int(B), int(P), int(M)))
+    return _query("sd_crowdhuman_target_workspace_bytes", int(B), int(P), int(M))
 
 
 def crowdhuman_target(proposal, gt_bbox, mt_state, *, num_reg_class, image_rois, fg_fraction, fg_thresh,
@@ -1844,9 +1740,9 @@ def crowdhuman_target(proposal, gt_bbox, mt_state, *, num_reg_class, image_rois,
     sec = [torch.empty((B, S), **f32), torch.empty((B, S, W), **f32), torch.empty((B, S, W), **f32)] if double \
         else [None, None, None]
     count = torch.empty((B,), device=dev, dtype=torch.int32)
-    ws = _workspace(dev, crowdhuman_target_workspace_bytes(B, P, M), workspace)
-    lib().call("sd_crowdhuman_target", _p(proposal), _p(gt_bbox), B, P, M, 1 if double else 0, ctypes.byref(prm),
-               _p(mt_state), *[_p(t) for t in outs + sec], _p(count), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_crowdhuman_target_workspace_bytes", B, P, M)
+    _call("sd_crowdhuman_target", proposal, gt_bbox, B, P, M, 1 if double else 0, ctypes.byref(prm), mt_state,
+          *outs, *sec, count, ws, ws.numel())
     return CrowdHumanTargets(*(outs + sec + [count]))
 
 
@@ -1861,12 +1757,8 @@ def _emd_args(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bb
                        (bbox_sec_delta, "bbox_sec_delta", R * D), (bbox_target, "bbox_target", R * D),
                        (bbox_sec_target, "bbox_sec_target", R * D), (bbox_weight, "bbox_weight", R * D),
                        (bbox_sec_weight, "bbox_sec_weight", R * D)):
-        _chk(t, name)
-        if t.numel() != n:
-            raise ValueError("%s needs %d floats, got %d" % (name, n, t.numel()))
-    ptrs = [_p(t) for t in (cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
-                            bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)]
-    return R, K, D, ptrs
+        _chk(t, name, numel=n)
+    return R, K, D
 
 
 def emd_loss_forward(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
@@ -1875,19 +1767,18 @@ def emd_loss_forward(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_de
     """DoublePredBboxHead.emd_loss (models/crowdhuman/builder.py:254-306) in one launch: logits (R, K), labels (R,),
     deltas / targets / weights (R, 4 K') -> loss (1,) = mean over the rows of min(L1, L2), the sums of the two ways
     to pair the heads with the labels.  return_pairing: also pairing (R,) int32, 1 where L1 <= L2, else 2."""
-    R, K, D, ptrs = _emd_args(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
-                              bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)
+    ts = (cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
+          bbox_sec_target, bbox_weight, bbox_sec_weight)
+    R, K, D = _emd_args(*ts)
     dev = cls_logit.device
-    loss = _ce_out(loss, "loss", 1, dev, (1,))
+    loss = _out(loss, "loss", (1,), dev, flat=True)
     if return_pairing or pairing is not None:
         if pairing is None:
             pairing = torch.empty((R,), device=dev, dtype=torch.int32)
-        _chk(pairing, "pairing", dtype=torch.int32)
-        if pairing.numel() != R:
-            raise ValueError("pairing needs %d int32, got %d" % (R, pairing.numel()))
+        _chk(pairing, "pairing", dtype=torch.int32, numel=R)
     if R == 0:
         loss.zero_()
-    lib().call("sd_emd_loss_fwd", *ptrs, R, K, D, float(smooth_l1_scalar), _p(loss), _p(pairing), _stream())
+    _call("sd_emd_loss_fwd", *ts, R, K, D, smooth_l1_scalar, loss, pairing)
     return (loss, pairing) if return_pairing else loss
 
 
@@ -1896,15 +1787,16 @@ def emd_loss_backward(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_d
                       d_cls_logit=None, d_cls_sec_logit=None, d_bbox_delta=None, d_bbox_sec_delta=None):
     """The four gradients of emd_loss_forward, written once: (d_cls_logit, d_cls_sec_logit, d_bbox_delta,
     d_bbox_sec_delta); only the winning pairing of a row contributes, scaled by grad_scale / R."""
-    R, K, D, ptrs = _emd_args(cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta,
-                              bbox_target, bbox_sec_target, bbox_weight, bbox_sec_weight)
+    ts = (cls_logit, cls_sec_logit, cls_label, cls_sec_label, bbox_delta, bbox_sec_delta, bbox_target,
+          bbox_sec_target, bbox_weight, bbox_sec_weight)
+    R, K, D = _emd_args(*ts)
     dev = cls_logit.device
-    d_cls_logit = _ce_out(d_cls_logit, "d_cls_logit", R * K, dev, (R, K))
-    d_cls_sec_logit = _ce_out(d_cls_sec_logit, "d_cls_sec_logit", R * K, dev, (R, K))
-    d_bbox_delta = _ce_out(d_bbox_delta, "d_bbox_delta", R * D, dev, (R, D))
-    d_bbox_sec_delta = _ce_out(d_bbox_sec_delta, "d_bbox_sec_delta", R * D, dev, (R, D))
-    lib().call("sd_emd_loss_bwd", *ptrs, R, K, D, float(smooth_l1_scalar), float(grad_scale), _p(d_cls_logit),
-               _p(d_cls_sec_logit), _p(d_bbox_delta), _p(d_bbox_sec_delta), _stream())
+    d_cls_logit = _out(d_cls_logit, "d_cls_logit", (R, K), dev, flat=True)
+    d_cls_sec_logit = _out(d_cls_sec_logit, "d_cls_sec_logit", (R, K), dev, flat=True)
+    d_bbox_delta = _out(d_bbox_delta, "d_bbox_delta", (R, D), dev, flat=True)
+    d_bbox_sec_delta = _out(d_bbox_sec_delta, "d_bbox_sec_delta", (R, D), dev, flat=True)
+    _call("sd_emd_loss_bwd", *ts, R, K, D, smooth_l1_scalar, grad_scale, d_cls_logit, d_cls_sec_logit, d_bbox_delta,
+          d_bbox_sec_delta)
     return d_cls_logit, d_cls_sec_logit, d_bbox_delta, d_bbox_sec_delta
 
 
@@ -1944,11 +1836,11 @@ RpnLossOut = collections.namedtuple("RpnLossOut", "prob reg_loss state")
 
 
 def rpn_loss_workspace_bytes(N, A, HW):
-    return int(lib().cdll.sd_rpn_loss_workspace_bytes(int(N), int(A), ctypes.c_long(int(HW))))
+    return _query("sd_rpn_loss_workspace_bytes", int(N), int(A), int(HW))
 
 
 def rcnn_loss_workspace_bytes(R):
-    return int(lib().cdll.sd_rcnn_loss_workspace_bytes(int(R)))
+    return _query("sd_rcnn_loss_workspace_bytes", int(R))
 
 
 def loss_state(device=None):
@@ -2013,14 +1905,10 @@ def _rpn_loss_levels(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight)
         hws.append(hw)
     HW = sum(hws)
     if cls_logits is not None:
-        _chk(cls_label, "cls_label")
-        if cls_label.numel() != N * A * HW:
-            raise ValueError("cls_label needs %d floats, got %d" % (N * A * HW, cls_label.numel()))
+        _chk(cls_label, "cls_label", numel=N * A * HW)
     if bbox_deltas is not None:
-        for t, name in ((reg_target, "reg_target"), (reg_weight, "reg_weight")):
-            _chk(t, name)
-            if t.numel() != N * 4 * A * HW:
-                raise ValueError("%s needs %d floats, got %d" % (name, N * 4 * A * HW, t.numel()))
+        _chk(reg_target, "reg_target", numel=N * 4 * A * HW)
+        _chk(reg_weight, "reg_weight", numel=N * 4 * A * HW)
     return N, A, HW, (ctypes.c_long * L)(*hws)
 
 
@@ -2038,22 +1926,21 @@ def rpn_loss_forward(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight,
     lead = cls_logits if cls_logits is not None else bbox_deltas
     dev = lead[0].device
     if cls_logits is not None and (want_prob or prob is not None):
-        prob = _fcos_out(prob, "prob", (N, 2, A, HW), dev)
+        prob = _out(prob, "prob", (N, 2, A, HW), dev, flat=True)
     else:
         prob = None
     if bbox_deltas is not None and (want_reg_loss or reg_loss is not None):
-        reg_loss = _fcos_out(reg_loss, "reg_loss", (N, 4 * A, HW), dev)
+        reg_loss = _out(reg_loss, "reg_loss", (N, 4 * A, HW), dev, flat=True)
     else:
         reg_loss = None
-    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    state = _out(state, "state", (4,), dev, torch.int32, flat=True)
     if N * A * HW == 0:
         state.zero_()
         return RpnLossOut(prob, reg_loss, state)
-    ws = _workspace(dev, rpn_loss_workspace_bytes(N, A, HW), workspace)
-    lib().call("sd_rpn_loss_fwd", None if cls_logits is None else _parr(cls_logits),
-               None if bbox_deltas is None else _parr(bbox_deltas), hws, len(lead), _p(cls_label), _p(reg_target),
-               _p(reg_weight), N, A, float(ignore_label), float(sigma), _p(prob), _p(reg_loss), _p(state), _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_rpn_loss_workspace_bytes", N, A, HW)
+    _call("sd_rpn_loss_fwd", None if cls_logits is None else _parr(cls_logits),
+          None if bbox_deltas is None else _parr(bbox_deltas), hws, len(lead), cls_label, reg_target, reg_weight, N, A,
+          ignore_label, sigma, prob, reg_loss, state, ws, ws.numel())
     return RpnLossOut(prob, reg_loss, state)
 
 
@@ -2085,11 +1972,10 @@ def rpn_loss_backward(cls_logits, bbox_deltas, cls_label, reg_target, reg_weight
     if cls_logits is not None:
         _chk(state, "state", dtype=torch.int32)
     lead = cls_logits if cls_logits is not None else bbox_deltas
-    lib().call("sd_rpn_loss_bwd", None if cls_logits is None else _parr(cls_logits),
-               None if bbox_deltas is None else _parr(bbox_deltas), hws, len(lead), _p(cls_label), _p(reg_target),
-               _p(reg_weight), N, A, float(ignore_label), float(sigma), float(cls_grad_scale), float(reg_grad_scale),
-               _p(state), None if d_cls is None else _parr(d_cls), None if d_delta is None else _parr(d_delta),
-               _stream())
+    _call("sd_rpn_loss_bwd", None if cls_logits is None else _parr(cls_logits),
+          None if bbox_deltas is None else _parr(bbox_deltas), hws, len(lead), cls_label, reg_target, reg_weight, N, A,
+          ignore_label, sigma, cls_grad_scale, reg_grad_scale, state, None if d_cls is None else _parr(d_cls),
+          None if d_delta is None else _parr(d_delta))
     return d_cls, d_delta
 
 
@@ -2136,18 +2022,14 @@ def _rcnn_loss_args(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight):
     if cls_logit is not None:
         _chk(cls_logit, "cls_logit", ndim=2)
         R, K = int(cls_logit.shape[0]), int(cls_logit.shape[1])
-        _chk(cls_label, "cls_label")
-        if cls_label.numel() != R:
-            raise ValueError("cls_label needs %d floats, got %d" % (R, cls_label.numel()))
+        _chk(cls_label, "cls_label", numel=R)
     if bbox_delta is not None:
         _chk(bbox_delta, "bbox_delta", ndim=2)
         if R is not None and int(bbox_delta.shape[0]) != R:
             raise ValueError("bbox_delta should have %d rows, got %d" % (R, int(bbox_delta.shape[0])))
         R, D = int(bbox_delta.shape[0]), int(bbox_delta.shape[1])
-        for t, name in ((bbox_target, "bbox_target"), (bbox_weight, "bbox_weight")):
-            _chk(t, name)
-            if t.numel() != R * D:
-                raise ValueError("%s needs %d floats, got %d" % (name, R * D, t.numel()))
+        _chk(bbox_target, "bbox_target", numel=R * D)
+        _chk(bbox_weight, "bbox_weight", numel=R * D)
     if R is None:
         raise ValueError("cls_logit or bbox_delta must be given")
     return R, K if K is not None else 1, D if D is not None else 0
@@ -2163,21 +2045,20 @@ def rcnn_loss_forward(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight
     R, K, D = _rcnn_loss_args(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight)
     dev = (cls_logit if cls_logit is not None else bbox_delta).device
     if cls_logit is not None and (want_prob or prob is not None):
-        prob = _fcos_out(prob, "prob", (R, K), dev)
+        prob = _out(prob, "prob", (R, K), dev, flat=True)
     else:
         prob = None
     if bbox_delta is not None and (want_reg_loss or reg_loss is not None):
-        reg_loss = _fcos_out(reg_loss, "reg_loss", (R, D), dev)
+        reg_loss = _out(reg_loss, "reg_loss", (R, D), dev, flat=True)
     else:
         reg_loss = None
-    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    state = _out(state, "state", (4,), dev, torch.int32, flat=True)
     if R == 0:
         state.zero_()
         return RpnLossOut(prob, reg_loss, state)
-    ws = _workspace(dev, rcnn_loss_workspace_bytes(R), workspace)
-    lib().call("sd_rcnn_loss_fwd", _p(cls_logit), _p(cls_label), _p(bbox_delta), _p(bbox_target), _p(bbox_weight),
-               R, K, D, float(smooth_l1_scalar), _p(prob), _p(reg_loss), _p(state), _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_rcnn_loss_workspace_bytes", R)
+    _call("sd_rcnn_loss_fwd", cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight, R, K, D, smooth_l1_scalar,
+          prob, reg_loss, state, ws, ws.numel())
     return RpnLossOut(prob, reg_loss, state)
 
 
@@ -2190,16 +2071,15 @@ def rcnn_loss_backward(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weigh
     R, K, D = _rcnn_loss_args(cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight)
     dev = (cls_logit if cls_logit is not None else bbox_delta).device
     if cls_logit is not None:
-        d_cls_logit = _ce_out(d_cls_logit, "d_cls_logit", R * K, dev, (R, K))
+        d_cls_logit = _out(d_cls_logit, "d_cls_logit", (R, K), dev, flat=True)
         _chk(state, "state", dtype=torch.int32)
     else:
         d_cls_logit = None
-    d_bbox_delta = None if bbox_delta is None else _ce_out(d_bbox_delta, "d_bbox_delta", R * D, dev, (R, D))
+    d_bbox_delta = None if bbox_delta is None else _out(d_bbox_delta, "d_bbox_delta", (R, D), dev, flat=True)
     if R == 0:
         return d_cls_logit, d_bbox_delta
-    lib().call("sd_rcnn_loss_bwd", _p(cls_logit), _p(cls_label), _p(bbox_delta), _p(bbox_target), _p(bbox_weight),
-               R, K, D, float(smooth_l1_scalar), float(cls_grad_scale), float(reg_grad_scale), _p(state),
-               _p(d_cls_logit), _p(d_bbox_delta) if D else None, _stream())
+    _call("sd_rcnn_loss_bwd", cls_logit, cls_label, bbox_delta, bbox_target, bbox_weight, R, K, D, smooth_l1_scalar,
+          cls_grad_scale, reg_grad_scale, state, d_cls_logit, d_bbox_delta if D else None)
     return d_cls_logit, d_bbox_delta
 
 
@@ -2248,11 +2128,11 @@ def quant_int8_state(delay_quant=0, device=None):
 
 
 def quant_int8_workspace_bytes(n):
-    return int(lib().cdll.sd_quant_int8_workspace_bytes(ctypes.c_long(int(n))))
+    return _query("sd_quant_int8_workspace_bytes", int(n))
 
 
 def quant_int8_weights_workspace_bytes(T, n_total):
-    return int(lib().cdll.sd_quant_int8_weights_workspace_bytes(int(T), ctypes.c_long(int(n_total))))
+    return _query("sd_quant_int8_weights_workspace_bytes", int(T), int(n_total))
 
 
 def _q_aux(minmax, state):
@@ -2282,10 +2162,9 @@ def quantization_int8_forward(data, minmax, state, *, is_weight, is_train=True, 
     n = data.numel()
     if n == 0:
         return out
-    ws = _workspace(data.device, quant_int8_workspace_bytes(n), workspace)
-    lib().call("sd_quant_int8_fwd", _p(data), _p(out), _p(minmax), _p(state), ctypes.c_long(n), int(bool(is_weight)),
-               int(bool(is_train)), int(bool(fix_act_scale)), float(ema_decay), _p(ws), ctypes.c_size_t(ws.numel()),
-               _stream())
+    ws = _ws(data.device, workspace, "sd_quant_int8_workspace_bytes", n)
+    _call("sd_quant_int8_fwd", data, out, minmax, state, n, bool(is_weight), bool(is_train), bool(fix_act_scale),
+          ema_decay, ws, ws.numel())
     return out
 
 
@@ -2312,8 +2191,8 @@ def quantization_int8_backward(out_grad, data, minmax, *, is_weight, grad_mode="
         _chk(d_data, "d_data")
         if d_data.numel() != out_grad.numel():
             raise ValueError("d_data must have the size of out_grad")
-    lib().call("sd_quant_int8_bwd", _p(out_grad), _p(data) if clip else None, _p(minmax) if clip else None,
-               _p(d_data), ctypes.c_long(out_grad.numel()), int(clip), REQ[req], _stream())
+    _call("sd_quant_int8_bwd", out_grad, data if clip else None, minmax if clip else None, d_data, out_grad.numel(),
+          clip, REQ[req])
     return d_data
 
 
@@ -2357,10 +2236,8 @@ def quantization_int8_weights_forward(datas, minmaxes, states, *, is_train=True,
     n_total = sum(int(d.numel()) for d in datas)
     if T == 0 or n_total == 0:
         return outs
-    ws = _workspace(table.device, quant_int8_weights_workspace_bytes(T, n_total), workspace)
-    row = [ctypes.c_void_p(table[i].data_ptr()) for i in range(5)]
-    lib().call("sd_quant_int8_weights_fwd", row[0], row[1], row[2], row[3], row[4], T, ctypes.c_long(n_total),
-               int(bool(is_train)), int(bool(fix_act_scale)), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(table.device, workspace, "sd_quant_int8_weights_workspace_bytes", T, n_total)
+    _call("sd_quant_int8_weights_fwd", *table, T, n_total, bool(is_train), bool(fix_act_scale), ws, ws.numel())
     return outs
 
 
@@ -2404,29 +2281,17 @@ def fcos_num_locations(data_size, strides):
     """(HW, [H_l * W_l per level]) of the reference's location grid (input.py:99-107)."""
     h, w = (int(v) for v in data_size)
     L = len(strides)
-    levels, total = (ctypes.c_long * max(L, 1))(), ctypes.c_long(0)
-    lib().call("sd_fcos_num_locations", h, w, _iarr(strides), L, levels, ctypes.byref(total))
-    return int(total.value), [int(levels[i]) for i in range(L)]
+    levels, total = (ctypes.c_long * max(L, 1))(), (ctypes.c_long * 1)()
+    _call("sd_fcos_num_locations", h, w, _iarr(strides), L, levels, total)
+    return int(total[0]), [int(levels[i]) for i in range(L)]
 
 
 def fcos_target_workspace_bytes(N, HW):
-    return int(lib().cdll.sd_fcos_target_workspace_bytes(int(N), ctypes.c_long(int(HW))))
+    return _query("sd_fcos_target_workspace_bytes", int(N), int(HW))
 
 
 def fcos_loss_workspace_bytes(N, K, HW):
-    return int(lib().cdll.sd_fcos_loss_workspace_bytes(int(N), int(K), ctypes.c_long(int(HW))))
-
-
-def _fcos_out(t, name, shape, dev, dtype=torch.float32):
-    if t is None:
-        return torch.empty(shape, device=dev, dtype=dtype)
-    _chk(t, name, dtype=dtype)
-    n = 1
-    for d in shape:
-        n *= int(d)
-    if t.numel() != n:
-        raise ValueError("%s needs %d elements, got %d" % (name, n, t.numel()))
-    return t
+    return _query("sd_fcos_loss_workspace_bytes", int(N), int(K), int(HW))
 
 
 def fcos_target(gt_bbox, im_info, data_size, strides, num_classifier, *, ignore_offset=-1.0, ignore_label=-1.0,
@@ -2450,19 +2315,18 @@ def fcos_target(gt_bbox, im_info, data_size, strides, num_classifier, *, ignore_
         raise ValueError("the stage bounds need one entry per stride")
     HW, _ = fcos_num_locations(data_size, strides)
     dev = gt_bbox.device
-    centerness = _fcos_out(centerness, "centerness", (N, HW), dev)
-    offset = _fcos_out(offset, "offset", (N, 4, HW), dev)
-    cls_id = _fcos_out(cls_id, "cls_id", (N, HW), dev, torch.int32)
-    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    centerness = _out(centerness, "centerness", (N, HW), dev, flat=True)
+    offset = _out(offset, "offset", (N, 4, HW), dev, flat=True)
+    cls_id = _out(cls_id, "cls_id", (N, HW), dev, torch.int32, flat=True)
+    state = _out(state, "state", (4,), dev, torch.int32, flat=True)
     if dense or cls_dense is not None:
-        cls_dense = _fcos_out(cls_dense, "cls_dense", (N, K * HW), dev)
+        cls_dense = _out(cls_dense, "cls_dense", (N, K * HW), dev, flat=True)
     if N * HW == 0:       # the entry point writes nothing: the normalisers of an empty problem are zero
         state.zero_()
-    ws = _workspace(dev, fcos_target_workspace_bytes(N, HW), workspace)
-    lib().call("sd_fcos_target", _p(gt_bbox), _p(im_info), _p(centerness), _p(offset), _p(cls_id), _p(cls_dense),
-               _p(state), N, M, K, int(data_size[0]), int(data_size[1]), _iarr(strides),
-               None if stage_lower is None else _farr(stage_lower), None if stage_upper is None else _farr(stage_upper),
-               L, float(ignore_offset), float(ignore_label), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_fcos_target_workspace_bytes", N, HW)
+    _call("sd_fcos_target", gt_bbox, im_info, centerness, offset, cls_id, cls_dense, state, N, M, K,
+          int(data_size[0]), int(data_size[1]), _iarr(strides), None if stage_lower is None else _farr(stage_lower),
+          None if stage_upper is None else _farr(stage_upper), L, ignore_offset, ignore_label, ws, ws.numel())
     return FcosTargets(centerness, offset, cls_id, state, cls_dense)
 
 
@@ -2501,14 +2365,13 @@ def fcos_loss_forward(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25,
     without the one-hot labels: returns (3,) = centerness BCE, sigmoid focal, IoU -- the order of get_loss."""
     N, K, HW, hws = _fcos_levels(cls_logits, ctr_logits, off_preds, targets)
     dev = cls_logits[0].device
-    losses = _fcos_out(losses, "losses", (3,), dev)
+    losses = _out(losses, "losses", (3,), dev, flat=True)
     if N * K * HW == 0:
         return losses.zero_()
-    ws = _workspace(dev, fcos_loss_workspace_bytes(N, K, HW), workspace)
-    lib().call("sd_fcos_loss_fwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), hws, len(cls_logits),
-               _p(targets.centerness), _p(targets.offset), _p(targets.cls_id), _p(targets.state), _p(losses), N, K,
-               float(alpha), float(gamma), float(ignore_offset), float(ignore_label), _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_fcos_loss_workspace_bytes", N, K, HW)
+    _call("sd_fcos_loss_fwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), hws, len(cls_logits),
+          targets.centerness, targets.offset, targets.cls_id, targets.state, losses, N, K, alpha, gamma, ignore_offset,
+          ignore_label, ws, ws.numel())
     return losses
 
 
@@ -2517,24 +2380,14 @@ def fcos_loss_backward(cls_logits, ctr_logits, off_preds, targets, *, alpha=0.25
     """The gradients of fcos_loss_forward, written straight into per-level tensors of the inputs' shapes in ONE
     launch: (d_cls list, d_ctr list, d_off list).  No top gradient enters (the reference's losses ignore it)."""
     N, K, HW, hws = _fcos_levels(cls_logits, ctr_logits, off_preds, targets)
-    outs = []
-    for given, like, name in ((d_cls, cls_logits, "d_cls"), (d_ctr, ctr_logits, "d_ctr"), (d_off, off_preds, "d_off")):
-        if given is None:
-            given = [torch.empty_like(t) for t in like]
-        if len(given) != len(like):
-            raise ValueError("%s needs one tensor per level" % name)
-        for g, t in zip(given, like):
-            _chk(g, name)
-            if g.numel() != t.numel():
-                raise ValueError("%s must have the sizes of the inputs" % name)
-        outs.append(list(given))
+    outs = (_grad_levels(d_cls, cls_logits, "d_cls"), _grad_levels(d_ctr, ctr_logits, "d_ctr"),
+            _grad_levels(d_off, off_preds, "d_off"))
     if N * K * HW == 0:
-        return tuple(outs)
-    lib().call("sd_fcos_loss_bwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), _parr(outs[0]),
-               _parr(outs[1]), _parr(outs[2]), hws, len(cls_logits), _p(targets.centerness), _p(targets.offset),
-               _p(targets.cls_id), _p(targets.state), N, K, float(alpha), float(gamma), float(ignore_offset),
-               float(ignore_label), _stream())
-    return tuple(outs)
+        return outs
+    _call("sd_fcos_loss_bwd", _parr(cls_logits), _parr(ctr_logits), _parr(off_preds), _parr(outs[0]), _parr(outs[1]),
+          _parr(outs[2]), hws, len(cls_logits), targets.centerness, targets.offset, targets.cls_id, targets.state, N,
+          K, alpha, gamma, ignore_offset, ignore_label)
+    return outs
 
 
 class FcosLossFunction(torch.autograd.Function):
@@ -2576,11 +2429,11 @@ REPPOINTS_TRANSFORMS = {"minmax": 0, "partial_minmax": 1, "moment": 2}
 
 
 def reppoints_target_workspace_bytes(N, M, P):
-    return int(lib().cdll.sd_reppoints_target_workspace_bytes(int(N), int(M), ctypes.c_long(int(P))))
+    return _query("sd_reppoints_target_workspace_bytes", int(N), int(M), int(P))
 
 
 def reppoints_box_loss_workspace_bytes(N, P):
-    return int(lib().cdll.sd_reppoints_box_loss_workspace_bytes(int(N), ctypes.c_long(int(P))))
+    return _query("sd_reppoints_box_loss_workspace_bytes", int(N), int(P))
 
 
 def _reppoints_levels(maps, strides, name, like=None):
@@ -2626,18 +2479,17 @@ def reppoints_target(pts_init, gt_bbox, strides, *, transform="moment", moment_t
     M = int(gt_bbox.shape[1])
     tr = _reppoints_transform(transform, moment_transfer)
     dev = gt_bbox.device
-    label_init = _fcos_out(label_init, "label_init", (N, P), dev)
-    gt_init = _fcos_out(gt_init, "gt_init", (N, P, 4), dev)
-    label_refine = _fcos_out(label_refine, "label_refine", (N, P), dev)
-    gt_refine = _fcos_out(gt_refine, "gt_refine", (N, P, 4), dev)
-    state = _fcos_out(state, "state", (4,), dev, torch.int32)
+    label_init = _out(label_init, "label_init", (N, P), dev, flat=True)
+    gt_init = _out(gt_init, "gt_init", (N, P, 4), dev, flat=True)
+    label_refine = _out(label_refine, "label_refine", (N, P), dev, flat=True)
+    gt_refine = _out(gt_refine, "gt_refine", (N, P, 4), dev, flat=True)
+    state = _out(state, "state", (4,), dev, torch.int32, flat=True)
     if N * P == 0:        # the entry point writes nothing: no label, and the denominators are 0 + 1
         state.copy_(torch.tensor([0, 0, 0x3f800000, 0x3f800000], dtype=torch.int32))
-    ws = _workspace(dev, reppoints_target_workspace_bytes(N, M, P), workspace)
-    lib().call("sd_reppoints_target", _parr(pts_init), Hs, Ws, st, len(pts_init), _p(gt_bbox), _p(moment_transfer),
-               _p(label_init), _p(gt_init), _p(label_refine), _p(gt_refine), _p(state), N, M, K, tr,
-               float(target_scale), int(num_pos), float(pos_iou_thr), float(neg_iou_thr), float(min_pos_iou), _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_reppoints_target_workspace_bytes", N, M, P)
+    _call("sd_reppoints_target", _parr(pts_init), Hs, Ws, st, len(pts_init), gt_bbox, moment_transfer, label_init,
+          gt_init, label_refine, gt_refine, state, N, M, K, tr, target_scale, int(num_pos), pos_iou_thr, neg_iou_thr,
+          min_pos_iou, ws, ws.numel())
     return RepPointsTargets(label_init, gt_init, label_refine, gt_refine, state)
 
 
@@ -2646,8 +2498,7 @@ def _reppoints_loss_args(pts_init, pts_refine, targets, strides, transform, mome
     _reppoints_levels(pts_refine, strides, "pts_refine", like=pts_init)
     tr = _reppoints_transform(transform, moment_transfer)
     for name in ("label_init", "gt_init", "label_refine", "gt_refine"):
-        t = getattr(targets, name)
-        _chk(t, name)
+        t = _chk(getattr(targets, name), name)
         if t.numel() != N * P * (4 if name.startswith("gt") else 1):
             raise ValueError("the targets do not hold N = %d images of P = %d points" % (N, P))
     _chk(targets.state, "state", dtype=torch.int32)
@@ -2660,11 +2511,11 @@ def reppoints_box_loss_forward(pts_init, pts_refine, targets, strides, *, transf
     per-level point maps in one launch: smooth_l1((box - gt) / (stride * scale), 3) * (label > 0)."""
     N, K, P, Hs, Ws, st, tr = _reppoints_loss_args(pts_init, pts_refine, targets, strides, transform, moment_transfer)
     dev = pts_init[0].device
-    loss_init = _fcos_out(loss_init, "loss_init", (N, P, 4), dev)
-    loss_refine = _fcos_out(loss_refine, "loss_refine", (N, P, 4), dev)
-    lib().call("sd_reppoints_box_loss_fwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init),
-               _p(moment_transfer), _p(targets.label_init), _p(targets.gt_init), _p(targets.label_refine),
-               _p(targets.gt_refine), _p(loss_init), _p(loss_refine), N, K, tr, float(scale), _stream())
+    loss_init = _out(loss_init, "loss_init", (N, P, 4), dev, flat=True)
+    loss_refine = _out(loss_refine, "loss_refine", (N, P, 4), dev, flat=True)
+    _call("sd_reppoints_box_loss_fwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init), moment_transfer,
+          targets.label_init, targets.gt_init, targets.label_refine, targets.gt_refine, loss_init, loss_refine, N, K,
+          tr, scale)
     return loss_init, loss_refine
 
 
@@ -2688,15 +2539,14 @@ def reppoints_box_loss_backward(pts_init, pts_refine, targets, strides, *, trans
         outs.append(list(given))
     if d_moment_transfer is None and req == "add":
         raise ValueError("req='add' needs the tensors to add to")
-    d_moment_transfer = _fcos_out(d_moment_transfer, "d_moment_transfer", (2,), dev)
+    d_moment_transfer = _out(d_moment_transfer, "d_moment_transfer", (2,), dev, flat=True)
     if N * P == 0:
         return outs[0], outs[1], d_moment_transfer if req == "add" else d_moment_transfer.zero_()
-    ws = _workspace(dev, reppoints_box_loss_workspace_bytes(N, P), workspace)
-    lib().call("sd_reppoints_box_loss_bwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init),
-               _p(moment_transfer), _p(targets.label_init), _p(targets.gt_init), _p(targets.label_refine),
-               _p(targets.gt_refine), _p(targets.state), _parr(outs[0]), _parr(outs[1]), _p(d_moment_transfer), N, K,
-               tr, float(scale), float(grad_scale_init), float(grad_scale_refine), REQ[req], _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, "sd_reppoints_box_loss_workspace_bytes", N, P)
+    _call("sd_reppoints_box_loss_bwd", _parr(pts_init), _parr(pts_refine), Hs, Ws, st, len(pts_init), moment_transfer,
+          targets.label_init, targets.gt_init, targets.label_refine, targets.gt_refine, targets.state,
+          _parr(outs[0]), _parr(outs[1]), d_moment_transfer, N, K, tr, scale, grad_scale_init, grad_scale_refine,
+          REQ[req], ws, ws.numel())
     return outs[0], outs[1], d_moment_transfer
 
 
@@ -2737,15 +2587,14 @@ def reppoints_box_loss(pts_init, pts_refine, targets, strides, *, transform="mom
 def fcos_decode_workspace_bytes(N, C, hws, top_n):
     """bytes of workspace of fcos_decode; hws = H_l * W_l per level"""
     L = len(hws)
-    return int(lib().cdll.sd_fcos_decode_workspace_bytes(int(N), int(C), L, (ctypes.c_long * max(L, 1))(*hws),
-                                                         int(top_n)))
+    return _query("sd_fcos_decode_workspace_bytes", int(N), int(C), L, (ctypes.c_long * max(L, 1))(*hws), int(top_n))
 
 
 def fcos_sigmoid(x, out=None):
     """1.0f / (1.0f + expf(-x)) element-wise: the sigmoid fcos_decode(input_logits=True) applies, same bits."""
     _chk(x, "x")
-    out = _fcos_out(out, "out", tuple(x.shape), x.device)
-    lib().call("sd_fcos_sigmoid", _p(x), _p(out), ctypes.c_long(x.numel()), _stream())
+    out = _out(out, "out", x.shape, x.device, flat=True)
+    _call("sd_fcos_sigmoid", x, out, x.numel())
     return out
 
 
@@ -2777,16 +2626,16 @@ def fcos_decode(cls_list, ctr_list, off_list, im_info, strides, top_n, pre_nms_t
     top_n = int(top_n)
     R = L * max(top_n, 0)
     dev = im_info.device
-    bbox = _fcos_out(bbox, "bbox", (N, R, 4), dev)
-    score = _fcos_out(score, "score", (N, R, 81), dev)
-    cls_id = _fcos_out(cls_id, "cls_id", (N, R), dev)
+    bbox = _out(bbox, "bbox", (N, R, 4), dev, flat=True)
+    score = _out(score, "score", (N, R, 81), dev, flat=True)
+    cls_id = _out(cls_id, "cls_id", (N, R), dev, flat=True)
     if return_stage or stage is not None:
-        stage = _fcos_out(stage, "stage", (N, R, 6), dev)
+        stage = _out(stage, "stage", (N, R, 6), dev, flat=True)
     hws = [h * w for h, w in zip(Hs, Ws)]
-    ws = _workspace(dev, fcos_decode_workspace_bytes(N, C, hws, top_n), workspace)
-    lib().call("sd_fcos_decode", _parr(cls_list), _parr(ctr_list), _parr(off_list), _p(im_info), _iarr(Hs), _iarr(Ws),
-               _iarr(strides), L, N, C, top_n, float(pre_nms_thresh), int(bool(input_logits)), _p(bbox), _p(score),
-               _p(cls_id), _p(stage), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(dev, workspace, fcos_decode_workspace_bytes(N, C, hws, top_n))
+    _call("sd_fcos_decode", _parr(cls_list), _parr(ctr_list), _parr(off_list), im_info, _iarr(Hs), _iarr(Ws),
+          _iarr(strides), L, N, C, top_n, pre_nms_thresh, bool(input_logits), bbox, score, cls_id, stage, ws,
+          ws.numel())
     return (bbox, score, cls_id, stage) if return_stage else (bbox, score, cls_id)
 
 
@@ -2804,8 +2653,8 @@ def reppoints_decode_workspace_bytes(N, C, hws, ks):
     L = len(hws)
     if len(ks) != L:
         raise ValueError("hws and ks need one entry per level each")
-    return int(lib().cdll.sd_reppoints_decode_workspace_bytes(int(N), int(C), L, (ctypes.c_long * max(L, 1))(*hws),
-                                                              _iarr(ks)))
+    return _query("sd_reppoints_decode_workspace_bytes", int(N), int(C), L, (ctypes.c_long * max(L, 1))(*hws),
+                  _iarr(ks))
 
 
 def reppoints_decode(cls_list, pts_refine_list, im_info, strides, ks, *, transform="moment", moment_transfer=None,
@@ -2840,12 +2689,12 @@ def reppoints_decode(cls_list, pts_refine_list, im_info, strides, ks, *, transfo
     ks = [int(k) for k in ks]
     R = sum(k if k > 0 else hw for k, hw in zip(ks, hws))
     dev = im_info.device
-    cls_score = _fcos_out(cls_score, "cls_score", (N, R, C + 1), dev)
-    bbox_xyxy = _fcos_out(bbox_xyxy, "bbox_xyxy", (N, R, 4), dev)
-    ws = _workspace(dev, reppoints_decode_workspace_bytes(N, C, hws, ks), workspace)
-    lib().call("sd_reppoints_decode", _parr(cls_list), _parr(pts_refine_list), _p(im_info), _p(moment_transfer),
-               _iarr(Hs), _iarr(Ws), _iarr(strides), _iarr(ks), L, N, C, K2 // 2, tr, int(bool(input_logits)),
-               _p(cls_score), _p(bbox_xyxy), _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    cls_score = _out(cls_score, "cls_score", (N, R, C + 1), dev, flat=True)
+    bbox_xyxy = _out(bbox_xyxy, "bbox_xyxy", (N, R, 4), dev, flat=True)
+    ws = _ws(dev, workspace, reppoints_decode_workspace_bytes(N, C, hws, ks))
+    _call("sd_reppoints_decode", _parr(cls_list), _parr(pts_refine_list), im_info, moment_transfer, _iarr(Hs),
+          _iarr(Ws), _iarr(strides), _iarr(ks), L, N, C, K2 // 2, tr, bool(input_logits), cls_score, bbox_xyxy, ws,
+          ws.numel())
     return cls_score, bbox_xyxy
 
 
@@ -2866,11 +2715,9 @@ def nms(dets, rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300, threshold=0.7, alr
     out = torch.empty((B, post, 4), device=dets.device, dtype=torch.float32)
     score = torch.empty((B, post, 1), device=dets.device, dtype=torch.float32)
     keep = torch.empty((B, post), device=dets.device, dtype=torch.int32) if return_index else None
-    wsb = lib().cdll.sd_nms_workspace_bytes(B, N, int(rpn_pre_nms_top_n))
-    ws = torch.empty(wsb, device=dets.device, dtype=torch.uint8)
-    lib().call("sd_nms", _p(dets), B, N, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n),
-               float(threshold), int(bool(threshold_ge)), int(bool(already_sorted)), _p(out),
-               _p(score), _p(keep), _p(ws), ctypes.c_size_t(wsb), _stream())
+    ws = _ws(dets.device, None, "sd_nms_workspace_bytes", B, N, int(rpn_pre_nms_top_n))
+    _call("sd_nms", dets, B, N, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n), threshold, bool(threshold_ge),
+          bool(already_sorted), out, score, keep, ws, ws.numel())
     return (out, score, keep) if return_index else (out, score)
 
 
@@ -2894,8 +2741,7 @@ def soft_nms_batched(dets, counts=None, sigma=0.5, Nt=0.3, threshold=0.001, meth
     od = torch.empty_like(dets)
     oi = torch.empty((P, Nmax), device=dets.device, dtype=torch.int32)
     oc = torch.empty((P,), device=dets.device, dtype=torch.int32)
-    lib().call("sd_soft_nms_batched", _p(dets), _p(counts), P, Nmax, float(sigma), float(Nt),
-               float(threshold), int(method), _p(od), _p(oi), _p(oc), _stream())
+    _call("sd_soft_nms_batched", dets, counts, P, Nmax, sigma, Nt, threshold, int(method), od, oi, oc)
     return od, oi, oc
 
 
@@ -2905,7 +2751,7 @@ def bbox_overlaps(boxes, query_boxes):
     _chk(query_boxes, "query_boxes", ndim=2)
     n, k = boxes.shape[0], query_boxes.shape[0]
     ov = torch.empty((n, k), device=boxes.device, dtype=torch.float32)
-    lib().call("sd_bbox_overlaps", _p(boxes), n, _p(query_boxes), k, _p(ov), _stream())
+    _call("sd_bbox_overlaps", boxes, n, query_boxes, k, ov)
     return ov
 
 
@@ -2941,8 +2787,8 @@ def deform_im2col(x, offset, kernel=(3, 3), pad=1, stride=1, dilate=1, num_defor
     kh, kw = kernel
     Ho, Wo = _dcn_out_hw(H, W, kh, kw, pad, stride, dilate)
     col = torch.empty((N, C * kh * kw, Ho * Wo), device=x.device, dtype=torch.float32)
-    lib().call("sd_deform_im2col", _p(x), _p(offset), _p(col), N, C, H, W, kh, kw,
-               *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _stream())
+    _call("sd_deform_im2col", x, offset, col, N, C, H, W, kh, kw, *_dcn_geom(pad, stride, dilate),
+          int(num_deformable_group))
     return col
 
 
@@ -2954,14 +2800,12 @@ def deform_col2im(col, offset, x_shape, kernel=(3, 3), pad=1, stride=1, dilate=1
     kh, kw = kernel
     dx = torch.empty((N, C, H, W), device=col.device, dtype=torch.float32)
     if not workspace:   # fp32 compare-and-swap adds (what a caller without a workspace gets)
-        lib().call("sd_deform_col2im", _p(col), _p(offset), _p(dx), REQ["write"], N, C, H, W, kh, kw,
-                   *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _stream())
+        _call("sd_deform_col2im", col, offset, dx, REQ["write"], N, C, H, W, kh, kw, *_dcn_geom(pad, stride, dilate),
+              int(num_deformable_group))
         return dx
-    lib().cdll.sd_deform_col2im_workspace_bytes.restype = ctypes.c_size_t
-    n = int(lib().cdll.sd_deform_col2im_workspace_bytes(N, int(num_deformable_group)))
-    ws = torch.empty(n, device=col.device, dtype=torch.uint8)
-    lib().call("sd_deform_col2im_ws", _p(col), _p(offset), _p(dx), REQ["write"], N, C, H, W, kh, kw,
-               *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _p(ws), ctypes.c_size_t(n), _stream())
+    ws = _ws(col.device, None, "sd_deform_col2im_workspace_bytes", N, int(num_deformable_group))
+    _call("sd_deform_col2im_ws", col, offset, dx, REQ["write"], N, C, H, W, kh, kw, *_dcn_geom(pad, stride, dilate),
+          int(num_deformable_group), ws, ws.numel())
     return dx
 
 
@@ -2973,8 +2817,8 @@ def deform_col2im_coord(col, x, offset, kernel=(3, 3), pad=1, stride=1, dilate=1
     N, C, H, W = x.shape
     kh, kw = kernel
     doff = torch.empty_like(offset)
-    lib().call("sd_deform_col2im_coord", _p(col), _p(x), _p(offset), _p(doff), REQ["write"], N, C, H,
-               W, kh, kw, *_dcn_geom(pad, stride, dilate), int(num_deformable_group), _stream())
+    _call("sd_deform_col2im_coord", col, x, offset, doff, REQ["write"], N, C, H, W, kh, kw,
+          *_dcn_geom(pad, stride, dilate), int(num_deformable_group))
     return doff
 
 
@@ -2992,17 +2836,10 @@ def gemm_f32(a, b, trans_a=False, trans_b=False, out=None, accumulate=0):
         raise ValueError("GEMM shape mismatch")
     if out is None:
         out = torch.empty((Bt, M, N), device=a.device, dtype=torch.float32)
-    ws = torch.empty(64, device=a.device, dtype=torch.uint8)
-    lib().call("sd_gemm_f32_ws", int(trans_a), int(trans_b), M, N, K, _p(a), a.shape[2],
-               a.shape[1] * a.shape[2], _p(b), b.shape[2], b.shape[1] * b.shape[2], _p(out), N,
-               M * N, Bt, int(accumulate), _p(ws), ctypes.c_size_t(64), _stream())
+    ws = _ws(a.device, None, 64)
+    _call("sd_gemm_f32_ws", trans_a, trans_b, M, N, K, a, a.shape[2], a.shape[1] * a.shape[2], b,
+          b.shape[2], b.shape[1] * b.shape[2], out, N, M * N, Bt, int(accumulate), ws, ws.numel())
     return out
-
-
-def _dcn_ws(x, kh, kw, pad, stride, dilate):
-    N, C, H, W = x.shape
-    n = lib().cdll.sd_deform_conv_workspace_bytes(N, C, H, W, kh, kw, pad, stride, dilate)
-    return torch.empty(n, device=x.device, dtype=torch.uint8), n
 
 
 def deform_conv_forward(x, offset, weight, pad=1, stride=1, dilate=1, num_deformable_group=1,
@@ -3032,13 +2869,10 @@ def deform_conv_forward(x, offset, weight, pad=1, stride=1, dilate=1, num_deform
     # keep_col = False: no col matrix where the shape allows -- sampling fused into the GEMM (3x3, num_group 1,
     # C / groups % 16 == 0, H*W % 4 == 0); other shapes run im2col + GEMM behind the same entry point, which
     # its workspace size accounts for
-    n = int(lib().cdll.sd_deform_convolution_fwd_workspace_bytes(N, C, H, W, F, kh, kw, pad, stride, dilate,
-                                                                 int(num_deformable_group), num_group,
-                                                                 int(bool(keep_col))))
-    ws = torch.empty(n, device=x.device, dtype=torch.uint8)
-    lib().call("sd_deform_convolution_fwd", _p(x), _p(offset), _p(weight), _p(bias) if bias is not None else None,
-               _p(y), N, C, H, W, F, kh, kw, pad, stride, dilate, int(num_deformable_group), num_group,
-               int(bool(keep_col)), _p(ws), ctypes.c_size_t(n), _stream())
+    ws = _ws(x.device, None, "sd_deform_convolution_fwd_workspace_bytes", N, C, H, W, F, kh, kw, pad, stride, dilate,
+             int(num_deformable_group), num_group, bool(keep_col))
+    _call("sd_deform_convolution_fwd", x, offset, weight, bias, y, N, C, H, W, F, kh, kw, pad, stride, dilate,
+          int(num_deformable_group), num_group, bool(keep_col), ws, ws.numel())
     return (y, ws) if keep_col else y
 
 
@@ -3051,7 +2885,7 @@ def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1,
     _chk(out_grad, "out_grad", ndim=4)
     N, C, H, W = x.shape
     F, _, kh, kw = weight.shape
-    r = [REQ[v] if isinstance(v, str) else int(v) for v in req]
+    r = [_req_of(v) for v in req]
     if bias and len(r) == 3:
         r.append(REQ["write"])
     if grads is None:
@@ -3061,14 +2895,13 @@ def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1,
     elif len(grads) != (4 if bias else 3):
         raise ValueError("grads must hold %d tensors (d_data, d_offset, d_weight%s), got %d"
                          % (4 if bias else 3, ", d_bias" if bias else "", len(grads)))
-    ws, n = _dcn_ws(x, kh, kw, pad, stride, dilate)
+    ws = _ws(x.device, None, "sd_deform_conv_workspace_bytes", N, C, H, W, kh, kw, pad, stride, dilate)
     col = None
     if fwd_ws is not None:
-        col = ctypes.c_void_p((fwd_ws.data_ptr() + 255) & ~255)  # sd_deform_conv_col_of_workspace
-    lib().call("sd_deform_convolution_bwd", _p(out_grad), _p(x), _p(offset), _p(weight), col, _p(grads[0]),
-               _p(grads[1]), _p(grads[2]), _p(grads[3]) if bias else None, r[0], r[1], r[2],
-               r[3] if bias else REQ["null"], N, C, H, W, F, kh, kw, pad, stride, dilate,
-               int(num_deformable_group), int(num_group), _p(ws), ctypes.c_size_t(n), _stream())
+        col = (fwd_ws.data_ptr() + 255) & ~255  # sd_deform_conv_col_of_workspace
+    _call("sd_deform_convolution_bwd", out_grad, x, offset, weight, col, grads[0], grads[1], grads[2],
+          grads[3] if bias else None, r[0], r[1], r[2], r[3] if bias else REQ["null"], N, C, H, W, F, kh, kw, pad,
+          stride, dilate, int(num_deformable_group), int(num_group), ws, ws.numel())
     return grads
 
 
@@ -3099,13 +2932,10 @@ def proposal_v3(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_n
     post = int(rpn_post_nms_top_n) if not is_train else min(int(rpn_post_nms_top_n), pre)
     out = torch.empty((B, post, 4), device=cls_prob.device, dtype=torch.float32)
     score = torch.empty((B, post, 1), device=cls_prob.device, dtype=torch.float32)
-    wsb = lib().cdll.sd_proposal_v3_workspace_bytes(B, A, H, W, int(rpn_pre_nms_top_n))
-    ws = torch.empty(wsb, device=cls_prob.device, dtype=torch.uint8)
-    lib().call("sd_proposal_v3_iou" if iou_loss else "sd_proposal_v3",
-               _p(cls_prob), _p(bbox_pred), _p(im_info), _p(out), _p(score), B, A,
-               H, W, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n), float(threshold),
-               int(rpn_min_size), _farr(scales), len(scales), _farr(ratios), len(ratios),
-               int(feature_stride), int(bool(is_train)), _p(ws), ctypes.c_size_t(wsb), _stream())
+    ws = _ws(cls_prob.device, None, "sd_proposal_v3_workspace_bytes", B, A, H, W, int(rpn_pre_nms_top_n))
+    _call("sd_proposal_v3_iou" if iou_loss else "sd_proposal_v3", cls_prob, bbox_pred, im_info, out, score, B, A, H, W,
+          int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n), threshold, int(rpn_min_size), _farr(scales), len(scales),
+          _farr(ratios), len(ratios), int(feature_stride), bool(is_train), ws, ws.numel())
     return out, score
 
 
@@ -3127,12 +2957,6 @@ def _proposal_v12_args(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n, rpn_post
     return B, A, H, W, out, score
 
 
-def _proposal_v12_ws(name, B, A, H, W, pre, device, workspace):
-    fn = getattr(lib().cdll, name)
-    fn.restype = ctypes.c_size_t
-    return _workspace(device, int(fn(B, A, H, W, int(pre))), workspace)
-
-
 def proposal_v2(cls_prob, bbox_pred, im_info, valid_ranges, rpn_pre_nms_top_n=6000,
                 rpn_post_nms_top_n=300, threshold=0.7, rpn_min_size=16, scales=(4., 8., 16., 32.),
                 ratios=(0.5, 1., 2.), feature_stride=16, filter_scales=False, iou_loss=False,
@@ -3147,13 +2971,10 @@ def proposal_v2(cls_prob, bbox_pred, im_info, valid_ranges, rpn_pre_nms_top_n=60
     if valid_ranges.shape != (B, 2):
         raise ValueError("valid_ranges must be (B,2)")
     scales, ratios = list(scales), list(ratios)
-    ws = _proposal_v12_ws("sd_proposal_v2_workspace_bytes", B, A, H, W, rpn_pre_nms_top_n,
-                          cls_prob.device, workspace)
-    lib().call("sd_proposal_v2", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(valid_ranges),
-               _p(out), _p(score), B, A, H, W, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n),
-               float(threshold), int(rpn_min_size), _farr(scales), len(scales), _farr(ratios),
-               len(ratios), int(feature_stride), int(bool(filter_scales)), int(bool(iou_loss)),
-               _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(cls_prob.device, workspace, "sd_proposal_v2_workspace_bytes", B, A, H, W, int(rpn_pre_nms_top_n))
+    _call("sd_proposal_v2", cls_prob, bbox_pred, im_info, valid_ranges, out, score, B, A, H, W,
+          int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n), threshold, int(rpn_min_size), _farr(scales), len(scales),
+          _farr(ratios), len(ratios), int(feature_stride), bool(filter_scales), bool(iou_loss), ws, ws.numel())
     return out, score
 
 
@@ -3166,13 +2987,10 @@ def proposal(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n=6000, rpn_post_nms_
     B, A, H, W, out, score = _proposal_v12_args(cls_prob, bbox_pred, im_info, rpn_pre_nms_top_n,
                                                 rpn_post_nms_top_n)
     scales, ratios = list(scales), list(ratios)
-    ws = _proposal_v12_ws("sd_proposal_workspace_bytes", B, A, H, W, rpn_pre_nms_top_n,
-                          cls_prob.device, workspace)
-    lib().call("sd_proposal", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(out), _p(score), B, A,
-               H, W, int(rpn_pre_nms_top_n), int(rpn_post_nms_top_n), float(threshold),
-               int(rpn_min_size), _farr(scales), len(scales), _farr(ratios), len(ratios),
-               int(feature_stride), int(bool(is_train)), int(bool(iou_loss)), _p(ws),
-               ctypes.c_size_t(ws.numel()), _stream())
+    ws = _ws(cls_prob.device, workspace, "sd_proposal_workspace_bytes", B, A, H, W, int(rpn_pre_nms_top_n))
+    _call("sd_proposal", cls_prob, bbox_pred, im_info, out, score, B, A, H, W, int(rpn_pre_nms_top_n),
+          int(rpn_post_nms_top_n), threshold, int(rpn_min_size), _farr(scales), len(scales), _farr(ratios),
+          len(ratios), int(feature_stride), bool(is_train), bool(iou_loss), ws, ws.numel())
     return out, score
 
 
@@ -3183,8 +3001,7 @@ def get_top_proposal(bbox, score, top_n):
     B, N, _ = bbox.shape
     ob = torch.empty((B, int(top_n), 4), device=bbox.device, dtype=torch.float32)
     os_ = torch.empty((B, int(top_n), 1), device=bbox.device, dtype=torch.float32)
-    lib().call("sd_get_top_proposal", _p(bbox), _p(score), B, N, int(top_n), _p(ob), _p(os_),
-               _stream())
+    _call("sd_get_top_proposal", bbox, score, B, N, int(top_n), ob, os_)
     return ob, os_
 
 
@@ -3193,8 +3010,7 @@ def get_top_proposal(bbox, score, top_n):
 # models/retinanet/builder.py:358-389)
 # --------------------------------------------------------------------------------------------------
 def gen_proposal_retina_workspace_bytes(B, AK, H, W):
-    lib().cdll.sd_gen_proposal_retina_workspace_bytes.restype = ctypes.c_size_t
-    return int(lib().cdll.sd_gen_proposal_retina_workspace_bytes(B, AK, H, W))
+    return _query("sd_gen_proposal_retina_workspace_bytes", B, AK, H, W)
 
 
 def gen_proposal_retina(cls_prob, bbox_pred, im_info, anchors, *, num_anchors, rpn_pre_nms_top_n=6000,
@@ -3226,12 +3042,10 @@ def gen_proposal_retina(cls_prob, bbox_pred, im_info, anchors, *, num_anchors, r
     oc = K + 1 if output_one_hot else 1
     out = torch.empty((B, top_n, 4), device=cls_prob.device, dtype=torch.float32)
     score = torch.empty((B, top_n, oc), device=cls_prob.device, dtype=torch.float32)
-    workspace = _workspace(cls_prob.device, gen_proposal_retina_workspace_bytes(B, AK, H, W), workspace)
-    lib().call("sd_gen_proposal_retina", _p(cls_prob), _p(bbox_pred), _p(im_info), _p(anchors),
-               _p(out), _p(score), B, AK, H, W, A, top_n, int(rpn_min_size), float(thresh),
-               _farr(anchor_mean), _farr(anchor_std), int(bool(iou_loss)), int(bool(output_one_hot)),
-               int(bool(batch_wise_anchor)), _p(workspace), ctypes.c_size_t(workspace.numel()),
-               _stream())
+    ws = _ws(cls_prob.device, workspace, "sd_gen_proposal_retina_workspace_bytes", B, AK, H, W)
+    _call("sd_gen_proposal_retina", cls_prob, bbox_pred, im_info, anchors, out, score, B, AK, H, W, A, top_n,
+          int(rpn_min_size), thresh, _farr(anchor_mean), _farr(anchor_std), bool(iou_loss), bool(output_one_hot),
+          bool(batch_wise_anchor), ws, ws.numel())
     return out, score
 
 
@@ -3252,9 +3066,8 @@ def decode_bbox(rois, bbox_pred, im_info, bbox_mean=(0., 0., 0., 0.), bbox_std=(
     K = bbox_pred.shape[2] // 4
     out = torch.empty((B, R, 4 if class_agnostic else 4 * K), device=rois.device,
                       dtype=torch.float32)
-    lib().call("sd_decode_bbox", _p(rois), _p(bbox_pred), _p(im_info), _p(out), B, R, K,
-               _farr(bbox_mean), _farr(bbox_std), int(bool(class_agnostic)),
-               int(bbox_decode_type == "xyxy"), _stream())
+    _call("sd_decode_bbox", rois, bbox_pred, im_info, out, B, R, K, _farr(bbox_mean), _farr(bbox_std),
+          bool(class_agnostic), bbox_decode_type == "xyxy")
     return out
 
 
@@ -3267,8 +3080,7 @@ def det_filter(bbox_xyxy, cls_score, min_det_score):
     Kb = bbox_xyxy.shape[2] // 4
     dets = torch.empty((B * K, R, 5), device=cls_score.device, dtype=torch.float32)
     counts = torch.empty((B * K,), device=cls_score.device, dtype=torch.int32)
-    lib().call("sd_det_filter", _p(bbox_xyxy), _p(cls_score), B, R, K, Kb, float(min_det_score),
-               _p(dets), _p(counts), _stream())
+    _call("sd_det_filter", bbox_xyxy, cls_score, B, R, K, Kb, min_det_score, dets, counts)
     return dets, counts
 
 
@@ -3293,8 +3105,7 @@ def hard_nms_batched(dets, counts=None, thresh=0.5):
     od = torch.empty_like(dets)
     oi = torch.empty((P, Nmax), device=dets.device, dtype=torch.int32)
     oc = torch.empty((P,), device=dets.device, dtype=torch.int32)
-    lib().call("sd_hard_nms_batched", _p(dets), _p(counts), P, Nmax, float(thresh), _p(od), _p(oi),
-               _p(oc), _stream())
+    _call("sd_hard_nms_batched", dets, counts, P, Nmax, thresh, od, oi, oc)
     return od, oi, oc
 
 
@@ -3314,8 +3125,7 @@ def multiclass_nms(cls_score, bbox_xyxy, min_det_score=0.05, nms_thr=0.5, skip_b
 
 
 def bbox_post_processing_workspace_bytes(B, R, K, bbox_classes, max_det_per_image):
-    return int(lib().cdll.sd_bbox_post_processing_workspace_bytes(B, R, K, bbox_classes,
-                                                                  int(max_det_per_image)))
+    return _query("sd_bbox_post_processing_workspace_bytes", B, R, K, bbox_classes, int(max_det_per_image))
 
 
 def bbox_post_processing(cls_score, bbox_xyxy, max_det_per_image=100, min_det_score=0.05, nms_thr=0.5,
@@ -3342,10 +3152,9 @@ def bbox_post_processing(cls_score, bbox_xyxy, max_det_per_image=100, min_det_sc
         if tuple(t.shape) != (B, top, last):
             raise ValueError("%s must be %s" % (name, (B, top, last)))
     wsb = bbox_post_processing_workspace_bytes(B, R, K, Kb, top) if K >= 1 and Kb in (1, K) else 16
-    workspace = _workspace(cls_score.device, wsb, workspace)
-    lib().call("sd_bbox_post_processing", _p(cls_score), _p(bbox_xyxy), B, R, K, Kb,
-               float(min_det_score), float(nms_thr), top, _p(ps), _p(pb), _p(pc), _p(workspace),
-               ctypes.c_size_t(workspace.numel()), _stream())
+    ws = _ws(cls_score.device, workspace, wsb)
+    _call("sd_bbox_post_processing", cls_score, bbox_xyxy, B, R, K, Kb, min_det_score, nms_thr, top, ps, pb, pc, ws,
+          ws.numel())
     return ps, pb, pc
 
 
