@@ -74,10 +74,15 @@ const char* sd_last_dispatch(void);
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
 /* kernel-variant knobs for A/B measurements (bench.py, tests); every variant computes the same
- * result.  Unknown keys are an error.  Knobs that disable parts of a kernel for profiling exist
- * only in the separate -DSD_PROFILING build used by tools/, not in this library. */
+ * result.  The knobs, their defaults and the ranges a read clamps to are the rows of ONE list, SD_KNOBS in
+ * simpledet_amd/csrc/common.h; nothing else states a default.  A knob holds its default until sd_set_tuning
+ * changes it (any integer is accepted), sd_get_tuning returns the value it holds, and sd_tuning_key(index) names
+ * row `index` (NULL past the last row), so a caller can list the knobs and put back what it changed.  Unknown
+ * keys are an error.  Knobs that disable parts of a kernel for profiling are rows only in the separate
+ * -DSD_PROFILING build used by tools/, not in this library. */
 int sd_set_tuning(const char* key, int value);
 int sd_get_tuning(const char* key, int* value);
+const char* sd_tuning_key(int index);
 
 /* Block the calling host thread until `stream` has drained.  Only the MXNet CustomOp adapter
  * uses it (a CustomOp's outputs must be complete when forward()/backward() returns); the compute

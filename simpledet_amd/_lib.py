@@ -4,6 +4,7 @@ The argtypes are generated from the header itself, so the header is the single s
 the boundary.  There is NO CPU fallback: if the shared library is missing or a symbol is absent the
 import fails loudly.
 """
+import contextlib
 import ctypes
 import operator
 import os
@@ -186,10 +187,30 @@ class _Lib:
         self.call("sd_set_tuning", key.encode(), int(value))
 
     def get_tuning(self, key):
-        """value of a kernel-variant knob, -1 when it was never set (= the library's default)."""
-        v = ctypes.c_int(-1)
+        """the value a kernel-variant knob holds: the library's default until someone sets it"""
+        v = ctypes.c_int()
         self.call("sd_get_tuning", key.encode(), ctypes.byref(v))
         return int(v.value)
+
+    def tuning_keys(self):
+        """the keys of the library's knob list, in its order"""
+        keys = []
+        while (key := self.entry("sd_tuning_key")((len(keys),))) is not None:
+            keys.append(key.decode())
+        return keys
+
+    @contextlib.contextmanager
+    def tuned(self, **knobs):
+        """Run a block under these knob values and put the previous ones back after it, in reverse order, however
+        the block ends.  An unknown key raises before anything is changed."""
+        before = [(key, self.get_tuning(key)) for key in knobs]
+        try:
+            for key, value in knobs.items():
+                self.set_tuning(key, value)
+            yield
+        finally:
+            for key, value in reversed(before):
+                self.set_tuning(key, value)
 
 
 _lib = None

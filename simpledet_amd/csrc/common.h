@@ -1,6 +1,7 @@
 // Shared host/device helpers for the simpledet_amd HIP library (gfx950 / CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -35,18 +36,78 @@ void note_dispatch(const char* fmt, ...);
 
 #define SD_LAUNCH_CHECK() SD_HIP_CHECK(hipGetLastError())
 
-// Kernel-VARIANT knobs (A/B of correct implementations from bench.py / the tests; defaults are the
-// shipped path).  Lock-free reads.  Knobs that switch parts of a kernel OFF for profiling (results
-// are wrong) exist only in the -DSD_PROFILING build (tools/libsimpledet_ops_hip_prof.so, `make prof`)
-// and are compiled out of the product library.
-int tuning(const char* key, int dflt);
+// Kernel-VARIANT knobs (A/B of correct implementations from bench.py / the tests), THE list: one row per knob,
+// X(identifier = key, default, lowest, highest, what it selects).  The default is the shipped path and the value a knob
+// holds until sd_set_tuning changes it (to any integer); a read clamps the value to [lowest, highest].  Every product key
+// selects a kernel that some shape or entry point reaches without it (workspace-free calls, C % 4 != 0, ...): tests force it.
+constexpr int kBandXcdDefault = 1, kBandStaffDefault = 0;   // (the band forward's plan, roi_align_common.h)
+#define SD_PRODUCT_KNOBS(X)                                                                                             \
+  X(roi_align_fwd, 1, INT_MIN, INT_MAX, "1: band-resident kernel / tiled kernels where it does not apply; 0: naive per-element kernel") \
+  X(roi_align_fwd_band, 1, INT_MIN, INT_MAX, "1: band-resident forward, planes streamed through LDS, no gathers; 0: the tiled fallback kernels") \
+  X(roi_align_fwd_quad, 1, INT_MIN, INT_MAX, "1: single-level float arg-max forward with four channel-last planes per workgroup when they fit (the C4 family); 0: the band kernel") \
+  X(roi_align_plan_tail, 1, INT_MIN, INT_MAX, "1: the band forward's pre-pass builds only what that kernel reads; the coordinate table and the backward's plan are tasks in the band kernel's tail; 0: all of it in the (merged) pre-pass launch") \
+  X(roi_align_fwd_xcd, kBandXcdDefault, 0, 2, "band forward, which share of the cost prefix a block starts on: 0 linear in blockIdx; 1 XCD-contiguous (a unit's workgroups write through one L2); 2 the same, unit table interleaving the levels") \
+  X(roi_align_fwd_staff, kBandStaffDefault, 0, 1, "band forward, which virtual unit a workgroup starts on: 0 where the midpoint of its share of the cost prefix falls; 1 whole workgroups per unit, chosen so that the units end together after whole reservations (band_staffing, roi_align_common.h)") \
+  X(roi_align_fwd_grab, 0, 0, 64, "band forward: channels a workgroup reserves at a time, rounded up to whole fills; 0: the launcher's choice (2 for the fp32 packed arg-max forward, else 4)") \
+  X(roi_align_fwd_tail, 0, 0, 100, "band forward: last per cent of a unit's channels handed out in smaller pieces") \
+  X(roi_align_fwd_tail_planes, 8, 1, 8, "band forward: planes of such a piece; 8: whole fills")                        \
+  X(roi_align_bwd, 2, INT_MIN, INT_MAX, "2 fused all-level kernel; 1 per-level LDS planes; 0 global atomics")          \
+  X(roi_align_bwd_flt4, 1, INT_MIN, INT_MAX, "1: single-level float arg-max backward with four channel planes per workgroup when they fit") \
+  X(roi_align_bwd_fx, 1, INT_MIN, INT_MAX, "1: band sums in 32-bit fixed point (bit-reproducible); 0: fp32 compare-and-swap adds, hardware order") \
+  X(roi_align_bwd_pixbound, 1, INT_MIN, INT_MAX, "1: the list pre-pass bounds the weight per 4 x 4 pixel cell of a band (2-D difference array); 0: summed over the band's RoIs (what workspace-free calls get)") \
+  X(roi_align_bwd_lists, 1, INT_MIN, INT_MAX, "workspace pre-pass: 1 RoI lists + tap tables per band unit, 2 lists only, 0 none") \
+  X(roi_pool_fwd, 1, INT_MIN, INT_MAX, "1 four planes in LDS per workgroup when they fit, 2 one plane, 0 wave per (roi, channel)") \
+  X(roi_pool_bwd, 1, INT_MIN, INT_MAX, "1 LDS planes, four channels per workgroup, 2 one channel, 0 global atomics")   \
+  X(deform_psroi_bwd_patch, 1, INT_MIN, INT_MAX, "1 (RoI, channel) patch summed in LDS, one atomic per touched pixel; 0 one global atomic per tap") \
+  X(proposal_topk, 0, INT_MIN, INT_MAX, "0 by level size, 1 single workgroup, 2 multi-workgroup")                      \
+  X(soft_nms_threads, 256, INT_MIN, INT_MAX, "threads per problem: 64, 128 or 256")                                    \
+  X(deform_gemm_split, 2, INT_MIN, INT_MAX, "2: scaled fp16 hi/lo split (needs operand maxima); 1: bf16 hi/lo split; 0: fp32 MFMA") \
+  X(deform_gemm_vecstore, 1, INT_MIN, INT_MAX, "1: whole-tile plain stores of the split GEMM leave as 512-byte tile rows through LDS; 0: element stores from the accumulator layout (what unaligned C gets)") \
+  X(deform_gemm_nt, 1, INT_MIN, INT_MAX, "1: those whole-tile stores are non-temporal; 0: plain")                      \
+  X(deform_gemm_ksplit, 1, INT_MIN, INT_MAX, "1: tiles of a mostly empty last round are cut into k slices (atomic adds)") \
+  X(dcn_im2col, 1, INT_MIN, INT_MAX, "1 LDS-plane im2col, 0 per-lane global gathers")                                  \
+  X(dcn_window, 1, INT_MIN, INT_MAX, "1 stage only the touched range of each plane")                                   \
+  X(dcn_im2col_pipe, 1, INT_MIN, INT_MAX, "1: 3x3 im2col with the next window loads before this channel is sampled, col rows stored as 1 KB pieces behind them (s_waitcnt vmcnt(3)); 0: stores in place") \
+  X(dcn_col2im, 1, INT_MIN, INT_MAX, "1 four channels per workgroup, shared sample geometry, 0 one channel")           \
+  X(dcn_col2im_fx, 1, INT_MIN, INT_MAX, "1: the layer's backward sums dX in fixed point (integer LDS adds), 0 fp32 compare-and-swap") \
+  X(dcn_coord, 1, INT_MIN, INT_MAX, "1 LDS-plane offset gradient, 0 per-lane gathers")                                 \
+  X(dcn_fused, 1, INT_MIN, INT_MAX, "1: the col-free entry points sample inside the GEMM; 0: im2col + GEMM")           \
+  X(dcn_fused_tile, 0, INT_MIN, INT_MAX, "pixels per tile of the fused kernels (1..96), 0 = balanced over the CUs: partial-tile tests") \
+  X(crowdhuman_front, 0, INT_MIN, INT_MAX, "0: ch_finish traces each front entry back through the swaps; 1: LDS replay")
+// Knobs that switch parts of a kernel OFF for profiling (results are WRONG off their default) are rows only in the
+// -DSD_PROFILING build (tools/libsimpledet_ops_hip_prof.so, `make prof`).  The product library cannot set them:
+// there SD_PROF_TUNING(knob) is the default as a compile-time constant and the ablated branches are not in the code.
+#define SD_PROF_KNOBS(X)                                                                                                \
+  X(roi_align_fwd_ablate, 0, INT_MIN, INT_MAX, "parts of the RoIAlign forward switched off")                           \
+  X(roi_pool_fwd_ablate, 0, INT_MIN, INT_MAX, "parts of the RoIPool forward switched off")                             \
+  X(crowdhuman_target_stop, 0, INT_MIN, INT_MAX, "k in 1..3: sd_crowdhuman_target launches its first k kernels only")  \
+  X(roi_align_bwd_ablate, 0, INT_MIN, INT_MAX, "parts of the RoIAlign backward switched off")                          \
+  X(roi_align_dbg_lo, 0, INT_MIN, INT_MAX, "device buffer for per-wave phase clocks, low word of its address")         \
+  X(roi_align_dbg_hi, 0, INT_MIN, INT_MAX, "the high word")                                                            \
+  X(gemm_ablate, 0, INT_MIN, INT_MAX, "skip the A (1) / B (2) prefetch of the split GEMM")                             \
+  X(gemm_dbg_cap, 0, INT_MIN, INT_MAX, "waves the buffer above has room for (split GEMM)")                             \
+  X(dcn_im2col_nt, 1, INT_MIN, INT_MAX, "bits 1-2: parts of the LDS im2col switched off")                              \
+  X(dcn_fused_ablate, 0, INT_MIN, INT_MAX, "parts of the fused forward switched off")
 #ifdef SD_PROFILING
-#define SD_PROF_TUNING(key, dflt) ::sd::tuning(key, dflt)
+#define SD_KNOBS(X) SD_PRODUCT_KNOBS(X) SD_PROF_KNOBS(X)
+#define SD_PROF_TUNING(knob) ::sd::tuning(::sd::Knob::knob)
 #define SD_ABLATE(args, bits) ((args).ablate & (bits))
 #else
-#define SD_PROF_TUNING(key, dflt) (dflt)
+#define SD_KNOBS(X) SD_PRODUCT_KNOBS(X)
+namespace prof_default {
+#define SD_KNOB_DEFAULT(id, dflt, lo, hi, what) constexpr int id = dflt;
+SD_PROF_KNOBS(SD_KNOB_DEFAULT)
+#undef SD_KNOB_DEFAULT
+}  // namespace prof_default
+#define SD_PROF_TUNING(knob) (::sd::prof_default::knob)
 #define SD_ABLATE(args, bits) 0  // the ablated branches are not in the product code at all
 #endif
+// the value in effect, clamped to the row's range: one relaxed load (runtime.hip); a knob that is not in the list is
+// no enumerator, so a mistyped read does not compile
+#define SD_KNOB_ENUM(id, dflt, lo, hi, what) id,
+enum class Knob : int { SD_KNOBS(SD_KNOB_ENUM) kCount };
+#undef SD_KNOB_ENUM
+int tuning(Knob knob);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

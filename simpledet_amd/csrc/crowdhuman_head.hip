@@ -465,7 +465,7 @@ extern "C" int sd_crowdhuman_target(const float* proposal, const float* gt_bbox,
   a.fg_thr = p.fg_thresh; a.bg_hi = p.bg_thresh_hi; a.bg_lo = p.bg_thresh_lo;
   for (int k = 0; k < 4; ++k) a.istd[k] = (float)(1.0 / p.bbox_target_std[k]);
   a.mt = mt_state;
-  a.front = tuning("crowdhuman_front", 0) == 1 ? 1 : 0;
+  a.front = tuning(Knob::crowdhuman_front) == 1 ? 1 : 0;
   a.rois = sampled_proposal; a.cls = bbox_cls; a.tgt = bbox_target; a.wgt = bbox_target_weight;
   a.scls = bbox_sec_cls; a.stgt = bbox_sec_target; a.swgt = bbox_sec_target_weight; a.count = count;
   const size_t need = ch_layout(B, a.N, &a, workspace);
@@ -474,7 +474,7 @@ extern "C" int sd_crowdhuman_target(const float* proposal, const float* gt_bbox,
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)M * (sizeof(float4) + sizeof(float) + sizeof(int));
   // (profiling build only: tools/crowdhuman_head_time.py times the chain cut short to apportion it)
-  const int stop = SD_PROF_TUNING("crowdhuman_target_stop", 0);
+  const int stop = SD_PROF_TUNING(crowdhuman_target_stop);
   const int nk = stop >= 1 && stop <= 3 ? stop : 4;
   hipLaunchKernelGGL(ch_match_kernel, dim3(cdiv(a.N, kChT), B), dim3(kChT), lds, st, a);
   if (nk >= 2) hipLaunchKernelGGL(ch_lists_kernel, dim3(B), dim3(1024), 0, st, a);

@@ -667,7 +667,7 @@ using namespace sd;
 // ---- forward without a col matrix (fused sampling + GEMM) ----------------------------------------
 bool sd::dcn_fused_shape_ok(int C, int H, int W, int kh, int kw, int dgroup) {
   return kh == 3 && kw == 3 && dgroup > 0 && C % dgroup == 0 && (C / dgroup) % 16 == 0 && ((long)H * W) % 4 == 0 &&
-         (long)H * W < (1L << 28) && W + 16 < kFXFloats / 16 && tuning("dcn_fused", 1) == 1;
+         (long)H * W < (1L << 28) && W + 16 < kFXFloats / 16 && tuning(Knob::dcn_fused) == 1;
 }
 
 extern "C" size_t sd_deform_conv_fwd_nocol_workspace_bytes(int N, int C, int H, int W, int F, int kh, int kw,
@@ -726,16 +726,16 @@ int sd::deform_conv_fwd_nocol_impl(const float* x, const float* offset, const fl
   const long fit = rounds * kNumCU / ((long)N * mtiles);
   if (fit > T) T = (int)(fit < P ? fit : P);
   a.tile_w = cdiv(P, T);
-  const int tw = tuning("dcn_fused_tile", 0);
+  const int tw = tuning(Knob::dcn_fused_tile);
   if (tw >= 1 && tw <= kFN) a.tile_w = tw;
   a.tiles_per_image = cdiv(P, a.tile_w);
   SD_REQUIRE((long)a.tiles_per_image * 8 * cdiv(N, 8) * mtiles < (1L << 31), "too many tiles");
   a.flags = reinterpret_cast<int*>(amax + 64);   // (behind the maxima: 256 bytes into the 512 of slack)
-  a.ablate = SD_PROF_TUNING("dcn_fused_ablate", 0);
+  a.ablate = SD_PROF_TUNING(dcn_fused_ablate);
   a.dbg = nullptr;
 #ifdef SD_PROFILING
-  a.dbg = reinterpret_cast<long long*>(((uintptr_t)(unsigned)SD_PROF_TUNING("roi_align_dbg_hi", 0) << 32) |
-                                       (uintptr_t)(unsigned)SD_PROF_TUNING("roi_align_dbg_lo", 0));
+  a.dbg = reinterpret_cast<long long*>(((uintptr_t)(unsigned)SD_PROF_TUNING(roi_align_dbg_hi) << 32) |
+                                       (uintptr_t)(unsigned)SD_PROF_TUNING(roi_align_dbg_lo));
 #endif
   // (every call: the attribute is per device, and a process may drive several)
   SD_HIP_CHECK(hipFuncSetAttribute((const void*)dcn_fwd_fused_kernel<true>,

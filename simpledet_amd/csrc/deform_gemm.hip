@@ -553,7 +553,7 @@ static int launch_gemm(GemmArgs& g, int batch, hipStream_t st) {
   // deform_gemm_split: 2 (default) scaled fp16 hi/lo split -- needs the operand maxima (g.amax: the
   // DCN entry points and sd_gemm_f32_ws provide them), without them the exact fp32 path runs;
   // 1 bf16 hi/lo split (no maxima needed, 9x the error); 0 fp32 MFMA
-  int split = tuning("deform_gemm_split", 2);
+  int split = tuning(Knob::deform_gemm_split);
   if (split == 2 && !g.amax) split = 0;
   if (split != 2) g.amax = nullptr;
   if (split >= 1) {
@@ -571,7 +571,7 @@ static int launch_gemm(GemmArgs& g, int batch, hipStream_t st) {
     const int slots = 2 * kNumCU, rem = tiles % slots;
     g.whole = tiles;
     g.ksplit = 1;
-    if (tuning("deform_gemm_ksplit", 1) == 1 && tiles > slots && rem > 0 && rem <= slots / 2 && nk >= 4) {
+    if (tuning(Knob::deform_gemm_ksplit) == 1 && tiles > slots && rem > 0 && rem <= slots / 2 && nk >= 4) {
       int ks = slots / rem;
       if (ks > nk / 2) ks = nk / 2;
       if (ks >= 2) {
@@ -589,16 +589,16 @@ static int launch_gemm(GemmArgs& g, int batch, hipStream_t st) {
                 : (((uintptr_t)p & 15) == 0 && sk % 4 == 0 && sbatch % 4 == 0 && rows % 4 == 0);
     };
 #ifdef SD_PROFILING
-    g.dbg = reinterpret_cast<long long*>(((uintptr_t)(unsigned)SD_PROF_TUNING("roi_align_dbg_hi", 0) << 32) |
-                                         (uintptr_t)(unsigned)SD_PROF_TUNING("roi_align_dbg_lo", 0));
-    g.dbg_cap = SD_PROF_TUNING("gemm_dbg_cap", 0);
-    g.ablate = SD_PROF_TUNING("gemm_ablate", 0);
+    g.dbg = reinterpret_cast<long long*>(((uintptr_t)(unsigned)SD_PROF_TUNING(roi_align_dbg_hi) << 32) |
+                                         (uintptr_t)(unsigned)SD_PROF_TUNING(roi_align_dbg_lo));
+    g.dbg_cap = SD_PROF_TUNING(gemm_dbg_cap);
+    g.ablate = SD_PROF_TUNING(gemm_ablate);
 #endif
     g.fast = aligned(g.A, ak, g.sam, g.sak, g.strideA, g.M) &&
              aligned(g.B, bk, g.sbn, g.sbk, g.strideB, g.N);
     g.vec_store = (((uintptr_t)g.C & 15) == 0 && g.ldc % 4 == 0 && g.strideC % 4 == 0 && g.N % 4 == 0 &&
-                   tuning("deform_gemm_vecstore", 1) == 1) ? 1 : 0;
-    g.nt_store = tuning("deform_gemm_nt", 1);
+                   tuning(Knob::deform_gemm_vecstore) == 1) ? 1 : 0;
+    g.nt_store = tuning(Knob::deform_gemm_nt);
     int e;
     if (ak && bk) e = launch_gemm_split<true, true>(g, grid, st);
     else if (ak) e = launch_gemm_split<true, false>(g, grid, st);
@@ -759,7 +759,7 @@ extern "C" int sd_gemm_f32_ws(int transA, int transB, int M, int N, int K, const
                               size_t workspace_bytes, void* stream) {
   unsigned* amax = nullptr;
   if (workspace && workspace_bytes >= 32 && M > 0 && N > 0 && K > 0 && batch > 0 && A && B &&
-      tuning("deform_gemm_split", 2) == 2) {
+      tuning(Knob::deform_gemm_split) == 2) {
     amax = reinterpret_cast<unsigned*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
     hipStream_t st = (hipStream_t)stream;
     SD_HIP_CHECK(hipMemsetAsync(amax, 0, 8, st));

@@ -418,7 +418,7 @@ static size_t dp_bwd_lds(const DpArgs& a, int* cap) {
   const long fixed = (long)dp_bwd_fixed_lds_bytes(a.ncls, a.P, a.S);
   long c = (kDpLds - fixed) / (4 * kDpNW);
   c = c > kDpPatchMax ? kDpPatchMax : (c < kDpPatchMin ? 0 : c & ~63L);
-  if (tuning("deform_psroi_bwd_patch", 1) == 0) c = 0;   // every tap straight to memory (A/B measurements)
+  if (tuning(Knob::deform_psroi_bwd_patch) == 0) c = 0;   // every tap straight to memory (A/B measurements)
   *cap = (int)c;
   return (size_t)(fixed + c * 4 * kDpNW);
 }

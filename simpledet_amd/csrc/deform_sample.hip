@@ -940,17 +940,17 @@ extern "C" int sd_deform_im2col(const float* x, const float* offset, float* col,
   const int P = g.Ho * g.Wo;
   const size_t lds = ((size_t)H * W + W + 8) * sizeof(float);
   if (kh * kw <= kDcnMaxTaps && lds <= 64 * 1024 && (long)H * W < (1L << 28) &&
-      tuning("dcn_im2col", 1) == 1) {
+      tuning(Knob::dcn_im2col) == 1) {
     constexpr int T = 256;
     const int vec = (((H * W) % 4 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0) |
-                    (tuning("dcn_window", 1) ? 0 : 2);
+                    (tuning(Knob::dcn_window) ? 0 : 2);
     // bit 0: non-temporal col stores (the product's setting); bits 1-2 switch parts off, profiling build only
-    const int nt = 1 | (SD_PROF_TUNING("dcn_im2col_nt", 1) & 6);
+    const int nt = 1 | (SD_PROF_TUNING(dcn_im2col_nt) & 6);
     // (channel splits per (image, group, pixel tile): 2-8 measured in round 3, no gain -- one)
     const int nsplit = 1;
     if (kh * kw == 9 && kw == 3 && vec == 1 && nt == 1 && C / dgroup >= 2 && P % 4 == 0 && ((uintptr_t)col & 15) == 0 &&
-        lds + 16 + 9 * T * sizeof(float) <= 31 * 1024 && tuning("dcn_im2col", 1) == 1 &&
-        tuning("dcn_im2col_pipe", 1) == 1)
+        lds + 16 + 9 * T * sizeof(float) <= 31 * 1024 && tuning(Knob::dcn_im2col) == 1 &&
+        tuning(Knob::dcn_im2col_pipe) == 1)
       hipLaunchKernelGGL((deform_im2col_pipe_kernel<T>), dim3(cdiv(P, T), dgroup, N), dim3(T),
                          lds + 16 + 9 * T * sizeof(float), (hipStream_t)stream, x, offset, col, g);
     else if (kh * kw == 9)
@@ -988,7 +988,7 @@ int sd::col2im_impl(const float* col, const float* offset, float* dx, int req, i
     int nb4 = (int)(((long)CC * H * W * 4 + budget4 - 1) / budget4);
     const int rows4 = (H + nb4 - 1) / nb4;
     nb4 = (H + rows4 - 1) / rows4;
-    if (tuning("dcn_col2im", 1) == 1 && (C / dgroup) % CC == 0 && P % 4 == 0 &&
+    if (tuning(Knob::dcn_col2im) == 1 && (C / dgroup) % CC == 0 && P % 4 == 0 &&
         (((uintptr_t)col | (uintptr_t)offset) & 15) == 0 && (long)CC * rows4 * W * 4 <= 150 * 1024 &&
         nb4 <= 65535) {
       const size_t lds4 = (size_t)CC * rows4 * W * sizeof(float);
@@ -997,7 +997,7 @@ int sd::col2im_impl(const float* col, const float* offset, float* dx, int req, i
       int wshift = 20;
       while (wshift > 0 && (double)kh * kw * P * (double)(1u << wshift) >= 4294967296.0) --wshift;
       const bool fx = wsum && ldsw <= 150 * 1024 && kh * kw <= 65535 && wshift >= 8 &&
-                      tuning("dcn_col2im_fx", 1) == 1;
+                      tuning(Knob::dcn_col2im_fx) == 1;
       if (fx) {
         SD_HIP_CHECK(hipMemsetAsync(wsum, 0, sizeof(unsigned) * (size_t)N * dgroup, st));
         if (ldsw > 64 * 1024)
@@ -1081,10 +1081,10 @@ extern "C" int sd_deform_col2im_coord(const float* col, const float* x, const fl
   const int P = g.Ho * g.Wo;
   const size_t lds = ((size_t)H * W + W + 8) * sizeof(float);
   if (kh * kw <= kDcnMaxTaps && lds <= 64 * 1024 && (long)H * W < (1L << 28) &&
-      tuning("dcn_coord", 1) == 1) {
+      tuning(Knob::dcn_coord) == 1) {
     constexpr int T = 256;
     const int vec = (((H * W) % 4 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0) |
-                    (tuning("dcn_window", 1) ? 0 : 2);
+                    (tuning(Knob::dcn_window) ? 0 : 2);
     if (kh * kw == 9)
       hipLaunchKernelGGL((deform_col2im_coord_lds_kernel<T, 9>), dim3(cdiv(P, T), dgroup, N),
                          dim3(T), lds, (hipStream_t)stream, col, x, offset, d_offset, g,

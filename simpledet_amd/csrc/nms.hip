@@ -959,7 +959,7 @@ static int proposal_impl(int version, const float* cls_prob, const float* bbox_p
   const size_t lds = (size_t)P2 * sizeof(unsigned long long);
   // levels with many anchors: the select is spread over G workgroups per image (6 short launches);
   // small levels keep the single-workgroup kernel (knob proposal_topk: 1 forces it, 2 forces multi)
-  const int mode = tuning("proposal_topk", 0);
+  const int mode = tuning(Knob::proposal_topk);
   const bool multi = mode == 2 || (mode != 1 && count >= 32768);
   if (multi) {
     a.G = topk_groups(count);

@@ -1015,16 +1015,16 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   // LDS with the band, so the band budget is a little smaller
   const bool flt = !a.amax8 && a.ax && a.ay;  // float arg-max planes: the same kernel without tables
   SD_REQUIRE(a.amax8 || flt, "RoIAlign backward needs the forward's arg-max (packed bytes or the two float planes)");
-  a.float_adds = tuning("roi_align_bwd_fx", 1) == 0 ? 1 : 0;
+  a.float_adds = tuning(Knob::roi_align_bwd_fx) == 0 ? 1 : 0;
   // RoIs per staged table chunk: the coordinate table (MODE 0) takes 3 words per axis bin and RoI, the tap table
   // (MODE 1) kTapMainWords = 4 -- two candidate entries of 8 bytes; 48 x 56 words = 10.75 KB at 7x7, as 24 x 112 at 14x14
   const int tch_coords = a.PP == 49 ? 32 : 16, tch_taps = a.PP == 49 ? 48 : 24;
   const int ne = a.PP == 49 ? 3 * 14 : 3 * 28;  // sample coordinates per RoI
-  a.ablate = SD_PROF_TUNING("roi_align_bwd_ablate", 0);
+  a.ablate = SD_PROF_TUNING(roi_align_bwd_ablate);
   if ((long)a.R * a.C * a.PP >= (1L << 31)) return SD_ERR_UNSUPPORTED;  // 32-bit lane offsets
   // single-level float arg-max backward on a small map: four channels per workgroup
   if (prepass == 0 && flt && !a.filter && nlvl == 1 && a.dx[0] && a.C % 4 == 0 && a.B <= 65535 &&
-      (long)a.L.H[0] * a.L.W[0] * 16 <= 72 * 1024 && tuning("roi_align_bwd_flt4", 1) == 1 &&
+      (long)a.L.H[0] * a.L.W[0] * 16 <= 72 * 1024 && tuning(Knob::roi_align_bwd_flt4) == 1 &&
       (((uintptr_t)a.dy | (uintptr_t)a.ax | (uintptr_t)a.ay) & 15) == 0) {
     const size_t lds4 = (size_t)a.L.H[0] * a.L.W[0] * 16 + 32;
     if (lds4 > 64 * 1024)
@@ -1069,7 +1069,7 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   // With the workspace pre-pass providing 8-byte tap entries the tables take twice the LDS; the band
   // budget drops from 36 to 27 KB so that FOUR workgroups still share a CU (27 + 10.75 + 2.1 KB):
   // 86.6 us against 98.5 us with 36 KB bands at three per CU.
-  const int lists_mode = tuning("roi_align_bwd_lists", 1);  // 1 lists + taps, 2 lists only, 0 none
+  const int lists_mode = tuning(Knob::roi_align_bwd_lists);  // 1 lists + taps, 2 lists only, 0 none
   bool use_taps = false, use_lists = false;
   size_t list_bytes = 0;
   if (!flt && workspace && ((uintptr_t)workspace & 15) == 0 && lists_mode == 1) {
@@ -1135,7 +1135,7 @@ int launch_bwd_fused(BwdFusedArgs& a, int nlvl, hipStream_t st, void* workspace,
   }
   a.lists_units = 0;
   a.pix_bound_words = 0;
-  if (tuning("roi_align_bwd_pixbound", 1) == 1)
+  if (tuning(Knob::roi_align_bwd_pixbound) == 1)
     for (int i = 0; i < nl; ++i) {
       const int l = a.order[i];
       const long words = (long)(((a.band_rows[l] - 1) >> 2) + 2) * (((a.L.W[l] - 1) >> 2) + 2);   // 4 x 4 cells (bwd_lists_block)
@@ -1236,8 +1236,8 @@ int launch_bwd(BwdArgs& a, hipStream_t st) {
   const long count = (long)a.B * a.R * a.C * a.PP;
   const size_t dx_bytes = (size_t)a.B * a.C * a.H * a.W * 4;
   if (dx_bytes == 0) return SD_OK;
-  const int variant = tuning("roi_align_bwd", 1);  // 0 global atomics, 1 LDS planes
-  a.ablate = SD_PROF_TUNING("roi_align_bwd_ablate", 0);
+  const int variant = tuning(Knob::roi_align_bwd);  // 0 global atomics, >= 1 LDS planes (2, the fused kernel, is the callers' choice)
+  a.ablate = SD_PROF_TUNING(roi_align_bwd_ablate);
   const size_t list_bytes = (size_t)(a.R + 8) * 4;
   if (variant >= 1 && (a.PP == 49 || a.PP == 196) && list_bytes < 20 * 1024 && count > 0) {
     return a.PP == 49 ? launch_bwd_plane<49>(a, st) : launch_bwd_plane<196>(a, st);
@@ -1278,7 +1278,7 @@ extern "C" int sd_roi_align_v2_bwd(const float* out_grad, const float* rois, con
     bool done = false;
     // (the fused kernels' weight bounds count bins per axis: square 7x7 / 14x14 pools only -- a 1x49 pool has
     // PP = 49 too and goes to the plane kernels, whose 64-bit sums need no such bound)
-    if (tuning("roi_align_bwd", 2) == 2 && (a.PP == 49 || a.PP == 196) && pooled_h == pooled_w &&
+    if (tuning(Knob::roi_align_bwd) == 2 && (a.PP == 49 || a.PP == 196) && pooled_h == pooled_w &&
         (long)B * R * C > 0 && R <= 8192) {
       BwdFusedArgs f{};
       f.L = a.L;
@@ -1457,7 +1457,7 @@ extern "C" int sd_fpn_roi_align_bwd(const float* out_grad, const float* rois,
   for (int l = 0; l < nlvl; ++l)
     SD_REQUIRE(d_feats_host[l] || (long)B * C == 0, "d_feats[%d] null", l);
   const long count = (long)B * R * C * a.PP;
-  if (tuning("roi_align_bwd", 2) == 2 && (a.PP == 49 || a.PP == 196) && pooled_h == pooled_w && count > 0 &&
+  if (tuning(Knob::roi_align_bwd) == 2 && (a.PP == 49 || a.PP == 196) && pooled_h == pooled_w && count > 0 &&
       R <= 8192) {
     BwdFusedArgs f{};
     f.L = a.L;

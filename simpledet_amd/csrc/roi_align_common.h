@@ -232,8 +232,6 @@ constexpr int kBandNP = 4;              // passes a wave keeps in registers (one
 constexpr int kBandMaxUnits = 512;      // virtual units ((level, image, band) x rounds of items) of one launch
 constexpr int kBandFillCost = 140, kBandPlaneCost = 60, kBandSetupCost = 1500;  // cost model, in item times
 constexpr int kBandSub = 4;             // list segments per unit (pre-pass workgroups per (level, image))
-constexpr int kBandXcdDefault = 1;      // roi_align_fwd_xcd when not set
-constexpr int kBandStaffDefault = 0;    // roi_align_fwd_staff when not set
 constexpr int kBandFallbackWGs = 0;    // (no separate exact-path blocks: the band workgroups do that work last)
 
 typedef float v2f __attribute__((ext_vector_type(2)));

@@ -1420,10 +1420,10 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
   const long count = (long)a.B * a.R * a.C * a.PH * a.PW;
   if (count == 0) return SD_OK;
   // 0: the naive per-element kernel only, 1 (default): band-resident kernel, tiled kernels where it does not apply
-  const int variant = tuning("roi_align_fwd", 1);
-  a.ablate = SD_PROF_TUNING("roi_align_fwd_ablate", 0);
-  a.dbg = reinterpret_cast<long long*>(((uintptr_t)(unsigned)SD_PROF_TUNING("roi_align_dbg_hi", 0) << 32) |
-                                       (uintptr_t)(unsigned)SD_PROF_TUNING("roi_align_dbg_lo", 0));
+  const int variant = tuning(Knob::roi_align_fwd);
+  a.ablate = SD_PROF_TUNING(roi_align_fwd_ablate);
+  a.dbg = reinterpret_cast<long long*>(((uintptr_t)(unsigned)SD_PROF_TUNING(roi_align_dbg_hi) << 32) |
+                                       (uintptr_t)(unsigned)SD_PROF_TUNING(roi_align_dbg_lo));
   const int nroi = a.B * a.R;
   // tiled fallback: 8 channel slices (workgroups) per RoI -- the largest divisor of C not above that
   a.nslice = 1;
@@ -1443,7 +1443,7 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     if (a.L.stride[l] >= 0 && a.L.W[l] < 2) wide = false;
   // ---- band-resident forward (default): pre-pass + one launch; needs the workspace ----
   if (variant == 1 && wide && ((a.PH == 7 && a.PW == 7) || (a.PH == 14 && a.PW == 14)) &&
-      a.R <= 65535 && workspace && tuning("roi_align_fwd_band", 1)) {
+      a.R <= 65535 && workspace && tuning(Knob::roi_align_fwd_band)) {
     BandArgs A{};
     BandPlan& P = A.p;
     const int POOL = a.PH;
@@ -1519,27 +1519,18 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
     // and again with the clocks of profiles/fwd_finish_clocks.txt)
     // (knobs roi_align_fwd_grab / _tail / _tail_planes: the same three values for A/B; any setting computes the same bytes.
     // Re-measured with the per-workgroup clocks of profiles/fwd_finish_clocks.txt: profiles/fwd_staffing_ab.txt)
-    auto knob_in = [](const char* key, int dflt, int lo, int hi) {
-      const int v = tuning(key, dflt);
-      return v < lo ? lo : (v > hi ? hi : v);
-    };
-    P.grab = knob_in("roi_align_fwd_grab", 0, 0, 64);   // (0: the launcher's choice)
+    P.grab = tuning(Knob::roi_align_fwd_grab);   // (0: the launcher's choice)
     if (P.grab == 0) P.grab = a.amax8 && !a.half_io ? 2 : 4;
     P.gbias = 0;
-    P.tail = knob_in("roi_align_fwd_tail", 0, 0, 100);
-    P.tail_planes = knob_in("roi_align_fwd_tail_planes", 8, 1, 8);
-    // roi_align_fwd_staff: which virtual unit a workgroup starts on -- 0 where the midpoint of its share of the cost
-    // prefix falls, 1 whole workgroups per unit so that units end together after whole reservations (band_staffing)
-    P.staff = knob_in("roi_align_fwd_staff", kBandStaffDefault, 0, 1);
+    P.tail = tuning(Knob::roi_align_fwd_tail);
+    P.tail_planes = tuning(Knob::roi_align_fwd_tail_planes);
+    P.staff = tuning(Knob::roi_align_fwd_staff);
     for (int l = 0; l < a.L.nlvl; ++l) {   // a level's reservation in channels, and reservations per unit
       const int g = P.g[l] > 0 ? P.g[l] : 1;
       P.gres[l] = (P.grab + g - 1) / g * g;
       P.nres[l] = (a.C + P.gres[l] - 1) / P.gres[l];
     }
-    // roi_align_fwd_xcd: how the workgroups' shares of the cost prefix map to blocks (see band_xcd_slot and the
-    // kernel's unit table).  Any value computes the same bytes.
-    P.xcd = tuning("roi_align_fwd_xcd", kBandXcdDefault);
-    P.xcd = P.xcd < 0 ? 0 : (P.xcd > 2 ? 2 : P.xcd);
+    P.xcd = tuning(Knob::roi_align_fwd_xcd);   // (see band_xcd_slot and the kernel's unit table; any value computes the same bytes)
     {
       // virtual units = sum over units of ceil(items / CAP) <= units + floor(all items / CAP), and a RoI
       // has at most POOL items: beyond the table's size the launch goes to the tiled kernels (the
@@ -1576,7 +1567,7 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
       // a plan has no such tables; roi_align_fwd_quad, float arg-max only, keeps its pre-pass as it is.)
       const int nbwd = merged ? bplan->lists_units * (kMergedListSplit + (bplan->pix_bound_words > 0 ? 1 : 0)) : 0;
       const size_t tail_lds = merged ? (size_t)(a.R + 8 + 16 + bplan->pix_bound_words) * 4 : 0;
-      const bool tail = tuning("roi_align_plan_tail", 1) == 1 && ncoord + nbwd > 0 && tail_lds <= (size_t)smem;
+      const bool tail = tuning(Knob::roi_align_plan_tail) == 1 && ncoord + nbwd > 0 && tail_lds <= (size_t)smem;
       static const BwdFusedArgs no_plan{};
       const BwdFusedArgs& tplan = tail && merged ? *bplan : no_plan;
       if (tail) {
@@ -1595,7 +1586,7 @@ int launch_fwd(FwdArgs& a, hipStream_t st, void* workspace, size_t workspace_byt
         if (!a.amax8 && !a.half_io && POOL == 7 && a.L.nlvl == 1 && a.L.stride[0] >= 0 && P.nbands[0] == 1 &&
             a.C % 4 == 0 && lds <= 78 * 1024 && a.B <= 65535 &&
             (((uintptr_t)a.L.data[0] | (uintptr_t)a.out | (uintptr_t)a.ax | (uintptr_t)a.ay) & 15) == 0 &&
-            tuning("roi_align_fwd_quad", 1) == 1) {
+            tuning(Knob::roi_align_fwd_quad) == 1) {
           SD_HIP_CHECK(hipFuncSetAttribute((const void*)roi_align_fwd_quad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
           hipLaunchKernelGGL(roi_align_fwd_quad, dim3(a.C / 4, a.B), dim3(512), lds, st, A);
           note_dispatch("sd::roi_fwd_prep_kernel<7> + sd::roi_align_fwd_quad");

@@ -376,11 +376,11 @@ extern "C" int sd_roi_pool_v1_fwd(const float* data, const float* rois, float* o
   SD_REQUIRE((long)H * W < (1L << 24), "plane too large for a float argmax index");
   if ((long)K * C == 0) return SD_OK;
   SD_REQUIRE(data && rois && out && maxidx, "null tensor pointer");
-  PoolArgs a{data, rois, out, maxidx, B, C, H, W, K, pooled_h, pooled_w, spatial_scale, SD_PROF_TUNING("roi_pool_fwd_ablate", 0)};
+  PoolArgs a{data, rois, out, maxidx, B, C, H, W, K, pooled_h, pooled_w, spatial_scale, SD_PROF_TUNING(roi_pool_fwd_ablate)};
   const size_t lds = (size_t)((((long)H * W + 3) & ~3L) + kPoolChunk * (4 + pooled_h + pooled_w)) * 4;
   // four planes + tables + per-wave staging rows (7x7 only), one workgroup of 1024 lanes per CU
   const size_t lds4 = (size_t)((long)H * W * 4 + ((kPoolChunk * (4 + 7 + 7) + 3) & ~3) + 16 * 2 * 196) * 4;
-  const int mode = tuning("roi_pool_fwd", 1);  // 1 default (four channels per workgroup when they fit), 2 one channel, 0 per-item kernel
+  const int mode = tuning(Knob::roi_pool_fwd);  // 1 four channels per workgroup when they fit, 2 one channel, 0 per-item kernel
   if (lds <= 64 * 1024 && H <= 32767 && W <= 32767 && B >= 1 && B <= 65535 && mode != 0) {
     // (with B == 0 every batch index is out of range: the wave-per-item kernel writes the zeros)
     hipStream_t st = (hipStream_t)stream;
@@ -430,7 +430,7 @@ extern "C" int sd_roi_pool_v1_bwd(const float* out_grad, const float* rois, cons
     nb = (H + rows - 1) / rows;
     const size_t lds = (size_t)((((long)rows * W + 3) & ~3L) * 4) + (size_t)(K + 4) * 4;
     const size_t lds4 = (size_t)H * W * 16 + (size_t)(K + 4) * 4;
-    const int mode = tuning("roi_pool_bwd", 1);  // 1 default, 2 one channel per workgroup, 0 global atomics
+    const int mode = tuning(Knob::roi_pool_bwd);  // 1 four channels per workgroup, 2 one channel, 0 global atomics
     if (mode == 1 && C % 4 == 0 && lds4 <= 76 * 1024 && B <= 65535 &&
         (((uintptr_t)out_grad | (uintptr_t)maxidx) & 15) == 0) {
       if (lds4 > 64 * 1024)

@@ -22,69 +22,27 @@ int fail(int code, const char* fmt, ...) {
 }
 
 namespace {
-struct Knob {
+// the rows of SD_KNOBS (common.h), each with the value in effect, which starts at the row's default
+struct KnobRow {
   const char* key;
+  int lo, hi;
   std::atomic<int> value;
-  std::atomic<bool> set;
-  Knob(const char* k, int v, bool s) : key(k), value(v), set(s) {}
 };
-// every knob a kernel launcher reads must be listed here (sd_set_tuning rejects unknown keys)
-Knob g_knobs[] = {
-    // ---- product: every key selects a kernel that some shape or entry point reaches without it (the
-    // workspace-free entry points, C % 4 != 0, planes over the LDS budget, ...); tests force them here ----
-    {"roi_align_fwd", 0, false},         // 1 (default): band-resident kernel / tiled kernels where it does not apply; 0: naive per-element kernel
-    {"roi_align_fwd_band", 0, false},    // 1 (default) band-resident forward: planes streamed through LDS, no gathers; 0: the tiled fallback kernels
-    {"roi_align_fwd_quad", 0, false},    // 1 (default): single-level float arg-max forward with four channel-last planes per workgroup when they fit (the C4 family); 0: the band kernel
-    {"roi_align_plan_tail", 0, false},   // 1 (default): the band forward's pre-pass builds only what that kernel reads; the coordinate table and the backward's plan are tasks in the band kernel's tail; 0: all of it in the (merged) pre-pass launch
-    {"roi_align_fwd_xcd", 0, false},     // band forward, which share of the cost prefix a block starts on: 0 linear in blockIdx; 1 XCD-contiguous (a unit's workgroups write through one L2); 2 the same, unit table interleaving the levels (default 1)
-    {"roi_align_fwd_staff", 0, false},   // band forward, which virtual unit a workgroup starts on: 0 where the midpoint of its share of the cost prefix falls; 1 whole workgroups per unit, chosen so that the units end together after whole reservations (band_staffing, roi_align_common.h)
-    {"roi_align_fwd_grab", 0, false},    // band forward: channels a workgroup reserves at a time, rounded up to whole fills (default 0: 2 for the fp32 packed arg-max forward, else 4)
-    {"roi_align_fwd_tail", 0, false},    // band forward: last per cent of a unit's channels handed out in smaller pieces (default 0)
-    {"roi_align_fwd_tail_planes", 0, false}, // band forward: planes of such a piece, 1..8 (default 8: whole fills)
-    {"roi_align_bwd", 0, false},         // 2 (default) fused all-level kernel; 1 per-level LDS planes; 0 global atomics
-    {"roi_align_bwd_flt4", 0, false},    // 1 (default): single-level float arg-max backward with four channel planes per workgroup when they fit
-    {"roi_align_bwd_fx", 0, false},      // 1 (default): band sums in 32-bit fixed point (bit-reproducible); 0: fp32 compare-and-swap adds, hardware order
-    {"roi_align_bwd_pixbound", 0, false}, // 1 (default): the list pre-pass bounds the weight per 4 x 4 pixel cell of a band (2-D difference array); 0: summed over the band's RoIs (what workspace-free calls get)
-    {"roi_align_bwd_lists", 0, false},   // workspace pre-pass: 1 RoI lists + tap tables per band unit (default), 2 lists only, 0 none
-    {"roi_pool_fwd", 0, false},          // 1 (default) four planes in LDS per workgroup, 2 one plane, 0 wave per (roi, channel)
-    {"roi_pool_bwd", 0, false},          // 1 (default) LDS planes, four channels per workgroup, 2 one channel, 0 global atomics
-    {"deform_psroi_bwd_patch", 0, false}, // 1 (default) (RoI, channel) patch summed in LDS, one atomic per touched pixel; 0 one global atomic per tap
-    {"proposal_topk", 0, false},         // 0 by level size (default), 1 single workgroup, 2 multi-workgroup
-    {"soft_nms_threads", 0, false},      // threads per problem: 64, 128 or 256 (default)
-    {"deform_gemm_split", 0, false},     // 2 (default): scaled fp16 hi/lo split (needs operand maxima); 1: bf16 hi/lo split; 0: fp32 MFMA
-    {"deform_gemm_vecstore", 0, false},  // 1 (default): whole-tile plain stores of the split GEMM leave as 512-byte tile rows through LDS; 0: element stores from the accumulator layout (what unaligned C gets)
-    {"deform_gemm_nt", 0, false},        // 1 (default): those whole-tile stores are non-temporal; 0: plain
-    {"deform_gemm_ksplit", 0, false},    // 1 (default): tiles of a mostly empty last round are cut into k slices (atomic adds)
-    {"dcn_im2col", 0, false},            // 1 LDS-plane im2col (default), 0 per-lane global gathers
-    {"dcn_window", 0, false},            // 1 stage only the touched range of each plane (default)
-    {"dcn_im2col_pipe", 0, false},       // 1 (default): 3x3 im2col with the next window loads before this channel is sampled, col rows stored as 1 KB pieces behind them (s_waitcnt vmcnt(3)); 0: stores in place
-    {"dcn_col2im", 0, false},            // 1 four channels per workgroup, shared sample geometry (default), 0 one channel
-    {"dcn_col2im_fx", 0, false},         // 1 (default): the layer's backward sums dX in fixed point (integer LDS adds), 0 fp32 compare-and-swap
-    {"dcn_coord", 0, false},             // 1 LDS-plane offset gradient (default), 0 per-lane gathers
-    {"dcn_fused", 0, false},             // 1 (default): the col-free entry points sample inside the GEMM; 0: im2col + GEMM
-    {"dcn_fused_tile", 0, false},        // pixels per tile of the fused kernels (1..96), 0 = balanced over the CUs (default): partial-tile tests
-    {"crowdhuman_front", 0, false},      // 0 (default): ch_finish traces each front entry back through the swaps; 1: LDS replay
-#ifdef SD_PROFILING
-    // ---- profiling build only (tools/libsimpledet_ops_hip_prof.so): results are WRONG when != 0 ----
-    {"roi_align_fwd_ablate", 0, false},
-    {"roi_pool_fwd_ablate", 0, false},
-    {"crowdhuman_target_stop", 0, false}, // k in 1..3: sd_crowdhuman_target launches its first k kernels only
-    {"roi_align_bwd_ablate", 0, false},
-    {"roi_align_dbg_lo", 0, false},      // device buffer for per-wave phase clocks
-    {"roi_align_dbg_hi", 0, false},
-    {"gemm_ablate", 0, false},           // skip the A (1) / B (2) prefetch of the split GEMM
-    {"gemm_dbg_cap", 0, false},          // waves the buffer above has room for (split GEMM)
-    {"dcn_im2col_nt", 0, false},         // bits 1-2: parts of the LDS im2col switched off
-    {"dcn_fused_ablate", 0, false},      // parts of the fused forward switched off
-#endif
-};
+#define SD_KNOB_ROW(id, dflt, lo, hi, what) {#id, lo, hi, {dflt}},
+KnobRow g_knobs[] = {SD_KNOBS(SD_KNOB_ROW)};
+#undef SD_KNOB_ROW
+
+KnobRow* find_knob(const char* key) {
+  for (auto& k : g_knobs)
+    if (!strcmp(k.key, key)) return &k;
+  return nullptr;
+}
 }  // namespace
 
-int tuning(const char* key, int dflt) {
-  for (auto& k : g_knobs)
-    if (!strcmp(k.key, key))
-      return k.set.load(std::memory_order_acquire) ? k.value.load(std::memory_order_relaxed) : dflt;
-  return dflt;
+int tuning(Knob knob) {
+  const KnobRow& k = g_knobs[(int)knob];
+  const int v = k.value.load(std::memory_order_relaxed);
+  return v < k.lo ? k.lo : (v > k.hi ? k.hi : v);
 }
 
 }  // namespace sd
@@ -195,21 +153,20 @@ extern "C" int sd_abi_version(void) { return SD_ABI_VERSION; }
 
 extern "C" int sd_set_tuning(const char* key, int value) {
   if (!key) return sd::fail(SD_ERR_INVALID_ARG, "null tuning key");
-  for (auto& k : sd::g_knobs)
-    if (!strcmp(k.key, key)) {
-      k.value.store(value, std::memory_order_relaxed);
-      k.set.store(true, std::memory_order_release);
-      return SD_OK;
-    }
-  return sd::fail(SD_ERR_INVALID_ARG, "unknown tuning key '%s'", key);
+  sd::KnobRow* k = sd::find_knob(key);
+  if (!k) return sd::fail(SD_ERR_INVALID_ARG, "unknown tuning key '%s'", key);
+  k->value.store(value, std::memory_order_relaxed);
+  return SD_OK;
 }
 
 extern "C" int sd_get_tuning(const char* key, int* value) {
   if (!key || !value) return sd::fail(SD_ERR_INVALID_ARG, "null argument");
-  for (auto& k : sd::g_knobs)
-    if (!strcmp(k.key, key)) {
-      *value = k.set.load() ? k.value.load() : -1;
-      return SD_OK;
-    }
-  return sd::fail(SD_ERR_INVALID_ARG, "unknown tuning key '%s'", key);
+  const sd::KnobRow* k = sd::find_knob(key);
+  if (!k) return sd::fail(SD_ERR_INVALID_ARG, "unknown tuning key '%s'", key);
+  *value = k->value.load(std::memory_order_relaxed);
+  return SD_OK;
+}
+
+extern "C" const char* sd_tuning_key(int index) {
+  return index >= 0 && index < (int)sd::Knob::kCount ? sd::g_knobs[index].key : nullptr;
 }

@@ -364,7 +364,7 @@ extern "C" int sd_soft_nms_batched(const float* dets, const int32_t* counts, int
     return SD_OK;
   }
   SD_REQUIRE(dets && out_dets && out_inds, "null tensor pointer");
-  int T = tuning("soft_nms_threads", 256);
+  int T = tuning(Knob::soft_nms_threads);
   if (T != 64 && T != 128) T = 256;
   const size_t lds = (((size_t)6 * Nmax + 1) & ~(size_t)1) * 4 + ((size_t)(Nmax + 63) / 64 + 1) * 8 +
                      (size_t)(T / kWave) * 8 + 16 +

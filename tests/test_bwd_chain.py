@@ -193,13 +193,10 @@ def test_coordinate_table_mode(ops, oracle, lists, mode):
     fw, want = reference(oracle, ("count7", 49), feats, rois, dy, 7)
     tf, tr, tdy = [_t(f) for f in feats], _t(rois), _t(dy)
     _, state = ops.fpn_roi_align_forward_packed(tf, tr, STRIDES, (7, 7))
-    lib().set_tuning("roi_align_bwd_lists", lists)
-    try:
+    with lib().tuned(roi_align_bwd_lists=lists):
         g1 = ops.fpn_roi_align_backward_packed(tdy, tr, state, [f.shape for f in feats], STRIDES)
         name = (lib().cdll.sd_last_dispatch() or b"").decode()
         g2 = ops.fpn_roi_align_backward_packed(tdy, tr, state, [f.shape for f in feats], STRIDES)
-    finally:
-        lib().set_tuning("roi_align_bwd_lists", 1)
     assert "roi_align_bwd_packed4<7,7,512,32,%d>" % mode in name, name
     compare(g1, want, "lists=%d" % lists)
     assert all(bool(torch.equal(a, b)) for a, b in zip(g1, g2))

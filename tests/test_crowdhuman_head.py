@@ -200,14 +200,11 @@ def test_hip_lds_replay_variant_gives_the_same_bits(ops, name):
     """tuning crowdhuman_front = 1: the front of the permutations from a replay of all swaps in LDS"""
     g, c = _golden(), _cases()[name]
     l = _lib.lib()
-    l.set_tuning("crowdhuman_front", 1)
-    try:
+    with l.tuned(crowdhuman_front=1):
         st = _state(ops, g[name + "/seed"][0])
         res = _run_target(ops, c, st)
         _check_targets(res, g, name, c["mode"], c["cfg"]["num_reg_class"])
         _check_state(st, g, name)
-    finally:
-        l.set_tuning("crowdhuman_front", 0)
 
 
 @pytest.mark.gpu

@@ -161,26 +161,16 @@ def test_sampling_kernel_families_give_the_same_bits(ops, cfg):
     tx, to = _t(x), _t(off)
     res = {}
     g = None
-    try:
-        for mode in (1, 0):
-            for k in ("dcn_im2col", "dcn_coord"):
-                lib().set_tuning(k, mode)
+    for mode in (1, 0):
+        with lib().tuned(dcn_im2col=mode, dcn_coord=mode):
             col = ops.deform_im2col(tx, to, **a)
             if g is None:
                 g = torch.randn_like(col)
             res[mode] = (col, ops.deform_col2im_coord(g, tx, to, **a))
-        for k in ("dcn_im2col", "dcn_coord"):
-            lib().set_tuning(k, 1)
-        lib().set_tuning("dcn_window", 0)
+    with lib().tuned(dcn_window=0):
         res["whole"] = (ops.deform_im2col(tx, to, **a), ops.deform_col2im_coord(g, tx, to, **a))
-        lib().set_tuning("dcn_window", 1)
-        lib().set_tuning("dcn_im2col_pipe", 0)   # col stores in place instead of one channel behind the window loads
+    with lib().tuned(dcn_im2col_pipe=0):   # col stores in place instead of one channel behind the window loads
         res["inplace"] = (ops.deform_im2col(tx, to, **a), res[1][1])
-    finally:
-        lib().set_tuning("dcn_window", 1)
-        lib().set_tuning("dcn_im2col_pipe", 1)
-        for k in ("dcn_im2col", "dcn_coord"):
-            lib().set_tuning(k, 1)
     for key in (0, "whole", "inplace"):
         assert torch.equal(res[1][0], res[key][0]), ("im2col", key)
         assert torch.equal(res[1][1], res[key][1]), ("col2im_coord", key)   # same products, same channel order
@@ -203,8 +193,7 @@ def test_mfma_gemm_all_layouts(ops, shape, split):
     B = rs.standard_normal((Bt, K, N)).astype(np.float32)
     want = np.einsum("bmk,bkn->bmn", A.astype(np.float64), B.astype(np.float64))
     tol = (2e-5 if split == 1 else 2e-6) * max(1.0, float(np.abs(want).max()))
-    lib().set_tuning("deform_gemm_split", split)
-    try:
+    with lib().tuned(deform_gemm_split=split):
         for ta in (False, True):
             for tb in (False, True):
                 a = _t(A.transpose(0, 2, 1).copy() if ta else A)
@@ -216,8 +205,6 @@ def test_mfma_gemm_all_layouts(ops, shape, split):
         for mode in (1, 2):
             got = ops.gemm_f32(_t(A), _t(B), out=_t(c0), accumulate=mode).cpu().numpy()
             assert np.abs(got - (want + c0)).max() <= tol, mode
-    finally:
-        lib().set_tuning("deform_gemm_split", 2)
 
 
 @pytest.mark.gpu
@@ -233,17 +220,11 @@ def test_gemm_tile_rows_through_lds_are_the_same_bits(ops, shape):
     a = torch.randn((Bt, K, M), device="cuda", generator=g)   # trans_a: the dcol product's layout
     b = torch.randn((Bt, K, N), device="cuda", generator=g)
     got = ops.gemm_f32(a, b, trans_a=True)
-    lib().set_tuning("deform_gemm_vecstore", 0)
-    try:
+    with lib().tuned(deform_gemm_vecstore=0):
         want = ops.gemm_f32(a, b, trans_a=True)
-    finally:
-        lib().set_tuning("deform_gemm_vecstore", 1)
     assert torch.equal(got, want)
-    lib().set_tuning("deform_gemm_nt", 0)   # (round 6: those row stores are non-temporal by default; plain ones: same bits)
-    try:
+    with lib().tuned(deform_gemm_nt=0):   # (round 6: those row stores are non-temporal by default; plain ones: same bits)
         plain = ops.gemm_f32(a, b, trans_a=True)
-    finally:
-        lib().set_tuning("deform_gemm_nt", 1)
     assert torch.equal(got, plain)
     ref = torch.bmm(a.double().transpose(1, 2), b.double())
     assert float((got.double() - ref).abs().max()) <= 2e-6 * float(ref.abs().max())
@@ -279,13 +260,10 @@ def test_dcn_products_default_split_is_as_good_as_exact_fp32(ops, scales):
                torch.bmm(dy.double(), col.double().transpose(1, 2)).sum(0)),
     }
     err = {}
-    try:
-        for split in (2, 0, 1):
-            lib().set_tuning("deform_gemm_split", split)
+    for split in (2, 0, 1):
+        with lib().tuned(deform_gemm_split=split):
             for name, (fn, want) in prods.items():
                 err[name, split] = float((fn().double() - want).abs().max() / want.abs().max())
-    finally:
-        lib().set_tuning("deform_gemm_split", 2)
     for name in prods:
         assert err[name, 2] <= 2.0 * err[name, 0] + 1e-9, (name, err)
         assert err[name, 2] <= 2e-6, (name, err)           # fp32-class accuracy in absolute terms too
@@ -344,13 +322,10 @@ def test_dcn_products_with_one_outlier_of_2_to_the_20(ops, where):
         reached["y"][0][:, hit.any(0)] = True
         reached["dW"][0][:, hit.any(1)] = True
     res = {}
-    try:
-        for split in (2, 0):
-            lib().set_tuning("deform_gemm_split", split)
+    for split in (2, 0):
+        with lib().tuned(deform_gemm_split=split):
             for name, (fn, want) in prods.items():
                 res[name, split] = (fn().double() - want).abs()
-    finally:
-        lib().set_tuning("deform_gemm_split", 2)
     seen = {}
     for name, (_, want) in prods.items():
         r, calm = reached[name], ~reached[name]
@@ -381,8 +356,7 @@ def test_gemm_k_slices_of_the_last_round(ops):
     tol = 2e-5 * float(want.abs().max())
     outs = []
     for ks in (1, 0):
-        lib().set_tuning("deform_gemm_ksplit", ks)
-        try:
+        with lib().tuned(deform_gemm_ksplit=ks):
             c = torch.full((Bt, M, N), float("nan"), device="cuda")
             got = ops.gemm_f32(A, B, out=c)
             assert float((got.double() - want).abs().max()) <= tol, ks
@@ -391,8 +365,6 @@ def test_gemm_k_slices_of_the_last_round(ops):
             for mode in (1, 2):
                 got = ops.gemm_f32(A, B, out=c0.clone(), accumulate=mode)
                 assert float((got.double() - want - c0.double()).abs().max()) <= tol, (ks, mode)
-        finally:
-            lib().set_tuning("deform_gemm_ksplit", 1)
     # whole tiles are the same blocks in both modes
     assert torch.equal(outs[0][:32], outs[1][:32])
 
@@ -537,17 +509,11 @@ def test_fused_forward_without_col_matrix(ops, oracle, cfg):
         assert float(np.abs(yn[n] - want).max()) <= _bar(want), (n, float(np.abs(yn[n] - want).max()))
     assert float((y - y_unf).abs().max()) <= _bar(y_unf.cpu().numpy())
     for tile in (96, 37, 1) if x.shape[2] * x.shape[3] <= 600 else (64,):
-        lib().set_tuning("dcn_fused_tile", tile)
-        try:
+        with lib().tuned(dcn_fused_tile=tile):
             yt = ops.deform_conv_forward(tx, to, tw, **a)
-        finally:
-            lib().set_tuning("dcn_fused_tile", 0)
         assert float((yt - y).abs().max()) <= 1e-5 * max(1.0, float(y.abs().max())), tile
-    lib().set_tuning("dcn_fused", 0)
-    try:
+    with lib().tuned(dcn_fused=0):
         y0 = ops.deform_conv_forward(tx, to, tw, **a)
-    finally:
-        lib().set_tuning("dcn_fused", 1)
     assert torch.equal(y0, y_unf)
 
 
@@ -660,13 +626,10 @@ def test_backward_fixed_point_col2im(ops, oracle, case):
     if case == "inf":
         dy[1, 3, 5, 6] = np.inf
     outs = {}
-    try:
-        for fx in (1, 1, 0):
-            lib().set_tuning("dcn_col2im_fx", fx)
+    for fx in (1, 1, 0):
+        with lib().tuned(dcn_col2im_fx=fx):
             outs.setdefault(fx, []).append(
                 ops.deform_conv_backward(_t(dy), _t(x), _t(off), _t(w), **a)[0].cpu().numpy())
-    finally:
-        lib().set_tuning("dcn_col2im_fx", 1)
     np.testing.assert_array_equal(outs[1][0], outs[1][1])          # order independent
     wdx = np.zeros_like(x)
     with np.errstate(invalid="ignore", over="ignore"):

@@ -70,7 +70,6 @@ ROWS = dict(TABLE, **EXTRA)
 WILD = ("A", "E", "I", "M")     # again with offsets of scale 40: whole-plane windows, most samples outside
 GPU_CASES = [(r, None) for r in ROWS] + [(r, 40.0) for r in WILD]
 DG = 2
-KNOBS = ("dcn_im2col", "dcn_window", "dcn_im2col_pipe", "dcn_col2im", "dcn_col2im_fx", "dcn_coord")
 
 
 def _geo(row):
@@ -241,45 +240,37 @@ def _t(a):
 
 
 def _with(knob, fn):
-    """fn() with one kernel family switched off; the knob goes back to its default whatever happens"""
+    """fn() with one kernel family switched off; the knob goes back to what it was whatever happens"""
     from simpledet_amd._lib import lib
-    lib().set_tuning(knob, 0)
-    try:
+    with lib().tuned(**{knob: 0}):
         return fn()
-    finally:
-        lib().set_tuning(knob, 1)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("row,scale", GPU_CASES)
 def test_pieces_match_the_oracle(ops, row, scale):
-    from simpledet_amd._lib import lib
     x, off, g = _inputs(row, scale)
     wcol, wdx, wdo = _want(row, scale)
     a = _ops_geo(row)
     tx, to, tg = _t(x), _t(off), _t(g)
-    try:
-        # im2col: the same float operations in the same order as the oracle -- the same bits, from every family
-        col = ops.deform_im2col(tx, to, **a)
-        np.testing.assert_array_equal(col.cpu().numpy(), wcol)
-        for knob in ("dcn_im2col", "dcn_window", "dcn_im2col_pipe"):
-            assert torch.equal(_with(knob, lambda: ops.deform_im2col(tx, to, **a)), col), knob
-        # col2im: fixed-point sums (workspace), fp32 compare-and-swap adds (none), four-channel float, one-channel
-        runs = {("default", ws): ops.deform_col2im(tg, to, x.shape, workspace=ws, **a) for ws in (True, False)}
-        for knob in ("dcn_col2im", "dcn_col2im_fx"):
-            for ws in (True, False):
-                runs[knob, ws] = _with(knob, lambda: ops.deform_col2im(tg, to, x.shape, workspace=ws, **a))
-        for key, dx in runs.items():
-            np.testing.assert_allclose(dx.cpu().numpy(), wdx, rtol=1e-4, atol=1e-4, err_msg=str(key))
-        if (x.shape[1] // DG) % 4 == 0 and wcol.shape[2] % 4 == 0:   # the fixed-point kernel: order independent
-            assert torch.equal(ops.deform_col2im(tg, to, x.shape, workspace=True, **a), runs["default", True])
-        # col2im_coord: a per-lane reduction in the oracle's channel order -- LDS and per-lane forms, same bits
-        do = ops.deform_col2im_coord(tg, tx, to, **a)
-        np.testing.assert_allclose(do.cpu().numpy(), wdo, rtol=1e-4, atol=1e-4)
-        assert torch.equal(_with("dcn_coord", lambda: ops.deform_col2im_coord(tg, tx, to, **a)), do)
-    finally:
-        for knob in KNOBS:
-            lib().set_tuning(knob, 1)
+    # im2col: the same float operations in the same order as the oracle -- the same bits, from every family
+    col = ops.deform_im2col(tx, to, **a)
+    np.testing.assert_array_equal(col.cpu().numpy(), wcol)
+    for knob in ("dcn_im2col", "dcn_window", "dcn_im2col_pipe"):
+        assert torch.equal(_with(knob, lambda: ops.deform_im2col(tx, to, **a)), col), knob
+    # col2im: fixed-point sums (workspace), fp32 compare-and-swap adds (none), four-channel float, one-channel
+    runs = {("default", ws): ops.deform_col2im(tg, to, x.shape, workspace=ws, **a) for ws in (True, False)}
+    for knob in ("dcn_col2im", "dcn_col2im_fx"):
+        for ws in (True, False):
+            runs[knob, ws] = _with(knob, lambda: ops.deform_col2im(tg, to, x.shape, workspace=ws, **a))
+    for key, dx in runs.items():
+        np.testing.assert_allclose(dx.cpu().numpy(), wdx, rtol=1e-4, atol=1e-4, err_msg=str(key))
+    if (x.shape[1] // DG) % 4 == 0 and wcol.shape[2] % 4 == 0:   # the fixed-point kernel: order independent
+        assert torch.equal(ops.deform_col2im(tg, to, x.shape, workspace=True, **a), runs["default", True])
+    # col2im_coord: a per-lane reduction in the oracle's channel order -- LDS and per-lane forms, same bits
+    do = ops.deform_col2im_coord(tg, tx, to, **a)
+    np.testing.assert_allclose(do.cpu().numpy(), wdo, rtol=1e-4, atol=1e-4)
+    assert torch.equal(_with("dcn_coord", lambda: ops.deform_col2im_coord(tg, tx, to, **a)), do)
 
 
 @pytest.mark.gpu
@@ -310,13 +301,10 @@ def test_fused_forward_transposition_relation(ops, cfg, tile):
     w = (rs.standard_normal((F, C, 3, 3)) * 0.2).astype(np.float32)
     offt = np.ascontiguousarray(off.reshape(N, DG, 3, 3, 2, Ho, Wo).transpose(0, 1, 3, 2, 4, 6, 5)[:, :, :, :, ::-1])
     offt = offt.reshape(N, DG * 18, Wo, Ho)
-    lib().set_tuning("dcn_fused_tile", tile)
-    try:
+    with lib().tuned(dcn_fused_tile=tile):
         y = ops.deform_conv_forward(_t(x), _t(off), _t(w), num_deformable_group=DG, **cfg).cpu().numpy()
         yt = ops.deform_conv_forward(_t(x.transpose(0, 1, 3, 2)), _t(offt), _t(w.transpose(0, 1, 3, 2)),
                                      num_deformable_group=DG, **cfg).cpu().numpy()
-    finally:
-        lib().set_tuning("dcn_fused_tile", 0)
     assert y.shape == (N, F, Ho, Wo) and yt.shape == (N, F, Wo, Ho)
     assert float(np.abs(y).max()) > 1.0
     err = float(np.abs(yt.transpose(0, 1, 3, 2) - y).max())

@@ -45,11 +45,8 @@ def test_roi_pool_forward_backward(ops, oracle, case, fwd):
     seed, ph, pw, scale = case
     data, rois = _pool_case(seed)
     want, widx = oracle.roi_pool_v1_fwd(data, rois, (ph, pw), scale)
-    lib().set_tuning("roi_pool_fwd", fwd)
-    try:
+    with lib().tuned(roi_pool_fwd=fwd):
         out, idx = ops.roi_pool_v1_forward(_t(data), _t(rois), (ph, pw), scale)
-    finally:
-        lib().set_tuning("roi_pool_fwd", 1)
     np.testing.assert_array_equal(out.cpu().numpy(), want)
     np.testing.assert_array_equal(idx.cpu().numpy(), widx)
     dy = np.random.RandomState(9).standard_normal(want.shape).astype(np.float32)
@@ -80,11 +77,8 @@ def test_roi_pool_forward_kernels_agree_at_c4_size(ops):
     rois = _t(np.concatenate([bi, r], 1))
     o1, i1 = ops.roi_pool_v1_forward(data, rois, (7, 7), 1 / 16.0)
     for mode in (0, 2):
-        lib().set_tuning("roi_pool_fwd", mode)
-        try:
+        with lib().tuned(roi_pool_fwd=mode):
             o0, i0 = ops.roi_pool_v1_forward(data, rois, (7, 7), 1 / 16.0)
-        finally:
-            lib().set_tuning("roi_pool_fwd", 1)
         assert torch.equal(o1, o0) and torch.equal(i1, i0), mode
     assert float(o1[[7, 600]].abs().max()) == 0 and float((i1[[7, 600]] + 1).abs().max()) == 0
 
@@ -107,11 +101,8 @@ def test_roi_pool_backward_bands_and_fallback(ops, oracle):
     wdx = oracle.roi_pool_v1_bwd(dy, rois, widx, data.shape, scale)
     dx, _ = ops.roi_pool_v1_backward(_t(dy), _t(rois), idx, data.shape, scale)
     np.testing.assert_allclose(dx.cpu().numpy(), wdx, rtol=1e-5, atol=1e-5)
-    lib().set_tuning("roi_pool_bwd", 0)
-    try:
+    with lib().tuned(roi_pool_bwd=0):
         dx0, _ = ops.roi_pool_v1_backward(_t(dy), _t(rois), idx, data.shape, scale)
-    finally:
-        lib().set_tuning("roi_pool_bwd", 1)
     np.testing.assert_allclose(dx0.cpu().numpy(), wdx, rtol=1e-5, atol=1e-5)
     # conservation at the C4 baseline shape: every pooled gradient lands in exactly one pixel
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -124,11 +115,8 @@ def test_roi_pool_backward_bands_and_fallback(ops, oracle):
     # (64 channels: the four-channel kernel) == the one-channel LDS kernel == the global-atomic structure,
     # also with kAddTo
     for mode in (2, 0):
-        lib().set_tuning("roi_pool_bwd", mode)
-        try:
+        with lib().tuned(roi_pool_bwd=mode):
             gm, _ = ops.roi_pool_v1_backward(gy, br, ix, big.shape, 1 / 16.0)
-        finally:
-            lib().set_tuning("roi_pool_bwd", 1)
         assert float((gm - gx).abs().max()) <= 1e-5 * float(gx.abs().max()), mode
     ga, _ = ops.roi_pool_v1_backward(gy, br, ix, big.shape, 1 / 16.0, req_data="add", req_rois="null",
                                      d_data=gx.clone())
@@ -393,15 +381,12 @@ def test_soft_nms_nan_inf_scores_and_lane_count_boundaries(ops, oracle, threads)
     weird[[9, 200], 4] = np.inf
     weird[[11], 4] = -np.inf
     dets = np.stack([d, synth.nms_dets(4, 400, mode="all_overlap"), weird])
-    lib().set_tuning("soft_nms_threads", threads)
-    try:
+    with lib().tuned(soft_nms_threads=threads):
         for method in (0, 1, 2):
             _soft_check(ops, oracle, dets, np.array([400, 400, 400]), 0.5, 0.3, 0.01, method)
         for Nmax in (1, 63, 64, 65, 127, 129, 255, 256, 257, 511, 513, 1000, 1025, 2049):
             b = np.stack([synth.nms_dets(70 + Nmax + p, Nmax) for p in range(2)])
             _soft_check(ops, oracle, b, np.array([Nmax, int(rs.randint(0, Nmax + 1))]), 0.5, 0.5, 0.001, 1)
-    finally:
-        lib().set_tuning("soft_nms_threads", 256)
 
 
 @pytest.mark.gpu
@@ -596,12 +581,9 @@ def test_proposal_v3_matches_oracle(ops, oracle, cfg, topk):
     thr, ms = cfg.get("thr", 0.7), cfg.get("min_size", 16)
     want = oracle.proposal_v3(cls, bb, info, cfg["pre"], cfg["post"], thr, ms, scales, ratios,
                               cfg["stride"], cfg["train"])
-    lib().set_tuning("proposal_topk", topk)
-    try:
+    with lib().tuned(proposal_topk=topk):
         out, score = ops.proposal_v3(_t(cls), _t(bb), _t(info), cfg["pre"], cfg["post"], thr, ms,
                                      scales, ratios, cfg["stride"], cfg["train"])
-    finally:
-        lib().set_tuning("proposal_topk", 0)
     np.testing.assert_array_equal(score.cpu().numpy(), want[1])
     np.testing.assert_array_equal(out.cpu().numpy(), want[0])
 
@@ -613,12 +595,9 @@ def test_proposal_v3_score_ties_are_stable(ops, oracle, topk):
     cls, bb, info = synth.rpn_outputs(5, 1, 3, 50, 84, 16)
     cls[:, 3:] = np.round(cls[:, 3:] * 32) / 32   # thousands of exactly tied scores
     want = oracle.proposal_v3(cls, bb, info, 1000, 1000, 0.7, 0, (8,), (0.5, 1, 2), 16, False)
-    lib().set_tuning("proposal_topk", topk)
-    try:
+    with lib().tuned(proposal_topk=topk):
         out, score = ops.proposal_v3(_t(cls), _t(bb), _t(info), 1000, 1000, 0.7, 0, (8,),
                                      (0.5, 1, 2), 16)
-    finally:
-        lib().set_tuning("proposal_topk", 0)
     np.testing.assert_array_equal(score.cpu().numpy(), want[1])
     np.testing.assert_array_equal(out.cpu().numpy(), want[0])
 

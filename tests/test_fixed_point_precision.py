@@ -138,11 +138,9 @@ def test_fused_fpn_backward_gaussian_full_size_pixel_bound(ops, oracle):
     wd = np.concatenate([w.ravel() for w in oracle.fpn_roi_align_bwd(dy, rois, want[1], want[2], shapes, STRIDES)])
     tdy = _t(dy)
     errs = {}
-    try:
-        for name, pix, fx, plan in (("pixel_bound_plan", 1, 1, True), ("pixel_bound", 1, 1, False),
-                                    ("band_sum_bound", 0, 1, False), ("float_adds", 1, 0, False)):
-            lib().set_tuning("roi_align_bwd_pixbound", pix)
-            lib().set_tuning("roi_align_bwd_fx", fx)
+    for name, pix, fx, plan in (("pixel_bound_plan", 1, 1, True), ("pixel_bound", 1, 1, False),
+                                ("band_sum_bound", 0, 1, False), ("float_adds", 1, 0, False)):
+        with lib().tuned(roi_align_bwd_pixbound=pix, roi_align_bwd_fx=fx):
             out, state = ops.fpn_roi_align_forward_packed(tf, tr, STRIDES, (7, 7), plan=plan)
             gd = ops.fpn_roi_align_backward_packed(tdy, tr, state, shapes, STRIDES)
             got = np.concatenate([g.cpu().numpy().ravel() for g in gd])
@@ -150,9 +148,6 @@ def test_fused_fpn_backward_gaussian_full_size_pixel_bound(ops, oracle):
             if fx:   # integer sums: a deterministic function of the inputs
                 gd2 = ops.fpn_roi_align_backward_packed(tdy, tr, state, shapes, STRIDES)
                 assert all(bool((a == b).all()) for a, b in zip(gd, gd2)), name
-    finally:
-        lib().set_tuning("roi_align_bwd_pixbound", 1)
-        lib().set_tuning("roi_align_bwd_fx", 1)
     _save("fused_fpn_gaussian_full_size_max_abs_err", errs)
     assert max(errs.values()) <= 1e-4, errs
     assert errs["pixel_bound"] <= errs["band_sum_bound"], errs
@@ -160,9 +155,9 @@ def test_fused_fpn_backward_gaussian_full_size_pixel_bound(ops, oracle):
 
 
 # ------------------------------------------------------------------------------------------------ (b)
-def _fx(ops, knob, value):
+def _fx(**knobs):
     from simpledet_amd._lib import lib
-    lib().set_tuning(knob, value)
+    return lib().tuned(**knobs)
 
 
 @pytest.mark.gpu
@@ -180,17 +175,12 @@ def test_fused_fpn_backward_heavy_tailed_loss_scaled(ops, oracle):
     mass = oracle.fpn_roi_align_bwd(np.abs(dy), rois, want[1], want[2], shapes, STRIDES)
     tdy = _t(dy)
     res = {}
-    try:
-        for fx in (1, 0):
-            _fx(ops, "roi_align_bwd_fx", fx)
+    for fx in (1, 0):
+        with _fx(roi_align_bwd_fx=fx):
             gd = ops.fpn_roi_align_backward_packed(tdy, tr, state, shapes, STRIDES)
-            if fx == 1:   # a deterministic function of the inputs whichever adds a workgroup took ... except float adds
-                pass
             got = np.concatenate([g.cpu().numpy().ravel() for g in gd])
-            res["fx%d" % fx] = _stats(got, np.concatenate([w.ravel() for w in wd]),
-                                      np.concatenate([m.ravel() for m in mass]), float(np.median(np.abs(dy))))
-    finally:
-        _fx(ops, "roi_align_bwd_fx", 1)
+        res["fx%d" % fx] = _stats(got, np.concatenate([w.ravel() for w in wd]),
+                                  np.concatenate([m.ravel() for m in mass]), float(np.median(np.abs(dy))))
     _save("fused_fpn_heavy_tailed", res)
     _assert_bars("fused_fpn", res["fx1"])
 
@@ -207,13 +197,10 @@ def test_c4_backward_heavy_tailed_loss_scaled(ops, oracle):
     mass = oracle.roi_align_v2_bwd(np.abs(dy), ax, ay, data.shape)
     args = (_t(dy), _t(rois), _t(ax), _t(ay), data.shape, 1 / 16.0)
     res = {}
-    try:
-        for fx in (1, 0):
-            _fx(ops, "roi_align_bwd_fx", fx)
+    for fx in (1, 0):
+        with _fx(roi_align_bwd_fx=fx):
             got = ops.roi_align_v2_backward(*args)[0].cpu().numpy()
-            res["fx%d" % fx] = _stats(got, want, mass, float(np.median(np.abs(dy))))
-    finally:
-        _fx(ops, "roi_align_bwd_fx", 1)
+        res["fx%d" % fx] = _stats(got, want, mass, float(np.median(np.abs(dy))))
     _save("c4_heavy_tailed", res)
     _assert_bars("c4", res["fx1"])
 
@@ -237,19 +224,18 @@ def test_dcn_col2im_heavy_tailed_loss_scaled(ops, oracle):
         mass[n] = oracle.deform_col2im(np.abs(dcol), off[n], x[n].shape, **kw)
     res = {}
     floor = float(np.median(np.abs(np.stack([w.reshape(F, -1).T @ dy[n].reshape(F, -1) for n in range(N)]))))   # median |dcol|
-    try:
-        for fx in (1, 0):
-            _fx(ops, "dcn_col2im_fx", fx)
+    for fx in (1, 0):
+        with _fx(dcn_col2im_fx=fx):
             got = ops.deform_conv_backward(_t(dy), _t(x), _t(off), _t(w), pad=1, stride=1, dilate=1,
                                            num_deformable_group=dg)[0].cpu().numpy()
-            res["fx%d" % fx] = _stats(got, wdx, mass, floor)
-        # the stand-alone entry point (sd_deform_col2im_ws) on the oracle's own dcol: no GEMM in between
-        dcols = np.stack([(w.reshape(F, -1).T.astype(np.float64) @ dy[n].reshape(F, -1).astype(np.float64)).astype(np.float32)
-                          for n in range(N)])
+        res["fx%d" % fx] = _stats(got, wdx, mass, floor)
+    # the stand-alone entry point (sd_deform_col2im_ws) on the oracle's own dcol: no GEMM in between (it has
+    # always run behind the loop's last setting, dcn_col2im_fx = 0, and still does)
+    dcols = np.stack([(w.reshape(F, -1).T.astype(np.float64) @ dy[n].reshape(F, -1).astype(np.float64)).astype(np.float32)
+                      for n in range(N)])
+    with _fx(dcn_col2im_fx=0):
         got = ops.deform_col2im(_t(dcols), _t(off), x.shape, (3, 3), 1, 1, 1, dg).cpu().numpy()
-        res["standalone_ws"] = _stats(got, wdx, mass, floor)
-    finally:
-        _fx(ops, "dcn_col2im_fx", 1)
+    res["standalone_ws"] = _stats(got, wdx, mass, floor)
     _save("dcn_col2im_heavy_tailed", res)
     assert res["standalone_ws"]["mass_bar"] <= 1e-4, res["standalone_ws"]
     # dcol itself comes out of the split-fp16 GEMM (2e-6 x max|dcol| per element): the bar is the

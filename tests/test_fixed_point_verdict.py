@@ -260,12 +260,9 @@ def _run_fused(ops, oracle, rois, dy, pooled, modes, C=8, seed=0):
         else:
             _, state = ops.fpn_roi_align_forward_packed(tf, tr, STRIDES, P)
             run = lambda: ops.fpn_roi_align_backward_packed(tdy, tr, state, shapes, STRIDES)
-        lib().set_tuning("roi_align_bwd_lists", 0 if mode == "lists0" else 1)
-        try:
+        with lib().tuned(roi_align_bwd_lists=0 if mode == "lists0" else 1):
             g1 = run()
             g2 = run()
-        finally:
-            lib().set_tuning("roi_align_bwd_lists", 1)
         same = all(bool(torch.equal(a, b)) for a, b in zip(g1, g2))
         res[mode] = (_mass_bar(_cat([g.cpu().numpy() for g in g1]), want, mass, dy), same)
     return res

@@ -165,11 +165,8 @@ def test_proposal_v3_fuzz(ops, oracle):
                 ops.proposal_v3(_t(cls), _t(bb), _t(info), pre, post, thr, ms, scales, ratios, stride, train)
             continue
         want = oracle.proposal_v3(cls, bb, info, pre, post, thr, ms, scales, ratios, stride, train)
-        lib().set_tuning("proposal_topk", topk)
-        try:
+        with lib().tuned(proposal_topk=topk):
             out, score = ops.proposal_v3(_t(cls), _t(bb), _t(info), pre, post, thr, ms, scales, ratios,
                                          stride, train)
-        finally:
-            lib().set_tuning("proposal_topk", 0)
         np.testing.assert_array_equal(score.cpu().numpy(), want[1], err_msg=msg)
         np.testing.assert_array_equal(out.cpu().numpy(), want[0], err_msg=msg)

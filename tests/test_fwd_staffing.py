@@ -15,7 +15,6 @@ band_staffing itself is held to the plain-integer restatement of tools/fwd_sched
 import ctypes
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -60,20 +59,6 @@ def _feats(rs, B, C, shapes):
     return [rs.standard_normal((B, C, h, w)).astype(f32) for h, w in shapes]
 
 
-def defaults(ops):
-    """what the library runs when nobody has set the knobs, read off the dispatch string of one tiny launch"""
-    if "defaults" not in _CACHE:
-        from simpledet_amd._lib import lib
-        rs = np.random.RandomState(0)
-        ops.fpn_roi_align_forward_packed([_t(f) for f in _feats(rs, 1, 4, [(16, 16)])], _t(_rois(rs, 1, 4, 0, 30, 60, 8.0, 30.0)), [4], (7, 7))
-        d = (lib().cdll.sd_last_dispatch() or b"").decode()
-        m = re.search(r"\[roi_align_fwd_staff = (\d)\] \[reservations: grab (\d+), tail (\d+) % in pieces of (\d+) planes\]", d)
-        assert m, "the band forward's dispatch string names the staffing and the reservations that ran: " + d
-        staff, _, tail, planes = (int(x) for x in m.groups())
-        _CACHE["defaults"] = (staff, 0, tail, planes)      # (grab 0: the launcher's own choice, which depends on the form)
-    return _CACHE["defaults"]
-
-
 def forward(ops, feats, rois, P, strides, mode, setting):
     """one forward with the knobs set -> every buffer it wrote (and the dispatch string); mode "plan": packed arg-max
     with the backward's plan built in the same step, "f16": packed with fp16 features and output"""
@@ -82,10 +67,7 @@ def forward(ops, feats, rois, P, strides, mode, setting):
     from simpledet_amd.ops import _iarr, _p, _parr, _stream
     B, R = rois.shape[:2]
     C = feats[0].shape[1]
-    dflt = defaults(ops)
-    for k, v in zip(KNOBS, setting):
-        lib().set_tuning(k, v)
-    try:
+    with lib().tuned(**dict(zip(KNOBS, setting))):
         tr = _t(rois)
         tf = [_t(f.astype(f16) if mode == "f16" else f) for f in feats]
         hs, ws_ = _iarr([f.shape[2] for f in feats]), _iarr([f.shape[3] for f in feats])
@@ -107,9 +89,6 @@ def forward(ops, feats, rois, P, strides, mode, setting):
             res["plan"] = plan
         res["dispatch"] = (lib().cdll.sd_last_dispatch() or b"").decode()
         torch.cuda.synchronize()
-    finally:
-        for k, v in zip(KNOBS, dflt):
-            lib().set_tuning(k, v)
     return res
 
 

@@ -19,7 +19,6 @@ one wave, and every way the rows of the two y-samples can coincide (one row, the
 apart, clipped at the border, the zero box), through each instantiation of the kernel.
 """
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -60,23 +59,6 @@ def _feats(rs, B, C, img_h, img_w, strides):
     return [rs.standard_normal((B, C, img_h // s, img_w // s)).astype(f32) for s in strides]
 
 
-_DEFAULTS = []
-
-
-def knob_defaults(ops):
-    """what the library runs when nobody has set the knob, read off the dispatch string of one tiny launch (this
-    module is the only one that sets it, and puts this value back after every run)"""
-    if not _DEFAULTS:
-        from simpledet_amd._lib import lib
-        rs = np.random.RandomState(0)
-        ops.fpn_roi_align_forward_packed([_t(f) for f in _feats(rs, 1, 4, 64, 64, [4])], _t(_rois(rs, 1, 4, 64, 64, 8.0, 30.0)),
-                                         [4], (7, 7))
-        m = re.search(r"\[roi_align_fwd_xcd = (\d)\]", (lib().cdll.sd_last_dispatch() or b"").decode())
-        assert m, "the band forward's dispatch string names the value that ran"
-        _DEFAULTS.append(int(m.group(1)))
-    return _DEFAULTS
-
-
 def forward(ops, feats, rois, P, strides, mode, xcd):
     """one forward with the knob set -> every buffer it wrote (and the dispatch string).
     mode: "plan" packed arg-max with the backward's plan built in the same step, "f16" packed with fp16 features
@@ -86,9 +68,7 @@ def forward(ops, feats, rois, P, strides, mode, xcd):
     from simpledet_amd.ops import _iarr, _p, _parr, _stream
     B, R = rois.shape[:2]
     C = feats[0].shape[1]
-    dflt = knob_defaults(ops)
-    lib().set_tuning("roi_align_fwd_xcd", xcd)
-    try:
+    with lib().tuned(roi_align_fwd_xcd=xcd):
         tr = _t(rois)
         if mode == "float":
             assert len(feats) == 1
@@ -115,8 +95,6 @@ def forward(ops, feats, rois, P, strides, mode, xcd):
                 res["plan"] = plan
         res["dispatch"] = (lib().cdll.sd_last_dispatch() or b"").decode()
         torch.cuda.synchronize()
-    finally:
-        lib().set_tuning("roi_align_fwd_xcd", dflt[0])
     return res
 
 

@@ -111,8 +111,7 @@ def step(ops, feats, rois, dy, P, strides, tail, mode="plan", bufs=None, backwar
     res = {"out": out}
     tail_args = (B, C, R, P, P, 224.0, 4.0, _p(bufs.work), ctypes.c_size_t(bufs.wsb))
     head = (_parr(tf), bufs.hs, bufs.ws_, _iarr(strides), len(tf), _p(tr), _p(out))
-    lib().set_tuning(KNOB, tail)
-    try:
+    with lib().tuned(**{KNOB: tail}):
         if mode == "float":
             ax, ay = torch.zeros_like(out), torch.zeros_like(out)
             lib().call("sd_fpn_roi_align_fwd", *head, _p(ax), _p(ay), *tail_args, _stream())
@@ -145,8 +144,6 @@ def step(ops, feats, rois, dy, P, strides, tail, mode="plan", bufs=None, backwar
             for i, t in enumerate(g):
                 res["d_feat_%d" % i] = t
         torch.cuda.synchronize()
-    finally:
-        lib().set_tuning(KNOB, 1)
     return res
 
 

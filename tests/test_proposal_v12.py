@@ -5,6 +5,7 @@ the cut inside a long run of rows filtered to -1 on both top-k paths, graph capt
 the TridentNet Proposal_v2 -> ProposalTarget_v2 chain.  The restatement itself is held to the
 reference's .cu run through the MXNet stand-in and to its Python twins (tests/golden/proposal_ref.npz,
 made by tests/golden/make_golden_proposal.py)."""
+import contextlib
 import ctypes
 import os
 
@@ -222,9 +223,10 @@ def _trident(seed, B=6, H=50, W=75, **kw):
 
 @pytest.fixture
 def topk_mode():
+    """topk_mode(m): the rest of the test runs under proposal_topk = m"""
     from simpledet_amd._lib import lib
-    yield lambda m: lib().set_tuning("proposal_topk", m)
-    lib().set_tuning("proposal_topk", 0)
+    with contextlib.ExitStack() as stack:
+        yield lambda m: stack.enter_context(lib().tuned(proposal_topk=m))
 
 
 @pytest.mark.gpu

@@ -146,8 +146,7 @@ def _fwd_path(path):
     workspace and the shape fits), "tiled" (what workspace-free calls and other shapes get), "naive"
     (per-element kernel: any pooled size)"""
     from simpledet_amd._lib import lib
-    lib().set_tuning("roi_align_fwd", 0 if path == "naive" else 1)
-    lib().set_tuning("roi_align_fwd_band", 0 if path == "tiled" else 1)
+    return lib().tuned(roi_align_fwd=0 if path == "naive" else 1, roi_align_fwd_band=0 if path == "tiled" else 1)
 
 
 @pytest.mark.gpu
@@ -155,8 +154,7 @@ def _fwd_path(path):
 @pytest.mark.parametrize("case", ["small", "c4", "p5", "p2", "mask14", "odd_pool"])
 def test_single_level_forward_bit_exact(ops, oracle, case, variant):
     from simpledet_amd._lib import lib
-    _fwd_path(variant)
-    try:
+    with _fwd_path(variant):
         if case == "small":
             data, rois = small_case(0, C=8)
             pooled, scale = (7, 7), 1 / 16.0
@@ -184,8 +182,6 @@ def test_single_level_forward_bit_exact(ops, oracle, case, variant):
         got = ops.roi_align_v2_forward(_t(data), _t(rois), pooled, scale)
         for g, w, name in zip(got, want, ("output", "maxidx_x", "maxidx_y")):
             np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=name)
-    finally:
-        _fwd_path("band")
 
 
 @pytest.mark.gpu
@@ -199,12 +195,9 @@ def test_c4_whole_plane_forward_equals_band_kernel_at_full_size(ops):
     from simpledet_amd._lib import lib
     data = torch.randn((2, 1024, 50, 84), device="cuda")
     rois = _t(synth.random_rois(21, 2, 512))
-    lib().set_tuning("roi_align_fwd_quad", 0)
-    try:
+    with lib().tuned(roi_align_fwd_quad=0):
         want = [t.clone() for t in ops.roi_align_v2_forward(data, rois, (7, 7), 1 / 16.0)]
         assert "fwd_band" in (lib().cdll.sd_last_dispatch() or b"").decode()
-    finally:
-        lib().set_tuning("roi_align_fwd_quad", 1)
     for _ in range(3):
         got = ops.roi_align_v2_forward(data, rois, (7, 7), 1 / 16.0)
         assert "fwd_quad" in (lib().cdll.sd_last_dispatch() or b"").decode()
@@ -218,8 +211,7 @@ def test_c4_whole_plane_forward_equals_band_kernel_at_full_size(ops):
 @pytest.mark.parametrize("case", ["small", "p2_bands", "c4", "mask14", "odd_pool"])
 def test_single_level_backward(ops, oracle, case, variant):
     from simpledet_amd._lib import lib
-    lib().set_tuning("roi_align_bwd", variant)
-    try:
+    with lib().tuned(roi_align_bwd=variant):
         if case == "small":
             data, rois = small_case(0, C=8)
             pooled, scale = (7, 7), 1 / 16.0
@@ -253,8 +245,6 @@ def test_single_level_backward(ops, oracle, case, variant):
                                   req_data="add", req_rois="null", d_data=acc)
         torch.cuda.synchronize()
         _assert_bwd_close(acc.cpu().numpy(), want + base)
-    finally:
-        lib().set_tuning("roi_align_bwd", 2)
 
 
 @pytest.mark.gpu
@@ -288,11 +278,8 @@ def test_c4_backward_fixed_point_planes(ops, oracle, case):
     args = (_t(dy), _t(rois), _t(ax), _t(ay), data.shape, 1 / 16.0)
     got = ops.roi_align_v2_backward(*args)[0]
     again = ops.roi_align_v2_backward(*args)[0]
-    lib().set_tuning("roi_align_bwd_fx", 0)
-    try:
+    with lib().tuned(roi_align_bwd_fx=0):
         flt = ops.roi_align_v2_backward(*args)[0]
-    finally:
-        lib().set_tuning("roi_align_bwd_fx", 1)
     g, f = got.cpu().numpy(), flt.cpu().numpy()
     # integer sums do not depend on the order of the adds (float adds do; round 6: a workgroup whose max|dY| is
     # beyond kFxUnitsPerMean x its mean |dY| -- the planes the 1000 x outlier lands in -- takes the float adds too)
@@ -409,9 +396,7 @@ def test_fpn_full_size_baseline_config(ops, oracle):
     assert abs(mass - want_mass) <= 1e-3 * max(1.0, abs(want_mass))
     # the naive (reference-structure) kernels agree with the tiled/LDS ones
     from simpledet_amd._lib import lib
-    lib().set_tuning("roi_align_fwd", 0)
-    lib().set_tuning("roi_align_bwd", 0)
-    try:
+    with lib().tuned(roi_align_fwd=0, roi_align_bwd=0):
         got0 = ops.fpn_roi_align_forward(tf, _t(rois), STRIDES, (7, 7))
         for a, b in zip(got, got0):
             assert torch.equal(a, b)
@@ -420,14 +405,11 @@ def test_fpn_full_size_baseline_config(ops, oracle):
         for g, w in zip(gd0, wd):
             _assert_bwd_close(g.cpu().numpy(), w)
         # ... and so do the per-level LDS-plane kernels (fixed-point accumulators)
-        lib().set_tuning("roi_align_bwd", 1)
-        gd1 = ops.fpn_roi_align_backward(_t(dy), _t(rois), got[1], got[2],
-                                         [f.shape for f in feats], STRIDES)
+        with lib().tuned(roi_align_bwd=1):
+            gd1 = ops.fpn_roi_align_backward(_t(dy), _t(rois), got[1], got[2],
+                                             [f.shape for f in feats], STRIDES)
         for g, w in zip(gd1, wd):
             _assert_bwd_close(g.cpu().numpy(), w)
-    finally:
-        lib().set_tuning("roi_align_fwd", 1)
-        lib().set_tuning("roi_align_bwd", 2)
 
 
 @pytest.mark.gpu
@@ -465,11 +447,8 @@ def test_fpn_band_forward_many_virtual_units(ops, oracle, case):
     from simpledet_amd._lib import lib
     amn = ops.argmax_codes(amp[0], (7, 7))
     np.testing.assert_array_equal(amn.cpu().numpy() == 255, want[1] == -1)
-    lib().set_tuning("roi_align_fwd", 0)
-    try:
+    with lib().tuned(roi_align_fwd=0):
         out0, am0 = ops.fpn_roi_align_forward_packed(tf, _t(rois), STRIDES, (7, 7))
-    finally:
-        lib().set_tuning("roi_align_fwd", 1)
     assert torch.equal(out0, outp) and torch.equal(ops.argmax_codes(am0[0], (7, 7)), amn)
     assert torch.equal(am0[1], amp[1])
 
@@ -524,11 +503,8 @@ def test_fpn_packed_argmax_forward_backward(ops, oracle, variant):
     want = oracle.fpn_roi_align_fwd(feats, rois, STRIDES, (7, 7))
     _, level = oracle.fpn_roi_assign(rois, STRIDES)
     tf = [_t(f) for f in feats]
-    _fwd_path(variant)
-    try:
+    with _fwd_path(variant):
         out, am = ops.fpn_roi_align_forward_packed(tf, _t(rois), STRIDES, (7, 7))
-    finally:
-        _fwd_path("band")
     np.testing.assert_array_equal(out.cpu().numpy(), want[0])
     amn, con = ops.argmax_codes(am[0], (7, 7)).cpu().numpy(), am[1].cpu().numpy()
     np.testing.assert_array_equal(amn == 255, want[1] == -1)
@@ -590,12 +566,9 @@ def test_forward_variants_agree_at_full_size(ops, variant):
     rois = _t(synth.random_rois(2, 2, 512))
     o1, am1 = ops.fpn_roi_align_forward_packed(feats, rois, STRIDES, (7, 7))
     f1 = ops.fpn_roi_align_forward(feats, rois, STRIDES, (7, 7))
-    _fwd_path(variant)
-    try:
+    with _fwd_path(variant):
         o2, am2 = ops.fpn_roi_align_forward_packed(feats, rois, STRIDES, (7, 7))
         f2 = ops.fpn_roi_align_forward(feats, rois, STRIDES, (7, 7))
-    finally:
-        _fwd_path("band")
     assert torch.equal(o1, o2)
     assert torch.equal(ops.argmax_codes(am1[0], (7, 7)), ops.argmax_codes(am2[0], (7, 7)))
     # the coordinate table has entries only for RoIs assigned to a level (the rest is never read)
@@ -692,18 +665,13 @@ def test_planned_pair_one_prepass_equals_the_unplanned_pair(ops, pooled, num, ch
     torch.manual_seed(43)
     dy = torch.randn_like(o0)
     g0 = ops.fpn_roi_align_backward_packed(dy, rois, st0, shapes, STRIDES)
-    for k, v in knobs.items():
-        lib().set_tuning(k, v)
-    try:
+    with lib().tuned(**knobs):
         o1, st1 = ops.fpn_roi_align_forward_packed(feats, rois, STRIDES, pooled, plan=True)
         assert len(st1) == 3
         g1 = ops.fpn_roi_align_backward_packed(dy, rois, st1, shapes, STRIDES)
         # the plan is op state: a second backward from the same plan (e.g. gradient accumulation)
         acc = [torch.ones_like(g) for g in g1]
         ops.fpn_roi_align_backward_packed(dy, rois, st1, shapes, STRIDES, req_data="add", d_feats=acc)
-    finally:
-        for k in knobs:
-            lib().set_tuning(k, 1)
     assert torch.equal(o1, o0)
     assert torch.equal(ops.argmax_codes(st1[0], pooled), ops.argmax_codes(st0[0], pooled))   # (rows are padded)
     lvl = ops.fpn_roi_assign(rois, STRIDES)[1].reshape(-1) >= 0
@@ -739,14 +707,9 @@ def test_packed_backward_workspace_modes(ops, oracle, pooled, num):
     # workspace modes a finer fixed-point unit than the workspace-free call (whose workgroups sum the bound over
     # the band's RoIs themselves); with the per-pixel bound off, lists-only and no workspace are the same sums
     for mode, pix in ((1, 1), (2, 1), (2, 0), (0, 1)):
-        lib().set_tuning("roi_align_bwd_lists", mode)
-        lib().set_tuning("roi_align_bwd_pixbound", pix)
-        try:
+        with lib().tuned(roi_align_bwd_lists=mode, roi_align_bwd_pixbound=pix):
             res[mode, pix] = ops.fpn_roi_align_backward_packed(dy, rois, am, shapes, STRIDES)
             again = ops.fpn_roi_align_backward_packed(dy, rois, am, shapes, STRIDES)
-        finally:
-            lib().set_tuning("roi_align_bwd_lists", 1)
-            lib().set_tuning("roi_align_bwd_pixbound", 1)
         for a, b in zip(res[mode, pix], again):
             assert torch.equal(a, b), "mode %d is not bit-reproducible" % mode
     for a, b in zip(res[2, 0], res[0, 1]):
@@ -828,12 +791,9 @@ def test_fpn_packed_forward_fp16_io(ops, oracle, pooled, num, channels):
     # where the band-resident kernel is not eligible the fp16 op still works
     # (cast -> fp32 op -> cast instead of SD_ERR_UNSUPPORTED), with the same bits
     from simpledet_amd._lib import lib
-    lib().set_tuning("roi_align_fwd_band", 0)
-    try:
+    with lib().tuned(roi_align_fwd_band=0):
         out_fb, (am_fb, _) = ops.fpn_roi_align_forward_packed_f16([_t(f) for f in feats16], _t(rois),
                                                                   STRIDES, pooled)
-    finally:
-        lib().set_tuning("roi_align_fwd_band", 1)
     assert torch.equal(out_fb, out)
     assert torch.equal(ops.argmax_codes(am_fb, pooled), ops.argmax_codes(am, pooled))
 

@@ -242,12 +242,9 @@ def _check_forward(ops, oracle, name, kind):
     with np.errstate(all="ignore"):
         E.assert_same_half_bits(_half(out), o32.cpu().numpy().astype(F16), "fp16 entry against the fp32 entry")
     # where the band-resident kernel is switched off: cast -> fp32 op -> cast, the same bits (both casts at odd n)
-    lib().set_tuning("roi_align_fwd_band", 0)
-    try:
+    with lib().tuned(roi_align_fwd_band=0):
         out_fb, (am_fb, _) = ops.fpn_roi_align_forward_packed_f16(tf16, tr, STRIDES, pooled)
         ran_fb = _dispatch()
-    finally:
-        lib().set_tuning("roi_align_fwd_band", 1)
     assert "true,true" not in ran_fb, ran_fb
     E.assert_same_half_bits(_half(out_fb), ref["out16"], "%s %s: cast fallback against the oracle" % (name, kind))
     E.assert_same_half_bits(_half(out_fb), _half(out), "cast fallback against the fp16 kernel")

@@ -241,11 +241,8 @@ def main():
     for key, fn in (("target", target), ("loss_fwd_bwd", fwd_bwd), ("chain", chain)):
         res[key] = both_ways(fn, args.iters, nsets)
     # the other way to resolve the front of the permutations: all swaps replayed on an LDS array, one lane per list
-    _lib.lib().set_tuning("crowdhuman_front", 1)
-    try:
+    with _lib.lib().tuned(crowdhuman_front=1):
         res["target_front_lds_replay"] = both_ways(target, args.iters, nsets)
-    finally:
-        _lib.lib().set_tuning("crowdhuman_front", 0)
     # the host algorithm of the reference (cannot be captured: it synchronises by construction)
     res["host_reference"] = dict(target_us=round(time_host(lambda i: host_targets(sets[i][0], sets[i][1], CFG),
                                                            max(5, args.iters // 5), nsets), 1))

@@ -13,10 +13,8 @@ for _ in range(3): ops.deform_conv_forward(x, off, wt, 1, 1, 1, 4)
 nblk = 768
 dbg = torch.zeros(nblk * 8 * 4, dtype=torch.int64, device="cuda")
 p = dbg.data_ptr(); lo = p & 0xffffffff
-lib().set_tuning("roi_align_dbg_lo", lo - (1 << 32) if lo & 0x80000000 else lo)
-lib().set_tuning("roi_align_dbg_hi", p >> 32)
-ops.deform_conv_forward(x, off, wt, 1, 1, 1, 4); torch.cuda.synchronize()
-lib().set_tuning("roi_align_dbg_lo", 0); lib().set_tuning("roi_align_dbg_hi", 0)
+with lib().tuned(roi_align_dbg_lo=lo - (1 << 32) if lo & 0x80000000 else lo, roi_align_dbg_hi=p >> 32):
+    ops.deform_conv_forward(x, off, wt, 1, 1, 1, 4); torch.cuda.synchronize()
 d = dbg.cpu().numpy().reshape(nblk, 8, 4)
 d = d[d[:, 0, 0] > 0]
 print("blocks", d.shape[0], "(100 MHz counter ticks: x24 = core clocks)")

@@ -22,12 +22,9 @@ nblk = 256
 dbg = torch.zeros(nblk * 16 * 8 + nblk * 4 * 8, dtype=torch.int64, device="cuda")
 p = dbg.data_ptr()
 lo = p & 0xffffffff
-lib().set_tuning("roi_align_dbg_lo", lo - (1 << 32) if lo & 0x80000000 else lo)
-lib().set_tuning("roi_align_dbg_hi", p >> 32)
-ops.fpn_roi_align_forward_packed(feats, rois, strides, (7, 7))
-torch.cuda.synchronize()
-lib().set_tuning("roi_align_dbg_lo", 0)
-lib().set_tuning("roi_align_dbg_hi", 0)
+with lib().tuned(roi_align_dbg_lo=lo - (1 << 32) if lo & 0x80000000 else lo, roi_align_dbg_hi=p >> 32):
+    ops.fpn_roi_align_forward_packed(feats, rois, strides, (7, 7))
+    torch.cuda.synchronize()
 raw = dbg.cpu().numpy()
 d = raw[:nblk * 16 * 8].reshape(nblk, 16, 8)
 used = d[:, :, 4].max(1) > 0

@@ -34,13 +34,9 @@ for name, fn in cases:
     dbg = torch.zeros(cap * 8, dtype=torch.int64, device="cuda")
     p = dbg.data_ptr()
     lo = p & 0xffffffff
-    lib().set_tuning("roi_align_dbg_lo", lo - (1 << 32) if lo & 0x80000000 else lo)
-    lib().set_tuning("roi_align_dbg_hi", p >> 32)
-    lib().set_tuning("gemm_dbg_cap", cap)
-    fn()
-    torch.cuda.synchronize()
-    lib().set_tuning("roi_align_dbg_lo", 0)
-    lib().set_tuning("roi_align_dbg_hi", 0)
+    with lib().tuned(roi_align_dbg_lo=lo - (1 << 32) if lo & 0x80000000 else lo, roi_align_dbg_hi=p >> 32, gemm_dbg_cap=cap):
+        fn()
+        torch.cuda.synchronize()
     d = dbg.cpu().numpy().reshape(cap, 8)
     full = d
     d = d[d[:, 4] > 0]

@@ -1,5 +1,7 @@
 #!/usr/bin/env python
-"""Run pytest with kernel-variant knobs set first: tools/pytest_tuned.py key=value [key=value ...] -- <pytest args>"""
+"""Run pytest with kernel-variant knobs set first: tools/pytest_tuned.py key=value [key=value ...] -- <pytest args>
+The tests' `tuned()` blocks return to these values, not to the defaults, so the setting holds for the whole session;
+tests/test_zz_knobs_restored.py compares against the defaults and fails under it by design (--deselect it)."""
 import sys
 
 import pytest

@@ -284,11 +284,8 @@ def main():
             e["composition_ratio"] = {k: {m: round(e["composition_" + k][m] / e["fused_" + k][m], 2)
                                           for m in ("eager_us", "graph_us")} for k in ("fwd", "bwd", "fwd_bwd")}
             # the alternative inside the same kernel: no LDS patch, one global atomic per tap
-            lib().set_tuning("deform_psroi_bwd_patch", 0)
-            try:
+            with lib().tuned(deform_psroi_bwd_patch=0):
                 e["direct_bwd"] = both_ways(lambda i: bwd(0, forms), args.iters)
-            finally:
-                lib().set_tuning("deform_psroi_bwd_patch", 1)
             # where the backward's time goes: each of its two outputs alone (the other's req is null)
             e["fused_bwd_d_data_only"] = both_ways(lambda i: bwd_part(0, forms, "write", "null"), args.iters)
             e["fused_bwd_d_trans_only"] = both_ways(lambda i: bwd_part(0, forms, "null", "write"), args.iters)
