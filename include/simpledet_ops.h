@@ -69,7 +69,8 @@ const char* sd_last_dispatch(void);
  * sd_msrcnn_mask_loss_* / sd_maskiou_loss_* (the Mask Scoring R-CNN training head), and sd_reppoints_decode (the
  * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head),
  * and sd_scale_bias_act_* (the merged-BN affine and _contrib_BroadcastScale), and sd_rpn_loss_* / sd_rcnn_loss_*
- * (the Faster / Mask R-CNN loss heads), and sd_fpn_topdown_* (the FPN top-down pathway).
+ * (the Faster / Mask R-CNN loss heads), and sd_fpn_topdown_* (the FPN top-down pathway), and sd_free_anchor_* (the
+ * FreeAnchor training head).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -1622,6 +1623,58 @@ int sd_fpn_topdown_fwd_f16(const void* top, const void* const* lateral, void* co
                            const int* ws, int L, void* stream);
 int sd_fpn_topdown_bwd_f16(const void* const* g, void* d_top, void* const* d_lateral, int N, int C, const int* hs,
                            const int* ws, int L, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The FreeAnchor training head (config/FreeAnchor/free_anchor_r50v1_fpn_1x.py and r101), fp32:
+ *   FreeAnchorRetinaNetHead.get_loss (models/FreeAnchor/builder.py:67-148) with _prepare_anchors, _positive_loss and
+ *   _negative_loss (models/FreeAnchor/ops.py:44-210).  Additions only: the ABI version stays 12 (tests pin it).
+ *   DESIGN 4.26 is the specification.
+ *   Inputs, read in place: three HOST tables of L <= SD_MAX_FPN_LEVELS device pointers (read during the call only) --
+ *     cls_logit[l] (N, A*K, H_l, W_l), bbox_delta[l] (N, A*4, H_l, W_l), anchor[l] (1, 1, S_l, S_l, A*4) as the
+ *     loader makes it -- with hw_host[l] = H_l * W_l, w_host[l] = W_l and anchor_pitch_host[l] = S_l >= W_l (the
+ *     row pitch in locations: slice_like without a copy).  Anchor i = (off_l + y * W_l + x) * A + a, off_l the
+ *     locations of the levels in front; its class c is channel a * K + c, its delta j channel a * 4 + j.
+ *     gt_bbox (N, M, 5) = x1, y1, x2, y2, label (a row counts when label > 0); im_info (N, 3) = h, w, scale.
+ *   loss[0] = positive_loss, loss[1] = negative_loss, term by term as ops.py:67-210 with
+ *     box_iou      corner format, no +1, extents clamped at 0, 0 where the union is <= 0;
+ *     decode_bbox  decodebbox.cc's class-agnostic xyxy form as sd_decode_bbox(decode_xyxy = 1) computes it: means /
+ *                  stds, +1 widths, the clip to im_info;
+ *     topk         descending IoU, the lower anchor index first among equal IoUs.
+ *     The arg-max over the gt rows takes the first maximum, padding rows included: where every entry is 0, row 0
+ *     wins, and the anchor counts only if row 0's label is > 0 (the reference's behaviour).  A label above K hits
+ *     no class in the negative part and reads class K - 1 in the positive part (the reference gathers out of bounds).
+ *   bags (N, M, top_n) int32, may be NULL: the anchor indices of each gt's bag in rank order, -1 in the rows of
+ *     gts that do not count.
+ *   Gradients (sd_free_anchor_loss_bwd, after a forward on the same inputs and workspace): both outputs are loss
+ *     heads, no top gradient; d_cls_logit[l] and d_bbox_delta[l] get every element written (kWriteTo) with
+ *     grad_scale * d(positive_loss + negative_loss).  MXNet's conventions at kinks: clip passes the gradient on the
+ *     closed interval, maximum to its left operand when it is >=; the mean-max weights are differentiated, box_prob
+ *     is a constant.
+ *   The workspace (sd_free_anchor_workspace_bytes; 8 bytes per anchor and image, 24 per bag entry) carries the
+ *     forward's bags, per-anchor records and gradient coefficients to the backward; it needs no clearing.  Integer
+ *     atomics only, no memset, no host read, graph-capturable; two calls give equal bits.  Pointers need element
+ *     alignment only (anchors are read with 16-byte loads where all their tables are 16-byte aligned).
+ *   SD_ERR_INVALID_ARG: L outside 1..8, N < 0, A / K / M / top_n < 1, an empty level, H_l * W_l no multiple of W_l,
+ *   a pitch below W_l, top_n above the anchor count, std 0, a null table or pointer; SD_ERR_UNSUPPORTED: M > 256,
+ *   top_n > 512, M * top_n > 16384, more than 2^31 - 1 elements; SD_ERR_WORKSPACE: a NULL or too small workspace.
+ *   N = 0 succeeds without a launch.  With M * top_n > 8192 the backward needs more than 64 KB of dynamic LDS: the
+ *   first such call of a process raises its kernel's limit (hipFuncSetAttribute); make that call outside a stream
+ *   capture -- the attribute call has not been exercised inside one.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_free_anchor_workspace_bytes(int N, int L, const long* hw_host, int A, int K, int M, int top_n);
+int sd_free_anchor_loss_fwd(const float* const* cls_ptrs_host, const float* const* delta_ptrs_host,
+                            const float* const* anchor_ptrs_host, const long* anchor_pitch_host,
+                            const float* gt_bbox, const float* im_info, int N, int L, const long* hw_host,
+                            const long* w_host, int A, int K, int M, int top_n, float bbox_thr, float alpha,
+                            float gamma, const float* mean_host, const float* std_host, float* loss, int32_t* bags,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int sd_free_anchor_loss_bwd(const float* const* cls_ptrs_host, const float* const* delta_ptrs_host,
+                            const float* const* anchor_ptrs_host, const long* anchor_pitch_host,
+                            const float* gt_bbox, const float* im_info, int N, int L, const long* hw_host,
+                            const long* w_host, int A, int K, int M, int top_n, float bbox_thr, float alpha,
+                            float gamma, const float* mean_host, const float* std_host, void* workspace,
+                            size_t workspace_bytes, float grad_scale, float* const* dcls_ptrs_host,
+                            float* const* ddelta_ptrs_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@
 // filter: one wave per (image, class) problem compacts the rows with score > min_det_score in row
 // order (ballot + prefix popcount) straight into the (P, Nmax, 5) layout sd_soft_nms_batched reads,
 // so bbox head output -> decode -> filter -> soft-NMS never leaves the device.
+#include "box_common.h"
 #include "common.h"
 #include "wg_common.h"
 #include "../../include/simpledet_ops.h"
@@ -33,32 +34,8 @@ __global__ __launch_bounds__(256) void decode_bbox_kernel(DecodeArgs a) {
     const float4 b = reinterpret_cast<const float4*>(a.rois)[nr];
     const int decode_cls = a.class_agnostic ? 1 : cls;
     const float4 d = *reinterpret_cast<const float4*>(a.deltas + nr * 4 * a.K + decode_cls * 4);
-    const float width = b.z - b.x + 1.0f, height = b.w - b.y + 1.0f;
-    float px1, py1, px2, py2;
-    if (!a.xyxy) {
-      const float ctr_x = b.x + 0.5f * (width - 1.0f), ctr_y = b.y + 0.5f * (height - 1.0f);
-      const float dx = d.x * a.stds[0] + a.means[0], dy = d.y * a.stds[1] + a.means[1];
-      const float dw = d.z * a.stds[2] + a.means[2], dh = d.w * a.stds[3] + a.means[3];
-      const float pred_ctr_x = dx * width + ctr_x, pred_ctr_y = dy * height + ctr_y;
-      const float pred_w = (float)(exp((double)dw) * (double)width);
-      const float pred_h = (float)(exp((double)dh) * (double)height);
-      px1 = pred_ctr_x - 0.5f * (pred_w - 1.0f);
-      py1 = pred_ctr_y - 0.5f * (pred_h - 1.0f);
-      px2 = pred_ctr_x + 0.5f * (pred_w - 1.0f);
-      py2 = pred_ctr_y + 0.5f * (pred_h - 1.0f);
-    } else {
-      px1 = b.x + (d.x * a.stds[0] + a.means[0]) * width;
-      py1 = b.y + (d.y * a.stds[1] + a.means[1]) * height;
-      px2 = b.z + (d.z * a.stds[2] + a.means[2]) * width;
-      py2 = b.w + (d.w * a.stds[3] + a.means[3]) * height;
-    }
     const float wm = a.im_info[n * 3 + 1] - 1.0f, hm = a.im_info[n * 3 + 0] - 1.0f;
-    // std::max(std::min(x, m), 0)
-    float4 o;
-    o.x = fmaxr(fminr(px1, wm), 0.0f);
-    o.y = fmaxr(fminr(py1, hm), 0.0f);
-    o.z = fmaxr(fminr(px2, wm), 0.0f);
-    o.w = fmaxr(fminr(py2, hm), 0.0f);
+    const float4 o = decode_box(b, d, a.means, a.stds, a.xyxy != 0, wm, hm);
     reinterpret_cast<float4*>(a.out)[i] = o;
   }
 }

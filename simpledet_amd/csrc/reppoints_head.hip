@@ -26,6 +26,7 @@
 // No float atomics, no memset node, no host read: every call is graph-capturable and repeatable bit for bit.  The
 // arithmetic is the reference's float32 expressions one operation at a time (-ffp-contract=off, correctly rounded
 // divide / sqrt); the sums over the points of a set run sequentially in point order.
+#include "box_common.h"
 #include "reppoints_common.h"
 #include "loss_common.h"
 #include "wg_common.h"
@@ -69,17 +70,7 @@ __device__ __forceinline__ void rp_load(const float* base, int hw, float* y, flo
 
 // rp_moment and rp_points2bbox (_points2bbox, point_ops.py:219-274): reppoints_common.h, shared with the decode
 
-// upstream box_iou, corner format (no +1): extents clamped at 0, 0 where the union is <= 0
-__device__ __forceinline__ float rp_iou(const float* a, const float* g) {
-  const float l = fmaxr(a[0], g[0]), t = fmaxr(a[1], g[1]), r = fminr(a[2], g[2]), b = fminr(a[3], g[3]);
-  float w = r - l, h = b - t;
-  w = w < 0.f ? 0.f : w;
-  h = h < 0.f ? 0.f : h;
-  const float i = w * h;
-  const float u = ((a[2] - a[0]) * (a[3] - a[1]) + (g[2] - g[0]) * (g[3] - g[1])) - i;
-  return u <= 0.f ? 0.f : i / u;
-}
-
+// upstream box_iou, corner format: box_iou_corner (box_common.h), shared with the FreeAnchor head
 // ---------------------------------------------------------------------------------------- targets --
 struct RpTargetArgs {
   const float* pts[kRpMaxL];
@@ -172,7 +163,7 @@ __global__ __launch_bounds__(kRpT) void rp_box_kernel(RpTargetArgs a) {
     o[0] = box[0]; o[1] = box[1]; o[2] = box[2]; o[3] = box[3];
   }
   for (int m = 0; m < a.M; ++m) {
-    const float v = rp_iou(box, sgt + m * 5);
+    const float v = box_iou_corner(box, sgt + m * 5);
     const unsigned wm = wave_max_u32(live ? __float_as_uint(v) : 0u);
     if ((threadIdx.x & (kWave - 1)) == 0 && wm) atomicMax(smax + m, wm);
   }
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(kRpT) void rp_assign_kernel(RpTargetArgs a) {
     int arg = 0;
     bool maxfg = false;
     for (int m = 0; m < a.M; ++m) {
-      const float v = rp_iou(box, sgt + m * 5);
+      const float v = box_iou_corner(box, sgt + m * 5);
       if (m == 0 || v > best) { best = v; arg = m; }   // the first arg-max, padding rows included
       if (v == scol[m] && scol[m] > a.min_pos) maxfg = true;
     }
