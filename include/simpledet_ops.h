@@ -70,7 +70,8 @@ const char* sd_last_dispatch(void);
  * RepPoints test-time decode), and sd_crowdhuman_target / sd_emd_loss_* (the CrowdHuman double-prediction head),
  * and sd_scale_bias_act_* (the merged-BN affine and _contrib_BroadcastScale), and sd_rpn_loss_* / sd_rcnn_loss_*
  * (the Faster / Mask R-CNN loss heads), and sd_fpn_topdown_* (the FPN top-down pathway), and sd_free_anchor_* (the
- * FreeAnchor training head).
+ * FreeAnchor training head), and sd_deform_convolution_fwd_f16 / _bwd_f16 with their workspace queries
+ * (DeformableConvolution on halves).
  * sd_abi_version() returns the library's value; compare with this macro. */
 #define SD_ABI_VERSION 12
 int sd_abi_version(void);
@@ -659,6 +660,30 @@ int sd_deform_convolution_bwd(const float* out_grad, const float* x, const float
                               int req_x, int req_offset, int req_weight, int req_bias, int N, int C, int H,
                               int W, int F, int kh, int kw, int pad, int stride, int dil, int dgroup,
                               int num_group, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The operator on halves (the reference's fp16 graphs: the config/sepc configs, the fp16 TridentNet configs): x, offset,
+ * weight, bias, y and every gradient are fp16, pointers aligned to 2 bytes.
+ * forward: 3x3 kernels with num_group = 1 and C / dgroup % 16 == 0 (any stride, dilation, pad, H, W) run a col-free
+ *   kernel on native-half matrix-core operands: offsets and corners widened to fp32, sd_deform_im2col's bilinear
+ *   expression, the sample rounded once to fp16 (as upstream's half col is), the fp16 weights untouched, products on
+ *   single-term v_mfma_f32_32x32x16_f16 into fp32, the bias added in fp32, one rounding to fp16.  Against fp64 on the
+ *   widened inputs: |y - y64| <= (2^-11 + (K + 16) 2^-24) sum_k |w_k col_k| + 2^-11 |y64| + 2^-25, K = 9 C.  There is
+ *   no col matrix, hence no keep_col.  Every other shape widens into the workspace, runs sd_deform_convolution_fwd
+ *   (keep_col = 0) and rounds y once: bit-equal to that composition.
+ * backward: sd_deform_convolution_bwd on widened operands (fwd_col = NULL), each requested gradient rounded once;
+ *   req = add widens the destination, adds and rounds once.  Bit-equal to cast -> fp32 backward -> cast. */
+size_t sd_deform_convolution_fwd_workspace_bytes_f16(int N, int C, int H, int W, int F, int kh, int kw, int pad,
+                                                     int stride, int dil, int dgroup, int num_group);
+int sd_deform_convolution_fwd_f16(const void* x, const void* offset, const void* weight, const void* bias, void* y,
+                                  int N, int C, int H, int W, int F, int kh, int kw, int pad, int stride, int dil,
+                                  int dgroup, int num_group, void* workspace, size_t workspace_bytes, void* stream);
+size_t sd_deform_convolution_bwd_workspace_bytes_f16(int N, int C, int H, int W, int F, int kh, int kw, int pad,
+                                                     int stride, int dil, int dgroup, int num_group);
+int sd_deform_convolution_bwd_f16(const void* out_grad, const void* x, const void* offset, const void* weight,
+                                  void* d_x, void* d_offset, void* d_weight, void* d_bias, int req_x, int req_offset,
+                                  int req_weight, int req_bias, int N, int C, int H, int W, int F, int kh, int kw,
+                                  int pad, int stride, int dil, int dgroup, int num_group, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_Proposal_v3  (mx.sym.contrib.Proposal_v3, models/FPN/builder.py:275-287) -- SURVEY 8(f)

@@ -1,0 +1,195 @@
+"""DeformableConvolution on float16 tensors (the reference's fp16 graphs: the `config/sepc` RetinaNet configs build
+`models/sepc/sepc_dconv.py:12-16` on half pyramid levels, the fp16 TridentNet configs the dilated deformable blocks
+of `models/tridentnet/resnet_v*.py:85-90`).
+
+    deform_conv_forward / deform_conv_backward   the `ops` functions of the same names for float16 tensors (float32
+                                                 tensors go to `ops` unchanged)
+    deform_conv                                  an autograd function over both
+    install(mx)                                  after mxnet_plugin.install(mx): `mx.sym.contrib.DeformableConvolution`
+                                                 builds a prop whose infer_type passes float16 through and whose
+                                                 operator picks the entry points by the dtype of its data
+
+Forward, 3x3 kernels with num_group = 1 and C / num_deformable_group % 16 == 0: the col-free kernel of
+csrc/deform_fused_f16.hip -- fp32 sampling rounded once to fp16, fp16 weights untouched, single-term
+fp16 matrix-core products into fp32, one final rounding.  Every other shape, and the backward: the float32 operator
+on widened operands, each result rounded once (bit-equal to cast -> float32 call -> cast).
+
+It stays out of `ops.py` and of mxnet_plugin's tables, like sync_bn.py and free_anchor.py: their public surfaces are
+pinned."""
+import torch
+
+from . import ops
+from ._mx_adapter import REQ, _call, _mx, _no_add, _ptr, _req, _sync, _wait, _ws, alias_ctor, drop_alias, put_alias, \
+    register_ops
+from .ops import _chk, _dcn_out_hw, _req_of
+
+F16_OP = "_contrib_DeformableConvolution_f16"
+_own = {"installed": False, "props": {}}
+fallbacks = []
+
+
+def _geom(x, offset, weight, pad, stride, dilate, num_deformable_group, num_group, bias=None):
+    for t, name in ((x, "data"), (offset, "offset"), (weight, "weight")):
+        _chk(t, name, torch.float16, ndim=4)
+    N, C, H, W = x.shape
+    F, Cw, kh, kw = weight.shape
+    num_group, dg = int(num_group), int(num_deformable_group)
+    if num_group < 1 or C % num_group or F % num_group:
+        raise ValueError("num_group %d must divide data channels %d and num_filter %d" % (num_group, C, F))
+    if Cw * num_group != C:
+        raise ValueError("weight channels %d != data channels %d / num_group %d" % (Cw, C, num_group))
+    if bias is not None:
+        _chk(bias, "bias", torch.float16, shape=(F,))
+    Ho, Wo = _dcn_out_hw(H, W, kh, kw, pad, stride, dilate)
+    if tuple(offset.shape) != (N, dg * 2 * kh * kw, Ho, Wo):
+        raise ValueError("offset shape %s != %s" % (tuple(offset.shape), (N, dg * 2 * kh * kw, Ho, Wo)))
+    return (N, C, H, W, F, kh, kw, int(pad), int(stride), int(dilate), dg, num_group), (Ho, Wo)
+
+
+def deform_conv_forward(x, offset, weight, pad=1, stride=1, dilate=1, num_deformable_group=1, keep_col=False,
+                        bias=None, num_group=1, out=None):
+    """ops.deform_conv_forward for float16 tensors: y (N,F,Ho,Wo) float16.  There is no col matrix to keep:
+    keep_col=True is refused for float16.  float32 tensors are handed to ops.deform_conv_forward (which takes no
+    out=: refused there)."""
+    if x.dtype == torch.float32:
+        if out is not None:
+            raise ValueError("out= is for float16 tensors; ops.deform_conv_forward allocates its float32 result")
+        return ops.deform_conv_forward(x, offset, weight, pad, stride, dilate, num_deformable_group, keep_col, bias,
+                                       num_group)
+    if keep_col:
+        raise ValueError("the float16 forward has no col matrix to keep")
+    dims, (Ho, Wo) = _geom(x, offset, weight, pad, stride, dilate, num_deformable_group, num_group, bias)
+    y = ops._out(out, "out", (dims[0], dims[4], Ho, Wo), x.device, torch.float16)
+    ws = ops._ws(x.device, None, "sd_deform_convolution_fwd_workspace_bytes_f16", *dims)
+    ops._call("sd_deform_convolution_fwd_f16", x, offset, weight, bias, y, *dims, ws, ws.numel())
+    return y
+
+
+def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1, num_deformable_group=1,
+                         req=("write", "write", "write"), grads=None, fwd_ws=None, num_group=1, bias=False):
+    """ops.deform_conv_backward for float16 tensors -> (d_data, d_offset, d_weight[, d_bias]), float16: the float32
+    backward on widened operands, every gradient rounded once (req "add": onto the widened destination)."""
+    if x.dtype == torch.float32:
+        return ops.deform_conv_backward(out_grad, x, offset, weight, pad, stride, dilate, num_deformable_group, req,
+                                        grads, fwd_ws, num_group, bias)
+    dims, (Ho, Wo) = _geom(x, offset, weight, pad, stride, dilate, num_deformable_group, num_group)
+    _chk(out_grad, "out_grad", torch.float16, shape=(dims[0], dims[4], Ho, Wo))
+    r = [_req_of(v) for v in req]
+    if bias and len(r) == 3:
+        r.append(REQ["write"])
+    if grads is None:
+        grads = (torch.empty_like(x), torch.empty_like(offset), torch.empty_like(weight))
+        if bias:
+            grads = grads + (torch.empty(dims[4], device=x.device, dtype=torch.float16),)
+    elif len(grads) != (4 if bias else 3):
+        raise ValueError("grads must hold %d tensors, got %d" % (4 if bias else 3, len(grads)))
+    for t, like in zip(grads, (x, offset, weight)):
+        _chk(t, "gradient", torch.float16, shape=like.shape)
+    ws = ops._ws(x.device, None, "sd_deform_convolution_bwd_workspace_bytes_f16", *dims)
+    ops._call("sd_deform_convolution_bwd_f16", out_grad, x, offset, weight, grads[0], grads[1], grads[2],
+              grads[3] if bias else None, r[0], r[1], r[2], r[3] if bias else REQ["null"], *dims, ws, ws.numel())
+    return grads
+
+
+class _DeformConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offset, weight, bias, pad, stride, dilate, dg, num_group):
+        ctx.save_for_backward(x, offset, weight)
+        ctx.geom, ctx.has_bias = (pad, stride, dilate, dg), bias is not None
+        ctx.num_group = num_group
+        return deform_conv_forward(x, offset, weight, pad, stride, dilate, dg, False, bias, num_group)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, offset, weight = ctx.saved_tensors
+        g = deform_conv_backward(dy.contiguous(), x, offset, weight, *ctx.geom, num_group=ctx.num_group,
+                                 bias=ctx.has_bias)
+        return g[0], g[1], g[2], (g[3] if ctx.has_bias else None), None, None, None, None, None
+
+
+def deform_conv(x, offset, weight, bias=None, pad=1, stride=1, dilate=1, num_deformable_group=1, num_group=1):
+    """differentiable DeformableConvolution on float16 or float32 tensors"""
+    return _DeformConv.apply(x, offset, weight, bias, pad, stride, dilate, num_deformable_group, num_group)
+
+
+# ----------------------------------------------------------------------------------- MXNet adapter ----
+def _is_half(nd):
+    """an NDArray's dtype is a numpy type; the test stub's arrays wrap torch tensors"""
+    d = getattr(nd, "dtype", None)
+    return "float16" in str(d if d is not None else nd.t.dtype)
+
+
+def _build_ops(mx):
+    from .mxnet_plugin import _deform_conv_ops
+    base = _deform_conv_ops(mx)["_contrib_DeformableConvolution"][0]
+
+    class DeformConvF16(base.OP):
+        """half data: the `_f16` entry points; float data: the adapter's operator as it is (cache_col included)"""
+
+        def _dims(self, x):
+            g = self.g
+            return tuple(x.shape) + (g["F"], g["kh"], g["kw"], g["pad"], g["stride"], g["dil"], g["dg"], g["G"])
+
+        def forward(self, is_train, req, in_data, out_data, aux):
+            if not _is_half(in_data[0]):
+                return super().forward(is_train, req, in_data, out_data, aux)
+            _no_add(req)
+            _wait(*in_data)
+            x, off, w = in_data[:3]
+            b = in_data[3] if self.g["bias"] else None
+            dims = self._dims(x)
+            ws, wsp, wsn = _ws(x, "sd_deform_convolution_fwd_workspace_bytes_f16", *dims)
+            _call("sd_deform_convolution_fwd_f16", _ptr(x), _ptr(off), _ptr(w), _ptr(b), _ptr(out_data[0]), *dims,
+                  wsp, wsn, None)
+            _sync()
+
+        def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
+            if not _is_half(in_data[0]):
+                return super().backward(req, out_grad, in_data, out_data, in_grad, aux)
+            _wait(out_grad[0], *in_data)
+            x, off, w = in_data[:3]
+            has_b = self.g["bias"]
+            dims = self._dims(x)
+            ws, wsp, wsn = _ws(x, "sd_deform_convolution_bwd_workspace_bytes_f16", *dims)
+            _call("sd_deform_convolution_bwd_f16", _ptr(out_grad[0]), _ptr(x), _ptr(off), _ptr(w), _ptr(in_grad[0]),
+                  _ptr(in_grad[1]), _ptr(in_grad[2]), _ptr(in_grad[3]) if has_b else None, _req(req[0]), _req(req[1]),
+                  _req(req[2]), _req(req[3]) if has_b else REQ["null"], *dims, wsp, wsn, None)
+            _sync()
+
+    class DeformConvF16Prop(base):
+        OP = DeformConvF16
+
+        def infer_type(self, in_type):
+            """every input and the output take the data's type: float16 passes through, as float32 does"""
+            n = len(self.list_arguments())
+            return [in_type[0]] * n, [in_type[0]], []
+
+    return {F16_OP: DeformConvF16Prop}
+
+
+def register(mx=None):
+    """Register `sd__contrib_DeformableConvolution_f16`.  Returns {name: PropClass}."""
+    mx = _mx(mx)
+    return register_ops(mx, _build_ops(mx), _own)
+
+
+def install(mx=None):
+    """After mxnet_plugin.install(mx): register() + point the `DeformableConvolution` alias of every contrib
+    namespace at the dtype-dispatching operator.  The constructor the plugin's alias replaced stays the fallback for
+    parameter sets `sd_supports` (unchanged) does not take; stream and sync are the plugin's."""
+    mx = _mx(mx)
+    props = register(mx)
+    del fallbacks[:]
+    put_alias(mx, "contrib", "DeformableConvolution",
+              lambda original: alias_ctor(mx, F16_OP, props[F16_OP], original,
+                                          lambda *fallback: fallbacks.append(fallback),
+                                          label="DeformableConvolution", native_drop=("cache_col",)))
+    _own["installed"] = True
+    return props
+
+
+def uninstall(mx=None):
+    """Put back the constructor `DeformableConvolution` had before any alias (mxnet_plugin.install(mx) re-creates
+    the plugin's own)."""
+    drop_alias(_mx(mx), "contrib", "DeformableConvolution")
+    _own["installed"] = False

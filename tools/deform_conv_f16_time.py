@@ -1,0 +1,179 @@
+#!/usr/bin/env python
+"""Timing of DeformableConvolution on float16 tensors (simpledet_amd/csrc/deform_fused_f16.hip).
+
+Forward, per shape, in one run, the variants alternating pass by pass, each pass over a rotation of input sets (so
+no call finds its inputs in L2 from the one before):
+  f16          sd_deform_convolution_fwd_f16 (the col-free kernel on native-half matrix-core operands), eagerly and
+               as ONE captured HIP graph
+  composition  what a half graph had to do before: cast x / offset / weight (/ bias) to float32, the fused float32
+               forward (keep_col = 0), cast y to float16; eagerly only: the float32 forward clears its operand maxima
+               with hipMemsetAsync, and this project's captured graphs are kept to kernel nodes (its graph tests
+               replay kernel-only graphs), so no memset node is recorded here.  `forward_speedup` is eager over eager.
+Backward: sd_deform_convolution_bwd_f16 (casts + the float32 backward + casts) against the float32 backward alone,
+eagerly, for the same reason (the float32 backward clears d_weight and its maxima with hipMemsetAsync).
+
+Shapes: the README's DCN row (16, 256, 50, 84) dg 4 -> 256, and the sepc neck's (2, 256, 100, 168) and
+(2, 256, 50, 84) at stride 1 and 2, dg 1, with a bias.  Every shape at the two offset spreads bench_ops.py's DCN row
+reports: offsets ~ N(0, 2^2) (its headline) and N(0, 0.5^2) (its trained-layer case).  The spread decides how many
+(tile, group) windows fit the LDS buffers; `window_fit` is that fraction, computed on the host from the offsets the
+way the kernel does (one contiguous position range per tile and deformable group, against its capacity).
+Bytes: x + offset + weight + bias + y once, in halves.  fp16 MFMA fraction: 2 N F Ho Wo 9 C flop over the time over
+2.5e15 flop/s (dense fp16 matrix-core peak of the MI355X).
+
+    python tools/deform_conv_f16_time.py [--iters 20] [--out profiles/deform_conv_f16_time.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from simpledet_amd import deform_conv_f16 as d16, ops  # noqa: E402
+
+PEAK_F16 = 2.5e15
+SETS = 4
+SIGMAS = (2.0, 0.5)
+TILE, MAX_WINDOW, NUM_CU = 64, 1536, 256   # kHN, kHMaxW of csrc/deform_fused_f16.hip
+# name: (N, C, H, W, F, dg, stride, bias)
+SHAPES = dict(readme_dcn=(16, 256, 50, 84, 256, 4, 1, False),
+              sepc_100x168_s1=(2, 256, 100, 168, 256, 1, 1, True), sepc_100x168_s2=(2, 256, 100, 168, 256, 1, 2, True),
+              sepc_50x84_s1=(2, 256, 50, 84, 256, 1, 1, True), sepc_50x84_s2=(2, 256, 50, 84, 256, 1, 2, True))
+
+
+def inputs(shape, seed, sigma):
+    N, C, H, W, F, dg, stride, bias = shape
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+    r = lambda *s: torch.randn(s, device="cuda", generator=gen)   # noqa: E731
+    return (r(N, C, H, W).half(), (r(N, 18 * dg, Ho, Wo) * sigma).half(), (r(F, C, 3, 3) * 0.05).half(),
+            r(F).half() if bias else None)
+
+
+def window_fit(off, shape):
+    """fraction of (image, tile, group) windows of at most MAX_WINDOW positions: the host's tile rule and the kernel's
+    window rule of csrc/deform_fused_f16.hip, on the real offsets"""
+    N, C, H, W, F, dg, stride, _ = shape
+    Ho, Wo = off.shape[2:]
+    P = Ho * Wo
+    T = -(-P // TILE)
+    rounds = -(-N * T // NUM_CU)
+    T = max(T, min(rounds * NUM_CU // N, P))
+    tile_w = -(-P // T)
+    o = off.float().reshape(N, dg, 9, 2, P)
+    p = torch.arange(P, device=off.device)
+    tap = torch.arange(9, device=off.device).reshape(1, 1, 9, 1)
+    h = (p // Wo * stride - 1).reshape(1, 1, 1, P) + tap // 3 + o[:, :, :, 0]
+    w = (p % Wo * stride - 1).reshape(1, 1, 1, P) + tap % 3 + o[:, :, :, 1]
+    ok = (h >= 0) & (w >= 0) & (h < H) & (w < W)
+    hl, wl = h.floor().clamp(0, H - 1), w.floor().clamp(0, W - 1)
+    lo = torch.where(ok, hl * W + wl, torch.full_like(h, float("inf")))
+    hi = torch.where(ok, (hl + 1).clamp(max=H - 1) * W + (wl + 1).clamp(max=W - 1), torch.full_like(h, -1.0))
+    pad = T * tile_w - P
+    lo = torch.nn.functional.pad(lo, (0, pad), value=float("inf")).reshape(N, dg, 9, T, tile_w).amin((2, 4))
+    hi = torch.nn.functional.pad(hi, (0, pad), value=-1.0).reshape(N, dg, 9, T, tile_w).amax((2, 4))
+    count = torch.where(hi >= 0, hi + 1 - torch.nan_to_num(lo, posinf=0.0) + 7, torch.zeros_like(hi))
+    return float((count <= MAX_WINDOW).float().mean())
+
+
+def f16_forward(t, shape):
+    return d16.deform_conv_forward(t[0], t[1], t[2], 1, shape[6], 1, shape[5], bias=t[3])
+
+
+def composition(t, shape):
+    b = t[3].float() if t[3] is not None else None
+    return ops.deform_conv_forward(t[0].float(), t[1].float(), t[2].float(), 1, shape[6], 1, shape[5], bias=b).half()
+
+
+def capture(fn, sets, shape):
+    """one graph that runs fn on every input set in turn"""
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        for t in sets:
+            fn(t, shape)
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            outs = [fn(t, shape) for t in sets]
+    return graph, outs
+
+
+def time_alternating(runs, iters):
+    """runs: {name: callable}; -> {name: median ms per call of the callable}, the callables alternating"""
+    times = {k: [] for k in runs}
+    for k, run in runs.items():
+        for _ in range(3):
+            run()
+    torch.cuda.synchronize()
+    for _ in range(iters):
+        for k, run in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            run()
+            b.record()
+            b.synchronize()
+            times[k].append(a.elapsed_time(b))
+    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deform_conv_f16_time.json"))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+    result = dict(device=torch.cuda.get_device_name(0), iters=args.iters, input_sets=SETS, offset_sigmas=list(SIGMAS),
+                  shapes={})
+    for name, shape in SHAPES.items():
+        for sigma in SIGMAS:
+            N, C, H, W, F, dg, stride, bias = shape
+            sets = [inputs(shape, s, sigma) for s in range(SETS)]
+            g16, o16 = capture(f16_forward, sets, shape)
+            oco = [composition(t, shape) for t in sets]
+            g16.replay()
+            torch.cuda.synchronize()
+            diff = max(float((a.float() - b.float()).abs().max()) for a, b in zip(o16, oco))
+            ymax = max(float(b.float().abs().max()) for b in oco)
+            t = time_alternating(dict(graph=g16.replay, f16=lambda: [f16_forward(v, shape) for v in sets],
+                                      composition=lambda: [composition(v, shape) for v in sets]), args.iters)
+            f16_ms, comp_ms, graph_ms = t["f16"] / SETS, t["composition"] / SETS, t["graph"] / SETS
+            Ho, Wo = o16[0].shape[2:]
+            flop = 2.0 * N * F * Ho * Wo * 9 * C
+            nbytes = 2 * (N * C * H * W + N * 18 * dg * Ho * Wo + F * C * 9 + (F if bias else 0) + N * F * Ho * Wo)
+            dy = [torch.randn(o.shape, device="cuda").half() for o in o16]
+            dyf, setsf = [d.float() for d in dy], [[v.float() if v is not None else None for v in s] for s in sets]
+            i = [0]
+
+            def bwd16():
+                k = i[0] % SETS
+                d16.deform_conv_backward(dy[k], *sets[k][:3], 1, stride, 1, dg, bias=bias)
+
+            def bwd32():
+                k = i[0] % SETS
+                i[0] += 1
+                ops.deform_conv_backward(dyf[k], *setsf[k][:3], 1, stride, 1, dg, bias=bias)
+
+            tb = time_alternating(dict(f16=bwd16, float32=bwd32), args.iters)
+            key = "%s/sigma%g" % (name, sigma)
+            result["shapes"][key] = dict(
+                offset_sigma=sigma, window_fit=round(window_fit(sets[0][1], shape), 4),
+                shape=dict(N=N, C=C, H=H, W=W, F=F, num_deformable_group=dg, stride=stride, bias=bias),
+                forward_f16_graph_ms=round(graph_ms, 4), forward_f16_ms=round(f16_ms, 4),
+                forward_composition_ms=round(comp_ms, 4),
+                forward_speedup=round(comp_ms / f16_ms, 3), bytes_moved=nbytes,
+                achieved_bytes_per_s=round(nbytes / (graph_ms * 1e-3), 0),
+                f16_mfma_fraction=round(flop / (graph_ms * 1e-3) / PEAK_F16, 4),
+                max_abs_diff_to_composition=diff, max_abs_y=ymax,
+                backward_f16_ms=round(tb["f16"], 4), backward_float32_ms=round(tb["float32"], 4),
+                backward_ratio=round(tb["f16"] / tb["float32"], 3))
+            print(key, json.dumps(result["shapes"][key]))
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
