@@ -684,6 +684,27 @@ int sd_deform_convolution_bwd_f16(const void* out_grad, const void* x, const voi
                                   int req_weight, int req_bias, int N, int C, int H, int W, int F, int kh, int kw,
                                   int pad, int stride, int dil, int dgroup, int num_group, void* workspace,
                                   size_t workspace_bytes, void* stream);
+/* The same backward with the weight gradient on native-half matrix-core operands and no col matrix (3x3, num_group = 1,
+ * C / dgroup % 16 == 0, any stride, dilation, pad, H, W, N, F; pointers aligned to 2 bytes):
+ *   d_weight = sum_{n,p} out_grad . col^T: the sample is the forward's B element bit for bit (offsets and corners
+ *   widened to fp32, sd_deform_im2col's expression in its order, 0 outside the image, one RNE to fp16), out_grad as it
+ *   lies, single-term v_mfma_f32_16x16x32_f16 products into fp32, the sum over all images and pixels in fp32 in an order
+ *   the launch geometry fixes (no float atomics: two calls give equal bits), one rounding to fp16; req = add widens the
+ *   destination, adds in fp32 and rounds once.  Against fp64 on the widened inputs, T = N Ho Wo:
+ *   |dW - dW64| <= (1 + 2^-10) [(2^-11 + (T + 16) 2^-24) sum_{n,p} |dy col| + 2^-11 |dW64| + 2^-25].
+ *   d_x, d_offset, d_bias: sd_deform_convolution_bwd_f16 with req_weight = 0 (which skips its im2col and dW product),
+ *   bit-equal to it; with only d_weight requested nothing is widened.  Every other shape runs
+ *   sd_deform_convolution_bwd_f16 whole.
+ *   pixel_runs: pixel runs per image, each one workgroup per 16-channel slab and filter tile; 0 = chosen from N, the
+ *   slab count and the CU count, k > 0 = exactly min(k, ceil(Ho Wo / 64)). */
+size_t sd_deform_convolution_bwd_workspace_bytes_f16_fused(int N, int C, int H, int W, int F, int kh, int kw, int pad,
+                                                           int stride, int dil, int dgroup, int num_group,
+                                                           int pixel_runs);
+int sd_deform_convolution_bwd_f16_fused(const void* out_grad, const void* x, const void* offset, const void* weight,
+                                        void* d_x, void* d_offset, void* d_weight, void* d_bias, int req_x,
+                                        int req_offset, int req_weight, int req_bias, int N, int C, int H, int W, int F,
+                                        int kh, int kw, int pad, int stride, int dil, int dgroup, int num_group,
+                                        int pixel_runs, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_Proposal_v3  (mx.sym.contrib.Proposal_v3, models/FPN/builder.py:275-287) -- SURVEY 8(f)

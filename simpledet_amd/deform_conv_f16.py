@@ -13,6 +13,9 @@ Forward, 3x3 kernels with num_group = 1 and C / num_deformable_group % 16 == 0: 
 csrc/deform_fused_f16.hip -- fp32 sampling rounded once to fp16, fp16 weights untouched, single-term
 fp16 matrix-core products into fp32, one final rounding.  Every other shape, and the backward: the float32 operator
 on widened operands, each result rounded once (bit-equal to cast -> float32 call -> cast).
+Backward with fused_weight_grad=True (opt-in, same shapes as the native forward): d_weight from the col-free kernel of
+csrc/deform_wgrad_f16.hip -- the forward's samples, dY as it lies, single-term fp16 matrix-core products
+summed in fp32 over all images and pixels in a fixed order, one rounding; the other gradients keep their bits.
 
 It stays out of `ops.py` and of mxnet_plugin's tables, like sync_bn.py and free_anchor.py: their public surfaces are
 pinned."""
@@ -24,7 +27,7 @@ from ._mx_adapter import REQ, _call, _mx, _no_add, _ptr, _req, _sync, _wait, _ws
 from .ops import _chk, _dcn_out_hw, _req_of
 
 F16_OP = "_contrib_DeformableConvolution_f16"
-_own = {"installed": False, "props": {}}
+_own = {"installed": False, "props": {}, "fused_weight_grad": False}
 fallbacks = []
 
 
@@ -66,9 +69,12 @@ def deform_conv_forward(x, offset, weight, pad=1, stride=1, dilate=1, num_deform
 
 
 def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1, num_deformable_group=1,
-                         req=("write", "write", "write"), grads=None, fwd_ws=None, num_group=1, bias=False):
+                         req=("write", "write", "write"), grads=None, fwd_ws=None, num_group=1, bias=False,
+                         fused_weight_grad=False, pixel_runs=0):
     """ops.deform_conv_backward for float16 tensors -> (d_data, d_offset, d_weight[, d_bias]), float16: the float32
-    backward on widened operands, every gradient rounded once (req "add": onto the widened destination)."""
+    backward on widened operands, every gradient rounded once (req "add": onto the widened destination).
+    fused_weight_grad=True: sd_deform_convolution_bwd_f16_fused -- d_weight from the col-free half kernel where the
+    shape allows, in `pixel_runs` pixel runs per image (0: chosen for the device); the other gradients unchanged."""
     if x.dtype == torch.float32:
         return ops.deform_conv_backward(out_grad, x, offset, weight, pad, stride, dilate, num_deformable_group, req,
                                         grads, fwd_ws, num_group, bias)
@@ -85,31 +91,37 @@ def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1,
         raise ValueError("grads must hold %d tensors, got %d" % (4 if bias else 3, len(grads)))
     for t, like in zip(grads, (x, offset, weight)):
         _chk(t, "gradient", torch.float16, shape=like.shape)
-    ws = ops._ws(x.device, None, "sd_deform_convolution_bwd_workspace_bytes_f16", *dims)
-    ops._call("sd_deform_convolution_bwd_f16", out_grad, x, offset, weight, grads[0], grads[1], grads[2],
-              grads[3] if bias else None, r[0], r[1], r[2], r[3] if bias else REQ["null"], *dims, ws, ws.numel())
+    tail, extra = ("_fused", (int(pixel_runs),)) if fused_weight_grad else ("", ())
+    ws = ops._ws(x.device, None, "sd_deform_convolution_bwd_workspace_bytes_f16" + tail, *dims, *extra)
+    ops._call("sd_deform_convolution_bwd_f16" + tail, out_grad, x, offset, weight, grads[0], grads[1], grads[2],
+              grads[3] if bias else None, r[0], r[1], r[2], r[3] if bias else REQ["null"], *dims, *extra, ws,
+              ws.numel())
     return grads
 
 
 class _DeformConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, offset, weight, bias, pad, stride, dilate, dg, num_group):
+    def forward(ctx, x, offset, weight, bias, pad, stride, dilate, dg, num_group, fused_weight_grad):
         ctx.save_for_backward(x, offset, weight)
         ctx.geom, ctx.has_bias = (pad, stride, dilate, dg), bias is not None
-        ctx.num_group = num_group
+        ctx.num_group, ctx.fused = num_group, fused_weight_grad
         return deform_conv_forward(x, offset, weight, pad, stride, dilate, dg, False, bias, num_group)
 
     @staticmethod
     def backward(ctx, dy):
         x, offset, weight = ctx.saved_tensors
+        kw = dict(fused_weight_grad=True) if ctx.fused and x.dtype == torch.float16 else {}
         g = deform_conv_backward(dy.contiguous(), x, offset, weight, *ctx.geom, num_group=ctx.num_group,
-                                 bias=ctx.has_bias)
-        return g[0], g[1], g[2], (g[3] if ctx.has_bias else None), None, None, None, None, None
+                                 bias=ctx.has_bias, **kw)
+        return g[0], g[1], g[2], (g[3] if ctx.has_bias else None), None, None, None, None, None, None
 
 
-def deform_conv(x, offset, weight, bias=None, pad=1, stride=1, dilate=1, num_deformable_group=1, num_group=1):
-    """differentiable DeformableConvolution on float16 or float32 tensors"""
-    return _DeformConv.apply(x, offset, weight, bias, pad, stride, dilate, num_deformable_group, num_group)
+def deform_conv(x, offset, weight, bias=None, pad=1, stride=1, dilate=1, num_deformable_group=1, num_group=1,
+                fused_weight_grad=False):
+    """differentiable DeformableConvolution on float16 or float32 tensors; fused_weight_grad: the half backward's
+    d_weight from the col-free kernel (deform_conv_backward)"""
+    return _DeformConv.apply(x, offset, weight, bias, pad, stride, dilate, num_deformable_group, num_group,
+                             bool(fused_weight_grad))
 
 
 # ----------------------------------------------------------------------------------- MXNet adapter ----
@@ -150,10 +162,12 @@ def _build_ops(mx):
             x, off, w = in_data[:3]
             has_b = self.g["bias"]
             dims = self._dims(x)
-            ws, wsp, wsn = _ws(x, "sd_deform_convolution_bwd_workspace_bytes_f16", *dims)
-            _call("sd_deform_convolution_bwd_f16", _ptr(out_grad[0]), _ptr(x), _ptr(off), _ptr(w), _ptr(in_grad[0]),
-                  _ptr(in_grad[1]), _ptr(in_grad[2]), _ptr(in_grad[3]) if has_b else None, _req(req[0]), _req(req[1]),
-                  _req(req[2]), _req(req[3]) if has_b else REQ["null"], *dims, wsp, wsn, None)
+            tail, extra = ("_fused", (0,)) if _own["fused_weight_grad"] else ("", ())   # (pixel_runs: the host's)
+            ws, wsp, wsn = _ws(x, "sd_deform_convolution_bwd_workspace_bytes_f16" + tail, *dims, *extra)
+            _call("sd_deform_convolution_bwd_f16" + tail, _ptr(out_grad[0]), _ptr(x), _ptr(off), _ptr(w),
+                  _ptr(in_grad[0]), _ptr(in_grad[1]), _ptr(in_grad[2]), _ptr(in_grad[3]) if has_b else None,
+                  _req(req[0]), _req(req[1]), _req(req[2]), _req(req[3]) if has_b else REQ["null"], *dims, *extra,
+                  wsp, wsn, None)
             _sync()
 
     class DeformConvF16Prop(base):
@@ -173,12 +187,14 @@ def register(mx=None):
     return register_ops(mx, _build_ops(mx), _own)
 
 
-def install(mx=None):
+def install(mx=None, fused_weight_grad=False):
     """After mxnet_plugin.install(mx): register() + point the `DeformableConvolution` alias of every contrib
     namespace at the dtype-dispatching operator.  The constructor the plugin's alias replaced stays the fallback for
-    parameter sets `sd_supports` (unchanged) does not take; stream and sync are the plugin's."""
+    parameter sets `sd_supports` (unchanged) does not take; stream and sync are the plugin's.
+    fused_weight_grad=True: the half operator's backward calls sd_deform_convolution_bwd_f16_fused."""
     mx = _mx(mx)
     props = register(mx)
+    _own["fused_weight_grad"] = bool(fused_weight_grad)
     del fallbacks[:]
     put_alias(mx, "contrib", "DeformableConvolution",
               lambda original: alias_ctor(mx, F16_OP, props[F16_OP], original,

@@ -11,6 +11,11 @@ no call finds its inputs in L2 from the one before):
                replay kernel-only graphs), so no memset node is recorded here.  `forward_speedup` is eager over eager.
 Backward: sd_deform_convolution_bwd_f16 (casts + the float32 backward + casts) against the float32 backward alone,
 eagerly, for the same reason (the float32 backward clears d_weight and its maxima with hipMemsetAsync).
+Weight gradient without a col matrix (csrc/deform_wgrad_f16.hip), the paths alternating in one run on the
+rotating inputs: (a) the whole backward, sd_deform_convolution_bwd_f16 against sd_deform_convolution_bwd_f16_fused;
+(b) the weight gradient alone (req null for the rest): widen + im2col + product against the new kernel + its reduce;
+(c) the parent's whole backward timed a second time in the same rotation: the run's own spread.  `--only-fused` runs
+just the fused weight gradient (for a kernel trace in a run of its own).
 
 Shapes: the README's DCN row (16, 256, 50, 84) dg 4 -> 256, and the sepc neck's (2, 256, 100, 168) and
 (2, 256, 50, 84) at stride 1 and 2, dg 1, with a bias.  Every shape at the two offset spreads bench_ops.py's DCN row
@@ -123,8 +128,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deform_conv_f16_time.json"))
+    ap.add_argument("--only-fused", action="store_true", help="the fused weight gradient alone, readme_dcn, no file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
+    if args.only_fused:
+        shape = SHAPES["readme_dcn"]
+        t = inputs(shape, 0, SIGMAS[0])
+        dy = torch.randn(f16_forward(t, shape).shape, device="cuda").half()
+        for _ in range(args.iters):
+            d16.deform_conv_backward(dy, *t[:3], 1, shape[6], 1, shape[5], req=("null", "null", "write"),
+                                     fused_weight_grad=True)
+        torch.cuda.synchronize()
+        return
     result = dict(device=torch.cuda.get_device_name(0), iters=args.iters, input_sets=SETS, offset_sigmas=list(SIGMAS),
                   shapes={})
     for name, shape in SHAPES.items():
@@ -157,6 +172,18 @@ def main():
                 ops.deform_conv_backward(dyf[k], *setsf[k][:3], 1, stride, 1, dg, bias=bias)
 
             tb = time_alternating(dict(f16=bwd16, float32=bwd32), args.iters)
+            j = [0]
+
+            def bwd(fused, req, step=False):
+                def run():
+                    k = j[0] % SETS
+                    j[0] += step
+                    d16.deform_conv_backward(dy[k], *sets[k][:3], 1, stride, 1, dg, req=req, fused_weight_grad=fused)
+                return run
+
+            whole, only_w = ("write",) * 3, ("null", "null", "write")
+            tw = time_alternating(dict(parent=bwd(False, whole), fused=bwd(True, whole), parent_again=bwd(False, whole),
+                                       parent_dw=bwd(False, only_w), fused_dw=bwd(True, only_w, True)), args.iters)
             key = "%s/sigma%g" % (name, sigma)
             result["shapes"][key] = dict(
                 offset_sigma=sigma, window_fit=round(window_fit(sets[0][1], shape), 4),
@@ -168,7 +195,12 @@ def main():
                 f16_mfma_fraction=round(flop / (graph_ms * 1e-3) / PEAK_F16, 4),
                 max_abs_diff_to_composition=diff, max_abs_y=ymax,
                 backward_f16_ms=round(tb["f16"], 4), backward_float32_ms=round(tb["float32"], 4),
-                backward_ratio=round(tb["f16"] / tb["float32"], 3))
+                backward_ratio=round(tb["f16"] / tb["float32"], 3),
+                backward_parent_ms=round(tw["parent"], 4), backward_fused_ms=round(tw["fused"], 4),
+                backward_parent_again_ms=round(tw["parent_again"], 4),
+                backward_fused_speedup=round(tw["parent"] / tw["fused"], 3),
+                weight_grad_parent_ms=round(tw["parent_dw"], 4), weight_grad_fused_ms=round(tw["fused_dw"], 4),
+                weight_grad_speedup=round(tw["parent_dw"] / tw["fused_dw"], 3))
             print(key, json.dumps(result["shapes"][key]))
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
