@@ -705,6 +705,33 @@ int sd_deform_convolution_bwd_f16_fused(const void* out_grad, const void* x, con
                                         int req_offset, int req_weight, int req_bias, int N, int C, int H, int W, int F,
                                         int kh, int kw, int pad, int stride, int dil, int dgroup, int num_group,
                                         int pixel_runs, void* workspace, size_t workspace_bytes, void* stream);
+/* The same backward with d_x and d_offset on the half operands as they lie as well (the shapes above; every other
+ * shape, and a call that requests neither, runs _bwd_f16_fused -- fused_weight_grad set -- or _bwd_f16, whole):
+ *   dcol = W^T out_grad per (image, deformable group, 64-pixel tile): exact fp16 x fp16 products on single-term
+ *   v_mfma_f32_16x16x32_f16, F fp32 additions; the weights re-laid once per call (a copy).
+ *   d_offset: from the unrounded fp32 dcol in the tile, sd_deform_col2im_coord's sampling state and expression in its
+ *   order on widened corners, channels ascending, one sum per (tap, pixel, direction) over the group's channels in
+ *   fp32 in a fixed order (no atomics: two calls give equal bits), one rounding.  cpg = C / dgroup,
+ *   A[c,tap,p] = sum_f |w dy|, S_o = sum_c A sum_i |f_i x_i|:
+ *   |dO - dO64| <= (1 + 2^-10) [((F + cpg + 16) 2^-24) S_o + 2^-11 |dO64| + 2^-25].
+ *   d_x: dcol rounded once to fp16 into the workspace ([image][16-channel slab][tap][pixel][16 channels], written
+ *   and read once), then summed per band of rows in fp32 in LDS with sd_deform_col2im's landing weights g >= 0 and
+ *   rounded once.  The LDS additions are native float adds in hardware order: where the fp32 sums are not exact, two
+ *   calls can differ in the last bit of a result.  T = 9 Ho Wo, S_x = sum_{tap,p} g A:
+ *   |dX - dX64| <= (1 + 2^-10) [(2^-11 + (F + T + 16) 2^-24) S_x + 2^-11 |dX64| + 2^-25 (1 + sum g)].
+ *   Both bounds against fp64 on the widened inputs.  req = add widens the destination, adds in fp32, rounds once.
+ *   Each of d_x, d_offset honours its own req; with one of them null its work is skipped (d_offset alone writes no
+ *   dcol).  d_weight: _bwd_f16_fused's kernel (fused_weight_grad != 0) or _bwd_f16's route, bit-equal to them;
+ *   d_bias: bit-equal to _bwd_f16, summed from out_grad as it lies.  With fused_weight_grad set nothing is widened. */
+size_t sd_deform_convolution_bwd_workspace_bytes_f16_native(int N, int C, int H, int W, int F, int kh, int kw, int pad,
+                                                            int stride, int dil, int dgroup, int num_group,
+                                                            int fused_weight_grad, int pixel_runs);
+int sd_deform_convolution_bwd_f16_native(const void* out_grad, const void* x, const void* offset, const void* weight,
+                                         void* d_x, void* d_offset, void* d_weight, void* d_bias, int req_x,
+                                         int req_offset, int req_weight, int req_bias, int N, int C, int H, int W,
+                                         int F, int kh, int kw, int pad, int stride, int dil, int dgroup,
+                                         int num_group, int fused_weight_grad, int pixel_runs, void* workspace,
+                                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * _contrib_Proposal_v3  (mx.sym.contrib.Proposal_v3, models/FPN/builder.py:275-287) -- SURVEY 8(f)

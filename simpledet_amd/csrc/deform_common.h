@@ -55,6 +55,39 @@ __device__ __forceinline__ Sample im2col_sample(const DcnGeom& g, int h_in, int 
   return s;
 }
 
+// where a sample lands: LDS index of the (floor, floor) corner relative to the band and the factors of
+// the two rows / two columns (0 for a corner that does not exist, lies outside the band or has weight 0)
+__device__ __forceinline__ void col2im_geom(const DcnGeom& g, float inv_h, float inv_w, int row0, int row1,
+                                            int& base, float (&fhv)[2], float (&fwv)[2]) {
+  // same arithmetic as deform_col2im_kernel above, as (index, weight) pairs
+  float ah = inv_h, aw = inv_w;
+  const bool inside = !(ah < 0 || ah > g.H || aw < 0 || aw > g.W);
+  int hl = (int)ah, wl = (int)aw, hh_, wh_;
+  if (hl >= g.H - 1) {
+    hh_ = hl = g.H - 1;
+    ah = (float)hl;
+  } else {
+    hh_ = hl + 1;
+  }
+  if (wl >= g.W - 1) {
+    wh_ = wl = g.W - 1;
+    aw = (float)wl;
+  } else {
+    wh_ = wl + 1;
+  }
+  const int fh = (int)floorf(inv_h), fw = (int)floorf(inv_w);
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    const int hh = fh + d;
+    const bool ok = inside && hh >= 0 && hh < g.H && fabsf(inv_h - hh) < 1 && hh >= row0 && hh < row1;
+    fhv[d] = !ok ? 0.f : hh == hl ? (hh + 1 - ah) : hh == hh_ ? (ah + 1 - hh) : 0.f;
+    const int ww = fw + d;
+    const bool okw = ww >= 0 && ww < g.W && fabsf(inv_w - ww) < 1;
+    fwv[d] = !okw ? 0.f : ww == wl ? (ww + 1 - aw) : ww == wh_ ? (aw + 1 - ww) : 0.f;
+  }
+  base = (fh - row0) * g.W + fw;
+}
+
 constexpr int kDcnMaxTaps = 9;        // taps whose sampling state the LDS-plane kernels keep in registers
 
 // packed corner state: bits 0-27 index of (h_low, w_low), bit 28 w_high - w_low, bit 29

@@ -180,38 +180,7 @@ __global__ __launch_bounds__(256) void deform_col2im_kernel(const float* __restr
 // where the reference sends them.
 
 
-// where a sample lands: LDS index of the (floor, floor) corner relative to the band and the factors of
-// the two rows / two columns (0 for a corner that does not exist, lies outside the band or has weight 0)
-__device__ __forceinline__ void col2im_geom(const DcnGeom& g, float inv_h, float inv_w, int row0, int row1,
-                                            int& base, float (&fhv)[2], float (&fwv)[2]) {
-  // same arithmetic as deform_col2im_kernel above, as (index, weight) pairs
-  float ah = inv_h, aw = inv_w;
-  const bool inside = !(ah < 0 || ah > g.H || aw < 0 || aw > g.W);
-  int hl = (int)ah, wl = (int)aw, hh_, wh_;
-  if (hl >= g.H - 1) {
-    hh_ = hl = g.H - 1;
-    ah = (float)hl;
-  } else {
-    hh_ = hl + 1;
-  }
-  if (wl >= g.W - 1) {
-    wh_ = wl = g.W - 1;
-    aw = (float)wl;
-  } else {
-    wh_ = wl + 1;
-  }
-  const int fh = (int)floorf(inv_h), fw = (int)floorf(inv_w);
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const int hh = fh + d;
-    const bool ok = inside && hh >= 0 && hh < g.H && fabsf(inv_h - hh) < 1 && hh >= row0 && hh < row1;
-    fhv[d] = !ok ? 0.f : hh == hl ? (hh + 1 - ah) : hh == hh_ ? (ah + 1 - hh) : 0.f;
-    const int ww = fw + d;
-    const bool okw = ww >= 0 && ww < g.W && fabsf(inv_w - ww) < 1;
-    fwv[d] = !okw ? 0.f : ww == wl ? (ww + 1 - aw) : ww == wh_ ? (aw + 1 - ww) : 0.f;
-  }
-  base = (fh - row0) * g.W + fw;
-}
+// (col2im_geom -- where a sample lands -- lives in deform_common.h: the fp16 data gradient shares it)
 
 // per (tap, group, image): the largest sum of weights one pixel collects from this tap's samples, added
 // into wsum[image * dgroup + group] (zeroed by the caller).  In integers -- every weight rounded UP to a

@@ -16,6 +16,9 @@ on widened operands, each result rounded once (bit-equal to cast -> float32 call
 Backward with fused_weight_grad=True (opt-in, same shapes as the native forward): d_weight from the col-free kernel of
 csrc/deform_wgrad_f16.hip -- the forward's samples, dY as it lies, single-term fp16 matrix-core products
 summed in fp32 over all images and pixels in a fixed order, one rounding; the other gradients keep their bits.
+Backward with fused_input_grads=True (opt-in, same shapes): d_data and d_offset from csrc/deform_igrad_f16.hip
+ -- dcol = W^T dY on single-term fp16 matrix-core products, d_offset from the fp32 accumulators in the
+tile, d_data from an fp16 dcol written and read once; d_weight and d_bias keep their bits.
 
 It stays out of `ops.py` and of mxnet_plugin's tables, like sync_bn.py and free_anchor.py: their public surfaces are
 pinned."""
@@ -27,7 +30,7 @@ from ._mx_adapter import REQ, _call, _mx, _no_add, _ptr, _req, _sync, _wait, _ws
 from .ops import _chk, _dcn_out_hw, _req_of
 
 F16_OP = "_contrib_DeformableConvolution_f16"
-_own = {"installed": False, "props": {}, "fused_weight_grad": False}
+_own = {"installed": False, "props": {}, "fused_weight_grad": False, "fused_input_grads": False}
 fallbacks = []
 
 
@@ -70,11 +73,13 @@ def deform_conv_forward(x, offset, weight, pad=1, stride=1, dilate=1, num_deform
 
 def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1, num_deformable_group=1,
                          req=("write", "write", "write"), grads=None, fwd_ws=None, num_group=1, bias=False,
-                         fused_weight_grad=False, pixel_runs=0):
+                         fused_weight_grad=False, pixel_runs=0, fused_input_grads=False):
     """ops.deform_conv_backward for float16 tensors -> (d_data, d_offset, d_weight[, d_bias]), float16: the float32
     backward on widened operands, every gradient rounded once (req "add": onto the widened destination).
     fused_weight_grad=True: sd_deform_convolution_bwd_f16_fused -- d_weight from the col-free half kernel where the
-    shape allows, in `pixel_runs` pixel runs per image (0: chosen for the device); the other gradients unchanged."""
+    shape allows, in `pixel_runs` pixel runs per image (0: chosen for the device); the other gradients unchanged.
+    fused_input_grads=True: sd_deform_convolution_bwd_f16_native -- d_data and d_offset from the half kernels where
+    the shape allows (bounds: include/simpledet_ops.h); d_weight as fused_weight_grad says, d_bias unchanged."""
     if x.dtype == torch.float32:
         return ops.deform_conv_backward(out_grad, x, offset, weight, pad, stride, dilate, num_deformable_group, req,
                                         grads, fwd_ws, num_group, bias)
@@ -91,7 +96,7 @@ def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1,
         raise ValueError("grads must hold %d tensors, got %d" % (4 if bias else 3, len(grads)))
     for t, like in zip(grads, (x, offset, weight)):
         _chk(t, "gradient", torch.float16, shape=like.shape)
-    tail, extra = ("_fused", (int(pixel_runs),)) if fused_weight_grad else ("", ())
+    tail, extra = _route(fused_weight_grad, fused_input_grads, pixel_runs)
     ws = ops._ws(x.device, None, "sd_deform_convolution_bwd_workspace_bytes_f16" + tail, *dims, *extra)
     ops._call("sd_deform_convolution_bwd_f16" + tail, out_grad, x, offset, weight, grads[0], grads[1], grads[2],
               grads[3] if bias else None, r[0], r[1], r[2], r[3] if bias else REQ["null"], *dims, *extra, ws,
@@ -99,29 +104,38 @@ def deform_conv_backward(out_grad, x, offset, weight, pad=1, stride=1, dilate=1,
     return grads
 
 
+def _route(fused_weight_grad, fused_input_grads, pixel_runs):
+    """the backward entry point's suffix and the arguments it takes in front of the workspace"""
+    if fused_input_grads:
+        return "_native", (int(bool(fused_weight_grad)), int(pixel_runs))
+    return ("_fused", (int(pixel_runs),)) if fused_weight_grad else ("", ())
+
+
 class _DeformConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, offset, weight, bias, pad, stride, dilate, dg, num_group, fused_weight_grad):
+    def forward(ctx, x, offset, weight, bias, pad, stride, dilate, dg, num_group, fused_weight_grad,
+                fused_input_grads=False):
         ctx.save_for_backward(x, offset, weight)
         ctx.geom, ctx.has_bias = (pad, stride, dilate, dg), bias is not None
-        ctx.num_group, ctx.fused = num_group, fused_weight_grad
+        ctx.num_group, ctx.fused, ctx.fused_in = num_group, fused_weight_grad, fused_input_grads
         return deform_conv_forward(x, offset, weight, pad, stride, dilate, dg, False, bias, num_group)
 
     @staticmethod
     def backward(ctx, dy):
         x, offset, weight = ctx.saved_tensors
-        kw = dict(fused_weight_grad=True) if ctx.fused and x.dtype == torch.float16 else {}
+        kw = dict(fused_weight_grad=ctx.fused, fused_input_grads=ctx.fused_in) if x.dtype == torch.float16 else {}
         g = deform_conv_backward(dy.contiguous(), x, offset, weight, *ctx.geom, num_group=ctx.num_group,
                                  bias=ctx.has_bias, **kw)
-        return g[0], g[1], g[2], (g[3] if ctx.has_bias else None), None, None, None, None, None, None
+        return g[0], g[1], g[2], (g[3] if ctx.has_bias else None), None, None, None, None, None, None, None
 
 
 def deform_conv(x, offset, weight, bias=None, pad=1, stride=1, dilate=1, num_deformable_group=1, num_group=1,
-                fused_weight_grad=False):
+                fused_weight_grad=False, fused_input_grads=False):
     """differentiable DeformableConvolution on float16 or float32 tensors; fused_weight_grad: the half backward's
-    d_weight from the col-free kernel (deform_conv_backward)"""
+    d_weight from the col-free kernel, fused_input_grads: its d_data and d_offset from the half kernels
+    (deform_conv_backward)"""
     return _DeformConv.apply(x, offset, weight, bias, pad, stride, dilate, num_deformable_group, num_group,
-                             bool(fused_weight_grad))
+                             bool(fused_weight_grad), bool(fused_input_grads))
 
 
 # ----------------------------------------------------------------------------------- MXNet adapter ----
@@ -162,7 +176,7 @@ def _build_ops(mx):
             x, off, w = in_data[:3]
             has_b = self.g["bias"]
             dims = self._dims(x)
-            tail, extra = ("_fused", (0,)) if _own["fused_weight_grad"] else ("", ())   # (pixel_runs: the host's)
+            tail, extra = _route(_own["fused_weight_grad"], _own["fused_input_grads"], 0)   # (pixel_runs: the host's)
             ws, wsp, wsn = _ws(x, "sd_deform_convolution_bwd_workspace_bytes_f16" + tail, *dims, *extra)
             _call("sd_deform_convolution_bwd_f16" + tail, _ptr(out_grad[0]), _ptr(x), _ptr(off), _ptr(w),
                   _ptr(in_grad[0]), _ptr(in_grad[1]), _ptr(in_grad[2]), _ptr(in_grad[3]) if has_b else None,
@@ -187,14 +201,15 @@ def register(mx=None):
     return register_ops(mx, _build_ops(mx), _own)
 
 
-def install(mx=None, fused_weight_grad=False):
+def install(mx=None, fused_weight_grad=False, fused_input_grads=False):
     """After mxnet_plugin.install(mx): register() + point the `DeformableConvolution` alias of every contrib
     namespace at the dtype-dispatching operator.  The constructor the plugin's alias replaced stays the fallback for
     parameter sets `sd_supports` (unchanged) does not take; stream and sync are the plugin's.
-    fused_weight_grad=True: the half operator's backward calls sd_deform_convolution_bwd_f16_fused."""
+    fused_weight_grad=True: the half operator's backward calls sd_deform_convolution_bwd_f16_fused;
+    fused_input_grads=True: sd_deform_convolution_bwd_f16_native (with fused_weight_grad as its argument)."""
     mx = _mx(mx)
     props = register(mx)
-    _own["fused_weight_grad"] = bool(fused_weight_grad)
+    _own["fused_weight_grad"], _own["fused_input_grads"] = bool(fused_weight_grad), bool(fused_input_grads)
     del fallbacks[:]
     put_alias(mx, "contrib", "DeformableConvolution",
               lambda original: alias_ctor(mx, F16_OP, props[F16_OP], original,

@@ -16,6 +16,11 @@ rotating inputs: (a) the whole backward, sd_deform_convolution_bwd_f16 against s
 (b) the weight gradient alone (req null for the rest): widen + im2col + product against the new kernel + its reduce;
 (c) the parent's whole backward timed a second time in the same rotation: the run's own spread.  `--only-fused` runs
 just the fused weight gradient (for a kernel trace in a run of its own).
+Data and offset gradients on the half operands (csrc/deform_igrad_f16.hip), medians of `--native-iters`
+(12) in the same rotation, the parent being sd_deform_convolution_bwd_f16_fused and the native route
+sd_deform_convolution_bwd_f16_native with fused_weight_grad: (a) the whole backward; (b) d_data + d_offset alone (req
+null for the weight); (c) the parent's two timed a second time: the spread.  `--only-native` times just these and
+updates the rows of the existing file; `--only-igrad` runs the native d_data + d_offset alone (for a kernel trace).
 
 Shapes: the README's DCN row (16, 256, 50, 84) dg 4 -> 256, and the sepc neck's (2, 256, 100, 168) and
 (2, 256, 50, 84) at stride 1 and 2, dg 1, with a bias.  Every shape at the two offset spreads bench_ops.py's DCN row
@@ -124,13 +129,65 @@ def time_alternating(runs, iters):
     return {k: sorted(v)[len(v) // 2] for k, v in times.items()}
 
 
+def native_rows(sets, dy, shape, iters):
+    """the parent (_bwd_f16_fused) and the native route alternating on the rotating inputs -> the row's native keys"""
+    stride, dg = shape[6], shape[5]
+    j = [0]
+
+    def bwd(native, req, step=False):
+        def run():
+            k = j[0] % SETS
+            j[0] += step
+            d16.deform_conv_backward(dy[k], *sets[k][:3], 1, stride, 1, dg, req=req, fused_weight_grad=True,
+                                     fused_input_grads=native)
+        return run
+
+    whole, inp = ("write",) * 3, ("write", "write", "null")
+    t = time_alternating(dict(parent=bwd(False, whole), native=bwd(True, whole), parent_in=bwd(False, inp),
+                              native_in=bwd(True, inp), parent_again=bwd(False, whole),
+                              parent_in_again=bwd(False, inp, True)), iters)
+    return dict(native_iters=iters, backward_fused_parent_ms=round(t["parent"], 4),
+                backward_native_ms=round(t["native"], 4), backward_fused_parent_again_ms=round(t["parent_again"], 4),
+                backward_native_speedup=round(t["parent"] / t["native"], 3),
+                input_grads_parent_ms=round(t["parent_in"], 4), input_grads_native_ms=round(t["native_in"], 4),
+                input_grads_parent_again_ms=round(t["parent_in_again"], 4),
+                input_grads_speedup=round(t["parent_in"] / t["native_in"], 3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deform_conv_f16_time.json"))
     ap.add_argument("--only-fused", action="store_true", help="the fused weight gradient alone, readme_dcn, no file")
+    ap.add_argument("--native-iters", type=int, default=12)
+    ap.add_argument("--only-native", action="store_true", help="the native input gradients alone, into the file's rows")
+    ap.add_argument("--only-igrad", action="store_true", help="native d_data + d_offset alone, readme_dcn, no file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
+    if args.only_igrad:
+        shape = SHAPES["readme_dcn"]
+        for sigma in SIGMAS:
+            t = inputs(shape, 0, sigma)
+            dy = torch.randn(f16_forward(t, shape).shape, device="cuda").half()
+            for _ in range(args.iters):
+                d16.deform_conv_backward(dy, *t[:3], 1, shape[6], 1, shape[5], req=("write", "write", "null"),
+                                         fused_weight_grad=True, fused_input_grads=True)
+        torch.cuda.synchronize()
+        return
+    if args.only_native:
+        with open(args.out) as f:
+            result = json.load(f)
+        for name, shape in SHAPES.items():
+            for sigma in SIGMAS:
+                sets = [inputs(shape, s, sigma) for s in range(SETS)]
+                dy = [torch.randn(f16_forward(t, shape).shape, device="cuda").half() for t in sets]
+                key = "%s/sigma%g" % (name, sigma)
+                result["shapes"][key].update(native_rows(sets, dy, shape, args.native_iters))
+                print(key, json.dumps(result["shapes"][key]))
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        return
     if args.only_fused:
         shape = SHAPES["readme_dcn"]
         t = inputs(shape, 0, SIGMAS[0])
@@ -200,7 +257,8 @@ def main():
                 backward_parent_again_ms=round(tw["parent_again"], 4),
                 backward_fused_speedup=round(tw["parent"] / tw["fused"], 3),
                 weight_grad_parent_ms=round(tw["parent_dw"], 4), weight_grad_fused_ms=round(tw["fused_dw"], 4),
-                weight_grad_speedup=round(tw["parent_dw"] / tw["fused_dw"], 3))
+                weight_grad_speedup=round(tw["parent_dw"] / tw["fused_dw"], 3),
+                **native_rows(sets, dy, shape, args.native_iters))
             print(key, json.dumps(result["shapes"][key]))
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
