@@ -733,6 +733,53 @@ int sd_deform_convolution_bwd_f16_native(const void* out_grad, const void* x, co
                                          int num_group, int fused_weight_grad, int pixel_runs, void* workspace,
                                          size_t workspace_bytes, void* stream);
 
+/* A list of independent fp16 forward problems in ONE launch (the SEPC neck's pyramid convolutions,
+ * models/sepc/sepc_neck.py: dozens of tiny calls per forward, most on levels of a few tiles).  Entry points only:
+ * SD_ABI_VERSION is unchanged.
+ *   problem p   y (N, F, Ho, Wo) fp16 from 1 or 2 sources, plus an optional residual.
+ *   source s    x (N, C_s, H_s, W_s), offset (N, dgroup_s 18, Ho, Wo), weight (F, C_s, 3, 3), bias (F) or NULL, its own
+ *               pad / stride / dil (square, as in _fwd_f16).  Its output size must be the problem's (Ho, Wo), and it
+ *               must be a shape of _fwd_f16's native kernel: 3x3, num_group = 1, C_s / dgroup_s % 16 == 0.
+ *   residual    r (N, F, Hr, Wr) fp16 or NULL, read at (h >> shift, w >> shift), shift in {0, 1}, with
+ *               (Hr << shift) >= Ho and (Wr << shift) >= Wo: nearest 2x upsampling cropped from the origin
+ *               (UpSampling(scale = 2, nearest) -> slice_like), or a plain add at shift 0.
+ *   y = RNE_f16( sum_s sum_k w_s,k col_s,k  +  bias_0 + bias_1 + r ): the products as in _fwd_f16 (fp32 sampling with
+ *   sd_deform_im2col's expression, one RNE to fp16 per sample, single-term v_mfma_f32_32x32x16_f16 into fp32), the
+ *   sources in order and _fwd_f16's k order inside a source; then the biases and the residual widened and added in
+ *   fp32 in that order, absent terms skipped; ONE rounding.  A single-source problem without a residual equals
+ *   sd_deform_convolution_fwd_f16 in every bit.  A graph of single calls and fp16 adds rounds a dual-source problem
+ *   with a residual three times; this rounds it once.
+ *   Error against fp64 on the widened inputs.  Each sample is an fp32 bilinear expression (< 16 roundings of 2^-24,
+ *   relative to the sample's own magnitude terms) rounded once to fp16 (2^-11 relative, or 2^-25 absolute where the
+ *   result is subnormal); w col is exact in fp32 (11 x 11 significant bits); the accumulator takes
+ *   sum_s 9 C_s additions and the epilogue up to 3 more, each with a relative error 2^-24 of a partial sum bounded
+ *   by S; the final rounding adds 2^-11 |y| <= 2^-11 (|y64| + the error so far), which the factor 1 + 2^-10 covers:
+ *     |y - y64| <= (1 + 2^-10) [(2^-11 + (K + 16) 2^-24) S + 2^-11 |y64| + 2^-25],
+ *     K = sum_s 9 C_s + 3,  S = sum_s sum_k |w_s,k col_s,k| + sum_s |bias_s| + |r|.
+ *   Limits: at most 16 problems per call, at most 2 sources per problem; more, or a source that is no native shape:
+ *   SD_ERR_UNSUPPORTED.  A null or odd pointer, an output size that differs from the problem's, a residual that
+ *   does not cover the output: SD_ERR_INVALID_ARG.  Every check runs before the first launch: a refused call leaves
+ *   every output untouched.  No y may alias an input of the same call.
+ *   Two kernels, no copies and no memsets (the problem table travels in the kernel arguments), so a captured call is
+ *   two kernel nodes: one re-order of every DISTINCT (weight, F, C_s) of the list into the workspace, one forward
+ *   over all tiles of all problems, heaviest problems first.  count = 0 does nothing. */
+typedef struct sd_dcn_pyramid_source {
+  const void* x;
+  const void* offset;
+  const void* weight;
+  const void* bias;
+  int C, H, W, kh, kw, pad, stride, dil, dgroup, num_group;
+} sd_dcn_pyramid_source;
+typedef struct sd_dcn_pyramid_problem {
+  void* y;
+  const void* residual;
+  int N, F, Ho, Wo, Hr, Wr, shift, num_sources;
+  sd_dcn_pyramid_source sources[2];
+} sd_dcn_pyramid_problem;
+size_t sd_deform_convolution_pyramid_fwd_workspace_bytes_f16(const sd_dcn_pyramid_problem* problems, int count);
+int sd_deform_convolution_pyramid_fwd_f16(const sd_dcn_pyramid_problem* problems, int count, void* workspace,
+                                          size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * _contrib_Proposal_v3  (mx.sym.contrib.Proposal_v3, models/FPN/builder.py:275-287) -- SURVEY 8(f)
  *   replaces ProposalGPUOp_v3::Forward  operator_cxx/contrib/proposal_v3.cu:428-638 (anchor grid

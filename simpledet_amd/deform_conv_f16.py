@@ -5,6 +5,11 @@ of `models/tridentnet/resnet_v*.py:85-90`).
     deform_conv_forward / deform_conv_backward   the `ops` functions of the same names for float16 tensors (float32
                                                  tensors go to `ops` unchanged)
     deform_conv                                  an autograd function over both
+    deform_conv_pyramid_forward / deform_conv_pyramid
+                                                 a list of independent forward problems in one launch, each with up
+                                                 to two sources summed in the accumulator and an optional upsampled
+                                                 residual (csrc/deform_pyramid_f16.hip); opt-in, the
+                                                 adapter does not use it
     install(mx)                                  after mxnet_plugin.install(mx): `mx.sym.contrib.DeformableConvolution`
                                                  builds a prop whose infer_type passes float16 through and whose
                                                  operator picks the entry points by the dtype of its data
@@ -22,9 +27,13 @@ tile, d_data from an fp16 dcol written and read once; d_weight and d_bias keep t
 
 It stays out of `ops.py` and of mxnet_plugin's tables, like sync_bn.py and free_anchor.py: their public surfaces are
 pinned."""
+import collections
+import ctypes
+
 import torch
 
 from . import ops
+from ._lib import SD_ERR_UNSUPPORTED, SimpleDetOpsError
 from ._mx_adapter import REQ, _call, _mx, _no_add, _ptr, _req, _sync, _wait, _ws, alias_ctor, drop_alias, put_alias, \
     register_ops
 from .ops import _chk, _dcn_out_hw, _req_of
@@ -136,6 +145,173 @@ def deform_conv(x, offset, weight, bias=None, pad=1, stride=1, dilate=1, num_def
     (deform_conv_backward)"""
     return _DeformConv.apply(x, offset, weight, bias, pad, stride, dilate, num_deformable_group, num_group,
                              bool(fused_weight_grad), bool(fused_input_grads))
+
+
+# ------------------------------------------------------------------- a pyramid of problems, one launch ----
+class _PyrSource(ctypes.Structure):
+    """struct sd_dcn_pyramid_source of include/simpledet_ops.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("x", "offset", "weight", "bias")] + \
+               [(k, ctypes.c_int) for k in ("C", "H", "W", "kh", "kw", "pad", "stride", "dil", "dgroup", "num_group")]
+
+
+class _PyrProblem(ctypes.Structure):
+    """struct sd_dcn_pyramid_problem"""
+    _fields_ = [("y", ctypes.c_void_p), ("residual", ctypes.c_void_p)] + \
+               [(k, ctypes.c_int) for k in ("N", "F", "Ho", "Wo", "Hr", "Wr", "shift", "num_sources")] + \
+               [("sources", _PyrSource * 2)]
+
+
+PyramidProblem = collections.namedtuple("PyramidProblem", "sources residual", defaults=(None,))
+
+
+def _problem(p):
+    """a problem as (sources, residual): sources a list of (x, offset, weight, bias, pad, stride, dilate,
+    num_deformable_group), residual None or (tensor, shift)"""
+    p = PyramidProblem(**p) if isinstance(p, dict) else PyramidProblem(*p)
+    if not p.sources:
+        raise ValueError("a pyramid problem needs at least one source")
+    return PyramidProblem([tuple(s) for s in p.sources], None if p.residual is None else tuple(p.residual))
+
+
+def _pyramid_shape(p):
+    """(N, F, Ho, Wo) of a problem, from its first source; every tensor of the problem checked against it"""
+    dims = None
+    for x, offset, weight, bias, pad, stride, dilate, dg in p.sources:
+        d, (Ho, Wo) = _geom(x, offset, weight, pad, stride, dilate, dg, 1, bias)
+        dims = dims or (d[0], d[4], Ho, Wo)   # (a source of another output size: the C call refuses it)
+        if (d[0], d[4]) != dims[:2]:
+            raise ValueError("sources of one problem must share N and num_filter")
+    if p.residual is not None:
+        r, shift = p.residual
+        _chk(r, "residual", torch.float16, ndim=4)
+        if tuple(r.shape[:2]) != dims[:2]:
+            raise ValueError("residual %s does not match the output's (N, F) = %s" % (tuple(r.shape), dims[:2]))
+    return dims
+
+
+def pyramid_call(problems, outs):
+    """sd_deform_convolution_pyramid_fwd_f16 on a list of _problem()s and their outputs, as it is: a list the entry
+    point refuses raises SimpleDetOpsError with the C code, before anything is launched"""
+    table = (_PyrProblem * len(problems))()
+    for q, p, y in zip(table, problems, outs):
+        N, F, Ho, Wo = _pyramid_shape(p)
+        _chk(y, "out", torch.float16, shape=(N, F, Ho, Wo))
+        q.y, q.N, q.F, q.Ho, q.Wo, q.num_sources = y.data_ptr(), N, F, Ho, Wo, len(p.sources)
+        if p.residual is not None:
+            r, shift = p.residual
+            q.residual, q.Hr, q.Wr, q.shift = r.data_ptr(), r.shape[2], r.shape[3], int(shift)
+        for s, (x, offset, weight, bias, pad, stride, dilate, dg) in zip(q.sources, p.sources):   # (the first two)
+            s.x, s.offset, s.weight = x.data_ptr(), offset.data_ptr(), weight.data_ptr()
+            s.bias = None if bias is None else bias.data_ptr()
+            (_, s.C, s.H, s.W), (s.kh, s.kw) = x.shape, weight.shape[2:]
+            s.pad, s.stride, s.dil, s.dgroup, s.num_group = int(pad), int(stride), int(dilate), int(dg), 1
+    ws = ops._ws(outs[0].device, None, "sd_deform_convolution_pyramid_fwd_workspace_bytes_f16", table, len(table))
+    ops._call("sd_deform_convolution_pyramid_fwd_f16", table, len(table), ws, ws.numel())
+
+
+def _upsampled(r, shift, Ho, Wo):
+    """the residual as the epilogue reads it: element (h >> shift, w >> shift), cropped from the origin"""
+    if shift:
+        r = r.repeat_interleave(2, 2).repeat_interleave(2, 3)
+    return r[:, :, :Ho, :Wo]
+
+
+def deform_conv_pyramid_forward(problems, out=None):
+    """A list of independent float16 DeformableConvolution problems in one launch (csrc/deform_pyramid_f16.hip, DESIGN
+    4.30).  A problem is a dict or PyramidProblem: sources=[(x, offset, weight, bias, pad, stride, dilate,
+    num_deformable_group), ...] (one or two, 3x3, summed in the fp32 accumulator), residual=None | (tensor, shift)
+    (read at (h >> shift, w >> shift): shift 1 is UpSampling(2, nearest) -> slice_like).  Returns the list of outputs
+    (out: a list of tensors to write), each rounded ONCE; a single-source problem without a residual has
+    deform_conv_forward's bits.  No output may be an input of the same call.
+    A list the entry point refuses as unsupported (more than 16 problems or 2 sources, a shape outside the native
+    kernel) runs as single deform_conv_forward calls plus float16 torch adds instead, which round per node."""
+    probs = [_problem(p) for p in problems]
+    if not probs:
+        return []
+    dims = [_pyramid_shape(p) for p in probs]
+    dev = probs[0].sources[0][0].device
+    if out is None:
+        out = [torch.empty(d, device=dev, dtype=torch.float16) for d in dims]
+    elif len(out) != len(probs):
+        raise ValueError("out must hold %d tensors, got %d" % (len(probs), len(out)))
+    try:
+        pyramid_call(probs, out)
+    except SimpleDetOpsError as e:
+        if e.code != SD_ERR_UNSUPPORTED:
+            raise
+        for p, y, (_, _, Ho, Wo) in zip(probs, out, dims):
+            acc = None
+            for x, offset, weight, bias, pad, stride, dilate, dg in p.sources:
+                t = deform_conv_forward(x, offset, weight, pad, stride, dilate, dg, bias=bias)
+                acc = t if acc is None else acc + t
+            if p.residual is not None:
+                acc = acc + _upsampled(p.residual[0], p.residual[1], Ho, Wo)
+            y.copy_(acc)
+    return list(out)
+
+
+def _d_residual(dy, shape, shift):
+    """the residual's gradient: the fp32 sum of the (<= 4) dy elements that read each element, rounded once; zero
+    where the crop left nothing"""
+    (Hr, Wr), (Ho, Wo) = shape[2:], dy.shape[2:]
+    d = torch.zeros(shape[:2] + (Hr << shift, Wr << shift), device=dy.device, dtype=torch.float32)
+    d[:, :, :Ho, :Wo] = dy
+    if shift:
+        d = d.view(shape[0], shape[1], Hr, 2, Wr, 2).sum((3, 5))
+    return d.half()
+
+
+class _DeformConvPyramid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, route, *flat):
+        ctx.spec, ctx.route = spec, route
+        ctx.save_for_backward(*flat)
+        ys = deform_conv_pyramid_forward(_unflatten(spec, flat))
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        flat, grads, at = ctx.saved_tensors, [], 0
+        for (sources, shift), dy in zip(ctx.spec, dys):
+            dy = dy.contiguous()
+            for pad, stride, dilate, dg, has_bias in sources:
+                x, offset, weight = flat[at:at + 3]
+                at += 4 if has_bias else 3
+                grads += deform_conv_backward(dy, x, offset, weight, pad, stride, dilate, dg, bias=has_bias, **ctx.route)
+            if shift is not None:
+                grads.append(_d_residual(dy, tuple(flat[at].shape), shift))
+                at += 1
+        return (None, None) + tuple(grads)
+
+
+def _unflatten(spec, flat):
+    probs, at = [], 0
+    for sources, shift in spec:
+        srcs = []
+        for pad, stride, dilate, dg, has_bias in sources:
+            x, offset, weight = flat[at:at + 3]
+            srcs.append((x, offset, weight, flat[at + 3] if has_bias else None, pad, stride, dilate, dg))
+            at += 4 if has_bias else 3
+        probs.append(PyramidProblem(srcs, None if shift is None else (flat[at], shift)))
+        at += shift is not None
+    return probs
+
+
+def deform_conv_pyramid(problems, fused_weight_grad=False, fused_input_grads=False):
+    """differentiable deform_conv_pyramid_forward -> tuple of outputs.  The backward adds no kernel: per source it is
+    deform_conv_backward(dy, ...) on the problem's dy (fused_weight_grad / fused_input_grads choose its route), so its
+    bits are the single call's; the residual's gradient is _d_residual."""
+    spec, flat = [], []
+    for p in (_problem(p) for p in problems):
+        sources = []
+        for x, offset, weight, bias, pad, stride, dilate, dg in p.sources:
+            flat += [x, offset, weight] + ([] if bias is None else [bias])
+            sources.append((pad, stride, dilate, dg, bias is not None))
+        if p.residual is not None:
+            flat.append(p.residual[0])
+        spec.append((sources, None if p.residual is None else int(p.residual[1])))
+    route = dict(fused_weight_grad=bool(fused_weight_grad), fused_input_grads=bool(fused_input_grads))
+    return _DeformConvPyramid.apply(spec, route, *flat)
 
 
 # ----------------------------------------------------------------------------------- MXNet adapter ----

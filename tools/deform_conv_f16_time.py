@@ -21,6 +21,11 @@ Data and offset gradients on the half operands (csrc/deform_igrad_f16.hip, DESIG
 sd_deform_convolution_bwd_f16_native with fused_weight_grad: (a) the whole backward; (b) d_data + d_offset alone (req
 null for the weight); (c) the parent's two timed a second time: the spread.  `--only-native` times just these and
 updates the rows of the existing file; `--only-igrad` runs the native d_data + d_offset alone (for a kernel trace).
+A pyramid of problems in one launch (csrc/deform_pyramid_f16.hip), the `pconv` rows: the deformable part
+of one PConv of the sepc neck (N = 2, C = F = 256, levels 100x168 .. 7x11, start_level 1) as (a) the 11 single calls
+plus the fp16 torch adds / interpolate(nearest) / crop a half graph runs today and (b) the two pyramid launches, eagerly
+and (b) as one captured graph; launch 2 alone against its eight single calls; (a) timed a second time in the same
+rotation: the spread.  `--only-pconv` times just these and updates the existing file.
 
 Shapes: the README's DCN row (16, 256, 50, 84) dg 4 -> 256, and the sepc neck's (2, 256, 100, 168) and
 (2, 256, 50, 84) at stride 1 and 2, dg 1, with a bias.  Every shape at the two offset spreads bench_ops.py's DCN row
@@ -154,8 +159,87 @@ def native_rows(sets, dy, shape, iters):
                 input_grads_speedup=round(t["parent_in"] / t["native_in"], 3))
 
 
+PCONV_LEVELS = ((100, 168), (50, 84), (25, 42), (13, 21), (7, 11))   # P3..P7 of 800 x 1333; start_level 1
+
+
+def pconv_inputs(seed, sigma, N=2, C=256):
+    """one PConv's deformable part (models/sepc/sepc_neck.py:PConvModule): x of five levels, the three shared weights
+    and biases, and the offsets of its 11 convolutions: sepc1 on x[1..4], sepc2 (stride 2) on x[0..3], sepc0 on x[2..4]"""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    r = lambda *s: torch.randn(s, device="cuda", generator=gen)   # noqa: E731
+    x = [r(N, C, h, w).half() for h, w in PCONV_LEVELS]
+    off = {k: {l: (r(N, 18, *PCONV_LEVELS[l + (k == 0)]) * sigma).half() for l in range(1, 5 - (k == 0))} for k in range(3)}
+    return dict(x=x, off=off, w=[(r(C, C, 3, 3) * 0.05).half() for _ in range(3)], b=[r(C).half() for _ in range(3)])
+
+
+def pconv_calls(s, l):
+    """the (sepc1, sepc2, sepc0) sources of output level l"""
+    src = lambda k, xl, stride: (s["x"][xl], s["off"][k][l], s["w"][k], s["b"][k], 1, stride, 1, 1)   # noqa: E731
+    return src(1, l, 1), src(2, l - 1, 2), (src(0, l + 1, 1) if l < 4 else None)
+
+
+def _single(v):
+    return d16.deform_conv_forward(v[0], v[1], v[2], v[4], v[5], v[6], v[7], bias=v[3])
+
+
+def pconv_graph_route(s):
+    """route (a), what a half graph runs today: 11 calls, the fp16 adds, UpSampling(nearest) -> slice_like"""
+    ys = []
+    for l in range(1, 5):
+        one, two, zero = pconv_calls(s, l)
+        t = _single(one) + _single(two)
+        if zero is not None:
+            up = torch.nn.functional.interpolate(_single(zero), scale_factor=2, mode="nearest")
+            t = t + up[:, :, :t.shape[2], :t.shape[3]]
+        ys.append(t)
+    return ys
+
+
+def pconv_launch1(s):
+    return d16.deform_conv_pyramid_forward([dict(sources=[pconv_calls(s, l)[2]]) for l in range(1, 4)])
+
+
+def pconv_launch2(s, res):
+    return d16.deform_conv_pyramid_forward([dict(sources=list(pconv_calls(s, l)[:2]),
+                                                 residual=(res[l - 1], 1) if l < 4 else None) for l in range(1, 5)])
+
+
+def pconv_rows(iters):
+    """route (a) against route (b) = the two pyramid launches, alternating on rotating input sets; (b) also as one
+    captured graph; launch 2 alone against its eight single calls; route (a) a second time: the run's own spread"""
+    rows = {}
+    for sigma in SIGMAS:
+        sets = [pconv_inputs(s, sigma) for s in range(SETS)]
+        res = [pconv_launch1(s) for s in sets]
+        graph, outs = capture(lambda s, _: pconv_launch2(s, pconv_launch1(s)), sets, None)
+        graph.replay()
+        torch.cuda.synchronize()
+        want = [pconv_graph_route(s) for s in sets]
+        diff = max(float((a.float() - b.float()).abs().max()) for o, w in zip(outs, want) for a, b in zip(o, w))
+        over = lambda fn: (lambda: [fn(s) for s in sets])   # noqa: E731
+        eight = lambda s: [_single(v) for l in range(1, 5) for v in pconv_calls(s, l)[:2]]   # noqa: E731
+        launch2_alone = lambda: [pconv_launch2(s, r) for s, r in zip(sets, res)]   # noqa: E731
+        t = time_alternating(dict(a=over(pconv_graph_route), b=over(lambda s: pconv_launch2(s, pconv_launch1(s))),
+                                  b_graph=graph.replay, a_again=over(pconv_graph_route), eight=over(eight),
+                                  launch2=launch2_alone), iters)
+        t = {key: v / SETS for key, v in t.items()}
+        spread = abs(t["a"] - t["a_again"])
+        rows["pconv/sigma%g" % sigma] = dict(
+            offset_sigma=sigma, levels=[list(v) for v in PCONV_LEVELS], N=2, C=256, F=256, start_level=1,
+            graph_route_ms=round(t["a"], 4), graph_route_again_ms=round(t["a_again"], 4),
+            pyramid_route_ms=round(t["b"], 4), pyramid_route_graph_ms=round(t["b_graph"], 4),
+            pyramid_over_graph_route=round(t["b"] / t["a"], 3),
+            pyramid_not_slower_within_spread=bool(t["b"] <= t["a"] + spread),
+            launch2_ms=round(t["launch2"], 4), launch2_eight_calls_ms=round(t["eight"], 4),
+            launch2_over_eight_calls=round(t["launch2"] / t["eight"], 3), max_abs_diff_between_routes=diff,
+            max_abs_y=max(float(b.float().abs().max()) for w in want for b in w))
+        print("pconv/sigma%g" % sigma, json.dumps(rows["pconv/sigma%g" % sigma]))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--only-pconv", action="store_true", help="the pyramid routes alone, into the file's `pconv` rows")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deform_conv_f16_time.json"))
     ap.add_argument("--only-fused", action="store_true", help="the fused weight gradient alone, readme_dcn, no file")
@@ -173,6 +257,14 @@ def main():
                 d16.deform_conv_backward(dy, *t[:3], 1, shape[6], 1, shape[5], req=("write", "write", "null"),
                                          fused_weight_grad=True, fused_input_grads=True)
         torch.cuda.synchronize()
+        return
+    if args.only_pconv:
+        with open(args.out) as f:
+            result = json.load(f)
+        result["pconv"] = pconv_rows(args.iters)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
         return
     if args.only_native:
         with open(args.out) as f:
@@ -260,6 +352,7 @@ def main():
                 weight_grad_speedup=round(tw["parent_dw"] / tw["fused_dw"], 3),
                 **native_rows(sets, dy, shape, args.native_iters))
             print(key, json.dumps(result["shapes"][key]))
+    result["pconv"] = pconv_rows(args.iters)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
