@@ -1796,6 +1796,58 @@ int sd_free_anchor_loss_bwd(const float* const* cls_ptrs_host, const float* cons
                             size_t workspace_bytes, float grad_scale, float* const* dcls_ptrs_host,
                             float* const* ddelta_ptrs_host, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The squeeze-and-excitation block  (se() of models/efficientnet/builder.py:17-27, imported by models/se/builder.py:6:
+ *   mean(axis=-1) -> mean(axis=-2) -> 1x1 conv -> relu6 -> 1x1 conv -> sigmoid -> broadcast_mul; behind every
+ *   bottleneck of SEv2ResNetV1bFPN, every MBConv of EfficientNet-B4..B7 and four times in MaskRcnnSe4convHead), fp32
+ *   and fp16, NCHW, forward and backward.  Additions only: the ABI version stays 12.  DESIGN 4.31.
+ *   replaces seven nodes forward (x read twice, written once) and about a dozen launches and eight tensor passes
+ *   backward by two kernels each way (one where an image fits in LDS) plus one small weight-gradient kernel.
+ *   x / y / dy / dx (N,C,HxW) contiguous; w1 (Cr,C), b1 (Cr) or NULL, w2 (C,Cr), b2 (C) or NULL: the 1x1 convolutions'
+ *   weights as matrices, in the element type of x, widened on load; gap (N,C), z1 (N,Cr), a (N,C), g (N,C) float32.
+ *   All arithmetic is float32, every step rounded on its own.
+ *   Forward:   gap[n,c] = (sum over the plane of x) / (float)HxW;  z1 = w1 gap + b1;  h = min(max(z1, 0), 6);
+ *              z2 = w2 h + b2;  a = 1 / (1 + expf(-z2));  y = x * a[n,c].  gap, z1 and a are outputs: the backward
+ *              reads them, so nothing of full size stays alive but x.
+ *   Backward:  s[n,c] = sum dy * x;  dz2 = s * (a * (1 - a));  dh = w2^T dz2;  dz1 = dh where 0 <= z1 <= 6, else 0
+ *              (upstream clip's inclusive rule);  g[n,c] = (w1^T dz1)[n,c] / (float)HxW;  dx = dy * a[n,c] + g[n,c];
+ *              dw2 = sum_n dz2 (x) h, db2 = sum_n dz2, dw1 = sum_n dz1 (x) gap, db1 = sum_n dz1, the images added in
+ *              order, float32 in both entry points.  g is an output (what dx was formed from); db1 / db2 may each be
+ *              NULL.  Everything is written (kWriteTo).
+ *   The *_f16 entry points take halves for x / y / dy / dx / w1 / b1 / w2 / b2 and round y / dx to half once.
+ *   Sums have a fixed order -- a thread's element in front of the first 16-byte boundary, its 16-byte vectors in order
+ *   (a vector's terms pairwise), its element behind; the wave butterfly; the waves and then a plane's chunks left to
+ *   right -- so two calls give equal bits; the order depends on the element type, the path and the pointer's phase,
+ *   never on which workgroup finishes last.  No floating-point atomics.  Pointers need element alignment only.
+ *   path: 0 automatic, 1 two-pass, 2 resident (one workgroup per image, the image held in LDS; SD_ERR_UNSUPPORTED
+ *   where (1024 + roundup(C, 4)) * 4 + roundup(C * HxW * element size, 16) bytes exceed 160 KB); automatic takes the
+ *   resident path where it fits.  split: workgroups per plane of the two-pass sums, 0 automatic (a wave per plane up to
+ *   4096 elements, else enough chunks of at least 8192 elements to fill the device).  Given equal a (and g), y (and dx)
+ *   have equal bits on both paths.
+ *   The workspace (sd_se_block_workspace_bytes, one size for both directions) needs no clearing: a kernel at the head
+ *   of a two-pass call clears the N tickets.  Kernels only, no host read, graph-capturable; the first resident call of
+ *   a process with more than 64 KB of LDS raises its kernel's limit (hipFuncSetAttribute): make it outside a capture.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a null pointer (b1, b2, db1, db2 excepted), a
+ *   pointer off its element alignment, N, C, Cr or HxW below 1, path outside 0..2, split outside 0..1024;
+ *   SD_ERR_UNSUPPORTED: C > 4096, Cr > 512, N*C*HxW > 2^31 - 1, path 2 on an image that does not fit;
+ *   SD_ERR_WORKSPACE: a NULL or too small workspace.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_se_block_workspace_bytes(int N, int C, int Cr, long HxW, int path, int split);
+int sd_se_block_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
+                    float* gap, float* z1, float* a, int N, int C, int Cr, long HxW, int path, int split,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int sd_se_block_bwd(const float* dy, const float* x, const float* gap, const float* z1, const float* a,
+                    const float* w1, const float* w2, float* dx, float* g, float* dw1, float* db1, float* dw2,
+                    float* db2, int N, int C, int Cr, long HxW, int path, int split, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int sd_se_block_fwd_f16(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y,
+                        float* gap, float* z1, float* a, int N, int C, int Cr, long HxW, int path, int split,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int sd_se_block_bwd_f16(const void* dy, const void* x, const float* gap, const float* z1, const float* a,
+                        const void* w1, const void* w2, void* dx, float* g, float* dw1, float* db1, float* dw2,
+                        float* db2, int N, int C, int Cr, long HxW, int path, int split, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
