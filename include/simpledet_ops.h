@@ -1848,6 +1848,81 @@ int sd_se_block_bwd_f16(const void* dy, const void* x, const float* gap, const f
                         float* db2, int N, int C, int Cr, long HxW, int path, int split, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pyramid batch norm  (SEPC's integrated batch norm, ibn_func of models/sepc/sepc_neck.py:112-119, with the caller's
+ *   relu of :108 and :50: reshape + Concat over the last axis, SyncBatchNorm on (N,C,1,sum HxW), L slice_axis,
+ *   L reshape_like and L relu), fp32 and fp16, NCHW.  Additions only: the ABI version stays 12.  DESIGN 4.32.
+ *   replaces nine tensor passes forward and about as many backward by three and five: batch norm whose reduction
+ *   domain is a LIST of 1..8 tensors, read in place and written in place, the activation in the same pass.
+ *   x / y / dy / dx: HOST arrays of L device pointers; level l is (N,C,HxW[l]) contiguous, HxW a host array.  N and C
+ *   are shared; n = N * sum_l HxW[l], the same on each of the W ranks.  gamma / beta / mean / var / moving_* / dgamma /
+ *   dbeta (C) float32.  g = fix_gamma ? 1 : gamma[c].  Every float32 step is rounded on its own.  T: the element type.
+ *     sd_pyramid_bn_stats      part (2,C): the mean of the rank's n elements of a channel and their biased variance
+ *                              about that mean.  Every level is read once.
+ *     sd_pyramid_bn_apply      parts (W,2,C) in rank order -> mean, var exactly as sd_sync_bn_apply combines them;
+ *                              inv = 1.0f / sqrtf(var + eps);  z = (g * (x - mean)) * inv + beta[c];  zt = (T)z;
+ *                              y = relu ? (zt > 0 ? zt : 0) : zt
+ *     sd_pyramid_bn_infer_fwd  a = g / sqrtf(moving_var + eps);  b = beta - (g * moving_mean) / sqrtf(moving_var + eps);
+ *                              z = a * x + b, then as above
+ *     sd_pyramid_bn_bwd_stats  dy' = dy; with relu, 0 wherever the forward STORED y <= 0: zt is recomputed from x, mean,
+ *                              var, gamma, beta with the forward's own expression and rounding to T (a z that underflows
+ *                              in fp16 is masked as well); y is no input.
+ *                              bpart (2,C): bpart[0,c] = sum dy', bpart[1,c] = sum dy' * (x - mean)
+ *     sd_pyramid_bn_bwd_apply  bparts (W,2,C), rank -> dx per level, dgamma, dbeta (NULL together: skipped) and the
+ *                              moving statistics (NULL together: skipped) by the rules of sd_sync_bn_bwd_apply with
+ *                              this n and dy' in the place of dy.
+ *   The *_f16 entry points take halves for x / y / dy / dx and compute in float32, rounding the result to half once:
+ *   the bits of cast -> the fp32 entry point -> cast (under relu the mask is taken on T: they part only where a
+ *   positive z underflows in fp16).  kAddTo is not provided.
+ *   Sums are defined on a level's items, the aligned groups of 8 elements of its flat index space, cut by the rows of
+ *   a channel (a partial head, whole items, a partial tail): no bit depends on the element type or on a pointer's
+ *   alignment.  16-byte accesses where every level pointer of the call is 16-byte aligned, element accesses otherwise
+ *   (element alignment suffices).  One launch per stage over all levels: levels are cut per channel into chunks of
+ *   8192 elements, a workgroup each; the smallest levels that fit 256 items per channel together are taken by one wave
+ *   per channel.  Partials carry their count and are merged in double by Chan's rule in a fixed order.  No
+ *   floating-point atomics, no memset, no copy, no host read; the level table travels in the kernel arguments, so a
+ *   captured call is kernel nodes only; every grid depends on the shapes alone.  The workspace
+ *   (sd_pyramid_bn_workspace_bytes, one size for every entry point) needs no clearing.
+ *   Checked before anything touches the device -- SD_ERR_INVALID_ARG: a negative size, W < 1, rank outside 0..W-1,
+ *   dgamma / dbeta or moving_mean / moving_var given half, a null pointer (a table or an entry of it), a pointer off
+ *   its element alignment; SD_ERR_UNSUPPORTED: L > 8, N*C*sum(HxW) > 2^31 - 1; SD_ERR_WORKSPACE: a NULL or too
+ *   small workspace.  L = 0, N = 0 or C = 0 succeed without a launch; a level with HxW[l] = 0 is left out.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sd_pyramid_bn_workspace_bytes(int N, int C, const long* HxW, int L);
+int sd_pyramid_bn_stats(const float* const* x, float* part, int N, int C, const long* HxW, int L, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int sd_pyramid_bn_apply(const float* const* x, const float* parts, int W, const float* gamma, const float* beta,
+                        float* const* y, float* mean, float* var, int N, int C, const long* HxW, int L, float eps,
+                        int fix_gamma, int relu, void* workspace, size_t workspace_bytes, void* stream);
+int sd_pyramid_bn_infer_fwd(const float* const* x, const float* gamma, const float* beta, const float* moving_mean,
+                            const float* moving_var, float* const* y, int N, int C, const long* HxW, int L, float eps,
+                            int fix_gamma, int relu, void* stream);
+int sd_pyramid_bn_bwd_stats(const float* const* dy, const float* const* x, const float* mean, const float* var,
+                            const float* gamma, const float* beta, float* bpart, int N, int C, const long* HxW, int L,
+                            float eps, int fix_gamma, int relu, void* workspace, size_t workspace_bytes, void* stream);
+int sd_pyramid_bn_bwd_apply(const float* const* dy, const float* const* x, const float* mean, const float* var,
+                            const float* gamma, const float* beta, const float* bparts, int W, int rank,
+                            float* const* dx, float* dgamma, float* dbeta, float* moving_mean, float* moving_var,
+                            float momentum, int N, int C, const long* HxW, int L, float eps, int fix_gamma, int relu,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int sd_pyramid_bn_stats_f16(const void* const* x, float* part, int N, int C, const long* HxW, int L, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int sd_pyramid_bn_apply_f16(const void* const* x, const float* parts, int W, const float* gamma, const float* beta,
+                            void* const* y, float* mean, float* var, int N, int C, const long* HxW, int L, float eps,
+                            int fix_gamma, int relu, void* workspace, size_t workspace_bytes, void* stream);
+int sd_pyramid_bn_infer_fwd_f16(const void* const* x, const float* gamma, const float* beta, const float* moving_mean,
+                                const float* moving_var, void* const* y, int N, int C, const long* HxW, int L,
+                                float eps, int fix_gamma, int relu, void* stream);
+int sd_pyramid_bn_bwd_stats_f16(const void* const* dy, const void* const* x, const float* mean, const float* var,
+                                const float* gamma, const float* beta, float* bpart, int N, int C, const long* HxW,
+                                int L, float eps, int fix_gamma, int relu, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int sd_pyramid_bn_bwd_apply_f16(const void* const* dy, const void* const* x, const float* mean, const float* var,
+                                const float* gamma, const float* beta, const float* bparts, int W, int rank,
+                                void* const* dx, float* dgamma, float* dbeta, float* moving_mean, float* moving_var,
+                                float momentum, int N, int C, const long* HxW, int L, float eps, int fix_gamma,
+                                int relu, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
