@@ -27,7 +27,7 @@
 //   -> cast): an L-level call equals L-1 chained two-level calls bit for bit (the fp16 backward where the inner
 //   g_l are NULL: a chain has to round S_l to half before an add outside it rounds again).
 //   No workspace, no atomics, no host read: graph-capturable, and two calls give equal bits.
-#include "common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
 
 namespace sd {
@@ -48,10 +48,6 @@ struct FtdArgs {
   unsigned tr, tc;            // tiles of a plane along its rows and columns
 };
 
-template <typename T>
-struct alignas(16) FtdItem {
-  T v[16 / sizeof(T)];
-};
 template <typename T>
 struct alignas(8) FtdHalfItem {
   T v[8 / sizeof(T)];
@@ -101,8 +97,7 @@ __device__ __forceinline__ void ftd_fwd_level(const T* cg, int cw, const T* cs, 
   const unsigned runlen = full ? (unsigned)rows * (unsigned)W : (unsigned)cols;
   for (int r = 0; r < nruns; ++r) {
     const unsigned f0 = (unsigned)(t.y0 + r) * (unsigned)W + (unsigned)t.x0;
-    unsigned head = (unsigned)(((16u - (unsigned)((uintptr_t)(out + f0) & 15u)) & 15u) / sizeof(T));
-    if (head > runlen) head = runlen;
+    const unsigned head = head_to_16(out + f0, runlen);
     const unsigned nv = (runlen - head) / V;
     const unsigned tail = runlen - head - nv * V;
     if (threadIdx.x < head + tail) {
@@ -116,12 +111,12 @@ __device__ __forceinline__ void ftd_fwd_level(const T* cg, int cw, const T* cs, 
     const bool latvec = ((uintptr_t)(lat + f0 + head) & 15u) == 0;
     for (unsigned i = threadIdx.x; i < nv; i += kFtdT) {
       const unsigned f = f0 + head + i * V;
-      FtdItem<T> a;
+      Vec16<T> a;
       if (latvec) {
-        a = *reinterpret_cast<const FtdItem<T>*>(lat + f);
+        a = vec16_ld(lat + f);
       } else {
 #pragma unroll
-        for (int k = 0; k < V; ++k) a.v[k] = lat[f + k];
+        for (int k = 0; k < V; ++k) a.e[k] = lat[f + k];
       }
       int y = (int)(f / (unsigned)W), x = (int)(f - (unsigned)y * (unsigned)W);
       T o[V];
@@ -148,12 +143,12 @@ __device__ __forceinline__ void ftd_fwd_level(const T* cg, int cw, const T* cs, 
 #pragma unroll
         for (int k = 0; k < V; ++k) {
           const T ce = c[k >> 1], co = c[(k + 1) >> 1];
-          o[k] = (odd ? co : ce) + a.v[k];
+          o[k] = (odd ? co : ce) + a.e[k];
         }
       } else {
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-          o[k] = coarse(y, x) + a.v[k];
+          o[k] = coarse(y, x) + a.e[k];
           if (++x == W) { x = 0; ++y; }   // (only a full-width run crosses a row end)
         }
       }
@@ -163,10 +158,10 @@ __device__ __forceinline__ void ftd_fwd_level(const T* cg, int cw, const T* cs, 
 #pragma unroll
         for (int k = 0; k < V; ++k) sp[k] = o[k];
       }
-      FtdItem<T> q;
+      Vec16<T> q;
 #pragma unroll
-      for (int k = 0; k < V; ++k) q.v[k] = o[k];
-      *reinterpret_cast<FtdItem<T>*>(out + f) = q;
+      for (int k = 0; k < V; ++k) q.e[k] = o[k];
+      vec16_st(out + f, q);
     }
   }
 }
@@ -223,9 +218,9 @@ __device__ __forceinline__ void ftd_bwd_level(const T* fg, const T* fs, const Ft
       } else {
         const T* p = fg + ((unsigned)y * (unsigned)fw + (unsigned)x);
         if (x + FV <= fw && ((uintptr_t)p & 15u) == 0) {
-          const FtdItem<T> q = *reinterpret_cast<const FtdItem<T>*>(p);
+          const Vec16<T> q = vec16_ld(p);
 #pragma unroll
-          for (int k = 0; k < FV; ++k) D[r][k] = (float)q.v[k];
+          for (int k = 0; k < FV; ++k) D[r][k] = (float)q.e[k];
         } else if (x + FV <= fw && ((uintptr_t)p & 7u) == 0) {
           const FtdHalfItem<T> q0 = *reinterpret_cast<const FtdHalfItem<T>*>(p);
           const FtdHalfItem<T> q1 = *reinterpret_cast<const FtdHalfItem<T>*>(p + CO);
@@ -312,8 +307,7 @@ __global__ __launch_bounds__(kFtdT) void ftd_bwd_kernel(FtdArgs a) {
 template <typename T>
 __global__ __launch_bounds__(kFtdT) void ftd_copy_kernel(const T* src, T* dst, unsigned n) {
   constexpr unsigned V = 16 / sizeof(T);
-  unsigned head = (unsigned)(((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u) / sizeof(T));
-  if (head > n) head = n;
+  const unsigned head = head_to_16(dst, n);
   const unsigned nv = (n - head) / V, tail = n - head - nv * V;
   if (blockIdx.x == 0 && threadIdx.x < head + tail) {
     const unsigned k = threadIdx.x < head ? threadIdx.x : n - tail + (threadIdx.x - head);
@@ -322,14 +316,14 @@ __global__ __launch_bounds__(kFtdT) void ftd_copy_kernel(const T* src, T* dst, u
   const bool vec = ((uintptr_t)(src + head) & 15u) == 0;
   for (unsigned i = blockIdx.x * kFtdT + threadIdx.x; i < nv; i += gridDim.x * kFtdT) {
     const unsigned e = head + i * V;
-    FtdItem<T> q;
+    Vec16<T> q;
     if (vec) {
-      q = *reinterpret_cast<const FtdItem<T>*>(src + e);
+      q = vec16_ld(src + e);
     } else {
 #pragma unroll
-      for (unsigned k = 0; k < V; ++k) q.v[k] = src[e + k];
+      for (unsigned k = 0; k < V; ++k) q.e[k] = src[e + k];
     }
-    *reinterpret_cast<FtdItem<T>*>(dst + e) = q;
+    vec16_st(dst + e, q);
   }
 }
 
@@ -409,7 +403,7 @@ static int ftd_fwd(const void* top, const void* const* lateral, void* const* out
   if (int e = ftd_check_ranges(in, L, ou, L - 1, sizeof(T))) return e;
   const unsigned grid = (unsigned)((long)N * C * a.tr * a.tc);
   hipLaunchKernelGGL(ftd_fwd_kernel<T>, dim3(grid), dim3(kFtdT), 0, (hipStream_t)stream, a);
-  note_dispatch("sd::ftd_fwd_kernel<%s> L=%d grid=%u tile=%dx%d tiles=%ux%u", sizeof(T) == 4 ? "f32" : "f16", L, grid,
+  note_dispatch("sd::ftd_fwd_kernel<%s> L=%d grid=%u tile=%dx%d tiles=%ux%u", elem_type_name<T>(), L, grid,
                 a.BR, a.BC, a.tr, a.tc);
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -447,7 +441,7 @@ static int ftd_bwd(const void* const* g, void* d_top, void* const* d_lateral, in
     hipLaunchKernelGGL(ftd_copy_kernel<T>, dim3(cgrid), dim3(kFtdT), 0, st, static_cast<const T*>(a.in[L - 1]), finest,
                        n);
   }
-  note_dispatch("sd::ftd_bwd_kernel<%s> L=%d grid=%u tile=%dx%d tiles=%ux%u%s", sizeof(T) == 4 ? "f32" : "f16", L,
+  note_dispatch("sd::ftd_bwd_kernel<%s> L=%d grid=%u tile=%dx%d tiles=%ux%u%s", elem_type_name<T>(), L,
                 grid, a.BR, a.BC, a.tr, a.tc, finest ? " + sd::ftd_copy_kernel" : "");
   SD_LAUNCH_CHECK();
   return SD_OK;

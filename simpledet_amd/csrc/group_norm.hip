@@ -32,9 +32,8 @@
 // left to right, the partials in index order): no floating-point atomics anywhere, two calls give equal bits.
 // Every workspace word that is read was written by a kernel of the same call: nothing to clear, no memset node.
 #include "common.h"
-#include "wg_common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
-#include <math.h>
 #include <type_traits>
 
 namespace sd {
@@ -150,13 +149,6 @@ struct GnDx {
   }
 };
 
-// sum over the TG threads that share a group: the wave's butterfly, then (TG == 256) the four wave results in
-// order.  `slot`: four floats of LDS that no other reduction in flight uses.
-template <int TG>
-__device__ __forceinline__ float gn_group_sum(float v, float* slot) {
-  if constexpr (TG == kWave) return wave_sum_f32(v);
-  else return block_sum_f32<TG, false>(v, slot);   // (no barrier behind the read: every reduction in flight has its own slot)
-}
 template <int TG>
 __device__ __forceinline__ void gn_group_sync() {
   if (TG == kWave) wave_lds_sync(); else __syncthreads();
@@ -169,12 +161,12 @@ __device__ __forceinline__ void gn_moments(const Item (&v)[PER], unsigned t, uns
   float s = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k) s += gn_hsum(v[k]);
-  mean = gn_group_sum<TG>(s, red) / cnt;
+  mean = group_sum_f32<TG>(s, red) / cnt;
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k)
     if (t + k * TG < items) q += gn_sq(v[k], mean);
-  m2 = gn_group_sum<TG>(q, red + 4);
+  m2 = group_sum_f32<TG>(q, red + 4);
 }
 
 template <int TG, int PER, int MODE>
@@ -232,16 +224,6 @@ __global__ __launch_bounds__(kGnT) void gn_fwd_partial_kernel(GnArgs a) {
   if (threadIdx.x == 0) a.part[blockIdx.x] = make_float2(mean, m2);
 }
 
-// Chan, Golub, LeVeque: (na, ma, Ma) + (nb, mb, Mb)
-__device__ __forceinline__ void gn_merge(double& na, double& ma, double& Ma, double nb, double mb, double Mb) {
-  if (nb == 0.0) return;
-  if (na == 0.0) { na = nb; ma = mb; Ma = Mb; return; }
-  const double n = na + nb, d = mb - ma;
-  ma = ma + d * (nb / n);
-  Ma = Ma + Mb + d * d * (na * nb / n);
-  na = n;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(kGnT) void gn_fwd_combine_kernel(GnArgs a) {
   const unsigned lane = threadIdx.x & (kWave - 1);
@@ -254,13 +236,9 @@ __global__ __launch_bounds__(kGnT) void gn_fwd_combine_kernel(GnArgs a) {
     const unsigned first = s * kGnChunk;
     const unsigned items = a.ipg - first < (unsigned)kGnChunk ? a.ipg - first : (unsigned)kGnChunk;
     const float2 v = p[s];
-    gn_merge(n, m, M, (double)(items * per), (double)v.x, (double)v.y);
+    chan_merge(n, m, M, (double)(items * per), (double)v.x, (double)v.y);
   }
-  // lanes in a fixed tree: lane l takes lane l + off; lane 0 ends with the whole group
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const double nb = __shfl_down(n, off), mb = __shfl_down(m, off), Mb = __shfl_down(M, off);
-    if (lane + off < (unsigned)kWave) gn_merge(n, m, M, nb, mb, Mb);
-  }
+  wave_tree_chan(lane, n, m, M);   // lane 0 ends with the whole group
   if (lane == 0) {
     a.mu[ng] = (float)m;
     a.rsig[ng] = 1.0f / sqrtf((float)(M / n) + a.eps);
@@ -327,7 +305,7 @@ __global__ __launch_bounds__(kGnT) void gn_bwd_small_kernel(GnArgs a) {
       if (a.table) { ia[i] = pa; ib[i] = pb; }
     }
   }
-  const float ds = gn_group_sum<TG>(sa, red), db = gn_group_sum<TG>(sb, red + 4);
+  const float ds = group_sum_f32<TG>(sa, red), db = group_sum_f32<TG>(sb, red + 4);
   const GnDx rule(mu, rsig, ds, db, a.n);
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
@@ -382,8 +360,8 @@ __global__ __launch_bounds__(kGnT) void gn_bwd_rows_kernel(GnArgs a) {
     sa += gn_dot(g0, x0, mu);
     sb += gn_hsum(g0);
   }
-  sa = gn_group_sum<TG>(sa, red);
-  sb = gn_group_sum<TG>(sb, red + 4);
+  sa = group_sum_f32<TG>(sa, red);
+  sb = group_sum_f32<TG>(sb, red + 4);
   if (t == 0) {
     a.table[2 * (size_t)row] = sa;
     a.table[2 * (size_t)row + 1] = sb;

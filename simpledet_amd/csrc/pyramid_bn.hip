@@ -41,8 +41,10 @@
 // all of them, the chunks of the largest level first, the wave units (four channels per workgroup) last.
 //   pbn_reduce_kernel       a unit -> (count, mean, M2 about its own mean), or (sum dy', sum dy' (x - mean))
 //   pbn_stats_merge_kernel  a wave per channel: Chan's rule for unequal counts, in double, in a fixed order
-//   pbn_bwd_merge_kernel    a wave per channel: the partial sums in double, in a fixed order
-//   pbn_fwd_coef_kernel / pbn_bwd_coef_kernel   a thread per channel: the combine over the ranks, the coefficients
+//   bn_bwd_merge_kernel     a wave per channel: the partial sums in double, in a fixed order
+//   bn_fwd_coef_kernel / bn_bwd_coef_kernel   a thread per channel: the combine over the ranks, the coefficients
+//                           (these three are norm_common.h's, the ones sync_bn.hip launches; so are the merge and
+//                           the sums)
 //   pbn_map_kernel          the element rules, flat over each level, a thread per item.  An item inside one row
 //                           takes one coefficient; an item that straddles rows (any HxW_l % 8 != 0) takes its
 //                           channel per element.  Both read a C x float4 table in LDS (two tables for the backward
@@ -50,10 +52,8 @@
 // No floating-point atomics, no memset, no copy, no host read: every workspace word that is read was written by a
 // kernel of the same call, and every grid depends on the shapes alone.
 #include "common.h"
-#include "wg_common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
-#include <math.h>
-#include <initializer_list>
 
 namespace sd {
 namespace {
@@ -102,21 +102,11 @@ struct PbnArgs {
   int fix_gamma, relu;
 };
 
-struct alignas(16) PbnH8 { _Float16 h[8]; };
-
 // elements [lo, hi) of the item [e0, e0 + 8) of a level; 0 outside
 template <typename T, bool VEC>
 __device__ __forceinline__ void pbn_ld(const T* p, unsigned e0, unsigned lo, unsigned hi, float (&v)[8]) {
   if (VEC && hi - lo == 8u) {
-    if constexpr (sizeof(T) == 4) {
-      const float4 f0 = reinterpret_cast<const float4*>(p + e0)[0], f1 = reinterpret_cast<const float4*>(p + e0)[1];
-      v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w;
-      v[4] = f1.x; v[5] = f1.y; v[6] = f1.z; v[7] = f1.w;
-    } else {
-      const PbnH8 h = *reinterpret_cast<const PbnH8*>(p + e0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = (float)h.h[k];
-    }
+    vec16_ld_f32(p + e0, v);
     return;
   }
 #pragma unroll
@@ -130,35 +120,12 @@ __device__ __forceinline__ void pbn_ld(const T* p, unsigned e0, unsigned lo, uns
 template <typename T, bool VEC>
 __device__ __forceinline__ void pbn_st(T* p, unsigned e0, unsigned cnt, const float (&v)[8]) {
   if (VEC && cnt == 8u) {
-    if constexpr (sizeof(T) == 4) {
-      reinterpret_cast<float4*>(p + e0)[0] = make_float4(v[0], v[1], v[2], v[3]);
-      reinterpret_cast<float4*>(p + e0)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-      PbnH8 h;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) h.h[k] = (_Float16)v[k];
-      *reinterpret_cast<PbnH8*>(p + e0) = h;
-    }
+    vec16_st_f32(p + e0, v);
     return;
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k)
     if ((unsigned)k < cnt) p[e0 + k] = (T)v[k];
-}
-
-// the sum of an item's eight terms, pairwise
-__device__ __forceinline__ float pbn_tree(float (&f)[8]) {
-#pragma unroll
-  for (int w = 1; w < 8; w *= 2)
-#pragma unroll
-    for (int j = 0; j < 8; j += 2 * w) f[j] = f[j] + f[j + w];
-  return f[0];
-}
-
-template <int TG>
-__device__ __forceinline__ float pbn_group_sum(float v, float* slot) {
-  if constexpr (TG == kWave) return wave_sum_f32(v);
-  else return block_sum_f32<TG, false>(v, slot);
 }
 
 // the forward's stored value: z rounded to T, then the ReLU
@@ -234,11 +201,11 @@ __device__ __forceinline__ void pbn_unit(const PbnArgs& a, unsigned c, unsigned 
       float f[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) f[i] = xv[k][i];
-      sm += pbn_tree(f);
+      sm += tree_sum(f);
       cn += (float)(hi8[k] - lo8[k]);
     }
-    sm = pbn_group_sum<TG>(sm, red);
-    cn = pbn_group_sum<TG>(cn, red + 4);       // (whole numbers below 2^24: exact)
+    sm = group_sum_f32<TG>(sm, red);
+    cn = group_sum_f32<TG>(cn, red + 4);       // (whole numbers below 2^24: exact)
     const float mean = cn > 0.f ? sm / cn : 0.f;
     float q2 = 0.f;
 #pragma unroll
@@ -249,9 +216,9 @@ __device__ __forceinline__ void pbn_unit(const PbnArgs& a, unsigned c, unsigned 
         const float d = xv[k][i] - mean;
         f[i] = (i >= lo8[k] && i < hi8[k]) ? d * d : 0.f;
       }
-      q2 += pbn_tree(f);
+      q2 += tree_sum(f);
     }
-    const float m2 = pbn_group_sum<TG>(q2, red + 8);
+    const float m2 = group_sum_f32<TG>(q2, red + 8);
     if (t == 0) static_cast<float4*>(a.partial)[(size_t)c * a.S + pidx] = make_float4(cn, mean, m2, 0.f);
   } else {
     const float mean = a.mean[c];
@@ -276,11 +243,11 @@ __device__ __forceinline__ void pbn_unit(const PbnArgs& a, unsigned c, unsigned 
         f[i] = dy;
         h[i] = dy * d;
       }
-      sg += pbn_tree(f);
-      sp += pbn_tree(h);
+      sg += tree_sum(f);
+      sp += tree_sum(h);
     }
-    sg = pbn_group_sum<TG>(sg, red);
-    sp = pbn_group_sum<TG>(sp, red + 4);
+    sg = group_sum_f32<TG>(sg, red);
+    sp = group_sum_f32<TG>(sp, red + 4);
     if (t == 0) static_cast<float2*>(a.partial)[(size_t)c * a.S + pidx] = make_float2(sg, sp);
   }
 }
@@ -305,16 +272,6 @@ __global__ __launch_bounds__(kPbnT) void pbn_reduce_kernel(PbnArgs a) {
   }
 }
 
-// Chan, Golub, LeVeque for unequal counts: (na, ma, Ma) + (nb, mb, Mb)
-__device__ __forceinline__ void pbn_chan(double& na, double& ma, double& Ma, double nb, double mb, double Mb) {
-  if (nb == 0.0) return;
-  if (na == 0.0) { na = nb; ma = mb; Ma = Mb; return; }
-  const double n = na + nb, d = mb - ma;
-  ma = ma + d * (nb / n);
-  Ma = Ma + Mb + d * d * (na * nb / n);
-  na = n;
-}
-
 // a wave per channel: lanes stride its S partials, then a fixed tree over the lanes
 __global__ __launch_bounds__(kPbnT) void pbn_stats_merge_kernel(const float4* partial, float* out, unsigned C,
                                                                 unsigned S) {
@@ -325,91 +282,12 @@ __global__ __launch_bounds__(kPbnT) void pbn_stats_merge_kernel(const float4* pa
   double n = 0.0, m = 0.0, M = 0.0;
   for (unsigned s = lane; s < S; s += kWave) {
     const float4 v = p[s];
-    pbn_chan(n, m, M, (double)v.x, (double)v.y, (double)v.z);
+    chan_merge(n, m, M, (double)v.x, (double)v.y, (double)v.z);
   }
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const double nb = __shfl_down(n, off), mb = __shfl_down(m, off), Mb = __shfl_down(M, off);
-    if (lane + off < (unsigned)kWave) pbn_chan(n, m, M, nb, mb, Mb);
-  }
+  wave_tree_chan(lane, n, m, M);
   if (lane == 0) {
     out[c] = (float)m;
     out[C + c] = (float)(M / n);
-  }
-}
-
-__global__ __launch_bounds__(kPbnT) void pbn_bwd_merge_kernel(const float2* partial, float* out, unsigned C,
-                                                              unsigned S) {
-  const unsigned lane = threadIdx.x & (kWave - 1);
-  const unsigned c = blockIdx.x * (kPbnT / kWave) + threadIdx.x / kWave;
-  if (c >= C) return;
-  const float2* p = partial + (size_t)c * S;
-  double sg = 0.0, sp = 0.0;
-  for (unsigned s = lane; s < S; s += kWave) {
-    const float2 v = p[s];
-    sg += (double)v.x;
-    sp += (double)v.y;
-  }
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const double gb = __shfl_down(sg, off), pb = __shfl_down(sp, off);
-    if (lane + off < (unsigned)kWave) { sg += gb; sp += pb; }
-  }
-  if (lane == 0) {
-    out[c] = (float)sg;
-    out[C + c] = (float)sp;
-  }
-}
-
-// a thread per channel: the combine over the ranks (double, rank order), mean / var, (mean, inv, g, beta)
-__global__ __launch_bounds__(kPbnT) void pbn_fwd_coef_kernel(const float* parts, int W, const float* gamma,
-                                                             const float* beta, float* mean, float* var, float4* coef,
-                                                             unsigned C, float eps, int fix_gamma) {
-  const unsigned c = blockIdx.x * kPbnT + threadIdx.x;
-  if (c >= C) return;
-  double sm = 0.0;
-  for (int r = 0; r < W; ++r) sm += (double)parts[((size_t)r * 2) * C + c];
-  const double m = sm / (double)W;
-  double sv = 0.0;
-  for (int r = 0; r < W; ++r) {
-    const double d = (double)parts[((size_t)r * 2) * C + c] - m;
-    sv += (double)parts[((size_t)r * 2 + 1) * C + c] + d * d;
-  }
-  const double v = sv / (double)W;
-  const float m32 = (float)m, v32 = (float)v;
-  mean[c] = m32;
-  var[c] = v32;
-  coef[c] = make_float4(m32, 1.0f / sqrtf(v32 + eps), fix_gamma ? 1.0f : gamma[c], beta[c]);
-}
-
-// a thread per channel: the sums over the ranks, (a, b, c, mean) of the element rule and the forward's coefficients
-// for its mask, the parameter gradients of this rank and the moving statistics
-__global__ __launch_bounds__(kPbnT) void pbn_bwd_coef_kernel(const float* bparts, int W, int rank, const float* mean,
-                                                             const float* var, const float* gamma, const float* beta,
-                                                             float* dgamma, float* dbeta, float* mmean, float* mvar,
-                                                             float momentum, float4* coef, float4* coef2, unsigned C,
-                                                             double wn, float eps, int fix_gamma) {
-  const unsigned c = blockIdx.x * kPbnT + threadIdx.x;
-  if (c >= C) return;
-  double SG = 0.0, SP = 0.0;
-  for (int r = 0; r < W; ++r) {
-    SG += (double)bparts[((size_t)r * 2) * C + c];
-    SP += (double)bparts[((size_t)r * 2 + 1) * C + c];
-  }
-  const float sg = (float)(SG / wn), sp = (float)(SP / wn);
-  const float mu = mean[c], vr = var[c];
-  const float g = fix_gamma ? 1.0f : gamma[c];
-  const float inv = 1.0f / sqrtf(vr + eps);
-  const float ka = g * inv;
-  const float kb = -(g * sp) * ((inv * inv) * inv);
-  const float kc = -(g * sg) * inv;
-  coef[c] = make_float4(ka, kb, kc, mu);
-  coef2[c] = make_float4(mu, inv, g, beta[c]);
-  if (dgamma) {
-    dbeta[c] = bparts[((size_t)rank * 2) * C + c];
-    dgamma[c] = fix_gamma ? 0.0f : bparts[((size_t)rank * 2 + 1) * C + c] * inv;
-  }
-  if (mmean) {
-    mmean[c] = mmean[c] * momentum + mu * (1.0f - momentum);
-    mvar[c] = mvar[c] * momentum + vr * (1.0f - momentum);
   }
 }
 
@@ -585,11 +463,6 @@ static PbnWs pbn_carve(const PbnPlan& p, void* workspace) {
 }
 static size_t pbn_need(const PbnPlan& p) { return 256 + pbn_carve(p, nullptr).need; }
 
-#define PBN_WORKSPACE(p, name)                                                                              \
-  if (!(workspace && workspace_bytes >= pbn_need(p)))                                                       \
-    return fail(SD_ERR_WORKSPACE, name " workspace too small: %zu < %zu bytes",                           \
-                workspace ? workspace_bytes : (size_t)0, pbn_need(p))
-
 // Sets the plan's level pointers from the caller's tables (in the caller's order; `dy` / `y` may be null tables).
 // -> 0, or 1: a null pointer, 2: a pointer off its element alignment.  *vec: all of them are 16-byte aligned.
 static int pbn_tables(PbnPlan& p, size_t esz, const void* const* x, const void* const* dy, void* const* y,
@@ -617,27 +490,19 @@ static int pbn_tables(PbnPlan& p, size_t esz, const void* const* x, const void* 
     SD_REQUIRE(e_ != 2, "a pointer is not aligned to its elements");                        \
   } while (0)
 
-static bool pbn_aligned4(std::initializer_list<const void*> ps) {
-  for (const void* q : ps)
-    if ((uintptr_t)q % 4) return false;
-  return true;
-}
-
-template <typename T> static const char* pbn_tn() { return sizeof(T) == 4 ? "f32" : "f16"; }
-
 template <typename T, bool BWD>
 static void pbn_reduce(const PbnPlan& p, bool vec, float* out, void* partial, hipStream_t st) {
   const PbnArgs& a = p.a;
   if (vec) hipLaunchKernelGGL((pbn_reduce_kernel<T, true, BWD>), dim3(p.rgrid), dim3(kPbnT), 0, st, a);
   else hipLaunchKernelGGL((pbn_reduce_kernel<T, false, BWD>), dim3(p.rgrid), dim3(kPbnT), 0, st, a);
   const dim3 mgrid(cdiv(a.C, kPbnT / kWave));
-  if (BWD) hipLaunchKernelGGL(pbn_bwd_merge_kernel, mgrid, dim3(kPbnT), 0, st, static_cast<const float2*>(partial), out,
+  if (BWD) hipLaunchKernelGGL(bn_bwd_merge_kernel<kPbnT>, mgrid, dim3(kPbnT), 0, st, static_cast<const float2*>(partial), out,
                               a.C, a.S);
   else hipLaunchKernelGGL(pbn_stats_merge_kernel, mgrid, dim3(kPbnT), 0, st, static_cast<const float4*>(partial), out,
                           a.C, a.S);
   note_dispatch("sd::pbn_reduce_kernel<%s,%s,%s> %u levels, %u in the wave group, %u units per channel + sd::%s",
-                pbn_tn<T>(), vec ? "vec" : "narrow", BWD ? "bwd" : "stats", a.L, a.L - a.nbig, a.S,
-                BWD ? "pbn_bwd_merge_kernel" : "pbn_stats_merge_kernel");
+                elem_type_name<T>(), vec ? "vec" : "narrow", BWD ? "bwd" : "stats", a.L, a.L - a.nbig, a.S,
+                BWD ? "bn_bwd_merge_kernel" : "pbn_stats_merge_kernel");
 }
 
 template <typename T, int KIND>
@@ -647,7 +512,7 @@ static void pbn_map(const PbnPlan& p, bool vec, hipStream_t st, const char* lead
   const size_t lds = (size_t)nl * sizeof(float4) * (KIND == kPbnBwd && a.relu ? 2 : 1);
   if (vec) hipLaunchKernelGGL((pbn_map_kernel<T, true, KIND>), dim3(p.mgrid), dim3(kPbnT), lds, st, a);
   else hipLaunchKernelGGL((pbn_map_kernel<T, false, KIND>), dim3(p.mgrid), dim3(kPbnT), lds, st, a);
-  note_dispatch("%ssd::pbn_map_kernel<%s,%s,%s%s> %u levels", lead, pbn_tn<T>(), vec ? "vec" : "narrow",
+  note_dispatch("%ssd::pbn_map_kernel<%s,%s,%s%s> %u levels", lead, elem_type_name<T>(), vec ? "vec" : "narrow",
                 KIND == kPbnFwd ? "fwd" : KIND == kPbnBwd ? "bwd" : "infer", a.relu ? ",relu" : "", a.L);
 }
 
@@ -660,8 +525,8 @@ static int pbn_stats(const void* const* x, float* part, int N, int C, const long
   bool vec = false;
   PBN_TABLES(p, sizeof(T), x, nullptr, nullptr, false, false, &vec);
   SD_REQUIRE(part, "null pointer");
-  SD_REQUIRE(pbn_aligned4({part}), "a pointer is not aligned to its elements");
-  PBN_WORKSPACE(p, "pyramid_bn_stats");
+  SD_REQUIRE(ptrs_aligned(4, {part}), "a pointer is not aligned to its elements");
+  if (int e = workspace_check(workspace, workspace_bytes, pbn_need(p), "pyramid_bn_stats")) return e;
   p.a.partial = pbn_carve(p, workspace).partial;
   pbn_reduce<T, false>(p, vec, part, p.a.partial, (hipStream_t)stream);
   SD_LAUNCH_CHECK();
@@ -679,15 +544,15 @@ static int pbn_apply(const void* const* x, const float* parts, int W, const floa
   bool vec = false;
   PBN_TABLES(p, sizeof(T), x, nullptr, y, false, true, &vec);
   SD_REQUIRE(parts && gamma && beta && mean && var, "null pointer");
-  SD_REQUIRE(pbn_aligned4({parts, gamma, beta, mean, var}), "a pointer is not aligned to its elements");
-  PBN_WORKSPACE(p, "pyramid_bn_apply");
+  SD_REQUIRE(ptrs_aligned(4, {parts, gamma, beta, mean, var}), "a pointer is not aligned to its elements");
+  if (int e = workspace_check(workspace, workspace_bytes, pbn_need(p), "pyramid_bn_apply")) return e;
   hipStream_t st = (hipStream_t)stream;
   const PbnWs ws = pbn_carve(p, workspace);
-  hipLaunchKernelGGL(pbn_fwd_coef_kernel, dim3(cdiv(C, kPbnT)), dim3(kPbnT), 0, st, parts, W, gamma, beta, mean, var,
+  hipLaunchKernelGGL(bn_fwd_coef_kernel<kPbnT>, dim3(cdiv(C, kPbnT)), dim3(kPbnT), 0, st, parts, W, gamma, beta, mean, var,
                      ws.coef, (unsigned)C, eps, fix_gamma);
   p.a.coef = ws.coef;
   p.a.relu = relu != 0;
-  pbn_map<T, kPbnFwd>(p, vec, st, "sd::pbn_fwd_coef_kernel + ");
+  pbn_map<T, kPbnFwd>(p, vec, st, "sd::bn_fwd_coef_kernel + ");
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -702,7 +567,7 @@ static int pbn_infer(const void* const* x, const float* gamma, const float* beta
   bool vec = false;
   PBN_TABLES(p, sizeof(T), x, nullptr, y, false, true, &vec);
   SD_REQUIRE(gamma && beta && mmean && mvar, "null pointer");
-  SD_REQUIRE(pbn_aligned4({gamma, beta, mmean, mvar}), "a pointer is not aligned to its elements");
+  SD_REQUIRE(ptrs_aligned(4, {gamma, beta, mmean, mvar}), "a pointer is not aligned to its elements");
   p.a.gamma = gamma; p.a.beta = beta; p.a.mmean = mmean; p.a.mvar = mvar;
   p.a.eps = eps; p.a.fix_gamma = fix_gamma; p.a.relu = relu != 0;
   pbn_map<T, kPbnInfer>(p, vec, (hipStream_t)stream, "");
@@ -720,8 +585,8 @@ static int pbn_bwd_stats(const void* const* dy, const void* const* x, const floa
   bool vec = false;
   PBN_TABLES(p, sizeof(T), x, dy, nullptr, true, false, &vec);
   SD_REQUIRE(mean && var && gamma && beta && bpart, "null pointer");
-  SD_REQUIRE(pbn_aligned4({mean, var, gamma, beta, bpart}), "a pointer is not aligned to its elements");
-  PBN_WORKSPACE(p, "pyramid_bn_bwd_stats");
+  SD_REQUIRE(ptrs_aligned(4, {mean, var, gamma, beta, bpart}), "a pointer is not aligned to its elements");
+  if (int e = workspace_check(workspace, workspace_bytes, pbn_need(p), "pyramid_bn_bwd_stats")) return e;
   p.a.partial = pbn_carve(p, workspace).partial;
   p.a.mean = mean; p.a.var = var; p.a.gamma = gamma; p.a.beta = beta;
   p.a.eps = eps; p.a.fix_gamma = fix_gamma; p.a.relu = relu != 0;
@@ -747,17 +612,17 @@ static int pbn_bwd_apply(const void* const* dy, const void* const* x, const floa
   bool vec = false;
   PBN_TABLES(p, sizeof(T), x, dy, dx, true, true, &vec);
   SD_REQUIRE(mean && var && gamma && beta && bparts, "null pointer");
-  SD_REQUIRE(pbn_aligned4({mean, var, gamma, beta, bparts, dgamma, dbeta, mmean, mvar}),
+  SD_REQUIRE(ptrs_aligned(4, {mean, var, gamma, beta, bparts, dgamma, dbeta, mmean, mvar}),
              "a pointer is not aligned to its elements");
-  PBN_WORKSPACE(p, "pyramid_bn_bwd_apply");
+  if (int e = workspace_check(workspace, workspace_bytes, pbn_need(p), "pyramid_bn_bwd_apply")) return e;
   hipStream_t st = (hipStream_t)stream;
   const PbnWs ws = pbn_carve(p, workspace);
-  hipLaunchKernelGGL(pbn_bwd_coef_kernel, dim3(cdiv(C, kPbnT)), dim3(kPbnT), 0, st, bparts, W, rank, mean, var, gamma,
+  hipLaunchKernelGGL(bn_bwd_coef_kernel<kPbnT>, dim3(cdiv(C, kPbnT)), dim3(kPbnT), 0, st, bparts, W, rank, mean, var, gamma,
                      beta, dgamma, dbeta, mmean, mvar, momentum, ws.coef, ws.coef2, (unsigned)C, (double)W * p.a.n, eps,
                      fix_gamma);
   p.a.coef = ws.coef; p.a.coef2 = ws.coef2;
   p.a.relu = relu != 0;
-  pbn_map<T, kPbnBwd>(p, vec, st, "sd::pbn_bwd_coef_kernel + ");
+  pbn_map<T, kPbnBwd>(p, vec, st, "sd::bn_bwd_coef_kernel + ");
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

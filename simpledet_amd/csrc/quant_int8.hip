@@ -27,9 +27,8 @@
 //   from minmax on the device.
 //   Stores go in 16-byte items from the first 16-byte boundary of the OUTPUT span; an input whose phase
 //   differs is loaded by 4-byte accesses, so pointers need 4-byte alignment only and the bits do not depend on it.
-#include "common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
-#include <math.h>
 
 namespace sd {
 namespace {
@@ -129,16 +128,10 @@ __device__ __forceinline__ Seg find_seg(const QArgs& a, int* s_pref) {
   return s;
 }
 
-// floats in front of the first 16-byte boundary of p (p is 4-byte aligned), at most len
-__device__ __forceinline__ long head_len(const void* p, long len) {
-  const long h = (long)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
-  return h < len ? h : len;
-}
-
 // max of the bit patterns of |p[0 .. len)| over the workgroup; valid in thread 0.  Every thread calls it.
 __device__ __forceinline__ unsigned block_absmax(const float* p, long len, unsigned* s_red) {
   const int tid = threadIdx.x;
-  const long head = head_len(p, len);
+  const long head = head_to_16(p, len);
   unsigned m = 0;
   if (tid < head) m = absbits(p[tid]);
   const float4* v = reinterpret_cast<const float4*>(p + head);
@@ -231,7 +224,7 @@ __device__ __forceinline__ float4 ld4(const float* p, bool vec) {
 template <bool kY, bool kOld, class F>
 __device__ __forceinline__ void map_span(const float* x, const float* y, float* q, long len, F f) {
   const int tid = threadIdx.x;
-  const long head = head_len(q, len);
+  const long head = head_to_16(q, len);
   if (tid < head) q[tid] = f(x[tid], kY ? y[tid] : 0.0f, kOld ? q[tid] : 0.0f);
   const long nv = (len - head) >> 2;
   const float* xb = x + head;

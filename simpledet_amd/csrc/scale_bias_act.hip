@@ -28,9 +28,8 @@
 //   Items there start at the segment's first element whatever the pointers' phase, so the order, and with it every
 //   bit, is independent of alignment.  No floating-point atomics: two calls give equal bits.
 #include "common.h"
-#include "wg_common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
-#include <initializer_list>
 
 namespace sd {
 namespace {
@@ -74,29 +73,23 @@ struct SbaArgs {
   int vec_in0, vec_in1, vec_out1;   // this tensor's items lie on 16-byte boundaries
 };
 
+// an item: one 16-byte access where `vec`, else by element
 template <typename T>
-struct alignas(16) SbaItem {
-  T v[16 / sizeof(T)];
-};
-
-template <typename T>
-__device__ __forceinline__ SbaItem<T> sba_ld(const T* p, bool vec) {
-  constexpr int V = 16 / sizeof(T);
-  if (vec) return *reinterpret_cast<const SbaItem<T>*>(p);
-  SbaItem<T> r;
+__device__ __forceinline__ Vec16<T> sba_ld(const T* p, bool vec) {
+  if (vec) return vec16_ld(p);
+  Vec16<T> r;
 #pragma unroll
-  for (int k = 0; k < V; ++k) r.v[k] = p[k];
+  for (int k = 0; k < Vec16<T>::N; ++k) r.e[k] = p[k];
   return r;
 }
 template <typename T>
-__device__ __forceinline__ void sba_st(T* p, bool vec, const SbaItem<T>& r) {
-  constexpr int V = 16 / sizeof(T);
+__device__ __forceinline__ void sba_st(T* p, bool vec, const Vec16<T>& r) {
   if (vec) {
-    *reinterpret_cast<SbaItem<T>*>(p) = r;
+    vec16_st(p, r);
     return;
   }
 #pragma unroll
-  for (int k = 0; k < V; ++k) p[k] = r.v[k];
+  for (int k = 0; k < Vec16<T>::N; ++k) p[k] = r.e[k];
 }
 
 __device__ __forceinline__ unsigned sba_channel(unsigned e, const SbaArgs& a, unsigned* rem = nullptr) {
@@ -139,7 +132,7 @@ __device__ __forceinline__ void sba_one(const SbaArgs& a, unsigned e) {
 template <typename T, bool BWD>
 __global__ __launch_bounds__(kSbaT) void sba_map_kernel(SbaArgs a) {
   constexpr int V = 16 / sizeof(T);
-  using Item = SbaItem<T>;
+  using Item = Vec16<T>;
   const T* in0 = static_cast<const T*>(a.in0);
   const T* in1 = static_cast<const T*>(a.in1);
   const T* gam = static_cast<const T*>(a.gamma);
@@ -195,11 +188,11 @@ __global__ __launch_bounds__(kSbaT) void sba_map_kernel(SbaArgs a) {
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         if (BWD) {
-          const T g1 = sba_g1<T>(A[k].v[j], use1 ? B[k].v[j] : (T)0, a.act != 0);
-          r1.v[j] = g1;
-          r0.v[j] = g1 * g[j];
+          const T g1 = sba_g1<T>(A[k].e[j], use1 ? B[k].e[j] : (T)0, a.act != 0);
+          r1.e[j] = g1;
+          r0.e[j] = g1 * g[j];
         } else {
-          r0.v[j] = sba_fwd_one<T>(A[k].v[j], g[j], b[j], use1 ? B[k].v[j] : (T)0, bet != nullptr, use1, a.act != 0);
+          r0.e[j] = sba_fwd_one<T>(A[k].e[j], g[j], b[j], use1 ? B[k].e[j] : (T)0, bet != nullptr, use1, a.act != 0);
         }
       }
       if (BWD && out1) sba_st<T>(out1 + e, a.vec_out1, r1);
@@ -224,12 +217,12 @@ __global__ __launch_bounds__(kSbaT) void sba_dbeta_partial_kernel(const T* dy, c
     const unsigned nv = len / V;
     float acc = 0.f;
     for (unsigned i = threadIdx.x; i < nv; i += kSbaT) {
-      const SbaItem<T> g = sba_ld<T>(gp + i * V, gvec);
-      SbaItem<T> w;
+      const Vec16<T> g = sba_ld<T>(gp + i * V, gvec);
+      Vec16<T> w;
       if (act) w = sba_ld<T>(yp + i * V, yvec);
       float f[V];
 #pragma unroll
-      for (int j = 0; j < V; ++j) f[j] = (float)sba_g1<T>(g.v[j], act ? w.v[j] : (T)0, act != 0);
+      for (int j = 0; j < V; ++j) f[j] = (float)sba_g1<T>(g.e[j], act ? w.e[j] : (T)0, act != 0);
 #pragma unroll
       for (int w2 = 1; w2 < V; w2 *= 2)
 #pragma unroll
@@ -286,12 +279,6 @@ static int sba_plan(int N, int C, long HxW, int act, SbaPlan* p, bool* empty) {
 }
 static size_t sba_need(const SbaPlan& p) { return 256 + round256(p.part_bytes); }
 
-static bool sba_elem_aligned(size_t esz, std::initializer_list<const void*> ps) {
-  for (const void* q : ps)
-    if ((uintptr_t)q % esz) return false;
-  return true;
-}
-
 // the flat cut of the element kernels about out0's first 16-byte boundary
 template <typename T>
 static void sba_cut(SbaArgs& a, const SbaPlan& p, int C, long HxW) {
@@ -299,8 +286,7 @@ static void sba_cut(SbaArgs& a, const SbaPlan& p, int C, long HxW) {
   a.hw = sba_div((unsigned)HxW);
   a.c = sba_div((unsigned)C);
   a.total = (unsigned)p.total;
-  const unsigned h = (unsigned)(((16u - (unsigned)((uintptr_t)a.out0 & 15u)) & 15u) / sizeof(T));
-  a.head = h < a.total ? h : a.total;
+  a.head = head_to_16(static_cast<const T*>(a.out0), a.total);
   a.nv = (a.total - a.head) / V;
   a.tail = a.total - a.head - a.nv * V;
   a.tiles = (a.nv + kSbaT * kSbaU - 1) / (kSbaT * kSbaU);
@@ -320,14 +306,14 @@ static int sba_fwd(const void* x, const void* gamma, const void* beta, const voi
   if (int e = sba_plan(N, C, HxW, act, &p, &empty)) return e;
   if (empty) return SD_OK;
   SD_REQUIRE(x && gamma && y, "null pointer");
-  SD_REQUIRE(sba_elem_aligned(sizeof(T), {x, gamma, beta, residual, y}), "a pointer is not aligned to its %zu-byte elements",
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {x, gamma, beta, residual, y}), "a pointer is not aligned to its %zu-byte elements",
              sizeof(T));
   SbaArgs a{};
   a.in0 = x; a.in1 = residual; a.gamma = gamma; a.beta = beta; a.out0 = y; a.act = act;
   sba_cut<T>(a, p, C, HxW);
   const int grid = sba_grid(a);
   hipLaunchKernelGGL((sba_map_kernel<T, false>), dim3(grid), dim3(kSbaT), 0, (hipStream_t)stream, a);
-  note_dispatch("sd::sba_fwd_kernel<%s> grid=%d tiles=%u (x:%s residual:%s)", sizeof(T) == 4 ? "f32" : "f16", grid,
+  note_dispatch("sd::sba_fwd_kernel<%s> grid=%d tiles=%u (x:%s residual:%s)", elem_type_name<T>(), grid,
                 a.tiles, sba_ph(x, a.vec_in0), sba_ph(residual, a.vec_in1));
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -342,14 +328,14 @@ static int sba_bwd(const void* dy, const void* y, const void* gamma, void* dx, v
   if (empty) return SD_OK;   // (dbeta is a sum over nothing; like every empty call, nothing is written)
   SD_REQUIRE(dy && gamma && dx, "null pointer");
   SD_REQUIRE(!act || y, "null pointer: act = 1 reads y");
-  SD_REQUIRE(sba_elem_aligned(sizeof(T), {dy, y, gamma, dx, dres}), "a pointer is not aligned to its %zu-byte elements",
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {dy, y, gamma, dx, dres}), "a pointer is not aligned to its %zu-byte elements",
              sizeof(T));
-  SD_REQUIRE(sba_elem_aligned(sizeof(float), {dbeta}), "dbeta is not aligned to 4 bytes");
+  SD_REQUIRE(ptrs_aligned(sizeof(float), {dbeta}), "dbeta is not aligned to 4 bytes");
   if (dbeta && !(workspace && workspace_bytes >= sba_need(p)))
     return fail(SD_ERR_WORKSPACE, "scale_bias_act_bwd workspace too small for dbeta: %zu < %zu bytes",
                 workspace ? workspace_bytes : (size_t)0, sba_need(p));
   hipStream_t st = (hipStream_t)stream;
-  const char* tn = sizeof(T) == 4 ? "f32" : "f16";
+  const char* tn = elem_type_name<T>();
   if (dbeta) {
     float* part = reinterpret_cast<float*>(round256((size_t)(uintptr_t)workspace));
     const long units = (long)N * C * p.S;

@@ -35,10 +35,8 @@
 // cleared by a kernel at the head of a call (a fresh workspace holds arbitrary bytes), everything else that is read was
 // written by the same call.
 #include "common.h"
-#include "wg_common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
-#include <math.h>
-#include <initializer_list>
 
 namespace sd {
 namespace {
@@ -70,22 +68,13 @@ struct SeArgs {
   float hw;                // (float)HW
 };
 
-template <typename T> struct alignas(16) SeVec { T e[16 / sizeof(T)]; };
-
-// elements of a run in front of its first 16-byte boundary
-template <typename T>
-__device__ __forceinline__ unsigned se_head(const T* p, unsigned len) {
-  const unsigned h = ((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / (unsigned)sizeof(T);
-  return h < len ? h : len;
-}
-
 // This thread's share of the sum of x (MUL: of dy * x) over a run of `len` elements worked on by G threads: the
 // element in front of the boundary, its vectors in order (a vector's terms pairwise), the element behind.  STASH keeps
 // the run (MUL: dy's) in `stash`.
 template <typename T, int G, bool MUL, bool STASH>
 __device__ __forceinline__ float se_run_sum(const T* x, const T* dy, unsigned len, unsigned t, T* stash) {
   constexpr unsigned V = 16 / sizeof(T);
-  const unsigned head = se_head(x, len);
+  const unsigned head = head_to_16(x, len);
   const bool dyvec = MUL && (((uintptr_t)(dy + head)) & 15u) == 0;
   float acc = 0.f;
   auto one = [&](unsigned i) {
@@ -101,13 +90,13 @@ __device__ __forceinline__ float se_run_sum(const T* x, const T* dy, unsigned le
   };
   if (t < head) one(t);
   const unsigned nv = (len - head) / V;
-  const SeVec<T>* xp = reinterpret_cast<const SeVec<T>*>(x + head);
+  const Vec16<T>* xp = reinterpret_cast<const Vec16<T>*>(x + head);
   for (unsigned j = t; j < nv; j += G) {
-    const SeVec<T> a = xp[j];
-    SeVec<T> b;
+    const Vec16<T> a = xp[j];
+    Vec16<T> b;
     if (MUL) {
       if (dyvec) {
-        b = reinterpret_cast<const SeVec<T>*>(dy + head)[j];
+        b = reinterpret_cast<const Vec16<T>*>(dy + head)[j];
       } else {
 #pragma unroll
         for (unsigned k = 0; k < V; ++k) b.e[k] = dy[head + j * V + k];
@@ -136,7 +125,7 @@ __device__ __forceinline__ float se_run_sum(const T* x, const T* dy, unsigned le
 template <typename T, int G, bool ADD, bool LDS_IN>
 __device__ __forceinline__ void se_run_apply(const T* in, T* out, unsigned len, unsigned t, float a, float g) {
   constexpr unsigned V = 16 / sizeof(T);
-  const unsigned head = se_head(out, len);
+  const unsigned head = head_to_16(out, len);
   const bool invec = !LDS_IN && (((uintptr_t)(in + head)) & 15u) == 0;
   auto f = [&](T v) -> T {
     float r = (float)v * a;
@@ -145,11 +134,11 @@ __device__ __forceinline__ void se_run_apply(const T* in, T* out, unsigned len, 
   };
   if (t < head) out[t] = f(in[t]);
   const unsigned nv = (len - head) / V;
-  SeVec<T>* op = reinterpret_cast<SeVec<T>*>(out + head);
+  Vec16<T>* op = reinterpret_cast<Vec16<T>*>(out + head);
   for (unsigned j = t; j < nv; j += G) {
-    SeVec<T> v;
+    Vec16<T> v;
     if (invec) {
-      v = reinterpret_cast<const SeVec<T>*>(in + head)[j];
+      v = reinterpret_cast<const Vec16<T>*>(in + head)[j];
     } else {
 #pragma unroll
       for (unsigned k = 0; k < V; ++k) v.e[k] = in[head + j * V + k];
@@ -477,14 +466,6 @@ static size_t se_carve(const SePlan& p, void* workspace, SeArgs* a) {
 }
 static size_t se_need(const SePlan& p) { return 256 + se_carve(p, nullptr, nullptr); }
 
-static bool se_aligned(size_t to, std::initializer_list<const void*> ps) {
-  for (const void* q : ps)
-    if ((uintptr_t)q % to) return false;
-  return true;
-}
-
-template <typename T> static const char* se_tn() { return sizeof(T) == 4 ? "f32" : "f16"; }
-
 // checks shared by both directions; *resident says which path runs
 template <typename T>
 static int se_begin(int N, int C, int Cr, long HxW, int path, int split, const void* workspace, size_t workspace_bytes,
@@ -493,12 +474,9 @@ static int se_begin(int N, int C, int Cr, long HxW, int path, int split, const v
   const size_t lds = sizeof(T) == 4 ? p->lds32 : p->lds16;
   if (path == 2 && lds > kSeLds)
     return fail(SD_ERR_UNSUPPORTED, "se_block: path 2 (resident) needs %zu B of LDS for an image of %d x %ld %s (limit %zu)",
-                lds, C, HxW, se_tn<T>(), kSeLds);
+                lds, C, HxW, elem_type_name<T>(), kSeLds);
   *resident = path == 2 || (path == 0 && lds <= kSeLds);
-  if (!(workspace && workspace_bytes >= se_need(*p)))
-    return fail(SD_ERR_WORKSPACE, "se_block workspace too small: %zu < %zu bytes", workspace ? workspace_bytes : (size_t)0,
-                se_need(*p));
-  return SD_OK;
+  return workspace_check(workspace, workspace_bytes, se_need(*p), "se_block");
 }
 
 static void se_fill(SeArgs& a, const SePlan& p, int N, int C, int Cr, long HxW) {
@@ -519,7 +497,7 @@ static int se_launch(SeArgs& a, const SePlan& p, bool resident, hipStream_t st) 
       raised = true;
     }
     hipLaunchKernelGGL((se_resident_kernel<T, BWD>), dim3(a.N), dim3(kSeResT), lds, st, a);
-    note_dispatch("sd::se_resident_kernel<%s,%s> x %u images, %zu B LDS%s", se_tn<T>(), dir, a.N, lds,
+    note_dispatch("sd::se_resident_kernel<%s,%s> x %u images, %zu B LDS%s", elem_type_name<T>(), dir, a.N, lds,
                   BWD ? " + sd::se_wgrad_kernel" : "");
     return SD_OK;
   }
@@ -528,12 +506,12 @@ static int se_launch(SeArgs& a, const SePlan& p, bool resident, hipStream_t st) 
   if (p.wave) {
     hipLaunchKernelGGL((se_apply_kernel<T, kWave, BWD>), dim3(cdiv((long)a.N * a.C, kSeT / kWave)), dim3(kSeT), 0, st,
                        a);
-    note_dispatch("sd::se_reduce_kernel<%s,%s,wave> + sd::se_apply_kernel<%s,%s,wave>%s", se_tn<T>(), dir, se_tn<T>(),
+    note_dispatch("sd::se_reduce_kernel<%s,%s,wave> + sd::se_apply_kernel<%s,%s,wave>%s", elem_type_name<T>(), dir, elem_type_name<T>(),
                   dir, BWD ? " + sd::se_wgrad_kernel" : "");
   } else {
     hipLaunchKernelGGL((se_apply_kernel<T, kSeT, BWD>), dim3(a.N * a.C * p.acp), dim3(kSeT), 0, st, a);
     note_dispatch("sd::se_reduce_kernel<%s,%s,block> x %u chunks of %u + sd::se_apply_kernel<%s,%s,block>%s",
-                  se_tn<T>(), dir, p.S, p.chunk, se_tn<T>(), dir, BWD ? " + sd::se_wgrad_kernel" : "");
+                  elem_type_name<T>(), dir, p.S, p.chunk, elem_type_name<T>(), dir, BWD ? " + sd::se_wgrad_kernel" : "");
   }
   return SD_OK;
 }
@@ -545,7 +523,7 @@ static int se_fwd(const void* x, const void* w1, const void* b1, const void* w2,
   SePlan p{};
   bool resident = false;
   SD_REQUIRE(x && w1 && w2 && y && gap && z1 && av, "se_block_fwd: null pointer");
-  SD_REQUIRE(se_aligned(sizeof(T), {x, w1, b1, w2, b2, y}) && se_aligned(4, {gap, z1, av}),
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {x, w1, b1, w2, b2, y}) && ptrs_aligned(4, {gap, z1, av}),
              "se_block_fwd: a pointer is not aligned to its elements");
   if (int e = se_begin<T>(N, C, Cr, HxW, path, split, workspace, workspace_bytes, &p, &resident)) return e;
   SeArgs a{};
@@ -564,7 +542,7 @@ static int se_bwd(const void* dy, const void* x, const float* gap, const float* 
   SePlan p{};
   bool resident = false;
   SD_REQUIRE(dy && x && gap && z1 && av && w1 && w2 && dx && g && dw1 && dw2, "se_block_bwd: null pointer");
-  SD_REQUIRE(se_aligned(sizeof(T), {dy, x, w1, w2, dx}) && se_aligned(4, {gap, z1, av, g, dw1, db1, dw2, db2}),
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {dy, x, w1, w2, dx}) && ptrs_aligned(4, {gap, z1, av, g, dw1, db1, dw2, db2}),
              "se_block_bwd: a pointer is not aligned to its elements");
   if (int e = se_begin<T>(N, C, Cr, HxW, path, split, workspace, workspace_bytes, &p, &resident)) return e;
   SeArgs a{};

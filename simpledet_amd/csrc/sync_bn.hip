@@ -46,17 +46,16 @@
 //   ... (split)                 above that a workgroup per chunk of 256 * PER items: (mean, M2 about the chunk's
 //                               mean) -> the workspace; sbn_stats_merge_kernel, a wave per channel, merges them by
 //                               Chan's rule in double in a fixed order
-//   sbn_bwd_stats_kernel        the same three regimes; sbn_bwd_merge_kernel adds the partial sums in double
-//   sbn_fwd_coef_kernel / sbn_bwd_coef_kernel   a thread per channel: the combine over the ranks and the channel's
+//   sbn_bwd_stats_kernel        the same three regimes; bn_bwd_merge_kernel adds the partial sums in double
+//   bn_fwd_coef_kernel / bn_bwd_coef_kernel   a thread per channel: the combine over the ranks and the channel's
 //                               coefficients -> the workspace; mean / var, dgamma / dbeta, moving_*
+//   (the three bn_* kernels, the merge and the sums are norm_common.h's: pyramid_bn.hip launches the same ones)
 //   sbn_map_kernel              the element rules over the flat tensor, an item's channel by two divisions
 // No floating-point atomics, no memset, no host read: every workspace word that is read was written by a kernel of
 // the same call, and every grid depends on the shapes alone.
 #include "common.h"
-#include "wg_common.h"
+#include "norm_common.h"
 #include "../../include/simpledet_ops.h"
-#include <math.h>
-#include <initializer_list>
 #include <type_traits>
 
 namespace sd {
@@ -92,7 +91,6 @@ struct SbnArgs {
 };
 
 template <int L> struct SbnItem { float v[L]; };
-struct alignas(16) SbnH8 { _Float16 h[8]; };
 
 // how an item of L elements of type T is moved; VEC: by 16-byte accesses
 template <typename T, int L, bool VEC>
@@ -101,16 +99,8 @@ struct SbnIO {
   using Item = SbnItem<L>;
   static __device__ __forceinline__ Item ld(const T* p) {
     Item r;
-    if constexpr (VEC && sizeof(T) == 4) {
-#pragma unroll
-      for (int q = 0; q < L / 4; ++q) {
-        const float4 f = reinterpret_cast<const float4*>(p)[q];
-        r.v[4 * q] = f.x; r.v[4 * q + 1] = f.y; r.v[4 * q + 2] = f.z; r.v[4 * q + 3] = f.w;
-      }
-    } else if constexpr (VEC) {
-      const SbnH8 h = *reinterpret_cast<const SbnH8*>(p);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) r.v[k] = (float)h.h[k];
+    if constexpr (VEC) {
+      vec16_ld_f32(p, r.v);
     } else {
 #pragma unroll
       for (int k = 0; k < L; ++k) r.v[k] = (float)p[k];
@@ -118,15 +108,8 @@ struct SbnIO {
     return r;
   }
   static __device__ __forceinline__ void st(T* p, const Item& r) {
-    if constexpr (VEC && sizeof(T) == 4) {
-#pragma unroll
-      for (int q = 0; q < L / 4; ++q)
-        reinterpret_cast<float4*>(p)[q] = make_float4(r.v[4 * q], r.v[4 * q + 1], r.v[4 * q + 2], r.v[4 * q + 3]);
-    } else if constexpr (VEC) {
-      SbnH8 h;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) h.h[k] = (_Float16)r.v[k];
-      *reinterpret_cast<SbnH8*>(p) = h;
+    if constexpr (VEC) {
+      vec16_st_f32(p, r.v);
     } else {
 #pragma unroll
       for (int k = 0; k < L; ++k) p[k] = (T)r.v[k];
@@ -134,21 +117,13 @@ struct SbnIO {
   }
 };
 
-// the sum of an item's L terms, pairwise
-template <int L>
-__device__ __forceinline__ float sbn_tree(float (&f)[L]) {
-#pragma unroll
-  for (int w = 1; w < L; w *= 2)
-#pragma unroll
-    for (int j = 0; j < L; j += 2 * w) f[j] = f[j] + f[j + w];
-  return f[0];
-}
+// sums over an item, pairwise
 template <int L>
 __device__ __forceinline__ float sbn_hsum(const SbnItem<L>& a) {
   float f[L];
 #pragma unroll
   for (int k = 0; k < L; ++k) f[k] = a.v[k];
-  return sbn_tree<L>(f);
+  return tree_sum(f);
 }
 template <int L>
 __device__ __forceinline__ float sbn_sq(const SbnItem<L>& a, float m) {
@@ -158,21 +133,14 @@ __device__ __forceinline__ float sbn_sq(const SbnItem<L>& a, float m) {
     const float d = a.v[k] - m;
     f[k] = d * d;
   }
-  return sbn_tree<L>(f);
+  return tree_sum(f);
 }
 template <int L>
 __device__ __forceinline__ float sbn_dot(const SbnItem<L>& g, const SbnItem<L>& x, float m) {
   float f[L];
 #pragma unroll
   for (int k = 0; k < L; ++k) f[k] = g.v[k] * (x.v[k] - m);
-  return sbn_tree<L>(f);
-}
-
-// sum over the TG threads that share a channel (chunk); `slot`: four floats of LDS of its own
-template <int TG>
-__device__ __forceinline__ float sbn_group_sum(float v, float* slot) {
-  if constexpr (TG == kWave) return wave_sum_f32(v);
-  else return block_sum_f32<TG, false>(v, slot);
+  return tree_sum(f);
 }
 
 // element index of item i of chunk-local order: item j of channel c lies in row n = j / ipr
@@ -207,12 +175,12 @@ __global__ __launch_bounds__(kSbnT) void sbn_stats_kernel(SbnArgs a) {
   float sm = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k) sm += sbn_hsum<L>(v[k]);
-  const float mean = sbn_group_sum<TG>(sm, red) / (float)(cnt * L);
+  const float mean = group_sum_f32<TG>(sm, red) / (float)(cnt * L);
   float q2 = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k)
     if (t + k * TG < cnt) q2 += sbn_sq<L>(v[k], mean);
-  const float m2 = sbn_group_sum<TG>(q2, red + 4);
+  const float m2 = group_sum_f32<TG>(q2, red + 4);
   if (t == 0) {
     if (a.S == 1) {
       a.out[c] = mean;
@@ -221,16 +189,6 @@ __global__ __launch_bounds__(kSbnT) void sbn_stats_kernel(SbnArgs a) {
       a.partial[u] = make_float2(mean, m2);
     }
   }
-}
-
-// Chan, Golub, LeVeque: (na, ma, Ma) + (nb, mb, Mb)
-__device__ __forceinline__ void sbn_merge(double& na, double& ma, double& Ma, double nb, double mb, double Mb) {
-  if (nb == 0.0) return;
-  if (na == 0.0) { na = nb; ma = mb; Ma = Mb; return; }
-  const double n = na + nb, d = mb - ma;
-  ma = ma + d * (nb / n);
-  Ma = Ma + Mb + d * d * (na * nb / n);
-  na = n;
 }
 
 // a wave per channel: lanes stride its S partials, then a fixed tree over the lanes
@@ -244,12 +202,9 @@ __global__ __launch_bounds__(kSbnT) void sbn_stats_merge_kernel(SbnArgs a, unsig
     const unsigned first = s * a.chunk;
     const unsigned cnt = a.ipc - first < a.chunk ? a.ipc - first : a.chunk;
     const float2 v = p[s];
-    sbn_merge(n, m, M, (double)cnt * (double)L, (double)v.x, (double)v.y);
+    chan_merge(n, m, M, (double)cnt * (double)L, (double)v.x, (double)v.y);
   }
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const double nb = __shfl_down(n, off), mb = __shfl_down(m, off), Mb = __shfl_down(M, off);
-    if (lane + off < (unsigned)kWave) sbn_merge(n, m, M, nb, mb, Mb);
-  }
+  wave_tree_chan(lane, n, m, M);
   if (lane == 0) {
     a.out[c] = (float)m;
     a.out[a.C + c] = (float)(M / n);
@@ -287,8 +242,8 @@ __global__ __launch_bounds__(kSbnT) void sbn_bwd_stats_kernel(SbnArgs a) {
       sg += sbn_hsum<L>(gv[k]);
       sp += sbn_dot<L>(gv[k], xv[k], mean);
     }
-  sg = sbn_group_sum<TG>(sg, red);
-  sp = sbn_group_sum<TG>(sp, red + 4);
+  sg = group_sum_f32<TG>(sg, red);
+  sp = group_sum_f32<TG>(sp, red + 4);
   if (t == 0) {
     if (a.S == 1) {
       a.out[c] = sg;
@@ -296,83 +251,6 @@ __global__ __launch_bounds__(kSbnT) void sbn_bwd_stats_kernel(SbnArgs a) {
     } else {
       a.partial[u] = make_float2(sg, sp);
     }
-  }
-}
-
-// a wave per channel: lanes stride its S partial sums, in double, then a fixed tree over the lanes
-__global__ __launch_bounds__(kSbnT) void sbn_bwd_merge_kernel(SbnArgs a) {
-  const unsigned lane = threadIdx.x & (kWave - 1);
-  const unsigned c = blockIdx.x * (kSbnT / kWave) + threadIdx.x / kWave;
-  if (c >= a.C) return;
-  const float2* p = a.partial + (size_t)c * a.S;
-  double sg = 0.0, sp = 0.0;
-  for (unsigned s = lane; s < a.S; s += kWave) {
-    const float2 v = p[s];
-    sg += (double)v.x;
-    sp += (double)v.y;
-  }
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const double gb = __shfl_down(sg, off), pb = __shfl_down(sp, off);
-    if (lane + off < (unsigned)kWave) { sg += gb; sp += pb; }
-  }
-  if (lane == 0) {
-    a.out[c] = (float)sg;
-    a.out[a.C + c] = (float)sp;
-  }
-}
-
-// a thread per channel: the combine over the ranks (double, rank order), mean / var, the coefficients of the
-// element rule (mean, inv, g, beta)
-__global__ __launch_bounds__(kSbnT) void sbn_fwd_coef_kernel(const float* parts, int W, const float* gamma,
-                                                             const float* beta, float* mean, float* var, float4* coef,
-                                                             unsigned C, float eps, int fix_gamma) {
-  const unsigned c = blockIdx.x * kSbnT + threadIdx.x;
-  if (c >= C) return;
-  double sm = 0.0;
-  for (int r = 0; r < W; ++r) sm += (double)parts[((size_t)r * 2) * C + c];
-  const double m = sm / (double)W;
-  double sv = 0.0;
-  for (int r = 0; r < W; ++r) {
-    const double d = (double)parts[((size_t)r * 2) * C + c] - m;
-    sv += (double)parts[((size_t)r * 2 + 1) * C + c] + d * d;
-  }
-  const double v = sv / (double)W;
-  const float m32 = (float)m, v32 = (float)v;
-  mean[c] = m32;
-  var[c] = v32;
-  const float inv = 1.0f / sqrtf(v32 + eps);
-  coef[c] = make_float4(m32, inv, fix_gamma ? 1.0f : gamma[c], beta[c]);
-}
-
-// a thread per channel: the sums over the ranks, (a, b, c, mean) of the element rule, the parameter gradients of
-// this rank and the moving statistics
-__global__ __launch_bounds__(kSbnT) void sbn_bwd_coef_kernel(const float* bparts, int W, int rank, const float* mean,
-                                                             const float* var, const float* gamma, float* dgamma,
-                                                             float* dbeta, float* mmean, float* mvar, float momentum,
-                                                             float4* coef, unsigned C, double wn, float eps,
-                                                             int fix_gamma) {
-  const unsigned c = blockIdx.x * kSbnT + threadIdx.x;
-  if (c >= C) return;
-  double SG = 0.0, SP = 0.0;
-  for (int r = 0; r < W; ++r) {
-    SG += (double)bparts[((size_t)r * 2) * C + c];
-    SP += (double)bparts[((size_t)r * 2 + 1) * C + c];
-  }
-  const float sg = (float)(SG / wn), sp = (float)(SP / wn);
-  const float mu = mean[c], vr = var[c];
-  const float g = fix_gamma ? 1.0f : gamma[c];
-  const float inv = 1.0f / sqrtf(vr + eps);
-  const float ka = g * inv;
-  const float kb = -(g * sp) * ((inv * inv) * inv);
-  const float kc = -(g * sg) * inv;
-  coef[c] = make_float4(ka, kb, kc, mu);
-  if (dgamma) {
-    dbeta[c] = bparts[((size_t)rank * 2) * C + c];
-    dgamma[c] = fix_gamma ? 0.0f : bparts[((size_t)rank * 2 + 1) * C + c] * inv;
-  }
-  if (mmean) {
-    mmean[c] = mmean[c] * momentum + mu * (1.0f - momentum);
-    mvar[c] = mvar[c] * momentum + vr * (1.0f - momentum);
   }
 }
 
@@ -464,19 +342,11 @@ static SbnWs sbn_carve(const SbnPlan& p, void* workspace) {
 }
 static size_t sbn_need(const SbnPlan& p) { return 256 + sbn_carve(p, nullptr).need; }
 
-static bool sbn_aligned(size_t to, std::initializer_list<const void*> ps) {
-  for (const void* q : ps)
-    if ((uintptr_t)q % to) return false;
-  return true;
-}
-
 static void sbn_fill(SbnArgs& a, const SbnPlan& p, int N, int C, long HxW) {
   a.N = (unsigned)N; a.C = (unsigned)C; a.HxW = (unsigned)HxW;
   a.ipr = p.ipr; a.ipc = p.ipc; a.items = p.items;
   a.n = (float)p.n;
 }
-
-template <typename T> static const char* sbn_tn() { return sizeof(T) == 4 ? "f32" : "f16"; }
 
 // calls f with SbnIO's <L, VEC> as integral constants
 template <typename T, typename F>
@@ -510,7 +380,7 @@ static void sbn_reduce(SbnArgs& a, const SbnPlan& p, bool vec, hipStream_t st) {
       const dim3 grid(cdiv(a.C, kSbnT / kWave));
       if (BWD) hipLaunchKernelGGL((sbn_bwd_stats_kernel<T, L, VEC, kWave>), grid, dim3(kSbnT), 0, st, a);
       else hipLaunchKernelGGL((sbn_stats_kernel<T, L, VEC, kWave>), grid, dim3(kSbnT), 0, st, a);
-      note_dispatch("sd::%s<%s,L%d,%s,wave>", name, sbn_tn<T>(), L, mv);
+      note_dispatch("sd::%s<%s,L%d,%s,wave>", name, elem_type_name<T>(), L, mv);
       return;
     }
     a.chunk = kSbnT * PER;
@@ -519,14 +389,14 @@ static void sbn_reduce(SbnArgs& a, const SbnPlan& p, bool vec, hipStream_t st) {
     if (BWD) hipLaunchKernelGGL((sbn_bwd_stats_kernel<T, L, VEC, kSbnT>), grid, dim3(kSbnT), 0, st, a);
     else hipLaunchKernelGGL((sbn_stats_kernel<T, L, VEC, kSbnT>), grid, dim3(kSbnT), 0, st, a);
     if (a.S == 1) {
-      note_dispatch("sd::%s<%s,L%d,%s,block>", name, sbn_tn<T>(), L, mv);
+      note_dispatch("sd::%s<%s,L%d,%s,block>", name, elem_type_name<T>(), L, mv);
       return;
     }
     const dim3 mgrid(cdiv(a.C, kSbnT / kWave));
-    if (BWD) hipLaunchKernelGGL(sbn_bwd_merge_kernel, mgrid, dim3(kSbnT), 0, st, a);
+    if (BWD) hipLaunchKernelGGL(bn_bwd_merge_kernel<kSbnT>, mgrid, dim3(kSbnT), 0, st, a.partial, a.out, a.C, a.S);
     else hipLaunchKernelGGL(sbn_stats_merge_kernel, mgrid, dim3(kSbnT), 0, st, a, (unsigned)L);
-    note_dispatch("sd::%s<%s,L%d,%s,block> x %u chunks + sd::%s (split)", name, sbn_tn<T>(), L, mv, a.S,
-                  BWD ? "sbn_bwd_merge_kernel" : "sbn_stats_merge_kernel");
+    note_dispatch("sd::%s<%s,L%d,%s,block> x %u chunks + sd::%s (split)", name, elem_type_name<T>(), L, mv, a.S,
+                  BWD ? "bn_bwd_merge_kernel" : "sbn_stats_merge_kernel");
   });
 }
 
@@ -537,15 +407,10 @@ static void sbn_map(SbnArgs& a, const SbnPlan& p, bool vec, hipStream_t st, cons
     constexpr bool VEC = decltype(v)::value;
     const int per = kSbnT * sbn_map_per<L>();
     hipLaunchKernelGGL((sbn_map_kernel<T, L, VEC, KIND>), dim3(cdiv(a.items, per)), dim3(kSbnT), 0, st, a);
-    note_dispatch("%ssd::sbn_map_kernel<%s,L%d,%s,%s>", lead, sbn_tn<T>(), L, VEC ? "vec" : "narrow",
+    note_dispatch("%ssd::sbn_map_kernel<%s,L%d,%s,%s>", lead, elem_type_name<T>(), L, VEC ? "vec" : "narrow",
                   KIND == kSbnFwd ? "fwd" : KIND == kSbnBwd ? "bwd" : "infer");
   });
 }
-
-#define SBN_WORKSPACE(p, name)                                                                              \
-  if (!(workspace && workspace_bytes >= sbn_need(p)))                                                       \
-    return fail(SD_ERR_WORKSPACE, name " workspace too small: %zu < %zu bytes",                           \
-                workspace ? workspace_bytes : (size_t)0, sbn_need(p))
 
 template <typename T>
 static int sbn_stats(const void* x, float* part, int N, int C, long HxW, void* workspace, size_t workspace_bytes,
@@ -555,13 +420,13 @@ static int sbn_stats(const void* x, float* part, int N, int C, long HxW, void* w
   if (int e = sbn_plan(N, C, HxW, &p, &empty)) return e;
   if (empty) return SD_OK;
   SD_REQUIRE(x && part, "null pointer");
-  SD_REQUIRE(sbn_aligned(sizeof(T), {x}) && sbn_aligned(4, {part}), "a pointer is not aligned to its elements");
-  SBN_WORKSPACE(p, "sync_bn_stats");
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {x}) && ptrs_aligned(4, {part}), "a pointer is not aligned to its elements");
+  if (int e = workspace_check(workspace, workspace_bytes, sbn_need(p), "sync_bn_stats")) return e;
   SbnArgs a{};
   sbn_fill(a, p, N, C, HxW);
   a.x = x; a.out = part;
   a.partial = sbn_carve(p, workspace).partial;
-  sbn_reduce<T, false>(a, p, sbn_aligned(16, {x}), (hipStream_t)stream);
+  sbn_reduce<T, false>(a, p, ptrs_aligned(16, {x}), (hipStream_t)stream);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -576,17 +441,17 @@ static int sbn_apply(const void* x, const float* parts, int W, const float* gamm
   SD_REQUIRE(W >= 1, "W=%d ranks: at least one", W);
   if (empty) return SD_OK;
   SD_REQUIRE(x && parts && gamma && beta && y && mean && var, "null pointer");
-  SD_REQUIRE(sbn_aligned(sizeof(T), {x, y}) && sbn_aligned(4, {parts, gamma, beta, mean, var}),
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {x, y}) && ptrs_aligned(4, {parts, gamma, beta, mean, var}),
              "a pointer is not aligned to its elements");
-  SBN_WORKSPACE(p, "sync_bn_apply");
+  if (int e = workspace_check(workspace, workspace_bytes, sbn_need(p), "sync_bn_apply")) return e;
   hipStream_t st = (hipStream_t)stream;
   const SbnWs ws = sbn_carve(p, workspace);
-  hipLaunchKernelGGL(sbn_fwd_coef_kernel, dim3(cdiv(C, kSbnT)), dim3(kSbnT), 0, st, parts, W, gamma, beta, mean, var,
+  hipLaunchKernelGGL(bn_fwd_coef_kernel<kSbnT>, dim3(cdiv(C, kSbnT)), dim3(kSbnT), 0, st, parts, W, gamma, beta, mean, var,
                      ws.coef, (unsigned)C, eps, fix_gamma);
   SbnArgs a{};
   sbn_fill(a, p, N, C, HxW);
   a.x = x; a.y = y; a.coef = ws.coef;
-  sbn_map<T, kSbnFwd>(a, p, sbn_aligned(16, {x, y}), st, "sd::sbn_fwd_coef_kernel + ");
+  sbn_map<T, kSbnFwd>(a, p, ptrs_aligned(16, {x, y}), st, "sd::bn_fwd_coef_kernel + ");
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -599,13 +464,13 @@ static int sbn_infer(const void* x, const float* gamma, const float* beta, const
   if (int e = sbn_plan(N, C, HxW, &p, &empty)) return e;
   if (empty) return SD_OK;
   SD_REQUIRE(x && gamma && beta && mmean && mvar && y, "null pointer");
-  SD_REQUIRE(sbn_aligned(sizeof(T), {x, y}) && sbn_aligned(4, {gamma, beta, mmean, mvar}),
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {x, y}) && ptrs_aligned(4, {gamma, beta, mmean, mvar}),
              "a pointer is not aligned to its elements");
   SbnArgs a{};
   sbn_fill(a, p, N, C, HxW);
   a.x = x; a.y = y; a.gamma = gamma; a.beta = beta; a.mmean = mmean; a.mvar = mvar;
   a.eps = eps; a.fix_gamma = fix_gamma;
-  sbn_map<T, kSbnInfer>(a, p, sbn_aligned(16, {x, y}), (hipStream_t)stream, "");
+  sbn_map<T, kSbnInfer>(a, p, ptrs_aligned(16, {x, y}), (hipStream_t)stream, "");
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -618,14 +483,14 @@ static int sbn_bwd_stats(const void* dy, const void* x, const float* mean, float
   if (int e = sbn_plan(N, C, HxW, &p, &empty)) return e;
   if (empty) return SD_OK;
   SD_REQUIRE(dy && x && mean && bpart, "null pointer");
-  SD_REQUIRE(sbn_aligned(sizeof(T), {dy, x}) && sbn_aligned(4, {mean, bpart}),
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {dy, x}) && ptrs_aligned(4, {mean, bpart}),
              "a pointer is not aligned to its elements");
-  SBN_WORKSPACE(p, "sync_bn_bwd_stats");
+  if (int e = workspace_check(workspace, workspace_bytes, sbn_need(p), "sync_bn_bwd_stats")) return e;
   SbnArgs a{};
   sbn_fill(a, p, N, C, HxW);
   a.x = x; a.dy = dy; a.mean_in = mean; a.out = bpart;
   a.partial = sbn_carve(p, workspace).partial;
-  sbn_reduce<T, true>(a, p, sbn_aligned(16, {dy, x}), (hipStream_t)stream);
+  sbn_reduce<T, true>(a, p, ptrs_aligned(16, {dy, x}), (hipStream_t)stream);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -645,19 +510,19 @@ static int sbn_bwd_apply(const void* dy, const void* x, const float* mean, const
              "moving_mean and moving_var must be given, or be NULL, together");
   if (empty) return SD_OK;   // (the sums are over nothing; like every empty call, nothing is written)
   SD_REQUIRE(dy && x && mean && var && gamma && bparts && dx, "null pointer");
-  SD_REQUIRE(sbn_aligned(sizeof(T), {dy, x, dx}) &&
-                 sbn_aligned(4, {mean, var, gamma, bparts, dgamma, dbeta, mmean, mvar}),
+  SD_REQUIRE(ptrs_aligned(sizeof(T), {dy, x, dx}) &&
+                 ptrs_aligned(4, {mean, var, gamma, bparts, dgamma, dbeta, mmean, mvar}),
              "a pointer is not aligned to its elements");
-  SBN_WORKSPACE(p, "sync_bn_bwd_apply");
+  if (int e = workspace_check(workspace, workspace_bytes, sbn_need(p), "sync_bn_bwd_apply")) return e;
   hipStream_t st = (hipStream_t)stream;
   const SbnWs ws = sbn_carve(p, workspace);
-  hipLaunchKernelGGL(sbn_bwd_coef_kernel, dim3(cdiv(C, kSbnT)), dim3(kSbnT), 0, st, bparts, W, rank, mean, var, gamma,
-                     dgamma, dbeta, mmean, mvar, momentum, ws.coef, (unsigned)C, (double)W * (double)p.n, eps,
-                     fix_gamma);
+  hipLaunchKernelGGL(bn_bwd_coef_kernel<kSbnT>, dim3(cdiv(C, kSbnT)), dim3(kSbnT), 0, st, bparts, W, rank, mean, var,
+                     gamma, (const float*)nullptr, dgamma, dbeta, mmean, mvar, momentum, ws.coef, (float4*)nullptr,
+                     (unsigned)C, (double)W * (double)p.n, eps, fix_gamma);
   SbnArgs a{};
   sbn_fill(a, p, N, C, HxW);
   a.x = x; a.dy = dy; a.y = dx; a.coef = ws.coef;
-  sbn_map<T, kSbnBwd>(a, p, sbn_aligned(16, {dy, x, dx}), st, "sd::sbn_bwd_coef_kernel + ");
+  sbn_map<T, kSbnBwd>(a, p, ptrs_aligned(16, {dy, x, dx}), st, "sd::bn_bwd_coef_kernel + ");
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

@@ -1,5 +1,6 @@
 // Workgroup primitives of the target and loss kernels, device only: ordered compaction of flagged lists
-// (thread order is list order, one barrier pair per scan, totals carried from trip to trip) and fixed-order sums.
+// (thread order is list order, one barrier pair per scan, totals carried from trip to trip) and fixed-order sums,
+// group_sum_f32 of the normalisation kernels (norm_common.h) among them.
 // Bit parity with the reference rests on their order of operations, so an operator file calls these and holds no copy.
 #pragma once
 #include "common.h"
@@ -100,6 +101,14 @@ __device__ __forceinline__ float block_sum_f32(float v, float* sh) {
 template <int THREADS>
 __device__ __forceinline__ int block_sum_i32(int v, int* sh) {
   return block_sum_waves<THREADS, true>(wave_sum_i32(v), sh);
+}
+// Sum over the TG threads that share a reduction unit of the normalisation kernels: the wave butterfly, or
+// (TG == 256) the four waves left to right.  `slot`: four floats of LDS that no other reduction in flight uses,
+// so no barrier follows the read.
+template <int TG>
+__device__ __forceinline__ float group_sum_f32(float v, float* slot) {
+  if constexpr (TG == kWave) return wave_sum_f32(v);
+  else return block_sum_f32<TG, false>(v, slot);
 }
 
 }  // namespace sd
